@@ -26,12 +26,16 @@ Multi-GPU (one process per GPU, launched by torch.distributed.run):
                    pair buffers for the join, (row, value) lists scattered back to
                    input order for count / coverage / nearest, per-contig pieces
                    spliced in key order for merge / subtract (sharded.py).
-In a weak run of the join with N > 1 the strong-scaling job is timed as well, after
-the official loop, and reported under "strong" (a labelled extra, not `value`).
-At N = 1 the default run also times every other operator after the official line
-and reports them under "ops" (labelled extras; --no-ops skips them).
+A plain run sets up, warms up, times the --steps steps and prints one JSON line;
+--dump-outputs DIR also writes what the last timed step computed.  Everything else
+comes with --full, after the timed steps: at N = 1 the CPU baseline with the parity
+of the timed pairs against the oracle, the two-call and end-to-end extras, and every
+other operator timed under "ops" (--no-ops skips them); in a weak run of the join
+with N > 1 the strong-scaling job, reported under "strong".  All of these are
+labelled extras, never `value`.
 
   python bench.py --gpus 1 --steps 10 --warmup 2
+  python bench.py --gpus 1 --steps 10 --warmup 2 --full
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 """
 import argparse
@@ -76,6 +80,34 @@ ALG = {
     "cluster": lambda n_in, _b=0, n_out=0: 20 * n_in + 48 * n_in,
     "complement": lambda n_in, n_v, n_out: 20 * (n_in + n_v) + 20 * n_out,
 }
+# --dump-outputs: names of the arrays a caller of each workload's step receives (the join's are named where it dumps them)
+OUT_NAMES = {
+    "count_coverage": {"out": ("count", "coverage")},
+    "nearest": {"out": ("nearest_build_idx", "distance")},
+    "merge_subtract": {"merge": ("merge_key", "merge_start", "merge_end", "merge_n"),
+                       "subtract": ("subtract_key", "subtract_start", "subtract_end", "subtract_row")},
+}
+DUMP_BYTES = 60 << 20          # data of all dumped arrays together (the .npy headers keep the files under 64 MB)
+DUMP_SEED = 0x5EED0D0
+
+
+def dump_outputs(path, arrays):
+    """Write every 1-D integer tensor of `arrays` (name -> tensor) as path/<name>.npy in float64 (exact below 2^53).  When
+    they hold more than DUMP_BYTES together, each array is cut to the same number of rows, drawn by a fixed seed and kept
+    in row order; arrays of one length share the drawn rows, so the columns of one output stay aligned."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    total = sum(int(t.numel()) for t in arrays.values())
+    per = DUMP_BYTES // 8 // max(1, len(arrays))
+    rows = {}
+    for name, t in arrays.items():
+        n = int(t.numel())
+        if total * 8 > DUMP_BYTES and n > per:
+            if n not in rows:
+                rows[n] = torch.from_numpy(np.sort(np.random.default_rng(DUMP_SEED).integers(0, n, per))).to(t.device)
+            t = t[rows[n]]
+        np.save(os.path.join(path, f"{name}.npy"), t.to(torch.float64).cpu().numpy())
 
 
 def main():
@@ -84,7 +116,13 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--workload", default="join_100Mx1M_24contigs", choices=sorted(WORKLOADS))
-    ap.add_argument("--cpu-sample", type=int, default=100_000_000, help="probe rows timed on the CPU baseline (0 = skip)")
+    ap.add_argument("--full", action="store_true", help="after the headline line's steps, also run what it does not need: the CPU "
+                    "baseline and the parity check against the oracle, the two-call and end-to-end extras, the strong-scaling "
+                    "extra of a multi-GPU weak run and the per-operator block (off: set up, warm up, time the steps, print)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last step "
+                    "computed as DIR/<name>.npy (float64, at most 64 MB in all: a fixed, seeded sample of the rows when larger; "
+                    "the join's pairs in (build, probe) order, as the path leaves their order open)")
+    ap.add_argument("--cpu-sample", type=int, default=100_000_000, help="probe rows timed on the CPU baseline of --full (0 = skip)")
     ap.add_argument("--gather", action="store_true", help="exchange the per-rank results (RCCL all-gatherv) inside the step (default with --scaling strong)")
     ap.add_argument("--no-gather", action="store_true")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL over xGMI; gloo only for rehearsals)")
@@ -98,6 +136,8 @@ def main():
     ap.add_argument("--no-build-overlap", action="store_true", help="build the index synchronously (default: ivx_ctx_set_build_overlap -- the build's tail runs beside the probe's routing pass; the build columns stay alive for the whole step, as the contract asks)")
     ap.add_argument("--check-union", action="store_true", help="strong + gather: rank 0 checks the exchanged result against a single-rank run of the whole job (rehearsals)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     import numpy as np
     import torch
@@ -357,6 +397,8 @@ def main():
         elapsed = timed_loop(step, steps, 0)
         kernel_ms = ctx.acc_ms / steps
         ctx.acc_ms = None
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, {n: t for part, names in OUT_NAMES[kind].items() for n, t in zip(names, res[part])})
         (tot_units,) = sum_over_ranks(meta["units"])
         out = None
         if rank == 0:
@@ -556,6 +598,12 @@ def main():
     (bk, bs, be), (pk, ps, pe) = r["cols"]
     ob, op = r["out"]
     pairs, n_probe, n_build = r["pairs"], r["n_probe"], r["n_build"]
+    if args.dump_outputs and rank == 0:
+        # before the --full extras, which fill the same buffers again
+        gb, gp = r["gathered"][0] if r["gathered"] is not None else (ob[:pairs], op[:pairs])
+        keys = torch.sort((gb.long() << 32) | gp.long()).values
+        dump_outputs(args.dump_outputs, {"build_idx": keys >> 32, "probe_idx": keys & 0xFFFFFFFF})
+        del gb, gp, keys
 
     out = None
     if rank == 0:
@@ -587,7 +635,7 @@ def main():
             out["roofline"]["traffic_frac"] = tr["bytes"] / (step_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS
 
     # ---- extras (not `value`): what a caller that does not know the pair count pays, and the PCIe-inclusive call
-    if rank == 0 and world == 1 and not args.no_extras:
+    if rank == 0 and world == 1 and args.full and not args.no_extras:
       try:
         tiny = (np.zeros(4, np.uint32), np.arange(4, dtype=np.int64), np.arange(4, dtype=np.int64) + 1)
         ix = ctx.build(pyivx.KIND_OVERLAP, bk, bs, be, n_keys=n_contigs)
@@ -619,7 +667,7 @@ def main():
         out["extras_error"] = f"{type(ex).__name__}: {ex}"
 
     # ---- CPU baseline beside it + parity of the timed GPU result against the oracle's pair set
-    if rank == 0 and world == 1 and args.cpu_sample > 0:
+    if rank == 0 and world == 1 and args.full and args.cpu_sample > 0:
         from oracle import oracle as orc                     # checker, used as the timed CPU baseline only
         ns = min(args.cpu_sample, n_probe)
         hb = (bk.cpu().numpy().view(np.uint32), bs.cpu().numpy(), be.cpu().numpy())
@@ -659,7 +707,7 @@ def main():
     # ---- labelled extra of a multi-GPU weak run: the ONE-job (strong-scaling) form of the same workload with the all-gatherv.
     #      Never at the price of the official line: any failure here is recorded, not raised (every rank takes the same path:
     #      the flag is agreed on with an all-reduce before the collective part starts and after it ends)
-    if world > 1 and args.scaling == "weak" and not args.no_extras:
+    if world > 1 and args.scaling == "weak" and args.full and not args.no_extras:
         del r, ob, op, bk, bs, be, pk, ps, pe
         torch.cuda.empty_cache()
         err = None
@@ -676,7 +724,7 @@ def main():
                 out["strong"] = {"error": err}
 
     # ---- every other operator, timed by this run (N = 1; after everything the official line needs, never at its cost)
-    if rank == 0 and world == 1 and not args.no_ops and not args.no_extras and not args.probe_rows and args.workload == "join_100Mx1M_24contigs":
+    if rank == 0 and world == 1 and args.full and not args.no_ops and not args.no_extras and not args.probe_rows and args.workload == "join_100Mx1M_24contigs":
         r = None
         del ob, op, bk, bs, be, pk, ps, pe
         gc.collect(); torch.cuda.empty_cache()

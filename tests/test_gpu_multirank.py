@@ -35,7 +35,7 @@ def test_two_ranks_strong_scaling_union_equals_single_rank_join():
 
 
 def test_two_ranks_weak_scaling_line_and_strong_extra():
-    out = _run(["--scaling", "weak"])
+    out = _run(["--scaling", "weak", "--full"])                   # the strong-scaling extra comes with --full
     assert out["n_gpus"] == 2 and out["scaling"] == "weak" and out["value"] > 0
     assert out["strong"]["value"] > 0 and out["strong"]["gather"] is True
 
