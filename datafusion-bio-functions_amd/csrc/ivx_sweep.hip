@@ -378,7 +378,10 @@ ivx_status sort64(ivx_ctx *ctx, int slot_a, int slot_b, const u32 *key, const i6
                        kmin, kmax);
     if (try_lin) hipLaunchKernelGGL(k_lin_layout64, dim3(1), dim3(1024), 0, st, (const long long *)kmin, (const long long *)kmax, nkeys, base, d_lin);
     IVX_HIP(ctx, hipMemcpyAsync(ctx->h_scalars + 24, d_rng, 8 * sizeof(u64), hipMemcpyDeviceToHost, st));   // Range64 (6 words), d_lin (2 words)
+    IVX_HIP(ctx, hipMemcpyAsync(ctx->h_scalars + 8, flags, sizeof(u64), hipMemcpyDeviceToHost, st));        // + the key flag k_range64 raised
     IVX_HIP(ctx, hipStreamSynchronize(st));
+    // a key id >= nkeys fails here, before the pack kernels index the per-key tables (base / kmin) with it
+    if (*(const u32 *)(ctx->h_scalars + 8)) return ctx->fail(IVX_ERR_INVALID, "key id >= n_keys");
     const Range64 r = *(const Range64 *)(ctx->h_scalars + 24);
     // coordinate-sorted input (the usual state of BED / VCF / BAM-derived tables): nothing to sort, and equal
     // rows already are in ascending row order
