@@ -426,6 +426,41 @@ extern "C" void ivx_index_free(ivx_index *ix)
 extern "C" uint64_t ivx_index_rows(const ivx_index *ix) { return ix ? ix->n : 0; }
 extern "C" uint64_t ivx_index_device_bytes(const ivx_index *ix) { return ix ? ix->bytes : 0; }
 
+// the binned overlap index's header, as the build left it (ivx_join.hip: k_join_layout, k_join_count, k_join_regdesc)
+extern "C" ivx_status ivx_index_layout(ivx_ctx *ctx, const ivx_index *ix, uint32_t *out, uint32_t n_out)
+{
+    if (!ctx) return IVX_ERR_INVALID;
+    if (!ix) return ctx->fail(IVX_ERR_INVALID, "null index");
+    if (n_out && !out) return ctx->fail(IVX_ERR_INVALID, "null out");
+    if (ix->device != ctx->device) return ctx->fail(IVX_ERR_INVALID, "index lives on another device");
+    u32 w[IVX_LAYOUT_WORDS] = {};
+    w[IVX_LAYOUT_KIND] = (u32)ix->kind;
+    if (ix->kind != IVX_KIND_NEAREST && ix->jv.hdr != nullptr) {
+        IVX_HIP(ctx, hipSetDevice(ctx->device));
+        // hdr[HDR_SLOW] and the level flags are written by the build's tail: with the build overlap on, behind `ready`
+        if (ix->ready != nullptr) IVX_HIP(ctx, hipStreamWaitEvent(ctx->stream, ix->ready, 0));
+        u32 h[HDR_WORDS];
+        IVX_HIP(ctx, hipMemcpyAsync(h, ix->jv.hdr, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
+        IVX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        const u32 nlev = h[HDR_NLEV] < IVX_MAXL ? h[HDR_NLEV] : IVX_MAXL;
+        u32 levrows = 0;
+        for (u32 l = 0; l < nlev; l++) if (h[HDR_LEVCNT + l]) levrows |= 1u << l;
+        w[IVX_LAYOUT_SH0] = h[HDR_SH0];
+        w[IVX_LAYOUT_NLEV] = h[HDR_NLEV];
+        w[IVX_LAYOUT_LEVROWS] = levrows;
+        w[IVX_LAYOUT_RCELLS] = h[HDR_NREG] ? h[HDR_RCELLS] : 0u;
+        w[IVX_LAYOUT_RCS] = h[HDR_NREG] ? h[HDR_CS] : 0xFFFFFFFFu;
+        w[IVX_LAYOUT_NREG] = h[HDR_NREG];
+        w[IVX_LAYOUT_PK24] = h[HDR_PK24];
+        w[IVX_LAYOUT_SLOW] = h[HDR_SLOW];
+        w[IVX_LAYOUT_FG] = h[HDR_FG];
+        w[IVX_LAYOUT_FBITS] = h[HDR_FG] != 0xFFFFFFFFu ? h[HDR_FBITS] : 0u;
+        w[IVX_LAYOUT_NROUTE_NREG] = ix->nroute_nreg;
+    }
+    for (u32 i = 0; i < n_out && i < (u32)IVX_LAYOUT_WORDS; i++) out[i] = w[i];
+    return IVX_OK;
+}
+
 // ---------------------------------------------------------------- a3 probes
 
 static bool rowval_routed_ok(u64 n)

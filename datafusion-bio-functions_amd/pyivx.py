@@ -27,8 +27,11 @@ SYMBOLS = [
     "ivx_probe_count", "ivx_probe_coverage", "ivx_probe_nearest", "ivx_merge", "ivx_subtract",
     "ivx_cluster", "ivx_complement", "ivx_take_fixed", "ivx_take_utf8", "ivx_take_bits", "ivx_take_view",
     "ivx_ctx_metrics", "ivx_ctx_reset_metrics", "ivx_ctx_set_memory_limit", "ivx_ctx_trim", "ivx_scatter_fixed",
-    "ivx_ctx_reserved_bytes", "ivx_ctx_set_build_overlap",
+    "ivx_ctx_reserved_bytes", "ivx_ctx_set_build_overlap", "ivx_index_layout",
 ]
+
+# slots of ivx_index_layout (include/ivx.h IVX_LAYOUT_*), in order
+LAYOUT_SLOTS = ["kind", "sh0", "nlev", "levrows", "rcells", "rcs", "nreg", "pk24", "slow", "fg", "fbits", "nroute_nreg"]
 
 
 class Metrics(C.Structure):
@@ -121,6 +124,12 @@ class Index:
     @property
     def device_bytes(self):
         return lib().ivx_index_device_bytes(self.h)
+
+    def layout(self):
+        """the form the build picked for the binned overlap index (include/ivx.h ivx_index_layout) as a dict"""
+        out = (C.c_uint32 * len(LAYOUT_SLOTS))()
+        self.ctx._chk(lib().ivx_index_layout(self.ctx.h, self.h, out, C.c_uint32(len(LAYOUT_SLOTS))))
+        return dict(zip(LAYOUT_SLOTS, list(out)))
 
     def free(self):
         if self.h:

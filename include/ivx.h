@@ -148,6 +148,27 @@ void       ivx_index_free(ivx_index *ix);
 uint64_t   ivx_index_rows(const ivx_index *ix);
 uint64_t   ivx_index_device_bytes(const ivx_index *ix);
 
+/* ---- layout readout (tests and diagnostics): the form the build picked on the device for the binned overlap index
+ *      behind OVERLAP, COUNT and COVERAGE indexes.  Writes min(n_out, IVX_LAYOUT_WORDS) words, the slots below; a
+ *      NEAREST index reports its kind and zeros.  Waits for an index whose build tail still runs (build overlap on),
+ *      so IVX_LAYOUT_SLOW is final; reads only, the index is unchanged. */
+enum {
+    IVX_LAYOUT_KIND = 0,        /* IVX_KIND_* */
+    IVX_LAYOUT_SH0 = 1,         /* log2 of the level-0 cell width */
+    IVX_LAYOUT_NLEV = 2,        /* length-class levels */
+    IVX_LAYOUT_LEVROWS = 3,     /* bit l set: level l holds build rows */
+    IVX_LAYOUT_RCELLS = 4,      /* level-0 cells per probe region (0: no regions) */
+    IVX_LAYOUT_RCS = 5,         /* log2 of that when it is a power of two, else 0xFFFFFFFF */
+    IVX_LAYOUT_NREG = 6,        /* probe regions (0: the region probe is not available) */
+    IVX_LAYOUT_PK24 = 7,        /* 1: a region spans at most 2^24 coordinates (routed rows pack into 8 bytes) */
+    IVX_LAYOUT_SLOW = 8,        /* 1: a row above level 0, or a region slice too big for LDS: no lean fill */
+    IVX_LAYOUT_FG = 9,          /* log2 of the occupancy bitmap's block width, or 0xFFFFFFFF: no bitmap */
+    IVX_LAYOUT_FBITS = 10,      /* the bitmap's size in bits */
+    IVX_LAYOUT_NROUTE_NREG = 11,/* regions of the routing view of big per-row probes (0: none) */
+    IVX_LAYOUT_WORDS = 12
+};
+ivx_status ivx_index_layout(ivx_ctx *ctx, const ivx_index *ix, uint32_t *out, uint32_t n_out);
+
 /* ---- a3: IntervalJoinAlgorithm::get + probe loop
  *      (interval_join.rs:849-900, :1614-1653).  Index kind OVERLAP. ---------
  * count: total pairs and, if per_row != NULL, the reference's rle_right

@@ -53,6 +53,7 @@ extern "C" {
     pub fn ivx_index_free(ix: *mut IvxIndex);
     pub fn ivx_index_rows(ix: *const IvxIndex) -> u64;
     pub fn ivx_index_device_bytes(ix: *const IvxIndex) -> u64;
+    pub fn ivx_index_layout(ctx: *mut IvxCtx, ix: *const IvxIndex, out: *mut u32, n_out: u32) -> i32;
     pub fn ivx_probe_overlap_count(ctx: *mut IvxCtx, ix: *const IvxIndex, mem: i32, key: *const u32, start: *const i32,
                                    end: *const i32, n: u64, per_row: *mut u32, total: *mut u64) -> i32;
     pub fn ivx_probe_overlap_fill(ctx: *mut IvxCtx, ix: *const IvxIndex, mem: i32, key: *const u32, start: *const i32,

@@ -27,6 +27,15 @@ def test_header_symbols_exported():
     assert sorted(pyivx.SYMBOLS) == names
 
 
+def test_layout_slots_match_the_header():
+    # pyivx.LAYOUT_SLOTS names the words of ivx_index_layout in the order of the IVX_LAYOUT_* enum of include/ivx.h
+    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "ivx.h")).read(), flags=re.S)
+    slots = {m.group(1).lower(): int(m.group(2)) for m in re.finditer(r"\bIVX_LAYOUT_(\w+)\s*=\s*(\d+)", src)}
+    words = slots.pop("words")
+    assert sorted(slots.values()) == list(range(words))
+    assert sorted(slots, key=slots.get) == pyivx.LAYOUT_SLOTS
+
+
 def test_no_cpu_fallback():
     import torch
     if torch.cuda.is_available():
