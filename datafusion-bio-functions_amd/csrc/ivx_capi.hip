@@ -29,7 +29,7 @@ ivx_status ivx_ctx::get_scratch(int slot, size_t bytes, void **out)
     if (tail_pending && slot != WS_SORTHIST && slot != WS_T0 && slot != WS_T1 && slot != WS_T2) join_tail();
     ivx_buf &b = scratch[slot];
     if (sub_plan.valid && ((sub_plan.slots >> slot) & 1)) sub_plan.valid = false;
-    if (join_plan.valid && ((join_plan.slots >> slot) & 1)) join_plan.valid = false;
+    if (join_plan.valid && ((join_plan.rows.slots >> slot) & 1)) join_plan.valid = false;
     if (bytes < 256) bytes = 256;
     if (b.cap < bytes) {
         size_t want = bytes + bytes / 8;

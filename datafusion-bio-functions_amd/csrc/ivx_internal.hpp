@@ -40,27 +40,56 @@ struct ivx_sub_plan {
     const u32 *plan_hlo; const i64 *plan_tail;      // per left row: its first gap head, where its tail fragment starts
 };
 
-// What a region-partitioned overlap COUNT call leaves behind for the fill call that follows it: the probe
-// rows routed to their regions (tile histogram, partitioned (start,end) and row ids) -- the fill call for
-// the same index, columns and stream goes straight to its probe kernel.
+// Probe rows routed to the regions of an overlap index or routing view (ivx_regions_route.hip fills one in, the probes of
+// ivx_regions_probe.hip and the routed operators of ivx_join.hip / ivx_ops32.hip read it).  It says where the rows are and in
+// what form, not who routed them.
+struct PageTab { u32 *ptab; u32 pstride, lgpg; };     // [region][page slot] -> pool page + 1 (0 = not there yet); a page holds 2^lgpg rows
+// control block of the one-pass partition, one zero-initialised scratch buffer (the counters up to `rfirst` are cleared per call)
+struct ivx_route_ctl {
+    u32 rcur[1024];                     // rows routed to every region
+    u32 pool_next, pad0[3];             // pages taken from the pool
+    u32 rest_n[2], pad1[2];             // the lean probes' rest lists: batches, rows
+    u32 rfirst[1032];                   // first routed row of every region (k_page_bounds / k_chunk_bounds)
+    u32 cfirst[1032];                   // first 8192-row chunk of every region (k_chunk_bounds)
+};
+struct FpRest;                          // a batch the lean fill kernel leaves to the generic walk (ivx_regions.hpp)
+enum {
+    IVX_ROWS_FLAT = 0,                  // contiguous runs; rfirst = scanned [digit][nblk] histogram: region r starts at rfirst[r * nblk]
+    IVX_ROWS_PAGED,                     // region pages behind a page table (one-pass partition); rfirst[r] = first routed row of region r
+    IVX_ROWS_TABLE                      // contiguous regions, rfirst[r] a global table (two-level routing: more than IVX_MAXREG_WIDE regions)
+};
+struct ivx_routed {
+    int form = IVX_ROWS_FLAT;
+    const u64 *se = nullptr;            // the row words in routed order: (start,end), or the packed form; PAGED: the page pool
+    const u32 *ids = nullptr;           // each row's id, at the row's position (null: packed rows carry their own) ...
+    const unsigned short *cidx = nullptr;   // ... or its index inside its workgroup's chunk (per-row-value consumers: k_unpermute)
+    const u32 *rfirst = nullptr;
+    u32 nblk = 1, chunk = 0, ndig = 0;  // FLAT: workgroups of the partition, rows each took, digits of the histogram (256 / 1024)
+    const u32 *unsorted = nullptr;      // FLAT / TABLE: *unsorted == 0: the rows came in region order, nothing was moved (read ds / de in place)
+    PageTab pt{nullptr, 0u, 0u};
+    bool packed = false;                // 8-byte routed rows (start in region | length | row), else (start,end) + row id
+    u32 rowbits = 32;                   // bits of a packed row's id (the rest of the word's upper half extends the length)
+    bool all_routed = false;            // no occupancy bitmap in use: every row was routed (the fill's rows-per-lane rule is then known on the host)
+    ivx_route_ctl *ctl = nullptr;
+    FpRest *rest = nullptr; u64 *rest_rows = nullptr;   // the lean probes' rest lists (batches: fill only; single rows), or null
+    const uint2 *vtab = nullptr;        // PAGED, per-row-value consumers: [tile][region] -> (virtual start, rows) of the tile's run
+    const i32 *ds = nullptr, *de = nullptr;   // device start / end columns the rows were routed from (packed escapes and unmoved rows read them)
+    u32 adj = 0;                        // 1: the UDTFs' strict mode, rows hold [start+1, end-1]
+    u64 slots = 0;                      // scratch slots all of this sits in (bit per slot)
+};
+
+// What a region-partitioned overlap COUNT call leaves behind for the fill call that follows it: the routed probe
+// rows and whose they are -- the fill call for the same index, columns and stream goes straight to its probe kernel.
+// Touching any scratch slot of the rows drops the plan (ivx_ctx::get_scratch).
 struct ivx_join_plan {
     bool valid = false;
-    u64 slots = 0;
     int mem = 0;
     const void *in[3] = {};
     u64 n = 0;
     u64 total = 0;                      // the pairs the count call found: the fill call's density hint, whatever its cap
     const void *ix = nullptr; u64 ix_serial = 0;
     hipStream_t stream = nullptr;
-    const u32 *hist = nullptr; const u64 *pse = nullptr; const u32 *prow = nullptr;
-    const i32 *ds = nullptr, *de = nullptr;     // device copies of the start / end columns (read in place when the rows were in region order)
-    u32 chunk = 0, nblk = 0;
-    // one-pass routing (ivx_join_regions.hip): the rows sit in pages; hist = first routed row of every region,
-    // ptab = [region][page slot] -> page + 1
-    bool paged = false, packed = false;   // packed: 8-byte routed rows (start in region | length | row), else (start,end) + row id
-    const u32 *ptab = nullptr; u32 pstride = 0, lgpg = 0, rowbits = 32;
-    void *rest = nullptr;                 // the lean fill kernel's list of batches left to the generic walk (scratch, in `slots`)
-    bool all_routed = false;              // no occupancy bitmap in use: every row was routed (the fill's rows-per-lane rule is then known on the host)
+    ivx_routed rows;
 };
 
 struct ivx_ctx {
@@ -153,10 +182,10 @@ enum { HDR_SH0 = 0, HDR_NLEV = 1, HDR_NBINS = 2, HDR_CS = 3 /* log2(cells per re
 #define IVX_MAXREG2 65025u   // most regions at all: beyond 255 the probe rows are routed by a two-digit stable sort
 #define IVX_REG_CS_MAX 13   // a region spans at most 2^13 level-0 cells, what a workgroup can stage in LDS
 
-// what a probe workgroup needs to stage one region's slice of level 0 (ivx_join_regions.hip), precomputed at
+// what a probe workgroup needs to stage one region's slice of level 0 (ivx_regions_probe.hip), precomputed at
 // build time so that staging starts with ONE load instead of a chain of four dependent ones
 #ifndef IVX_RP_ECAP
-#define IVX_RP_ECAP 6144          // level-0 entries a region's LDS slice holds (ivx_join_regions.hip)
+#define IVX_RP_ECAP 6144          // level-0 entries a region's LDS slice holds (ivx_regions_probe.hip)
 #endif
 #define IVX_RP_HALO 8u      // slice cells past the region's last cell
 struct ivx_regdesc { u32 k; i32 origin; u32 span, lb, slo, shi, e0, ne; i32 rbase; /* coordinate of the region's first cell */ };
@@ -234,11 +263,6 @@ struct ivx_index {
 };
 enum { IVX_IXF_REGION_ROWVAL = 1 };   // count/coverage index: jv is usable for the region-partitioned per-row probe
 
-// probe rows routed to the regions of a routing view (ivx_route_rows): scanned [1024][nblk] histogram (region r starts at
-// hist[r * nblk]), the rows' (start,end) in routed order, each row's index inside its one-tile chunk; *unsorted == 0:
-// the rows came in region order already and nothing was moved
-struct ivx_routed { const u32 *hist; const u64 *pse; const unsigned short *cidx; const u32 *unsorted; u32 nblk, chunk; };
-
 // ---------------------------------------------------------------- internal API
 // scan.hip
 ivx_status ivx_scan_exclusive_u32(ivx_ctx *ctx, u32 *data, u64 n);      // in place, uses WS_SCAN*
@@ -250,7 +274,7 @@ ivx_status ivx_join_probe(ivx_ctx *ctx, const JoinIndexView &jv, int mode,
                           const u32 *key, const i32 *s, const i32 *e, u64 n,
                           u32 *per_row, u8 *exists, u32 *ob, u32 *op, u64 cap, u64 *d_cursor);
 enum { JP_COUNT = 0, JP_PER_ROW = 1, JP_EXISTS = 2, JP_FILL = 3 };
-// join_regions.hip: partition the probe rows by index region, probe each region from LDS
+// ivx_regions_probe.hip: partition the probe rows by index region (ivx_regions_route.hip), probe each region from LDS
 ivx_status ivx_join_probe_regions(ivx_ctx *ctx, const JoinIndexView &jv, u32 nreg, int mode,
                                   const u32 *key, const i32 *s, const i32 *e, u64 n,
                                   u32 *ob, u32 *op, u64 cap, u64 *d_cursor, bool planned = false, bool has_filter = false, bool pk24 = false,

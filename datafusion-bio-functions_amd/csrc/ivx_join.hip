@@ -278,7 +278,7 @@ __global__ __launch_bounds__(256) void k_join_regdesc(const i32 *origin, const u
     d.e0 = binstart[d.lb + d.slo];
     d.ne = binstart[d.lb + d.shi] - d.e0;
     d.rbase = (i32)((i64)d.origin + (i64)(rc0w << sh0));           // (rc0 < cells0: at most the key's largest start)
-    if (d.ne > IVX_RP_ECAP || d.shi - d.slo + 1u > 8192u + IVX_RP_HALO + 2u) hdr[HDR_SLOW] = 1u;   // the slice does not fit LDS (ivx_join_regions.hip)
+    if (d.ne > IVX_RP_ECAP || d.shi - d.slo + 1u > 8192u + IVX_RP_HALO + 2u) hdr[HDR_SLOW] = 1u;   // the slice does not fit LDS (ivx_regions_probe.hip)
     rdesc[r] = d;
 }
 
@@ -523,7 +523,7 @@ ivx_status ivx_join_rowval_routed(ivx_ctx *ctx, const ivx_index *ix, int mode, c
     // (five workgroups per CU: the rows in flight on an XCD span less of the index than its L2 holds -- 100M x 10M rle_right
     //  11.0 -> 9.5 ms; see k_nearest_routed)
     const u32 grid = (ivx_stream_grid(n, PT * 4, 1280u) + 7u) & ~7u;
-    hipLaunchKernelGGL(k_overlap_rowval_routed, dim3(grid), dim3(PT), 0, st, ix->jv, ix->nroute.rkey, ix->nroute_nreg, R.pse, R.hist, R.nblk,
+    hipLaunchKernelGGL(k_overlap_rowval_routed, dim3(grid), dim3(PT), 0, st, ix->jv, ix->nroute.rkey, ix->nroute_nreg, R.se, R.rfirst, R.nblk,
                        mode == JP_EXISTS ? 1 : 0, vb, (unsigned long long *)d_total, R.unsorted);
     IVX_TRY(ivx_unroute_u32(ctx, R, n, vb, per_row, exists));
     // rows that came in region order were not moved: the plain kernel answers them in place (gated on the flag)

@@ -1,4 +1,4 @@
-// ivx_join.hpp -- device helpers shared by the overlap-index kernels (ivx_join.hip, ivx_join_regions.hip).
+// ivx_join.hpp -- device helpers shared by the overlap-index kernels (ivx_join.hip, ivx_regions_route.hip, ivx_regions_probe.hip).
 #pragma once
 #include "ivx_device.hpp"
 

@@ -65,7 +65,7 @@ __global__ __launch_bounds__(OT) void k_any_inverted(const i32 *__restrict__ s, 
     if (i < n && e[i] < s[i]) *flag = 1;
 }
 
-// large unsorted batches go through the region partition (ivx_join_regions.hip) unless told otherwise
+// large unsorted batches go through the region partition (ivx_regions_probe.hip) unless told otherwise
 bool rowval_regions_wanted(const ivx_index *ix, u64 n)
 {
     if (!(ix->flags & IVX_IXF_REGION_ROWVAL) || ix->jv_nreg == 0 || ix->jv_nreg > IVX_MAXREG_WIDE) return false;   // one partition pass only
@@ -881,8 +881,8 @@ static ivx_status rowval_routed(ivx_ctx *ctx, const ivx_index *ix, bool coverage
     i64 *vd;
     IVX_TRY(ctx->get_scratch(WS_T3, n * sizeof(i64), (void **)&vd));
     const u32 grid = (ivx_stream_grid(n, OT * 4) + 7u) & ~7u;
-    if (coverage) hipLaunchKernelGGL((k_rowval_routed<true>), dim3(grid), dim3(OT), 0, st, ix->gs, ix->ge, ix->cv, ix->nroute.rkey, ix->nroute_nreg, R.pse, R.hist, R.nblk, vd, R.unsorted);
-    else hipLaunchKernelGGL((k_rowval_routed<false>), dim3(grid), dim3(OT), 0, st, ix->gs, ix->ge, ix->cv, ix->nroute.rkey, ix->nroute_nreg, R.pse, R.hist, R.nblk, vd, R.unsorted);
+    if (coverage) hipLaunchKernelGGL((k_rowval_routed<true>), dim3(grid), dim3(OT), 0, st, ix->gs, ix->ge, ix->cv, ix->nroute.rkey, ix->nroute_nreg, R.se, R.rfirst, R.nblk, vd, R.unsorted);
+    else hipLaunchKernelGGL((k_rowval_routed<false>), dim3(grid), dim3(OT), 0, st, ix->gs, ix->ge, ix->cv, ix->nroute.rkey, ix->nroute_nreg, R.se, R.rfirst, R.nblk, vd, R.unsorted);
     IVX_TRY(ivx_unroute_pair(ctx, R, n, nullptr, vd, nullptr, nullptr, out, 0));      // rows that could not be routed: 0, as the reference answers
     // rows that came in region order were not moved: the plain kernels answer them in place
     if (coverage) hipLaunchKernelGGL(k_probe_coverage, dim3(ivx_stream_grid(n, OT * 4)), dim3(OT), 0, st, ix->cv, key, s, e, n, strict, out, R.unsorted);
@@ -932,8 +932,8 @@ ivx_status ivx_nearest_probe(ivx_ctx *ctx, const ivx_index *ix, const u32 *key, 
             const int pmax_first = getenv("IVX_NEAREST_PMAX_FIRST") ? atoi(getenv("IVX_NEAREST_PMAX_FIRST")) : 1;
             // five 256-thread workgroups per CU, not eight: the rows in flight on an XCD then span less of the index than its L2
             // holds (grid 2048 -> 1280: 3.75 -> 3.17 ms per 50M rows; 1024..1536 are within 3 %, 1792 and 2048 fall off)
-            hipLaunchKernelGGL(k_nearest_routed, dim3((ivx_stream_grid(n, NR_T * 4, 1280u) + 7u) & ~7u), dim3(NR_T), 0, st, ix->nv, ix->nroute.rkey, ix->nroute_nreg, R.pse,
-                               R.hist, R.nblk, strict ? 1u : 0u, include_overlaps, vb, vd, R.unsorted, pmax_first);
+            hipLaunchKernelGGL(k_nearest_routed, dim3((ivx_stream_grid(n, NR_T * 4, 1280u) + 7u) & ~7u), dim3(NR_T), 0, st, ix->nv, ix->nroute.rkey, ix->nroute_nreg, R.se,
+                               R.rfirst, R.nblk, strict ? 1u : 0u, include_overlaps, vb, vd, R.unsorted, pmax_first);
             IVX_TRY(ivx_unroute_pair(ctx, R, n, vb, vd, ob, op, od, -1));
             // rows that came in region order were not moved: the plain kernel answers them in place
             hipLaunchKernelGGL(k_probe_nearest1, dim3(ivx_stream_grid(n, OT * 4)), dim3(OT), 0, st, ix->nv, key, s, e, n, strict, include_overlaps, ob, op, od, R.unsorted);

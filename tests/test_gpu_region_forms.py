@@ -3,7 +3,7 @@
 The binned overlap index (csrc/ivx_join.hip) picks its layout on the device: the level-0 cell shift sh0, the cells per
 probe region R (a power of two, or any integer divided by multiplication), the packed 8-byte routed rows (pk24), the lean
 fill (off for the whole index when one row sits above level 0 or one slice outgrows IVX_RP_ECAP), the occupancy bitmap and
-the region count.  The probe (csrc/ivx_join_regions.hip) picks its own form from n and cap: rows-per-lane bands, dense
+the region count.  The probe (csrc/ivx_regions_probe.hip) picks its own form from n and cap: rows-per-lane bands, dense
 fill, the length field of packed rows, partition tiles, page size.  Every case below sits on one named side of one of
 those thresholds; it reads the index's form back through ivx_index_layout, restates the host rules (region_geometry,
 probe_form) and asserts the side it reaches before it compares bit-exactly with the CPU oracle, under the default settings
@@ -29,8 +29,8 @@ pytestmark = pytest.mark.gpu
 IVX_RP_ECAP = 6144                 # ivx_internal.hpp
 IVX_RP_HALO = 8                    # ivx_internal.hpp
 IVX_MAXREG, IVX_MAXREG_WIDE = 255, 1023
-KT_MAX = 256                       # ivx_join_regions.hip
-FP_CHUNK = 8192                    # ivx_join_regions.hip (RP_W * IVX_WAVE * 8)
+KT_MAX = 256                       # ivx_regions_route.hip
+FP_CHUNK = 8192                    # ivx_regions.hpp (RP_W * IVX_WAVE * 8)
 NOFG = 0xFFFFFFFF
 
 # knobs that turn a form off, applied to the probe calls (IVX_FILTER=force is a build-time knob: a second index)
@@ -95,7 +95,7 @@ def region_geometry(layout, key, s, e, n_keys):
 
 def probe_form(layout, n, cap, env_=None, mode="fill"):
     """The form ivx_probe_overlap_* takes for a batch of n rows with pair buffers of cap (ivx_capi.hip overlap_common,
-    ivx_join_regions.hip ivx_join_probe_regions).  env_: the IVX_* settings of the call."""
+    ivx_regions_probe.hip ivx_join_probe_regions).  env_: the IVX_* settings of the call."""
     env_ = env_ or {}
     nreg = layout["nreg"]
     f = {}
