@@ -456,6 +456,7 @@ extern "C" ivx_status ivx_index_layout(ivx_ctx *ctx, const ivx_index *ix, uint32
         w[IVX_LAYOUT_FG] = h[HDR_FG];
         w[IVX_LAYOUT_FBITS] = h[HDR_FG] != 0xFFFFFFFFu ? h[HDR_FBITS] : 0u;
         w[IVX_LAYOUT_NROUTE_NREG] = ix->nroute_nreg;
+        w[IVX_LAYOUT_LBUILD] = h[HDR_LBUILD];
     }
     for (u32 i = 0; i < n_out && i < (u32)IVX_LAYOUT_WORDS; i++) out[i] = w[i];
     return IVX_OK;
@@ -505,13 +506,15 @@ static ivx_status overlap_common(ivx_ctx *ctx, const ivx_index *ix, int mem, int
     IVX_TRY(stage_out(ctx, mem, WS_OUT_B, exists, n, &d_ex));
     IVX_TRY(stage_out(ctx, mem, WS_OUT_C, bidx, cap, &d_b));
     IVX_TRY(stage_out(ctx, mem, WS_OUT_D, pidx, cap, &d_p));
-    IVX_HIP(ctx, hipMemsetAsync(ctx->d_scalars, 0, 2 * sizeof(u64), ctx->stream));   // pair cursor | probe fault flags
+    // pair cursor | probe fault flags: zeroed here, or -- a region probe that routes its rows -- by the routing pass's clearing kernel
+    const bool defer_clear = regions && !planned;
+    if (!defer_clear) IVX_HIP(ctx, hipMemsetAsync(ctx->d_scalars, 0, 2 * sizeof(u64), ctx->stream));
     {
         KernelTimer t(ctx);
         if (regions) {
             if (!planned) pl.valid = false;                 // whatever an earlier count call left is gone now
             const ivx_status st = ivx_join_probe_regions(ctx, ix->jv, ix->jv_nreg, mode, dk, ds, de, n, d_b, d_p, cap, ctx->d_scalars, planned, ix->jv_filter, ix->jv_pk24,
-                                                         ix->jv_fast_unknown ? 2 : (ix->jv_fast ? 1 : 0), planned ? nullptr : ix->ready);
+                                                         ix->jv_fast_unknown ? 2 : (ix->jv_fast ? 1 : 0), planned ? nullptr : ix->ready, defer_clear);
             if (st != IVX_OK) { pl.valid = false; return st; }
             if (mode == JP_COUNT && pl.valid) { memcpy(pl.in, in, sizeof(in)); pl.mem = mem; pl.n = n; pl.ix = ix; pl.ix_serial = ix->serial; pl.stream = ctx->stream; }
         }

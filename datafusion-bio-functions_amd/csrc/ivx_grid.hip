@@ -17,6 +17,7 @@ __global__ void k_init_keystats(i32 *kmin, i32 *kmax, u32 *kcnt, u32 nkeys, ivx_
     if (blockIdx.x == 0)
         for (int r = 0; r < 3; r++)
             for (u32 j = threadIdx.x; j < z.n[r]; j += blockDim.x) z.p[r][j] = 0;
+    for (u32 j = i; j < z.nbig; j += gridDim.x * blockDim.x) z.big[j] = make_uint4(0u, 0u, 0u, 0u);
 }
 
 // per-key min / max of v and row counts, privatised in LDS; key ids >= nkeys raise *errflag.
@@ -218,7 +219,9 @@ ivx_status ivx_keystats_len(ivx_ctx *ctx, const u32 *key, const i32 *v, u64 n, u
     hipStream_t st = ctx->stream;
     ivx_zero_ranges z{};
     if (zero) z = *zero;
-    hipLaunchKernelGGL(k_init_keystats, dim3((nkeys + GT - 1) / GT), dim3(GT), 0, st, kmin, kmax, kcnt, nkeys, z);
+    u32 igrid = (nkeys + GT - 1) / GT;
+    if (z.nbig) { const u32 want = (z.nbig + GT * 8 - 1) / (GT * 8); igrid = igrid > want ? igrid : (want < 256u ? want : 256u); }   // (eight stores a thread)
+    hipLaunchKernelGGL(k_init_keystats, dim3(igrid), dim3(GT), 0, st, kmin, kmax, kcnt, nkeys, z);
     if (n) {
         const u32 grid = ivx_stream_grid(n, GT * 8, 1024);
         const size_t shm = nkeys <= KEYS_IN_LDS ? (size_t)nkeys * 12 : 0;

@@ -172,7 +172,9 @@ enum { HDR_SH0 = 0, HDR_NLEV = 1, HDR_NBINS = 2, HDR_CS = 3 /* log2(cells per re
        HDR_FG = 8 + IVX_MAXL /* log2(block width) of the occupancy bitmap, or ~0u: no bitmap */, HDR_FBITS = 9 + IVX_MAXL /* its size in bits */,
        HDR_PK24 = 10 + IVX_MAXL /* 1: a region spans at most 2^24 coordinates (routed rows pack into 8 bytes) */,
        HDR_SLOW = 11 + IVX_MAXL /* 0: every region is ONE LDS-resident level (all build rows in level 0, every slice fits): the lean fill probe applies */,
-       HDR_WORDS = 12 + IVX_MAXL };
+       HDR_LBUILD = 12 + IVX_MAXL /* 1: the build's tail sorts every region's rows in LDS (ivx_join.hip: k_lbuild_*); 0: the global counting sort */,
+       HDR_BADKEY = 13 + IVX_MAXL /* != 0: a build row's key id is >= n_keys (the key statistics' flag: one copy brings it to the host with the layout) */,
+       HDR_WORDS = 14 + IVX_MAXL };
 // Occupancy bitmap of the build side ("can a probe row match anything at all"): per key one bit per 2^g-wide block of
 // [origin, origin + span] plus one overflow block behind it; a bit is set when some build row touches the block.  Sized to
 // stay resident in an XCD's 4 MiB L2 next to the streamed probe rows.
@@ -265,7 +267,7 @@ enum { IVX_IXF_REGION_ROWVAL = 1 };   // count/coverage index: jv is usable for 
 
 // ---------------------------------------------------------------- internal API
 // scan.hip
-ivx_status ivx_scan_exclusive_u32(ivx_ctx *ctx, u32 *data, u64 n);      // in place, uses WS_SCAN*
+ivx_status ivx_scan_exclusive_u32(ivx_ctx *ctx, u32 *data, u64 n, const u32 *skip = nullptr);      // in place, uses WS_SCAN*; skip (nullable): the kernels leave at once when *skip != 0
 ivx_status ivx_scan_exclusive_u64(ivx_ctx *ctx, u64 *data, u64 n);
 
 // join.hip
@@ -278,7 +280,8 @@ enum { JP_COUNT = 0, JP_PER_ROW = 1, JP_EXISTS = 2, JP_FILL = 3 };
 ivx_status ivx_join_probe_regions(ivx_ctx *ctx, const JoinIndexView &jv, u32 nreg, int mode,
                                   const u32 *key, const i32 *s, const i32 *e, u64 n,
                                   u32 *ob, u32 *op, u64 cap, u64 *d_cursor, bool planned = false, bool has_filter = false, bool pk24 = false,
-                                  int fast = 0 /* 0 no, 1 yes, 2 the kernels test hdr[HDR_SLOW] themselves */, hipEvent_t ready = nullptr);
+                                  int fast = 0 /* 0 no, 1 yes, 2 the kernels test hdr[HDR_SLOW] themselves */, hipEvent_t ready = nullptr,
+                                  bool clear_cursor = false /* d_cursor[0..1] are still to be zeroed (with the routing pass's own clears) */);
 
 // per-row-output operators through the same partition (count_overlaps: jv over the build rows, no row with
 // end < start; coverage: jv over the merged nodes)

@@ -29,6 +29,20 @@ namespace {
 
 constexpr int BT = 256;              // build kernels
 
+// level-0 build per region (k_lbuild_*)
+constexpr int LB_T = 1024;                                  // threads of both kernels: one per region counter; a region of ~5000 rows is one workgroup's
+constexpr int LB_ROWS = 4;                                  // rows per thread of a tile
+constexpr u32 LB_TILE = LB_T * LB_ROWS;
+constexpr u32 LB_STRIDE = IVX_MAXREG_WIDE + 1;              // rows of the region table: prefix of regions 0 .. IVX_MAXREG_WIDE of every tile
+constexpr u32 LB_CCAP = 8192;                               // cells of a region's LDS table (2^IVX_REG_CS_MAX)
+constexpr u32 LB_MAXTILES = 1024;                           // tiles a region workgroup looks through
+constexpr int LB_KEEP = (IVX_RP_ECAP + LB_T - 1) / LB_T;    // rows a thread keeps in registers between count and scatter: a region the probe can stage
+constexpr u64 LB_MIN_ROWS = 1u << 14, LB_MAX_ROWS = (u64)LB_MAXTILES * LB_TILE;
+static_assert(LB_STRIDE == LB_T && LB_TILE <= 4096 && LB_CCAP == (1u << IVX_REG_CS_MAX), "k_lbuild_tiles: one table word per thread, 12-bit ranks");
+// the table is region-major, tab[region * tstride + tile], so that a region workgroup reads its two rows of it
+// contiguously; tstride is odd: the tiles' column writes spread over the memory channels
+static inline u32 lb_tstride(u32 ntiles) { return ntiles | 1u; }
+
 // ------------------------------------------------------------------ build
 
 __device__ __forceinline__ u32 cells_of(u32 cnt, u32 span, u32 sh) { return cnt ? (sh >= 32 ? 1u : (span >> sh) + 1u) : 0u; }
@@ -37,7 +51,7 @@ __device__ __forceinline__ u32 cells_of(u32 cnt, u32 span, u32 sh) { return cnt 
 // lay out the (level,key) cell ranges.  hdr: sh0, #levels, #cells.
 __global__ __launch_bounds__(1024) void k_join_layout(const i32 *kmin, const i32 *kmax, const u32 *kcnt, u32 nkeys, u64 n,
                                                       i32 *origin, u32 *span, u32 *lbase, u32 *hdr, u64 maxcells,
-                                                      u32 *kreg, u32 *rkey, const u32 *lenhist, u32 regmax, u32 *fbase, int filter_mode)
+                                                      u32 *kreg, u32 *rkey, const u32 *lenhist, u32 regmax, u32 *fbase, int filter_mode, int lbuild_ok, const u32 *badkey)
 {
     __shared__ u64 red[1024 / IVX_WAVE + 1];
     __shared__ u32 s_sh0;
@@ -250,7 +264,148 @@ __global__ __launch_bounds__(1024) void k_join_layout(const i32 *kmin, const i32
         const u64 M = R ? ((1ull << 40) + R - 1) / R : 0;
         hdr[HDR_RMUL_LO] = (u32)M; hdr[HDR_RMUL_HI] = (u32)(M >> 32);
         hdr[HDR_PK24] = (R && sh0 < 24 && R <= (1ull << (24 - sh0))) ? 1u : 0u;
+        // the build's tail sorts every region in LDS (k_lbuild_*) when all rows sit on level 0 (none has more than sh0
+        // length bits) and the regions are what one workgroup handles: one digit of them, a cell table that fits
+        hdr[HDR_BADKEY] = *badkey;
+        hdr[HDR_LBUILD] = (lbuild_ok && R && R <= LB_CCAP && rrun && rrun <= IVX_MAXREG_WIDE && s_cum[33] == s_cum[sh0 + 1]) ? 1u : 0u;
     }
+}
+
+// ---- the tail of a level-0 build, region by region.  The layout has cut level 0 into regions in cell order, so the
+// entries of region r follow those of region r - 1 and a region's cells are few enough to count and scan in LDS:
+//   k_lbuild_tiles   : a workgroup groups its LB_TILE rows by region (LDS counters) into `rows` and leaves the tile's
+//                      prefix over the regions in tab[region][tile] -- no global atomics, no order between workgroups;
+//   k_lbuild_regions : workgroup r finds its rows through row r of that table (the row's sum is the region's first
+//                      entry), counts and scans its cells in LDS, writes its piece of binstart and its entries.
+// Every level-0 cell belongs to a region; the cells of the (empty) upper levels get the total.  k_join_regdesc follows.
+// Both kernels are queued before the device knows whether they apply (hdr[HDR_LBUILD]); where they do not,
+// k_lbuild_tiles clears the cell counters for the global path's kernels queued behind it, which otherwise leave at once.
+__global__ __launch_bounds__(LB_T) void k_lbuild_tiles(const u32 *__restrict__ key, const i32 *__restrict__ s, const i32 *__restrict__ e, u64 n, u32 nkeys,
+                                                     const i32 *origin, const u32 *kreg, u32 *hdr, ivx_ent *__restrict__ rows,
+                                                     u32 *__restrict__ tab, u32 tstride, u32 *__restrict__ binstart, u64 nbinwords)
+{
+    if (hdr[HDR_LBUILD] == 0) {
+        for (u64 i = (u64)blockIdx.x * LB_T + threadIdx.x; i < nbinwords; i += (u64)gridDim.x * LB_T) binstart[i] = 0;
+        return;
+    }
+    __shared__ u32 s_cnt[LB_STRIDE];
+    __shared__ u32 red[LB_T / IVX_WAVE + 1];
+    const u32 t = threadIdx.x;
+    s_cnt[t] = 0;
+    const u32 sh0 = hdr[HDR_SH0], cs = hdr[HDR_CS];
+    const u64 rmul = (u64)hdr[HDR_RMUL_LO] | ((u64)hdr[HDR_RMUL_HI] << 32);
+    __syncthreads();
+    const u64 base = (u64)blockIdx.x * LB_TILE;
+    const u32 have = n - base < LB_TILE ? (u32)(n - base) : LB_TILE;   // rows of this tile
+    const u32 *tk = key ? key + base : nullptr;
+    const i32 *ts = s + base, *te = e + base;
+    i32 rs[LB_ROWS], re[LB_ROWS];
+    u32 rr[LB_ROWS];                                                // region | rank inside the tile's run << 10, ~0u: no row
+#pragma unroll
+    for (int it = 0; it < LB_ROWS; it++) {
+        const u32 i = (u32)it * LB_T + t;
+        rr[it] = 0xFFFFFFFFu; rs[it] = 0; re[it] = 0;
+        if (i < have) {
+            const u32 k = tk ? tk[i] : 0u;
+            if (k < nkeys) {                                            // (a bad key id fails the build: k_keystats)
+                rs[it] = ts[i]; re[it] = te[i];
+                const u32 c = (u32)((i64)rs[it] - (i64)origin[k]) >> sh0;
+                u32 reg = kreg[k] + (cs != 0xFFFFFFFFu ? c >> cs : (u32)(((u64)c * rmul) >> 40));    // as the probe rows are routed
+                reg = reg < LB_STRIDE - 1 ? reg : LB_STRIDE - 2;
+                rr[it] = reg | (atomicAdd(&s_cnt[reg], 1u) << 10);
+            }
+        }
+    }
+    __syncthreads();
+    u32 tot;
+    const u32 p = block_excl_scan<u32, LB_T>(s_cnt[t], red, &tot);
+    s_cnt[t] = p; tab[(u64)t * tstride + blockIdx.x] = p;                 // (the last region's word: the tile's rows)
+    if (t == 0 && tot) hdr[HDR_LEVCNT] = 1u;                            // "level 0 holds rows" (same value from every writer)
+    __syncthreads();
+    ivx_ent *trows = rows + base;
+#pragma unroll
+    for (int it = 0; it < LB_ROWS; it++) {
+        if (rr[it] == 0xFFFFFFFFu) continue;
+        ivx_ent x; x.s = rs[it]; x.e = re[it]; x.row = (u32)base + (u32)it * LB_T + t;
+        trows[s_cnt[rr[it] & (LB_STRIDE - 1)] + (rr[it] >> 10)] = x;
+    }
+}
+
+__global__ __launch_bounds__(LB_T) void k_lbuild_regions(const i32 *origin, const u32 *span, const u32 *lbase, const u32 *kreg, const u32 *rkey,
+                                                       const u32 *hdr, u32 nkeys, const ivx_ent *__restrict__ rows, const u32 *__restrict__ tab,
+                                                       u32 ntiles, u32 tstride, u32 *__restrict__ binstart, ivx_ent *__restrict__ ent)
+{
+    if (hdr[HDR_LBUILD] == 0) return;
+    const u32 r = blockIdx.x, nreg = hdr[HDR_NREG], t = threadIdx.x;
+    if (r >= nreg) return;
+    __shared__ u32 s_cell[LB_CCAP];                                     // rows of every cell, then the cell's next free entry
+    __shared__ u32 s_tpre[LB_MAXTILES + 1];                             // the region's rows in the tiles before tile t
+    __shared__ unsigned short s_src[LB_MAXTILES];                       // where the region's run starts inside tile t
+    __shared__ u32 red[LB_T / IVX_WAVE + 1];
+    const u32 sh0 = hdr[HDR_SH0], R = hdr[HDR_RCELLS], k = rkey[r];
+    const i64 o = origin[k];
+    const u32 cells0 = (span[k] >> sh0) + 1u;
+    const u32 rc0 = (u32)((u64)(r - kreg[k]) * R);                      // < cells0: the region exists
+    const u32 nc = cells0 - rc0 < R ? cells0 - rc0 : R;
+    u32 run = 0, e0 = 0, total = 0;
+    for (u32 t0 = 0; t0 < ntiles; t0 += LB_T) {
+        const u32 ti = t0 + t;
+        u32 a = 0, b = 0;
+        if (ti < ntiles) {
+            a = tab[(u64)r * tstride + ti]; b = tab[(u64)(r + 1) * tstride + ti];
+            total += tab[(u64)(LB_STRIDE - 1) * tstride + ti];
+        }
+        u32 tot;
+        const u32 ex = block_excl_scan<u32, LB_T>(b - a, red, &tot);
+        if (ti < ntiles) { s_tpre[ti] = run + ex; s_src[ti] = (unsigned short)a; }
+        run += tot; e0 += a;
+    }
+    e0 = block_sum<u32, LB_T>(e0, red);                                   // rows of the regions before this one = its first entry
+    total = block_sum<u32, LB_T>(total, red);
+    const u32 N = run;
+    if (t == 0) s_tpre[ntiles] = N;
+    for (u32 j = t; j < nc; j += LB_T) s_cell[j] = 0;
+    __syncthreads();
+    auto fetch = [&](u32 i) -> ivx_ent {                                // row i of the region: the last tile with s_tpre <= i
+        u32 lo = 0, hi = ntiles - 1;
+        while (lo < hi) { const u32 m = (lo + hi + 1) >> 1; if (s_tpre[m] <= i) lo = m; else hi = m - 1; }
+        return rows[(u64)lo * LB_TILE + s_src[lo] + (i - s_tpre[lo])];
+    };
+    auto cell_in = [&](i32 st) -> u32 { const u32 c = ((u32)((i64)st - o) >> sh0) - rc0; return c < nc ? c : nc - 1; };
+    ivx_ent mine[LB_KEEP];                                              // a typical region's rows stay in registers between the passes
+#pragma unroll
+    for (int j = 0; j < LB_KEEP; j++) {
+        const u32 i = t + (u32)j * LB_T;
+        if (i < N) { mine[j] = fetch(i); atomicAdd(&s_cell[cell_in(mine[j].s)], 1u); }
+    }
+    for (u32 i = t + LB_KEEP * LB_T; i < N; i += LB_T) atomicAdd(&s_cell[cell_in(fetch(i).s)], 1u);
+    __syncthreads();
+    const u64 gb = (u64)lbase[k] + rc0;                                 // the region's first cell
+    u32 crun = 0;
+    for (u32 c0 = 0; c0 < nc; c0 += 4 * LB_T) {
+        const u32 j = c0 + 4 * t;
+        u32 c4[4], sum = 0, tot;
+#pragma unroll
+        for (int q = 0; q < 4; q++) { c4[q] = j + q < nc ? s_cell[j + q] : 0u; sum += c4[q]; }
+        u32 p = crun + block_excl_scan<u32, LB_T>(sum, red, &tot);
+#pragma unroll
+        for (int q = 0; q < 4; q++) { if (j + q < nc) { s_cell[j + q] = p; binstart[gb + j + q] = e0 + p; } p += c4[q]; }
+        crun += tot;
+    }
+    {   // the cells behind level 0 (upper levels, all empty here, and the closing word): a share per region
+        const u32 nlev = hdr[HDR_NLEV], nbins = hdr[HDR_NBINS];
+        const u32 l0 = nlev > 1 ? lbase[nkeys] : nbins;
+        const u32 len = nbins + 1 - l0, per = (len + nreg - 1) / nreg;
+        const u64 a = (u64)l0 + (u64)r * per, b = a + per < (u64)nbins + 1 ? a + per : (u64)nbins + 1;
+        for (u64 x = a + t; x < b; x += LB_T) binstart[x] = total;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < LB_KEEP; j++) {
+        const u32 i = t + (u32)j * LB_T;
+        if (i < N) ent[e0 + atomicAdd(&s_cell[cell_in(mine[j].s)], 1u)] = mine[j];
+    }
+    for (u32 i = t + LB_KEEP * LB_T; i < N; i += LB_T) { const ivx_ent x = fetch(i); ent[e0 + atomicAdd(&s_cell[cell_in(x.s)], 1u)] = x; }
 }
 
 // one thread per probe region: the level-0 cell window a workgroup stages for it and its entry range
@@ -287,6 +442,7 @@ __global__ __launch_bounds__(BT) void k_join_count(const u32 *__restrict__ key, 
                                                    const i32 *origin, const u32 *lbase, u32 *hdr, u32 *bincnt,
                                                    u32 *__restrict__ cellid, u32 *__restrict__ rank)
 {
+    if (hdr[HDR_LBUILD]) return;                           // (the regions were sorted in LDS: k_lbuild_*)
     const u32 sh0 = hdr[HDR_SH0], nlev = hdr[HDR_NLEV];
     u32 levels = 0;                                        // levels this thread put a row into
     for (u64 i = (u64)blockIdx.x * BT + threadIdx.x; i < n; i += (u64)gridDim.x * BT) {
@@ -308,8 +464,9 @@ __global__ __launch_bounds__(BT) void k_join_count(const u32 *__restrict__ key, 
 
 __global__ __launch_bounds__(BT) void k_join_scatter(const i32 *__restrict__ s, const i32 *__restrict__ e, u64 n,
                                                      const u32 *__restrict__ binstart, const u32 *__restrict__ cellid,
-                                                     const u32 *__restrict__ rank, ivx_ent *ent)
+                                                     const u32 *__restrict__ rank, ivx_ent *ent, const u32 *hdr)
 {
+    if (hdr[HDR_LBUILD]) return;
     for (u64 i = (u64)blockIdx.x * BT + threadIdx.x; i < n; i += (u64)gridDim.x * BT) {
         const u32 c = cellid[i];
         if (c == 0xFFFFFFFFu) continue;
@@ -565,20 +722,28 @@ ivx_status ivx_join_build(ivx_ctx *ctx, ivx_index *ix, const u32 *key, const i32
     i32 *kmin, *kmax; u32 *cellid, *rank, *errflag;
     IVX_TRY(ctx->get_scratch(WS_GRID0, nkeys * sizeof(i32), (void **)&kmin));
     IVX_TRY(ctx->get_scratch(WS_GRID1, nkeys * sizeof(i32), (void **)&kmax));
-    IVX_TRY(ctx->get_scratch(WS_GRID2, (n ? n : 1) * sizeof(u32), (void **)&cellid));
-    IVX_TRY(ctx->get_scratch(WS_T9, (n ? n : 1) * sizeof(u32), (void **)&rank));
+    // IVX_BUILD=global: never the per-region LDS tail (A/B runs, tests).  It takes builds of LB_MIN_ROWS .. LB_MAX_ROWS rows
+    // whose layout allows it, which the device decides (hdr[HDR_LBUILD]): both tails are queued then, one of them leaves at once.
+    const char *benv = getenv("IVX_BUILD");
+    const bool lb_try = n >= LB_MIN_ROWS && n <= LB_MAX_ROWS && !(benv && !strcmp(benv, "global"));
+    const u32 lb_tiles = lb_try ? (u32)((n + LB_TILE - 1) / LB_TILE) : 0u;
+    // (the two tails share their scratch: cell ids | the rows grouped by region, ranks | the tiles' region tables)
+    IVX_TRY(ctx->get_scratch(WS_GRID2, (n ? n : 1) * (lb_try ? sizeof(ivx_ent) : sizeof(u32)), (void **)&cellid));
+    const size_t tabbytes = (size_t)lb_tstride(lb_tiles) * LB_STRIDE * sizeof(u32);
+    IVX_TRY(ctx->get_scratch(WS_T9, (n ? n : 1) * sizeof(u32) > tabbytes ? (n ? n : 1) * sizeof(u32) : tabbytes, (void **)&rank));
     errflag = (u32 *)(ctx->d_scalars + 8);
     u32 *lenhist = (u32 *)(ctx->d_scalars + 32);                        // 33 counters
 
-    const ivx_zero_ranges zr{{errflag, lenhist, hdr}, {1u, 34u, (u32)HDR_WORDS}};     // cleared by the key-statistics' first kernel
+    ivx_zero_ranges zr{{errflag, lenhist, hdr}, {1u, 34u, (u32)HDR_WORDS}};     // cleared by the key-statistics' first kernel
     // IVX_FILTER=0: no occupancy bitmap; =force: whenever it fits (tests); default: when it would reject most probe rows
     const char *fenv = getenv("IVX_FILTER");
     const int filter_mode = !fenv ? 1 : !strcmp(fenv, "0") ? 0 : !strcmp(fenv, "force") ? 2 : 1;
-    if (filter_mode) IVX_HIP(ctx, hipMemsetAsync(fbits, 0, fwords * sizeof(u32), st));
+    static_assert((IVX_FBITS_MAX / 32 + 4) % 4 == 0, "the bitmap is cleared in 16-byte words");
+    if (filter_mode) { zr.big = (uint4 *)fbits; zr.nbig = (u32)(fwords / 4); }     // ... and so is the bitmap, by that kernel's extra workgroups
     IVX_TRY(ivx_keystats_len(ctx, key, s, n, nkeys, kmin, kmax, kcnt, errflag, 1u, e, lenhist, &zr));   // + the length classes for the layout
     // (every row's atomic returns a value, its loads depend on nothing: a row or two per thread, not a loop of eight round trips)
     const u32 grid = ivx_stream_grid(n, BT * 2, 16384);
-    hipLaunchKernelGGL(k_join_layout, dim3(1), dim3(1024), 0, st, kmin, kmax, kcnt, nkeys, n, origin, span, lbase, hdr, maxcells, kreg, rkey, (const u32 *)lenhist, (u32)(regcap - 1), fbase, filter_mode);
+    hipLaunchKernelGGL(k_join_layout, dim3(1), dim3(1024), 0, st, kmin, kmax, kcnt, nkeys, n, origin, span, lbase, hdr, maxcells, kreg, rkey, (const u32 *)lenhist, (u32)(regcap - 1), fbase, filter_mode, lb_try ? 1 : 0, (const u32 *)errflag);
     if (filter_mode) hipLaunchKernelGGL(k_join_filter, dim3(grid), dim3(BT), 0, st, key, s, e, n, nkeys, (const i32 *)origin, (const u32 *)span, (const u32 *)fbase, (const u32 *)hdr, fbits);
     // routing regions for the per-row modes of build sides that outgrow the LDS-slice pipeline (more than 1023 regions
     // takes > 5 M rows); count / coverage / nearest indexes route on their rank grids
@@ -588,22 +753,48 @@ ivx_status ivx_join_build(ivx_ctx *ctx, ivx_index *ix, const u32 *key, const i32
     // the aux stream and the caller gets its index back as soon as the layout has reached the host.
     overlap = overlap && ctx->overlap && ctx->aux != nullptr && !want_route && n >= (1u << 16);
     hipStream_t tail_st = st;
+    // an error exit behind the fork must not hand the index's buffers and the scratch back while the aux stream may still
+    // write them (ivx_index_build frees the index at once): such an exit waits for that stream first
+    struct TailGuard {
+        ivx_ctx *c; bool armed = false;
+        ~TailGuard() { if (armed) (void)hipStreamSynchronize(c->aux); }
+    } guard{ctx};
+    // which tails to queue: both, with the device's word deciding (hdr[HDR_LBUILD]) -- or, where the host has that word
+    // before it queues them, the one that applies
+    bool q_lds = lb_try, q_global = true;
     if (overlap) {
         ctx->join_tail();                                       // (an earlier tail may still read the scratch this one is about to write)
         IVX_HIP(ctx, hipEventRecord(ctx->ev_fork, st));
         IVX_HIP(ctx, hipStreamWaitEvent(ctx->aux, ctx->ev_fork, 0));
         tail_st = ctx->aux;
+        // the words the caller waits for are final: the one synchronisation of a build comes before the tail is queued,
+        // which then is the tail the layout asks for and nothing else, and a bad key id ends the build with nothing in flight
+        IVX_HIP(ctx, hipMemcpyAsync(ctx->h_scalars + 32, hdr, HDR_WORDS * sizeof(u32), hipMemcpyDeviceToHost, st));
+        IVX_HIP(ctx, hipStreamSynchronize(st));
+        if (((const u32 *)(ctx->h_scalars + 32))[HDR_BADKEY]) return ctx->fail(IVX_ERR_INVALID, "build key id >= n_keys");
+        q_lds = lb_try && ((const u32 *)(ctx->h_scalars + 32))[HDR_LBUILD] != 0;
+        q_global = !q_lds;
+        guard.armed = true;
     }
-    IVX_HIP(ctx, hipMemsetAsync(binstart, 0, (maxcells + 1) * sizeof(u32), tail_st));    // (8 MB per million rows: part of the tail, not of what the caller waits for)
-    hipLaunchKernelGGL(k_join_count, dim3(grid), dim3(BT), 0, tail_st, key, s, e, n, nkeys, origin, lbase, hdr, binstart, cellid, rank);
-    {
+    if (q_lds)
+        hipLaunchKernelGGL(k_lbuild_tiles, dim3(lb_tiles), dim3(LB_T), 0, tail_st, key, s, e, n, nkeys, (const i32 *)origin, (const u32 *)kreg, hdr,
+                           (ivx_ent *)cellid, rank, lb_tstride(lb_tiles), binstart, maxcells + 1);
+    else
+        IVX_HIP(ctx, hipMemsetAsync(binstart, 0, (maxcells + 1) * sizeof(u32), tail_st));    // (8 MB per million rows: part of the tail, not of what the caller waits for)
+    if (q_global) {
+        hipLaunchKernelGGL(k_join_count, dim3(grid), dim3(BT), 0, tail_st, key, s, e, n, nkeys, origin, lbase, hdr, binstart, cellid, rank);
         const hipStream_t keep = ctx->stream;
         ctx->stream = tail_st;                                  // (the scan launches on the context's stream)
-        const ivx_status sst = ivx_scan_exclusive_u32(ctx, binstart, maxcells + 1);
+        const ivx_status sst = ivx_scan_exclusive_u32(ctx, binstart, maxcells + 1, hdr + HDR_LBUILD);
         ctx->stream = keep;
         IVX_TRY(sst);
+        hipLaunchKernelGGL(k_join_scatter, dim3(grid), dim3(BT), 0, tail_st, s, e, n, (const u32 *)binstart, (const u32 *)cellid, (const u32 *)rank, ent, (const u32 *)hdr);
     }
-    hipLaunchKernelGGL(k_join_scatter, dim3(grid), dim3(BT), 0, tail_st, s, e, n, (const u32 *)binstart, (const u32 *)cellid, (const u32 *)rank, ent);
+    if (q_lds) {
+        const u32 rgrid = regcap - 1 < IVX_MAXREG_WIDE ? (u32)(regcap - 1) : (u32)IVX_MAXREG_WIDE;
+        hipLaunchKernelGGL(k_lbuild_regions, dim3(rgrid), dim3(LB_T), 0, tail_st, (const i32 *)origin, (const u32 *)span, (const u32 *)lbase, (const u32 *)kreg,
+                           (const u32 *)rkey, (const u32 *)hdr, nkeys, (const ivx_ent *)cellid, (const u32 *)rank, lb_tiles, lb_tstride(lb_tiles), binstart, ent);
+    }
     hipLaunchKernelGGL(k_join_regdesc, dim3((u32)((regcap + 255) / 256)), dim3(256), 0, tail_st, origin, span, lbase, hdr, kreg, rkey, binstart, rdesc);
     IVX_HIP(ctx, hipGetLastError());
     if (overlap) {
@@ -615,17 +806,19 @@ ivx_status ivx_join_build(ivx_ctx *ctx, ivx_index *ix, const u32 *key, const i32
     }
     if (want_route) IVX_TRY(ivx_route_view_build(ctx, ix, origin, span, kcnt));
 
-    // key ids are validated on the device; surface the flag (one small D2H).  (With the tail overlapped the header copy
+    // key ids are validated on the device; the flag comes with the header (one small D2H).  (With the tail overlapped the header copy
     // carries the layout's words -- regions, bitmap, packed rows -- but not yet the two flags the tail sets.)
-    IVX_HIP(ctx, hipMemcpyAsync(ctx->h_scalars + 8, errflag, sizeof(u32), hipMemcpyDeviceToHost, st));
-    IVX_HIP(ctx, hipMemcpyAsync(ctx->h_scalars + 32, hdr, HDR_WORDS * sizeof(u32), hipMemcpyDeviceToHost, st));
-    IVX_HIP(ctx, hipStreamSynchronize(st));
-    if (*(u32 *)(ctx->h_scalars + 8)) return ctx->fail(IVX_ERR_INVALID, "build key id >= n_keys");
+    if (!overlap) {
+        IVX_HIP(ctx, hipMemcpyAsync(ctx->h_scalars + 32, hdr, HDR_WORDS * sizeof(u32), hipMemcpyDeviceToHost, st));
+        IVX_HIP(ctx, hipStreamSynchronize(st));
+    }
+    if (((const u32 *)(ctx->h_scalars + 32))[HDR_BADKEY]) return ctx->fail(IVX_ERR_INVALID, "build key id >= n_keys");
     ix->jv_nreg = ((const u32 *)(ctx->h_scalars + 32))[HDR_NREG];
     ix->jv_filter = ((const u32 *)(ctx->h_scalars + 32))[HDR_FG] != 0xFFFFFFFFu;
     ix->jv_pk24 = ((const u32 *)(ctx->h_scalars + 32))[HDR_PK24] != 0;
     ix->jv_fast = ((const u32 *)(ctx->h_scalars + 32))[HDR_SLOW] == 0 && ix->jv_nreg > 0;
     if (want_route) ivx_route_view_ready(ctx, ix);
+    guard.armed = false;                                        // (the tail is the index's from here: `ready`, tail_ev)
 
     ix->jv.origin = origin; ix->jv.span = span; ix->jv.kcnt = kcnt; ix->jv.lbase = lbase;
     ix->jv.binstart = binstart; ix->jv.ent = ent; ix->jv.hdr = hdr; ix->jv.nkeys = nkeys;

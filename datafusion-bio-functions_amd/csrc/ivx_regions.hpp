@@ -49,7 +49,8 @@ ivx_status ivx_route_flat(ivx_ctx *ctx, const JoinIndexView &jv, const u32 *key,
                           u32 ndig, bool ids16, u32 max_tiles, ivx_routed *R);
 // one-pass partition into region pages (nreg <= IVX_MAXREG_WIDE).  rowval (per-row-value consumers; always packed, nreg <=
 // IVX_MAXREG): also vtab for the un-permute.  lean: the consumer may run the lean kernels (rest lists, chunk table)
-struct ivx_paged_opts { bool filter, packed, rowval, lean; u32 adj; };
+// zero2 (nullable): two 64-bit words of the caller's that the pass's clearing kernel zeroes on the way (a memset launch less)
+struct ivx_paged_opts { bool filter, packed, rowval, lean; u32 adj; u64 *zero2 = nullptr; };
 ivx_status ivx_route_paged(ivx_ctx *ctx, const JoinIndexView &jv, u32 nreg, const u32 *key, const i32 *s, const i32 *e, u64 n,
                            const ivx_paged_opts &o, ivx_routed *R);
 // more than IVX_MAXREG_WIDE regions: two partition passes (super-region, then region inside it) and a global region table

@@ -1324,14 +1324,18 @@ ivx_status probe_pairs(ivx_ctx *ctx, const JoinIndexView &jv, u32 nreg, int mode
 
 ivx_status ivx_join_probe_regions(ivx_ctx *ctx, const JoinIndexView &jv, u32 nreg, int mode,
                                   const u32 *key, const i32 *s, const i32 *e, u64 n,
-                                  u32 *ob, u32 *op, u64 cap, u64 *d_cursor, bool planned, bool has_filter, bool pk24, int fast, hipEvent_t ready)
+                                  u32 *ob, u32 *op, u64 cap, u64 *d_cursor, bool planned, bool has_filter, bool pk24, int fast, hipEvent_t ready, bool clear_cursor)
 {
     // `ready` (an index whose build tail may still run on another stream): the routing pass reads only what was final
     // before that tail started; the probe kernels come behind the event
     auto wait_ready = [&]() -> ivx_status { if (ready) { IVX_HIP(ctx, hipStreamWaitEvent(ctx->stream, ready, 0)); ready = nullptr; } return IVX_OK; };
+    // clear_cursor: d_cursor[0..1] (pair cursor, fault flags) are not zeroed yet -- the one-pass routing clears them with its
+    // own counters; every other way through here does it now
+    const RegionKnobs K = region_knobs();
+    const bool paged_route = !planned && n != 0 && nreg <= IVX_MAXREG_WIDE && !K.two_pass;
+    if (clear_cursor && !paged_route) IVX_HIP(ctx, hipMemsetAsync(d_cursor, 0, 2 * sizeof(u64), ctx->stream));
     if (n == 0) return wait_ready();
     ivx_join_plan &pl = ctx->join_plan;
-    const RegionKnobs K = region_knobs();
     ivx_routed R;
     if (planned) R = pl.rows;               // routed by the count call that sized this fill call (which left `unsorted` as it is)
     else {
@@ -1343,7 +1347,7 @@ ivx_status ivx_join_probe_regions(ivx_ctx *ctx, const JoinIndexView &jv, u32 nre
             IVX_TRY(ivx_route_flat(ctx, jv, key, s, e, n, 0u, nreg > IVX_MAXREG ? 1024u : 256u, false, 4, &R));
         } else {
             // 8-byte routed rows whenever a region's coordinates fit 24 bits
-            IVX_TRY(ivx_route_paged(ctx, jv, nreg, key, s, e, n, ivx_paged_opts{has_filter && !K.filter_off, pk24 && !K.pack_off, false, fast != 0, 0u}, &R));
+            IVX_TRY(ivx_route_paged(ctx, jv, nreg, key, s, e, n, ivx_paged_opts{has_filter && !K.filter_off, pk24 && !K.pack_off, false, fast != 0, 0u, clear_cursor ? d_cursor : nullptr}, &R));
         }
         if (mode == JP_COUNT) { pl.rows = R; pl.valid = true; }     // leave the routed rows for the fill call (ivx_capi.hip fills in whose they are)
     }

@@ -606,6 +606,18 @@ __global__ __launch_bounds__(1024) void k_chunk_bounds(const u32 *__restrict__ r
     if (t == 0) cfirst[nreg] = tot;
 }
 
+// what the one-pass partition wants zeroed before it starts, in one launch: its counters, the page table and (nullable) two
+// words of the caller's
+__global__ __launch_bounds__(256) void k_route_clear(u32 *__restrict__ ctl, u32 nctl, u32 *__restrict__ ptab, u64 nptab, u64 *zero2)
+{
+    const u64 i = (u64)blockIdx.x * 256 + threadIdx.x, step = (u64)gridDim.x * 256;
+    if (i < nctl) ctl[i] = 0;                                           // (nctl < 256 * gridDim.x: the host sizes the grid)
+    if (i < 2 && zero2) zero2[i] = 0;
+    uint4 *p4 = (uint4 *)ptab;                                          // (scratch: 256-byte aligned)
+    for (u64 j = i; j < nptab / 4; j += step) p4[j] = make_uint4(0u, 0u, 0u, 0u);
+    if (i < (nptab & 3)) ptab[(nptab & ~3ull) + i] = 0;
+}
+
 // rows one partition workgroup takes: 1, 2 or 4 tiles, so that mid-size batches still spread over all CUs
 static inline u32 part_chunk(u64 n, u32 max_tiles = 4) { const u32 t = n >= (16u << 20) ? 4u : n >= (4u << 20) ? 2u : 1u; return (u32)PA_TILE * (t < max_tiles ? t : max_tiles); }
 
@@ -941,8 +953,13 @@ ivx_status ivx_route_paged(ivx_ctx *ctx, const JoinIndexView &jv, u32 nreg, cons
     else if (o.lean) IVX_TRY(ctx->get_scratch(WS_T1, (size_t)fp_max_batches(n, nreg) * sizeof(FpRest) + (size_t)(n + 64) * sizeof(u64), &rest));
     if (rest) { R->rest = (FpRest *)rest; R->rest_rows = (u64 *)(R->rest + fp_max_batches(n, nreg)); }
     if (o.rowval && o.lean) { IVX_TRY(ctx->get_scratch(WS_T3, (size_t)(n + 64) * sizeof(u64), (void **)&R->rest_rows)); R->slots |= 1ull << WS_T3; }
-    IVX_HIP(ctx, hipMemsetAsync(ctl, 0, offsetof(ivx_route_ctl, rfirst), st));
-    IVX_HIP(ctx, hipMemsetAsync(ptab, 0, (size_t)nreg * pstride * sizeof(u32), st));
+    {
+        const u32 nctl = (u32)(offsetof(ivx_route_ctl, rfirst) / sizeof(u32));
+        const u64 nptab = (u64)nreg * pstride;
+        u64 cg = (nptab / 4 + 256 * 8 - 1) / (256 * 8);                 // eight 16-byte stores a thread
+        cg = cg < (nctl + 255) / 256 ? (nctl + 255) / 256 : (cg > 1024 ? 1024 : cg);
+        hipLaunchKernelGGL(k_route_clear, dim3((u32)cg), dim3(256), 0, st, (u32 *)ctl, nctl, ptab, nptab, o.zero2);
+    }
     const PageTab pt{ptab, (u32)pstride, lgpg};
     const u32 tiles = n >= (16u << 20) ? 4u : n >= (4u << 20) ? 2u : 1u;
     const u32 chunk1 = tile * tiles;

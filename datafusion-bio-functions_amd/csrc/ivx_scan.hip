@@ -11,5 +11,5 @@ struct SumOp {
 };
 }  // namespace
 
-ivx_status ivx_scan_exclusive_u32(ivx_ctx *ctx, u32 *data, u64 n) { return ivxscan::exclusive<SumOp<u32>>(ctx, data, n); }
+ivx_status ivx_scan_exclusive_u32(ivx_ctx *ctx, u32 *data, u64 n, const u32 *skip) { return ivxscan::exclusive<SumOp<u32>>(ctx, data, n, skip); }
 ivx_status ivx_scan_exclusive_u64(ivx_ctx *ctx, u64 *data, u64 n) { return ivxscan::exclusive<SumOp<unsigned long long>>(ctx, (unsigned long long *)data, n); }

@@ -51,9 +51,10 @@ __device__ __forceinline__ typename Op::T block_incl(typename Op::T v, typename 
 }
 
 template <class Op>
-__global__ __launch_bounds__(T_) void k_reduce(const typename Op::T *__restrict__ in, u64 n, typename Op::T *__restrict__ sums)
+__global__ __launch_bounds__(T_) void k_reduce(const typename Op::T *__restrict__ in, u64 n, typename Op::T *__restrict__ sums, const u32 *skip)
 {
     using T = typename Op::T;
+    if (skip && *skip) return;                              // (a scan queued for a path the device then did not take)
     __shared__ T lds[T_ / IVX_WAVE + 1];
     const u64 base = (u64)blockIdx.x * TILE_ + (u64)threadIdx.x * I_;
     T s = Op::identity();
@@ -67,9 +68,10 @@ __global__ __launch_bounds__(T_) void k_reduce(const typename Op::T *__restrict_
 
 // inclusive (INCL) or exclusive scan of the tile, seeded with offs[block] (exclusive prefix of earlier tiles)
 template <class Op, bool INCL>
-__global__ __launch_bounds__(T_) void k_apply(typename Op::T *__restrict__ data, u64 n, const typename Op::T *__restrict__ offs)
+__global__ __launch_bounds__(T_) void k_apply(typename Op::T *__restrict__ data, u64 n, const typename Op::T *__restrict__ offs, const u32 *skip)
 {
     using T = typename Op::T;
+    if (skip && *skip) return;
     __shared__ T lds[T_ / IVX_WAVE + 1];
     const u64 base = (u64)blockIdx.x * TILE_ + (u64)threadIdx.x * I_;
     T v[I_];
@@ -99,9 +101,10 @@ __global__ __launch_bounds__(T_) void k_apply(typename Op::T *__restrict__ data,
 }
 
 template <class Op, bool INCL>
-__global__ __launch_bounds__(T_) void k_single(typename Op::T *__restrict__ data, u64 n)
+__global__ __launch_bounds__(T_) void k_single(typename Op::T *__restrict__ data, u64 n, const u32 *skip)
 {
     using T = typename Op::T;
+    if (skip && *skip) return;
     __shared__ T lds[T_ / IVX_WAVE + 1];
     __shared__ T edge[T_ / IVX_WAVE];
     T carry = Op::identity();
@@ -130,20 +133,20 @@ __global__ __launch_bounds__(T_) void k_single(typename Op::T *__restrict__ data
 }
 
 template <class Op, bool INCL>
-ivx_status scan_rec(ivx_ctx *ctx, typename Op::T *data, u64 n, int level, int slot0)
+ivx_status scan_rec(ivx_ctx *ctx, typename Op::T *data, u64 n, int level, int slot0, const u32 *skip = nullptr)
 {
     using T = typename Op::T;
     if (n == 0) return IVX_OK;
     if (n <= 4 * TILE_ || level >= 2) {
-        hipLaunchKernelGGL((k_single<Op, INCL>), dim3(1), dim3(T_), 0, ctx->stream, data, n);
+        hipLaunchKernelGGL((k_single<Op, INCL>), dim3(1), dim3(T_), 0, ctx->stream, data, n, skip);
         return IVX_OK;
     }
     const u64 nblk = (n + TILE_ - 1) / TILE_;
     T *sums;
     IVX_TRY(ctx->get_scratch(slot0 + level, nblk * sizeof(T), (void **)&sums));
-    hipLaunchKernelGGL((k_reduce<Op>), dim3((u32)nblk), dim3(T_), 0, ctx->stream, (const T *)data, n, sums);
-    IVX_TRY((scan_rec<Op, false>(ctx, sums, nblk, level + 1, slot0)));     // block offsets are always exclusive
-    hipLaunchKernelGGL((k_apply<Op, INCL>), dim3((u32)nblk), dim3(T_), 0, ctx->stream, data, n, (const T *)sums);
+    hipLaunchKernelGGL((k_reduce<Op>), dim3((u32)nblk), dim3(T_), 0, ctx->stream, (const T *)data, n, sums, skip);
+    IVX_TRY((scan_rec<Op, false>(ctx, sums, nblk, level + 1, slot0, skip)));     // block offsets are always exclusive
+    hipLaunchKernelGGL((k_apply<Op, INCL>), dim3((u32)nblk), dim3(T_), 0, ctx->stream, data, n, (const T *)sums, skip);
     return IVX_OK;
 }
 
@@ -210,6 +213,6 @@ ivx_status inclusive_f(ivx_ctx *ctx, In in, Out out, u64 n)
 template <class Op>
 ivx_status inclusive(ivx_ctx *ctx, typename Op::T *data, u64 n) { return scan_rec<Op, true>(ctx, data, n, 0, WS_SCAN0); }
 template <class Op>
-ivx_status exclusive(ivx_ctx *ctx, typename Op::T *data, u64 n) { return scan_rec<Op, false>(ctx, data, n, 0, WS_SCAN0); }
+ivx_status exclusive(ivx_ctx *ctx, typename Op::T *data, u64 n, const u32 *skip = nullptr) { return scan_rec<Op, false>(ctx, data, n, 0, WS_SCAN0, skip); }
 
 }  // namespace ivxscan

@@ -31,7 +31,7 @@ SYMBOLS = [
 ]
 
 # slots of ivx_index_layout (include/ivx.h IVX_LAYOUT_*), in order
-LAYOUT_SLOTS = ["kind", "sh0", "nlev", "levrows", "rcells", "rcs", "nreg", "pk24", "slow", "fg", "fbits", "nroute_nreg"]
+LAYOUT_SLOTS = ["kind", "sh0", "nlev", "levrows", "rcells", "rcs", "nreg", "pk24", "slow", "fg", "fbits", "nroute_nreg", "lbuild"]
 
 
 class Metrics(C.Structure):

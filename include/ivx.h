@@ -165,7 +165,8 @@ enum {
     IVX_LAYOUT_FG = 9,          /* log2 of the occupancy bitmap's block width, or 0xFFFFFFFF: no bitmap */
     IVX_LAYOUT_FBITS = 10,      /* the bitmap's size in bits */
     IVX_LAYOUT_NROUTE_NREG = 11,/* regions of the routing view of big per-row probes (0: none) */
-    IVX_LAYOUT_WORDS = 12
+    IVX_LAYOUT_LBUILD = 12,     /* 1: the build sorted every region's rows in LDS; 0: the global counting sort (IVX_BUILD=global) */
+    IVX_LAYOUT_WORDS = 13
 };
 ivx_status ivx_index_layout(ivx_ctx *ctx, const ivx_index *ix, uint32_t *out, uint32_t n_out);
 
