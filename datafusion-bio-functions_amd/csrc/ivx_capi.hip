@@ -1102,13 +1102,20 @@ extern "C" ivx_status ivx_take_utf8(ivx_ctx *ctx, int mem, int large, const void
     IVX_TRY(stage_out(ctx, mem, WS_OUT_B, out_data, data_cap, &dodata));
     IVX_TRY(stage_out(ctx, mem, WS_OUT_C, out_valid, n, &dov));
     u64 total = 0;
+    ivx_status st;
     {
         KernelTimer t(ctx);
-        ivx_status st = ivx_take_utf8_device(ctx, large, doff, ddata, n_src, dvalid, didx, n, dooff, dodata, data_cap, &total, dov);
+        st = ivx_take_utf8_device(ctx, large, doff, ddata, n_src, dvalid, didx, n, dooff, dodata, data_cap, &total, dov);
         *data_bytes = total;
-        if (st != IVX_OK) return st;
     }
+    // a short data buffer leaves the offsets and out_valid final (the device has written them): they go out as in device mode
+    if (st != IVX_OK && st != IVX_ERR_CAPACITY) return st;
     IVX_TRY(copy_out(ctx, mem, (u8 *)out_offsets, dooff, (n + 1) * ow));
+    if (st == IVX_ERR_CAPACITY) {
+        IVX_TRY(copy_out(ctx, mem, out_valid, dov, n));
+        if (mem == IVX_MEM_HOST) IVX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        return st;
+    }
     if (out_data) IVX_TRY(copy_out(ctx, mem, out_data, dodata, total));
     IVX_TRY(copy_out(ctx, mem, out_valid, dov, n));
     if (mem == IVX_MEM_HOST) IVX_HIP(ctx, hipStreamSynchronize(ctx->stream));

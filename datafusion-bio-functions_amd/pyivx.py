@@ -510,3 +510,60 @@ class Ctx:
             st = lib().ivx_take_utf8(*head, _ptr(out_off), _ptr(out_data), C.c_uint64(cap), C.byref(need), _ptr(valid))
         self._chk(st)
         return out_off[: n + 1], out_data[: need.value], (valid[:n] if valid is not None else None)
+
+    def take_bits(self, src_bits, n_src, idx, src_valid_bits=None, want_valid=True):
+        """src_bits: uint8 bitmap (LSB first, bit offset 0) of a Boolean column of n_src rows.
+        -> (out_bits u8 [(n+7)/8], valid u8 or None)"""
+        dev = _is_torch(src_bits)
+        if _is_torch(idx) != dev:
+            raise ValueError("mix of host and device buffers in one call")
+        if dev:
+            import torch
+            assert src_bits.is_contiguous() and idx.is_contiguous()
+            n = int(idx.numel())
+            mk = lambda m: torch.empty(max(m, 1), dtype=torch.uint8, device=src_bits.device)
+            svb = src_valid_bits
+        else:
+            src_bits = np.ascontiguousarray(src_bits, np.uint8); idx = np.ascontiguousarray(idx, np.uint32)
+            n = len(idx)
+            mk = lambda m: np.empty(max(m, 1), np.uint8)
+            svb = None if src_valid_bits is None else np.ascontiguousarray(src_valid_bits, np.uint8)
+        nb = (n + 7) // 8
+        out = mk(nb)
+        valid = mk(n) if want_valid else None
+        self._chk(lib().ivx_take_bits(self.h, C.c_int(MEM_DEVICE if dev else MEM_HOST), _ptr(src_bits), C.c_uint64(int(n_src)), _ptr(svb),
+                                       _ptr(idx), C.c_uint64(n), _ptr(out), _ptr(valid)))
+        return out[:nb], (valid[:n] if valid is not None else None)
+
+    def take_view(self, views, data_bufs, idx, src_valid_bits=None, want_valid=True):
+        """views: uint8 [n_src, 16] (Utf8View / BinaryView); data_bufs: list of the variadic uint8 data buffers.
+        Sizes first, then fills.  -> (out_views u8 [n, 16], out_data u8 = the one data buffer of the output, valid u8 or None)"""
+        dev = _is_torch(views)
+        if _is_torch(idx) != dev or any(_is_torch(b) != dev for b in data_bufs):
+            raise ValueError("mix of host and device buffers in one call")
+        if dev:
+            import torch
+            assert views.is_contiguous() and idx.is_contiguous() and all(b.is_contiguous() for b in data_bufs)
+            n_src, n = int(views.numel()) // 16, int(idx.numel())
+            sizes = [int(b.numel()) for b in data_bufs]
+            mk = lambda *shape: torch.empty(shape, dtype=torch.uint8, device=views.device)
+            svb = src_valid_bits
+        else:
+            views = np.ascontiguousarray(views, np.uint8); idx = np.ascontiguousarray(idx, np.uint32)
+            data_bufs = [np.ascontiguousarray(b, np.uint8) for b in data_bufs]
+            n_src, n = views.size // 16, len(idx)
+            sizes = [len(b) for b in data_bufs]
+            mk = lambda *shape: np.empty(shape, np.uint8)
+            svb = None if src_valid_bits is None else np.ascontiguousarray(src_valid_bits, np.uint8)
+        nb = len(data_bufs)
+        table = (C.c_void_p * max(nb, 1))(*[_ptr(b).value for b in data_bufs])        # host table of the buffers' pointers, in either mode
+        nbytes = (C.c_uint64 * max(nb, 1))(*sizes)
+        valid = mk(max(n, 1)) if want_valid else None
+        need = C.c_uint64(0)
+        head = (self.h, C.c_int(MEM_DEVICE if dev else MEM_HOST), _ptr(views), table, nbytes, C.c_uint32(nb), C.c_uint64(n_src), _ptr(svb),
+                _ptr(idx), C.c_uint64(n))
+        self._chk(lib().ivx_take_view(*head, None, None, C.c_uint64(0), C.byref(need), _ptr(valid)))
+        cap = max(need.value, 1)
+        out_views, out_data = mk(max(n, 1), 16), mk(cap)
+        self._chk(lib().ivx_take_view(*head, _ptr(out_views), _ptr(out_data), C.c_uint64(cap), C.byref(need), _ptr(valid)))
+        return out_views[:n], out_data[: need.value], (valid[:n] if valid is not None else None)

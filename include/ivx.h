@@ -313,7 +313,9 @@ ivx_status ivx_take_bits(ivx_ctx *ctx, int mem, const uint8_t *src_bits, uint64_
 
 /*      Utf8 / Binary (large = 0, int32 offsets) and LargeUtf8 / LargeBinary (large = 1, int64).
  *      out_offsets[n+1] is written whenever given; *data_bytes always returns the bytes needed.
- *      out_data = NULL sizes only; data_cap < *data_bytes is IVX_ERR_CAPACITY. */
+ *      out_data = NULL sizes only; data_cap < *data_bytes is IVX_ERR_CAPACITY, which still leaves
+ *      out_offsets and out_valid written, in either memory mode.  More than 2^31-1 bytes with
+ *      int32 offsets is IVX_ERR_INVALID and writes no offsets. */
 ivx_status ivx_take_utf8(ivx_ctx *ctx, int mem, int large, const void *offsets, const uint8_t *data, uint64_t n_src,
                          uint64_t src_data_bytes, const uint8_t *src_valid_bits, const uint32_t *idx, uint64_t n,
                          void *out_offsets, uint8_t *out_data, uint64_t data_cap, uint64_t *data_bytes,
