@@ -25,6 +25,8 @@ _LIB_PATH = os.path.join(_HERE, "lib", "libbio_ranges_hip.so")
 DEFAULT_COLS = ("contig", "pos_start", "pos_end")
 WEAK, STRICT = 0, 1
 JOIN_INNER, JOIN_RIGHT_SEMI, JOIN_RIGHT_ANTI = 0, 1, 2
+# (3 = BRH_JOIN_NEAREST, join stream only)  The build-side and outer types: SQL semantics over the build side's match marks
+JOIN_LEFT_SEMI, JOIN_LEFT_ANTI, JOIN_LEFT, JOIN_RIGHT, JOIN_FULL = 4, 5, 6, 7, 8
 
 
 class _ArrowSchema(C.Structure):
@@ -174,6 +176,8 @@ class Session:
     # ---- IntervalJoinExec (the SQL range join), `build` = the SQL join's left table
     def interval_join(self, build, probe, cols_build=DEFAULT_COLS, cols_probe=DEFAULT_COLS, join_type=JOIN_INNER,
                       strict_predicate=False, nearest_algorithm=False):
+        """-> (build_idx, probe_idx) UInt32 arrays.  JOIN_RIGHT_SEMI / _ANTI: probe_idx only; JOIN_LEFT_SEMI / _ANTI: build_idx
+        only, ascending; JOIN_LEFT / _RIGHT / _FULL: the Inner pairs, then the unmatched rows with a NULL on the other side."""
         B, P = _Exported(build), _Exported(probe)
         (ba, bs), (pa_, ps) = _out(), _out()
         try:
@@ -198,7 +202,9 @@ class Session:
     def join_stream(self, build, cols_build=DEFAULT_COLS, cols_probe=DEFAULT_COLS, strict_predicate=False, coalesce_rows=0,
                     join_type="inner", max_output_rows=0):
         """IntervalJoinStream as a push interface: index `build` once, then push probe batches; see JoinStream.
-        join_type: "inner" | "right_semi" | "right_anti" | "nearest" (Algorithm::CoitreesNearest);
+        join_type: "inner" | "right_semi" | "right_anti" | "nearest" (Algorithm::CoitreesNearest) | "left_semi" | "left_anti" |
+        "left" | "right" | "full" (these five: finish() ends with one result of n_batches = 0 that carries the build-side rows;
+        max_output_rows must be 0);
         max_output_rows: 0 = one result per group, N = the low-memory stream's output budget, "env" = the reference's
         default (BIO_MAX_OUTPUT_BATCH_SIZE or 100000)."""
         return JoinStream(self, build, cols_build, cols_probe, strict_predicate, coalesce_rows, join_type, max_output_rows)
@@ -312,7 +318,7 @@ class JoinStream:
     first_batch, n_batches, group_done, build_idx, probe_idx (rows counted over the group's concatenated batches),
     batch_offsets."""
 
-    JOIN_TYPES = {"inner": 0, "right_semi": 1, "right_anti": 2, "nearest": 3}
+    JOIN_TYPES = {"inner": 0, "right_semi": 1, "right_anti": 2, "nearest": 3, "left_semi": 4, "left_anti": 5, "left": 6, "right": 7, "full": 8}
 
     def __init__(self, session, build, cols_build, cols_probe, strict_predicate, coalesce_rows, join_type="inner", max_output_rows=0):
         self.session = session

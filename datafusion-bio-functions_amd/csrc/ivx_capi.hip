@@ -710,6 +710,115 @@ extern "C" ivx_status ivx_probe_exists(ivx_ctx *ctx, const ivx_index *ix, int me
     return overlap_common(ctx, ix, mem, JP_EXISTS, key, start, end, n, nullptr, exists, nullptr, nullptr, 0, nullptr);
 }
 
+// ---------------------------------------------------------------- a3'': build-side match marks
+
+namespace {
+
+// the bitmap a mark call's kernels OR into: the caller's own words (device mode), or a zeroed scratch bitmap that
+// marks_or_back copies to the host and ORs into the caller's words (the caller's set bits survive)
+ivx_status marks_stage(ivx_ctx *ctx, int mem, u32 *caller, u64 nw, u32 **dev)
+{
+    if (mem == IVX_MEM_DEVICE) { *dev = caller; return IVX_OK; }
+    IVX_TRY(ctx->get_scratch(WS_OUT_A, (size_t)nw * sizeof(u32), (void **)dev));
+    if (nw) IVX_HIP(ctx, hipMemsetAsync(*dev, 0, (size_t)nw * sizeof(u32), ctx->stream));
+    return IVX_OK;
+}
+
+ivx_status marks_or_back(ivx_ctx *ctx, int mem, u32 *caller, const u32 *dev, u64 nw)
+{
+    if (mem == IVX_MEM_DEVICE || nw == 0) return IVX_OK;
+    std::vector<u32> got;
+    try { got.resize((size_t)nw); } catch (const std::bad_alloc &) { return ctx->fail(IVX_ERR_OOM, "host allocation failed"); }
+    IVX_HIP(ctx, hipMemcpyAsync(got.data(), dev, (size_t)nw * sizeof(u32), hipMemcpyDeviceToHost, ctx->stream));
+    IVX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (u64 w = 0; w < nw; w++) caller[w] |= got[w];
+    return IVX_OK;
+}
+
+// Beside overlap_common: the same two ways through the index, the match recorded by BUILD row.  Big batches over a lean
+// index (the form ivx_rowval_probe_regions runs k_rv_fast on) take the region kernel; everything else the direct one.
+ivx_status mark_common(ivx_ctx *ctx, const ivx_index *ix, int mem, const u32 *key, const i32 *start, const i32 *end, u64 n, u32 *marks)
+{
+    IVX_TRY(check_probe_args(ctx, ix, IVX_KIND_OVERLAP, mem, start, end, n));       // (orders the stream behind a build tail, too)
+    if (n && ix->n && !marks) return ctx->fail(IVX_ERR_INVALID, "null mark bitmap");
+    CallMetrics cm(ctx, false, n);
+    ctx->join_plan.valid = false;                           // as any other call between a count call and its fill
+    const u64 nw = (ix->n + 31) / 32;
+    if (n == 0 || nw == 0) return IVX_OK;
+    // thresholds and override of overlap_common's per-row branch
+    bool regions = ix->jv_nreg > 0 && ix->jv_nreg <= IVX_MAXREG_WIDE && n >= (1u << 21);
+    if (const char *f = getenv("IVX_JOIN_PATH")) {
+        if (!strcmp(f, "direct")) regions = false;
+        else if (!strcmp(f, "regions")) regions = ix->jv_nreg > 0 && ix->jv_nreg <= IVX_MAXREG_WIDE;
+    }
+    const u32 *dk = nullptr; const i32 *ds = nullptr, *de = nullptr; u32 *dm = nullptr;
+    IVX_TRY(stage_in(ctx, mem, WS_IN_KEY, key, n, &dk));
+    IVX_TRY(stage_in(ctx, mem, WS_IN_START, start, n, &ds));
+    IVX_TRY(stage_in(ctx, mem, WS_IN_END, end, n, &de));
+    IVX_TRY(marks_stage(ctx, mem, marks, nw, &dm));
+    {
+        KernelTimer t(ctx);
+        bool took = false;
+        if (regions) IVX_TRY(ivx_mark_probe_regions(ctx, ix->jv, ix->jv_nreg, dk, ds, de, n, dm, ix->jv_filter, ix->jv_pk24, ix->jv_fast && !ix->jv_fast_unknown, &took));
+        if (!took) IVX_TRY(ivx_mark_probe(ctx, ix->jv, dk, ds, de, n, dm));
+    }
+    return marks_or_back(ctx, mem, marks, dm, nw);
+}
+
+}  // namespace
+
+extern "C" ivx_status ivx_probe_mark_build(ivx_ctx *ctx, const ivx_index *ix, int mem, const uint32_t *key,
+                                           const int32_t *start, const int32_t *end, uint64_t n, uint32_t *marks)
+{
+    return mark_common(ctx, ix, mem, key, start, end, n, marks);
+}
+
+extern "C" ivx_status ivx_bits_mark(ivx_ctx *ctx, int mem, const uint32_t *idx, uint64_t n, uint32_t *bits, uint64_t n_bits)
+{
+    if (!ctx) return IVX_ERR_INVALID;
+    if (mem != IVX_MEM_HOST && mem != IVX_MEM_DEVICE) return ctx->fail(IVX_ERR_INVALID, "bad mem");
+    if (n && !idx) return ctx->fail(IVX_ERR_INVALID, "bits_mark: null idx");
+    if (n_bits && !bits) return ctx->fail(IVX_ERR_INVALID, "bits_mark: null bitmap");
+    if (n_bits > 0xFFFFFFFFull) return ctx->fail(IVX_ERR_INVALID, "bits_mark: bitmap exceeds UInt32 index capacity");
+    if (n == 0) return IVX_OK;
+    IVX_HIP(ctx, hipSetDevice(ctx->device));
+    const u64 nw = (n_bits + 31) / 32;
+    const u32 *didx; u32 *dbits;
+    IVX_TRY(stage_in(ctx, mem, WS_IN_KEY, idx, n, &didx));
+    IVX_TRY(marks_stage(ctx, mem, bits, nw, &dbits));
+    {
+        KernelTimer t(ctx);
+        IVX_TRY(ivx_bits_mark_device(ctx, didx, n, dbits, n_bits));
+    }
+    return marks_or_back(ctx, mem, bits, dbits, nw);
+}
+
+extern "C" ivx_status ivx_bits_select(ivx_ctx *ctx, int mem, const uint32_t *bits, uint64_t n_bits, int want_set,
+                                      uint32_t *out, uint64_t cap, uint64_t *n_out)
+{
+    if (!ctx) return IVX_ERR_INVALID;
+    if (!n_out) return ctx->fail(IVX_ERR_INVALID, "null n_out");
+    *n_out = 0;
+    if (mem != IVX_MEM_HOST && mem != IVX_MEM_DEVICE) return ctx->fail(IVX_ERR_INVALID, "bad mem");
+    if (n_bits && !bits) return ctx->fail(IVX_ERR_INVALID, "bits_select: null bitmap");
+    if (cap && !out) return ctx->fail(IVX_ERR_INVALID, "bits_select: null out");
+    if (n_bits > 0xFFFFFFFFull) return ctx->fail(IVX_ERR_INVALID, "bits_select: bitmap exceeds UInt32 index capacity");
+    IVX_HIP(ctx, hipSetDevice(ctx->device));
+    const u32 *dbits; u32 *dout;
+    IVX_TRY(stage_in(ctx, mem, WS_IN_KEY, bits, (n_bits + 31) / 32, &dbits));
+    IVX_TRY(stage_out(ctx, mem, WS_OUT_A, out, cap, &dout));
+    u64 m = 0;
+    {
+        KernelTimer t(ctx);
+        const ivx_status st = ivx_bits_select_device(ctx, dbits, n_bits, want_set, dout, cap, &m);
+        *n_out = m;
+        if (st != IVX_OK) return st;
+    }
+    if (cap) IVX_TRY(copy_out(ctx, mem, out, dout, m));
+    if (mem == IVX_MEM_HOST) IVX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return IVX_OK;
+}
+
 // ---------------------------------------------------------------- a4 / a5 / a6 probes
 
 ivx_status ivx_count_probe(ivx_ctx *ctx, const ivx_index *ix, const u32 *key, const i32 *s, const i32 *e, u64 n, int strict, i64 *out);

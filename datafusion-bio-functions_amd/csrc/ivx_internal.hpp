@@ -297,4 +297,11 @@ ivx_status ivx_rowval_probe_regions(ivx_ctx *ctx, const JoinIndexView &jv, u32 n
                                     const u32 *key, const i32 *s, const i32 *e, u64 n, int strict, void *out, u64 *d_total,
                                     bool has_filter = false, bool pk24 = false, bool fast = false);
 
+// build-side match marks (ivx_marks.hip; the lean region form in ivx_regions_probe.hip): one bit per build row, ORed
+ivx_status ivx_mark_probe(ivx_ctx *ctx, const JoinIndexView &jv, const u32 *key, const i32 *s, const i32 *e, u64 n, u32 *marks);
+ivx_status ivx_mark_probe_regions(ivx_ctx *ctx, const JoinIndexView &jv, u32 nreg, const u32 *key, const i32 *s, const i32 *e, u64 n,
+                                  u32 *marks, bool has_filter, bool pk24, bool fast, bool *took);
+ivx_status ivx_bits_mark_device(ivx_ctx *ctx, const u32 *idx, u64 n, u32 *bits, u64 n_bits);
+ivx_status ivx_bits_select_device(ivx_ctx *ctx, const u32 *bits, u64 n_bits, int want_set, u32 *out, u64 cap, u64 *n_out);
+
 ivx_status ivx_index_alloc(ivx_ctx *ctx, ivx_index *ix, size_t bytes, void **out);

@@ -57,3 +57,12 @@ __device__ __forceinline__ void walk(const JoinIndexView &ix, u32 sh0, u32 lev0,
     walk_ent(ix, sh0, lev0, nlev, k, qs, qe, [&](const ivx_ent &x) { f(x.row); });
 }
 
+// set bit `i` of a bitmap that other workgroups, streams and contexts OR into at the same time: the word is tested with a
+// plain load first (many probe rows hit the same build row; a stale "clear" only costs the atomic), then a device-scope OR
+__device__ __forceinline__ void mark_bit(u32 *bits, u32 i)
+{
+    u32 *w = bits + (i >> 5);
+    const u32 b = 1u << (i & 31u);
+    if ((*w & b) == 0u) atomicOr(w, b);
+}
+

@@ -9,12 +9,14 @@
 //                     fall back to global reads inside the same kernel.
 //   k_fill_fast/_rest the lean fill for the case the headline always meets: packed rows in pages, every region one
 //   k_rv_fast/_rest   LDS-resident level; the same for per-row values
+//   k_mark_fast/_rest ... and for the build-side match marks: the matched slice entries in an LDS bitmap, flushed per region
 //   k_probe_dense     match-dense fill: count the 64-row pieces, scan, write
 //   k_pick_rows       rows per lane of the fill, decided on the device when the routed row count is known only there
 //
 // Host side: region_knobs (the IVX_* environment settings, read once per call), probe_pairs (count / fill over any
-// ivx_routed), and the two entry points ivx_join_probe_regions (COUNT / FILL; a COUNT call leaves its routed rows to the
-// FILL call that follows: ivx_join_plan) and ivx_rowval_probe_regions (one value per probe row, in input order).
+// ivx_routed), and the entry points ivx_join_probe_regions (COUNT / FILL; a COUNT call leaves its routed rows to the
+// FILL call that follows: ivx_join_plan), ivx_rowval_probe_regions (one value per probe row, in input order) and
+// ivx_mark_probe_regions (one bit per matched BUILD row, ORed into the caller's bitmap; lean form only).
 //
 // HBM traffic per probe row behind the routing: 12 B or 8 B (probe) + 8 B per pair, all streaming (measured:
 // profiles/r1_d_regions_pipeline_pmc.txt).
@@ -993,6 +995,154 @@ __global__ __launch_bounds__(256) void k_rv_rest(JoinIndexView ix, u64 *__restri
     }
 }
 
+// ------------------------------------------------------------------ lean build-side marks
+// Which BUILD rows a big batch matched (ivx_probe_mark_build), over the same routed pages and with k_rv_fast's row
+// streaming and walk -- but nothing is written back per probe row.  Beside the slice the workgroup keeps one bit per slice
+// entry in LDS (RP_ECAP bits); a match ORs bit j, its slice entry, with one LDS atomic.  When the workgroup leaves a region,
+// and at the end of its share, it sweeps the LDS words: every set bit is a matched entry, whose build row (read from
+// ix.ent, the slice stages no row ids) gets its bit in the caller's bitmap by test-then-OR, and the LDS word is cleared.
+// Global atomics are then per distinct matched build row and workgroup visit, not per match (the headline: ~37 matches
+// per build row).  Rows the packed form cannot carry are listed as in k_rv_fast; k_mark_rest marks for them.
+template <int B>
+__global__ __launch_bounds__(RP_T, IVX_RV_WPS) void k_mark_fast(JoinIndexView ix, const u64 *__restrict__ pool, const u32 *__restrict__ rcur, const u32 *__restrict__ cfirst,
+                                                    PageTab pt, u32 rowbits, u64 *__restrict__ rest_rows, u32 *rest_n, u32 *marks)
+{
+    constexpr u32 WB = IVX_WAVE * B, SUB = 8u / B, NBW = RP_ECAP / 32u;
+    static_assert(RP_ECAP % 32u == 0, "one LDS bit per slice entry, whole words");
+    __shared__ unsigned short s_off[RP_CCAP];
+    __shared__ u64 s_ent[RP_ECAP];
+    __shared__ u32 s_cfirst[IVX_MAXREG_WIDE + 2];
+    __shared__ u32 s_bits[NBW];
+    ProbeLds L{s_off, s_ent, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    const u32 wv = __builtin_amdgcn_readfirstlane(threadIdx.x / IVX_WAVE), ln = lane_id();
+    const u32 nreg = ix.hdr[HDR_NREG];
+    for (u32 t = threadIdx.x; t <= nreg; t += RP_T) s_cfirst[t] = cfirst[t];
+    for (u32 t = threadIdx.x; t < NBW; t += RP_T) s_bits[t] = 0u;
+    __syncthreads();
+    const u32 nchunk = s_cfirst[nreg];
+    const u32 c_lo = (u32)((u64)nchunk * blockIdx.x / gridDim.x), c_hi = (u32)((u64)nchunk * (blockIdx.x + 1) / gridDim.x);
+    if (c_lo >= c_hi) return;
+    const u32 maxlen = pk_maxlen(rowbits);
+    const u32 pmask = (1u << pt.lgpg) - 1u;
+    Slice S;
+    slice_init(ix, S, L);
+    u32 r_next;
+    { u32 a = 0, b = nreg; while (a < b) { const u32 m = (a + b + 1) >> 1; if (s_cfirst[m] <= c_lo) a = m; else b = m - 1; } r_next = a; }
+    const u32 nbatch = (c_hi - c_lo) * SUB;
+    u64 nx[B];
+    u32 ncnt = 0, nfirst = 0;
+    auto prefetch = [&](u32 i) {
+        const u32 c = c_lo + i / SUB, sb = i % SUB;
+        while (c >= s_cfirst[r_next + 1]) r_next++;
+        nfirst = (c - s_cfirst[r_next]) * FP_CHUNK + wv * (8u * IVX_WAVE) + sb * WB;
+        const u32 rows = rcur[r_next];
+        ncnt = rows > nfirst ? (rows - nfirst < WB ? rows - nfirst : WB) : 0u;
+        if (ncnt) {
+            u32 pg = pt.ptab[(u64)r_next * pt.pstride + (nfirst >> pt.lgpg)];
+            if (pg == 0u) pg = 1u;                                       // (never published: see pages_load; stay in bounds)
+            const u64 *src = pool + (((u64)(pg - 1u) << pt.lgpg) + (nfirst & pmask));
+#pragma unroll
+            for (int q = 0; q < B; q++) nx[q] = src[q * IVX_WAVE + ln];
+        }
+    };
+    // the matched entries of the region just left: to the caller's bitmap, LDS words back to zero (all threads; the
+    // slice_load or the kernel's end that follows brings the barrier behind the sweep)
+    auto flush = [&]() {
+        __syncthreads();
+        for (u32 w = threadIdx.x; w < NBW; w += RP_T) {
+            u32 m = s_bits[w];
+            if (m == 0u) continue;
+            s_bits[w] = 0u;
+            do {
+                const u32 j = (w << 5) + (u32)__builtin_ctz(m);
+                m &= m - 1u;
+                mark_bit(marks, ix.ent[S.e0 + j].row);
+            } while (m);
+        }
+    };
+    prefetch(0);
+    u32 loaded_r = 0xFFFFFFFFu;
+    for (u32 i = 0; i < nbatch; i++) {
+        const u32 r = r_next, cnt = ncnt, first = nfirst;
+        if (r != loaded_r) {
+            if (loaded_r != 0xFFFFFFFFu) flush();
+            slice_load(ix, S, L, r, true);
+            loaded_r = r;
+        }
+        const bool full = cnt == WB;
+        u32 rel[B], len[B];
+#pragma unroll
+        for (int q = 0; q < B; q++) {
+            const u32 lo32 = (u32)nx[q], hi32 = (u32)(nx[q] >> 32);
+            rel[q] = lo32 & 0xFFFFFFu;
+            len[q] = (lo32 >> 24) | ((rowbits < 32 ? (hi32 >> rowbits) & 0xFFu : 0u) << 8);
+        }
+        if (i + 1 < nbatch) prefetch(i + 1);
+        const u32 sh0 = S.sh0, off = S.off, cmax = S.cmax, ncm1 = S.ncm1;
+        const i32 rbase = S.rbase;
+        u32 ca[B], cb[B], slow = 0;
+        auto cells = [&](auto full_tag) {
+            constexpr bool FULL = decltype(full_tag)::value;
+#pragma unroll
+            for (int q = 0; q < B; q++) {
+                const u32 t = ((rel[q] + 1u) >> sh0) + off;
+                const u32 bl0 = (t > 1u ? t : 1u) - 1u;
+                const u32 bh0 = ((rel[q] + len[q]) >> sh0) + off;
+                const u32 bh = bh0 < cmax ? bh0 : cmax;
+                bool bad = len[q] == maxlen || bh >= ncm1;
+                const bool ok = FULL || (u32)q * IVX_WAVE + ln < cnt;
+                if (ok && bad) slow |= 1u << q;
+                bad |= !ok;
+                const u32 e1 = bad ? 0u : bh + 1u;
+                const u32 bl = bl0 < e1 ? bl0 : e1;
+                ca[q] = s_off[bl];
+                cb[q] = s_off[e1];
+            }
+        };
+        if (full) cells(std::true_type{}); else cells(std::false_type{});
+#pragma unroll
+        for (int q = 0; q < B; q++) {
+            const i32 qs = (i32)((u32)rbase + rel[q]), qe = (i32)((u32)qs + len[q]);
+            for (u32 j = ca[q]; j < cb[q]; j++) {
+                const u64 x = s_ent[j];
+                if ((i32)(u32)x <= qe && (i32)(u32)(x >> 32) >= qs)
+                    __hip_atomic_fetch_or(&s_bits[j >> 5], 1u << (j & 31u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            }
+        }
+        if (__builtin_expect(slow != 0, 0)) {
+#pragma unroll
+            for (int q = 0; q < B; q++)
+                if ((slow >> q) & 1u) rest_rows[atomicAdd(rest_n + 1, 1u)] = (u64)(first + (u32)q * IVX_WAVE + ln) | ((u64)r << 32);
+        }
+    }
+    flush();
+}
+
+__global__ __launch_bounds__(256) void k_mark_rest(JoinIndexView ix, const u64 *__restrict__ pool, PageTab pt, const u64 *__restrict__ rest_rows,
+                                                   const u32 *__restrict__ rest_n, const i32 *__restrict__ ps_in, const i32 *__restrict__ pe_in,
+                                                   u32 rowbits, u32 *marks)
+{
+    const u32 nrow = rest_n[1];
+    const u32 rowmask = rowbits >= 32 ? 0xFFFFFFFFu : (1u << rowbits) - 1u;
+    const u32 maxlen = pk_maxlen(rowbits);
+    const u32 pmask = (1u << pt.lgpg) - 1u;
+    const u32 sh0 = ix.hdr[HDR_SH0], nlev = ix.hdr[HDR_NLEV];
+    for (u32 i = blockIdx.x * blockDim.x + threadIdx.x; i < nrow; i += gridDim.x * blockDim.x) {
+        const u64 ent = rest_rows[i];
+        const u32 r = (u32)(ent >> 32), vr = (u32)ent;
+        u32 pg = pt.ptab[(u64)r * pt.pstride + (vr >> pt.lgpg)];
+        if (pg == 0u) pg = 1u;
+        const u64 x = pool[((u64)(pg - 1u) << pt.lgpg) + (vr & pmask)];
+        const u32 lo32 = (u32)x, hi32 = (u32)(x >> 32);
+        const u32 len = (lo32 >> 24) | ((rowbits < 32 ? (hi32 >> rowbits) & 0xFFu : 0u) << 8);
+        const u32 row = hi32 & rowmask;
+        i32 qs, qe;
+        if (len == maxlen) { qs = ps_in[row]; qe = pe_in[row]; }
+        else { qs = (i32)((u32)ix.rdesc[r].rbase + (lo32 & 0xFFFFFFu)); qe = (i32)((u32)qs + len); }
+        walk(ix, sh0, 0, nlev, ix.rkey[r], qs, qe, [&](u32 brow) { mark_bit(marks, brow); });
+    }
+}
+
 // ------------------------------------------------------------------ match-dense fill: count, scan, write
 // With several pairs per probe row the staging ring holds only one 64-row batch per wavefront and the 16
 // wavefronts of a workgroup end up in lock step, round after round.  For such joins the pairs are written in two
@@ -1393,4 +1543,26 @@ ivx_status ivx_rowval_probe_regions(ivx_ctx *ctx, const JoinIndexView &jv, u32 n
     if (kind == IVX_RV_COVERAGE) probe(int_tag<RV_COVERAGE>{}); else if (kind == IVX_RV_COUNT) probe(int_tag<RV_COUNT>{}); else probe(int_tag<RV_MATCHES>{});
     IVX_HIP(ctx, hipGetLastError());
     return ivx_unroute_values(ctx, R, nreg, kind, val, n, out, d_total);
+}
+
+// The build rows a big batch matched, ORed into `marks` (one bit per build row), through the region partition -- the lean
+// form only: packed rows in region pages over an index whose every region is one LDS-resident level, i.e. when
+// ivx_rowval_probe_regions would launch k_rv_fast.  *took = false (nothing launched) when the index or the settings do not
+// qualify: the caller then runs the direct kernel (ivx_mark_probe) on its columns.
+ivx_status ivx_mark_probe_regions(ivx_ctx *ctx, const JoinIndexView &jv, u32 nreg, const u32 *key, const i32 *s, const i32 *e, u64 n,
+                                  u32 *marks, bool has_filter, bool pk24, bool fast, bool *took)
+{
+    *took = false;
+    const RegionKnobs K = region_knobs();
+    if (n == 0 || nreg == 0 || nreg > IVX_MAXREG || !pk24 || !fast || K.two_pass || K.pack_off || K.lean_off) return IVX_OK;
+    hipStream_t st = ctx->stream;
+    ivx_routed R;
+    IVX_TRY(ivx_route_paged(ctx, jv, nreg, key, s, e, n, ivx_paged_opts{has_filter && !K.filter_off, true, true, true, 0u}, &R));
+    if (R.rest_rows == nullptr || R.pt.lgpg < 13) return IVX_OK;
+    hipLaunchKernelGGL((k_mark_fast<IVX_RV_B>), dim3(RP_GRID * (IVX_RV_WPS / 4)), dim3(RP_T), 0, st, jv, R.se, (const u32 *)R.ctl->rcur, (const u32 *)R.ctl->cfirst, R.pt, R.rowbits,
+                       R.rest_rows, R.ctl->rest_n, marks);
+    hipLaunchKernelGGL(k_mark_rest, dim3(256), dim3(256), 0, st, jv, R.se, R.pt, (const u64 *)R.rest_rows, (const u32 *)R.ctl->rest_n, s, e, R.rowbits, marks);
+    IVX_HIP(ctx, hipGetLastError());
+    *took = true;
+    return IVX_OK;
 }

@@ -328,6 +328,44 @@ int load_side64(brh_session *s, brh_batch t, const brh_columns &c, Side64 *o)
 
 struct IndexGuard { ivx_index *ix = nullptr; ~IndexGuard() { if (ix) ivx_index_free(ix); } };
 
+// the join types that read the build side's match marks (bio_ranges_host.h)
+bool join_marks_build(int jt) { return jt >= BRH_JOIN_LEFT_SEMI && jt <= BRH_JOIN_FULL; }
+bool join_null_build(int jt) { return jt == BRH_JOIN_RIGHT || jt == BRH_JOIN_FULL; }    // unmatched probe rows, build_idx NULL
+bool join_null_probe(int jt) { return jt == BRH_JOIN_LEFT || jt == BRH_JOIN_FULL; }     // unmatched build rows, probe_idx NULL
+
+// the build rows whose bit in `marks` (nb bits, host words) is set / clear, ascending: ONE ivx_bits_select
+int select_build_rows(brh_session *s, const std::vector<uint32_t> &marks, uint64_t nb, bool want_set, std::vector<uint32_t> *rows)
+{
+    rows->assign(nb ? nb : 1, 0u);
+    uint64_t m = 0;
+    const ivx_status st = ivx_bits_select(s->ctx, IVX_MEM_HOST, marks.data(), nb, want_set ? 1 : 0, rows->data(), nb, &m);
+    if (st != IVX_OK) return fail_ivx(s, st);
+    rows->resize(m);
+    return 0;
+}
+
+// the Inner pairs of one batch (count, then fill), and behind them the probe rows without a match, build_idx NULL (Right / Full)
+int join_pairs(brh_session *s, const ivx_index *ix, const uint32_t *pk, const int32_t *ps, const int32_t *pe, uint64_t np, bool null_build,
+               std::vector<uint32_t> *bi, std::vector<uint32_t> *pi, std::vector<uint8_t> *bvalid, uint64_t *n_pairs)
+{
+    uint64_t total = 0, written = 0;
+    ivx_status st = ivx_probe_overlap_count(s->ctx, ix, IVX_MEM_HOST, pk, ps, pe, np, nullptr, &total);
+    if (st != IVX_OK) return fail_ivx(s, st);
+    bi->assign(total ? total : 1, 0u); pi->assign(total ? total : 1, 0u);
+    st = ivx_probe_overlap_fill(s->ctx, ix, IVX_MEM_HOST, pk, ps, pe, np, bi->data(), pi->data(), total, &written);
+    if (st != IVX_OK) return fail_ivx(s, st);
+    bi->resize(written); pi->resize(written);
+    *n_pairs = written;
+    if (null_build) {
+        std::vector<uint8_t> ex(np ? np : 1);
+        st = ivx_probe_exists(s->ctx, ix, IVX_MEM_HOST, pk, ps, pe, np, ex.data());
+        if (st != IVX_OK) return fail_ivx(s, st);
+        bvalid->assign(written, 1);
+        for (uint64_t i = 0; i < np; i++) if (!ex[i]) { bi->push_back(0u); pi->push_back((uint32_t)i); bvalid->push_back(0); }
+    }
+    return 0;
+}
+
 }  // namespace
 
 extern "C" int brh_session_create(int device_ordinal, brh_session **out)
@@ -442,6 +480,7 @@ extern "C" int brh_interval_join(brh_session *s, brh_batch build, brh_columns bc
                                  ArrowArray *build_idx, ArrowSchema *build_idx_schema, ArrowArray *probe_idx, ArrowSchema *probe_idx_schema)
 {
     if (!s) return 1;
+    if (nearest_algorithm && join_marks_build(join_type)) return fail(s, "interval join: Algorithm::CoitreesNearest is an Inner join");
     KeyDict kd; Side32 B, P;
     if (build_keys(s, {{build, bcols}, {probe, pcols}}, &kd, true) || load_side32(s, build, bcols, &B) || load_side32(s, probe, pcols, &P)) return 1;
     if (strict_predicate) {                                       // `a.start < b.end AND a.end > b.start`: end - 1 on both sides
@@ -474,6 +513,34 @@ extern "C" int brh_interval_join(brh_session *s, brh_batch build, brh_columns bc
         for (uint64_t i = 0; i < np; i++) if ((ex[i] != 0) == want) pi.push_back((uint32_t)i);
         make_primitive<uint32_t>(build_idx, nullptr, 0, nullptr); make_schema(build_idx_schema, "I", "build_idx", false);
         make_primitive<uint32_t>(probe_idx, pi.data(), (int64_t)pi.size(), nullptr); make_schema(probe_idx_schema, "I", "probe_idx", false);
+        return 0;
+    }
+    const uint64_t nb = B.s.size();
+    if (join_type == BRH_JOIN_LEFT_SEMI || join_type == BRH_JOIN_LEFT_ANTI) {        // the build rows with / without a match: no pairs are made
+        std::vector<uint32_t> marks((nb + 31) / 32 + 1, 0u), rows;
+        st = ivx_probe_mark_build(s->ctx, g.ix, IVX_MEM_HOST, kd.ids[1].data(), P.s.data(), P.e.data(), np, marks.data());
+        if (st != IVX_OK) return fail_ivx(s, st);
+        if (select_build_rows(s, marks, nb, join_type == BRH_JOIN_LEFT_SEMI, &rows)) return 1;
+        make_primitive<uint32_t>(build_idx, rows.data(), (int64_t)rows.size(), nullptr); make_schema(build_idx_schema, "I", "build_idx", false);
+        make_primitive<uint32_t>(probe_idx, nullptr, 0, nullptr); make_schema(probe_idx_schema, "I", "probe_idx", false);
+        return 0;
+    }
+    if (join_marks_build(join_type)) {                                               // Left / Right / Full: the pairs, then the NULL-extended rows
+        const bool nullb = join_null_build(join_type), nullp = join_null_probe(join_type);
+        std::vector<uint32_t> bi, pi; std::vector<uint8_t> bvalid, pvalid;
+        uint64_t n_pairs = 0;
+        if (join_pairs(s, g.ix, kd.ids[1].data(), P.s.data(), P.e.data(), np, nullb, &bi, &pi, &bvalid, &n_pairs)) return 1;
+        if (nullp) {
+            std::vector<uint32_t> marks((nb + 31) / 32 + 1, 0u), rows;
+            st = ivx_bits_mark(s->ctx, IVX_MEM_HOST, bi.data(), n_pairs, marks.data(), nb);
+            if (st != IVX_OK) return fail_ivx(s, st);
+            if (select_build_rows(s, marks, nb, false, &rows)) return 1;
+            pvalid.assign(bi.size(), 1);
+            for (uint32_t r : rows) { bi.push_back(r); pi.push_back(0u); pvalid.push_back(0); }
+            if (nullb) bvalid.resize(bi.size(), 1);
+        }
+        make_primitive<uint32_t>(build_idx, bi.data(), (int64_t)bi.size(), nullb ? bvalid.data() : nullptr); make_schema(build_idx_schema, "I", "build_idx", nullb);
+        make_primitive<uint32_t>(probe_idx, pi.data(), (int64_t)pi.size(), nullp ? pvalid.data() : nullptr); make_schema(probe_idx_schema, "I", "probe_idx", nullp);
         return 0;
     }
     uint64_t total = 0;
@@ -905,8 +972,11 @@ struct brh_join_stream {
     uint64_t first_batch = 0, n_pushed = 0;
     int join_type = BRH_JOIN_INNER;                                 // BRH_JOIN_* or BRH_JOIN_NEAREST (Algorithm::CoitreesNearest)
     uint64_t max_rows = 0;                                          // output rows per result (0 = a group's rows in one result)
-    struct Result { uint64_t first_batch, n_batches; std::vector<uint32_t> bi, pi; std::vector<uint8_t> bvalid; std::vector<int64_t> off; bool last; };
+    struct Result { uint64_t first_batch, n_batches; std::vector<uint32_t> bi, pi; std::vector<uint8_t> bvalid, pvalid; std::vector<int64_t> off; bool last; };
     std::deque<Result> ready;
+    // LeftSemi / LeftAnti / Left / Full: the build side's match marks, one bit per build row, ORed into by every flushed group
+    std::vector<uint32_t> marks; uint64_t nb = 0;
+    bool finished = false;                                          // the build-side result behind the last group is queued
     ~brh_join_stream() { if (ix) ivx_index_free(ix); }
 };
 
@@ -956,6 +1026,18 @@ int stream_flush(brh_join_stream *js)
             emit(std::move(sb), std::move(sp), std::move(bv), b >= rows);
             if (b >= rows) break;
         }
+    } else if (js->join_type == BRH_JOIN_LEFT_SEMI || js->join_type == BRH_JOIN_LEFT_ANTI) {     // marks only: the group gives no result
+        st = ivx_probe_mark_build(s->ctx, js->ix, IVX_MEM_HOST, gk, gs, ge, np, js->marks.data());
+        if (st != IVX_OK) return fail_ivx(s, st);
+    } else if (join_marks_build(js->join_type)) {                                                // Left / Right / Full (regular mode only)
+        std::vector<uint32_t> bi, pi; std::vector<uint8_t> bv;
+        uint64_t n_pairs = 0;
+        if (join_pairs(s, js->ix, gk, gs, ge, np, join_null_build(js->join_type), &bi, &pi, &bv, &n_pairs)) return 1;
+        if (join_null_probe(js->join_type)) {
+            st = ivx_bits_mark(s->ctx, IVX_MEM_HOST, bi.data(), n_pairs, js->marks.data(), js->nb);
+            if (st != IVX_OK) return fail_ivx(s, st);
+        }
+        emit(std::move(bi), std::move(pi), std::move(bv), true);
     } else if (!js->max_rows) {
         uint64_t total = 0, written = 0;
         st = ivx_probe_overlap_count(s->ctx, js->ix, IVX_MEM_HOST, gk, gs, ge, np, nullptr, &total);
@@ -1005,7 +1087,9 @@ extern "C" int brh_join_stream_open(brh_session *s, brh_batch build, brh_columns
 {
     if (!s || !out) return 1;
     *out = nullptr;
-    if (join_type < BRH_JOIN_INNER || join_type > BRH_JOIN_NEAREST) return fail(s, "join stream: unsupported join type");
+    if (join_type < BRH_JOIN_INNER || join_type > BRH_JOIN_FULL) return fail(s, "join stream: unsupported join type");
+    if (join_marks_build(join_type) && max_output_rows != 0)
+        return fail(s, "join stream: max_output_rows > 0 (the low-memory mode) is not supported with LeftSemi / LeftAnti / Left / Right / Full joins");
     if (max_output_rows == BRH_MAX_OUTPUT_ENV) {                  // the reference's low-memory default (interval_join.rs:543-548)
         // usize::from_str: an optional '+', then digits only, no overflow; anything else is the default.  A parsed 0 is kept by
         // the reference (it then emits after every probe row); here 0 already means "regular mode", so 0 becomes 1: one
@@ -1038,6 +1122,8 @@ extern "C" int brh_join_stream_open(brh_session *s, brh_batch build, brh_columns
     ivx_status st = ivx_index_build(s->ctx, join_type == BRH_JOIN_NEAREST ? IVX_KIND_NEAREST : IVX_KIND_OVERLAP, IVX_MEM_HOST, kd.ids[0].data(),
                                     B.s.data(), B.e.data(), B.s.size(), js->nk + 1, &js->ix);
     if (st != IVX_OK) return fail_ivx(s, st);
+    js->nb = B.s.size();
+    if (join_marks_build(join_type)) js->marks.assign((js->nb + 31) / 32 + 1, 0u);
     *out = js.release();
     return 0;
 }
@@ -1103,6 +1189,17 @@ extern "C" int brh_join_stream_finish(brh_join_stream *js, int *n_ready)
 {
     if (!js) return 1;
     if (stream_flush(js)) return 1;
+    if (join_marks_build(js->join_type) && !js->finished) {
+        // behind the last group: the build-side rows (matched: LeftSemi; unmatched: LeftAnti / Left / Full; Right has none)
+        brh_join_stream::Result r;
+        r.first_batch = js->n_pushed; r.n_batches = 0; r.off = {0}; r.last = true;
+        if (js->join_type != BRH_JOIN_RIGHT && select_build_rows(js->s, js->marks, js->nb, js->join_type == BRH_JOIN_LEFT_SEMI, &r.bi)) return 1;
+        if (js->join_type == BRH_JOIN_RIGHT) r.bi.clear();
+        if (join_null_probe(js->join_type)) { r.pi.assign(r.bi.size(), 0u); r.pvalid.assign(r.bi.size(), 0); }
+        if (join_null_build(js->join_type)) r.bvalid.assign(r.bi.size(), 1);
+        js->ready.push_back(std::move(r));
+        js->finished = true;
+    }
     if (n_ready) *n_ready = (int)js->ready.size();
     return 0;
 }
@@ -1117,9 +1214,10 @@ extern "C" int brh_join_stream_next(brh_join_stream *js, uint64_t *first_batch, 
     if (first_batch) *first_batch = r.first_batch;
     if (n_batches) *n_batches = r.n_batches;
     if (group_done) *group_done = r.last ? 1 : 0;
-    const bool nullable = js->join_type == BRH_JOIN_NEAREST;
-    make_primitive<uint32_t>(build_idx, r.bi.data(), (int64_t)r.bi.size(), nullable ? r.bvalid.data() : nullptr); make_schema(build_idx_schema, "I", "build_idx", nullable);
-    make_primitive<uint32_t>(probe_idx, r.pi.data(), (int64_t)r.pi.size(), nullptr); make_schema(probe_idx_schema, "I", "probe_idx", false);
+    const bool nullable = js->join_type == BRH_JOIN_NEAREST || join_null_build(js->join_type);
+    const bool pnullable = join_null_probe(js->join_type);          // (a result without a validity vector has no NULLs: a group's pairs)
+    make_primitive<uint32_t>(build_idx, r.bi.data(), (int64_t)r.bi.size(), nullable && !r.bvalid.empty() ? r.bvalid.data() : nullptr); make_schema(build_idx_schema, "I", "build_idx", nullable);
+    make_primitive<uint32_t>(probe_idx, r.pi.data(), (int64_t)r.pi.size(), pnullable && !r.pvalid.empty() ? r.pvalid.data() : nullptr); make_schema(probe_idx_schema, "I", "probe_idx", pnullable);
     make_primitive<int64_t>(batch_offsets, r.off.data(), (int64_t)r.off.size(), nullptr); make_schema(batch_offsets_schema, "l", "batch_offsets", false);
     js->ready.pop_front();
     return 0;

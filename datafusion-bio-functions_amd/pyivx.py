@@ -28,6 +28,7 @@ SYMBOLS = [
     "ivx_cluster", "ivx_complement", "ivx_take_fixed", "ivx_take_utf8", "ivx_take_bits", "ivx_take_view",
     "ivx_ctx_metrics", "ivx_ctx_reset_metrics", "ivx_ctx_set_memory_limit", "ivx_ctx_trim", "ivx_scatter_fixed",
     "ivx_ctx_reserved_bytes", "ivx_ctx_set_build_overlap", "ivx_index_layout",
+    "ivx_probe_mark_build", "ivx_bits_mark", "ivx_bits_select",
 ]
 
 # slots of ivx_index_layout (include/ivx.h IVX_LAYOUT_*), in order
@@ -269,6 +270,62 @@ class Ctx:
             out = np.empty(n, np.uint8)
         self._chk(lib().ivx_probe_exists(self.h, ix.h, C.c_int(mem), _ptr(key), _ptr(s), _ptr(e), C.c_uint64(n), _ptr(out)))
         return out
+
+    # ---- a3'': build-side match marks ----
+    @staticmethod
+    def new_marks(n_bits, device=None):
+        """a zeroed mark bitmap of n_bits bits: uint32 words on the host, or int32 on `device` (same bytes)"""
+        nw = (int(n_bits) + 31) // 32
+        if device is None:
+            return np.zeros(max(nw, 1), np.uint32)
+        import torch
+        return torch.zeros(max(nw, 1), dtype=torch.int32, device=device)
+
+    def mark_build(self, ix, key, start, end, marks):
+        """OR the bit of every build row of `ix` that a row of this batch overlaps into `marks` (ix.rows bits); -> marks"""
+        key, s, e, n, mem = _cols(key, start, end, np.int32)
+        if _is_torch(marks) != (mem == MEM_DEVICE):
+            raise ValueError("mix of host and device buffers in one call")
+        self._chk(lib().ivx_probe_mark_build(self.h, ix.h, C.c_int(mem), _ptr(key), _ptr(s), _ptr(e), C.c_uint64(n), _ptr(marks)))
+        return marks
+
+    def bits_mark(self, idx, bits, n_bits):
+        """OR bit idx[i] into `bits` (NULL_IDX skipped, anything else >= n_bits raises ERR_INVALID); -> bits"""
+        dev = _is_torch(bits)
+        if _is_torch(idx) != dev:
+            raise ValueError("mix of host and device buffers in one call")
+        if dev:
+            assert idx.is_contiguous() and bits.is_contiguous()
+            n = int(idx.numel())
+        else:
+            idx = np.ascontiguousarray(idx, np.uint32)
+            n = len(idx)
+        self._chk(lib().ivx_bits_mark(self.h, C.c_int(MEM_DEVICE if dev else MEM_HOST), _ptr(idx), C.c_uint64(n), _ptr(bits), C.c_uint64(int(n_bits))))
+        return bits
+
+    def bits_select(self, bits, n_bits, want_set=True, cap=None, count_only=False):
+        """positions < n_bits whose bit is set (or clear), ascending.  cap=None: a counting call sizes the output.
+        count_only: -> the count.  A cap that is too small raises IvxError(ERR_CAPACITY) whose .needed is the size."""
+        dev = _is_torch(bits)
+        mem, n_bits, want = C.c_int(MEM_DEVICE if dev else MEM_HOST), C.c_uint64(int(n_bits)), C.c_int(int(bool(want_set)))
+        m = C.c_uint64(0)
+        if count_only or cap is None:
+            self._chk(lib().ivx_bits_select(self.h, mem, _ptr(bits), n_bits, want, None, C.c_uint64(0), C.byref(m)))
+            if count_only:
+                return m.value
+            cap = m.value
+        if dev:
+            import torch
+            out = torch.empty(max(cap, 1), dtype=torch.int32, device=bits.device)
+        else:
+            out = np.empty(max(cap, 1), np.uint32)
+        st = lib().ivx_bits_select(self.h, mem, _ptr(bits), n_bits, want, _ptr(out), C.c_uint64(cap), C.byref(m))
+        if st == ERR_CAPACITY:
+            err = IvxError(st, f"need {m.value} positions, cap {cap}")
+            err.needed = m.value
+            raise err
+        self._chk(st)
+        return out[: m.value]
 
     # ---- a4 / a5 ----
     def _per_row_i64(self, fn, ix, key, start, end, strict, out=None):

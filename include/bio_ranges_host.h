@@ -57,9 +57,17 @@ const char *brh_last_error(const brh_session *s);
 
 /* FilterOp (R/src/filter_op.rs:4-10) */
 enum { BRH_WEAK = 0, BRH_STRICT = 1 };
-/* JoinType subset with real semantics in IntervalJoinExec (interval_join.rs:1014-1024) */
+/* JoinType.  The first three are the subset with real semantics in IntervalJoinExec (interval_join.rs:1014-1024); for the
+ * types from BRH_JOIN_LEFT_SEMI on the reference emits the Inner rows -- here they mean what SQL (and HashJoinExec, with its
+ * visited_left_side bitmap) means by them, over the build side's match marks (ivx.h ivx_probe_mark_build).  `build` is
+ * the SQL left side throughout. */
 enum { BRH_JOIN_INNER = 0, BRH_JOIN_RIGHT_SEMI = 1, BRH_JOIN_RIGHT_ANTI = 2,
-       BRH_JOIN_NEAREST = 3 /* join stream only: Inner with Algorithm::CoitreesNearest (interval_join.rs:864-870) */ };
+       BRH_JOIN_NEAREST = 3 /* join stream only: Inner with Algorithm::CoitreesNearest (interval_join.rs:864-870) */,
+       BRH_JOIN_LEFT_SEMI = 4,  /* the build rows with a match */
+       BRH_JOIN_LEFT_ANTI = 5,  /* the build rows without one */
+       BRH_JOIN_LEFT = 6,       /* the pairs, then every unmatched build row with a NULL probe_idx */
+       BRH_JOIN_RIGHT = 7,      /* the pairs, then every unmatched probe row with a NULL build_idx */
+       BRH_JOIN_FULL = 8        /* both */ };
 #define BRH_MAX_OUTPUT_ENV UINT64_MAX   /* join stream: take the output budget from BIO_MAX_OUTPUT_BATCH_SIZE (default 100000) */
 
 /* count_overlaps('left','right') / coverage(...): CountOverlapsProvider (R/src/count_overlaps.rs:107-169),
@@ -81,7 +89,13 @@ int brh_nearest(brh_session *s, brh_batch left, brh_columns lcols, brh_batch rig
  * strict_predicate = the planner's `<`/`>` rewrite: both sides' END minus one (intervals.rs:85-115).
  * nearest_algorithm != 0 = Algorithm::CoitreesNearest (one row per probe row, NULL build index when
  * nothing is found).  Inner: (build_idx, probe_idx); RightSemi/RightAnti: probe_idx only
- * (build_idx output left released/empty). */
+ * (build_idx output left released/empty).
+ * LeftSemi/LeftAnti: build_idx only, ascending (probe_idx empty): one ivx_probe_mark_build and one ivx_bits_select, no
+ * pairs are made.  Right / Left / Full: the Inner pairs first, then the NULL-extended rows -- Right / Full: the probe rows
+ * without a match (from ivx_probe_exists) with a NULL build_idx; Left / Full: the build rows without a match
+ * (ivx_bits_mark over the filled build_idx, ivx_bits_select of the clear bits) with a NULL probe_idx.  NULL is the
+ * validity buffer of a nullable UInt32 column, as the nearest join produces it (the slot's value is 0).  Pair order
+ * stays unspecified; the only promise is that the NULL-extended rows follow the pairs (Full: probe rows, then build rows). */
 int brh_interval_join(brh_session *s, brh_batch build, brh_columns bcols, brh_batch probe, brh_columns pcols,
                       int join_type, int strict_predicate, int nearest_algorithm,
                       struct ArrowArray *build_idx, struct ArrowSchema *build_idx_schema,
@@ -149,10 +163,20 @@ int brh_take(brh_session *s, const struct ArrowArray *column, const struct Arrow
  *   BRH_JOIN_RIGHT_SEMI / _ANTI   probe_idx only: the probe rows with / without a match, ascending (:1014-1024, :1433-1463)
  *   BRH_JOIN_NEAREST     Algorithm::CoitreesNearest: one row per probe row, build_idx NULL where the key has no build row
  *                        (:864-870, :1226-1238, :1628-1635)
+ *   BRH_JOIN_LEFT_SEMI / _ANTI / BRH_JOIN_LEFT / _RIGHT / _FULL   the stream keeps one match bitmap for its index (host
+ *                        words: this layer holds no device memory of its own; the library ORs every call's marks into
+ *                        them).  LeftSemi / LeftAnti: a flushed group marks the bitmap (ivx_probe_mark_build) and gives
+ *                        NO result.  Left / Full: the group's Inner pairs, and ivx_bits_mark over them.  Right / Full: the
+ *                        group's unmatched probe rows follow its pairs, build_idx NULL.  finish queues ONE more result
+ *                        behind the last group's: n_batches = 0, batch_offsets = [0], the build-side rows -- the matched
+ *                        ones for LeftSemi, the unmatched ones for LeftAnti / Left / Full (none for Right) -- ascending,
+ *                        with probe_idx all NULL (LeftSemi / LeftAnti: empty).
  * max_output_rows: 0 = every group gives ONE result (the regular mode).  > 0 = the reference's low-memory stream
  *   (:1153-1299): a result holds whole probe rows and ends after the row at which its running output-row count
  *   reaches the budget (:1199-1216, :1256-1273), so it stays below budget + the matches of its last row;
- *   BRH_MAX_OUTPUT_ENV = the reference's default, BIO_MAX_OUTPUT_BATCH_SIZE or 100000 (:543-548).
+ *   BRH_MAX_OUTPUT_ENV = the reference's default, BIO_MAX_OUTPUT_BATCH_SIZE or 100000 (:543-548).  With a join type from
+ *   BRH_JOIN_LEFT_SEMI on, open fails with "join stream: max_output_rows > 0 (the low-memory mode) is not supported with
+ *   LeftSemi / LeftAnti / Left / Right / Full joins".
  * next: probe_idx counts over the group's concatenated rows; batch_offsets Int64 [n_batches + 1] = the first row of
  * each of the group's batches, so the caller can concatenate its buffered batches (or split the pairs) and `take`
  * the payload columns as the reference does (:1655-1667); *group_done = 1 with the group's last result (the

@@ -206,6 +206,35 @@ ivx_status ivx_probe_exists(ivx_ctx *ctx, const ivx_index *ix, int mem,
                             const uint32_t *key, const int32_t *start, const int32_t *end, uint64_t n,
                             uint8_t *exists);
 
+/* a3'': which BUILD rows matched -- LeftSemi / LeftAnti / LeftMark and the unmatched side of Left / Full.  The reference
+ *      has no counterpart (IntervalJoinExec emits Inner rows for these types, interval_join.rs:1014-1024); semantics are
+ *      HashJoinExec's visited_left_side.  Index kind OVERLAP.
+ *      A mark bitmap is caller-owned: (ivx_index_rows(ix) + 31) / 32 uint32_t words, build row b = bit b & 31 of word
+ *      b >> 5 -- byte for byte an Arrow validity / Boolean bitmap, so a LeftMark column is the buffer itself.  It lives
+ *      where `mem` says.  The library only ever ORs into it: the caller zeroes it once and passes it to as many calls as it
+ *      has probe batches; bits set beforehand survive.
+ *      Same already-adjusted columns as the other ivx_probe_overlap_* calls; a key id the build side does not have never
+ *      matches (as in ivx_probe_exists); n = 0 is a no-op.  A build row is marked iff at least one probe row of the call
+ *      overlaps it: same key, bs <= qe && be >= qs.
+ *      IVX_MEM_DEVICE: the kernels use device-scope atomic OR, so several contexts may mark into the same buffer at once,
+ *      each on its own stream; the call may return with kernels in flight, like other device-mode calls, and the caller
+ *      synchronises all of those contexts before ivx_bits_select.  IVX_MEM_HOST: the library marks a zeroed scratch bitmap
+ *      (counted against the memory limit like other scratch), copies it back and ORs it into the caller's words on the host.
+ *      The call waits for an index whose build tail still runs, drops the state a count call left for its fill call, and
+ *      feeds ivx_ctx_metrics like ivx_probe_exists: one input batch and its rows, no output rows. */
+ivx_status ivx_probe_mark_build(ivx_ctx *ctx, const ivx_index *ix, int mem,
+                                const uint32_t *key, const int32_t *start, const int32_t *end, uint64_t n,
+                                uint32_t *marks);
+/*      OR bit idx[i] for i < n (what Left / Full use: the pairs exist anyway).  IVX_NULL_IDX is skipped, any other
+ *      idx[i] >= n_bits is IVX_ERR_INVALID (in-range bits of that call may or may not be set then; IVX_MEM_HOST leaves
+ *      the caller's words as they were).  n_bits < 2^32. */
+ivx_status ivx_bits_mark(ivx_ctx *ctx, int mem, const uint32_t *idx, uint64_t n, uint32_t *bits, uint64_t n_bits);
+/*      The positions < n_bits whose bit is set (want_set = 1) or clear (0), ascending.  cap = 0 with out = NULL only
+ *      counts; cap < *n_out is IVX_ERR_CAPACITY with *n_out = the size needed and nothing written.  Bits at or past
+ *      n_bits in the last word are ignored (they may hold anything).  n_bits < 2^32. */
+ivx_status ivx_bits_select(ivx_ctx *ctx, int mem, const uint32_t *bits, uint64_t n_bits, int want_set,
+                           uint32_t *out, uint64_t cap, uint64_t *n_out);
+
 /* ---- a4: CountOverlapIndex::query_count in get_count_stream
  *      (interval_tree.rs:41-49, :249-267).  Index kind COUNT. */
 ivx_status ivx_probe_count(ivx_ctx *ctx, const ivx_index *ix, int mem,

@@ -61,6 +61,12 @@ extern "C" {
                                   written: *mut u64) -> i32;
     pub fn ivx_probe_exists(ctx: *mut IvxCtx, ix: *const IvxIndex, mem: i32, key: *const u32, start: *const i32,
                             end: *const i32, n: u64, exists: *mut u8) -> i32;
+    // build-side match marks (LeftSemi / LeftAnti / Left / Full): an Arrow-layout bitmap of the build rows, ORed into
+    pub fn ivx_probe_mark_build(ctx: *mut IvxCtx, ix: *const IvxIndex, mem: i32, key: *const u32, start: *const i32,
+                                end: *const i32, n: u64, marks: *mut u32) -> i32;
+    pub fn ivx_bits_mark(ctx: *mut IvxCtx, mem: i32, idx: *const u32, n: u64, bits: *mut u32, n_bits: u64) -> i32;
+    pub fn ivx_bits_select(ctx: *mut IvxCtx, mem: i32, bits: *const u32, n_bits: u64, want_set: i32, out: *mut u32,
+                           cap: u64, n_out: *mut u64) -> i32;
     pub fn ivx_probe_count(ctx: *mut IvxCtx, ix: *const IvxIndex, mem: i32, key: *const u32, start: *const i32,
                            end: *const i32, n: u64, strict: i32, out: *mut i64) -> i32;
     pub fn ivx_probe_coverage(ctx: *mut IvxCtx, ix: *const IvxIndex, mem: i32, key: *const u32, start: *const i32,

@@ -18,6 +18,20 @@ use datafusion::common::{DataFusionError, Result};
 #[repr(C)] pub struct BrhBatch { pub array: *const FFI_ArrowArray, pub schema: *const FFI_ArrowSchema }
 #[repr(C)] pub struct BrhColumns { pub keys: *const *const c_char, pub n_keys: c_int, pub start: *const c_char, pub end: *const c_char }
 
+/// `join_type` of `brh_join_stream_open` (the BRH_JOIN_* enum of the header).  From LEFT_SEMI on: SQL semantics over the
+/// build side's match marks -- LeftSemi / LeftAnti groups give no result, and `finish` ends with one result of
+/// `n_batches == 0` that carries the build-side rows (probe_idx all NULL, or empty for LeftSemi / LeftAnti): take the
+/// build columns with build_idx and extend the probe columns with NULLs, there is no probe batch to concatenate.
+pub const BRH_JOIN_INNER: c_int = 0;
+pub const BRH_JOIN_RIGHT_SEMI: c_int = 1;
+pub const BRH_JOIN_RIGHT_ANTI: c_int = 2;
+pub const BRH_JOIN_NEAREST: c_int = 3;
+pub const BRH_JOIN_LEFT_SEMI: c_int = 4;
+pub const BRH_JOIN_LEFT_ANTI: c_int = 5;
+pub const BRH_JOIN_LEFT: c_int = 6;
+pub const BRH_JOIN_RIGHT: c_int = 7;
+pub const BRH_JOIN_FULL: c_int = 8;
+
 #[link(name = "bio_ranges_hip")]
 extern "C" {
     pub fn brh_session_create(device_ordinal: c_int, out: *mut *mut BrhSession) -> c_int;
