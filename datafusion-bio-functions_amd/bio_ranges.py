@@ -3,6 +3,7 @@
 
     count_overlaps('l','r'), coverage('l','r'), nearest('l','r',k,overlap,distance),
     overlap('l','r'[,mode]), merge('t'[,min_dist]), subtract('l','r'), cluster('t'[,min_dist]), complement('t'[,'view']),
+    depth('reads') of the pileup crate,
     and the SQL range join handled by IntervalJoinExec
 
 Argument meaning and output schemas follow R/src/table_function.rs and the providers
@@ -310,6 +311,24 @@ class Session:
                 V.close()
         key = cols[0] if isinstance(cols[0], str) else cols[0][0]
         return pa.table([_import(*o) for o in outs], names=[key, cols[1], cols[2]])
+
+
+    # ---- depth (bio-function-pileup: table_function.rs depth(); events.rs + coverage.rs)
+    def depth(self, reads, prior=None, lengths=None, filter_flag=1796, min_mapq=0):
+        """coverage blocks of a reads table (chrom, start UInt32, flags UInt32, mapping_quality UInt32, cigar Binary):
+        -> contig Utf8, pos_start Int32, pos_end Int32, coverage Int16.  prior: the blocks of an earlier call, added in;
+        lengths: a table (name, length) that turns the reference's dense-mode clipping on."""
+        tabs = [_Exported(t) if t is not None else None for t in (reads, prior, lengths)]
+        outs = [_out() for _ in range(4)]
+        try:
+            b = [t.c if t is not None else _Batch(None, None) for t in tabs]
+            self._chk(lib().brh_depth(self.h, b[0], b[1], b[2], C.c_uint32(int(filter_flag)), C.c_uint32(int(min_mapq)),
+                                      *[C.byref(x) for pair in outs for x in pair]))
+        finally:
+            for t in tabs:
+                if t is not None:
+                    t.close()
+        return pa.table([_import(*o) for o in outs], names=["contig", "pos_start", "pos_end", "coverage"])
 
 
 class JoinStream:

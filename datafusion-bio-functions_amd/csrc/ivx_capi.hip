@@ -1140,6 +1140,67 @@ extern "C" ivx_status ivx_complement(ivx_ctx *ctx, int mem, const uint32_t *key,
     return IVX_OK;
 }
 
+extern "C" ivx_status ivx_depth(ivx_ctx *ctx, int mem,
+                                const uint32_t *rkey, const uint32_t *rpos, const uint32_t *rflags, const uint32_t *rmapq,
+                                const int32_t *cigar_offsets, const uint32_t *cigar_ops, uint64_t n_reads,
+                                const uint32_t *skey, const uint32_t *sstart, const uint32_t *send, const int32_t *sweight, uint64_t n_seg,
+                                uint32_t n_keys, const uint32_t *key_len, uint32_t filter_flag, uint32_t min_mapq,
+                                uint32_t *out_key, uint32_t *out_start, uint32_t *out_end, int32_t *out_cov,
+                                uint64_t cap, uint64_t *n_out)
+{
+    if (!ctx) return IVX_ERR_INVALID;
+    if (!n_out) return ctx->fail(IVX_ERR_INVALID, "null n_out");
+    *n_out = 0;
+    if (mem != IVX_MEM_HOST && mem != IVX_MEM_DEVICE) return ctx->fail(IVX_ERR_INVALID, "bad mem");
+    if (n_reads && (!rpos || !cigar_offsets)) return ctx->fail(IVX_ERR_INVALID, "depth: null read position or CIGAR offset column");
+    if (n_seg && (!sstart || !send)) return ctx->fail(IVX_ERR_INVALID, "depth: null segment coordinate column");
+    if (n_reads >= 0xFFFFFFFFull || n_seg >= 0x7FFFFFFFull) return ctx->fail(IVX_ERR_INVALID, "depth: too many rows in one call");
+    if (n_keys == 0 && !rkey && !skey) n_keys = 1;
+    ctx->sub_plan.valid = false; ctx->join_plan.valid = false;   // as any other call between a sizing call and its fill
+    CallMetrics cm(ctx, false, n_reads + n_seg);
+    if (n_reads == 0 && n_seg == 0) return IVX_OK;
+    IVX_HIP(ctx, hipSetDevice(ctx->device));
+    // IVX_MEM_HOST: the ops column is staged up to the last offset (the device checks the offsets before it reads an op)
+    u64 n_ops_host = 0;
+    if (mem == IVX_MEM_HOST && n_reads && cigar_offsets[n_reads] > 0) n_ops_host = (u64)cigar_offsets[n_reads] / 4;
+    if (n_ops_host && !cigar_ops) return ctx->fail(IVX_ERR_INVALID, "depth: null CIGAR data buffer");
+    const u32 *drk, *drp, *drf, *drm, *dops, *dsk, *dss, *dse, *dkl; const i32 *doff, *dsw;
+    u32 *ok, *os, *oe; i32 *oc;
+    IVX_TRY(stage_in(ctx, mem, WS_IN_KEY, rkey, n_reads, &drk));
+    IVX_TRY(stage_in(ctx, mem, WS_IN_START, rpos, n_reads, &drp));
+    IVX_TRY(stage_in(ctx, mem, WS_IN_END, rflags, n_reads, &drf));
+    IVX_TRY(stage_in(ctx, mem, WS_IN2_KEY, rmapq, n_reads, &drm));
+    IVX_TRY(stage_in(ctx, mem, WS_IN2_START, n_reads ? cigar_offsets : nullptr, n_reads + 1, &doff));
+    IVX_TRY(stage_in(ctx, mem, WS_IN2_END, cigar_ops, n_ops_host, &dops));
+    IVX_TRY(stage_in(ctx, mem, WS_IN3_KEY, skey, n_seg, &dsk));
+    IVX_TRY(stage_in(ctx, mem, WS_IN3_START, sstart, n_seg, &dss));
+    IVX_TRY(stage_in(ctx, mem, WS_IN3_END, send, n_seg, &dse));
+    IVX_TRY(stage_in(ctx, mem, WS_IN3_WEIGHT, sweight, n_seg, &dsw));
+    IVX_TRY(stage_in(ctx, mem, WS_IN_KEYLEN, key_len, (u64)n_keys, &dkl));
+    IVX_TRY(stage_out(ctx, mem, WS_OUT_A, out_key, cap, &ok));
+    IVX_TRY(stage_out(ctx, mem, WS_OUT_B, out_start, cap, &os));
+    IVX_TRY(stage_out(ctx, mem, WS_OUT_C, out_end, cap, &oe));
+    IVX_TRY(stage_out(ctx, mem, WS_OUT_D, out_cov, cap, &oc));
+    const bool sizing = cap == 0 && !out_key && !out_start && !out_end && !out_cov;
+    u64 m = 0;
+    {
+        KernelTimer t(ctx);
+        ivx_status st = ivx_depth_device(ctx, drk, drp, drf, drm, doff, dops, n_reads, dsk, dss, dse, dsw, n_seg,
+                                         n_keys, dkl, filter_flag, min_mapq, ok, os, oe, oc, cap, &m);
+        *n_out = m;
+        if (st != IVX_OK) return st;
+    }
+    if (!sizing) {
+        cm.out(m);
+        IVX_TRY(copy_out(ctx, mem, out_key, ok, m));
+        IVX_TRY(copy_out(ctx, mem, out_start, os, m));
+        IVX_TRY(copy_out(ctx, mem, out_end, oe, m));
+        IVX_TRY(copy_out(ctx, mem, out_cov, oc, m));
+    }
+    if (mem == IVX_MEM_HOST) IVX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return IVX_OK;
+}
+
 extern "C" ivx_status ivx_take_fixed(ivx_ctx *ctx, int mem, const void *src, uint32_t width, uint64_t n_src,
                                      const uint8_t *src_valid_bits, const uint32_t *idx, uint64_t n, void *out, uint8_t *out_valid)
 {

@@ -154,8 +154,10 @@ enum {
     WS_SORTHIST,                                                                    // radix-sort histograms
     WS_SA0, WS_SA1, WS_SA2, WS_SB0, WS_SB1, WS_SB2,                                 // sort ping/pong records
     WS_RA0, WS_RA1, WS_RA2, WS_RB0, WS_RB1, WS_RB2,                                 // second record set (subtract's right side)
-    WS_T0, WS_T1, WS_T2, WS_T3, WS_T4, WS_T5, WS_T6, WS_T7, WS_T8, WS_T9            // per-op temporaries
+    WS_T0, WS_T1, WS_T2, WS_T3, WS_T4, WS_T5, WS_T6, WS_T7, WS_T8, WS_T9,           // per-op temporaries
+    WS_IN3_KEY, WS_IN3_START, WS_IN3_END, WS_IN3_WEIGHT, WS_IN_KEYLEN               // staged host inputs of depth(): the weighted segments, the key lengths
 };
+static_assert(WS_IN_KEYLEN < IVX_NSCRATCH, "scratch slot ids must fit the context's slot array");
 
 // ---------------------------------------------------------------- indexes
 #ifndef IVX_LSTEP
@@ -303,5 +305,12 @@ ivx_status ivx_mark_probe_regions(ivx_ctx *ctx, const JoinIndexView &jv, u32 nre
                                   u32 *marks, bool has_filter, bool pk24, bool fast, bool *took);
 ivx_status ivx_bits_mark_device(ivx_ctx *ctx, const u32 *idx, u64 n, u32 *bits, u64 n_bits);
 ivx_status ivx_bits_select_device(ivx_ctx *ctx, const u32 *bits, u64 n_bits, int want_set, u32 *out, u64 cap, u64 *n_out);
+
+// ivx_depth.hip: coverage blocks from reads with binary CIGARs and from weighted segments (device pointers)
+ivx_status ivx_depth_device(ivx_ctx *ctx, const u32 *rkey, const u32 *rpos, const u32 *rflags, const u32 *rmapq,
+                            const i32 *cigar_offsets, const u32 *cigar_ops, u64 n_reads,
+                            const u32 *skey, const u32 *sstart, const u32 *send, const i32 *sweight, u64 n_seg,
+                            u32 nkeys, const u32 *key_len, u32 filter_flag, u32 min_mapq,
+                            u32 *ok, u32 *os, u32 *oe, i32 *oc, u64 cap, u64 *n_out);
 
 ivx_status ivx_index_alloc(ivx_ctx *ctx, ivx_index *ix, size_t bytes, void **out);

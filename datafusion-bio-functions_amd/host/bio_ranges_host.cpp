@@ -656,6 +656,174 @@ extern "C" int brh_complement(brh_session *s, brh_batch table, brh_columns cols,
     return 0;
 }
 
+// ---- depth(): the pileup crate's coverage blocks (bio-function-pileup process_batch* + *_to_coverage_blocks)
+namespace {
+
+// a UInt32 column of the reads batch (schema.rs:7-11); the validity of flags / mapping_quality is not read, as in the reference
+int get_u32(brh_session *s, brh_batch t, const char *name, const ArrowArray **out)
+{
+    const int c = find_col(t.schema, name);
+    if (c < 0) return fail(s, "depth: column '" + std::string(name) + "' not found in batch with columns: " + column_list(t.schema));
+    if (std::strcmp(t.schema->children[c]->format, "I"))
+        return fail(s, "depth: unsupported data type " + std::string(t.schema->children[c]->format) + " for column '" + name + "'; expected UInt32");
+    *out = t.array->children[c];
+    return 0;
+}
+
+bool slot_null(const ArrowArray *a, int64_t i)
+{
+    if (a->n_buffers < 1 || !a->buffers[0] || a->null_count == 0) return false;
+    const uint8_t *v = (const uint8_t *)a->buffers[0];
+    const int64_t j = i + a->offset;
+    return !((v[j >> 3] >> (j & 7)) & 1);
+}
+
+// contig names -> ids in byte order (both of the reference's modes sort their contigs: coverage.rs:75-76,
+// physical_exec.rs:400-402); id_of gives IVX_NULL_IDX for a name the dictionary lacks
+struct NameDict {
+    std::vector<std::string> names;
+    std::unordered_map<std::string_view, uint32_t> ids;
+    void finish(std::vector<std::string_view> &uniq)
+    {
+        std::sort(uniq.begin(), uniq.end());
+        uniq.erase(std::unique(uniq.begin(), uniq.end()), uniq.end());
+        names.assign(uniq.begin(), uniq.end());
+        for (uint32_t i = 0; i < names.size(); i++) ids.emplace(std::string_view(names[i]), i);
+    }
+    uint32_t id_of(std::string_view k) const { auto it = ids.find(k); return it == ids.end() ? IVX_NULL_IDX : it->second; }
+};
+
+void collect_names(const StrCol &c, std::vector<std::string_view> *uniq)
+{
+    std::string_view last; bool have = false;
+    for (int64_t i = 0; i < c.a->length; i++) {
+        if (c.null_at(i)) continue;
+        const std::string_view k = c.at(i);
+        if (have && k == last) continue;
+        last = k; have = true;
+        uniq->push_back(k);
+    }
+}
+
+void ids_of(const StrCol &c, const NameDict &d, std::vector<uint32_t> *out)
+{
+    out->resize((size_t)c.a->length);
+    std::string_view last; uint32_t last_id = IVX_NULL_IDX; bool have = false;
+    for (int64_t i = 0; i < c.a->length; i++) {
+        if (c.null_at(i)) { (*out)[i] = IVX_NULL_IDX; continue; }
+        const std::string_view k = c.at(i);
+        if (!have || k != last) { last_id = d.id_of(k); last = k; have = true; }
+        (*out)[i] = last_id;
+    }
+}
+
+}  // namespace
+
+extern "C" int brh_depth(brh_session *s, brh_batch reads, brh_batch prior, brh_batch lengths, uint32_t filter_flag, uint32_t min_mapq,
+                         ArrowArray *contig, ArrowSchema *contig_schema, ArrowArray *pos_start, ArrowSchema *pos_start_schema,
+                         ArrowArray *pos_end, ArrowSchema *pos_end_schema, ArrowArray *coverage, ArrowSchema *coverage_schema)
+{
+    if (!s) return 1;
+    if (!reads.array || !reads.schema) return fail(s, "depth: null reads batch");
+    const bool has_prior = prior.array != nullptr, has_len = lengths.array != nullptr;
+    // ---- the reads batch (events.rs:106-112)
+    StrCol chrom;
+    const ArrowArray *start, *flags, *mapq;
+    if (get_contig(s, reads, "chrom", &chrom) || get_u32(s, reads, "start", &start) || get_u32(s, reads, "flags", &flags) ||
+        get_u32(s, reads, "mapping_quality", &mapq)) return 1;
+    const int cc = find_col(reads.schema, "cigar");
+    if (cc < 0) return fail(s, "depth: column 'cigar' not found in batch with columns: " + column_list(reads.schema));
+    const char *cf = reads.schema->children[cc]->format;
+    if (!std::strcmp(cf, "u") || !std::strcmp(cf, "U") || !std::strcmp(cf, "vu"))
+        return fail(s, "depth: string CIGAR columns are not supported, use the binary CIGAR column");
+    if (std::strcmp(cf, "z")) return fail(s, "depth: unsupported data type " + std::string(cf) + " for column 'cigar'; expected Binary");
+    const ArrowArray *cigar = reads.array->children[cc];
+    const uint64_t n_reads = (uint64_t)reads.array->length;
+    // ---- prior blocks (the output of an earlier call) and the length table
+    StrCol pcontig, lname;
+    const ArrowArray *pstart = nullptr, *pend = nullptr, *pcov = nullptr;
+    char pcov_fmt = 0;
+    uint64_t n_seg = 0;
+    if (has_prior) {
+        if (get_contig(s, prior, "contig", &pcontig)) return 1;
+        const char *names[3] = {"pos_start", "pos_end", "coverage"};
+        const ArrowArray **outp[3] = {&pstart, &pend, &pcov};
+        for (int k = 0; k < 3; k++) {
+            const int c = find_col(prior.schema, names[k]);
+            if (c < 0) return fail(s, "depth: column '" + std::string(names[k]) + "' not found in the prior batch with columns: " + column_list(prior.schema));
+            const char *f = prior.schema->children[c]->format;
+            const bool ok = k < 2 ? (!std::strcmp(f, "i") || !std::strcmp(f, "I")) : (!std::strcmp(f, "s") || !std::strcmp(f, "i"));
+            if (!ok) return fail(s, "depth: unsupported data type " + std::string(f) + " for column '" + names[k] + "' of the prior batch; expected " + (k < 2 ? "Int32" : "Int16"));
+            if (k == 2) pcov_fmt = f[0];
+            *outp[k] = prior.array->children[c];
+        }
+        n_seg = (uint64_t)prior.array->length;
+    }
+    std::vector<int64_t> len64;
+    if (has_len) {
+        PosCol pl;
+        if (get_contig(s, lengths, "name", &lname) || get_pos(s, lengths, "length", "length", &pl) || resolve_i64(s, pl, &len64)) return 1;
+    }
+    // ---- contig ids.  With a length table only its contigs exist: reads (and prior blocks) elsewhere are skipped (events.rs:247-260)
+    NameDict dict;
+    {
+        std::vector<std::string_view> uniq;
+        if (has_len) collect_names(lname, &uniq);
+        else { collect_names(chrom, &uniq); if (has_prior) collect_names(pcontig, &uniq); }
+        dict.finish(uniq);
+    }
+    const uint32_t nk = (uint32_t)std::max<size_t>(dict.names.size(), 1);
+    std::vector<uint32_t> rkey, skey, ss, se, key_len;
+    std::vector<int32_t> sw;
+    ids_of(chrom, dict, &rkey);
+    for (uint64_t i = 0; i < n_reads; i++) if (slot_null(start, (int64_t)i)) rkey[i] = IVX_NULL_IDX;       // events.rs:114
+    if (has_prior) {
+        ids_of(pcontig, dict, &skey);
+        ss.resize(n_seg); se.resize(n_seg); sw.resize(n_seg);
+        for (uint64_t j = 0; j < n_seg; j++) {
+            ss[j] = ((const uint32_t *)pstart->buffers[1])[pstart->offset + j];            // Int32 positions are the u32's bits (`as i32`)
+            se[j] = ((const uint32_t *)pend->buffers[1])[pend->offset + j];
+            sw[j] = pcov_fmt == 's' ? (int32_t)((const int16_t *)pcov->buffers[1])[pcov->offset + j] : ((const int32_t *)pcov->buffers[1])[pcov->offset + j];
+        }
+    }
+    if (has_len) {
+        key_len.assign(nk, 0);
+        for (int64_t i = 0; i < lname.a->length; i++) {
+            if (lname.null_at(i)) continue;
+            const uint32_t k = dict.id_of(lname.at(i));
+            const int64_t v = len64[(size_t)i];
+            key_len[k] = v < 0 ? 0u : (v > (int64_t)UINT32_MAX ? UINT32_MAX : (uint32_t)v);
+        }
+    }
+    const uint32_t *rpos = n_reads ? (const uint32_t *)start->buffers[1] + start->offset : nullptr;
+    const uint32_t *rflags = n_reads ? (const uint32_t *)flags->buffers[1] + flags->offset : nullptr;
+    const uint32_t *rmapq = n_reads ? (const uint32_t *)mapq->buffers[1] + mapq->offset : nullptr;
+    const int32_t *coff = n_reads ? (const int32_t *)cigar->buffers[1] + cigar->offset : nullptr;
+    const uint32_t *cops = n_reads ? (const uint32_t *)cigar->buffers[2] : nullptr;
+    // ---- sizing call, then the fill call
+    auto call = [&](uint32_t *ok, uint32_t *os, uint32_t *oe, int32_t *oc, uint64_t cap, uint64_t *m) {
+        return ivx_depth(s->ctx, IVX_MEM_HOST, rkey.data(), rpos, rflags, rmapq, coff, cops, n_reads,
+                         has_prior ? skey.data() : nullptr, ss.data(), se.data(), has_prior ? sw.data() : nullptr, n_seg,
+                         nk, has_len ? key_len.data() : nullptr, filter_flag, min_mapq, ok, os, oe, oc, cap, m);
+    };
+    uint64_t m = 0, m2 = 0;
+    ivx_status st = call(nullptr, nullptr, nullptr, nullptr, 0, &m);
+    if (st != IVX_OK) return fail_ivx(s, st);
+    std::vector<uint32_t> ok(m ? m : 1), os(m ? m : 1), oe(m ? m : 1); std::vector<int32_t> oc(m ? m : 1);
+    if (m) {
+        st = call(ok.data(), os.data(), oe.data(), oc.data(), m, &m2);
+        if (st != IVX_OK) return fail_ivx(s, st);
+    }
+    // ---- schema.rs:28-41: contig Utf8, pos_start / pos_end Int32 (`as i32`), coverage Int16 (`as i16`)
+    std::vector<int32_t> o32s(m2 ? m2 : 1), o32e(m2 ? m2 : 1); std::vector<int16_t> o16(m2 ? m2 : 1);
+    for (uint64_t i = 0; i < m2; i++) { o32s[i] = (int32_t)os[i]; o32e[i] = (int32_t)oe[i]; o16[i] = (int16_t)oc[i]; }
+    make_utf8(contig, dict.names, ok.data(), (int64_t)m2); make_schema(contig_schema, "u", "contig", true);
+    make_primitive<int32_t>(pos_start, o32s.data(), (int64_t)m2, nullptr); make_schema(pos_start_schema, "i", "pos_start", false);
+    make_primitive<int32_t>(pos_end, o32e.data(), (int64_t)m2, nullptr); make_schema(pos_end_schema, "i", "pos_end", false);
+    make_primitive<int16_t>(coverage, o16.data(), (int64_t)m2, nullptr); make_schema(coverage_schema, "s", "coverage", false);
+    return 0;
+}
+
 // ---- f3: payload gather
 namespace {
 

@@ -28,7 +28,7 @@ SYMBOLS = [
     "ivx_cluster", "ivx_complement", "ivx_take_fixed", "ivx_take_utf8", "ivx_take_bits", "ivx_take_view",
     "ivx_ctx_metrics", "ivx_ctx_reset_metrics", "ivx_ctx_set_memory_limit", "ivx_ctx_trim", "ivx_scatter_fixed",
     "ivx_ctx_reserved_bytes", "ivx_ctx_set_build_overlap", "ivx_index_layout",
-    "ivx_probe_mark_build", "ivx_bits_mark", "ivx_bits_select",
+    "ivx_probe_mark_build", "ivx_bits_mark", "ivx_bits_select", "ivx_depth",
 ]
 
 # slots of ivx_index_layout (include/ivx.h IVX_LAYOUT_*), in order
@@ -78,6 +78,10 @@ def lib():
         L.ivx_index_rows.restype = C.c_uint64
         L.ivx_index_device_bytes.restype = C.c_uint64
         L.ivx_ctx_reserved_bytes.restype = C.c_uint64
+        L.ivx_depth.restype = C.c_int
+        L.ivx_depth.argtypes = ([C.c_void_p, C.c_int] + [C.c_void_p] * 6 + [C.c_uint64] + [C.c_void_p] * 4 + [C.c_uint64] +
+                                [C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32] + [C.c_void_p] * 4 +
+                                [C.c_uint64, C.POINTER(C.c_uint64)])
         _lib = L
     return _lib
 
@@ -487,6 +491,57 @@ class Ctx:
         self._chk(st)
         m2 = m2.value
         return ok[:m2], os_[:m2], oe[:m2]
+
+    # ---- g: depth ----
+    def depth(self, rkey=None, rpos=None, rflags=None, rmapq=None, cigar_offsets=None, cigar_ops=None,
+              skey=None, sstart=None, send=None, sweight=None, n_keys=None, key_len=None, filter_flag=1796, min_mapq=0,
+              cap=None, outputs=(True, True, True, True)):
+        """coverage blocks of reads (rkey/rpos/rflags/rmapq + the Arrow Binary column cigar_offsets [bytes] / cigar_ops
+        [packed u32 ops]) and of weighted segments (skey/sstart/send/sweight); numpy arrays or torch device tensors.
+        cap=None: a sizing call, then the fill call.  outputs: which of (key, start, end, coverage) to ask for.
+        -> (key, start, end, coverage), None where not asked for."""
+        cols = [rkey, rpos, rflags, rmapq, cigar_offsets, cigar_ops, skey, sstart, send, sweight, key_len]
+        mem = _mem_of(*cols)
+        n_reads = 0 if rpos is None else (int(rpos.numel()) if _is_torch(rpos) else len(rpos))
+        n_seg = 0 if sstart is None else (int(sstart.numel()) if _is_torch(sstart) else len(sstart))
+        if mem == MEM_DEVICE:
+            assert all(c is None or c.is_contiguous() for c in cols)
+        else:
+            dts = [np.uint32, np.uint32, np.uint32, np.uint32, np.int32, np.uint32, np.uint32, np.uint32, np.uint32, np.int32, np.uint32]
+            cols = [_np(c, dt) for c, dt in zip(cols, dts)]
+        rkey, rpos, rflags, rmapq, cigar_offsets, cigar_ops, skey, sstart, send, sweight, key_len = cols
+        if n_keys is None:
+            if key_len is not None:
+                n_keys = int(key_len.numel()) if _is_torch(key_len) else len(key_len)
+            else:
+                mk = 0
+                for k_, n_ in ((rkey, n_reads), (skey, n_seg)):
+                    if k_ is not None and n_:
+                        kk = k_.to("cpu").numpy().view(np.uint32) if _is_torch(k_) else k_
+                        kk = kk[kk != NULL_IDX]
+                        if len(kk):
+                            mk = max(mk, int(kk.max()))
+                n_keys = mk + 1
+        args = (C.c_int(mem), _ptr(rkey), _ptr(rpos), _ptr(rflags), _ptr(rmapq), _ptr(cigar_offsets), _ptr(cigar_ops), n_reads,
+                _ptr(skey), _ptr(sstart), _ptr(send), _ptr(sweight), n_seg, n_keys, _ptr(key_len), int(filter_flag), int(min_mapq))
+
+        def bufs(cap):
+            if mem == MEM_DEVICE:
+                import torch
+                dev = next(c for c in cols if c is not None).device
+                return [torch.empty(cap, dtype=torch.int32, device=dev) if w else None for w in outputs]
+            return [np.empty(cap, dt) if w else None for w, dt in zip(outputs, (np.uint32, np.uint32, np.uint32, np.int32))]
+        if cap is None:
+            m = C.c_uint64(0)
+            self._chk(lib().ivx_depth(self.h, *args, None, None, None, None, 0, C.byref(m)))
+            cap = max(m.value, 1)
+        out = bufs(cap)
+        m2 = C.c_uint64(0)
+        st = lib().ivx_depth(self.h, *args, *[_ptr(o) for o in out], cap, C.byref(m2))
+        if st == ERR_CAPACITY:
+            raise IvxError(st, f"{lib().ivx_last_error(self.h).decode()} (needed {m2.value})")
+        self._chk(st)
+        return tuple(None if o is None else o[:m2.value] for o in out)
 
     # ---- f3: compute::take of payload columns ----
     def take_fixed(self, src, idx, src_valid_bits=None, want_valid=True):

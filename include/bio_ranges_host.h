@@ -140,6 +140,25 @@ int brh_complement(brh_session *s, brh_batch table, brh_columns cols, brh_batch 
                    struct ArrowArray *start, struct ArrowSchema *start_schema,
                    struct ArrowArray *end, struct ArrowSchema *end_schema);
 
+/* depth('reads'): the pileup crate's coverage blocks (bio-function-pileup: events.rs process_batch / process_batch_dense,
+ * coverage.rs events_to_coverage_blocks / dense_depth_to_coverage_blocks) in one ivx_depth call.
+ * reads: a batch with the reference's column names (schema.rs:7-11): chrom Utf8 / LargeUtf8 / Utf8View; start, flags,
+ *   mapping_quality UInt32; cigar Binary (packed u32 ops).  Rows with a NULL chrom or start are skipped; the validity of flags
+ *   and mapping_quality is not read (events.rs:114-121).  A Utf8 cigar column is the error "depth: string CIGAR columns are
+ *   not supported, use the binary CIGAR column".
+ * prior (array == NULL: none): contig, pos_start, pos_end, coverage -- the output of an earlier call, fed in as weighted
+ *   segments: that is how coverage accumulates over batches.
+ * lengths (array == NULL: none): name Utf8, length (any integer type; clamped to 2^32-1) -- the reference's dense mode: events
+ *   beyond a contig's length are dropped, reads on a contig the table lacks are skipped (events.rs:247-260).
+ * Contig ids are assigned in byte order of the names (coverage.rs:75-76, physical_exec.rs:400-402).  Outputs
+ * (schema.rs:28-41): contig Utf8, pos_start Int32, pos_end Int32 (the u32 positions `as i32`), coverage Int16 (`as i16`),
+ * in the coordinate system `start` came in. */
+int brh_depth(brh_session *s, brh_batch reads, brh_batch prior, brh_batch lengths, uint32_t filter_flag, uint32_t min_mapq,
+              struct ArrowArray *contig, struct ArrowSchema *contig_schema,
+              struct ArrowArray *pos_start, struct ArrowSchema *pos_start_schema,
+              struct ArrowArray *pos_end, struct ArrowSchema *pos_end_schema,
+              struct ArrowArray *coverage, struct ArrowSchema *coverage_schema);
+
 /* compute::take of ONE payload column with an index array a join / nearest call returned
  * (interval_join.rs:1655-1667, nearest.rs:469-482), on the device.  column: any fixed-width primitive
  * (ints, floats, date/time/timestamp/duration, decimal128/256, fixed-size binary of 1/2/4/8/16/32 bytes),

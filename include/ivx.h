@@ -318,6 +318,38 @@ ivx_status ivx_complement(ivx_ctx *ctx, int mem,
                           uint32_t *out_key, int64_t *out_start, int64_t *out_end,
                           uint64_t cap, uint64_t *n_out);
 
+/* ---- g: depth(), the pileup crate's coverage blocks (bio-function-pileup: cigar.rs:1-13, :78-132, :177-230;
+ *      events.rs:111-137, :181-185; coverage.rs:25-65) from two input groups, either of which may be empty.
+ *      READS: read i has rkey[i] (nullable column: one key), rpos[i], rflags[i] / rmapq[i] (nullable columns: every
+ *      flag 0 / every mapq passes) and the packed ops cigar_ops[cigar_offsets[i]/4 .. cigar_offsets[i+1]/4), an op being
+ *      BAM's u32 (len = w >> 4, code = w & 15).  cigar_offsets[n_reads+1] are the BYTE offsets of an Arrow Binary column
+ *      (element 0 need not be 0), cigar_ops that column's data buffer.  A read is skipped when rkey[i] == IVX_NULL_IDX,
+ *      it has no ops, (rflags[i] & filter_flag) != 0, or rmapq[i] < min_mapq.  Otherwise, with ref = rpos[i]: codes
+ *      0, 7, 8 (M = X) emit (ref, +1), advance ref by len saturating at 2^32-1, and emit (ref, -1); codes 2, 3 (D N)
+ *      only advance; every other code does nothing.
+ *      WEIGHTED SEGMENTS: segment j emits (sstart[j], +w) and (send[j] + 1 saturating, -w), w = sweight ? sweight[j] : 1
+ *      (any int32; send < sstart is not checked; skey[j] == IVX_NULL_IDX skips the segment).  The blocks of an earlier
+ *      call, with their coverage as weight, are such segments: that is how coverage accumulates over batches.
+ *      key_len (nullable, [n_keys]): the reference's dense mode -- every event with position > key_len[key] is dropped.
+ *      BLOCKS, per key ascending: the deltas at equal positions are summed (int32 wrap-around), c_i is the running sum
+ *      after the i-th distinct position; every i with c_i != c_(i-1) and c_i != 0 that has a later such change in its
+ *      key gives (key, p_i, p_next - 1, c_i) (coverage.rs:38-62).  A key whose coverage never returns to 0 (clipping,
+ *      saturation) loses its last open block, as in the reference.  Output is ordered by (key, start).
+ *      cap = 0 with NULL outputs only counts; cap < *n_out is IVX_ERR_CAPACITY with *n_out = the size needed; any
+ *      output may be NULL on its own.  IVX_ERR_INVALID, found on the device before anything is indexed with the values:
+ *      a key id >= n_keys other than IVX_NULL_IDX; offsets that decrease or are not multiples of 4 (the reference's
+ *      chunks_exact(4) silently drops a ragged tail instead).  Drops the state a sizing call of another operation left
+ *      on the context; nothing is kept between a sizing call and the fill call of this one. */
+ivx_status ivx_depth(ivx_ctx *ctx, int mem,
+                     const uint32_t *rkey /* nullable */, const uint32_t *rpos,
+                     const uint32_t *rflags /* nullable */, const uint32_t *rmapq /* nullable */,
+                     const int32_t *cigar_offsets, const uint32_t *cigar_ops, uint64_t n_reads,
+                     const uint32_t *skey /* nullable */, const uint32_t *sstart, const uint32_t *send,
+                     const int32_t *sweight /* nullable */, uint64_t n_seg,
+                     uint32_t n_keys, const uint32_t *key_len /* nullable */, uint32_t filter_flag, uint32_t min_mapq,
+                     uint32_t *out_key, uint32_t *out_start, uint32_t *out_end, int32_t *out_cov,
+                     uint64_t cap, uint64_t *n_out);
+
 /* ---- f3: `compute::take` of payload columns with the index arrays the probes return
  *      (interval_join.rs:1655-1667, nearest.rs:469-482).  idx[i] == IVX_NULL_IDX or a null source
  *      slot (src_valid_bits: Arrow validity bitmap of the source, bit offset 0, nullable) gives

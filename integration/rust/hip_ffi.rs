@@ -88,6 +88,12 @@ extern "C" {
     pub fn ivx_complement(ctx: *mut IvxCtx, mem: i32, key: *const u32, start: *const i64, end: *const i64, n: u64,
                           vkey: *const u32, vstart: *const i64, vend: *const i64, nv: u64, n_keys: u32, strict: i32,
                           out_key: *mut u32, out_start: *mut i64, out_end: *mut i64, cap: u64, n_out: *mut u64) -> i32;
+    pub fn ivx_depth(ctx: *mut IvxCtx, mem: i32, rkey: *const u32, rpos: *const u32, rflags: *const u32, rmapq: *const u32,
+                     cigar_offsets: *const i32, cigar_ops: *const u32, n_reads: u64,
+                     skey: *const u32, sstart: *const u32, send: *const u32, sweight: *const i32, n_seg: u64,
+                     n_keys: u32, key_len: *const u32, filter_flag: u32, min_mapq: u32,
+                     out_key: *mut u32, out_start: *mut u32, out_end: *mut u32, out_cov: *mut i32,
+                     cap: u64, n_out: *mut u64) -> i32;
     pub fn ivx_take_fixed(ctx: *mut IvxCtx, mem: i32, src: *const c_void, width: u32, n_src: u64, src_valid_bits: *const u8,
                           idx: *const u32, n: u64, out: *mut c_void, out_valid: *mut u8) -> i32;
     pub fn ivx_scatter_fixed(ctx: *mut IvxCtx, mem: i32, src: *const c_void, width: u32, idx: *const u32, n: u64,
