@@ -17,6 +17,28 @@
 // the length field's all-ones value: 8 bits plus the row id's spare bits, at most 16 (the host passes rowbits = 32, i.e. no
 // spare bits, when the occupancy bitmap is in use: the partition kernel then has no register to carry the upper bits in)
 __host__ __device__ __forceinline__ u32 pk_maxlen(u32 rowbits) { const u32 spare = rowbits >= 32 ? 0u : 32u - rowbits; return (1u << (8u + (spare > 8u ? 8u : spare))) - 1u; }
+// the reading side of the format (the packing side is k_part_onepass, whose fields are parked across registers): rel = start
+// inside the region, len = the length field (pk_maxlen(rowbits): an escape), hi = the word's upper half, from which callers
+// that want the row id mask it (hi & rowmask; the lean kernels put that off: see k_fill_fast's copy-out)
+struct PkRow { u32 rel, len, hi; };
+__device__ __forceinline__ PkRow pk_unpack(u64 w, u32 rowbits)
+{
+    const u32 lo32 = (u32)w, hi32 = (u32)(w >> 32);
+    return PkRow{lo32 & 0xFFFFFFu, (lo32 >> 24) | ((rowbits < 32 ? (hi32 >> rowbits) & 0xFFu : 0u) << 8), hi32};
+}
+
+// Where routed row v of region r (v: its number inside the region, "virtual row") sits in the page pool.  A page-table entry
+// of 0 means the partition never published the page: that cannot happen once k_part_onepass has completed (it did in a
+// profiling build whose switch skipped the publication, and the page "0 - 1" then was a wild address).  The word of page 0
+// is returned instead, which is in bounds, and miss() is called: the fill kernels raise the fault word there, the per-row
+// value and mark kernels pass a no-op.
+template <class W, class Miss>
+__device__ __forceinline__ W *routed_word(const PageTab &pt, W *pool, u32 r, u32 v, Miss &&miss)
+{
+    u32 pg = pt.ptab[(u64)r * pt.pstride + (v >> pt.lgpg)];
+    if (pg == 0u) { pg = 1u; miss(); }
+    return pool + (((u64)(pg - 1u) << pt.lgpg) + (v & ((1u << pt.lgpg) - 1u)));
+}
 
 constexpr int RP_T = 1024;                 // probe kernels: one workgroup per CU (LDS-bound), 16 wavefronts
 constexpr int RP_W = RP_T / IVX_WAVE;

@@ -527,11 +527,10 @@ __global__ __launch_bounds__(RP_T) void k_probe_regions(JoinIndexView ix, const 
 #pragma unroll
                     for (int q = 0; q < B; q++) {
                         if (PK) {
-                            const u32 lo32 = (u32)nx[q], hi32 = (u32)(nx[q] >> 32);
-                            const u32 len = (lo32 >> 24) | ((rowbits < 32 ? (hi32 >> rowbits) & 0xFFu : 0u) << 8);
-                            prel[PK ? q : 0] = lo32 & 0xFFFFFFu; plen[PK ? q : 0] = len;
-                            qs[q] = (i32)((u32)S.rbase + (lo32 & 0xFFFFFFu)); qe[q] = (i32)((u32)qs[q] + len); rowv[q] = hi32 & rowmask;
-                            nxr[q] = len;                               // (kept for the escape test below; the row id prefetch slot is free here)
+                            const PkRow w = pk_unpack(nx[q], rowbits);
+                            prel[PK ? q : 0] = w.rel; plen[PK ? q : 0] = w.len;
+                            qs[q] = (i32)((u32)S.rbase + w.rel); qe[q] = (i32)((u32)qs[q] + w.len); rowv[q] = w.hi & rowmask;
+                            nxr[q] = w.len;                             // (kept for the escape test below; the row id prefetch slot is free here)
                         } else { qs[q] = (i32)(u32)nx[q]; qe[q] = (i32)(u32)(nx[q] >> 32); rowv[q] = nxr[q]; }
                         if (!nfull && b0 + (u64)q * (RP_W * IVX_WAVE) + ln < c_hi) okmask |= 1u << q;
                     }
@@ -595,20 +594,162 @@ __global__ __launch_bounds__(RP_T) void k_probe_regions(JoinIndexView ix, const 
     if (FILL && round) round_copy_out(L, pend_mine, pend_start, round - 1, wv, ob, op, cap);
 }
 
-// ------------------------------------------------------------------ lean fill probe (round 3)
-// The headline's fill pass again, for the case it always meets: packed 8-byte rows in region pages (k_part_onepass) and an
-// index whose every region is one LDS-resident level (hdr[HDR_FAST]).  Same slices, same staging ring and round-level
-// output reservation as k_probe_regions<fill>; what differs is what a wavefront executes per row -- that kernel is bound
-// by the instructions it issues, 224 per 64 rows:
-//  * work is dealt in CHUNKS of 8192 routed rows that never straddle a pool page (chunk k of region r = its virtual rows
-//    [8192 k, 8192 (k + 1)); wavefront w owns rows [512 w, 512 (w + 1)) of it), so the rows of a wavefront batch are
-//    64 * B consecutive words behind ONE wave-uniform pointer: loads are `scalar base + lane offset + immediate`, with no
-//    per-row bounds test, page lookup or 64-bit address arithmetic (a third of the old kernel's instructions);
+// ------------------------------------------------------------------ lean probes: what the three kernels share
+// k_fill_fast, k_rv_fast and k_mark_fast serve the case the headline always meets: packed 8-byte rows in region pages
+// (k_part_onepass) and an index whose every region is one LDS-resident level (hdr[HDR_FAST]).  They share how a workgroup
+// gets its rows (LeanRows), how a row finds its cell range in the staged slice (lean_cells) and what happens to a row the
+// packed form cannot carry (lean_list_slow, and rest_row in the *_rest kernels that walk the listed rows afterwards with
+// the generic walk over the index in global memory -- the lean kernels hold no generic code, and no scratch).  A kernel
+// itself is its LDS, what it does when the region changes and what it does with a row's candidates.
+
+// The rows of a workgroup, batch by batch.  Work is dealt in CHUNKS of 8192 routed rows that never straddle a pool page
+// (chunk k of region r = its virtual rows [8192 k, 8192 (k + 1)); wavefront w owns rows [512 w, 512 (w + 1)) of it), so the
+// rows of a wavefront batch are 64 * B consecutive words behind ONE wave-uniform pointer: loads are `scalar base + lane
+// offset + immediate`, with no per-row bounds test, page lookup or 64-bit address arithmetic (a third of the general
+// kernel's instructions).  A workgroup takes an equal share of all chunks.  One batch is always in flight: take() hands
+// out the one whose loads were started before and starts the next one's.
+template <int B, class W>
+struct LeanRows {
+    static constexpr u32 WB = IVX_WAVE * B;                           // rows of a wavefront batch
+    static constexpr u32 SUB = 8u / B;                                // batches a wavefront makes of its 512 rows of a chunk
+    const u32 *s_cfirst, *rcur; PageTab pt; W *pool;
+    u32 rowbits, maxlen, wv, ln, nreg, c_lo, nbatch;
+    // the batch in flight: its region, first virtual row and row count are wave-uniform, its rows 64 * B consecutive words
+    // of one pool page behind src
+    u32 r, first, cnt; W *src; u64 nx[B];
+    struct Batch { u32 first, cnt; W *src; };
+
+    // The workgroup's share of the chunks (all threads; ONE barrier inside, which also covers whatever LDS the kernel
+    // initialised before the call).  s_cf: LDS for cfirst, the first chunk of every region.  False: no chunk falls to this
+    // workgroup, which leaves.  (init only tests; the work of a workgroup that stays is start's: with it on one side of the
+    // test here the compiler kept a second copy of the test behind the call.)
+    __device__ __forceinline__ bool init(const JoinIndexView &ix, u32 *s_cf, const u32 *cfirst, const u32 *rcur_, const PageTab &pt_, W *pool_, u32 rowbits_)
+    {
+        s_cfirst = s_cf; rcur = rcur_; pt = pt_; pool = pool_; rowbits = rowbits_; maxlen = pk_maxlen(rowbits_);
+        wv = __builtin_amdgcn_readfirstlane(threadIdx.x / IVX_WAVE); ln = lane_id();
+        nreg = ix.hdr[HDR_NREG];
+        for (u32 t = threadIdx.x; t <= nreg; t += RP_T) s_cf[t] = cfirst[t];
+        __syncthreads();
+        const u32 nchunk = s_cf[nreg];
+        c_lo = (u32)((u64)nchunk * blockIdx.x / gridDim.x);
+        const u32 c_hi = (u32)((u64)nchunk * (blockIdx.x + 1) / gridDim.x);
+        nbatch = (c_hi - c_lo) * SUB;
+        return c_lo < c_hi;
+    }
+    // batch 0 in flight.  miss(): see routed_word
+    template <class Miss>
+    __device__ __forceinline__ void start(Miss &&miss)
+    {
+        {   // last region whose first chunk is <= c_lo
+            u32 a = 0, b = nreg;
+            while (a < b) { const u32 m = (a + b + 1) >> 1; if (s_cfirst[m] <= c_lo) a = m; else b = m - 1; }
+            r = a;
+        }
+        src = pool;
+        prefetch(0, miss);
+    }
+    // batch i of this wavefront becomes the one in flight (r only ever moves forward)
+    template <class Miss>
+    __device__ __forceinline__ void prefetch(u32 i, Miss &&miss)
+    {
+        const u32 c = c_lo + i / SUB, sb = i % SUB;
+        while (c >= s_cfirst[r + 1]) r++;
+        first = (c - s_cfirst[r]) * FP_CHUNK + wv * (8u * IVX_WAVE) + sb * WB;
+        const u32 rows = rcur[r];
+        cnt = rows > first ? (rows - first < WB ? rows - first : WB) : 0u;
+        if (cnt) {
+            src = routed_word(pt, pool, r, first, miss);
+#pragma unroll
+            for (int q = 0; q < B; q++) nx[q] = src[q * IVX_WAVE + ln];      // (inside the page whatever cnt is: pages are whole)
+        }
+    }
+    // batch i (the caller has read its region from `r`): where it is, and its rows decoded -- start inside the region, length,
+    // the word's upper half; batch i + 1 is in flight afterwards
+    template <class Miss>
+    __device__ __forceinline__ Batch take(u32 i, u32 (&rel)[B], u32 (&len)[B], u32 (&hi)[B], Miss &&miss)
+    {
+        const Batch b{first, cnt, src};
+#pragma unroll
+        for (int q = 0; q < B; q++) { const PkRow w = pk_unpack(nx[q], rowbits); rel[q] = w.rel; len[q] = w.len; hi[q] = w.hi; }
+        if (i + 1 < nbatch) prefetch(i + 1, miss);
+        return b;
+    }
+};
+
+// The cell offsets [ca, cb) of a batch's B rows in the staged slice S (`fast`: see probe_row_rel), all fetched before the
+// first candidate loop runs: their LDS reads are in flight together.  slow: the lane's rows the packed form cannot carry
+// (lean_list_slow takes them); okm: its rows that are walked here.
+template <int B, bool FULL>
+__device__ __forceinline__ void lean_cells_of(const Slice &S, const u32 (&rel)[B], const u32 (&len)[B], u32 maxlen, u32 cnt, u32 ln,
+                                              u32 (&ca)[B], u32 (&cb)[B], u32 &slow, u32 &okm)
+{
+    const u32 sh0 = S.sh0, off = S.off, cmax = S.cmax, ncm1 = S.ncm1;
+#pragma unroll
+    for (int q = 0; q < B; q++) {
+        const u32 t = ((rel[q] + 1u) >> sh0) + off;                      // first cell a matching build row can start in: one cell back
+        const u32 bl0 = (t > 1u ? t : 1u) - 1u;
+        const u32 bh0 = ((rel[q] + len[q]) >> sh0) + off;
+        const u32 bh = bh0 < cmax ? bh0 : cmax;
+        bool bad = len[q] == maxlen || bh >= ncm1;                       // escape, or past the slice's halo: the rest list's
+        const bool ok = FULL || (u32)q * IVX_WAVE + ln < cnt;            // (only a region's last batch is short)
+        if (ok && bad) slow |= 1u << q;
+        if (ok && !bad) okm |= 1u << q;
+        bad |= !ok;
+        // no row to walk: an empty range (twice the same offset); a row behind the key's last cell gets one by the clamp
+        const u32 e1 = bad ? 0u : bh + 1u;
+        const u32 bl = bl0 < e1 ? bl0 : e1;
+        ca[q] = S.s_off[bl];
+        cb[q] = S.s_off[e1];
+    }
+}
+// (two copies of the block, chosen once per batch: a per-row choice between "every lane holds B rows" and "test the lane's
+//  row number" was two branches per row)
+template <int B>
+__device__ __forceinline__ void lean_cells(const Slice &S, const u32 (&rel)[B], const u32 (&len)[B], u32 maxlen, u32 cnt, u32 ln,
+                                           u32 (&ca)[B], u32 (&cb)[B], u32 &slow, u32 &okm)
+{
+    slow = 0; okm = 0;
+    if (cnt == IVX_WAVE * B) lean_cells_of<B, true>(S, rel, len, maxlen, cnt, ln, ca, cb, slow, okm);
+    else lean_cells_of<B, false>(S, rel, len, maxlen, cnt, ln, ca, cb, slow, okm);
+}
+
+// this lane's slow rows of the batch at virtual row `first` of region r, one by one, to the rest list (their cell ranges
+// were empty: nothing was walked for them)
+template <int B>
+__device__ __forceinline__ void lean_list_slow(u32 slow, u32 r, u32 first, u32 ln, u64 *__restrict__ rest_rows, u32 *rest_n)
+{
+#pragma unroll
+    for (int q = 0; q < B; q++)
+        if ((slow >> q) & 1u) rest_rows[atomicAdd(rest_n + 1, 1u)] = (u64)(first + (u32)q * IVX_WAVE + ln) | ((u64)r << 32);
+}
+
+// One listed row -- routed row v of region r -- as the *_rest kernels want it: its word's place in the pool, its row id, the
+// word's upper half and its closed coordinates, from the word or -- an escape -- from the input columns by the row id (adj: the
+// strict mode's shrinking, which the routing pass applied to the rows it packed)
+template <class W> struct RestRow { W *slot; u32 row, hi; i32 qs, qe; };
+template <class W, class Miss>
+__device__ __forceinline__ RestRow<W> rest_row(const JoinIndexView &ix, const PageTab &pt, W *pool, u32 r, u32 v, u32 rowbits,
+                                               const i32 *ps_in, const i32 *pe_in, u32 adj, Miss &&miss)
+{
+    W *slot = routed_word(pt, pool, r, v, miss);
+    const PkRow w = pk_unpack(*slot, rowbits);
+    const u32 row = w.hi & (rowbits >= 32 ? 0xFFFFFFFFu : (1u << rowbits) - 1u);
+    i32 qs, qe;
+    if (w.len == pk_maxlen(rowbits)) { qs = (i32)((u32)ps_in[row] + adj); qe = (i32)((u32)pe_in[row] - adj); }
+    else { qs = (i32)((u32)ix.rdesc[r].rbase + w.rel); qe = (i32)((u32)qs + w.len); }
+    return RestRow<W>{slot, row, w.hi, qs, qe};
+}
+
+// ------------------------------------------------------------------ lean fill probe
+// The headline's fill pass over LeanRows.  Same slices, same staging ring and round-level output reservation as
+// k_probe_regions<fill>; what differs is what a wavefront executes per row -- that kernel is bound by the instructions it
+// issues, 224 per 64 rows:
+//  * no per-row address work (LeanRows);
 //  * the walk is the 32-bit packed-row form only, staged as (slot, probe row): the slot -> build row lookup happens once per
 //    64 pairs in the copy-out, not per match inside the divergent loop; the cell offsets of all B rows are fetched before
 //    the first candidate loop runs;
 //  * rows the packed form cannot carry (escapes, rows reaching past the slice's halo) and batches that overflow the ring
-//    send their whole batch through the generic walk + direct write of k_probe_regions (cold code, out of line);
+//    go to the rest lists: k_fill_rest walks them (cold code, out of this kernel);
 //  * the last wavefront to arrive in a round leaves every wavefront's output position, not just the round's base.
 template <int B>
 __global__ __launch_bounds__(RP_T) void k_fill_fast(JoinIndexView ix, const u64 *__restrict__ pool, const u32 *__restrict__ rcur,
@@ -617,50 +758,17 @@ __global__ __launch_bounds__(RP_T) void k_fill_fast(JoinIndexView ix, const u64 
 {
     if (bsel != nullptr && *bsel != (u32)B) return;                   // (every B is launched; k_pick_rows chose one)
     if (ix.hdr[HDR_SLOW] != 0u) return;                               // not every region is one LDS-resident level: the general kernel's
-    constexpr u32 WB = IVX_WAVE * B;                                  // rows of a wavefront batch
-    constexpr u32 SUB = 8u / B;                                       // batches a wavefront makes of its 512 rows of a chunk
     IVX_PROBE_LDS(true)
     __shared__ u32 s_cfirst[IVX_MAXREG_WIDE + 2];
     __shared__ u32 s_wat[RP_NSLOT][RP_W];                             // a wavefront's output position inside its round's range
     const u32 wv = __builtin_amdgcn_readfirstlane(threadIdx.x / IVX_WAVE), ln = lane_id();
-    const u32 nreg = ix.hdr[HDR_NREG];
-    for (u32 t = threadIdx.x; t <= nreg; t += RP_T) s_cfirst[t] = cfirst[t];
-    __syncthreads();
-    const u32 nchunk = s_cfirst[nreg];
-    const u32 c_lo = (u32)((u64)nchunk * blockIdx.x / gridDim.x), c_hi = (u32)((u64)nchunk * (blockIdx.x + 1) / gridDim.x);
-    if (c_lo >= c_hi) return;
-    const u32 rowmask = rowbits >= 32 ? 0xFFFFFFFFu : (1u << rowbits) - 1u;
-    const u32 maxlen = pk_maxlen(rowbits);
-    const u32 pmask = (1u << pt.lgpg) - 1u;
+    auto miss = [&]() { if (ln == 0) atomicOr((unsigned int *)(cursor + 1), 1u); };     // a page never published: the host is told
+    LeanRows<B, const u64> rows;
+    if (!rows.init(ix, s_cfirst, cfirst, rcur, pt, pool, rowbits)) return;
     Slice S;
     slice_init(ix, S, L);
-    u32 r_next;                                                       // region of the batch in flight
-    {   // last region whose first chunk is <= c_lo
-        u32 a = 0, b = nreg;
-        while (a < b) { const u32 m = (a + b + 1) >> 1; if (s_cfirst[m] <= c_lo) a = m; else b = m - 1; }
-        r_next = a;
-    }
-    // batch i of this wavefront: its region, first virtual row and row count are wave-uniform, its rows 64 * B consecutive
-    // words of one pool page
-    const u32 nbatch = (c_hi - c_lo) * SUB;
-    u64 nx[B];
-    u32 ncnt = 0, nfirst = 0;
-    auto prefetch = [&](u32 i) {
-        const u32 c = c_lo + i / SUB, sb = i % SUB;
-        while (c >= s_cfirst[r_next + 1]) r_next++;
-        nfirst = (c - s_cfirst[r_next]) * FP_CHUNK + wv * (8u * IVX_WAVE) + sb * WB;
-        const u32 rows = rcur[r_next];
-        ncnt = rows > nfirst ? (rows - nfirst < WB ? rows - nfirst : WB) : 0u;
-        if (ncnt) {
-            u32 pg = pt.ptab[(u64)r_next * pt.pstride + (nfirst >> pt.lgpg)];
-            if (pg == 0u) { pg = 1u; if (ln == 0) atomicOr((unsigned int *)(cursor + 1), 1u); }     // never published (see pages_load): page 0, and the host is told
-            pg -= 1u;
-            const u64 *src = pool + (((u64)pg << pt.lgpg) + (nfirst & pmask));
-#pragma unroll
-            for (int q = 0; q < B; q++) nx[q] = src[q * IVX_WAVE + ln];      // (inside the page whatever ncnt is: pages are whole)
-        }
-    };
-    prefetch(0);
+    rows.start(miss);
+    const u32 rowmask = rowbits >= 32 ? 0xFFFFFFFFu : (1u << rowbits) - 1u;
     u32 loaded_r = 0xFFFFFFFFu;
     u32 round = 0;
     u32 pend_mine = 0;                                                // pairs the previous round staged (in its half of the ring)
@@ -688,8 +796,8 @@ __global__ __launch_bounds__(RP_T) void k_fill_fast(JoinIndexView ix, const u64 
             ob_w[t] = L.s_row[x.x]; op_w[t] = x.y & rowmask;
         }
     };
-    for (u32 i = 0; i < nbatch; i++) {
-        const u32 r = r_next, cnt = ncnt, first = nfirst;
+    for (u32 i = 0; i < rows.nbatch; i++) {
+        const u32 r = rows.r;
         if (r != loaded_r) {
             // the ring holds slice slots: whatever is still staged leaves before the slice changes
             if (round) { copy_out(round - 1u); pend_mine = 0; }
@@ -697,42 +805,13 @@ __global__ __launch_bounds__(RP_T) void k_fill_fast(JoinIndexView ix, const u64 
             loaded_r = r;
         }
         // ---- decode the batch in flight, start the next one
-        const bool full = cnt == WB;
-        u32 rel[B], len[B], roww[B];
-#pragma unroll
-        for (int q = 0; q < B; q++) {
-            const u32 lo32 = (u32)nx[q], hi32 = (u32)(nx[q] >> 32);
-            rel[q] = lo32 & 0xFFFFFFu;
-            len[q] = (lo32 >> 24) | ((rowbits < 32 ? (hi32 >> rowbits) & 0xFFu : 0u) << 8);
-            roww[q] = hi32;                                              // (the row id is masked out of it in the copy-out, 64 pairs at a time)
-        }
-        if (i + 1 < nbatch) prefetch(i + 1);
-        // ---- cells: of all B rows first (their LDS reads are in flight together), then the candidate loops
-        const u32 sh0 = S.sh0, off = S.off, cmax = S.cmax, ncm1 = S.ncm1;
+        u32 rel[B], len[B], roww[B];                                     // (roww: the row id is masked out of it in the copy-out, 64 pairs at a time)
+        const auto bt = rows.take(i, rel, len, roww, miss);
+        const u32 first = bt.first, cnt = bt.cnt;
+        // ---- cells: of all B rows first, then the candidate loops
         const i32 rbase = S.rbase;
-        u32 ca[B], cb[B], slow = 0;
-        // (two copies of the block, chosen once per batch: a per-row choice between "every lane holds B rows" and "test the
-        //  lane's row number" was two branches per row)
-        auto cells = [&](auto full_tag) {
-            constexpr bool FULL = decltype(full_tag)::value;
-#pragma unroll
-            for (int q = 0; q < B; q++) {
-                const u32 t = ((rel[q] + 1u) >> sh0) + off;              // first cell a matching build row can start in: one cell back
-                const u32 bl0 = (t > 1u ? t : 1u) - 1u;
-                const u32 bh0 = ((rel[q] + len[q]) >> sh0) + off;
-                const u32 bh = bh0 < cmax ? bh0 : cmax;
-                bool bad = len[q] == maxlen || bh >= ncm1;               // escape, or past the slice's halo: the rest list's
-                const bool ok = FULL || (u32)q * IVX_WAVE + ln < cnt;    // (only a region's last batch is short)
-                if (ok && bad) slow |= 1u << q;
-                bad |= !ok;
-                // no row to walk: an empty range (twice the same offset); a row behind the key's last cell gets one by the clamp
-                const u32 e1 = bad ? 0u : bh + 1u;
-                const u32 bl = bl0 < e1 ? bl0 : e1;
-                ca[q] = L.s_off[bl];
-                cb[q] = L.s_off[e1];
-            }
-        };
-        if (full) cells(std::true_type{}); else cells(std::false_type{});
+        u32 ca[B], cb[B], slow, okm;
+        lean_cells<B>(S, rel, len, rows.maxlen, cnt, ln, ca, cb, slow, okm);
         u32 wpos = 0;                                                    // pairs of this round so far (scalar)
         uint2 *half = (uint2 *)L.s_q[wv] + (round & 1u) * HALF;
 #pragma unroll
@@ -766,11 +845,7 @@ __global__ __launch_bounds__(RP_T) void k_fill_fast(JoinIndexView ix, const u64 
             // (as 64-row pieces: each gets a wavefront of its own in k_fill_rest)
             if (ln < B && ln * IVX_WAVE < cnt) rest[atomicAdd(rest_n, 1u)] = FpRest{r, first + ln * IVX_WAVE, cnt - ln * IVX_WAVE < IVX_WAVE ? cnt - ln * IVX_WAVE : (u32)IVX_WAVE, 0u};
             got = 0;
-        } else if (__builtin_expect(slow != 0, 0)) {                     // this lane's slow rows, one by one (their cell ranges were empty)
-#pragma unroll
-            for (int q = 0; q < B; q++)
-                if ((slow >> q) & 1u) rest_rows[atomicAdd(rest_n + 1, 1u)] = (u64)(first + (u32)q * IVX_WAVE + ln) | ((u64)r << 32);
-        }
+        } else if (__builtin_expect(slow != 0, 0)) lean_list_slow<B>(slow, r, first, ln, rest_rows, rest_n);
         // ---- publish the round's count; the last wavefront to arrive reserves the round's output range
         if (ln == 0) {
             const u32 sl = round % RP_NSLOT;
@@ -802,24 +877,14 @@ __global__ __launch_bounds__(256) void k_fill_rest(JoinIndexView ix, const u64 *
     const u32 nbat = rest_n[0], nrow = rest_n[1];
     if (nbat == 0 && nrow == 0) return;
     const u32 wpb = blockDim.x / IVX_WAVE, ln = lane_id();
-    const u32 rowmask = rowbits >= 32 ? 0xFFFFFFFFu : (1u << rowbits) - 1u;
-    const u32 maxlen = pk_maxlen(rowbits);
-    const u32 pmask = (1u << pt.lgpg) - 1u;
     const u32 sh0 = ix.hdr[HDR_SH0], nlev = ix.hdr[HDR_NLEV];
     // 64 routed rows, one per lane: (region, virtual row) or nothing
     auto rows64 = [&](bool ok, u32 r, u32 v) {
         i32 qs = 0, qe = -1; u32 row = 0, k = 0;
         if (ok) {
-            u32 pg = pt.ptab[(u64)r * pt.pstride + (v >> pt.lgpg)];
-            if (pg == 0u) { pg = 1u; atomicOr((unsigned int *)(cursor + 1), 1u); }     // never published (see pages_load)
-            pg -= 1u;
-            const u64 x = pool[((u64)pg << pt.lgpg) + (v & pmask)];
-            const u32 lo32 = (u32)x, hi32 = (u32)(x >> 32);
-            const u32 len = (lo32 >> 24) | ((rowbits < 32 ? (hi32 >> rowbits) & 0xFFu : 0u) << 8);
-            row = hi32 & rowmask;
+            const auto e = rest_row(ix, pt, pool, r, v, rowbits, ps_in, pe_in, 0u, [&]() { atomicOr((unsigned int *)(cursor + 1), 1u); });
+            qs = e.qs; qe = e.qe; row = e.row;
             k = ix.rkey[r];
-            if (len == maxlen) { qs = ps_in[row]; qe = pe_in[row]; }
-            else { qs = (i32)((u32)ix.rdesc[r].rbase + (lo32 & 0xFFFFFFu)); qe = (i32)((u32)qs + len); }
         }
         u32 m = 0;
         if (ok) walk(ix, sh0, 0, nlev, k, qs, qe, [&](u32) { m++; });
@@ -845,12 +910,11 @@ __global__ __launch_bounds__(256) void k_fill_rest(JoinIndexView ix, const u64 *
     }
 }
 
-// ------------------------------------------------------------------ lean per-row-value probe (round 3)
-// count_overlaps / the join's rle_right and exists (RV_COUNT, RV_MATCHES) and coverage (RV_COVERAGE) over packed rows in region
-// pages when every region is one LDS-resident level: k_fill_fast's row streaming and walk without a ring, rounds or any
-// synchronisation between wavefronts -- a row's value replaces the low half of its packed word in place, as in
-// k_probe_regions<RV_*>.  Rows the packed form cannot carry are listed (region, virtual row) and valued by k_rv_rest with the
-// generic walk over the index in global memory.
+// ------------------------------------------------------------------ lean per-row-value probe
+// count_overlaps / the join's rle_right and exists (RV_COUNT, RV_MATCHES) and coverage (RV_COVERAGE) over LeanRows and
+// lean_cells, without a ring, rounds or any synchronisation between wavefronts: nothing happens when the region changes but
+// the slice load, and a row's value replaces the low half of its packed word in place, as in k_probe_regions<RV_*>.  Rows the
+// packed form cannot carry are listed (region, virtual row) and valued by k_rv_rest.
 #ifndef IVX_RV_WPS
 #define IVX_RV_WPS 4
 #endif
@@ -861,80 +925,27 @@ template <int KIND, int B>
 __global__ __launch_bounds__(RP_T, IVX_RV_WPS) void k_rv_fast(JoinIndexView ix, u64 *__restrict__ pool, const u32 *__restrict__ rcur, const u32 *__restrict__ cfirst,
                                                   PageTab pt, u32 rowbits, u64 *__restrict__ rest_rows, u32 *rest_n)
 {
-    constexpr u32 WB = IVX_WAVE * B, SUB = 8u / B;
     __shared__ unsigned short s_off[RP_CCAP];
     __shared__ u64 s_ent[RP_ECAP];
     __shared__ u32 s_cfirst[IVX_MAXREG_WIDE + 2];
     ProbeLds L{s_off, s_ent, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    const u32 wv = __builtin_amdgcn_readfirstlane(threadIdx.x / IVX_WAVE), ln = lane_id();
-    const u32 nreg = ix.hdr[HDR_NREG];
-    for (u32 t = threadIdx.x; t <= nreg; t += RP_T) s_cfirst[t] = cfirst[t];
-    __syncthreads();
-    const u32 nchunk = s_cfirst[nreg];
-    const u32 c_lo = (u32)((u64)nchunk * blockIdx.x / gridDim.x), c_hi = (u32)((u64)nchunk * (blockIdx.x + 1) / gridDim.x);
-    if (c_lo >= c_hi) return;
-    const u32 maxlen = pk_maxlen(rowbits);
-    const u32 pmask = (1u << pt.lgpg) - 1u;
+    const u32 ln = lane_id();
+    auto miss = []() {};                                                 // (a page never published: stay in bounds, silently)
+    LeanRows<B, u64> rows;
+    if (!rows.init(ix, s_cfirst, cfirst, rcur, pt, pool, rowbits)) return;
     Slice S;
     slice_init(ix, S, L);
-    u32 r_next;
-    { u32 a = 0, b = nreg; while (a < b) { const u32 m = (a + b + 1) >> 1; if (s_cfirst[m] <= c_lo) a = m; else b = m - 1; } r_next = a; }
-    const u32 nbatch = (c_hi - c_lo) * SUB;
-    u64 nx[B];
-    u32 ncnt = 0, nfirst = 0; u64 *nsrc = pool;
-    auto prefetch = [&](u32 i) {
-        const u32 c = c_lo + i / SUB, sb = i % SUB;
-        while (c >= s_cfirst[r_next + 1]) r_next++;
-        nfirst = (c - s_cfirst[r_next]) * FP_CHUNK + wv * (8u * IVX_WAVE) + sb * WB;
-        const u32 rows = rcur[r_next];
-        ncnt = rows > nfirst ? (rows - nfirst < WB ? rows - nfirst : WB) : 0u;
-        if (ncnt) {
-            u32 pg = pt.ptab[(u64)r_next * pt.pstride + (nfirst >> pt.lgpg)];
-            if (pg == 0u) pg = 1u;                                       // (never published: see pages_load; stay in bounds)
-            nsrc = pool + (((u64)(pg - 1u) << pt.lgpg) + (nfirst & pmask));
-#pragma unroll
-            for (int q = 0; q < B; q++) nx[q] = nsrc[q * IVX_WAVE + ln];
-        }
-    };
-    prefetch(0);
+    rows.start(miss);
     u32 loaded_r = 0xFFFFFFFFu;
-    for (u32 i = 0; i < nbatch; i++) {
-        const u32 r = r_next, cnt = ncnt, first = nfirst;
-        u64 *dst = nsrc;
+    for (u32 i = 0; i < rows.nbatch; i++) {
+        const u32 r = rows.r;
         if (r != loaded_r) { slice_load(ix, S, L, r, true); loaded_r = r; }
-        const bool full = cnt == WB;
-        u32 rel[B], len[B], roww[B];
-#pragma unroll
-        for (int q = 0; q < B; q++) {
-            const u32 lo32 = (u32)nx[q], hi32 = (u32)(nx[q] >> 32);
-            rel[q] = lo32 & 0xFFFFFFu;
-            len[q] = (lo32 >> 24) | ((rowbits < 32 ? (hi32 >> rowbits) & 0xFFu : 0u) << 8);
-            roww[q] = hi32;                                              // (the un-permute masks the row id out of it)
-        }
-        if (i + 1 < nbatch) prefetch(i + 1);
-        const u32 sh0 = S.sh0, off = S.off, cmax = S.cmax, ncm1 = S.ncm1;
+        u32 rel[B], len[B], roww[B];                                     // (roww: the un-permute masks the row id out of it)
+        const auto bt = rows.take(i, rel, len, roww, miss);
+        u64 *dst = bt.src;
         const i32 rbase = S.rbase;
-        u32 ca[B], cb[B], slow = 0, okm = 0;
-        auto cells = [&](auto full_tag) {
-            constexpr bool FULL = decltype(full_tag)::value;
-#pragma unroll
-            for (int q = 0; q < B; q++) {
-                const u32 t = ((rel[q] + 1u) >> sh0) + off;
-                const u32 bl0 = (t > 1u ? t : 1u) - 1u;
-                const u32 bh0 = ((rel[q] + len[q]) >> sh0) + off;
-                const u32 bh = bh0 < cmax ? bh0 : cmax;
-                bool bad = len[q] == maxlen || bh >= ncm1;
-                const bool ok = FULL || (u32)q * IVX_WAVE + ln < cnt;
-                if (ok && bad) slow |= 1u << q;
-                if (ok && !bad) okm |= 1u << q;
-                bad |= !ok;
-                const u32 e1 = bad ? 0u : bh + 1u;
-                const u32 bl = bl0 < e1 ? bl0 : e1;
-                ca[q] = s_off[bl];
-                cb[q] = s_off[e1];
-            }
-        };
-        if (full) cells(std::true_type{}); else cells(std::false_type{});
+        u32 ca[B], cb[B], slow, okm;
+        lean_cells<B>(S, rel, len, rows.maxlen, bt.cnt, ln, ca, cb, slow, okm);
 #pragma unroll
         for (int q = 0; q < B; q++) {
             const i32 qs = (i32)((u32)rbase + rel[q]), qe = (i32)((u32)qs + len[q]);
@@ -950,11 +961,7 @@ __global__ __launch_bounds__(RP_T, IVX_RV_WPS) void k_rv_fast(JoinIndexView ix, 
             }
             if ((okm >> q) & 1u) dst[q * IVX_WAVE + ln] = (u64)v | ((u64)roww[q] << 32);
         }
-        if (__builtin_expect(slow != 0, 0)) {
-#pragma unroll
-            for (int q = 0; q < B; q++)
-                if ((slow >> q) & 1u) rest_rows[atomicAdd(rest_n + 1, 1u)] = (u64)(first + (u32)q * IVX_WAVE + ln) | ((u64)r << 32);
-        }
+        if (__builtin_expect(slow != 0, 0)) lean_list_slow<B>(slow, r, bt.first, ln, rest_rows, rest_n);
     }
 }
 
@@ -964,23 +971,12 @@ __global__ __launch_bounds__(256) void k_rv_rest(JoinIndexView ix, u64 *__restri
                                                  u32 rowbits, u32 adj)
 {
     const u32 nrow = rest_n[1];
-    const u32 rowmask = rowbits >= 32 ? 0xFFFFFFFFu : (1u << rowbits) - 1u;
-    const u32 maxlen = pk_maxlen(rowbits);
-    const u32 pmask = (1u << pt.lgpg) - 1u;
     const u32 sh0 = ix.hdr[HDR_SH0], nlev = ix.hdr[HDR_NLEV];
     for (u32 i = blockIdx.x * blockDim.x + threadIdx.x; i < nrow; i += gridDim.x * blockDim.x) {
         const u64 ent = rest_rows[i];
-        const u32 r = (u32)(ent >> 32), vr = (u32)ent;
-        u32 pg = pt.ptab[(u64)r * pt.pstride + (vr >> pt.lgpg)];
-        if (pg == 0u) pg = 1u;
-        u64 *slot = pool + (((u64)(pg - 1u) << pt.lgpg) + (vr & pmask));
-        const u64 x = *slot;
-        const u32 lo32 = (u32)x, hi32 = (u32)(x >> 32);
-        const u32 len = (lo32 >> 24) | ((rowbits < 32 ? (hi32 >> rowbits) & 0xFFu : 0u) << 8);
-        const u32 row = hi32 & rowmask;
-        i32 qs, qe;
-        if (len == maxlen) { qs = (i32)((u32)ps_in[row] + adj); qe = (i32)((u32)pe_in[row] - adj); }
-        else { qs = (i32)((u32)ix.rdesc[r].rbase + (lo32 & 0xFFFFFFu)); qe = (i32)((u32)qs + len); }
+        const u32 r = (u32)(ent >> 32);
+        const auto e = rest_row(ix, pt, pool, r, (u32)ent, rowbits, ps_in, pe_in, adj, []() {});
+        const i32 qs = e.qs, qe = e.qe;
         u32 v = 0;
         if (KIND == RV_COVERAGE) {
             const i32 a = rv_wadd(qe, 1), b = rv_wsub(qs, 1);
@@ -991,60 +987,37 @@ __global__ __launch_bounds__(256) void k_rv_rest(JoinIndexView ix, u64 *__restri
         } else if (KIND != RV_COUNT || !(qe < qs)) {
             walk_ent(ix, sh0, 0, nlev, ix.rkey[r], qs, qe, [&](const ivx_ent &) { v++; });
         }
-        *slot = (u64)v | ((u64)hi32 << 32);
+        *e.slot = (u64)v | ((u64)e.hi << 32);
     }
 }
 
 // ------------------------------------------------------------------ lean build-side marks
-// Which BUILD rows a big batch matched (ivx_probe_mark_build), over the same routed pages and with k_rv_fast's row
-// streaming and walk -- but nothing is written back per probe row.  Beside the slice the workgroup keeps one bit per slice
-// entry in LDS (RP_ECAP bits); a match ORs bit j, its slice entry, with one LDS atomic.  When the workgroup leaves a region,
-// and at the end of its share, it sweeps the LDS words: every set bit is a matched entry, whose build row (read from
-// ix.ent, the slice stages no row ids) gets its bit in the caller's bitmap by test-then-OR, and the LDS word is cleared.
-// Global atomics are then per distinct matched build row and workgroup visit, not per match (the headline: ~37 matches
-// per build row).  Rows the packed form cannot carry are listed as in k_rv_fast; k_mark_rest marks for them.
+// Which BUILD rows a big batch matched (ivx_probe_mark_build), over LeanRows and lean_cells -- but nothing is written back
+// per probe row.  Beside the slice the workgroup keeps one bit per slice entry in LDS (RP_ECAP bits); a match ORs bit j, its
+// slice entry, with one LDS atomic.  When the workgroup leaves a region, and at the end of its share, it sweeps the LDS
+// words: every set bit is a matched entry, whose build row (read from ix.ent, the slice stages no row ids) gets its bit in
+// the caller's bitmap by test-then-OR, and the LDS word is cleared.  Global atomics are then per distinct matched build row
+// and workgroup visit, not per match (the headline: ~37 matches per build row).  Rows the packed form cannot carry are
+// listed as in k_rv_fast; k_mark_rest marks for them.
 template <int B>
 __global__ __launch_bounds__(RP_T, IVX_RV_WPS) void k_mark_fast(JoinIndexView ix, const u64 *__restrict__ pool, const u32 *__restrict__ rcur, const u32 *__restrict__ cfirst,
                                                     PageTab pt, u32 rowbits, u64 *__restrict__ rest_rows, u32 *rest_n, u32 *marks)
 {
-    constexpr u32 WB = IVX_WAVE * B, SUB = 8u / B, NBW = RP_ECAP / 32u;
+    constexpr u32 NBW = RP_ECAP / 32u;
     static_assert(RP_ECAP % 32u == 0, "one LDS bit per slice entry, whole words");
     __shared__ unsigned short s_off[RP_CCAP];
     __shared__ u64 s_ent[RP_ECAP];
     __shared__ u32 s_cfirst[IVX_MAXREG_WIDE + 2];
     __shared__ u32 s_bits[NBW];
     ProbeLds L{s_off, s_ent, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    const u32 wv = __builtin_amdgcn_readfirstlane(threadIdx.x / IVX_WAVE), ln = lane_id();
-    const u32 nreg = ix.hdr[HDR_NREG];
-    for (u32 t = threadIdx.x; t <= nreg; t += RP_T) s_cfirst[t] = cfirst[t];
-    for (u32 t = threadIdx.x; t < NBW; t += RP_T) s_bits[t] = 0u;
-    __syncthreads();
-    const u32 nchunk = s_cfirst[nreg];
-    const u32 c_lo = (u32)((u64)nchunk * blockIdx.x / gridDim.x), c_hi = (u32)((u64)nchunk * (blockIdx.x + 1) / gridDim.x);
-    if (c_lo >= c_hi) return;
-    const u32 maxlen = pk_maxlen(rowbits);
-    const u32 pmask = (1u << pt.lgpg) - 1u;
+    const u32 ln = lane_id();
+    for (u32 t = threadIdx.x; t < NBW; t += RP_T) s_bits[t] = 0u;        // (the barrier behind it is init's)
+    auto miss = []() {};                                                 // (a page never published: stay in bounds, silently)
+    LeanRows<B, const u64> rows;
+    if (!rows.init(ix, s_cfirst, cfirst, rcur, pt, pool, rowbits)) return;
     Slice S;
     slice_init(ix, S, L);
-    u32 r_next;
-    { u32 a = 0, b = nreg; while (a < b) { const u32 m = (a + b + 1) >> 1; if (s_cfirst[m] <= c_lo) a = m; else b = m - 1; } r_next = a; }
-    const u32 nbatch = (c_hi - c_lo) * SUB;
-    u64 nx[B];
-    u32 ncnt = 0, nfirst = 0;
-    auto prefetch = [&](u32 i) {
-        const u32 c = c_lo + i / SUB, sb = i % SUB;
-        while (c >= s_cfirst[r_next + 1]) r_next++;
-        nfirst = (c - s_cfirst[r_next]) * FP_CHUNK + wv * (8u * IVX_WAVE) + sb * WB;
-        const u32 rows = rcur[r_next];
-        ncnt = rows > nfirst ? (rows - nfirst < WB ? rows - nfirst : WB) : 0u;
-        if (ncnt) {
-            u32 pg = pt.ptab[(u64)r_next * pt.pstride + (nfirst >> pt.lgpg)];
-            if (pg == 0u) pg = 1u;                                       // (never published: see pages_load; stay in bounds)
-            const u64 *src = pool + (((u64)(pg - 1u) << pt.lgpg) + (nfirst & pmask));
-#pragma unroll
-            for (int q = 0; q < B; q++) nx[q] = src[q * IVX_WAVE + ln];
-        }
-    };
+    rows.start(miss);
     // the matched entries of the region just left: to the caller's bitmap, LDS words back to zero (all threads; the
     // slice_load or the kernel's end that follows brings the barrier behind the sweep)
     auto flush = [&]() {
@@ -1060,46 +1033,19 @@ __global__ __launch_bounds__(RP_T, IVX_RV_WPS) void k_mark_fast(JoinIndexView ix
             } while (m);
         }
     };
-    prefetch(0);
     u32 loaded_r = 0xFFFFFFFFu;
-    for (u32 i = 0; i < nbatch; i++) {
-        const u32 r = r_next, cnt = ncnt, first = nfirst;
+    for (u32 i = 0; i < rows.nbatch; i++) {
+        const u32 r = rows.r;
         if (r != loaded_r) {
             if (loaded_r != 0xFFFFFFFFu) flush();
             slice_load(ix, S, L, r, true);
             loaded_r = r;
         }
-        const bool full = cnt == WB;
-        u32 rel[B], len[B];
-#pragma unroll
-        for (int q = 0; q < B; q++) {
-            const u32 lo32 = (u32)nx[q], hi32 = (u32)(nx[q] >> 32);
-            rel[q] = lo32 & 0xFFFFFFu;
-            len[q] = (lo32 >> 24) | ((rowbits < 32 ? (hi32 >> rowbits) & 0xFFu : 0u) << 8);
-        }
-        if (i + 1 < nbatch) prefetch(i + 1);
-        const u32 sh0 = S.sh0, off = S.off, cmax = S.cmax, ncm1 = S.ncm1;
+        u32 rel[B], len[B], roww[B];                                     // (roww: not used, no probe row is named here)
+        const auto bt = rows.take(i, rel, len, roww, miss);
         const i32 rbase = S.rbase;
-        u32 ca[B], cb[B], slow = 0;
-        auto cells = [&](auto full_tag) {
-            constexpr bool FULL = decltype(full_tag)::value;
-#pragma unroll
-            for (int q = 0; q < B; q++) {
-                const u32 t = ((rel[q] + 1u) >> sh0) + off;
-                const u32 bl0 = (t > 1u ? t : 1u) - 1u;
-                const u32 bh0 = ((rel[q] + len[q]) >> sh0) + off;
-                const u32 bh = bh0 < cmax ? bh0 : cmax;
-                bool bad = len[q] == maxlen || bh >= ncm1;
-                const bool ok = FULL || (u32)q * IVX_WAVE + ln < cnt;
-                if (ok && bad) slow |= 1u << q;
-                bad |= !ok;
-                const u32 e1 = bad ? 0u : bh + 1u;
-                const u32 bl = bl0 < e1 ? bl0 : e1;
-                ca[q] = s_off[bl];
-                cb[q] = s_off[e1];
-            }
-        };
-        if (full) cells(std::true_type{}); else cells(std::false_type{});
+        u32 ca[B], cb[B], slow, okm;
+        lean_cells<B>(S, rel, len, rows.maxlen, bt.cnt, ln, ca, cb, slow, okm);
 #pragma unroll
         for (int q = 0; q < B; q++) {
             const i32 qs = (i32)((u32)rbase + rel[q]), qe = (i32)((u32)qs + len[q]);
@@ -1109,11 +1055,7 @@ __global__ __launch_bounds__(RP_T, IVX_RV_WPS) void k_mark_fast(JoinIndexView ix
                     __hip_atomic_fetch_or(&s_bits[j >> 5], 1u << (j & 31u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             }
         }
-        if (__builtin_expect(slow != 0, 0)) {
-#pragma unroll
-            for (int q = 0; q < B; q++)
-                if ((slow >> q) & 1u) rest_rows[atomicAdd(rest_n + 1, 1u)] = (u64)(first + (u32)q * IVX_WAVE + ln) | ((u64)r << 32);
-        }
+        if (__builtin_expect(slow != 0, 0)) lean_list_slow<B>(slow, r, bt.first, ln, rest_rows, rest_n);
     }
     flush();
 }
@@ -1123,23 +1065,12 @@ __global__ __launch_bounds__(256) void k_mark_rest(JoinIndexView ix, const u64 *
                                                    u32 rowbits, u32 *marks)
 {
     const u32 nrow = rest_n[1];
-    const u32 rowmask = rowbits >= 32 ? 0xFFFFFFFFu : (1u << rowbits) - 1u;
-    const u32 maxlen = pk_maxlen(rowbits);
-    const u32 pmask = (1u << pt.lgpg) - 1u;
     const u32 sh0 = ix.hdr[HDR_SH0], nlev = ix.hdr[HDR_NLEV];
     for (u32 i = blockIdx.x * blockDim.x + threadIdx.x; i < nrow; i += gridDim.x * blockDim.x) {
         const u64 ent = rest_rows[i];
-        const u32 r = (u32)(ent >> 32), vr = (u32)ent;
-        u32 pg = pt.ptab[(u64)r * pt.pstride + (vr >> pt.lgpg)];
-        if (pg == 0u) pg = 1u;
-        const u64 x = pool[((u64)(pg - 1u) << pt.lgpg) + (vr & pmask)];
-        const u32 lo32 = (u32)x, hi32 = (u32)(x >> 32);
-        const u32 len = (lo32 >> 24) | ((rowbits < 32 ? (hi32 >> rowbits) & 0xFFu : 0u) << 8);
-        const u32 row = hi32 & rowmask;
-        i32 qs, qe;
-        if (len == maxlen) { qs = ps_in[row]; qe = pe_in[row]; }
-        else { qs = (i32)((u32)ix.rdesc[r].rbase + (lo32 & 0xFFFFFFu)); qe = (i32)((u32)qs + len); }
-        walk(ix, sh0, 0, nlev, ix.rkey[r], qs, qe, [&](u32 brow) { mark_bit(marks, brow); });
+        const u32 r = (u32)(ent >> 32);
+        const auto e = rest_row(ix, pt, pool, r, (u32)ent, rowbits, ps_in, pe_in, 0u, []() {});
+        walk(ix, sh0, 0, nlev, ix.rkey[r], e.qs, e.qe, [&](u32 brow) { mark_bit(marks, brow); });
     }
 }
 
@@ -1237,11 +1168,10 @@ __global__ __launch_bounds__(RP_T) void k_probe_dense(JoinIndexView ix, const vo
             i32 qs = (i32)(u32)nx, qe = (i32)(u32)(nx >> 32);
             u32 rowv = nxr;
             if (PK) {
-                const u32 lo32 = (u32)nx, hi32 = (u32)(nx >> 32);
-                const u32 len = (lo32 >> 24) | ((rowbits < 32 ? (hi32 >> rowbits) & 0xFFu : 0u) << 8);
-                rowv = hi32 & rowmask;
-                qs = (i32)((u32)S.rbase + (lo32 & 0xFFFFFFu)); qe = (i32)((u32)qs + len);
-                if (ok && len == maxlen) { qs = ps_in[rowv]; qe = pe_in[rowv]; }
+                const PkRow w = pk_unpack(nx, rowbits);
+                rowv = w.hi & rowmask;
+                qs = (i32)((u32)S.rbase + w.rel); qe = (i32)((u32)qs + w.len);
+                if (ok && w.len == maxlen) { qs = ps_in[rowv]; qe = pe_in[rowv]; }
             }
             { const u64 g2 = g + RP_W; const u64 i2 = g2 * 64 + ln; const bool ok2 = g2 < g1 && i2 >= lo && i2 < c_hi; const u64 at = ok2 ? row_at(i2, r, rf) : 0; nx = ok2 ? row_se(at) : 0; nxr = (PASS == 1 && !PK && ok2) ? row_id(i2, at) : 0u; }
             const u64 slot = g + r;
@@ -1368,6 +1298,14 @@ bool dense_fill_wanted(const RegionKnobs &K, u64 cap, u64 n)
     return (double)cap / (double)n > 3.5;                                  // measured crossover (tools/probe_only.py IVX_DENSE=0/1): the ring wins below
 }
 
+// may the lean kernels (k_fill_fast, k_rv_fast, k_mark_fast) run on these routed rows: packed words in region pages that
+// hold at least a chunk, and a rest list for the rows the packed form cannot carry (the routing pass made one: its `lean`
+// option).  Whether the INDEX qualifies (`fast`) and IVX_FILL=old are each launcher's own to test.
+bool lean_rows_ok(const ivx_routed &R)
+{
+    return R.form == IVX_ROWS_PAGED && R.packed && R.pt.lgpg >= 13 && R.rest_rows != nullptr;
+}
+
 template <int V> using int_tag = std::integral_constant<int, V>;
 // rows per lane in {1, 2, 4, 8} as a template argument: f(int_tag<B>)
 template <class F> void with_rows_per_lane(int b, F &&f)
@@ -1450,7 +1388,7 @@ ivx_status probe_pairs(ivx_ctx *ctx, const JoinIndexView &jv, u32 nreg, int mode
     // packed rows over an index whose every region is one LDS-resident level: the lean kernel, then whatever batches it
     // left to the generic walk (IVX_FILL=old: the general kernel, for A/B runs and the tests that pin both)
     const u32 *slow_gate = nullptr;
-    if (paged && R.packed && fast != 0 && !K.lean_off && R.pt.lgpg >= 13 && R.rest != nullptr) {
+    if (lean_rows_ok(R) && fast != 0 && !K.lean_off && R.rest != nullptr) {
         u32 *rest_n = R.ctl->rest_n;                                    // batches, rows
         if (reused) IVX_HIP(ctx, hipMemsetAsync(rest_n, 0, 2 * sizeof(u32), st));   // (else: zeroed with the routing pass's counters just now)
         every_b([&](auto b) {
@@ -1535,7 +1473,7 @@ ivx_status ivx_rowval_probe_regions(ivx_ctx *ctx, const JoinIndexView &jv, u32 n
         constexpr int M = decltype(kind_tag)::value;
         // every region one LDS-resident level: the lean kernel values the rows, k_rv_rest the few the packed form cannot carry
         // (IVX_FILL=old: the general kernel)
-        if (paged && R.rest_rows != nullptr && R.pt.lgpg >= 13) {
+        if (lean_rows_ok(R)) {
             hipLaunchKernelGGL((k_rv_fast<M, IVX_RV_B>), dim3(RP_GRID * (IVX_RV_WPS / 4)), dim3(RP_T), 0, st, jv, pool, (const u32 *)R.ctl->rcur, (const u32 *)R.ctl->cfirst, R.pt, R.rowbits, R.rest_rows, R.ctl->rest_n);
             hipLaunchKernelGGL((k_rv_rest<M>), dim3(256), dim3(256), 0, st, jv, pool, R.pt, (const u64 *)R.rest_rows, (const u32 *)R.ctl->rest_n, s, e, R.rowbits, adj);
         } else launch_probe_regions<M, RP_B>(st, jv, R, RP_VGRID, paged ? (u32 *)pool : val, nullptr, 0, nullptr);
@@ -1558,7 +1496,7 @@ ivx_status ivx_mark_probe_regions(ivx_ctx *ctx, const JoinIndexView &jv, u32 nre
     hipStream_t st = ctx->stream;
     ivx_routed R;
     IVX_TRY(ivx_route_paged(ctx, jv, nreg, key, s, e, n, ivx_paged_opts{has_filter && !K.filter_off, true, true, true, 0u}, &R));
-    if (R.rest_rows == nullptr || R.pt.lgpg < 13) return IVX_OK;
+    if (!lean_rows_ok(R)) return IVX_OK;
     hipLaunchKernelGGL((k_mark_fast<IVX_RV_B>), dim3(RP_GRID * (IVX_RV_WPS / 4)), dim3(RP_T), 0, st, jv, R.se, (const u32 *)R.ctl->rcur, (const u32 *)R.ctl->cfirst, R.pt, R.rowbits,
                        R.rest_rows, R.ctl->rest_n, marks);
     hipLaunchKernelGGL(k_mark_rest, dim3(256), dim3(256), 0, st, jv, R.se, R.pt, (const u64 *)R.rest_rows, (const u32 *)R.ctl->rest_n, s, e, R.rowbits, marks);
