@@ -42,6 +42,15 @@ constexpr u32 RP_ECAP = IVX_RP_ECAP;       // entries staged per slice
 constexpr u32 RP_RING = IVX_RP_RING;       // per-wavefront ring of staged pairs: two consecutive rounds must fit (power of two)
 constexpr u32 RP_NSLOT = 4;                // rounds whose reservation state is kept (see round_publish)
 constexpr u32 RP_NPG = 64;                 // page ids of one region segment kept in LDS (paged rows)
+constexpr u32 RP_STASH = 48;               // lean fill: unfinished list tails a wavefront keeps per batch (what LDS is left over holds 48)
+// a stashed tail in 32 bits: next slice slot j (13 bits: RP_ECAP <= 8192) | the row's slot in its wavefront batch, q * 64 + lane
+// (9 bits).  Where the list ends is not kept: the tail pass fetches the row's word again and finds its last cell from that.
+constexpr u32 FD_SLOT_SHIFT = 13;
+#ifndef IVX_FD_HEAD
+#define IVX_FD_HEAD 3
+#endif
+constexpr int FD_HEAD = IVX_FD_HEAD;       // steps a draining group that starts with more active lanes than it may drain takes before the next test
+static_assert(RP_ECAP <= (1u << FD_SLOT_SHIFT), "a slice slot must fit a stash entry's j field");
 constexpr u32 RP_GRID = 256;                // fill pass: one workgroup per CU (LDS-bound)
 #ifndef IVX_RP_VGRID
 #define IVX_RP_VGRID 512
@@ -751,16 +760,18 @@ __device__ __forceinline__ RestRow<W> rest_row(const JoinIndexView &ix, const Pa
 //  * rows the packed form cannot carry (escapes, rows reaching past the slice's halo) and batches that overflow the ring
 //    go to the rest lists: k_fill_rest walks them (cold code, out of this kernel);
 //  * the last wavefront to arrive in a round leaves every wavefront's output position, not just the round's base.
-template <int B>
+template <int B, bool DRAIN>
 __global__ __launch_bounds__(RP_T) void k_fill_fast(JoinIndexView ix, const u64 *__restrict__ pool, const u32 *__restrict__ rcur,
                                                     const u32 *__restrict__ cfirst, PageTab pt, u32 *__restrict__ ob, u32 *__restrict__ op, u64 cap,
-                                                    unsigned long long *cursor, const u32 *bsel, u32 rowbits, FpRest *__restrict__ rest, u64 *__restrict__ rest_rows, u32 *rest_n)
+                                                    unsigned long long *cursor, const u32 *bsel, u32 rowbits, FpRest *__restrict__ rest, u64 *__restrict__ rest_rows, u32 *rest_n,
+                                                    u32 drain)
 {
     if (bsel != nullptr && *bsel != (u32)B) return;                   // (every B is launched; k_pick_rows chose one)
     if (ix.hdr[HDR_SLOW] != 0u) return;                               // not every region is one LDS-resident level: the general kernel's
     IVX_PROBE_LDS(true)
     __shared__ u32 s_cfirst[IVX_MAXREG_WIDE + 2];
     __shared__ u32 s_wat[RP_NSLOT][RP_W];                             // a wavefront's output position inside its round's range
+    __shared__ u32 s_stash[DRAIN ? RP_W : 1][RP_STASH];                        // a wavefront's unfinished list tails of the batch at hand (see the walk)
     const u32 wv = __builtin_amdgcn_readfirstlane(threadIdx.x / IVX_WAVE), ln = lane_id();
     auto miss = [&]() { if (ln == 0) atomicOr((unsigned int *)(cursor + 1), 1u); };     // a page never published: the host is told
     LeanRows<B, const u64> rows;
@@ -814,6 +825,25 @@ __global__ __launch_bounds__(RP_T) void k_fill_fast(JoinIndexView ix, const u64 
         lean_cells<B>(S, rel, len, rows.maxlen, cnt, ln, ca, cb, slow, okm);
         u32 wpos = 0;                                                    // pairs of this round so far (scalar)
         uint2 *half = (uint2 *)L.s_q[wv] + (round & 1u) * HALF;
+        // one step of the lock-step walk: every lane of actm tests the slice entry at its j and moves on
+        // (lane masks straight from the compares -- uicmp / sicmp -- and back into a predicate -- inverse_ballot: the
+        //  bool-to-ballot round trip of `ballot(act && ...)` cost two VALU instructions per step, the recomputed loop
+        //  test one more: 13 -> 10 per step, and the walk is what the kernel's time goes into)
+        auto step = [&](u32 &j, u32 jend, i32 qs, i32 qe, u32 rw, u64 &actm) {
+            const u64 x = L.s_ent[j];                                    // (a lane past its list reads on inside LDS; its result is not used)
+            const u64 mm = actm & __builtin_amdgcn_sicmp((i32)(u32)x, qe, 41 /* SLE */) & __builtin_amdgcn_sicmp((i32)(u32)(x >> 32), qs, 39 /* SGE */);
+            if (__builtin_amdgcn_inverse_ballot_w64(mm)) half[mask_rank_from(mm, wpos) & (HALF - 1)] = make_uint2(j, rw);      // (the counter's addend carries the position)
+            wpos += (u32)__popcll(mm);
+            j++;
+            actm = __builtin_amdgcn_uicmp(j, jend, 36 /* ULT */);       // lanes whose list is not done
+        };
+        // Drained walk (DRAIN; without it the kernel is the plain walk, instruction for instruction, and holds no stash).  A
+        // 64-row group runs as many steps as its longest list, and after two steps most lanes idle (1.4 candidates per row,
+        // the longest of 64 lists ~5).  So a group's walk ends as soon as at most `drain` lanes are still active: each of them
+        // leaves (next slice slot, the row's slot in the batch) in the wavefront's stash, and ONE 64-lane pass per batch walks
+        // all stashed tails side by side (below).  Slots by ballot rank behind a scalar fill count, as in the ring; no atomic,
+        // no barrier, no wait on another wavefront.
+        u32 sfill = 0;                                                   // tails stashed so far in this batch (scalar)
 #pragma unroll
         for (int q = 0; q < B; q++) {
             const i32 qs = (i32)((u32)rbase + rel[q]), qe = (i32)((u32)qs + len[q]);
@@ -823,20 +853,44 @@ __global__ __launch_bounds__(RP_T) void k_fill_fast(JoinIndexView ix, const u64 
             //  measured: no change.  The walk is bound by the instructions it issues, not by those waits.)
             // One backward branch per step; the match block sits on the fall-through path (a taken branch empties the
             // wavefront's instruction buffer, and the kernel retired 31 branches per 64 rows).
-            // (lane masks straight from the compares -- uicmp / sicmp -- and back into a predicate -- inverse_ballot: the
-            //  bool-to-ballot round trip of `ballot(act && ...)` cost two VALU instructions per step, the recomputed loop
-            //  test one more: 13 -> 10 per step, and the walk is what the kernel's time goes into)
-            u64 actm = __builtin_amdgcn_uicmp(j, jend, 36 /* ULT */);   // lanes whose list is not done
-            if (actm != 0) {
-                do {
-                    const u64 x = L.s_ent[j];                            // (a lane past its list reads on inside LDS; its result is not used)
-                    const u64 mm = actm & __builtin_amdgcn_sicmp((i32)(u32)x, qe, 41 /* SLE */) & __builtin_amdgcn_sicmp((i32)(u32)(x >> 32), qs, 39 /* SGE */);
-                    if (__builtin_amdgcn_inverse_ballot_w64(mm)) half[mask_rank_from(mm, wpos) & (HALF - 1)] = make_uint2(j, roww[q]);      // (the counter's addend carries the position)
-                    wpos += (u32)__popcll(mm);
-                    j++;
-                    actm = __builtin_amdgcn_uicmp(j, jend, 36);
-                } while (actm != 0);
+            u64 actm = __builtin_amdgcn_uicmp(j, jend, 36);
+            if constexpr (!DRAIN) {
+                if (actm != 0) {
+                    do step(j, jend, qs, qe, roww[q], actm); while (actm != 0);
+                }
+            } else {
+                // the group walks on while more lanes are active than may be drained or the stash has room for
+                const u32 lim = drain < RP_STASH - sfill ? drain : RP_STASH - sfill;
+                if ((u32)__popcll(actm) > lim) {
+                    // (a group that starts with that many lists takes its first steps without a test -- no count, no compare,
+                    //  no branch: a step past the longest list changes nothing -- a group of few lists is stashed at once)
+#pragma unroll
+                    for (int h = 0; h < FD_HEAD; h++) step(j, jend, qs, qe, roww[q], actm);
+                    while ((u32)__popcll(actm) > lim) step(j, jend, qs, qe, roww[q], actm);
+                }
+                if (actm != 0) {
+                    if (__builtin_amdgcn_inverse_ballot_w64(actm)) s_stash[wv][mask_rank_from(actm, sfill)] = j | (((u32)q * IVX_WAVE + ln) << FD_SLOT_SHIFT);
+                    sfill += (u32)__popcll(actm);
+                }
             }
+        }
+        // ---- the stashed tails, one per lane: the row's word again from the batch's 4 KB (just streamed), the end of its list
+        // as lean_cells found it (a stashed row is one that was walked: neither slow nor past the batch's rows), the same step
+        if (DRAIN && sfill != 0) {
+            // the entries were written by other lanes of this wavefront: order the LDS writes above before the reads below
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            const bool has = ln < sfill;
+            const u32 e = has ? s_stash[wv][ln] : 0u;
+            const PkRow w = pk_unpack(bt.src[e >> FD_SLOT_SHIFT], rowbits);     // (a lane without a tail: row 0 of the batch, an empty list)
+            const i32 qs = (i32)((u32)rbase + w.rel), qe = (i32)((u32)qs + w.len);
+            const u32 bh0 = ((w.rel + w.len) >> S.sh0) + S.off;
+            u32 j = e & ((1u << FD_SLOT_SHIFT) - 1u);
+            const u32 jend = has ? (u32)S.s_off[(bh0 < S.cmax ? bh0 : S.cmax) + 1u] : 0u;
+            u64 actm = __builtin_amdgcn_uicmp(j, jend, 36);
+            while (actm != 0) step(j, jend, qs, qe, w.hi, actm);
+            // (the stash is empty again: sfill starts from 0 in the next batch, and nothing staged outlives a slice)
         }
         u32 got = wpos;
         // more pairs than the half holds: nothing of this batch counts as staged
@@ -1275,11 +1329,12 @@ struct RegionKnobs {
     bool filter_off;        // IVX_FILTER=0: route every row, whatever the build side's occupancy bitmap says
     const char *dense;      // IVX_DENSE=0/1: the match-dense fill never / always
     const char *rp_rows;    // IVX_RP_ROWS=1/2/4/8: rows per lane of the fill (experiments)
+    const char *fill_drain; // IVX_FILL_DRAIN=n: the lean fill ends a row group's walk at n active lanes, whatever the rows per lane (0: never)
 };
 RegionKnobs region_knobs()
 {
     auto is = [](const char *name, const char *v) { const char *x = getenv(name); return x && !strcmp(x, v); };
-    return RegionKnobs{is("IVX_PART", "two"), is("IVX_PACK", "0"), is("IVX_FILL", "old"), is("IVX_FILTER", "0"), getenv("IVX_DENSE"), getenv("IVX_RP_ROWS")};
+    return RegionKnobs{is("IVX_PART", "two"), is("IVX_PACK", "0"), is("IVX_FILL", "old"), is("IVX_FILTER", "0"), getenv("IVX_DENSE"), getenv("IVX_RP_ROWS"), getenv("IVX_FILL_DRAIN")};
 }
 
 // fill pass: rows per lane and batch from the expected matches per row (cap / n: callers size the output from the count
@@ -1290,6 +1345,15 @@ int fill_rows_per_lane(const RegionKnobs &K, u64 cap, u64 n)
     const double per_row = (double)cap / (double)n;
     // (a round's pairs must fit half a staging ring: 64 * rows per lane * pairs per row <= ~205 of its 256, four sigma below it)
     return per_row <= 0.40 ? 8 : per_row <= 0.8 ? 4 : per_row <= 1.6 ? 2 : 1;
+}
+
+// lean fill: the active lanes at which a 64-row group's walk ends and leaves its tails to the batch's tail pass (k_fill_fast's
+// `drain`; 0: the plain walk, the kernel without a stash), by rows per lane.  Measured (profiles/fill_drain_ab.txt): 8 rows per
+// lane gain from 4 to 12 alike, 4 rows per lane gain at 16 and not at 8, 2 rows per lane gain nothing beyond their own spread.
+u32 fill_drain_of(const RegionKnobs &K, int b)
+{
+    if (K.fill_drain) { const int t = atoi(K.fill_drain); return t <= 0 ? 0u : (u32)t < RP_STASH ? (u32)t : RP_STASH; }
+    return b == 8 ? 12u : b == 4 ? 16u : 0u;
 }
 
 bool dense_fill_wanted(const RegionKnobs &K, u64 cap, u64 n)
@@ -1392,8 +1456,11 @@ ivx_status probe_pairs(ivx_ctx *ctx, const JoinIndexView &jv, u32 nreg, int mode
         u32 *rest_n = R.ctl->rest_n;                                    // batches, rows
         if (reused) IVX_HIP(ctx, hipMemsetAsync(rest_n, 0, 2 * sizeof(u32), st));   // (else: zeroed with the routing pass's counters just now)
         every_b([&](auto b) {
-            hipLaunchKernelGGL((k_fill_fast<decltype(b)::value>), dim3(RP_GRID), dim3(RP_T), 0, st, jv, R.se, (const u32 *)R.ctl->rcur, (const u32 *)R.ctl->cfirst, R.pt, ob, op, cap, cur,
-                               (const u32 *)bsel, R.rowbits, R.rest, R.rest_rows, rest_n);
+            const u32 drain = fill_drain_of(K, decltype(b)::value);
+            with_bools([&](auto dr) {
+                hipLaunchKernelGGL((k_fill_fast<decltype(b)::value, IVX_B(dr)>), dim3(RP_GRID), dim3(RP_T), 0, st, jv, R.se, (const u32 *)R.ctl->rcur, (const u32 *)R.ctl->cfirst, R.pt, ob, op, cap, cur,
+                                   (const u32 *)bsel, R.rowbits, R.rest, R.rest_rows, rest_n, drain);
+            }, drain != 0);
         });
         hipLaunchKernelGGL(k_fill_rest, dim3(512), dim3(256), 0, st, jv, R.se, R.pt, (const FpRest *)R.rest, (const u64 *)R.rest_rows, (const u32 *)rest_n, ob, op, cap, cur, R.ds, R.de, R.rowbits);
         IVX_HIP(ctx, hipGetLastError());
