@@ -330,6 +330,32 @@ class Session:
                     t.close()
         return pa.table([_import(*o) for o in outs], names=["contig", "pos_start", "pos_end", "coverage"])
 
+    def depth_per_base(self, reads, prior=None, lengths=None, zero_based=False, batch_rows=8192, filter_flag=1796, min_mapq=0):
+        """depth(..., per_base = true): a generator of tables (contig Utf8, pos Int32, coverage Int16), one row per position
+        of every contig of `lengths` that has reads, contigs in byte order, at most batch_rows rows a table and one contig a
+        table.  Positions are [0, len) when zero_based, else [1, len + 1).  The profile is built on the first next(); the
+        stream is closed when the generator is exhausted, closed or dropped."""
+        tabs = [_Exported(t) if t is not None else None for t in (reads, prior, lengths)]
+        h = C.c_void_p()
+        try:
+            b = [t.c if t is not None else _Batch(None, None) for t in tabs]
+            self._chk(lib().brh_depth_per_base_open(self.h, b[0], b[1], b[2], C.c_int(int(bool(zero_based))), C.c_uint32(int(filter_flag)),
+                                                    C.c_uint32(int(min_mapq)), C.byref(h)))
+        finally:
+            for t in tabs:
+                if t is not None:
+                    t.close()
+        try:
+            while True:
+                outs = [_out() for _ in range(3)]
+                done = C.c_int(0)
+                self._chk(lib().brh_depth_per_base_next(h, C.c_uint64(int(batch_rows)), C.byref(done), *[C.byref(x) for pair in outs for x in pair]))
+                if done.value:
+                    return
+                yield pa.table([_import(*o) for o in outs], names=["contig", "pos", "coverage"])
+        finally:
+            lib().brh_depth_per_base_close(h)
+
 
 class JoinStream:
     """brh_join_stream: the build side indexed once, probe RecordBatches pushed one by one and coalesced into

@@ -1140,6 +1140,51 @@ extern "C" ivx_status ivx_complement(ivx_ctx *ctx, int mem, const uint32_t *key,
     return IVX_OK;
 }
 
+namespace {
+
+// the 17 input arguments of ivx_depth / ivx_depth_profile_build: the checks made on the host, then the columns on the device
+struct DepthIn {
+    const u32 *rkey, *rpos, *rflags, *rmapq, *ops, *skey, *ss, *se, *key_len; const i32 *off, *sw;
+};
+
+ivx_status depth_check_args(ivx_ctx *ctx, int mem, const uint32_t *rkey, const uint32_t *rpos, const int32_t *cigar_offsets, uint64_t n_reads,
+                            const uint32_t *skey, const uint32_t *sstart, const uint32_t *send, uint64_t n_seg, uint32_t *n_keys)
+{
+    if (mem != IVX_MEM_HOST && mem != IVX_MEM_DEVICE) return ctx->fail(IVX_ERR_INVALID, "bad mem");
+    if (n_reads && (!rpos || !cigar_offsets)) return ctx->fail(IVX_ERR_INVALID, "depth: null read position or CIGAR offset column");
+    if (n_seg && (!sstart || !send)) return ctx->fail(IVX_ERR_INVALID, "depth: null segment coordinate column");
+    if (n_reads >= 0xFFFFFFFFull || n_seg >= 0x7FFFFFFFull) return ctx->fail(IVX_ERR_INVALID, "depth: too many rows in one call");
+    if (*n_keys == 0 && !rkey && !skey) *n_keys = 1;
+    return IVX_OK;
+}
+
+ivx_status depth_stage_in(ivx_ctx *ctx, int mem,
+                          const uint32_t *rkey, const uint32_t *rpos, const uint32_t *rflags, const uint32_t *rmapq,
+                          const int32_t *cigar_offsets, const uint32_t *cigar_ops, uint64_t n_reads,
+                          const uint32_t *skey, const uint32_t *sstart, const uint32_t *send, const int32_t *sweight, uint64_t n_seg,
+                          uint32_t n_keys, const uint32_t *key_len, DepthIn *d)
+{
+    IVX_HIP(ctx, hipSetDevice(ctx->device));
+    // IVX_MEM_HOST: the ops column is staged up to the last offset (the device checks the offsets before it reads an op)
+    u64 n_ops_host = 0;
+    if (mem == IVX_MEM_HOST && n_reads && cigar_offsets[n_reads] > 0) n_ops_host = (u64)cigar_offsets[n_reads] / 4;
+    if (n_ops_host && !cigar_ops) return ctx->fail(IVX_ERR_INVALID, "depth: null CIGAR data buffer");
+    IVX_TRY(stage_in(ctx, mem, WS_IN_KEY, rkey, n_reads, &d->rkey));
+    IVX_TRY(stage_in(ctx, mem, WS_IN_START, rpos, n_reads, &d->rpos));
+    IVX_TRY(stage_in(ctx, mem, WS_IN_END, rflags, n_reads, &d->rflags));
+    IVX_TRY(stage_in(ctx, mem, WS_IN2_KEY, rmapq, n_reads, &d->rmapq));
+    IVX_TRY(stage_in(ctx, mem, WS_IN2_START, n_reads ? cigar_offsets : nullptr, n_reads + 1, &d->off));
+    IVX_TRY(stage_in(ctx, mem, WS_IN2_END, cigar_ops, n_ops_host, &d->ops));
+    IVX_TRY(stage_in(ctx, mem, WS_IN3_KEY, skey, n_seg, &d->skey));
+    IVX_TRY(stage_in(ctx, mem, WS_IN3_START, sstart, n_seg, &d->ss));
+    IVX_TRY(stage_in(ctx, mem, WS_IN3_END, send, n_seg, &d->se));
+    IVX_TRY(stage_in(ctx, mem, WS_IN3_WEIGHT, sweight, n_seg, &d->sw));
+    IVX_TRY(stage_in(ctx, mem, WS_IN_KEYLEN, key_len, (u64)n_keys, &d->key_len));
+    return IVX_OK;
+}
+
+}  // namespace
+
 extern "C" ivx_status ivx_depth(ivx_ctx *ctx, int mem,
                                 const uint32_t *rkey, const uint32_t *rpos, const uint32_t *rflags, const uint32_t *rmapq,
                                 const int32_t *cigar_offsets, const uint32_t *cigar_ops, uint64_t n_reads,
@@ -1151,32 +1196,14 @@ extern "C" ivx_status ivx_depth(ivx_ctx *ctx, int mem,
     if (!ctx) return IVX_ERR_INVALID;
     if (!n_out) return ctx->fail(IVX_ERR_INVALID, "null n_out");
     *n_out = 0;
-    if (mem != IVX_MEM_HOST && mem != IVX_MEM_DEVICE) return ctx->fail(IVX_ERR_INVALID, "bad mem");
-    if (n_reads && (!rpos || !cigar_offsets)) return ctx->fail(IVX_ERR_INVALID, "depth: null read position or CIGAR offset column");
-    if (n_seg && (!sstart || !send)) return ctx->fail(IVX_ERR_INVALID, "depth: null segment coordinate column");
-    if (n_reads >= 0xFFFFFFFFull || n_seg >= 0x7FFFFFFFull) return ctx->fail(IVX_ERR_INVALID, "depth: too many rows in one call");
-    if (n_keys == 0 && !rkey && !skey) n_keys = 1;
+    IVX_TRY(depth_check_args(ctx, mem, rkey, rpos, cigar_offsets, n_reads, skey, sstart, send, n_seg, &n_keys));
     ctx->sub_plan.valid = false; ctx->join_plan.valid = false;   // as any other call between a sizing call and its fill
     CallMetrics cm(ctx, false, n_reads + n_seg);
     if (n_reads == 0 && n_seg == 0) return IVX_OK;
-    IVX_HIP(ctx, hipSetDevice(ctx->device));
-    // IVX_MEM_HOST: the ops column is staged up to the last offset (the device checks the offsets before it reads an op)
-    u64 n_ops_host = 0;
-    if (mem == IVX_MEM_HOST && n_reads && cigar_offsets[n_reads] > 0) n_ops_host = (u64)cigar_offsets[n_reads] / 4;
-    if (n_ops_host && !cigar_ops) return ctx->fail(IVX_ERR_INVALID, "depth: null CIGAR data buffer");
-    const u32 *drk, *drp, *drf, *drm, *dops, *dsk, *dss, *dse, *dkl; const i32 *doff, *dsw;
+    DepthIn d;
     u32 *ok, *os, *oe; i32 *oc;
-    IVX_TRY(stage_in(ctx, mem, WS_IN_KEY, rkey, n_reads, &drk));
-    IVX_TRY(stage_in(ctx, mem, WS_IN_START, rpos, n_reads, &drp));
-    IVX_TRY(stage_in(ctx, mem, WS_IN_END, rflags, n_reads, &drf));
-    IVX_TRY(stage_in(ctx, mem, WS_IN2_KEY, rmapq, n_reads, &drm));
-    IVX_TRY(stage_in(ctx, mem, WS_IN2_START, n_reads ? cigar_offsets : nullptr, n_reads + 1, &doff));
-    IVX_TRY(stage_in(ctx, mem, WS_IN2_END, cigar_ops, n_ops_host, &dops));
-    IVX_TRY(stage_in(ctx, mem, WS_IN3_KEY, skey, n_seg, &dsk));
-    IVX_TRY(stage_in(ctx, mem, WS_IN3_START, sstart, n_seg, &dss));
-    IVX_TRY(stage_in(ctx, mem, WS_IN3_END, send, n_seg, &dse));
-    IVX_TRY(stage_in(ctx, mem, WS_IN3_WEIGHT, sweight, n_seg, &dsw));
-    IVX_TRY(stage_in(ctx, mem, WS_IN_KEYLEN, key_len, (u64)n_keys, &dkl));
+    IVX_TRY(depth_stage_in(ctx, mem, rkey, rpos, rflags, rmapq, cigar_offsets, cigar_ops, n_reads, skey, sstart, send, sweight, n_seg,
+                           n_keys, key_len, &d));
     IVX_TRY(stage_out(ctx, mem, WS_OUT_A, out_key, cap, &ok));
     IVX_TRY(stage_out(ctx, mem, WS_OUT_B, out_start, cap, &os));
     IVX_TRY(stage_out(ctx, mem, WS_OUT_C, out_end, cap, &oe));
@@ -1185,8 +1212,8 @@ extern "C" ivx_status ivx_depth(ivx_ctx *ctx, int mem,
     u64 m = 0;
     {
         KernelTimer t(ctx);
-        ivx_status st = ivx_depth_device(ctx, drk, drp, drf, drm, doff, dops, n_reads, dsk, dss, dse, dsw, n_seg,
-                                         n_keys, dkl, filter_flag, min_mapq, ok, os, oe, oc, cap, &m);
+        ivx_status st = ivx_depth_device(ctx, d.rkey, d.rpos, d.rflags, d.rmapq, d.off, d.ops, n_reads, d.skey, d.ss, d.se, d.sw, n_seg,
+                                         n_keys, d.key_len, filter_flag, min_mapq, ok, os, oe, oc, cap, &m);
         *n_out = m;
         if (st != IVX_OK) return st;
     }
@@ -1197,6 +1224,113 @@ extern "C" ivx_status ivx_depth(ivx_ctx *ctx, int mem,
         IVX_TRY(copy_out(ctx, mem, out_end, oe, m));
         IVX_TRY(copy_out(ctx, mem, out_cov, oc, m));
     }
+    if (mem == IVX_MEM_HOST) IVX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return IVX_OK;
+}
+
+// ---------------------------------------------------------------- g': depth profiles (per-base depth())
+
+extern "C" ivx_status ivx_depth_profile_build(ivx_ctx *ctx, int mem,
+                                              const uint32_t *rkey, const uint32_t *rpos, const uint32_t *rflags, const uint32_t *rmapq,
+                                              const int32_t *cigar_offsets, const uint32_t *cigar_ops, uint64_t n_reads,
+                                              const uint32_t *skey, const uint32_t *sstart, const uint32_t *send, const int32_t *sweight, uint64_t n_seg,
+                                              uint32_t n_keys, const uint32_t *key_len, uint32_t filter_flag, uint32_t min_mapq,
+                                              ivx_index **out)
+{
+    if (!ctx) return IVX_ERR_INVALID;
+    if (!out) return ctx->fail(IVX_ERR_INVALID, "null out");
+    *out = nullptr;
+    IVX_TRY(depth_check_args(ctx, mem, rkey, rpos, cigar_offsets, n_reads, skey, sstart, send, n_seg, &n_keys));
+    ctx->sub_plan.valid = false; ctx->join_plan.valid = false;   // as any other call between a sizing call and its fill
+    CallMetrics cm(ctx, true, n_reads + n_seg);
+    DepthIn d{};
+    if (n_reads || n_seg)
+        IVX_TRY(depth_stage_in(ctx, mem, rkey, rpos, rflags, rmapq, cigar_offsets, cigar_ops, n_reads, skey, sstart, send, sweight, n_seg,
+                               n_keys, key_len, &d));
+    else IVX_HIP(ctx, hipSetDevice(ctx->device));
+    ivx_index *ix = new (std::nothrow) ivx_index();
+    if (!ix) return ctx->fail(IVX_ERR_OOM, "host allocation failed");
+    ix->kind = IVX_KIND_DEPTH_PROFILE; ix->device = ctx->device; ix->n = 0; ix->nkeys = n_keys;
+    ctx->building_bytes = 0;
+    u8 *seen = nullptr;
+    ivx_depth_evs evs{0, nullptr, nullptr};
+    ivx_status st = ivx_depth_profile_begin(ctx, ix, &seen);
+    if (st == IVX_OK) {
+        KernelTimer t(ctx);
+        st = ivx_depth_events(ctx, d.rkey, d.rpos, d.rflags, d.rmapq, d.off, d.ops, n_reads, d.skey, d.ss, d.se, d.sw, n_seg,
+                              n_keys, d.key_len, filter_flag, min_mapq, seen, &evs);
+        if (st == IVX_OK) st = ivx_depth_profile_finish(ctx, ix, evs);
+    }
+    if (st == IVX_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) st = ctx->fail(IVX_ERR_HIP, "depth profile build failed on device");
+    ctx->building_bytes = 0;
+    if (st != IVX_OK) { ivx_index_free(ix); return st; }
+    ix->n = ix->dp.steps;
+    ix->owner_bytes = ctx->live_index_bytes;                    // reserved against this context's limit until the profile is freed
+    ix->owner_bytes->fetch_add(ix->bytes, std::memory_order_relaxed);
+    ctx->metrics.build_mem_used += ix->bytes;
+    *out = ix;
+    return IVX_OK;
+}
+
+extern "C" void ivx_depth_profile_free(ivx_index *p) { if (p && p->kind == IVX_KIND_DEPTH_PROFILE) ivx_index_free(p); }
+extern "C" uint64_t ivx_depth_profile_steps(const ivx_index *p) { return p && p->kind == IVX_KIND_DEPTH_PROFILE ? p->dp.steps : 0; }
+extern "C" uint64_t ivx_depth_profile_device_bytes(const ivx_index *p) { return p && p->kind == IVX_KIND_DEPTH_PROFILE ? p->bytes : 0; }
+
+static ivx_status check_profile_args(ivx_ctx *ctx, const ivx_index *p, int mem)
+{
+    if (!p) return ctx->fail(IVX_ERR_INVALID, "null depth profile");
+    if (p->kind != IVX_KIND_DEPTH_PROFILE) return ctx->fail(IVX_ERR_UNSUPPORTED, "not a depth profile");
+    if (p->device != ctx->device) return ctx->fail(IVX_ERR_INVALID, "depth profile lives on another device");
+    if (mem != IVX_MEM_HOST && mem != IVX_MEM_DEVICE) return ctx->fail(IVX_ERR_INVALID, "bad mem");
+    IVX_HIP(ctx, hipSetDevice(ctx->device));
+    return IVX_OK;
+}
+
+extern "C" ivx_status ivx_depth_profile_read(ivx_ctx *ctx, const ivx_index *p, int mem,
+                                             uint32_t *out_key, uint32_t *out_pos, int32_t *out_cov, uint8_t *key_seen,
+                                             uint64_t cap, uint64_t *n_out)
+{
+    if (!ctx) return IVX_ERR_INVALID;
+    if (!n_out) return ctx->fail(IVX_ERR_INVALID, "null n_out");
+    *n_out = 0;
+    IVX_TRY(check_profile_args(ctx, p, mem));
+    const DepthProfileView &dp = p->dp;
+    const hipMemcpyKind kind = mem == IVX_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+    *n_out = dp.steps;
+    if (key_seen && p->nkeys) IVX_HIP(ctx, hipMemcpyAsync(key_seen, dp.seen, p->nkeys, kind, ctx->stream));
+    const bool sizing = cap == 0 && !out_key && !out_pos && !out_cov;
+    ivx_status st = IVX_OK;
+    if (!sizing && dp.steps > cap) st = ctx->fail(IVX_ERR_CAPACITY, "depth profile: output buffers too small");
+    else if (!sizing && dp.steps) {
+        if (out_key) IVX_HIP(ctx, hipMemcpyAsync(out_key, dp.key, dp.steps * sizeof(u32), kind, ctx->stream));
+        if (out_pos) IVX_HIP(ctx, hipMemcpyAsync(out_pos, dp.pos, dp.steps * sizeof(u32), kind, ctx->stream));
+        if (out_cov) IVX_HIP(ctx, hipMemcpyAsync(out_cov, dp.cov, dp.steps * sizeof(i32), kind, ctx->stream));
+    }
+    if (mem == IVX_MEM_HOST) IVX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return st;
+}
+
+extern "C" ivx_status ivx_depth_profile_expand(ivx_ctx *ctx, const ivx_index *p, int mem,
+                                               uint32_t key, uint32_t first_pos, uint64_t n, int skip_pos0,
+                                               int32_t *out_pos, void *out_cov)
+{
+    if (!ctx) return IVX_ERR_INVALID;
+    IVX_TRY(check_profile_args(ctx, p, mem));
+    if (key >= p->nkeys) return ctx->fail(IVX_ERR_INVALID, "depth profile: key id >= n_keys");
+    if (n > 0x100000000ull || (u64)first_pos + n > 0x100000000ull) return ctx->fail(IVX_ERR_INVALID, "depth profile: window ends beyond position 2^32 - 1");
+    if (mem == IVX_MEM_DEVICE && ((((uintptr_t)out_pos) & 3u) || (((uintptr_t)out_cov) & 1u)))
+        return ctx->fail(IVX_ERR_INVALID, "depth profile: output pointer not aligned to its element size");
+    ctx->sub_plan.valid = false; ctx->join_plan.valid = false;
+    if (n == 0) return IVX_OK;
+    i32 *dpos; int16_t *dcov;
+    IVX_TRY(stage_out(ctx, mem, WS_OUT_A, out_pos, n, &dpos));
+    IVX_TRY(stage_out(ctx, mem, WS_OUT_B, (int16_t *)out_cov, n, &dcov));
+    {
+        KernelTimer t(ctx);
+        IVX_TRY(ivx_depth_expand_device(ctx, p->dp, key, first_pos, n, skip_pos0 != 0, dpos, dcov));
+    }
+    IVX_TRY(copy_out(ctx, mem, out_pos, dpos, n));
+    IVX_TRY(copy_out(ctx, mem, (int16_t *)out_cov, dcov, n));
     if (mem == IVX_MEM_HOST) IVX_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return IVX_OK;
 }

@@ -148,7 +148,8 @@ __global__ __launch_bounds__(ivxscan::T_) void k_ops_reduce(DepthReads R, u64 n,
 
 // offs[tile] = the scan over every earlier tile.  Writes the events of the tile's ops at ev[ev0 + events before the op].
 __global__ __launch_bounds__(ivxscan::T_) void k_ops_apply(DepthReads R, u64 n, const OpState *__restrict__ offs,
-                                                           u64 *__restrict__ ev, u32 *__restrict__ dl, u64 ev0, u32 *maxpos)
+                                                           u64 *__restrict__ ev, u32 *__restrict__ dl, u64 ev0, u32 *maxpos,
+                                                           u8 *seen)
 {
     using namespace ivxscan;
     __shared__ OpState lds[T_ / IVX_WAVE + 1];
@@ -178,11 +179,14 @@ __global__ __launch_bounds__(ivxscan::T_) void k_ops_apply(DepthReads R, u64 n, 
             const u64 s64 = (u64)x[i].pos + before;
             u32 ps = sat32(s64), pe = sat32(s64 + x[i].len);
             u32 ds = 1u, de = 0xFFFFFFFFu;
+            bool left = true;                                // does one of the two events survive the clipping
             if (R.key_len) {                                 // the dense array has len + 1 slots (events.rs:181-185)
                 const u32 kl = R.key_len[x[i].key];
+                left = ps <= kl || pe <= kl;
                 if (ps > kl) { ps = 0; ds = 0; }
                 if (pe > kl) { pe = 0; de = 0; }
             }
+            if (seen && left) seen[x[i].key] = 1;            // (every writer stores the same byte)
             const u64 slot = ev0 + run.cnt, kw = (u64)x[i].key << 32;
             ev[slot] = kw | ps; dl[slot] = ds;
             ev[slot + 1] = kw | pe; dl[slot + 1] = de;
@@ -203,7 +207,7 @@ __global__ __launch_bounds__(ivxscan::T_) void k_ops_apply(DepthReads R, u64 n, 
 // weighted segment j -> events 2j, 2j + 1: (start, +w), (end (+) 1, -w); a skipped segment leaves two events without weight
 __global__ __launch_bounds__(DT) void k_seg_events(const u32 *__restrict__ skey, const u32 *__restrict__ ss, const u32 *__restrict__ se,
                                                    const i32 *__restrict__ sw, u64 n_seg, const u32 *__restrict__ key_len,
-                                                   u64 *__restrict__ ev, u32 *__restrict__ dl, u32 *maxpos)
+                                                   u64 *__restrict__ ev, u32 *__restrict__ dl, u32 *maxpos, u8 *seen)
 {
     const u64 j = (u64)blockIdx.x * DT + threadIdx.x;
     u32 mp = 0;
@@ -214,11 +218,14 @@ __global__ __launch_bounds__(DT) void k_seg_events(const u32 *__restrict__ skey,
             kw = (u64)k << 32;
             ps = ss[j]; pe = sat32((u64)se[j] + 1ull);
             ds = sw ? (u32)sw[j] : 1u; de = 0u - ds;
+            bool left = true;
             if (key_len) {
                 const u32 kl = key_len[k];
+                left = ps <= kl || pe <= kl;
                 if (ps > kl) { ps = 0; ds = 0; }
                 if (pe > kl) { pe = 0; de = 0; }
             }
+            if (seen && left) seen[k] = 1;
         }
         ev[2 * j] = kw | ps; dl[2 * j] = ds;
         ev[2 * j + 1] = kw | pe; dl[2 * j + 1] = de;
@@ -318,16 +325,18 @@ struct BlkOut {
 
 }  // namespace
 
+// The front half, up to the end of scan 1: the events sorted by (key, position) and (c, g) at the last event of every group.
+// out->n = 0: the input has no event.  seen (nullable, [nkeys], zeroed by the caller): seen[k] = 1 for every key that keeps
+// an event after the filter and the clipping.
 // Scratch: WS_SCAN0 / WS_SCAN1 (tile sums of the scans), WS_SA0 / WS_SB0 (event words, ping and pong), WS_SA1 / WS_SB1 (their
 // deltas), WS_T0 ((c, g) per event), and the sort's WS_SORTHIST.
-ivx_status ivx_depth_device(ivx_ctx *ctx, const u32 *rkey, const u32 *rpos, const u32 *rflags, const u32 *rmapq,
+ivx_status ivx_depth_events(ivx_ctx *ctx, const u32 *rkey, const u32 *rpos, const u32 *rflags, const u32 *rmapq,
                             const i32 *off, const u32 *ops, u64 n_reads,
                             const u32 *skey, const u32 *ss, const u32 *se, const i32 *sw, u64 n_seg,
-                            u32 nkeys, const u32 *key_len, u32 filter_flag, u32 min_mapq,
-                            u32 *ok, u32 *os, u32 *oe, i32 *oc, u64 cap, u64 *n_out)
+                            u32 nkeys, const u32 *key_len, u32 filter_flag, u32 min_mapq, u8 *seen, ivx_depth_evs *out)
 {
     using namespace ivxscan;
-    *n_out = 0;
+    out->n = 0; out->ev = nullptr; out->cg = nullptr;
     if (n_reads == 0 && n_seg == 0) return IVX_OK;
     hipStream_t st = ctx->stream;
     u64 *sc = ctx->d_scalars, *hs = ctx->h_scalars;
@@ -373,8 +382,8 @@ ivx_status ivx_depth_device(ivx_ctx *ctx, const u32 *rkey, const u32 *rpos, cons
     IVX_TRY(ctx->get_scratch(WS_SA1, E * sizeof(u32), (void **)&da));
     IVX_TRY(ctx->get_scratch(WS_SB1, E * sizeof(u32), (void **)&db));
     u32 *maxpos = (u32 *)(sc + DS_MAXPOS);
-    if (n_seg) hipLaunchKernelGGL(k_seg_events, dim3(dgrid(n_seg)), dim3(DT), 0, st, skey, ss, se, sw, n_seg, key_len, wa, da, maxpos);
-    if (n_rev) hipLaunchKernelGGL(k_ops_apply, dim3((u32)nblk), dim3(T_), 0, st, R, n_ops, (const OpState *)tsum, wa, da, 2 * n_seg, maxpos);
+    if (n_seg) hipLaunchKernelGGL(k_seg_events, dim3(dgrid(n_seg)), dim3(DT), 0, st, skey, ss, se, sw, n_seg, key_len, wa, da, maxpos, seen);
+    if (n_rev) hipLaunchKernelGGL(k_ops_apply, dim3((u32)nblk), dim3(T_), 0, st, R, n_ops, (const OpState *)tsum, wa, da, 2 * n_seg, maxpos, seen);
     IVX_HIP(ctx, hipGetLastError());
     IVX_HIP(ctx, hipMemcpyAsync(hs + DS_MAXPOS, sc + DS_MAXPOS, sizeof(u64), hipMemcpyDeviceToHost, st));
     IVX_HIP(ctx, hipStreamSynchronize(st));
@@ -391,10 +400,32 @@ ivx_status ivx_depth_device(ivx_ctx *ctx, const u32 *rkey, const u32 *rpos, cons
     IVX_TRY(ivx_radix_sort(ctx, 1, a, b, E, f, nf, &in_b, true, pay));
     const u64 *ev = in_b ? wb : wa; const u32 *dl = pay[in_b];
 
-    // ---- scan 1, scan 2 (its output pass writes the blocks)
+    // ---- scan 1
     uint2 *cg;
     IVX_TRY(ctx->get_scratch(WS_T0, E * sizeof(uint2), (void **)&cg));
     IVX_TRY((inclusive_f<EvScan>(ctx, EvIn{ev, dl}, EvOut{ev, cg, E}, E)));
+    out->n = E; out->ev = ev; out->cg = cg;
+    return IVX_OK;
+}
+
+ivx_status ivx_depth_device(ivx_ctx *ctx, const u32 *rkey, const u32 *rpos, const u32 *rflags, const u32 *rmapq,
+                            const i32 *off, const u32 *ops, u64 n_reads,
+                            const u32 *skey, const u32 *ss, const u32 *se, const i32 *sw, u64 n_seg,
+                            u32 nkeys, const u32 *key_len, u32 filter_flag, u32 min_mapq,
+                            u32 *ok, u32 *os, u32 *oe, i32 *oc, u64 cap, u64 *n_out)
+{
+    using namespace ivxscan;
+    *n_out = 0;
+    ivx_depth_evs evs;
+    IVX_TRY(ivx_depth_events(ctx, rkey, rpos, rflags, rmapq, off, ops, n_reads, skey, ss, se, sw, n_seg, nkeys, key_len,
+                             filter_flag, min_mapq, nullptr, &evs));
+    const u64 E = evs.n;
+    if (E == 0) return IVX_OK;
+    hipStream_t st = ctx->stream;
+    u64 *sc = ctx->d_scalars, *hs = ctx->h_scalars;
+    const u64 *ev = evs.ev; const uint2 *cg = evs.cg;
+
+    // ---- scan 2 (its output pass writes the blocks)
     const BlkIn bin{ev, cg, E};
     IVX_TRY((inclusive_f<BlkScan>(ctx, bin, BlkOut{bin, ok, os, oe, oc, cap, sc + DS_TOTAL}, E)));
     IVX_HIP(ctx, hipGetLastError());

@@ -241,6 +241,16 @@ struct NearestView {
     JoinIndexView ov;                               // overlap index for k>1 include_overlaps
 };
 
+// a depth profile (ivx_depth_expand.hip): the step function of depth() -- per key ascending, every position where the
+// coverage changes and the coverage from there on
+struct DepthProfileView {
+    const u32 *key, *pos;   // [steps] ordered by (key, position)
+    const i32 *cov;         // [steps] coverage from pos on
+    const u32 *koff;        // [nkeys+1] first step of the key
+    const u8 *seen;         // [nkeys] 1: the key kept an event after the filter and the clipping
+    u64 steps;
+};
+
 struct ivx_index {
     u64 serial = 0;             // unique per built index (a freed index's address may come back)
     int kind = 0;
@@ -263,6 +273,7 @@ struct ivx_index {
     NearestView nv{};
     JoinIndexView nroute{};     // nearest index: regions that only ROUTE big probe batches (origin/span/kcnt/kreg/rkey/hdr; no cells)
     u32 nroute_nreg = 0;
+    DepthProfileView dp{};      // IVX_KIND_DEPTH_PROFILE
     int flags = 0;              // IVX_IXF_*
 };
 enum { IVX_IXF_REGION_ROWVAL = 1 };   // count/coverage index: jv is usable for the region-partitioned per-row probe
@@ -312,5 +323,18 @@ ivx_status ivx_depth_device(ivx_ctx *ctx, const u32 *rkey, const u32 *rpos, cons
                             const u32 *skey, const u32 *sstart, const u32 *send, const i32 *sweight, u64 n_seg,
                             u32 nkeys, const u32 *key_len, u32 filter_flag, u32 min_mapq,
                             u32 *ok, u32 *os, u32 *oe, i32 *oc, u64 cap, u64 *n_out);
+
+// its front half: the events sorted by (key, position), and (c, g) = (the key's running sum, the group's sum) at the last
+// event of every (key, position) group; all of it in scratch
+struct ivx_depth_evs { u64 n; const u64 *ev; const uint2 *cg; };
+ivx_status ivx_depth_events(ivx_ctx *ctx, const u32 *rkey, const u32 *rpos, const u32 *rflags, const u32 *rmapq,
+                            const i32 *cigar_offsets, const u32 *cigar_ops, u64 n_reads,
+                            const u32 *skey, const u32 *sstart, const u32 *send, const i32 *sweight, u64 n_seg,
+                            u32 nkeys, const u32 *key_len, u32 filter_flag, u32 min_mapq, u8 *seen, ivx_depth_evs *out);
+// ivx_depth_expand.hip: the steps of those events as a profile (ix->dp), and windows of a profile expanded to positions
+ivx_status ivx_depth_profile_begin(ivx_ctx *ctx, ivx_index *ix, u8 **seen);     // before the front half: key_seen and the per-key table, zeroed
+ivx_status ivx_depth_profile_finish(ivx_ctx *ctx, ivx_index *ix, const ivx_depth_evs &evs);
+ivx_status ivx_depth_expand_device(ivx_ctx *ctx, const DepthProfileView &dp, u32 key, u32 first_pos, u64 n, int skip_pos0,
+                                   i32 *out_pos, int16_t *out_cov);
 
 ivx_status ivx_index_alloc(ivx_ctx *ctx, ivx_index *ix, size_t bytes, void **out);

@@ -719,13 +719,26 @@ void ids_of(const StrCol &c, const NameDict &d, std::vector<uint32_t> *out)
 
 }  // namespace
 
-extern "C" int brh_depth(brh_session *s, brh_batch reads, brh_batch prior, brh_batch lengths, uint32_t filter_flag, uint32_t min_mapq,
-                         ArrowArray *contig, ArrowSchema *contig_schema, ArrowArray *pos_start, ArrowSchema *pos_start_schema,
-                         ArrowArray *pos_end, ArrowSchema *pos_end_schema, ArrowArray *coverage, ArrowSchema *coverage_schema)
+namespace {
+
+// the inputs of one depth() call as ivx_depth / ivx_depth_profile_build take them.  The read columns point into the caller's
+// batch: use them before the call that brought the batch returns.
+struct DepthInputs {
+    bool has_prior = false, has_len = false;
+    uint64_t n_reads = 0, n_seg = 0;
+    uint32_t nk = 1;
+    NameDict dict;
+    std::vector<uint32_t> rkey, skey, ss, se, key_len;
+    std::vector<int32_t> sw;
+    const uint32_t *rpos = nullptr, *rflags = nullptr, *rmapq = nullptr, *cops = nullptr;
+    const int32_t *coff = nullptr;
+    int load(brh_session *s, brh_batch reads, brh_batch prior, brh_batch lengths);
+};
+
+int DepthInputs::load(brh_session *s, brh_batch reads, brh_batch prior, brh_batch lengths)
 {
-    if (!s) return 1;
     if (!reads.array || !reads.schema) return fail(s, "depth: null reads batch");
-    const bool has_prior = prior.array != nullptr, has_len = lengths.array != nullptr;
+    has_prior = prior.array != nullptr; has_len = lengths.array != nullptr;
     // ---- the reads batch (events.rs:106-112)
     StrCol chrom;
     const ArrowArray *start, *flags, *mapq;
@@ -738,12 +751,12 @@ extern "C" int brh_depth(brh_session *s, brh_batch reads, brh_batch prior, brh_b
         return fail(s, "depth: string CIGAR columns are not supported, use the binary CIGAR column");
     if (std::strcmp(cf, "z")) return fail(s, "depth: unsupported data type " + std::string(cf) + " for column 'cigar'; expected Binary");
     const ArrowArray *cigar = reads.array->children[cc];
-    const uint64_t n_reads = (uint64_t)reads.array->length;
+    n_reads = (uint64_t)reads.array->length;
     // ---- prior blocks (the output of an earlier call) and the length table
     StrCol pcontig, lname;
     const ArrowArray *pstart = nullptr, *pend = nullptr, *pcov = nullptr;
     char pcov_fmt = 0;
-    uint64_t n_seg = 0;
+    n_seg = 0;
     if (has_prior) {
         if (get_contig(s, prior, "contig", &pcontig)) return 1;
         const char *names[3] = {"pos_start", "pos_end", "coverage"};
@@ -765,16 +778,13 @@ extern "C" int brh_depth(brh_session *s, brh_batch reads, brh_batch prior, brh_b
         if (get_contig(s, lengths, "name", &lname) || get_pos(s, lengths, "length", "length", &pl) || resolve_i64(s, pl, &len64)) return 1;
     }
     // ---- contig ids.  With a length table only its contigs exist: reads (and prior blocks) elsewhere are skipped (events.rs:247-260)
-    NameDict dict;
     {
         std::vector<std::string_view> uniq;
         if (has_len) collect_names(lname, &uniq);
         else { collect_names(chrom, &uniq); if (has_prior) collect_names(pcontig, &uniq); }
         dict.finish(uniq);
     }
-    const uint32_t nk = (uint32_t)std::max<size_t>(dict.names.size(), 1);
-    std::vector<uint32_t> rkey, skey, ss, se, key_len;
-    std::vector<int32_t> sw;
+    nk = (uint32_t)std::max<size_t>(dict.names.size(), 1);
     ids_of(chrom, dict, &rkey);
     for (uint64_t i = 0; i < n_reads; i++) if (slot_null(start, (int64_t)i)) rkey[i] = IVX_NULL_IDX;       // events.rs:114
     if (has_prior) {
@@ -795,11 +805,31 @@ extern "C" int brh_depth(brh_session *s, brh_batch reads, brh_batch prior, brh_b
             key_len[k] = v < 0 ? 0u : (v > (int64_t)UINT32_MAX ? UINT32_MAX : (uint32_t)v);
         }
     }
-    const uint32_t *rpos = n_reads ? (const uint32_t *)start->buffers[1] + start->offset : nullptr;
-    const uint32_t *rflags = n_reads ? (const uint32_t *)flags->buffers[1] + flags->offset : nullptr;
-    const uint32_t *rmapq = n_reads ? (const uint32_t *)mapq->buffers[1] + mapq->offset : nullptr;
-    const int32_t *coff = n_reads ? (const int32_t *)cigar->buffers[1] + cigar->offset : nullptr;
-    const uint32_t *cops = n_reads ? (const uint32_t *)cigar->buffers[2] : nullptr;
+    rpos = n_reads ? (const uint32_t *)start->buffers[1] + start->offset : nullptr;
+    rflags = n_reads ? (const uint32_t *)flags->buffers[1] + flags->offset : nullptr;
+    rmapq = n_reads ? (const uint32_t *)mapq->buffers[1] + mapq->offset : nullptr;
+    coff = n_reads ? (const int32_t *)cigar->buffers[1] + cigar->offset : nullptr;
+    cops = n_reads ? (const uint32_t *)cigar->buffers[2] : nullptr;
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int brh_depth(brh_session *s, brh_batch reads, brh_batch prior, brh_batch lengths, uint32_t filter_flag, uint32_t min_mapq,
+                         ArrowArray *contig, ArrowSchema *contig_schema, ArrowArray *pos_start, ArrowSchema *pos_start_schema,
+                         ArrowArray *pos_end, ArrowSchema *pos_end_schema, ArrowArray *coverage, ArrowSchema *coverage_schema)
+{
+    if (!s) return 1;
+    DepthInputs in;
+    if (in.load(s, reads, prior, lengths)) return 1;
+    const bool has_prior = in.has_prior, has_len = in.has_len;
+    const uint64_t n_reads = in.n_reads, n_seg = in.n_seg;
+    const uint32_t nk = in.nk;
+    const NameDict &dict = in.dict;
+    const std::vector<uint32_t> &rkey = in.rkey, &skey = in.skey, &ss = in.ss, &se = in.se, &key_len = in.key_len;
+    const std::vector<int32_t> &sw = in.sw;
+    const uint32_t *rpos = in.rpos, *rflags = in.rflags, *rmapq = in.rmapq, *cops = in.cops;
+    const int32_t *coff = in.coff;
     // ---- sizing call, then the fill call
     auto call = [&](uint32_t *ok, uint32_t *os, uint32_t *oe, int32_t *oc, uint64_t cap, uint64_t *m) {
         return ivx_depth(s->ctx, IVX_MEM_HOST, rkey.data(), rpos, rflags, rmapq, coff, cops, n_reads,
@@ -822,6 +852,82 @@ extern "C" int brh_depth(brh_session *s, brh_batch reads, brh_batch prior, brh_b
     make_primitive<int32_t>(pos_end, o32e.data(), (int64_t)m2, nullptr); make_schema(pos_end_schema, "i", "pos_end", false);
     make_primitive<int16_t>(coverage, o16.data(), (int64_t)m2, nullptr); make_schema(coverage_schema, "s", "coverage", false);
     return 0;
+}
+
+// ---- depth(per_base = true): the reference's PerBaseEmitter (coverage.rs:271-365) as a pull stream over ONE depth profile
+struct brh_depth_stream {
+    brh_session *s = nullptr;
+    ivx_index *profile = nullptr;
+    std::vector<std::string> names;         // contigs in byte order = key ids
+    std::vector<uint32_t> key_len;
+    std::vector<uint8_t> seen;
+    int zero_based = 0;
+    uint32_t key = 0;                       // the contig being emitted
+    uint64_t next = 0;                      // rows of it already returned
+};
+
+extern "C" int brh_depth_per_base_open(brh_session *s, brh_batch reads, brh_batch prior, brh_batch lengths, int zero_based,
+                                       uint32_t filter_flag, uint32_t min_mapq, brh_depth_stream **out)
+{
+    if (!s) return 1;
+    if (!out) return fail(s, "depth_per_base: null out");
+    *out = nullptr;
+    if (!lengths.array)                     // physical_exec.rs:299-303
+        return fail(s, "per_base mode requires dense accumulation (BAM header with contig lengths). "
+                       "Sparse fallback (e.g. MemTable) is not supported for per_base output.");
+    DepthInputs in;
+    if (in.load(s, reads, prior, lengths)) return 1;
+    std::unique_ptr<brh_depth_stream> ds(new brh_depth_stream());
+    ds->s = s; ds->zero_based = zero_based != 0;
+    ivx_status st = ivx_depth_profile_build(s->ctx, IVX_MEM_HOST, in.rkey.data(), in.rpos, in.rflags, in.rmapq, in.coff, in.cops, in.n_reads,
+                                            in.has_prior ? in.skey.data() : nullptr, in.ss.data(), in.se.data(), in.has_prior ? in.sw.data() : nullptr,
+                                            in.n_seg, in.nk, in.key_len.data(), filter_flag, min_mapq, &ds->profile);
+    if (st != IVX_OK) return fail_ivx(s, st);
+    ds->names = in.dict.names; ds->key_len = in.key_len;
+    ds->seen.assign(in.nk, 0);
+    uint64_t steps = 0;
+    st = ivx_depth_profile_read(s->ctx, ds->profile, IVX_MEM_HOST, nullptr, nullptr, nullptr, ds->seen.data(), 0, &steps);
+    if (st != IVX_OK) { ivx_depth_profile_free(ds->profile); return fail_ivx(s, st); }
+    if (ds->names.empty()) ds->seen.assign(ds->seen.size(), 0);     // (an empty length table: key 0 stands for no contig)
+    *out = ds.release();
+    return 0;
+}
+
+extern "C" int brh_depth_per_base_next(brh_depth_stream *ds, uint64_t max_rows, int *done,
+                                       ArrowArray *contig, ArrowSchema *contig_schema, ArrowArray *pos, ArrowSchema *pos_schema,
+                                       ArrowArray *coverage, ArrowSchema *coverage_schema)
+{
+    if (!ds) return 1;
+    brh_session *s = ds->s;
+    if (!done) return fail(s, "depth_per_base: null done");
+    *done = 0;
+    if (max_rows == 0) return fail(s, "depth_per_base: max_rows must be at least 1");
+    // the next contig that was touched and still has rows (coverage.rs:319-321)
+    while (ds->key < ds->seen.size() && (!ds->seen[ds->key] || ds->next >= ds->key_len[ds->key])) { ds->key++; ds->next = 0; }
+    if (ds->key >= ds->seen.size()) { *done = 1; return 0; }
+    const std::string &name = ds->names[ds->key];
+    uint64_t n = std::min<uint64_t>(max_rows, (uint64_t)ds->key_len[ds->key] - ds->next);      // a batch never spans two contigs
+    if (!name.empty()) n = std::min<uint64_t>(n, std::max<uint64_t>(1, (uint64_t)INT32_MAX / name.size()));   // Utf8 offsets are int32
+    n = std::min<uint64_t>(n, (uint64_t)INT32_MAX);
+    // zero_based: positions [0, len); else [1, len + 1), never adding slot 0 (coverage.rs:294-301)
+    const uint64_t first = (ds->zero_based ? 0u : 1u) + ds->next;
+    std::vector<int32_t> p32(n); std::vector<int16_t> c16(n);
+    const ivx_status st = ivx_depth_profile_expand(s->ctx, ds->profile, IVX_MEM_HOST, ds->key, (uint32_t)first, n, ds->zero_based ? 0 : 1,
+                                                   p32.data(), c16.data());
+    if (st != IVX_OK) return fail_ivx(s, st);
+    const std::vector<uint32_t> ids(n, ds->key);
+    make_utf8(contig, ds->names, ids.data(), (int64_t)n); make_schema(contig_schema, "u", "contig", true);
+    make_primitive<int32_t>(pos, p32.data(), (int64_t)n, nullptr); make_schema(pos_schema, "i", "pos", false);
+    make_primitive<int16_t>(coverage, c16.data(), (int64_t)n, nullptr); make_schema(coverage_schema, "s", "coverage", false);
+    ds->next += n;
+    return 0;
+}
+
+extern "C" void brh_depth_per_base_close(brh_depth_stream *ds)
+{
+    if (!ds) return;
+    if (ds->profile) ivx_depth_profile_free(ds->profile);
+    delete ds;
 }
 
 // ---- f3: payload gather

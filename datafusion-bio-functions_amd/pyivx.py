@@ -29,7 +29,12 @@ SYMBOLS = [
     "ivx_ctx_metrics", "ivx_ctx_reset_metrics", "ivx_ctx_set_memory_limit", "ivx_ctx_trim", "ivx_scatter_fixed",
     "ivx_ctx_reserved_bytes", "ivx_ctx_set_build_overlap", "ivx_index_layout",
     "ivx_probe_mark_build", "ivx_bits_mark", "ivx_bits_select", "ivx_depth",
+    "ivx_depth_profile_build", "ivx_depth_profile_free", "ivx_depth_profile_steps", "ivx_depth_profile_device_bytes",
+    "ivx_depth_profile_read", "ivx_depth_profile_expand",
 ]
+
+# outputs one workgroup of the expand kernel makes (csrc/ivx_depth_expand.hip DEPTH_EXPAND_TILE; tests/test_depth_per_base_tile.py)
+DEPTH_EXPAND_TILE = 4096
 
 # slots of ivx_index_layout (include/ivx.h IVX_LAYOUT_*), in order
 LAYOUT_SLOTS = ["kind", "sh0", "nlev", "levrows", "rcells", "rcs", "nreg", "pk24", "slow", "fg", "fbits", "nroute_nreg", "lbuild"]
@@ -82,6 +87,18 @@ def lib():
         L.ivx_depth.argtypes = ([C.c_void_p, C.c_int] + [C.c_void_p] * 6 + [C.c_uint64] + [C.c_void_p] * 4 + [C.c_uint64] +
                                 [C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32] + [C.c_void_p] * 4 +
                                 [C.c_uint64, C.POINTER(C.c_uint64)])
+        L.ivx_depth_profile_build.restype = C.c_int
+        L.ivx_depth_profile_build.argtypes = L.ivx_depth.argtypes[:18] + [C.POINTER(C.c_void_p)]
+        L.ivx_depth_profile_free.restype = None
+        L.ivx_depth_profile_free.argtypes = [C.c_void_p]
+        L.ivx_depth_profile_steps.restype = C.c_uint64
+        L.ivx_depth_profile_steps.argtypes = [C.c_void_p]
+        L.ivx_depth_profile_device_bytes.restype = C.c_uint64
+        L.ivx_depth_profile_device_bytes.argtypes = [C.c_void_p]
+        L.ivx_depth_profile_read.restype = C.c_int
+        L.ivx_depth_profile_read.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_uint64, C.POINTER(C.c_uint64)]
+        L.ivx_depth_profile_expand.restype = C.c_int
+        L.ivx_depth_profile_expand.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 
@@ -139,6 +156,76 @@ class Index:
     def free(self):
         if self.h:
             lib().ivx_index_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class DepthProfile:
+    """the step function of depth() on the device (include/ivx.h ivx_depth_profile_*).  `ctx` is the context that built it;
+    read() and expand() take any other context of the same device as ctx=."""
+
+    def __init__(self, ctx, handle, n_keys, device):
+        self.ctx, self.h, self.n_keys, self.device = ctx, handle, n_keys, device
+
+    def steps(self):
+        return lib().ivx_depth_profile_steps(self.h)
+
+    @property
+    def device_bytes(self):
+        return lib().ivx_depth_profile_device_bytes(self.h)
+
+    def read(self, device=False, ctx=None):
+        """-> (key u32, pos u32, coverage i32, key_seen u8[n_keys]); numpy arrays, or torch tensors with device=True
+        (the unsigned columns as their int32 bits)"""
+        ctx = ctx or self.ctx
+        n = self.steps()
+        if device:
+            import torch
+            dev = self.device or "cuda:0"
+            out = [torch.empty(max(n, 1), dtype=torch.int32, device=dev) for _ in range(3)]
+            seen = torch.empty(max(self.n_keys, 1), dtype=torch.uint8, device=dev)
+        else:
+            out = [np.empty(max(n, 1), dt) for dt in (np.uint32, np.uint32, np.int32)]
+            seen = np.empty(max(self.n_keys, 1), np.uint8)
+        m = C.c_uint64(0)
+        ctx._chk0(lib().ivx_depth_profile_read(ctx.h, self.h, MEM_DEVICE if device else MEM_HOST, *[_ptr(o) for o in out], _ptr(seen),
+                                               max(n, 1), C.byref(m)))
+        return tuple(o[:m.value] for o in out) + (seen[:self.n_keys],)
+
+    def expand(self, key, first_pos, n, skip_pos0=False, want_pos=True, out_pos=None, out_cov=None, device=None, ctx=None, want_cov=True):
+        """positions [first_pos, first_pos + n) of `key` -> (pos int32 or None, coverage int16 or None).  out_pos / out_cov:
+        caller's buffers of n elements (numpy, or torch device tensors: then the call may return with the kernel in
+        flight); without them numpy arrays are made, or device tensors with device=True."""
+        ctx = ctx or self.ctx
+        given = [o for o in (out_pos, out_cov) if o is not None]
+        if device is None:
+            device = bool(given) and _is_torch(given[0])
+        if device:
+            import torch
+            dev = given[0].device if given else (self.device or "cuda:0")
+            if want_pos and out_pos is None:
+                out_pos = torch.empty(n, dtype=torch.int32, device=dev)
+            if want_cov and out_cov is None:
+                out_cov = torch.empty(n, dtype=torch.int16, device=dev)
+            assert all(o is None or (o.is_contiguous() and o.numel() >= n) for o in (out_pos, out_cov))
+        else:
+            if want_pos and out_pos is None:
+                out_pos = np.empty(n, np.int32)
+            if want_cov and out_cov is None:
+                out_cov = np.empty(n, np.int16)
+        mem = _mem_of(out_pos, out_cov) if (out_pos is not None or out_cov is not None) else (MEM_DEVICE if device else MEM_HOST)
+        ctx._chk(lib().ivx_depth_profile_expand(ctx.h, self.h, mem, int(key), int(first_pos), int(n), int(bool(skip_pos0)),
+                                                _ptr(out_pos), _ptr(out_cov)))
+        return out_pos, out_cov
+
+    def free(self):
+        if self.h:
+            lib().ivx_depth_profile_free(self.h)
             self.h = None
 
     def __del__(self):
@@ -500,6 +587,40 @@ class Ctx:
         [packed u32 ops]) and of weighted segments (skey/sstart/send/sweight); numpy arrays or torch device tensors.
         cap=None: a sizing call, then the fill call.  outputs: which of (key, start, end, coverage) to ask for.
         -> (key, start, end, coverage), None where not asked for."""
+        args, mem, cols, n_keys = self._depth_args(rkey, rpos, rflags, rmapq, cigar_offsets, cigar_ops, skey, sstart, send, sweight,
+                                                   n_keys, key_len, filter_flag, min_mapq)
+
+        def bufs(cap):
+            if mem == MEM_DEVICE:
+                import torch
+                dev = next(c for c in cols if c is not None).device
+                return [torch.empty(cap, dtype=torch.int32, device=dev) if w else None for w in outputs]
+            return [np.empty(cap, dt) if w else None for w, dt in zip(outputs, (np.uint32, np.uint32, np.uint32, np.int32))]
+        if cap is None:
+            m = C.c_uint64(0)
+            self._chk(lib().ivx_depth(self.h, *args, None, None, None, None, 0, C.byref(m)))
+            cap = max(m.value, 1)
+        out = bufs(cap)
+        m2 = C.c_uint64(0)
+        st = lib().ivx_depth(self.h, *args, *[_ptr(o) for o in out], cap, C.byref(m2))
+        if st == ERR_CAPACITY:
+            raise IvxError(st, f"{lib().ivx_last_error(self.h).decode()} (needed {m2.value})")
+        self._chk(st)
+        return tuple(None if o is None else o[:m2.value] for o in out)
+
+    def depth_profile(self, rkey=None, rpos=None, rflags=None, rmapq=None, cigar_offsets=None, cigar_ops=None,
+                      skey=None, sstart=None, send=None, sweight=None, n_keys=None, key_len=None, filter_flag=1796, min_mapq=0):
+        """the depth profile of the same inputs as depth() -> DepthProfile (per-base output: .expand())"""
+        args, mem, cols, n_keys = self._depth_args(rkey, rpos, rflags, rmapq, cigar_offsets, cigar_ops, skey, sstart, send, sweight,
+                                                   n_keys, key_len, filter_flag, min_mapq)
+        h = C.c_void_p()
+        self._chk(lib().ivx_depth_profile_build(self.h, *args, C.byref(h)))
+        dev = next(c for c in cols if c is not None).device if mem == MEM_DEVICE else None
+        return DepthProfile(self, h, n_keys, dev)
+
+    def _depth_args(self, rkey, rpos, rflags, rmapq, cigar_offsets, cigar_ops, skey, sstart, send, sweight, n_keys, key_len,
+                    filter_flag, min_mapq):
+        """the 17 input arguments of ivx_depth / ivx_depth_profile_build -> (ctypes args, mem, normalised columns, n_keys)"""
         cols = [rkey, rpos, rflags, rmapq, cigar_offsets, cigar_ops, skey, sstart, send, sweight, key_len]
         mem = _mem_of(*cols)
         n_reads = 0 if rpos is None else (int(rpos.numel()) if _is_torch(rpos) else len(rpos))
@@ -524,24 +645,7 @@ class Ctx:
                 n_keys = mk + 1
         args = (C.c_int(mem), _ptr(rkey), _ptr(rpos), _ptr(rflags), _ptr(rmapq), _ptr(cigar_offsets), _ptr(cigar_ops), n_reads,
                 _ptr(skey), _ptr(sstart), _ptr(send), _ptr(sweight), n_seg, n_keys, _ptr(key_len), int(filter_flag), int(min_mapq))
-
-        def bufs(cap):
-            if mem == MEM_DEVICE:
-                import torch
-                dev = next(c for c in cols if c is not None).device
-                return [torch.empty(cap, dtype=torch.int32, device=dev) if w else None for w in outputs]
-            return [np.empty(cap, dt) if w else None for w, dt in zip(outputs, (np.uint32, np.uint32, np.uint32, np.int32))]
-        if cap is None:
-            m = C.c_uint64(0)
-            self._chk(lib().ivx_depth(self.h, *args, None, None, None, None, 0, C.byref(m)))
-            cap = max(m.value, 1)
-        out = bufs(cap)
-        m2 = C.c_uint64(0)
-        st = lib().ivx_depth(self.h, *args, *[_ptr(o) for o in out], cap, C.byref(m2))
-        if st == ERR_CAPACITY:
-            raise IvxError(st, f"{lib().ivx_last_error(self.h).decode()} (needed {m2.value})")
-        self._chk(st)
-        return tuple(None if o is None else o[:m2.value] for o in out)
+        return args, mem, cols, n_keys
 
     # ---- f3: compute::take of payload columns ----
     def take_fixed(self, src, idx, src_valid_bits=None, want_valid=True):

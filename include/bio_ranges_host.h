@@ -159,6 +159,26 @@ int brh_depth(brh_session *s, brh_batch reads, brh_batch prior, brh_batch length
               struct ArrowArray *pos_end, struct ArrowSchema *pos_end_schema,
               struct ArrowArray *coverage, struct ArrowSchema *coverage_schema);
 
+/* depth('reads', zero_based, per_base = true): one (contig, pos Int32, coverage Int16) row per position of every contig that
+ * has reads (bio-function-pileup coverage.rs:271-365 PerBaseEmitter, physical_exec.rs:404-414, :517-548), as a pull stream.
+ * open: the column rules of brh_depth; builds ONE depth profile (ivx_depth_profile_build) that the stream keeps on the device.
+ *   lengths is required: without it the error is the reference's "per_base mode requires dense accumulation (BAM header with
+ *   contig lengths). Sparse fallback (e.g. MemTable) is not supported for per_base output." (physical_exec.rs:299-303).
+ * next: mirrors PerBaseEmitter::next_batch.  Contigs come in byte order of their names, and only those an event touched
+ *   (events.rs:198-206) -- also when its events cancel; a contig of the length table without reads is absent.  Positions run
+ *   [0, len) when zero_based, else [1, len + 1) without the depth array's slot 0 (coverage.rs:294-301).  A batch holds at most
+ *   max_rows rows and never spans two contigs; max_rows = 0 is an error.  *done = 1, with no arrays exported, once everything
+ *   has been returned.  contig: Utf8 (the name repeated, filled on the host); pos: Int32; coverage: Int16 (`as i16`).
+ * close: frees the profile.  The stream must not outlive its session. */
+typedef struct brh_depth_stream brh_depth_stream;
+int  brh_depth_per_base_open(brh_session *s, brh_batch reads, brh_batch prior, brh_batch lengths, int zero_based,
+                             uint32_t filter_flag, uint32_t min_mapq, brh_depth_stream **out);
+int  brh_depth_per_base_next(brh_depth_stream *ds, uint64_t max_rows, int *done,
+                             struct ArrowArray *contig, struct ArrowSchema *contig_schema,
+                             struct ArrowArray *pos, struct ArrowSchema *pos_schema,
+                             struct ArrowArray *coverage, struct ArrowSchema *coverage_schema);
+void brh_depth_per_base_close(brh_depth_stream *ds);
+
 /* compute::take of ONE payload column with an index array a join / nearest call returned
  * (interval_join.rs:1655-1667, nearest.rs:469-482), on the device.  column: any fixed-width primitive
  * (ints, floats, date/time/timestamp/duration, decimal128/256, fixed-size binary of 1/2/4/8/16/32 bytes),

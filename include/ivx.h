@@ -77,7 +77,8 @@ enum {
     IVX_KIND_OVERLAP = 0,   /* COITree per key            interval_join.rs:745-763 (a1+a2)        */
     IVX_KIND_COUNT = 1,     /* CountOverlapIndex          interval_tree.rs:20-39, :113-143        */
     IVX_KIND_COVERAGE = 2,  /* merged COITree             interval_tree.rs:52-111 (coverage=true) */
-    IVX_KIND_NEAREST = 3    /* NearestIntervalIndex       nearest_index.rs:44-71                  */
+    IVX_KIND_NEAREST = 3,   /* NearestIntervalIndex       nearest_index.rs:44-71                  */
+    IVX_KIND_DEPTH_PROFILE = 4  /* the step function of depth(); made by ivx_depth_profile_build only, see there */
 };
 
 #define IVX_NULL_IDX 0xFFFFFFFFu   /* NULL build row (interval_join.rs:1233 u32::MAX marker) */
@@ -349,6 +350,52 @@ ivx_status ivx_depth(ivx_ctx *ctx, int mem,
                      uint32_t n_keys, const uint32_t *key_len /* nullable */, uint32_t filter_flag, uint32_t min_mapq,
                      uint32_t *out_key, uint32_t *out_start, uint32_t *out_end, int32_t *out_cov,
                      uint64_t cap, uint64_t *n_out);
+
+/* ---- g': per-base depth(), the pileup crate's per_base = true form (bio-function-pileup table_function.rs:97-123,
+ *      coverage.rs:271-365 PerBaseEmitter, physical_exec.rs:404-414, :517-548): one (position, coverage Int16) row per base.
+ *      It cannot be made from ivx_depth's blocks -- a key whose coverage never returns to 0 loses its last open block, and a
+ *      key whose events all cancel has no block at all, yet the reference emits both -- so the step function itself is kept
+ *      on the device, as a DEPTH PROFILE, and windows of it are expanded to positions.
+ *      A profile is an ivx_index of kind IVX_KIND_DEPTH_PROFILE: immutable after the build, readable and expandable by any
+ *      context on the same device, its device bytes reserved against the building context's memory limit until it is freed
+ *      (ivx_ctx_reserved_bytes shows them); a build that would go over the limit returns IVX_ERR_OOM.  ivx_index_build does
+ *      not make one, the probes refuse one (IVX_ERR_UNSUPPORTED), and the calls below refuse any other index.
+ *      build: the 17 input arguments of ivx_depth, with the same checks and the same IVX_ERR_INVALID cases; drops the state a
+ *      sizing call of another operation left on the context.  STEPS: with p_i, g_i, c_i as for ivx_depth's blocks, position
+ *      i is a step iff g_i != 0 (that is c_i != c_(i-1), c_(-1) = 0); the profile holds (key, p_i, c_i) ordered by (key,
+ *      position), the first step of every key, and key_seen[k] = 1 iff key k keeps at least one event after the read filter
+ *      and the key_len clipping, whether or not those events cancel (the reference's "touched" contig: events.rs:198-206,
+ *      physical_exec.rs:378-382).  A call without any event gives a valid empty profile. */
+ivx_status ivx_depth_profile_build(ivx_ctx *ctx, int mem,
+                                   const uint32_t *rkey /* nullable */, const uint32_t *rpos,
+                                   const uint32_t *rflags /* nullable */, const uint32_t *rmapq /* nullable */,
+                                   const int32_t *cigar_offsets, const uint32_t *cigar_ops, uint64_t n_reads,
+                                   const uint32_t *skey /* nullable */, const uint32_t *sstart, const uint32_t *send,
+                                   const int32_t *sweight /* nullable */, uint64_t n_seg,
+                                   uint32_t n_keys, const uint32_t *key_len /* nullable */, uint32_t filter_flag, uint32_t min_mapq,
+                                   ivx_index **out);
+/*      Same contract as ivx_index_free (synchronise every context that expanded it in device mode first). */
+void       ivx_depth_profile_free(ivx_index *profile);
+uint64_t   ivx_depth_profile_steps(const ivx_index *profile);
+uint64_t   ivx_depth_profile_device_bytes(const ivx_index *profile);
+/*      Copy the steps out (tests, diagnostics, accumulation).  cap = 0 with NULL outputs only counts; cap < *n_out is
+ *      IVX_ERR_CAPACITY with *n_out = the size needed; any output may be NULL on its own.  key_seen (nullable, [n_keys],
+ *      where `mem` says) is written whenever it is given. */
+ivx_status ivx_depth_profile_read(ivx_ctx *ctx, const ivx_index *profile, int mem,
+                                  uint32_t *out_key, uint32_t *out_pos, int32_t *out_cov,
+                                  uint8_t *key_seen /* nullable */, uint64_t cap, uint64_t *n_out);
+/*      The window [first_pos, first_pos + n) of `key`, for i < n and p = first_pos + i:
+ *        out_pos[i] = (int32_t)p                           (int32_t[n], nullable)
+ *        out_cov[i] = (int16_t)(C(p) - c0), int32 wrap     (int16_t[n], nullable)
+ *      C(p) = the c of the key's last step at a position <= p, 0 if there is none; c0 = the c of the key's step at
+ *      position 0 when skip_pos0 is set and that step exists, else 0 -- the reference's 1-based emitter starts at index 1
+ *      and never adds depth[0] (coverage.rs:294-301).  A key without steps gives zeros; n = 0 is a no-op.
+ *      IVX_ERR_INVALID: key >= n_keys; first_pos + n > 2^32; in device mode a pointer that is not aligned to its element.
+ *      Both columns leave in 16-byte stores whatever the alignment of the two pointers; only the window's first and last
+ *      partial 16 bytes are written element by element.  IVX_MEM_DEVICE calls may return with the kernel in flight. */
+ivx_status ivx_depth_profile_expand(ivx_ctx *ctx, const ivx_index *profile, int mem,
+                                    uint32_t key, uint32_t first_pos, uint64_t n, int skip_pos0,
+                                    int32_t *out_pos /* nullable */, void *out_cov /* int16_t[n], nullable */);
 
 /* ---- f3: `compute::take` of payload columns with the index arrays the probes return
  *      (interval_join.rs:1655-1667, nearest.rs:469-482).  idx[i] == IVX_NULL_IDX or a null source

@@ -94,6 +94,19 @@ extern "C" {
                      n_keys: u32, key_len: *const u32, filter_flag: u32, min_mapq: u32,
                      out_key: *mut u32, out_start: *mut u32, out_end: *mut u32, out_cov: *mut i32,
                      cap: u64, n_out: *mut u64) -> i32;
+    // per-base depth(): a depth profile is an IvxIndex of kind IVX_KIND_DEPTH_PROFILE; out_cov of expand is int16_t[n]
+    pub fn ivx_depth_profile_build(ctx: *mut IvxCtx, mem: i32, rkey: *const u32, rpos: *const u32, rflags: *const u32,
+                                   rmapq: *const u32, cigar_offsets: *const i32, cigar_ops: *const u32, n_reads: u64,
+                                   skey: *const u32, sstart: *const u32, send: *const u32, sweight: *const i32, n_seg: u64,
+                                   n_keys: u32, key_len: *const u32, filter_flag: u32, min_mapq: u32,
+                                   out: *mut *mut IvxIndex) -> i32;
+    pub fn ivx_depth_profile_free(profile: *mut IvxIndex);
+    pub fn ivx_depth_profile_steps(profile: *const IvxIndex) -> u64;
+    pub fn ivx_depth_profile_device_bytes(profile: *const IvxIndex) -> u64;
+    pub fn ivx_depth_profile_read(ctx: *mut IvxCtx, profile: *const IvxIndex, mem: i32, out_key: *mut u32, out_pos: *mut u32,
+                                  out_cov: *mut i32, key_seen: *mut u8, cap: u64, n_out: *mut u64) -> i32;
+    pub fn ivx_depth_profile_expand(ctx: *mut IvxCtx, profile: *const IvxIndex, mem: i32, key: u32, first_pos: u32, n: u64,
+                                    skip_pos0: i32, out_pos: *mut i32, out_cov: *mut c_void) -> i32;
     pub fn ivx_take_fixed(ctx: *mut IvxCtx, mem: i32, src: *const c_void, width: u32, n_src: u64, src_valid_bits: *const u8,
                           idx: *const u32, n: u64, out: *mut c_void, out_valid: *mut u8) -> i32;
     pub fn ivx_scatter_fixed(ctx: *mut IvxCtx, mem: i32, src: *const c_void, width: u32, idx: *const u32, n: u64,

@@ -15,6 +15,7 @@ use datafusion::common::{DataFusionError, Result};
 
 #[repr(C)] pub struct BrhSession { _p: [u8; 0] }
 #[repr(C)] pub struct BrhJoinStream { _p: [u8; 0] }
+#[repr(C)] pub struct BrhDepthStream { _p: [u8; 0] }
 #[repr(C)] pub struct BrhBatch { pub array: *const FFI_ArrowArray, pub schema: *const FFI_ArrowSchema }
 #[repr(C)] pub struct BrhColumns { pub keys: *const *const c_char, pub n_keys: c_int, pub start: *const c_char, pub end: *const c_char }
 
@@ -46,6 +47,14 @@ extern "C" {
                                 probe_idx: *mut FFI_ArrowArray, probe_idx_schema: *mut FFI_ArrowSchema,
                                 batch_offsets: *mut FFI_ArrowArray, batch_offsets_schema: *mut FFI_ArrowSchema) -> c_int;
     pub fn brh_join_stream_close(js: *mut BrhJoinStream);
+    // depth(path, zero_based, per_base = true): PerBaseEmitter as a pull stream over one depth profile kept on the device
+    pub fn brh_depth_per_base_open(s: *mut BrhSession, reads: BrhBatch, prior: BrhBatch, lengths: BrhBatch, zero_based: c_int,
+                                   filter_flag: u32, min_mapq: u32, out: *mut *mut BrhDepthStream) -> c_int;
+    pub fn brh_depth_per_base_next(ds: *mut BrhDepthStream, max_rows: u64, done: *mut c_int,
+                                   contig: *mut FFI_ArrowArray, contig_schema: *mut FFI_ArrowSchema,
+                                   pos: *mut FFI_ArrowArray, pos_schema: *mut FFI_ArrowSchema,
+                                   coverage: *mut FFI_ArrowArray, coverage_schema: *mut FFI_ArrowSchema) -> c_int;
+    pub fn brh_depth_per_base_close(ds: *mut BrhDepthStream);
 }
 
 /// What `IntervalJoinStream` keeps per partition when `Algorithm::Hip` is selected.
