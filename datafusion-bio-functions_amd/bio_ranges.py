@@ -135,6 +135,12 @@ class Session:
         """device bytes the session may reserve (MemoryReservation, interval_join.rs:614-639); 0 = no limit"""
         self._chk(lib().brh_session_set_memory_limit(self.h, C.c_uint64(int(nbytes))))
 
+    def reserved_bytes(self):
+        """device bytes the session holds reserved right now: scratch plus live indexes and depth profiles"""
+        n = C.c_uint64(0)
+        self._chk(lib().brh_session_reserved_bytes(self.h, C.byref(n)))
+        return n.value
+
     # ---- count_overlaps / coverage: RangeTableFunction (table_function.rs:521-560)
     def _count(self, left, right, cols_left, cols_right, strict, coverage):
         L, R = _Exported(left), _Exported(right)
@@ -355,6 +361,73 @@ class Session:
                 yield pa.table([_import(*o) for o in outs], names=["contig", "pos", "coverage"])
         finally:
             lib().brh_depth_per_base_close(h)
+
+    def depth_stream(self, lengths=None, filter_flag=1796, min_mapq=0):
+        """depth() over a stream of read batches (brh_depth_push): -> DepthStream"""
+        return DepthStream(self, lengths, filter_flag, min_mapq)
+
+
+class DepthStream:
+    """brh_depth_push: read tables pushed one by one, each accumulated into a depth profile on the device; finish() gives the
+    table Session.depth() gives for all of them together, finish_per_base() the tables of Session.depth_per_base().  Also a
+    context manager; close() is run when the object is dropped."""
+
+    def __init__(self, session, lengths=None, filter_flag=1796, min_mapq=0):
+        self.session = session
+        self.h = C.c_void_p()
+        L = _Exported(lengths) if lengths is not None else None
+        try:
+            session._chk(lib().brh_depth_push_open(session.h, L.c if L is not None else _Batch(None, None), C.c_uint32(int(filter_flag)),
+                                                   C.c_uint32(int(min_mapq)), C.byref(self.h)))
+        finally:
+            if L is not None:
+                L.close()
+
+    def push(self, table):
+        T = _Exported(table)
+        try:
+            self.session._chk(lib().brh_depth_push_batch(self.h, T.c))
+        finally:
+            T.close()
+
+    def finish(self):
+        """-> contig Utf8, pos_start Int32, pos_end Int32, coverage Int16 of everything pushed"""
+        outs = [_out() for _ in range(4)]
+        self.session._chk(lib().brh_depth_push_finish(self.h, *[C.byref(x) for pair in outs for x in pair]))
+        return pa.table([_import(*o) for o in outs], names=["contig", "pos_start", "pos_end", "coverage"])
+
+    def finish_per_base(self, zero_based=False, batch_rows=8192):
+        """a generator of tables (contig Utf8, pos Int32, coverage Int16) like Session.depth_per_base; the stream is finished
+        on the first next()"""
+        h = C.c_void_p()
+        self.session._chk(lib().brh_depth_push_finish_per_base(self.h, C.c_int(int(bool(zero_based))), C.byref(h)))
+        try:
+            while True:
+                outs = [_out() for _ in range(3)]
+                done = C.c_int(0)
+                self.session._chk(lib().brh_depth_per_base_next(h, C.c_uint64(int(batch_rows)), C.byref(done), *[C.byref(x) for pair in outs for x in pair]))
+                if done.value:
+                    return
+                yield pa.table([_import(*o) for o in outs], names=["contig", "pos", "coverage"])
+        finally:
+            lib().brh_depth_per_base_close(h)
+
+    def close(self):
+        if self.h:
+            lib().brh_depth_push_close(self.h)
+            self.h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class JoinStream:

@@ -1335,6 +1335,72 @@ extern "C" ivx_status ivx_depth_profile_expand(ivx_ctx *ctx, const ivx_index *p,
     return IVX_OK;
 }
 
+extern "C" ivx_status ivx_depth_profile_merge(ivx_ctx *ctx, const ivx_index *a, const ivx_index *b, ivx_index **out)
+{
+    if (!ctx) return IVX_ERR_INVALID;
+    if (!out) return ctx->fail(IVX_ERR_INVALID, "null out");
+    *out = nullptr;
+    IVX_TRY(check_profile_args(ctx, a, IVX_MEM_DEVICE));
+    IVX_TRY(check_profile_args(ctx, b, IVX_MEM_DEVICE));
+    ctx->sub_plan.valid = false; ctx->join_plan.valid = false;   // as any other call between a sizing call and its fill
+    if (a->dp.steps + b->dp.steps >= 0xFFFFFF00ull)
+        return ctx->fail(IVX_ERR_INVALID, "depth profile merge: more than 2^32-257 steps in the two profiles");
+    CallMetrics cm(ctx, true, a->dp.steps + b->dp.steps);
+    ivx_index *ix = new (std::nothrow) ivx_index();
+    if (!ix) return ctx->fail(IVX_ERR_OOM, "host allocation failed");
+    ix->kind = IVX_KIND_DEPTH_PROFILE; ix->device = ctx->device; ix->n = 0; ix->nkeys = a->nkeys > b->nkeys ? a->nkeys : b->nkeys;
+    ctx->building_bytes = 0;
+    u8 *seen = nullptr;
+    ivx_status st = ivx_depth_profile_begin(ctx, ix, &seen);
+    if (st == IVX_OK) {
+        KernelTimer t(ctx);
+        st = ivx_depth_profile_merge_device(ctx, a->dp, a->nkeys, b->dp, b->nkeys, ix);
+    }
+    if (st == IVX_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) st = ctx->fail(IVX_ERR_HIP, "depth profile merge failed on device");
+    ctx->building_bytes = 0;
+    if (st != IVX_OK) { ivx_index_free(ix); return st; }
+    ix->n = ix->dp.steps;
+    ix->owner_bytes = ctx->live_index_bytes;                    // reserved against this context's limit until the profile is freed
+    ix->owner_bytes->fetch_add(ix->bytes, std::memory_order_relaxed);
+    ctx->metrics.build_mem_used += ix->bytes;
+    *out = ix;
+    return IVX_OK;
+}
+
+extern "C" ivx_status ivx_depth_profile_blocks(ivx_ctx *ctx, const ivx_index *p, int mem,
+                                               uint32_t *out_key, uint32_t *out_start, uint32_t *out_end, int32_t *out_cov,
+                                               uint64_t cap, uint64_t *n_out)
+{
+    if (!ctx) return IVX_ERR_INVALID;
+    if (!n_out) return ctx->fail(IVX_ERR_INVALID, "null n_out");
+    *n_out = 0;
+    IVX_TRY(check_profile_args(ctx, p, mem));
+    ctx->sub_plan.valid = false; ctx->join_plan.valid = false;
+    CallMetrics cm(ctx, false, p->dp.steps);
+    u32 *ok, *os, *oe; i32 *oc;
+    IVX_TRY(stage_out(ctx, mem, WS_OUT_A, out_key, cap, &ok));
+    IVX_TRY(stage_out(ctx, mem, WS_OUT_B, out_start, cap, &os));
+    IVX_TRY(stage_out(ctx, mem, WS_OUT_C, out_end, cap, &oe));
+    IVX_TRY(stage_out(ctx, mem, WS_OUT_D, out_cov, cap, &oc));
+    const bool sizing = cap == 0 && !out_key && !out_start && !out_end && !out_cov;
+    u64 m = 0;
+    {
+        KernelTimer t(ctx);
+        ivx_status st = ivx_depth_profile_blocks_device(ctx, p->dp, ok, os, oe, oc, cap, &m);
+        *n_out = m;
+        if (st != IVX_OK) return st;
+    }
+    if (!sizing) {
+        cm.out(m);
+        IVX_TRY(copy_out(ctx, mem, out_key, ok, m));
+        IVX_TRY(copy_out(ctx, mem, out_start, os, m));
+        IVX_TRY(copy_out(ctx, mem, out_end, oe, m));
+        IVX_TRY(copy_out(ctx, mem, out_cov, oc, m));
+    }
+    if (mem == IVX_MEM_HOST) IVX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return IVX_OK;
+}
+
 extern "C" ivx_status ivx_take_fixed(ivx_ctx *ctx, int mem, const void *src, uint32_t width, uint64_t n_src,
                                      const uint8_t *src_valid_bits, const uint32_t *idx, uint64_t n, void *out, uint8_t *out_valid)
 {

@@ -185,6 +185,14 @@ ivx_status ivx_depth_profile_begin(ivx_ctx *ctx, ivx_index *ix, u8 **seen)
     return IVX_OK;
 }
 
+// the per-key table of a profile's key column (also what a merge rebuilds: ivx_depth_merge.hip)
+ivx_status ivx_depth_profile_koff(ivx_ctx *ctx, const u32 *skey, u32 steps, u32 nkeys, u32 *koff)
+{
+    hipLaunchKernelGGL(k_profile_koff, dim3((u32)(((u64)nkeys + 1 + PT - 1) / PT)), dim3(PT), 0, ctx->stream, skey, steps, nkeys, koff);
+    IVX_HIP(ctx, hipGetLastError());
+    return IVX_OK;
+}
+
 // Scratch: WS_SCAN0 / WS_SCAN1 (tile sums of the counting scan); reads the front half's WS_SA0 / WS_SB0 and WS_T0.
 ivx_status ivx_depth_profile_finish(ivx_ctx *ctx, ivx_index *ix, const ivx_depth_evs &evs)
 {
@@ -206,8 +214,7 @@ ivx_status ivx_depth_profile_finish(ivx_ctx *ctx, ivx_index *ix, const ivx_depth
     IVX_TRY(ivx_index_alloc(ctx, ix, S * sizeof(i32), (void **)&sv));
     IVX_TRY((inclusive_f<CntScan>(ctx, in, StepOut{in, sk, sp, sv, sc + PS_TOTAL}, evs.n)));
     u32 *koff = const_cast<u32 *>(ix->dp.koff);
-    hipLaunchKernelGGL(k_profile_koff, dim3((u32)(((u64)ix->nkeys + 1 + PT - 1) / PT)), dim3(PT), 0, st, (const u32 *)sk, (u32)S, ix->nkeys, koff);
-    IVX_HIP(ctx, hipGetLastError());
+    IVX_TRY(ivx_depth_profile_koff(ctx, sk, (u32)S, ix->nkeys, koff));
     ix->dp.key = sk; ix->dp.pos = sp; ix->dp.cov = sv; ix->dp.steps = S;
     return IVX_OK;
 }

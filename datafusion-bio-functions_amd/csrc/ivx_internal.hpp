@@ -334,7 +334,11 @@ ivx_status ivx_depth_events(ivx_ctx *ctx, const u32 *rkey, const u32 *rpos, cons
 // ivx_depth_expand.hip: the steps of those events as a profile (ix->dp), and windows of a profile expanded to positions
 ivx_status ivx_depth_profile_begin(ivx_ctx *ctx, ivx_index *ix, u8 **seen);     // before the front half: key_seen and the per-key table, zeroed
 ivx_status ivx_depth_profile_finish(ivx_ctx *ctx, ivx_index *ix, const ivx_depth_evs &evs);
+ivx_status ivx_depth_profile_koff(ivx_ctx *ctx, const u32 *skey, u32 steps, u32 nkeys, u32 *koff);    // koff[k] = the first step with key >= k
 ivx_status ivx_depth_expand_device(ivx_ctx *ctx, const DepthProfileView &dp, u32 key, u32 first_pos, u64 n, int skip_pos0,
                                    i32 *out_pos, int16_t *out_cov);
+// ivx_depth_merge.hip: ix (from ivx_depth_profile_begin, nkeys = the larger of the two) = a + b; the coverage blocks of a profile
+ivx_status ivx_depth_profile_merge_device(ivx_ctx *ctx, const DepthProfileView &a, u32 nka, const DepthProfileView &b, u32 nkb, ivx_index *ix);
+ivx_status ivx_depth_profile_blocks_device(ivx_ctx *ctx, const DepthProfileView &dp, u32 *ok, u32 *os, u32 *oe, i32 *oc, u64 cap, u64 *n_out);
 
 ivx_status ivx_index_alloc(ivx_ctx *ctx, ivx_index *ix, size_t bytes, void **out);

@@ -417,6 +417,13 @@ extern "C" int brh_session_set_strict_null_contigs(brh_session *s, int on)
     return 0;
 }
 
+extern "C" int brh_session_reserved_bytes(brh_session *s, uint64_t *out)
+{
+    if (!s || !out) return 1;
+    *out = ivx_ctx_reserved_bytes(s->ctx);
+    return 0;
+}
+
 extern "C" int brh_session_set_memory_limit(brh_session *s, uint64_t bytes)
 {
     if (!s) return 1;
@@ -717,6 +724,26 @@ void ids_of(const StrCol &c, const NameDict &d, std::vector<uint32_t> *out)
     }
 }
 
+// the length table (name Utf8, length: any integer type, clamped to [0, 2^32-1]) -> its contigs in byte order and their lengths
+// (at least one slot: key 0 stands for no contig when the table is empty)
+int load_lengths(brh_session *s, brh_batch lengths, NameDict *dict, std::vector<uint32_t> *key_len)
+{
+    StrCol lname; PosCol pl;
+    std::vector<int64_t> len64;
+    if (get_contig(s, lengths, "name", &lname) || get_pos(s, lengths, "length", "length", &pl) || resolve_i64(s, pl, &len64)) return 1;
+    std::vector<std::string_view> uniq;
+    collect_names(lname, &uniq);
+    dict->finish(uniq);
+    key_len->assign(std::max<size_t>(dict->names.size(), 1), 0);
+    for (int64_t i = 0; i < lname.a->length; i++) {
+        if (lname.null_at(i)) continue;
+        const uint32_t k = dict->id_of(lname.at(i));
+        const int64_t v = len64[(size_t)i];
+        (*key_len)[k] = v < 0 ? 0u : (v > (int64_t)UINT32_MAX ? UINT32_MAX : (uint32_t)v);
+    }
+    return 0;
+}
+
 }  // namespace
 
 namespace {
@@ -753,7 +780,7 @@ int DepthInputs::load(brh_session *s, brh_batch reads, brh_batch prior, brh_batc
     const ArrowArray *cigar = reads.array->children[cc];
     n_reads = (uint64_t)reads.array->length;
     // ---- prior blocks (the output of an earlier call) and the length table
-    StrCol pcontig, lname;
+    StrCol pcontig;
     const ArrowArray *pstart = nullptr, *pend = nullptr, *pcov = nullptr;
     char pcov_fmt = 0;
     n_seg = 0;
@@ -772,16 +799,11 @@ int DepthInputs::load(brh_session *s, brh_batch reads, brh_batch prior, brh_batc
         }
         n_seg = (uint64_t)prior.array->length;
     }
-    std::vector<int64_t> len64;
-    if (has_len) {
-        PosCol pl;
-        if (get_contig(s, lengths, "name", &lname) || get_pos(s, lengths, "length", "length", &pl) || resolve_i64(s, pl, &len64)) return 1;
-    }
     // ---- contig ids.  With a length table only its contigs exist: reads (and prior blocks) elsewhere are skipped (events.rs:247-260)
-    {
+    if (has_len) { if (load_lengths(s, lengths, &dict, &key_len)) return 1; }
+    else {
         std::vector<std::string_view> uniq;
-        if (has_len) collect_names(lname, &uniq);
-        else { collect_names(chrom, &uniq); if (has_prior) collect_names(pcontig, &uniq); }
+        collect_names(chrom, &uniq); if (has_prior) collect_names(pcontig, &uniq);
         dict.finish(uniq);
     }
     nk = (uint32_t)std::max<size_t>(dict.names.size(), 1);
@@ -794,15 +816,6 @@ int DepthInputs::load(brh_session *s, brh_batch reads, brh_batch prior, brh_batc
             ss[j] = ((const uint32_t *)pstart->buffers[1])[pstart->offset + j];            // Int32 positions are the u32's bits (`as i32`)
             se[j] = ((const uint32_t *)pend->buffers[1])[pend->offset + j];
             sw[j] = pcov_fmt == 's' ? (int32_t)((const int16_t *)pcov->buffers[1])[pcov->offset + j] : ((const int32_t *)pcov->buffers[1])[pcov->offset + j];
-        }
-    }
-    if (has_len) {
-        key_len.assign(nk, 0);
-        for (int64_t i = 0; i < lname.a->length; i++) {
-            if (lname.null_at(i)) continue;
-            const uint32_t k = dict.id_of(lname.at(i));
-            const int64_t v = len64[(size_t)i];
-            key_len[k] = v < 0 ? 0u : (v > (int64_t)UINT32_MAX ? UINT32_MAX : (uint32_t)v);
         }
     }
     rpos = n_reads ? (const uint32_t *)start->buffers[1] + start->offset : nullptr;
@@ -928,6 +941,191 @@ extern "C" void brh_depth_per_base_close(brh_depth_stream *ds)
     if (!ds) return;
     if (ds->profile) ivx_depth_profile_free(ds->profile);
     delete ds;
+}
+
+// ---- streaming depth(): the reference's accumulate_partition (physical_exec.rs:269-329) as a push interface -- one depth
+// profile per pushed batch, kept on a stack that is merged like a binary counter, and merge_*_results (:367-463) at finish
+struct brh_depth_push {
+    brh_session *s = nullptr;
+    bool dense = false, finished = false;
+    uint32_t filter_flag = 0, min_mapq = 0;
+    std::vector<std::string> names;                     // key id -> contig: byte order (dense), arrival order (sparse)
+    std::unordered_map<std::string, uint32_t> ids;
+    std::vector<uint32_t> key_len;                      // dense only
+    std::vector<ivx_index *> stack;                     // profiles not yet merged, the oldest first
+    uint32_t nk() const { return (uint32_t)std::max<size_t>(names.size(), 1); }
+};
+
+namespace {
+
+int depth_push_check(brh_depth_push *dp)
+{
+    return dp->finished ? fail(dp->s, "depth stream: already finished") : 0;
+}
+
+// the two profiles on top of the stack -> their sum
+int depth_push_merge_top(brh_depth_push *dp)
+{
+    ivx_index *a = dp->stack[dp->stack.size() - 2], *b = dp->stack.back(), *m = nullptr;
+    const ivx_status st = ivx_depth_profile_merge(dp->s->ctx, a, b, &m);
+    if (st != IVX_OK) return fail_ivx(dp->s, st);
+    ivx_depth_profile_free(a); ivx_depth_profile_free(b);
+    dp->stack.pop_back();
+    dp->stack.back() = m;
+    return 0;
+}
+
+// everything pushed so far as ONE profile on the stack (an empty one when nothing was)
+int depth_push_merge_all(brh_depth_push *dp)
+{
+    while (dp->stack.size() > 1) if (depth_push_merge_top(dp)) return 1;
+    if (dp->stack.empty()) {
+        ivx_index *e = nullptr;
+        const ivx_status st = ivx_depth_profile_build(dp->s->ctx, IVX_MEM_HOST, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0,
+                                                      nullptr, nullptr, nullptr, nullptr, 0, dp->nk(), dp->dense ? dp->key_len.data() : nullptr,
+                                                      dp->filter_flag, dp->min_mapq, &e);
+        if (st != IVX_OK) return fail_ivx(dp->s, st);
+        dp->stack.push_back(e);
+    }
+    return 0;
+}
+
+}  // namespace
+
+// the rows [lo[k], lo[k + 1]) of every key k, the keys taken in byte order of their names: for each output row the input row it
+// comes from.  (Rows are grouped by key ascending, so a key's rows are contiguous.)  Not part of the C interface; it has external
+// linkage so that a stand-alone program can link it and check it on the CPU.
+void brh_depth_rows_in_name_order(const std::vector<std::string> &names, const uint32_t *key, uint64_t n, std::vector<uint64_t> *src)
+{
+    std::vector<uint64_t> lo(names.size() + 1, n);
+    for (uint64_t i = n; i-- > 0;) if (key[i] < names.size()) lo[key[i]] = i;
+    for (size_t k = names.size(); k-- > 0;) if (lo[k] > lo[k + 1]) lo[k] = lo[k + 1];       // a key without rows starts where the next one does
+    std::vector<uint32_t> order(names.size());
+    for (uint32_t k = 0; k < names.size(); k++) order[k] = k;
+    std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return names[a] < names[b]; });
+    src->clear(); src->reserve(n);
+    for (uint32_t k : order) for (uint64_t i = lo[k]; i < lo[k + 1]; i++) src->push_back(i);
+}
+
+extern "C" int brh_depth_push_open(brh_session *s, brh_batch lengths, uint32_t filter_flag, uint32_t min_mapq, brh_depth_push **out)
+{
+    if (!s) return 1;
+    if (!out) return fail(s, "depth stream: null out");
+    *out = nullptr;
+    std::unique_ptr<brh_depth_push> dp(new brh_depth_push());
+    dp->s = s; dp->filter_flag = filter_flag; dp->min_mapq = min_mapq;
+    dp->dense = lengths.array != nullptr;
+    if (dp->dense) {
+        NameDict dict;
+        if (load_lengths(s, lengths, &dict, &dp->key_len)) return 1;
+        dp->names = dict.names;
+        for (uint32_t i = 0; i < dp->names.size(); i++) dp->ids.emplace(dp->names[i], i);
+    }
+    *out = dp.release();
+    return 0;
+}
+
+extern "C" int brh_depth_push_batch(brh_depth_push *dp, brh_batch reads)
+{
+    if (!dp) return 1;
+    brh_session *s = dp->s;
+    if (depth_push_check(dp)) return 1;
+    if (reads.array && reads.schema && reads.array->length == 0) return 0;             // physical_exec.rs:282-284
+    DepthInputs in;
+    if (in.load(s, reads, brh_batch{nullptr, nullptr}, brh_batch{nullptr, nullptr})) return 1;
+    // the batch's own ids (byte order of ITS names) -> the stream's
+    std::vector<uint32_t> to_stream(in.dict.names.size());
+    for (size_t i = 0; i < to_stream.size(); i++) {
+        auto it = dp->ids.find(in.dict.names[i]);
+        if (it != dp->ids.end()) to_stream[i] = it->second;
+        else if (dp->dense) to_stream[i] = IVX_NULL_IDX;                                 // events.rs:247-260
+        else {
+            to_stream[i] = (uint32_t)dp->names.size();
+            dp->ids.emplace(in.dict.names[i], to_stream[i]);
+            dp->names.push_back(in.dict.names[i]);
+        }
+    }
+    for (uint32_t &k : in.rkey) if (k != IVX_NULL_IDX) k = to_stream[k];
+    ivx_index *p = nullptr;
+    const ivx_status st = ivx_depth_profile_build(s->ctx, IVX_MEM_HOST, in.rkey.data(), in.rpos, in.rflags, in.rmapq, in.coff, in.cops, in.n_reads,
+                                                  nullptr, nullptr, nullptr, nullptr, 0, dp->nk(), dp->dense ? dp->key_len.data() : nullptr,
+                                                  dp->filter_flag, dp->min_mapq, &p);
+    if (st != IVX_OK) return fail_ivx(s, st);
+    dp->stack.push_back(p);
+    // a binary counter: merge while the new top has at least half the steps of the profile below it
+    while (dp->stack.size() > 1 &&
+           2 * ivx_depth_profile_steps(dp->stack.back()) >= ivx_depth_profile_steps(dp->stack[dp->stack.size() - 2]))
+        if (depth_push_merge_top(dp)) return 1;
+    return 0;
+}
+
+extern "C" int brh_depth_push_finish(brh_depth_push *dp,
+                                     ArrowArray *contig, ArrowSchema *contig_schema, ArrowArray *pos_start, ArrowSchema *pos_start_schema,
+                                     ArrowArray *pos_end, ArrowSchema *pos_end_schema, ArrowArray *coverage, ArrowSchema *coverage_schema)
+{
+    if (!dp) return 1;
+    brh_session *s = dp->s;
+    if (depth_push_check(dp) || depth_push_merge_all(dp)) return 1;
+    const ivx_index *p = dp->stack[0];
+    uint64_t m = 0, m2 = 0;
+    ivx_status st = ivx_depth_profile_blocks(s->ctx, p, IVX_MEM_HOST, nullptr, nullptr, nullptr, nullptr, 0, &m);
+    if (st != IVX_OK) return fail_ivx(s, st);
+    std::vector<uint32_t> ok(m ? m : 1), os(m ? m : 1), oe(m ? m : 1); std::vector<int32_t> oc(m ? m : 1);
+    if (m) {
+        st = ivx_depth_profile_blocks(s->ctx, p, IVX_MEM_HOST, ok.data(), os.data(), oe.data(), oc.data(), m, &m2);
+        if (st != IVX_OK) return fail_ivx(s, st);
+    }
+    ivx_depth_profile_free(dp->stack[0]);
+    dp->stack.clear();
+    dp->finished = true;
+    // ---- sparse: the stream's ids are in arrival order, the output is in byte order of the names (coverage.rs:75-76)
+    std::vector<uint64_t> src;
+    if (!dp->dense) brh_depth_rows_in_name_order(dp->names, ok.data(), m2, &src);
+    // ---- schema.rs:28-41: contig Utf8, pos_start / pos_end Int32 (`as i32`), coverage Int16 (`as i16`)
+    std::vector<uint32_t> oid(m2 ? m2 : 1);
+    std::vector<int32_t> o32s(m2 ? m2 : 1), o32e(m2 ? m2 : 1); std::vector<int16_t> o16(m2 ? m2 : 1);
+    for (uint64_t i = 0; i < m2; i++) {
+        const uint64_t j = dp->dense ? i : src[i];
+        oid[i] = ok[j]; o32s[i] = (int32_t)os[j]; o32e[i] = (int32_t)oe[j]; o16[i] = (int16_t)oc[j];
+    }
+    make_utf8(contig, dp->names, oid.data(), (int64_t)m2); make_schema(contig_schema, "u", "contig", true);
+    make_primitive<int32_t>(pos_start, o32s.data(), (int64_t)m2, nullptr); make_schema(pos_start_schema, "i", "pos_start", false);
+    make_primitive<int32_t>(pos_end, o32e.data(), (int64_t)m2, nullptr); make_schema(pos_end_schema, "i", "pos_end", false);
+    make_primitive<int16_t>(coverage, o16.data(), (int64_t)m2, nullptr); make_schema(coverage_schema, "s", "coverage", false);
+    return 0;
+}
+
+extern "C" int brh_depth_push_finish_per_base(brh_depth_push *dp, int zero_based, brh_depth_stream **out)
+{
+    if (!dp) return 1;
+    brh_session *s = dp->s;
+    if (!out) return fail(s, "depth stream: null out");
+    *out = nullptr;
+    if (depth_push_check(dp)) return 1;
+    if (!dp->dense)                         // physical_exec.rs:299-303
+        return fail(s, "per_base mode requires dense accumulation (BAM header with contig lengths). "
+                       "Sparse fallback (e.g. MemTable) is not supported for per_base output.");
+    if (depth_push_merge_all(dp)) return 1;
+    std::unique_ptr<brh_depth_stream> ds(new brh_depth_stream());
+    ds->s = s; ds->zero_based = zero_based != 0;
+    ds->names = dp->names; ds->key_len = dp->key_len;
+    ds->seen.assign(dp->nk(), 0);
+    uint64_t steps = 0;
+    const ivx_status st = ivx_depth_profile_read(s->ctx, dp->stack[0], IVX_MEM_HOST, nullptr, nullptr, nullptr, ds->seen.data(), 0, &steps);
+    if (st != IVX_OK) return fail_ivx(s, st);
+    if (ds->names.empty()) ds->seen.assign(ds->seen.size(), 0);     // (an empty length table: key 0 stands for no contig)
+    ds->profile = dp->stack[0];                                     // the profile moves into the pull stream
+    dp->stack.clear();
+    dp->finished = true;
+    *out = ds.release();
+    return 0;
+}
+
+extern "C" void brh_depth_push_close(brh_depth_push *dp)
+{
+    if (!dp) return;
+    for (ivx_index *p : dp->stack) ivx_depth_profile_free(p);
+    delete dp;
 }
 
 // ---- f3: payload gather

@@ -30,11 +30,13 @@ SYMBOLS = [
     "ivx_ctx_reserved_bytes", "ivx_ctx_set_build_overlap", "ivx_index_layout",
     "ivx_probe_mark_build", "ivx_bits_mark", "ivx_bits_select", "ivx_depth",
     "ivx_depth_profile_build", "ivx_depth_profile_free", "ivx_depth_profile_steps", "ivx_depth_profile_device_bytes",
-    "ivx_depth_profile_read", "ivx_depth_profile_expand",
+    "ivx_depth_profile_read", "ivx_depth_profile_expand", "ivx_depth_profile_merge", "ivx_depth_profile_blocks",
 ]
 
 # outputs one workgroup of the expand kernel makes (csrc/ivx_depth_expand.hip DEPTH_EXPAND_TILE; tests/test_depth_per_base_tile.py)
 DEPTH_EXPAND_TILE = 4096
+# merged steps one workgroup of the merge kernel makes (csrc/ivx_depth_merge.hip DEPTH_MERGE_TILE; tests/test_depth_merge_cpu.py)
+DEPTH_MERGE_TILE = 2048
 
 # slots of ivx_index_layout (include/ivx.h IVX_LAYOUT_*), in order
 LAYOUT_SLOTS = ["kind", "sh0", "nlev", "levrows", "rcells", "rcs", "nreg", "pk24", "slow", "fg", "fbits", "nroute_nreg", "lbuild"]
@@ -99,6 +101,10 @@ def lib():
         L.ivx_depth_profile_read.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_uint64, C.POINTER(C.c_uint64)]
         L.ivx_depth_profile_expand.restype = C.c_int
         L.ivx_depth_profile_expand.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p]
+        L.ivx_depth_profile_merge.restype = C.c_int
+        L.ivx_depth_profile_merge.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
+        L.ivx_depth_profile_blocks.restype = C.c_int
+        L.ivx_depth_profile_blocks.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_uint64, C.POINTER(C.c_uint64)]
         _lib = L
     return _lib
 
@@ -222,6 +228,36 @@ class DepthProfile:
         ctx._chk(lib().ivx_depth_profile_expand(ctx.h, self.h, mem, int(key), int(first_pos), int(n), int(bool(skip_pos0)),
                                                 _ptr(out_pos), _ptr(out_cov)))
         return out_pos, out_cov
+
+    def merge(self, other, ctx=None):
+        """self + other -> a new DepthProfile: the profile of the union of the inputs that made the two (both stay valid;
+        other may be self).  Built by, and reserved against, ctx (default: the context that built self)."""
+        ctx = ctx or self.ctx
+        h = C.c_void_p()
+        ctx._chk(lib().ivx_depth_profile_merge(ctx.h, self.h, other.h if other is not None else None, C.byref(h)))
+        return DepthProfile(ctx, h, max(self.n_keys, other.n_keys), self.device or other.device)
+
+    def blocks(self, device=False, ctx=None, cap=None, outputs=(True, True, True, True)):
+        """the coverage blocks of the profile, what Ctx.depth() gives for the inputs that made it -> (key, start, end,
+        coverage), None where not asked for; numpy arrays, or torch tensors with device=True (the unsigned columns as
+        their int32 bits).  cap=None: a sizing call, then the fill call."""
+        ctx = ctx or self.ctx
+        mem = MEM_DEVICE if device else MEM_HOST
+        if cap is None:
+            m = C.c_uint64(0)
+            ctx._chk(lib().ivx_depth_profile_blocks(ctx.h, self.h, mem, None, None, None, None, 0, C.byref(m)))
+            cap = max(m.value, 1)
+        if device:
+            import torch
+            out = [torch.empty(cap, dtype=torch.int32, device=self.device or "cuda:0") if w else None for w in outputs]
+        else:
+            out = [np.empty(cap, dt) if w else None for w, dt in zip(outputs, (np.uint32, np.uint32, np.uint32, np.int32))]
+        m2 = C.c_uint64(0)
+        st = lib().ivx_depth_profile_blocks(ctx.h, self.h, mem, *[_ptr(o) for o in out], cap, C.byref(m2))
+        if st == ERR_CAPACITY:
+            raise IvxError(st, f"{lib().ivx_last_error(ctx.h).decode()} (needed {m2.value})")
+        ctx._chk(st)
+        return tuple(None if o is None else o[:m2.value] for o in out)
 
     def free(self):
         if self.h:

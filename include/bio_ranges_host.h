@@ -179,6 +179,38 @@ int  brh_depth_per_base_next(brh_depth_stream *ds, uint64_t max_rows, int *done,
                              struct ArrowArray *coverage, struct ArrowSchema *coverage_schema);
 void brh_depth_per_base_close(brh_depth_stream *ds);
 
+/* Streaming depth(): the shape the reference runs depth() in -- accumulate_partition drains a STREAM of read batches into one
+ * accumulator (bio-function-pileup physical_exec.rs:269-329), merge_dense_results / merge_sparse_results add the partitions'
+ * accumulators together (:367-463), and only then is anything emitted.  The accumulator here is a depth profile on the device
+ * (ivx.h g'): exact int32 coverage, the open block of a clipped contig and key_seen included, none of which the `prior`
+ * round trip of brh_depth can carry.
+ * open: lengths (array == NULL: the sparse mode) as for brh_depth.  With it the contig dictionary is the table's names in byte
+ *   order, fixed for the stream; reads elsewhere are skipped.  Without it the dictionary grows in arrival order: a new name gets
+ *   the next id, and a batch's profile is built with as many keys as the dictionary has by then.
+ * push: the column rules and errors of brh_depth's reads batch (a batch that fails them changes nothing: the stream goes on).
+ *   One ivx_depth_profile_build per batch; the profile goes onto a stack that is merged like a binary counter -- while the new
+ *   top has at least half the steps of the profile below it, the two are merged (ivx_depth_profile_merge) and freed -- so about
+ *   log2(batches) profiles are alive and the merge work is O(n log n) instead of one merge of everything per batch.  A batch
+ *   of 0 rows is a no-op (:282-284).  Coalescing 8192-row batches into large ones before they are pushed remains the caller's
+ *   job (CoalesceBatchesExec), as for the join stream: a device call per small batch is all launch latency.
+ * finish: merges the stack down to one profile and returns its blocks (ivx_depth_profile_blocks) as brh_depth does: contig
+ *   Utf8, pos_start / pos_end Int32, coverage Int16 (`as i16`), contigs in byte order of their names -- in the sparse mode a
+ *   per-contig copy on the host.  A stream that never received a row gives four empty arrays.
+ * finish_per_base: without lengths the error is the reference's (see brh_depth_per_base_open).  Otherwise the merged profile
+ *   MOVES into a brh_depth_stream, which brh_depth_per_base_next / _close then serve as ever.
+ * After either finish the push object holds no profile, and push / finish* fail with "depth stream: already finished"; close is
+ *   still required and frees whatever is left.  The stream must not outlive its session. */
+typedef struct brh_depth_push brh_depth_push;
+int  brh_depth_push_open(brh_session *s, brh_batch lengths, uint32_t filter_flag, uint32_t min_mapq, brh_depth_push **out);
+int  brh_depth_push_batch(brh_depth_push *dp, brh_batch reads);
+int  brh_depth_push_finish(brh_depth_push *dp,
+                           struct ArrowArray *contig, struct ArrowSchema *contig_schema,
+                           struct ArrowArray *pos_start, struct ArrowSchema *pos_start_schema,
+                           struct ArrowArray *pos_end, struct ArrowSchema *pos_end_schema,
+                           struct ArrowArray *coverage, struct ArrowSchema *coverage_schema);
+int  brh_depth_push_finish_per_base(brh_depth_push *dp, int zero_based, brh_depth_stream **out);
+void brh_depth_push_close(brh_depth_push *dp);
+
 /* compute::take of ONE payload column with an index array a join / nearest call returned
  * (interval_join.rs:1655-1667, nearest.rs:469-482), on the device.  column: any fixed-width primitive
  * (ints, floats, date/time/timestamp/duration, decimal128/256, fixed-size binary of 1/2/4/8/16/32 bytes),
@@ -251,6 +283,8 @@ int brh_session_set_strict_null_contigs(brh_session *s, int on);
  * ivx_ctx_set_memory_limit. */
 int brh_session_metrics(brh_session *s, ivx_metrics *out);
 int brh_session_set_memory_limit(brh_session *s, uint64_t bytes);
+/* device bytes the session holds reserved right now: scratch plus live indexes and depth profiles (ivx_ctx_reserved_bytes) */
+int brh_session_reserved_bytes(brh_session *s, uint64_t *out);
 
 #ifdef __cplusplus
 }

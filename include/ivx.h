@@ -397,6 +397,32 @@ ivx_status ivx_depth_profile_expand(ivx_ctx *ctx, const ivx_index *profile, int 
                                     uint32_t key, uint32_t first_pos, uint64_t n, int skip_pos0,
                                     int32_t *out_pos /* nullable */, void *out_cov /* int16_t[n], nullable */);
 
+/*      STREAMING depth(): the reference drains a stream of read batches into one accumulator per partition and adds the
+ *      partitions' accumulators together before anything is emitted (physical_exec.rs:269-329 accumulate_partition,
+ *      :367-463 merge_dense_results / merge_sparse_results).  A profile is that accumulator: coverage is additive, so
+ *      out = a + b is the profile of the union of the inputs that made a and b, by a merge of the two sorted step lists.
+ *      MERGE.  Let w = key << 32 | pos.  The merged positions are the union of both lists' w; for a merged w of key k,
+ *      c(w) = CA(w) + CB(w) with int32 wrap-around, CX(w) = the c of X's last step with the same key and a position <= pos
+ *      (0 if there is none), and prev(w) = the same sum over the steps at positions < pos; w is a step of the result iff
+ *      c(w) != prev(w).  A position present in both lists appears once.  n_keys of the result = the larger of the two (the
+ *      profile with fewer keys has no steps for the higher ones), key_seen = a.key_seen | b.key_seen with missing keys
+ *      counting as 0, and the first step of every key is found again.  a == b is allowed: the inputs are only read, stay
+ *      valid and stay the caller's to free.  The result is a normal profile, reserved against ctx's memory limit until it
+ *      is freed; a merge that would go over the limit returns IVX_ERR_OOM, keeps nothing allocated and leaves
+ *      ivx_ctx_reserved_bytes as it was.  Errors: a null profile or one on another device is IVX_ERR_INVALID, any other
+ *      index IVX_ERR_UNSUPPORTED; steps(a) + steps(b) >= 0xFFFFFF00 is IVX_ERR_INVALID (the merged index space is 32-bit,
+ *      like the expand kernel's search).  Drops the state a sizing call left on the context, synchronises before it returns
+ *      (it needs the step count anyway) and adds the result's bytes to build_mem_used. */
+ivx_status ivx_depth_profile_merge(ivx_ctx *ctx, const ivx_index *a, const ivx_index *b, ivx_index **out);
+/*      The coverage blocks of a profile: what ivx_depth returns for the inputs that made it.  Step i gives the block
+ *      (key_i, p_i, p_(i+1) - 1, c_i) iff c_i != 0 and step i + 1 exists and has the same key (coverage.rs:38-62 restated on
+ *      steps: a key's last step never gives a block).  Output is ordered by (key, start).  The capacity protocol of
+ *      ivx_depth: cap = 0 with NULL outputs only counts; cap < *n_out is IVX_ERR_CAPACITY with *n_out = the size needed and
+ *      nothing written; any output may be NULL on its own.  IVX_MEM_DEVICE calls may return with kernels in flight. */
+ivx_status ivx_depth_profile_blocks(ivx_ctx *ctx, const ivx_index *profile, int mem,
+                                    uint32_t *out_key, uint32_t *out_start, uint32_t *out_end, int32_t *out_cov,
+                                    uint64_t cap, uint64_t *n_out);
+
 /* ---- f3: `compute::take` of payload columns with the index arrays the probes return
  *      (interval_join.rs:1655-1667, nearest.rs:469-482).  idx[i] == IVX_NULL_IDX or a null source
  *      slot (src_valid_bits: Arrow validity bitmap of the source, bit offset 0, nullable) gives

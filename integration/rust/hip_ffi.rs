@@ -107,6 +107,10 @@ extern "C" {
                                   out_cov: *mut i32, key_seen: *mut u8, cap: u64, n_out: *mut u64) -> i32;
     pub fn ivx_depth_profile_expand(ctx: *mut IvxCtx, profile: *const IvxIndex, mem: i32, key: u32, first_pos: u32, n: u64,
                                     skip_pos0: i32, out_pos: *mut i32, out_cov: *mut c_void) -> i32;
+    // streaming depth(): out = a + b (accumulate_partition / merge_*_results), and the coverage blocks of a profile
+    pub fn ivx_depth_profile_merge(ctx: *mut IvxCtx, a: *const IvxIndex, b: *const IvxIndex, out: *mut *mut IvxIndex) -> i32;
+    pub fn ivx_depth_profile_blocks(ctx: *mut IvxCtx, profile: *const IvxIndex, mem: i32, out_key: *mut u32, out_start: *mut u32,
+                                    out_end: *mut u32, out_cov: *mut i32, cap: u64, n_out: *mut u64) -> i32;
     pub fn ivx_take_fixed(ctx: *mut IvxCtx, mem: i32, src: *const c_void, width: u32, n_src: u64, src_valid_bits: *const u8,
                           idx: *const u32, n: u64, out: *mut c_void, out_valid: *mut u8) -> i32;
     pub fn ivx_scatter_fixed(ctx: *mut IvxCtx, mem: i32, src: *const c_void, width: u32, idx: *const u32, n: u64,

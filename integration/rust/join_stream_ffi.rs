@@ -16,6 +16,7 @@ use datafusion::common::{DataFusionError, Result};
 #[repr(C)] pub struct BrhSession { _p: [u8; 0] }
 #[repr(C)] pub struct BrhJoinStream { _p: [u8; 0] }
 #[repr(C)] pub struct BrhDepthStream { _p: [u8; 0] }
+#[repr(C)] pub struct BrhDepthPush { _p: [u8; 0] }
 #[repr(C)] pub struct BrhBatch { pub array: *const FFI_ArrowArray, pub schema: *const FFI_ArrowSchema }
 #[repr(C)] pub struct BrhColumns { pub keys: *const *const c_char, pub n_keys: c_int, pub start: *const c_char, pub end: *const c_char }
 
@@ -55,6 +56,17 @@ extern "C" {
                                    pos: *mut FFI_ArrowArray, pos_schema: *mut FFI_ArrowSchema,
                                    coverage: *mut FFI_ArrowArray, coverage_schema: *mut FFI_ArrowSchema) -> c_int;
     pub fn brh_depth_per_base_close(ds: *mut BrhDepthStream);
+    // depth() over a stream of read batches: accumulate_partition as a push interface; finish = merge_*_results + the blocks,
+    // finish_per_base hands the merged profile to the pull stream above
+    pub fn brh_depth_push_open(s: *mut BrhSession, lengths: BrhBatch, filter_flag: u32, min_mapq: u32, out: *mut *mut BrhDepthPush) -> c_int;
+    pub fn brh_depth_push_batch(dp: *mut BrhDepthPush, reads: BrhBatch) -> c_int;
+    pub fn brh_depth_push_finish(dp: *mut BrhDepthPush,
+                                 contig: *mut FFI_ArrowArray, contig_schema: *mut FFI_ArrowSchema,
+                                 pos_start: *mut FFI_ArrowArray, pos_start_schema: *mut FFI_ArrowSchema,
+                                 pos_end: *mut FFI_ArrowArray, pos_end_schema: *mut FFI_ArrowSchema,
+                                 coverage: *mut FFI_ArrowArray, coverage_schema: *mut FFI_ArrowSchema) -> c_int;
+    pub fn brh_depth_push_finish_per_base(dp: *mut BrhDepthPush, zero_based: c_int, out: *mut *mut BrhDepthStream) -> c_int;
+    pub fn brh_depth_push_close(dp: *mut BrhDepthPush);
 }
 
 /// What `IntervalJoinStream` keeps per partition when `Algorithm::Hip` is selected.
