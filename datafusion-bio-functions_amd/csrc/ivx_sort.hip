@@ -16,6 +16,7 @@
 // are skipped (one OR-reduction up front).
 #include "ivx_device.hpp"
 #include "ivx_sort.hpp"
+#include <cstdlib>
 
 namespace {
 
@@ -28,7 +29,7 @@ constexpr int RS_HWAVES = RS_HT / IVX_WAVE;
 constexpr u64 RS_CHUNK = 65536;                 // records per workgroup of a big sort (histogram and scatter agree on it; sort_impl
                                                 // takes fewer for inputs that would not fill the chip: whole tiles, at least one)
 template <int NW> struct Tile {
-    static constexpr int I = NW == 3 ? 4 : NW == 1 ? 8 : 8;   // records per thread per tile: 8192-record tiles, 4096 for 24-byte records, 16384 for 8-byte ones (LDS)
+    static constexpr int I = NW == 3 ? 4 : 8;   // records per thread per tile: 8192-record tiles, 4096 for 24-byte records (LDS)
     static constexpr int N = RS_T * I;
     static constexpr int WT = N / RS_WAVES;     // consecutive records per wavefront
 };
@@ -275,11 +276,15 @@ __global__ __launch_bounds__(RS_T) void k_scatter(CPtrs<NW> in, Ptrs<NW> out, u6
 
 // records per workgroup: RS_CHUNK for big inputs; smaller ones are spread over ~4 workgroups per CU's worth of chunks
 // (whole tiles), or a 1 M-row sort would run on 16 of the 256 CUs
+// (tests: IVX_SORT_CHUNK_TILES=k, k in 1..8, makes it k tiles whatever n is, so that a small sort walks several tiles per
+//  workgroup; read here, so that ivx_sort_geometry1 and with it the sweeps' k_pack1h stay in step with the sort)
 template <int NW>
 u64 sort_chunk(u64 n)
 {
     u64 chunk = RS_CHUNK;
     const u64 tile = (u64)Tile<NW>::N;
+    if (const char *e = getenv("IVX_SORT_CHUNK_TILES"))
+        if (e[0] >= '1' && e[0] <= '8' && e[1] == 0) return (u64)(e[0] - '0') * tile;
     const u64 want = (n + 1023) / 1024;                                // ~1024 chunks
     const u64 c = (want + tile - 1) / tile * tile;
     if (c < chunk) chunk = c < tile ? tile : c;
@@ -356,48 +361,53 @@ ivx_status ivx_radix_sort(ivx_ctx *ctx, int nw, u64 *const *a, u64 *const *b, u6
     }
 }
 
-// test hook (not part of include/ivx.h): sort (w0[,w1]) device or host arrays by the given fields
-extern "C" ivx_status ivx_debug_sort(ivx_ctx *ctx, int nw, u64 *w0, u64 *w1, u64 *w2, u64 n,
-                                     const int *field_words, const int *field_lo, const int *field_hi, int nfields)
+// test hook (not part of include/ivx.h): sort host arrays (w0[,w1[,w2]]) by the given fields, `tight` as the library passes it; pay
+// (nullable, nw == 1): a 32-bit payload per record.  geom (nullable) receives the records per workgroup and the workgroups
+// that were in force, and in_b.
+extern "C" ivx_status ivx_debug_sort_geom(ivx_ctx *ctx, int nw, u64 *w0, u64 *w1, u64 *w2, u32 *pay, u64 n,
+                                          const int *field_words, const int *field_lo, const int *field_hi, int nfields, int tight, u64 *geom)
 {
-    if (!ctx || nw < 1 || nw > 3 || nfields > 8) return IVX_ERR_INVALID;
+    if (!ctx || nw < 1 || nw > 3 || nfields < 0 || nfields > 8) return IVX_ERR_INVALID;
     IVX_HIP(ctx, hipSetDevice(ctx->device));
     u64 *host[3] = {w0, w1, w2};
-    u64 *a[3], *b[3];
+    u64 *a[3], *b[3]; u32 *p[2] = {nullptr, nullptr};
     for (int q = 0; q < nw; q++) {
         IVX_TRY(ctx->get_scratch(WS_SA0 + q, n * sizeof(u64), (void **)&a[q]));
         IVX_TRY(ctx->get_scratch(WS_SB0 + q, n * sizeof(u64), (void **)&b[q]));
         IVX_HIP(ctx, hipMemcpyAsync(a[q], host[q], n * sizeof(u64), hipMemcpyHostToDevice, ctx->stream));
     }
+    if (pay) {
+        if (nw != 1) return ctx->fail(IVX_ERR_INVALID, "sort: a 32-bit payload goes with one-word records");
+        IVX_TRY(ctx->get_scratch(WS_SA1, n * sizeof(u32), (void **)&p[0]));
+        IVX_TRY(ctx->get_scratch(WS_SB1, n * sizeof(u32), (void **)&p[1]));
+        IVX_HIP(ctx, hipMemcpyAsync(p[0], pay, n * sizeof(u32), hipMemcpyHostToDevice, ctx->stream));
+    }
     ivx_sort_field f[8];
     for (int i = 0; i < nfields; i++) { f[i].word = field_words[i]; f[i].lo = field_lo[i]; f[i].hi = field_hi[i]; }
     int in_b = 0;
-    IVX_TRY(ivx_radix_sort(ctx, nw, a, b, n, f, nfields, &in_b));
+    IVX_TRY(ivx_radix_sort(ctx, nw, a, b, n, f, nfields, &in_b, tight != 0, pay ? p : nullptr));
     for (int q = 0; q < nw; q++)
         IVX_HIP(ctx, hipMemcpyAsync(host[q], in_b ? b[q] : a[q], n * sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
+    if (pay) IVX_HIP(ctx, hipMemcpyAsync(pay, p[in_b], n * sizeof(u32), hipMemcpyDeviceToHost, ctx->stream));
     IVX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (geom) {
+        const u64 chunk = nw == 1 ? sort_chunk<1>(n) : nw == 2 ? sort_chunk<2>(n) : sort_chunk<3>(n);      // as sort_impl
+        geom[0] = chunk; geom[1] = (n + chunk - 1) / chunk; geom[2] = (u64)in_b;
+    }
     return IVX_OK;
+}
+
+// test hook: sort (w0[,w1[,w2]]) by the given fields
+extern "C" ivx_status ivx_debug_sort(ivx_ctx *ctx, int nw, u64 *w0, u64 *w1, u64 *w2, u64 n,
+                                     const int *field_words, const int *field_lo, const int *field_hi, int nfields)
+{
+    return ivx_debug_sort_geom(ctx, nw, w0, w1, w2, nullptr, n, field_words, field_lo, field_hi, nfields, 0, nullptr);
 }
 
 // test hook: one-word records with a 32-bit payload (pay may be NULL), fields at any bit position, `tight` as the library passes it
 extern "C" ivx_status ivx_debug_sort_pay(ivx_ctx *ctx, u64 *w0, u32 *pay, u64 n, int lo, int hi, int tight)
 {
-    if (!ctx || !w0) return IVX_ERR_INVALID;
-    IVX_HIP(ctx, hipSetDevice(ctx->device));
-    u64 *a[1], *b[1]; u32 *p[2] = {nullptr, nullptr};
-    IVX_TRY(ctx->get_scratch(WS_SA0, n * sizeof(u64), (void **)&a[0]));
-    IVX_TRY(ctx->get_scratch(WS_SB0, n * sizeof(u64), (void **)&b[0]));
-    IVX_HIP(ctx, hipMemcpyAsync(a[0], w0, n * sizeof(u64), hipMemcpyHostToDevice, ctx->stream));
-    if (pay) {
-        IVX_TRY(ctx->get_scratch(WS_SA1, n * sizeof(u32), (void **)&p[0]));
-        IVX_TRY(ctx->get_scratch(WS_SB1, n * sizeof(u32), (void **)&p[1]));
-        IVX_HIP(ctx, hipMemcpyAsync(p[0], pay, n * sizeof(u32), hipMemcpyHostToDevice, ctx->stream));
-    }
-    const ivx_sort_field f[1] = {{0, lo, hi}};
-    int in_b = 0;
-    IVX_TRY(ivx_radix_sort(ctx, 1, a, b, n, f, 1, &in_b, tight != 0, pay ? p : nullptr));
-    IVX_HIP(ctx, hipMemcpyAsync(w0, in_b ? b[0] : a[0], n * sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
-    if (pay) IVX_HIP(ctx, hipMemcpyAsync(pay, p[in_b], n * sizeof(u32), hipMemcpyDeviceToHost, ctx->stream));
-    IVX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return IVX_OK;
+    if (!w0) return IVX_ERR_INVALID;
+    const int word = 0;
+    return ivx_debug_sort_geom(ctx, 1, w0, nullptr, nullptr, pay, n, &word, &lo, &hi, 1, tight, nullptr);
 }

@@ -2,8 +2,11 @@
 #pragma once
 #include "ivx_internal.hpp"
 
-// sort by bits [lo,hi) of word `word`; lo and hi byte aligned.  Fields are given
+// sort by bits [lo,hi) of word `word`, at any bit position (hi == lo: no criterion).  Fields are given
 // from the LEAST significant sort criterion to the most significant one.
+// A field is sorted in 8-bit digits [sh, sh + 8), sh = lo, lo + 8, ..., and its last pass reads the whole digit:
+// where hi - lo is no multiple of 8, the bits between hi and that digit's end (below bit 64) must be constant over
+// the input, or belong to the next more significant field (whose passes then put them in order anyway).
 struct ivx_sort_field { int word, lo, hi; };
 
 // a[0..nw) hold the input arrays, b[0..nw) same-sized scratch; *in_b tells where
