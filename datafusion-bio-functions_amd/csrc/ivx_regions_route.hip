@@ -422,11 +422,73 @@ __device__ __forceinline__ void load4nt(const u32 *__restrict__ pkey, const i32 
     }
 }
 
+// CH rows of a thread (CH / 4 quads; quad q of a tile = rows (q * T + tid) * 4 .. + 3 from t0) into registers.  `whole`
+// (wave-uniform): the quads lie inside the workgroup's rows and the columns are 16-byte aligned -- 16-byte loads streamed
+// past the caches' keep-lists; otherwise element by element, checked against hi
+template <int CH, int T>
+__device__ __forceinline__ void part_load_rows(const u32 *__restrict__ pkey, const i32 *__restrict__ ps, const i32 *__restrict__ pe,
+                                               u64 t0, int quad0, u64 hi, bool whole, u32 (&kk)[CH], i32 (&qs)[CH], i32 (&qe)[CH])
+{
+    const u32 tid = threadIdx.x;
+    if (whole) {
+        typedef u32 __attribute__((ext_vector_type(4))) v4u;
+        typedef i32 __attribute__((ext_vector_type(4))) v4i;
+        // a wave-uniform 64-bit base and the thread's 32-bit offset: one address register for all of a thread's loads.  The
+        // offset is made opaque here, or column + offset is kept as three 64-bit per-thread pointers across the whole tile
+        // loop (six registers that the rows loaded ahead need)
+        u32 o = tid * 4u;
+        asm volatile("" : "+v"(o));
+#pragma unroll
+        for (int v = 0; v < CH / 4; v++) {
+            const u64 q = t0 + (u64)(quad0 + v) * T * 4;
+            const v4u kv = pkey ? __builtin_nontemporal_load(reinterpret_cast<const v4u *>(pkey + q + o)) : v4u{0u, 0u, 0u, 0u};
+            const v4i sv = __builtin_nontemporal_load(reinterpret_cast<const v4i *>(ps + q + o));
+            const v4i ev = __builtin_nontemporal_load(reinterpret_cast<const v4i *>(pe + q + o));
+            kk[v * 4] = kv.x; kk[v * 4 + 1] = kv.y; kk[v * 4 + 2] = kv.z; kk[v * 4 + 3] = kv.w;
+            qs[v * 4] = sv.x; qs[v * 4 + 1] = sv.y; qs[v * 4 + 2] = sv.z; qs[v * 4 + 3] = sv.w;
+            qe[v * 4] = ev.x; qe[v * 4 + 1] = ev.y; qe[v * 4 + 2] = ev.z; qe[v * 4 + 3] = ev.w;
+        }
+    } else {
+#pragma unroll
+        for (int v = 0; v < CH / 4; v++) {
+            u32 k4[4]; i32 s4[4], e4[4];
+            load4nt<false>(pkey, ps, pe, t0 + ((u64)(quad0 + v) * T + tid) * 4, hi, k4, s4, e4);
+#pragma unroll
+            for (int j = 0; j < 4; j++) { kk[v * 4 + j] = k4[j]; qs[v * 4 + j] = s4[j]; qe[v * 4 + j] = e4[j]; }
+        }
+    }
+}
+
+// Whether an instantiation of k_part_onepass loads its rows one stage AHEAD of their use (see there).  The rows loaded
+// ahead occupy a chunk's raw columns (3 * CH registers) through the rest of the tile, and the kernel is held to 128
+// registers (two workgroups per CU).  With aligned columns (VEC) that fits without scratch where a chunk is eight rows and the
+// bitmap is not in use: the 16-row packed tiles without filter (the join's usual form) and all the 8-row tiles (1024
+// digits).  The 12-row tiles (one chunk of twelve) and the filtered 16-row tiles would spill three to four times what they
+// spill already: they keep loading each chunk at its top.  (profiles/route_prefetch_ab.txt has the resource table.)
+template <bool VEC, int I, bool FILT>
+constexpr bool part_loads_ahead() { return !(VEC && (I == 12 || (I == 16 && FILT))); }
+
 // ND digits (256 / 1024), T threads, I rows per thread and tile (tile = T * I rows <= one page).  Packed rows need no
 // slot array in LDS: two 512-thread workgroups with 8192-row tiles then share a CU, and one's loads overlap the other's
 // LDS phases (the kernel is bound by those phases, not by HBM: 8-byte instead of 12-byte rows alone changed nothing)
 // PK: a routed row is ONE 8-byte word, (start inside its region | length) and the row id (route_prep), instead of
 // (start, end) in one array and the row id in another: a third fewer bytes written here and read by the probe
+//
+// A workgroup walks chunk / TILE consecutive tiles.  Per tile: load the rows (a chunk of CH per thread at a time), route
+// them (route_prep), count them per region in LDS, barrier, reserve the runs (rcur) and scan the counts, barrier, re-order
+// the rows in LDS by region while the reservations return, take / look up the pages, barrier, write the runs out,
+// barrier.  At four wavefronts per SIMD the latency of the row loads is not covered by other wavefronts, so the loads run
+// one stage ahead of their use (AHEAD, part_loads_ahead): a chunk's raw columns are dead once it is routed, and the next
+// chunk's -- or the next tile's first chunk's -- are loaded into the same registers right then:
+//     tile k:   [load c0]* route c0 | LOAD c1 | count c0 | route c1 | LOAD c0 of tile k + 1 | count c1 | barrier | reserve,
+//               scan | re-order | pages | write-out | barrier
+//     tile k+1: dstart cleared, barrier | route c0 (no load) | LOAD c1 | ...
+// (* only a workgroup's first tile, a partial tile and unaligned columns load here.)  What is in flight when: chunk 1's loads
+// during chunk 0's LDS counting; the next tile's during chunk 1's counting, the barrier and the scan -- they have landed
+// by the time the reservation's return value is waited for, which is before the write-out.  A tile's stores, the closing
+// barrier and the next tile's dstart barrier no longer stand between a tile and its first rows.
+// Nothing else differs from the order without it: same barriers, same reservation and publication protocol, no wait on
+// another workgroup that was not there before.
 template <bool VEC, int ND, int I, bool KLDS, bool FILT, bool PK, int T = PA_T>
 __global__ __launch_bounds__(T, 4) void k_part_onepass(JoinIndexView ix, const u32 *__restrict__ pkey, const i32 *__restrict__ ps,
                                                        const i32 *__restrict__ pe, u64 n, u32 chunk, u32 *__restrict__ rcur, PageTab pt,
@@ -453,52 +515,53 @@ __global__ __launch_bounds__(T, 4) void k_part_onepass(JoinIndexView ix, const u
     const u32 pmask = (1u << pt.lgpg) - 1u;
     const u64 lo = (u64)blockIdx.x * chunk;
     const u64 hi = lo + chunk < n ? lo + chunk : n;
+    // the tile's rows in chunks of CH per thread (all of them, or eight at a time when a thread holds sixteen: the raw
+    // columns of sixteen rows plus their routed form do not fit the registers)
+    constexpr int CH = (I % 8 == 0 && I > 8) ? 8 : I;
+    constexpr bool AHEAD = part_loads_ahead<VEC, I, FILT>();
+    // the raw columns of ONE chunk: the only registers rows are loaded into.  AHEAD: they are loaded one stage before they
+    // are used, at the point where the chunk before has been routed and no longer needs them (see the chunk loop)
+    u32 kk[CH]; i32 qs[CH], qe[CH];
+    bool ahead = false;                                      // wave-uniform: kk / qs / qe hold (or wait for) this tile's first chunk
     for (u64 t0 = lo; t0 < hi; t0 += TILE) {
         if (tid < ND) dstart[tid] = 0;
         __syncthreads();
         u64 se[PK ? 1 : I]; u32 plo[PK ? I : 1], dig[I];     // PK: low word of the packed row (the length's bits above its low 8 ride in dig)
-        // the tile's rows in chunks of CH per thread (all of them, or eight at a time when a thread holds sixteen: the raw
-        // columns of sixteen rows plus their routed form do not fit the registers)
-        constexpr int CH = (I % 8 == 0 && I > 8) ? 8 : I;
+        const bool whole = VEC && t0 + TILE <= hi;
 #pragma unroll
         for (int c0 = 0; c0 < I; c0 += CH) {
-            // a chunk's row loads first, then all of its bitmap gathers: straight-line code (no per-row branches), so that
-            // the loads of a stage are in flight together
-            u32 kk[CH]; i32 qs[CH], qe[CH];
-            if (VEC && t0 + TILE <= hi) {
-                typedef u32 __attribute__((ext_vector_type(4))) v4u;
-                typedef i32 __attribute__((ext_vector_type(4))) v4i;
-#pragma unroll
-                for (int v = 0; v < CH / 4; v++) {
-                    const u64 i = t0 + ((u64)(c0 / 4 + v) * T + tid) * 4;
-                    const v4u kv = pkey ? __builtin_nontemporal_load(reinterpret_cast<const v4u *>(pkey + i)) : v4u{0u, 0u, 0u, 0u};
-                    const v4i sv = __builtin_nontemporal_load(reinterpret_cast<const v4i *>(ps + i));
-                    const v4i ev = __builtin_nontemporal_load(reinterpret_cast<const v4i *>(pe + i));
-                    kk[v * 4] = kv.x; kk[v * 4 + 1] = kv.y; kk[v * 4 + 2] = kv.z; kk[v * 4 + 3] = kv.w;
-                    qs[v * 4] = sv.x; qs[v * 4 + 1] = sv.y; qs[v * 4 + 2] = sv.z; qs[v * 4 + 3] = sv.w;
-                    qe[v * 4] = ev.x; qe[v * 4 + 1] = ev.y; qe[v * 4 + 2] = ev.z; qe[v * 4 + 3] = ev.w;
-                }
-            } else {
-#pragma unroll
-                for (int v = 0; v < CH / 4; v++) {
-                    u32 k4[4]; i32 s4[4], e4[4];
-                    load4nt<false>(pkey, ps, pe, t0 + ((u64)(c0 / 4 + v) * T + tid) * 4, hi, k4, s4, e4);
-#pragma unroll
-                    for (int j = 0; j < 4; j++) { kk[v * 4 + j] = k4[j]; qs[v * 4 + j] = s4[j]; qe[v * 4 + j] = e4[j]; }
-                }
-            }
+            // What is in flight when.  A chunk's rows are loaded, routed (route_prep: straight-line code, no per-row
+            // branches), tested against the bitmap (all gathers of the chunk in flight together) and counted in LDS.  Its raw
+            // columns are dead once route_prep has turned them into dig / plo / fpos, so AHEAD issues the NEXT stage's row
+            // loads right there, into the same registers, and they fly while this chunk gathers and counts:
+            //   - not the last chunk: the tile's next chunk;
+            //   - the last chunk: the first chunk of the workgroup's next tile, if that tile is whole and the columns are
+            //     aligned (`ahead`, wave-uniform; nothing at or beyond hi <= n is touched).  Those loads also fly through
+            //     the reservation, the LDS re-order, the write-out, the closing barrier and the next tile's dstart
+            //     barrier, and the next iteration starts routing without loading.
+            // Only a workgroup's first tile, a partial last tile and unaligned columns load at the top of the tile.
+            // !AHEAD (the order before): every chunk loads its own rows at its top.
+            if (c0 == 0 ? !ahead : !AHEAD) part_load_rows<CH, T>(pkey, ps, pe, t0, c0 / 4, hi, whole, kk, qs, qe);
             u32 fpos[CH];
 #pragma unroll
             for (int k = 0; k < CH; k++) {
                 u64 packed;
                 const u32 maxlen = pk_maxlen(rowbits);
-                qs[k] = (i32)((u32)qs[k] + adj); qe[k] = (i32)((u32)qe[k] - adj);
-                dig[c0 + k] = route_prep<KLDS, FILT, PK>(ix, kt, kk[k], qs[k], qe[k], fpos[k], packed, maxlen);
+                const i32 s1 = (i32)((u32)qs[k] + adj), e1 = (i32)((u32)qe[k] - adj);
+                dig[c0 + k] = route_prep<KLDS, FILT, PK>(ix, kt, kk[k], s1, e1, fpos[k], packed, maxlen);
                 if (PK) {
                     const u32 lenf = packed == PK_ESCAPE ? maxlen : (u32)(packed >> 24);
                     plo[PK ? c0 + k : 0] = (packed == PK_ESCAPE ? 0u : (u32)packed & 0xFFFFFFu) | (lenf << 24);
                     fpos[k] = FILT ? fpos[k] : (lenf >> 8);       // (parked until the row's rank is known; with the bitmap in use lengths keep to 8 bits)
-                } else se[PK ? 0 : c0 + k] = (u64)(u32)qs[k] | ((u64)(u32)qe[k] << 32);
+                } else se[PK ? 0 : c0 + k] = (u64)(u32)s1 | ((u64)(u32)e1 << 32);
+            }
+            if (AHEAD) {
+                asm volatile("" ::: "memory");                  // (the loads below stay below the routing above: no second set of raw columns)
+                if (c0 + CH < I) part_load_rows<CH, T>(pkey, ps, pe, t0, (c0 + CH) / 4, hi, whole, kk, qs, qe);
+                else {
+                    ahead = VEC && t0 + TILE < hi && t0 + 2 * (u64)TILE <= hi;
+                    if (ahead) part_load_rows<CH, T>(pkey, ps, pe, t0 + TILE, 0, hi, true, kk, qs, qe);
+                }
             }
             if (FILT) {
                 u64 win[CH];
@@ -519,14 +582,18 @@ __global__ __launch_bounds__(T, 4) void k_part_onepass(JoinIndexView ix, const u
                     dig[c0 + k] = dig[c0 + k] == NO_REGION ? NO_REGION : (dig[c0 + k] | (lr[u] << 10) | lhi);
                 }
             }
-            if (CH != I) asm volatile("" ::: "memory");         // (keeps the next chunk's loads from being hoisted above this chunk's work)
+            if (!AHEAD && CH != I) asm volatile("" ::: "memory");   // (keeps the next chunk's loads from being hoisted above this chunk's work)
         }
         __syncthreads();
         // ---- reserve the tile's run in every region's row stream; take / look up the pages it touches
         const u32 mine = tid < ND ? dstart[tid] : 0u;
+        // (the thread's slots in rcur, vtab and ptab are addressed from a copy of tid that is opaque per tile: their three
+        // 64-bit addresses are computed where they are used, not held in six registers across the tile loop)
+        u32 tidt = tid;
+        asm volatile("" : "+v"(tidt));
         u32 v = 0;
-        if (mine) v = atomicAdd(&rcur[tid], mine);
-        if (vtab && tid < ND) vtab[(u64)(t0 / TILE) * ND + tid] = make_uint2(v, mine);
+        if (mine) v = atomicAdd(&rcur[tidt], mine);
+        if (vtab && tid < ND) vtab[(u64)(t0 / TILE) * ND + tidt] = make_uint2(v, mine);
         u32 tot;
         const u32 ds = block_excl_scan<u32, T>(mine, scan_lds, &tot);     // (barriers inside: every counter is read before any is overwritten)
         if (tid < ND) dstart[tid] = ds;
@@ -548,7 +615,7 @@ __global__ __launch_bounds__(T, 4) void k_part_onepass(JoinIndexView ix, const u
             }
         }
         if (mine) {
-            u32 *row = pt.ptab + (u64)tid * pt.pstride;
+            u32 *row = pt.ptab + (u64)tidt * pt.pstride;
             const u32 p0 = v >> pt.lgpg, p1 = (v + mine - 1u) >> pt.lgpg;       // TILE <= page: at most one page border inside the run
             const bool own0 = (v & pmask) == 0u, own1 = p1 != p0;
             u32 got = 0;
@@ -961,7 +1028,12 @@ ivx_status ivx_route_paged(ivx_ctx *ctx, const JoinIndexView &jv, u32 nreg, cons
         hipLaunchKernelGGL(k_route_clear, dim3((u32)cg), dim3(256), 0, st, (u32 *)ctl, nctl, ptab, nptab, o.zero2);
     }
     const PageTab pt{ptab, (u32)pstride, lgpg};
-    const u32 tiles = n >= (16u << 20) ? 4u : n >= (4u << 20) ? 2u : 1u;
+    // tiles per workgroup: every tile but a workgroup's first finds its first rows loaded ahead (k_part_onepass)
+    // (tests: IVX_PART_TILES=t, t in 1, 2, 4, 8, makes it t tiles whatever n is, so that a small batch walks several tiles per
+    //  workgroup)
+    u32 tiles = n >= (16u << 20) ? 4u : n >= (4u << 20) ? 2u : 1u;
+    if (const char *tenv = getenv("IVX_PART_TILES"))
+        if ((tenv[0] == '1' || tenv[0] == '2' || tenv[0] == '4' || tenv[0] == '8') && tenv[1] == 0) tiles = (u32)(tenv[0] - '0');
     const u32 chunk1 = tile * tiles;
     const u32 nblk1 = (u32)((n + chunk1 - 1) / chunk1);
     with_bools([&](auto vec, auto klds, auto filt, auto pk) {
