@@ -32,6 +32,7 @@ struct ivx_sub_plan {
     u64 nl = 0, nr = 0, nh = 0, total = 0;
     u32 nkeys = 0;
     int strict = 0;
+    int wf = 0;                         // the count pass took the two-search plan (every right row has start <= end)
     hipStream_t stream = nullptr;
     const u32 *lk, *lrow, *rk, *hk, *hj;
     const i64 *lsv, *lev, *rsv, *hrs, *hpm;

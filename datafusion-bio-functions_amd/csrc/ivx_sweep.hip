@@ -716,10 +716,16 @@ __global__ __launch_bounds__(ST) void k_sub_brackets(const u32 *__restrict__ lk,
     brk[b] = r < nl ? lex_rank(hk, hrs, nh, lk[r], lsv[r], true) : nh;
 }
 
+// DEBUG (ivx_debug_subtract_paths, tests only): the same pass also says what it did -- per workgroup SUB_DBG_WORDS words
+// (brk[b], brk[b+1], h0, hn, r0, rn, lds, rows planned again after `esc`; all 0 for the workgroup that owns only cnt[nl]),
+// zeroed by the caller, and per left row, at its original index, whether its LDS plan raised `esc`.
+constexpr u32 SUB_DBG_WORDS = 8;
+template <bool DEBUG>
 __global__ __launch_bounds__(ST) void k_sub_count(const u32 *__restrict__ lk, const i64 *__restrict__ lsv, const i64 *__restrict__ lev, u64 nl,
                                                   int strict, const u32 *hk, const i64 *hrs, const u32 *hj, u32 nh,
                                                   const u32 *rk, const i64 *rs, const SegMax64 *sm, u32 nr, u64 *cnt,
-                                                  u32 *__restrict__ plan_hlo, i64 *__restrict__ plan_tail, const u32 *__restrict__ brk, int wf)
+                                                  u32 *__restrict__ plan_hlo, i64 *__restrict__ plan_tail, const u32 *__restrict__ brk, int wf,
+                                                  u32 *dbg_wg, u8 *dbg_esc, const u32 *dbg_lrow)
 {
     __shared__ u32 s_h[2], s_win[4];
     __shared__ u32 l_hk[SUB_HW], l_hj[SUB_HW], l_rk[SUB_RW];
@@ -739,6 +745,12 @@ __global__ __launch_bounds__(ST) void k_sub_count(const u32 *__restrict__ lk, co
     }
     __syncthreads();
     const bool lds = i0 < nl && s_win[1] <= SUB_HW && s_win[3] <= SUB_RW;          // (the same for the whole workgroup)
+    if constexpr (DEBUG) {
+        if (threadIdx.x == 0 && i0 < nl) {
+            u32 *w = dbg_wg + (size_t)blockIdx.x * SUB_DBG_WORDS;
+            w[0] = s_h[0]; w[1] = s_h[1]; w[2] = s_win[0]; w[3] = s_win[1]; w[4] = s_win[2]; w[5] = s_win[3]; w[6] = lds ? 1u : 0u;
+        }
+    }
     if (lds) {
         const u32 h0 = s_win[0], hn = s_win[1], r0 = s_win[2], rn = s_win[3];
         for (u32 x = threadIdx.x; x < hn; x += ST) { l_hk[x] = hk[h0 + x]; l_hrs[x] = hrs[h0 + x]; l_hj[x] = hj[h0 + x]; }
@@ -756,6 +768,11 @@ __global__ __launch_bounds__(ST) void k_sub_count(const u32 *__restrict__ lk, co
         SubLds a{l_hk, l_hrs, l_hj, l_rk, l_rs, l_pm, s_win[0], s_win[1], s_win[2], s_win[3], false};
         p = wf ? plan_row<SubLds, true>(k, ls, le, strict, a, nh, nr, s_h[0], s_h[1]) : plan_row<SubLds, false>(k, ls, le, strict, a, nh, nr, s_h[0], s_h[1]);
         redo = a.esc;
+    }
+    if constexpr (DEBUG) {
+        const bool esc = lds && redo;
+        dbg_esc[dbg_lrow[i]] = esc ? 1 : 0;
+        if (esc) atomicAdd(dbg_wg + (size_t)blockIdx.x * SUB_DBG_WORDS + 7, 1u);
     }
     if (redo) p = wf ? plan_row<SubGlobal, true>(k, ls, le, strict, g, nh, nr, s_h[0], s_h[1]) : plan_row<SubGlobal, false>(k, ls, le, strict, g, nh, nr, s_h[0], s_h[1]);
     cnt[i] = (u64)(p.h_hi - p.h_lo) + p.has_tail;
@@ -1057,9 +1074,9 @@ ivx_status ivx_subtract_device(ivx_ctx *ctx, const u32 *lkey, const i64 *ls, con
     u32 *brk;
     IVX_TRY(ctx->get_scratch(WS_GRID0, ((size_t)nblk_c + 2) * sizeof(u32), (void **)&brk));
     hipLaunchKernelGGL(k_sub_brackets, dim3(grid1((u64)nblk_c + 1)), dim3(ST), 0, st, (const u32 *)lk, (const i64 *)lsv, nl, (const u32 *)hk, (const i64 *)hrs, (u32)nh, nblk_c, brk);
-    hipLaunchKernelGGL(k_sub_count, dim3(nblk_c), dim3(ST), 0, st, (const u32 *)lk, (const i64 *)lsv, (const i64 *)lev, nl, strict,
+    hipLaunchKernelGGL(k_sub_count<false>, dim3(nblk_c), dim3(ST), 0, st, (const u32 *)lk, (const i64 *)lsv, (const i64 *)lev, nl, strict,
                        (const u32 *)hk, (const i64 *)hrs, (const u32 *)hj, (u32)nh, (const u32 *)rk, (const i64 *)rsv, (const SegMax64 *)sm, (u32)nr, cnt,
-                       plan_hlo, plan_tail, (const u32 *)brk, wf);
+                       plan_hlo, plan_tail, (const u32 *)brk, wf, (u32 *)nullptr, (u8 *)nullptr, (const u32 *)nullptr);
     IVX_TRY(ivx_scan_exclusive_u64(ctx, cnt, nl + 1));
     IVX_HIP(ctx, hipMemcpyAsync(ctx->h_scalars + 5, cnt + nl, sizeof(u64), hipMemcpyDeviceToHost, st));
     IVX_HIP(ctx, hipStreamSynchronize(st));
@@ -1068,7 +1085,7 @@ ivx_status ivx_subtract_device(ivx_ctx *ctx, const u32 *lkey, const i64 *ls, con
     ivx_sub_plan &pl = ctx->sub_plan;
     pl.nl = nl; pl.nr = nr; pl.nh = nh; pl.total = total; pl.nkeys = nkeys; pl.strict = strict; pl.stream = st;
     pl.lk = lk; pl.lsv = lsv; pl.lev = lev; pl.lrow = lrow; pl.rk = rk; pl.rsv = rsv; pl.sm = sm;
-    pl.hk = hk; pl.hrs = hrs; pl.hpm = hpm; pl.hj = hj; pl.offs = cnt; pl.plan_hlo = plan_hlo; pl.plan_tail = plan_tail;
+    pl.hk = hk; pl.hrs = hrs; pl.hpm = hpm; pl.hj = hj; pl.offs = cnt; pl.plan_hlo = plan_hlo; pl.plan_tail = plan_tail; pl.wf = wf;
     if (cap == 0 && !ok && !os && !oe && !orow) {                       // count only: the fill call that follows reuses all of it
         pl.slots = 0;
         for (int slot : {WS_T0, WS_T1, WS_T2, WS_T3, WS_T4, WS_T5, WS_T7, WS_T9, WS_RA0, WS_RA1, WS_RA2, WS_RB0, WS_RB1, WS_RB2}) pl.slots |= 1ull << slot;
@@ -1088,6 +1105,45 @@ ivx_status ivx_subtract_fill_planned(ivx_ctx *ctx, u32 *ok, i64 *os, i64 *oe, u3
                        pl.hk, pl.hrs, pl.hpm, pl.hj, (u32)pl.nh, pl.rk, pl.rsv, (const SegMax64 *)pl.sm, (u32)pl.nr,
                        pl.offs, cap, ok, os, oe, orow, pl.plan_hlo, pl.plan_tail);
     IVX_HIP(ctx, hipGetLastError());
+    return IVX_OK;
+}
+
+// Test hook (not in include/ivx.h): what the count pass of the last subtract SIZING call did, read off a second run of that
+// pass (k_sub_count<true>) over the plan the call left in the context.  wg: SUB_DBG_WORDS words per workgroup (k_sub_count),
+// row_esc: one byte per left row at its original index; both host buffers, capacities in workgroups / rows.  The run writes
+// its counts and row plans into scratch of its own, in slots that are none of the plan's: the fill call that follows is
+// still served by the plan.
+extern "C" ivx_status ivx_debug_subtract_paths(ivx_ctx *ctx, u32 *wg, u64 wg_cap, u8 *row_esc, u64 row_cap, u64 *n_wg, u64 *n_rows)
+{
+    if (!ctx) return IVX_ERR_INVALID;
+    const ivx_sub_plan &pl = ctx->sub_plan;
+    if (!pl.valid || !pl.lrow || !n_wg || !n_rows) return ctx->fail(IVX_ERR_INVALID, "debug_subtract_paths: no subtract plan (call it after a sizing call)");
+    const u64 nl = pl.nl;
+    const u32 nblk_c = grid1(nl + 1);
+    *n_wg = nblk_c; *n_rows = nl;
+    if (wg_cap < nblk_c || row_cap < nl || !wg || !row_esc) return ctx->fail(IVX_ERR_CAPACITY, "debug_subtract_paths: buffers too small");
+    IVX_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = pl.stream;
+    u64 *cnt; u32 *plan_hlo, *brk, *d_wg; i64 *plan_tail; u8 *d_esc;
+    constexpr int mine[] = {WS_T6, WS_T8, WS_SA0, WS_GRID0, WS_SA1, WS_SA2};
+    for (int slot : mine)
+        if ((pl.slots >> slot) & 1) return ctx->fail(IVX_ERR_INVALID, "debug_subtract_paths: scratch slot belongs to the plan");
+    IVX_TRY(ctx->get_scratch(WS_T6, (nl + 1) * sizeof(u64), (void **)&cnt));
+    IVX_TRY(ctx->get_scratch(WS_T8, nl * sizeof(u32), (void **)&plan_hlo));
+    IVX_TRY(ctx->get_scratch(WS_SA0, nl * sizeof(i64), (void **)&plan_tail));
+    IVX_TRY(ctx->get_scratch(WS_GRID0, ((size_t)nblk_c + 2) * sizeof(u32), (void **)&brk));
+    IVX_TRY(ctx->get_scratch(WS_SA1, (size_t)nblk_c * SUB_DBG_WORDS * sizeof(u32), (void **)&d_wg));
+    IVX_TRY(ctx->get_scratch(WS_SA2, nl, (void **)&d_esc));
+    IVX_HIP(ctx, hipMemsetAsync(d_wg, 0, (size_t)nblk_c * SUB_DBG_WORDS * sizeof(u32), st));
+    hipLaunchKernelGGL(k_sub_brackets, dim3(grid1((u64)nblk_c + 1)), dim3(ST), 0, st, pl.lk, pl.lsv, nl, pl.hk, pl.hrs, (u32)pl.nh, nblk_c, brk);
+    hipLaunchKernelGGL(k_sub_count<true>, dim3(nblk_c), dim3(ST), 0, st, pl.lk, pl.lsv, pl.lev, nl, pl.strict,
+                       pl.hk, pl.hrs, pl.hj, (u32)pl.nh, pl.rk, pl.rsv, (const SegMax64 *)pl.sm, (u32)pl.nr, cnt,
+                       plan_hlo, plan_tail, (const u32 *)brk, pl.wf, d_wg, d_esc, pl.lrow);
+    IVX_HIP(ctx, hipGetLastError());
+    IVX_HIP(ctx, hipMemcpyAsync(wg, d_wg, (size_t)nblk_c * SUB_DBG_WORDS * sizeof(u32), hipMemcpyDeviceToHost, st));
+    IVX_HIP(ctx, hipMemcpyAsync(row_esc, d_esc, nl, hipMemcpyDeviceToHost, st));
+    IVX_HIP(ctx, hipStreamSynchronize(st));
+    if (!pl.valid) return ctx->fail(IVX_ERR_INVALID, "debug_subtract_paths: the plan was dropped");
     return IVX_OK;
 }
 

@@ -105,6 +105,9 @@ def lib():
         L.ivx_depth_profile_merge.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
         L.ivx_depth_profile_blocks.restype = C.c_int
         L.ivx_depth_profile_blocks.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_uint64, C.POINTER(C.c_uint64)]
+        # test hook of csrc/ivx_sweep.hip (not in include/ivx.h): what subtract's count pass did (tests/test_gpu_subtract_edges.py)
+        L.ivx_debug_subtract_paths.restype = C.c_int
+        L.ivx_debug_subtract_paths.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         _lib = L
     return _lib
 
