@@ -131,6 +131,11 @@ class Session:
         """refuse batches with NULL contigs instead of treating them as the reference does (bio_ranges_host.h)"""
         self._chk(lib().brh_session_set_strict_null_contigs(self.h, C.c_int(int(on))))
 
+    def set_string_cigars(self, on=True):
+        """depth(), depth_per_base() and depth_stream() accept a Utf8 / LargeUtf8 cigar column ("5M3D5M"), parsed on the
+        device; off (the default) such a column is refused (bio_ranges_host.h brh_session_set_string_cigars)"""
+        self._chk(lib().brh_session_set_string_cigars(self.h, C.c_int(int(on))))
+
     def set_memory_limit(self, nbytes):
         """device bytes the session may reserve (MemoryReservation, interval_join.rs:614-639); 0 = no limit"""
         self._chk(lib().brh_session_set_memory_limit(self.h, C.c_uint64(int(nbytes))))
@@ -321,7 +326,8 @@ class Session:
 
     # ---- depth (bio-function-pileup: table_function.rs depth(); events.rs + coverage.rs)
     def depth(self, reads, prior=None, lengths=None, filter_flag=1796, min_mapq=0):
-        """coverage blocks of a reads table (chrom, start UInt32, flags UInt32, mapping_quality UInt32, cigar Binary):
+        """coverage blocks of a reads table (chrom, start UInt32, flags UInt32, mapping_quality UInt32, cigar Binary -- or
+        Utf8 / LargeUtf8 text after set_string_cigars(True)):
         -> contig Utf8, pos_start Int32, pos_end Int32, coverage Int16.  prior: the blocks of an earlier call, added in;
         lengths: a table (name, length) that turns the reference's dense-mode clipping on."""
         tabs = [_Exported(t) if t is not None else None for t in (reads, prior, lengths)]

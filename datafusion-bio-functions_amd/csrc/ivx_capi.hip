@@ -1167,7 +1167,7 @@ ivx_status depth_stage_in(ivx_ctx *ctx, int mem,
     IVX_HIP(ctx, hipSetDevice(ctx->device));
     // IVX_MEM_HOST: the ops column is staged up to the last offset (the device checks the offsets before it reads an op)
     u64 n_ops_host = 0;
-    if (mem == IVX_MEM_HOST && n_reads && cigar_offsets[n_reads] > 0) n_ops_host = (u64)cigar_offsets[n_reads] / 4;
+    if (mem == IVX_MEM_HOST && n_reads && cigar_offsets && cigar_offsets[n_reads] > 0) n_ops_host = (u64)cigar_offsets[n_reads] / 4;   // (null: the text calls)
     if (n_ops_host && !cigar_ops) return ctx->fail(IVX_ERR_INVALID, "depth: null CIGAR data buffer");
     IVX_TRY(stage_in(ctx, mem, WS_IN_KEY, rkey, n_reads, &d->rkey));
     IVX_TRY(stage_in(ctx, mem, WS_IN_START, rpos, n_reads, &d->rpos));
@@ -1183,6 +1183,63 @@ ivx_status depth_stage_in(ivx_ctx *ctx, int mem,
     return IVX_OK;
 }
 
+// the cigar column of the text calls: an Arrow Utf8 (large = 0) / LargeUtf8 (1) column
+struct TextIn { int large; const void *off; const uint8_t *text; };
+
+// the text column on the device.  IVX_MEM_HOST: the offsets, and the bytes between the first and the last offset (the extent
+// is read from the host offsets, as depth_stage_in does for ops; the device checks the offsets before it reads a byte
+// through one, and offsets that pass name bytes inside the extent) -- *at_off0: *dtext is the byte at offset off[0]
+ivx_status cigar_stage_text(ivx_ctx *ctx, int mem, const TextIn &t, u64 n_reads, const void **doff, const u8 **dtext, bool *at_off0)
+{
+    *at_off0 = false;
+    if (mem == IVX_MEM_DEVICE) { *doff = t.off; *dtext = t.text; return IVX_OK; }
+    const i64 o0 = t.large ? ((const i64 *)t.off)[0] : (i64)((const i32 *)t.off)[0];
+    const i64 oN = t.large ? ((const i64 *)t.off)[n_reads] : (i64)((const i32 *)t.off)[n_reads];
+    u64 extent = 0;
+    if (o0 >= 0 && oN > o0) {
+        extent = (u64)(oN - o0);
+        if (extent >= (1ull << 32)) return ctx->fail(IVX_ERR_INVALID, "cigar: 2^32 or more bytes of CIGAR text in one call");
+        if (!t.text) return ctx->fail(IVX_ERR_INVALID, "cigar: null text buffer");
+    }
+    const u8 *o8;
+    IVX_TRY(stage_in(ctx, mem, WS_IN_TEXTOFF, (const u8 *)t.off, (n_reads + 1) * (t.large ? 8 : 4), &o8));
+    *doff = o8;
+    *dtext = nullptr;
+    if (extent) { IVX_TRY(stage_in(ctx, mem, WS_IN_TEXT, t.text + o0, extent, dtext)); *at_off0 = true; }
+    return IVX_OK;
+}
+
+// the text column parsed into context scratch: d->off / d->ops as the binary calls take them
+ivx_status depth_parse_text(ivx_ctx *ctx, int mem, const TextIn &t, u64 n_reads, DepthIn *d)
+{
+    d->off = nullptr; d->ops = nullptr;
+    if (n_reads == 0) return IVX_OK;
+    const void *doff; const u8 *dtext; bool at0;
+    IVX_TRY(cigar_stage_text(ctx, mem, t, n_reads, &doff, &dtext, &at0));
+    ivx_cigar_plan P;
+    IVX_TRY(ivx_cigar_count(ctx, t.large, doff, dtext, at0, n_reads, &P));
+    i32 *off; u32 *ops;
+    IVX_TRY(ctx->get_scratch(WS_IN2_START, (size_t)(n_reads + 1) * sizeof(i32), (void **)&off));
+    IVX_TRY(ctx->get_scratch(WS_IN2_END, (size_t)P.n_ops * sizeof(u32), (void **)&ops));
+    IVX_TRY(ivx_cigar_write(ctx, P, off, ops));
+    d->off = off; d->ops = ops;
+    return IVX_OK;
+}
+
+ivx_status depth_call(ivx_ctx *ctx, int mem,
+                      const uint32_t *rkey, const uint32_t *rpos, const uint32_t *rflags, const uint32_t *rmapq,
+                      const int32_t *cigar_offsets, const uint32_t *cigar_ops, const TextIn *text, uint64_t n_reads,
+                      const uint32_t *skey, const uint32_t *sstart, const uint32_t *send, const int32_t *sweight, uint64_t n_seg,
+                      uint32_t n_keys, const uint32_t *key_len, uint32_t filter_flag, uint32_t min_mapq,
+                      uint32_t *out_key, uint32_t *out_start, uint32_t *out_end, int32_t *out_cov,
+                      uint64_t cap, uint64_t *n_out);
+ivx_status depth_profile_call(ivx_ctx *ctx, int mem,
+                              const uint32_t *rkey, const uint32_t *rpos, const uint32_t *rflags, const uint32_t *rmapq,
+                              const int32_t *cigar_offsets, const uint32_t *cigar_ops, const TextIn *text, uint64_t n_reads,
+                              const uint32_t *skey, const uint32_t *sstart, const uint32_t *send, const int32_t *sweight, uint64_t n_seg,
+                              uint32_t n_keys, const uint32_t *key_len, uint32_t filter_flag, uint32_t min_mapq,
+                              ivx_index **out);
+
 }  // namespace
 
 extern "C" ivx_status ivx_depth(ivx_ctx *ctx, int mem,
@@ -1193,17 +1250,94 @@ extern "C" ivx_status ivx_depth(ivx_ctx *ctx, int mem,
                                 uint32_t *out_key, uint32_t *out_start, uint32_t *out_end, int32_t *out_cov,
                                 uint64_t cap, uint64_t *n_out)
 {
+    return depth_call(ctx, mem, rkey, rpos, rflags, rmapq, cigar_offsets, cigar_ops, nullptr, n_reads, skey, sstart, send, sweight, n_seg,
+                      n_keys, key_len, filter_flag, min_mapq, out_key, out_start, out_end, out_cov, cap, n_out);
+}
+
+extern "C" ivx_status ivx_depth_text(ivx_ctx *ctx, int mem,
+                                     const uint32_t *rkey, const uint32_t *rpos, const uint32_t *rflags, const uint32_t *rmapq,
+                                     int large, const void *text_offsets, const uint8_t *text, uint64_t n_reads,
+                                     const uint32_t *skey, const uint32_t *sstart, const uint32_t *send, const int32_t *sweight, uint64_t n_seg,
+                                     uint32_t n_keys, const uint32_t *key_len, uint32_t filter_flag, uint32_t min_mapq,
+                                     uint32_t *out_key, uint32_t *out_start, uint32_t *out_end, int32_t *out_cov,
+                                     uint64_t cap, uint64_t *n_out)
+{
+    const TextIn t{large, text_offsets, text};
+    return depth_call(ctx, mem, rkey, rpos, rflags, rmapq, nullptr, nullptr, &t, n_reads, skey, sstart, send, sweight, n_seg,
+                      n_keys, key_len, filter_flag, min_mapq, out_key, out_start, out_end, out_cov, cap, n_out);
+}
+
+extern "C" ivx_status ivx_depth_profile_build_text(ivx_ctx *ctx, int mem,
+                                                   const uint32_t *rkey, const uint32_t *rpos, const uint32_t *rflags, const uint32_t *rmapq,
+                                                   int large, const void *text_offsets, const uint8_t *text, uint64_t n_reads,
+                                                   const uint32_t *skey, const uint32_t *sstart, const uint32_t *send, const int32_t *sweight, uint64_t n_seg,
+                                                   uint32_t n_keys, const uint32_t *key_len, uint32_t filter_flag, uint32_t min_mapq,
+                                                   ivx_index **out)
+{
+    const TextIn t{large, text_offsets, text};
+    return depth_profile_call(ctx, mem, rkey, rpos, rflags, rmapq, nullptr, nullptr, &t, n_reads, skey, sstart, send, sweight, n_seg,
+                              n_keys, key_len, filter_flag, min_mapq, out);
+}
+
+extern "C" ivx_status ivx_cigar_parse(ivx_ctx *ctx, int mem, int large, const void *text_offsets, const uint8_t *text, uint64_t n_reads,
+                                      int32_t *out_offsets, uint32_t *out_ops, uint64_t cap_ops, uint64_t *n_ops)
+{
+    if (!ctx) return IVX_ERR_INVALID;
+    if (!n_ops) return ctx->fail(IVX_ERR_INVALID, "null n_ops");
+    *n_ops = 0;
+    if (mem != IVX_MEM_HOST && mem != IVX_MEM_DEVICE) return ctx->fail(IVX_ERR_INVALID, "bad mem");
+    if (large != 0 && large != 1) return ctx->fail(IVX_ERR_INVALID, "cigar: large must be 0 (Utf8) or 1 (LargeUtf8)");
+    if (n_reads >= 0xFFFFFFFFull) return ctx->fail(IVX_ERR_INVALID, "cigar: too many rows in one call");
+    ctx->sub_plan.valid = false; ctx->join_plan.valid = false;   // as any other call between a sizing call and its fill
+    if (n_reads == 0) return IVX_OK;
+    if (!text_offsets) return ctx->fail(IVX_ERR_INVALID, "cigar: null text offset column");
+    IVX_HIP(ctx, hipSetDevice(ctx->device));
+    const TextIn t{large, text_offsets, text};
+    const void *doff; const u8 *dtext; bool at0;
+    IVX_TRY(cigar_stage_text(ctx, mem, t, n_reads, &doff, &dtext, &at0));
+    ivx_cigar_plan P;
+    IVX_TRY(ivx_cigar_count(ctx, large, doff, dtext, at0, n_reads, &P));
+    *n_ops = P.n_ops;
+    // the op lengths are checked in every call, a counting call included; ops are written only into a buffer that holds all
+    const bool fits = out_ops && cap_ops >= P.n_ops;
+    i32 *ooff; u32 *oops = nullptr;
+    IVX_TRY(stage_out(ctx, mem, WS_OUT_A, out_offsets, n_reads + 1, &ooff));
+    if (fits) IVX_TRY(stage_out(ctx, mem, WS_OUT_B, out_ops, P.n_ops, &oops));
+    IVX_TRY(ivx_cigar_write(ctx, P, ooff, oops));
+    IVX_TRY(copy_out(ctx, mem, out_offsets, ooff, n_reads + 1));
+    if (fits) IVX_TRY(copy_out(ctx, mem, out_ops, oops, P.n_ops));
+    IVX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (out_ops && !fits) return ctx->fail(IVX_ERR_CAPACITY, "cigar: op buffer too small");
+    if (!out_ops && cap_ops && cap_ops < P.n_ops) return ctx->fail(IVX_ERR_CAPACITY, "cigar: op buffer too small");
+    return IVX_OK;
+}
+
+namespace {
+
+// ivx_depth (text = null) and ivx_depth_text (the cigar column as text, parsed into context scratch first)
+ivx_status depth_call(ivx_ctx *ctx, int mem,
+                      const uint32_t *rkey, const uint32_t *rpos, const uint32_t *rflags, const uint32_t *rmapq,
+                      const int32_t *cigar_offsets, const uint32_t *cigar_ops, const TextIn *text, uint64_t n_reads,
+                      const uint32_t *skey, const uint32_t *sstart, const uint32_t *send, const int32_t *sweight, uint64_t n_seg,
+                      uint32_t n_keys, const uint32_t *key_len, uint32_t filter_flag, uint32_t min_mapq,
+                      uint32_t *out_key, uint32_t *out_start, uint32_t *out_end, int32_t *out_cov,
+                      uint64_t cap, uint64_t *n_out)
+{
     if (!ctx) return IVX_ERR_INVALID;
     if (!n_out) return ctx->fail(IVX_ERR_INVALID, "null n_out");
     *n_out = 0;
+    if (text) {
+        if (text->large != 0 && text->large != 1) return ctx->fail(IVX_ERR_INVALID, "cigar: large must be 0 (Utf8) or 1 (LargeUtf8)");
+        cigar_offsets = (const int32_t *)text->off;             // (for the null check only)
+    }
     IVX_TRY(depth_check_args(ctx, mem, rkey, rpos, cigar_offsets, n_reads, skey, sstart, send, n_seg, &n_keys));
     ctx->sub_plan.valid = false; ctx->join_plan.valid = false;   // as any other call between a sizing call and its fill
     CallMetrics cm(ctx, false, n_reads + n_seg);
     if (n_reads == 0 && n_seg == 0) return IVX_OK;
     DepthIn d;
     u32 *ok, *os, *oe; i32 *oc;
-    IVX_TRY(depth_stage_in(ctx, mem, rkey, rpos, rflags, rmapq, cigar_offsets, cigar_ops, n_reads, skey, sstart, send, sweight, n_seg,
-                           n_keys, key_len, &d));
+    IVX_TRY(depth_stage_in(ctx, mem, rkey, rpos, rflags, rmapq, text ? nullptr : cigar_offsets, text ? nullptr : cigar_ops, n_reads,
+                           skey, sstart, send, sweight, n_seg, n_keys, key_len, &d));
     IVX_TRY(stage_out(ctx, mem, WS_OUT_A, out_key, cap, &ok));
     IVX_TRY(stage_out(ctx, mem, WS_OUT_B, out_start, cap, &os));
     IVX_TRY(stage_out(ctx, mem, WS_OUT_C, out_end, cap, &oe));
@@ -1212,6 +1346,7 @@ extern "C" ivx_status ivx_depth(ivx_ctx *ctx, int mem,
     u64 m = 0;
     {
         KernelTimer t(ctx);
+        if (text) IVX_TRY(depth_parse_text(ctx, mem, *text, n_reads, &d));
         ivx_status st = ivx_depth_device(ctx, d.rkey, d.rpos, d.rflags, d.rmapq, d.off, d.ops, n_reads, d.skey, d.ss, d.se, d.sw, n_seg,
                                          n_keys, d.key_len, filter_flag, min_mapq, ok, os, oe, oc, cap, &m);
         *n_out = m;
@@ -1228,6 +1363,8 @@ extern "C" ivx_status ivx_depth(ivx_ctx *ctx, int mem,
     return IVX_OK;
 }
 
+}  // namespace
+
 // ---------------------------------------------------------------- g': depth profiles (per-base depth())
 
 extern "C" ivx_status ivx_depth_profile_build(ivx_ctx *ctx, int mem,
@@ -1237,16 +1374,33 @@ extern "C" ivx_status ivx_depth_profile_build(ivx_ctx *ctx, int mem,
                                               uint32_t n_keys, const uint32_t *key_len, uint32_t filter_flag, uint32_t min_mapq,
                                               ivx_index **out)
 {
+    return depth_profile_call(ctx, mem, rkey, rpos, rflags, rmapq, cigar_offsets, cigar_ops, nullptr, n_reads, skey, sstart, send, sweight, n_seg,
+                              n_keys, key_len, filter_flag, min_mapq, out);
+}
+
+namespace {
+
+ivx_status depth_profile_call(ivx_ctx *ctx, int mem,
+                              const uint32_t *rkey, const uint32_t *rpos, const uint32_t *rflags, const uint32_t *rmapq,
+                              const int32_t *cigar_offsets, const uint32_t *cigar_ops, const TextIn *text, uint64_t n_reads,
+                              const uint32_t *skey, const uint32_t *sstart, const uint32_t *send, const int32_t *sweight, uint64_t n_seg,
+                              uint32_t n_keys, const uint32_t *key_len, uint32_t filter_flag, uint32_t min_mapq,
+                              ivx_index **out)
+{
     if (!ctx) return IVX_ERR_INVALID;
     if (!out) return ctx->fail(IVX_ERR_INVALID, "null out");
     *out = nullptr;
+    if (text) {
+        if (text->large != 0 && text->large != 1) return ctx->fail(IVX_ERR_INVALID, "cigar: large must be 0 (Utf8) or 1 (LargeUtf8)");
+        cigar_offsets = (const int32_t *)text->off;             // (for the null check only)
+    }
     IVX_TRY(depth_check_args(ctx, mem, rkey, rpos, cigar_offsets, n_reads, skey, sstart, send, n_seg, &n_keys));
     ctx->sub_plan.valid = false; ctx->join_plan.valid = false;   // as any other call between a sizing call and its fill
     CallMetrics cm(ctx, true, n_reads + n_seg);
     DepthIn d{};
     if (n_reads || n_seg)
-        IVX_TRY(depth_stage_in(ctx, mem, rkey, rpos, rflags, rmapq, cigar_offsets, cigar_ops, n_reads, skey, sstart, send, sweight, n_seg,
-                               n_keys, key_len, &d));
+        IVX_TRY(depth_stage_in(ctx, mem, rkey, rpos, rflags, rmapq, text ? nullptr : cigar_offsets, text ? nullptr : cigar_ops, n_reads,
+                               skey, sstart, send, sweight, n_seg, n_keys, key_len, &d));
     else IVX_HIP(ctx, hipSetDevice(ctx->device));
     ivx_index *ix = new (std::nothrow) ivx_index();
     if (!ix) return ctx->fail(IVX_ERR_OOM, "host allocation failed");
@@ -1257,7 +1411,8 @@ extern "C" ivx_status ivx_depth_profile_build(ivx_ctx *ctx, int mem,
     ivx_status st = ivx_depth_profile_begin(ctx, ix, &seen);
     if (st == IVX_OK) {
         KernelTimer t(ctx);
-        st = ivx_depth_events(ctx, d.rkey, d.rpos, d.rflags, d.rmapq, d.off, d.ops, n_reads, d.skey, d.ss, d.se, d.sw, n_seg,
+        if (text) st = depth_parse_text(ctx, mem, *text, n_reads, &d);
+        if (st == IVX_OK) st = ivx_depth_events(ctx, d.rkey, d.rpos, d.rflags, d.rmapq, d.off, d.ops, n_reads, d.skey, d.ss, d.se, d.sw, n_seg,
                               n_keys, d.key_len, filter_flag, min_mapq, seen, &evs);
         if (st == IVX_OK) st = ivx_depth_profile_finish(ctx, ix, evs);
     }
@@ -1271,6 +1426,8 @@ extern "C" ivx_status ivx_depth_profile_build(ivx_ctx *ctx, int mem,
     *out = ix;
     return IVX_OK;
 }
+
+}  // namespace
 
 extern "C" void ivx_depth_profile_free(ivx_index *p) { if (p && p->kind == IVX_KIND_DEPTH_PROFILE) ivx_index_free(p); }
 extern "C" uint64_t ivx_depth_profile_steps(const ivx_index *p) { return p && p->kind == IVX_KIND_DEPTH_PROFILE ? p->dp.steps : 0; }

@@ -156,9 +156,10 @@ enum {
     WS_SA0, WS_SA1, WS_SA2, WS_SB0, WS_SB1, WS_SB2,                                 // sort ping/pong records
     WS_RA0, WS_RA1, WS_RA2, WS_RB0, WS_RB1, WS_RB2,                                 // second record set (subtract's right side)
     WS_T0, WS_T1, WS_T2, WS_T3, WS_T4, WS_T5, WS_T6, WS_T7, WS_T8, WS_T9,           // per-op temporaries
-    WS_IN3_KEY, WS_IN3_START, WS_IN3_END, WS_IN3_WEIGHT, WS_IN_KEYLEN               // staged host inputs of depth(): the weighted segments, the key lengths
+    WS_IN3_KEY, WS_IN3_START, WS_IN3_END, WS_IN3_WEIGHT, WS_IN_KEYLEN,              // staged host inputs of depth(): the weighted segments, the key lengths
+    WS_IN_TEXTOFF, WS_IN_TEXT                                                       // staged host inputs of the text-CIGAR calls: the Utf8 offsets and bytes
 };
-static_assert(WS_IN_KEYLEN < IVX_NSCRATCH, "scratch slot ids must fit the context's slot array");
+static_assert(WS_IN_TEXT < IVX_NSCRATCH, "scratch slot ids must fit the context's slot array");
 
 // ---------------------------------------------------------------- indexes
 #ifndef IVX_LSTEP
@@ -332,6 +333,15 @@ ivx_status ivx_depth_events(ivx_ctx *ctx, const u32 *rkey, const u32 *rpos, cons
                             const i32 *cigar_offsets, const u32 *cigar_ops, u64 n_reads,
                             const u32 *skey, const u32 *sstart, const u32 *send, const i32 *sweight, u64 n_seg,
                             u32 nkeys, const u32 *key_len, u32 filter_flag, u32 min_mapq, u8 *seen, ivx_depth_evs *out);
+// ivx_cigar.hip: text CIGARs (an Arrow Utf8 / LargeUtf8 column on the device) to packed ops.  count: the checks and the op
+// count (synchronises); write: out_off [n_reads + 1] and out_ops [n_ops], either nullable (synchronises: an op length that
+// cannot be packed is an error).  Scratch: WS_SCAN0 / WS_SCAN1, which must stay untouched between the two.
+struct ivx_cigar_plan {
+    int large; const void *off; const u8 *txt; u64 n_reads, n_bytes, n_ops, nblk; i64 off0; u32 mis; void *tsum;
+};
+ivx_status ivx_cigar_count(ivx_ctx *ctx, int large, const void *text_offsets, const u8 *text, bool text_at_off0, u64 n_reads,
+                           ivx_cigar_plan *plan);
+ivx_status ivx_cigar_write(ivx_ctx *ctx, const ivx_cigar_plan &plan, i32 *out_off, u32 *out_ops);
 // ivx_depth_expand.hip: the steps of those events as a profile (ix->dp), and windows of a profile expanded to positions
 ivx_status ivx_depth_profile_begin(ivx_ctx *ctx, ivx_index *ix, u8 **seen);     // before the front half: key_seen and the per-key table, zeroed
 ivx_status ivx_depth_profile_finish(ivx_ctx *ctx, ivx_index *ix, const ivx_depth_evs &evs);

@@ -19,6 +19,7 @@ struct brh_session {
     std::string err;
     // NULL contigs: 0 = as the reference treats them (see get_contig), 1 = refuse the batch (opt-in; BIO_STRICT_NULL_CONTIGS=1
     // makes it the default of new sessions)
+    int string_cigars = 0;              // brh_session_set_string_cigars: depth() accepts a Utf8 / LargeUtf8 cigar column
     int strict_null_contigs = [] { const char *e = std::getenv("BIO_STRICT_NULL_CONTIGS"); return e && *e && *e != '0' ? 1 : 0; }();
 };
 
@@ -417,6 +418,13 @@ extern "C" int brh_session_set_strict_null_contigs(brh_session *s, int on)
     return 0;
 }
 
+extern "C" int brh_session_set_string_cigars(brh_session *s, int on)
+{
+    if (!s) return 1;
+    s->string_cigars = on != 0;
+    return 0;
+}
+
 extern "C" int brh_session_reserved_bytes(brh_session *s, uint64_t *out)
 {
     if (!s || !out) return 1;
@@ -759,7 +767,30 @@ struct DepthInputs {
     std::vector<int32_t> sw;
     const uint32_t *rpos = nullptr, *rflags = nullptr, *rmapq = nullptr, *cops = nullptr;
     const int32_t *coff = nullptr;
+    // a text cigar column (brh_session_set_string_cigars): its offsets (int32, or int64 when large) and bytes instead of coff / cops
+    bool text = false; int large = 0;
+    const void *toff = nullptr; const uint8_t *ctext = nullptr;
     int load(brh_session *s, brh_batch reads, brh_batch prior, brh_batch lengths);
+    // ivx_depth / ivx_depth_text and ivx_depth_profile_build / ..._text on the read columns, whichever form the cigar column has
+    ivx_status depth(ivx_ctx *ctx, const uint32_t *skey_, const uint32_t *ss_, const uint32_t *se_, const int32_t *sw_, uint64_t n_seg_,
+                     uint32_t nk_, const uint32_t *key_len_, uint32_t filter_flag, uint32_t min_mapq,
+                     uint32_t *ok, uint32_t *os, uint32_t *oe, int32_t *oc, uint64_t cap, uint64_t *m) const
+    {
+        if (text)
+            return ivx_depth_text(ctx, IVX_MEM_HOST, rkey.data(), rpos, rflags, rmapq, large, toff, ctext, n_reads, skey_, ss_, se_, sw_, n_seg_,
+                                  nk_, key_len_, filter_flag, min_mapq, ok, os, oe, oc, cap, m);
+        return ivx_depth(ctx, IVX_MEM_HOST, rkey.data(), rpos, rflags, rmapq, coff, cops, n_reads, skey_, ss_, se_, sw_, n_seg_,
+                         nk_, key_len_, filter_flag, min_mapq, ok, os, oe, oc, cap, m);
+    }
+    ivx_status profile(ivx_ctx *ctx, const uint32_t *skey_, const uint32_t *ss_, const uint32_t *se_, const int32_t *sw_, uint64_t n_seg_,
+                       uint32_t nk_, const uint32_t *key_len_, uint32_t filter_flag, uint32_t min_mapq, ivx_index **out) const
+    {
+        if (text)
+            return ivx_depth_profile_build_text(ctx, IVX_MEM_HOST, rkey.data(), rpos, rflags, rmapq, large, toff, ctext, n_reads,
+                                                skey_, ss_, se_, sw_, n_seg_, nk_, key_len_, filter_flag, min_mapq, out);
+        return ivx_depth_profile_build(ctx, IVX_MEM_HOST, rkey.data(), rpos, rflags, rmapq, coff, cops, n_reads,
+                                       skey_, ss_, se_, sw_, n_seg_, nk_, key_len_, filter_flag, min_mapq, out);
+    }
 };
 
 int DepthInputs::load(brh_session *s, brh_batch reads, brh_batch prior, brh_batch lengths)
@@ -774,9 +805,16 @@ int DepthInputs::load(brh_session *s, brh_batch reads, brh_batch prior, brh_batc
     const int cc = find_col(reads.schema, "cigar");
     if (cc < 0) return fail(s, "depth: column 'cigar' not found in batch with columns: " + column_list(reads.schema));
     const char *cf = reads.schema->children[cc]->format;
-    if (!std::strcmp(cf, "u") || !std::strcmp(cf, "U") || !std::strcmp(cf, "vu"))
-        return fail(s, "depth: string CIGAR columns are not supported, use the binary CIGAR column");
-    if (std::strcmp(cf, "z")) return fail(s, "depth: unsupported data type " + std::string(cf) + " for column 'cigar'; expected Binary");
+    const bool is_str = !std::strcmp(cf, "u") || !std::strcmp(cf, "U");
+    if (s->string_cigars) {
+        if (!is_str && std::strcmp(cf, "z"))
+            return fail(s, "depth: unsupported data type " + std::string(cf) + " for column 'cigar'; expected Binary, Utf8 or LargeUtf8");
+        text = is_str; large = cf[0] == 'U';
+    } else {
+        if (is_str || !std::strcmp(cf, "vu"))
+            return fail(s, "depth: string CIGAR columns are not supported, use the binary CIGAR column");
+        if (std::strcmp(cf, "z")) return fail(s, "depth: unsupported data type " + std::string(cf) + " for column 'cigar'; expected Binary");
+    }
     const ArrowArray *cigar = reads.array->children[cc];
     n_reads = (uint64_t)reads.array->length;
     // ---- prior blocks (the output of an earlier call) and the length table
@@ -821,8 +859,14 @@ int DepthInputs::load(brh_session *s, brh_batch reads, brh_batch prior, brh_batc
     rpos = n_reads ? (const uint32_t *)start->buffers[1] + start->offset : nullptr;
     rflags = n_reads ? (const uint32_t *)flags->buffers[1] + flags->offset : nullptr;
     rmapq = n_reads ? (const uint32_t *)mapq->buffers[1] + mapq->offset : nullptr;
-    coff = n_reads ? (const int32_t *)cigar->buffers[1] + cigar->offset : nullptr;
-    cops = n_reads ? (const uint32_t *)cigar->buffers[2] : nullptr;
+    if (text) {                                              // (the validity of cigar is not read: the reference's schema has it non-null)
+        toff = !n_reads ? nullptr : large ? (const void *)((const int64_t *)cigar->buffers[1] + cigar->offset)
+                                          : (const void *)((const int32_t *)cigar->buffers[1] + cigar->offset);
+        ctext = n_reads ? (const uint8_t *)cigar->buffers[2] : nullptr;
+    } else {
+        coff = n_reads ? (const int32_t *)cigar->buffers[1] + cigar->offset : nullptr;
+        cops = n_reads ? (const uint32_t *)cigar->buffers[2] : nullptr;
+    }
     return 0;
 }
 
@@ -836,18 +880,15 @@ extern "C" int brh_depth(brh_session *s, brh_batch reads, brh_batch prior, brh_b
     DepthInputs in;
     if (in.load(s, reads, prior, lengths)) return 1;
     const bool has_prior = in.has_prior, has_len = in.has_len;
-    const uint64_t n_reads = in.n_reads, n_seg = in.n_seg;
+    const uint64_t n_seg = in.n_seg;
     const uint32_t nk = in.nk;
     const NameDict &dict = in.dict;
-    const std::vector<uint32_t> &rkey = in.rkey, &skey = in.skey, &ss = in.ss, &se = in.se, &key_len = in.key_len;
+    const std::vector<uint32_t> &skey = in.skey, &ss = in.ss, &se = in.se, &key_len = in.key_len;
     const std::vector<int32_t> &sw = in.sw;
-    const uint32_t *rpos = in.rpos, *rflags = in.rflags, *rmapq = in.rmapq, *cops = in.cops;
-    const int32_t *coff = in.coff;
     // ---- sizing call, then the fill call
     auto call = [&](uint32_t *ok, uint32_t *os, uint32_t *oe, int32_t *oc, uint64_t cap, uint64_t *m) {
-        return ivx_depth(s->ctx, IVX_MEM_HOST, rkey.data(), rpos, rflags, rmapq, coff, cops, n_reads,
-                         has_prior ? skey.data() : nullptr, ss.data(), se.data(), has_prior ? sw.data() : nullptr, n_seg,
-                         nk, has_len ? key_len.data() : nullptr, filter_flag, min_mapq, ok, os, oe, oc, cap, m);
+        return in.depth(s->ctx, has_prior ? skey.data() : nullptr, ss.data(), se.data(), has_prior ? sw.data() : nullptr, n_seg,
+                        nk, has_len ? key_len.data() : nullptr, filter_flag, min_mapq, ok, os, oe, oc, cap, m);
     };
     uint64_t m = 0, m2 = 0;
     ivx_status st = call(nullptr, nullptr, nullptr, nullptr, 0, &m);
@@ -892,9 +933,8 @@ extern "C" int brh_depth_per_base_open(brh_session *s, brh_batch reads, brh_batc
     if (in.load(s, reads, prior, lengths)) return 1;
     std::unique_ptr<brh_depth_stream> ds(new brh_depth_stream());
     ds->s = s; ds->zero_based = zero_based != 0;
-    ivx_status st = ivx_depth_profile_build(s->ctx, IVX_MEM_HOST, in.rkey.data(), in.rpos, in.rflags, in.rmapq, in.coff, in.cops, in.n_reads,
-                                            in.has_prior ? in.skey.data() : nullptr, in.ss.data(), in.se.data(), in.has_prior ? in.sw.data() : nullptr,
-                                            in.n_seg, in.nk, in.key_len.data(), filter_flag, min_mapq, &ds->profile);
+    ivx_status st = in.profile(s->ctx, in.has_prior ? in.skey.data() : nullptr, in.ss.data(), in.se.data(), in.has_prior ? in.sw.data() : nullptr,
+                               in.n_seg, in.nk, in.key_len.data(), filter_flag, min_mapq, &ds->profile);
     if (st != IVX_OK) return fail_ivx(s, st);
     ds->names = in.dict.names; ds->key_len = in.key_len;
     ds->seen.assign(in.nk, 0);
@@ -1047,9 +1087,8 @@ extern "C" int brh_depth_push_batch(brh_depth_push *dp, brh_batch reads)
     }
     for (uint32_t &k : in.rkey) if (k != IVX_NULL_IDX) k = to_stream[k];
     ivx_index *p = nullptr;
-    const ivx_status st = ivx_depth_profile_build(s->ctx, IVX_MEM_HOST, in.rkey.data(), in.rpos, in.rflags, in.rmapq, in.coff, in.cops, in.n_reads,
-                                                  nullptr, nullptr, nullptr, nullptr, 0, dp->nk(), dp->dense ? dp->key_len.data() : nullptr,
-                                                  dp->filter_flag, dp->min_mapq, &p);
+    const ivx_status st = in.profile(s->ctx, nullptr, nullptr, nullptr, nullptr, 0, dp->nk(), dp->dense ? dp->key_len.data() : nullptr,
+                                     dp->filter_flag, dp->min_mapq, &p);
     if (st != IVX_OK) return fail_ivx(s, st);
     dp->stack.push_back(p);
     // a binary counter: merge while the new top has at least half the steps of the profile below it

@@ -31,12 +31,16 @@ SYMBOLS = [
     "ivx_probe_mark_build", "ivx_bits_mark", "ivx_bits_select", "ivx_depth",
     "ivx_depth_profile_build", "ivx_depth_profile_free", "ivx_depth_profile_steps", "ivx_depth_profile_device_bytes",
     "ivx_depth_profile_read", "ivx_depth_profile_expand", "ivx_depth_profile_merge", "ivx_depth_profile_blocks",
+    "ivx_cigar_parse", "ivx_depth_text", "ivx_depth_profile_build_text",
 ]
 
 # outputs one workgroup of the expand kernel makes (csrc/ivx_depth_expand.hip DEPTH_EXPAND_TILE; tests/test_depth_per_base_tile.py)
 DEPTH_EXPAND_TILE = 4096
 # merged steps one workgroup of the merge kernel makes (csrc/ivx_depth_merge.hip DEPTH_MERGE_TILE; tests/test_depth_merge_cpu.py)
 DEPTH_MERGE_TILE = 2048
+# bytes one thread / one workgroup of the text-CIGAR parser takes (csrc/ivx_cigar.hip CIGAR_B, CIGAR_TILE)
+CIGAR_B = 16
+CIGAR_TILE = 4096
 
 # slots of ivx_index_layout (include/ivx.h IVX_LAYOUT_*), in order
 LAYOUT_SLOTS = ["kind", "sh0", "nlev", "levrows", "rcells", "rcs", "nreg", "pk24", "slow", "fg", "fbits", "nroute_nreg", "lbuild"]
@@ -91,6 +95,14 @@ def lib():
                                 [C.c_uint64, C.POINTER(C.c_uint64)])
         L.ivx_depth_profile_build.restype = C.c_int
         L.ivx_depth_profile_build.argtypes = L.ivx_depth.argtypes[:18] + [C.POINTER(C.c_void_p)]
+        L.ivx_cigar_parse.restype = C.c_int
+        L.ivx_cigar_parse.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
+                                      C.c_uint64, C.POINTER(C.c_uint64)]
+        # (large, text_offsets, text) in place of (cigar_offsets, cigar_ops)
+        L.ivx_depth_text.restype = C.c_int
+        L.ivx_depth_text.argtypes = L.ivx_depth.argtypes[:6] + [C.c_int, C.c_void_p, C.c_void_p] + L.ivx_depth.argtypes[8:]
+        L.ivx_depth_profile_build_text.restype = C.c_int
+        L.ivx_depth_profile_build_text.argtypes = L.ivx_depth_text.argtypes[:19] + [C.POINTER(C.c_void_p)]
         L.ivx_depth_profile_free.restype = None
         L.ivx_depth_profile_free.argtypes = [C.c_void_p]
         L.ivx_depth_profile_steps.restype = C.c_uint64
@@ -619,15 +631,51 @@ class Ctx:
         return ok[:m2], os_[:m2], oe[:m2]
 
     # ---- g: depth ----
+    def cigar_parse(self, text_offsets, text):
+        """text CIGARs -> packed ops (include/ivx.h ivx_cigar_parse): text_offsets int32 (Utf8) or int64 (LargeUtf8)
+        [n_reads + 1], text uint8; numpy arrays or torch device tensors.  -> (offsets int32 [n_reads + 1], ops uint32)"""
+        mem = _mem_of(text_offsets, text)
+        if mem == MEM_DEVICE:
+            import torch
+            assert text_offsets.is_contiguous() and (text is None or text.is_contiguous())
+            large = int(text_offsets.dtype == torch.int64)
+            assert large or text_offsets.dtype == torch.int32
+            n_reads = max(int(text_offsets.numel()) - 1, 0)
+        else:
+            text_offsets = np.ascontiguousarray(text_offsets)
+            large = int(text_offsets.dtype == np.int64)
+            if not large:
+                text_offsets = np.ascontiguousarray(text_offsets, np.int32)
+            text = _np(text, np.uint8)
+            n_reads = max(len(text_offsets) - 1, 0)
+        head = (self.h, C.c_int(mem), C.c_int(large), _ptr(text_offsets), _ptr(text), C.c_uint64(n_reads))
+        m = C.c_uint64(0)
+        self._chk0(lib().ivx_cigar_parse(*head, None, None, 0, C.byref(m)))
+        cap = m.value
+        if mem == MEM_DEVICE:
+            import torch
+            off = torch.empty(n_reads + 1, dtype=torch.int32, device=text_offsets.device)
+            ops = torch.empty(max(cap, 1), dtype=torch.int32, device=text_offsets.device)
+        else:
+            off = np.empty(n_reads + 1, np.int32)
+            ops = np.empty(max(cap, 1), np.uint32)
+        if n_reads == 0:
+            off[:] = 0
+        self._chk0(lib().ivx_cigar_parse(*head, _ptr(off), _ptr(ops), C.c_uint64(max(cap, 1)), C.byref(m)))
+        return off, ops[:m.value]
+
     def depth(self, rkey=None, rpos=None, rflags=None, rmapq=None, cigar_offsets=None, cigar_ops=None,
               skey=None, sstart=None, send=None, sweight=None, n_keys=None, key_len=None, filter_flag=1796, min_mapq=0,
-              cap=None, outputs=(True, True, True, True)):
+              cap=None, outputs=(True, True, True, True), text_offsets=None, text=None):
         """coverage blocks of reads (rkey/rpos/rflags/rmapq + the Arrow Binary column cigar_offsets [bytes] / cigar_ops
         [packed u32 ops]) and of weighted segments (skey/sstart/send/sweight); numpy arrays or torch device tensors.
+        text_offsets (int32: Utf8, int64: LargeUtf8) / text (uint8) in place of cigar_offsets / cigar_ops: the cigar
+        column as text (ivx_depth_text).
         cap=None: a sizing call, then the fill call.  outputs: which of (key, start, end, coverage) to ask for.
         -> (key, start, end, coverage), None where not asked for."""
         args, mem, cols, n_keys = self._depth_args(rkey, rpos, rflags, rmapq, cigar_offsets, cigar_ops, skey, sstart, send, sweight,
-                                                   n_keys, key_len, filter_flag, min_mapq)
+                                                   n_keys, key_len, filter_flag, min_mapq, text_offsets, text)
+        fn = lib().ivx_depth if text_offsets is None else lib().ivx_depth_text
 
         def bufs(cap):
             if mem == MEM_DEVICE:
@@ -637,31 +685,49 @@ class Ctx:
             return [np.empty(cap, dt) if w else None for w, dt in zip(outputs, (np.uint32, np.uint32, np.uint32, np.int32))]
         if cap is None:
             m = C.c_uint64(0)
-            self._chk(lib().ivx_depth(self.h, *args, None, None, None, None, 0, C.byref(m)))
+            self._chk(fn(self.h, *args, None, None, None, None, 0, C.byref(m)))
             cap = max(m.value, 1)
         out = bufs(cap)
         m2 = C.c_uint64(0)
-        st = lib().ivx_depth(self.h, *args, *[_ptr(o) for o in out], cap, C.byref(m2))
+        st = fn(self.h, *args, *[_ptr(o) for o in out], cap, C.byref(m2))
         if st == ERR_CAPACITY:
             raise IvxError(st, f"{lib().ivx_last_error(self.h).decode()} (needed {m2.value})")
         self._chk(st)
         return tuple(None if o is None else o[:m2.value] for o in out)
 
     def depth_profile(self, rkey=None, rpos=None, rflags=None, rmapq=None, cigar_offsets=None, cigar_ops=None,
-                      skey=None, sstart=None, send=None, sweight=None, n_keys=None, key_len=None, filter_flag=1796, min_mapq=0):
+                      skey=None, sstart=None, send=None, sweight=None, n_keys=None, key_len=None, filter_flag=1796, min_mapq=0,
+                      text_offsets=None, text=None):
         """the depth profile of the same inputs as depth() -> DepthProfile (per-base output: .expand())"""
         args, mem, cols, n_keys = self._depth_args(rkey, rpos, rflags, rmapq, cigar_offsets, cigar_ops, skey, sstart, send, sweight,
-                                                   n_keys, key_len, filter_flag, min_mapq)
+                                                   n_keys, key_len, filter_flag, min_mapq, text_offsets, text)
         h = C.c_void_p()
-        self._chk(lib().ivx_depth_profile_build(self.h, *args, C.byref(h)))
+        fn = lib().ivx_depth_profile_build if text_offsets is None else lib().ivx_depth_profile_build_text
+        self._chk(fn(self.h, *args, C.byref(h)))
         dev = next(c for c in cols if c is not None).device if mem == MEM_DEVICE else None
         return DepthProfile(self, h, n_keys, dev)
 
     def _depth_args(self, rkey, rpos, rflags, rmapq, cigar_offsets, cigar_ops, skey, sstart, send, sweight, n_keys, key_len,
-                    filter_flag, min_mapq):
-        """the 17 input arguments of ivx_depth / ivx_depth_profile_build -> (ctypes args, mem, normalised columns, n_keys)"""
+                    filter_flag, min_mapq, text_offsets=None, text=None):
+        """the 17 input arguments of ivx_depth / ivx_depth_profile_build (18 with text_offsets / text, for the _text calls)
+        -> (ctypes args, mem, normalised columns, n_keys)"""
         cols = [rkey, rpos, rflags, rmapq, cigar_offsets, cigar_ops, skey, sstart, send, sweight, key_len]
-        mem = _mem_of(*cols)
+        if text_offsets is not None and (cigar_offsets is not None or cigar_ops is not None):
+            raise ValueError("give the cigar column as packed ops or as text, not both")
+        mem = _mem_of(*cols, text_offsets, text)
+        large = 0
+        if text_offsets is not None:
+            if mem == MEM_DEVICE:
+                import torch
+                assert text_offsets.is_contiguous() and (text is None or text.is_contiguous())
+                large = int(text_offsets.dtype == torch.int64)
+                assert large or text_offsets.dtype == torch.int32
+            else:
+                text_offsets = np.ascontiguousarray(text_offsets)
+                large = int(text_offsets.dtype == np.int64)
+                if not large:
+                    text_offsets = np.ascontiguousarray(text_offsets, np.int32)
+                text = _np(text, np.uint8)
         n_reads = 0 if rpos is None else (int(rpos.numel()) if _is_torch(rpos) else len(rpos))
         n_seg = 0 if sstart is None else (int(sstart.numel()) if _is_torch(sstart) else len(sstart))
         if mem == MEM_DEVICE:
@@ -682,9 +748,10 @@ class Ctx:
                         if len(kk):
                             mk = max(mk, int(kk.max()))
                 n_keys = mk + 1
-        args = (C.c_int(mem), _ptr(rkey), _ptr(rpos), _ptr(rflags), _ptr(rmapq), _ptr(cigar_offsets), _ptr(cigar_ops), n_reads,
+        cig = (_ptr(cigar_offsets), _ptr(cigar_ops)) if text_offsets is None else (C.c_int(large), _ptr(text_offsets), _ptr(text))
+        args = (C.c_int(mem), _ptr(rkey), _ptr(rpos), _ptr(rflags), _ptr(rmapq), *cig, n_reads,
                 _ptr(skey), _ptr(sstart), _ptr(send), _ptr(sweight), n_seg, n_keys, _ptr(key_len), int(filter_flag), int(min_mapq))
-        return args, mem, cols, n_keys
+        return args, mem, cols + [text_offsets, text], n_keys
 
     # ---- f3: compute::take of payload columns ----
     def take_fixed(self, src, idx, src_valid_bits=None, want_valid=True):

@@ -145,7 +145,11 @@ int brh_complement(brh_session *s, brh_batch table, brh_columns cols, brh_batch 
  * reads: a batch with the reference's column names (schema.rs:7-11): chrom Utf8 / LargeUtf8 / Utf8View; start, flags,
  *   mapping_quality UInt32; cigar Binary (packed u32 ops).  Rows with a NULL chrom or start are skipped; the validity of flags
  *   and mapping_quality is not read (events.rs:114-121).  A Utf8 cigar column is the error "depth: string CIGAR columns are
- *   not supported, use the binary CIGAR column".
+ *   not supported, use the binary CIGAR column" unless the session has brh_session_set_string_cigars on: then cigar may also be
+ *   Utf8 or LargeUtf8 ("5M3D5M"), parsed on the device (ivx.h ivx_cigar_parse: its token rules, its two divergences and its
+ *   errors); sliced arrays as for Binary, the validity of cigar is not read, and any other type is the error "depth: unsupported
+ *   data type <format> for column 'cigar'; expected Binary, Utf8 or LargeUtf8".  brh_depth_per_base_open and brh_depth_push_batch
+ *   follow the same rule.
  * prior (array == NULL: none): contig, pos_start, pos_end, coverage -- the output of an earlier call, fed in as weighted
  *   segments: that is how coverage accumulates over batches.
  * lengths (array == NULL: none): name Utf8, length (any integer type; clamped to 2^32-1) -- the reference's dense mode: events
@@ -277,6 +281,10 @@ int brh_check_contig_column(brh_session *s_or_null, brh_batch table, const char 
  * None of the reference's tests pins this (parity unpinned).  on = 1: a batch with a NULL contig is refused with an error
  * instead (the default of new sessions when BIO_STRICT_NULL_CONTIGS=1 is set). */
 int brh_session_set_strict_null_contigs(brh_session *s, int on);
+/* Text CIGARs for depth().  Default (on = 0): a Utf8 / LargeUtf8 cigar column is refused, see brh_depth.  on = 1: brh_depth,
+ * brh_depth_per_base_open and brh_depth_push_batch accept one and go through ivx_depth_text / ivx_depth_profile_build_text;
+ * Binary columns work as before. */
+int brh_session_set_string_cigars(brh_session *s, int on);
 
 /* BuildProbeJoinMetrics of the session's context under the reference's names (joins/utils.rs:399-453), and the device
  * memory the session may reserve (MemoryReservation::try_grow, interval_join.rs:614-639): ivx.h ivx_ctx_metrics /

@@ -351,6 +351,45 @@ ivx_status ivx_depth(ivx_ctx *ctx, int mem,
                      uint32_t *out_key, uint32_t *out_start, uint32_t *out_end, int32_t *out_cov,
                      uint64_t cap, uint64_t *n_out);
 
+/* ---- g-text: the cigar column as TEXT.  The reference's pileup crate reads `cigar` as Binary (packed ops, above) or as
+ *      Utf8 ("5M3D5M": events.rs:42-55, :138-165, :295-321; cigar.rs:78-168); ivx_cigar_parse turns the bytes of an Arrow
+ *      Utf8 (large = 0: int32 offsets) or LargeUtf8 (large = 1: int64 offsets) column into the packed form of ivx_depth, on
+ *      the device, in one segmented scan over the bytes: no thread walks a read.  text_offsets[n_reads+1] are the column's
+ *      offsets (element 0 need not be 0), text its data buffer.
+ *      TOKENS, per read and over BYTES (cigar.rs:141-168): every byte that is not '0'..'9' ends a token whose length is the
+ *      decimal value of the digits immediately before it, back to the previous non-digit byte or the read's first byte;
+ *      no digits give 0, a value >= 2^32 gives 0 (Rust's parse::<u32>() error -> 0), leading zeros are fine.  M I D N S H
+ *      P = X emit an op with BAM's codes 0..8; any other non-digit byte ('*', '+', ' ', 'B', a byte >= 0x80) only separates.
+ *      Digits after a read's last non-digit byte are dropped (they never reach the next read).  A read without an emitted op
+ *      ("*", "", "12") has zero ops, which ivx_depth skips: the reference's output.
+ *      OUTPUT: out_offsets[n_reads+1] (nullable) = 4 * (ops emitted by the reads before i), element 0 = 0; out_ops (nullable)
+ *      = len << 4 | code in text order; *n_ops = the op count.  The capacity protocol of ivx_depth: cap_ops = 0 with NULL
+ *      outputs only counts; cap_ops < *n_ops is IVX_ERR_CAPACITY with *n_ops = the size needed and no op written;
+ *      out_offsets is written whenever it is given.
+ *      IVX_ERR_INVALID, found on the device before a byte is read through an offset: offsets that are negative or decrease;
+ *      2^32 or more bytes between the first and the last offset; more than 2^29-1 ops.  DIVERGENCES from the reference: an
+ *      emitted op with 2^28 <= len <= 2^32-1 cannot be packed (nor held by BAM) and is IVX_ERR_INVALID, the text naming the
+ *      lowest such read index -- checked on every read, whatever a later filter keeps, and in a counting call too; bytes >=
+ *      0x80 are separators, where the reference panics when it slices inside a multi-byte character.
+ *      Synchronises (it needs the count); drops the state a sizing call of another operation left on the context; is not
+ *      counted in ivx_metrics; n_reads = 0 is a no-op with *n_ops = 0. */
+ivx_status ivx_cigar_parse(ivx_ctx *ctx, int mem, int large, const void *text_offsets, const uint8_t *text, uint64_t n_reads,
+                           int32_t *out_offsets /* [n_reads+1], nullable */, uint32_t *out_ops /* nullable */,
+                           uint64_t cap_ops, uint64_t *n_ops);
+/*      ivx_depth with (large, text_offsets, text) in place of (cigar_offsets, cigar_ops): the text is staged (IVX_MEM_HOST:
+ *      the bytes between the first and the last host offset), parsed into context scratch, and ivx_depth runs on the result.
+ *      Contract, errors, metrics and memory-limit accounting are those of ivx_depth (the scratch of the parse counts against
+ *      the limit); the IVX_ERR_INVALID cases of ivx_cigar_parse come on top. */
+ivx_status ivx_depth_text(ivx_ctx *ctx, int mem,
+                          const uint32_t *rkey /* nullable */, const uint32_t *rpos,
+                          const uint32_t *rflags /* nullable */, const uint32_t *rmapq /* nullable */,
+                          int large, const void *text_offsets, const uint8_t *text, uint64_t n_reads,
+                          const uint32_t *skey /* nullable */, const uint32_t *sstart, const uint32_t *send,
+                          const int32_t *sweight /* nullable */, uint64_t n_seg,
+                          uint32_t n_keys, const uint32_t *key_len /* nullable */, uint32_t filter_flag, uint32_t min_mapq,
+                          uint32_t *out_key, uint32_t *out_start, uint32_t *out_end, int32_t *out_cov,
+                          uint64_t cap, uint64_t *n_out);
+
 /* ---- g': per-base depth(), the pileup crate's per_base = true form (bio-function-pileup table_function.rs:97-123,
  *      coverage.rs:271-365 PerBaseEmitter, physical_exec.rs:404-414, :517-548): one (position, coverage Int16) row per base.
  *      It cannot be made from ivx_depth's blocks -- a key whose coverage never returns to 0 loses its last open block, and a
@@ -374,6 +413,15 @@ ivx_status ivx_depth_profile_build(ivx_ctx *ctx, int mem,
                                    const int32_t *sweight /* nullable */, uint64_t n_seg,
                                    uint32_t n_keys, const uint32_t *key_len /* nullable */, uint32_t filter_flag, uint32_t min_mapq,
                                    ivx_index **out);
+/*      ivx_depth_profile_build with the cigar column as text: see ivx_depth_text. */
+ivx_status ivx_depth_profile_build_text(ivx_ctx *ctx, int mem,
+                                        const uint32_t *rkey /* nullable */, const uint32_t *rpos,
+                                        const uint32_t *rflags /* nullable */, const uint32_t *rmapq /* nullable */,
+                                        int large, const void *text_offsets, const uint8_t *text, uint64_t n_reads,
+                                        const uint32_t *skey /* nullable */, const uint32_t *sstart, const uint32_t *send,
+                                        const int32_t *sweight /* nullable */, uint64_t n_seg,
+                                        uint32_t n_keys, const uint32_t *key_len /* nullable */, uint32_t filter_flag, uint32_t min_mapq,
+                                        ivx_index **out);
 /*      Same contract as ivx_index_free (synchronise every context that expanded it in device mode first). */
 void       ivx_depth_profile_free(ivx_index *profile);
 uint64_t   ivx_depth_profile_steps(const ivx_index *profile);

@@ -94,6 +94,20 @@ extern "C" {
                      n_keys: u32, key_len: *const u32, filter_flag: u32, min_mapq: u32,
                      out_key: *mut u32, out_start: *mut u32, out_end: *mut u32, out_cov: *mut i32,
                      cap: u64, n_out: *mut u64) -> i32;
+    // text CIGARs: an Arrow Utf8 (large = 0, int32 offsets) / LargeUtf8 (large = 1, int64 offsets) column parsed on the device
+    pub fn ivx_cigar_parse(ctx: *mut IvxCtx, mem: i32, large: i32, text_offsets: *const c_void, text: *const u8, n_reads: u64,
+                           out_offsets: *mut i32, out_ops: *mut u32, cap_ops: u64, n_ops: *mut u64) -> i32;
+    pub fn ivx_depth_text(ctx: *mut IvxCtx, mem: i32, rkey: *const u32, rpos: *const u32, rflags: *const u32, rmapq: *const u32,
+                          large: i32, text_offsets: *const c_void, text: *const u8, n_reads: u64,
+                          skey: *const u32, sstart: *const u32, send: *const u32, sweight: *const i32, n_seg: u64,
+                          n_keys: u32, key_len: *const u32, filter_flag: u32, min_mapq: u32,
+                          out_key: *mut u32, out_start: *mut u32, out_end: *mut u32, out_cov: *mut i32,
+                          cap: u64, n_out: *mut u64) -> i32;
+    pub fn ivx_depth_profile_build_text(ctx: *mut IvxCtx, mem: i32, rkey: *const u32, rpos: *const u32, rflags: *const u32,
+                                        rmapq: *const u32, large: i32, text_offsets: *const c_void, text: *const u8, n_reads: u64,
+                                        skey: *const u32, sstart: *const u32, send: *const u32, sweight: *const i32, n_seg: u64,
+                                        n_keys: u32, key_len: *const u32, filter_flag: u32, min_mapq: u32,
+                                        out: *mut *mut IvxIndex) -> i32;
     // per-base depth(): a depth profile is an IvxIndex of kind IVX_KIND_DEPTH_PROFILE; out_cov of expand is int16_t[n]
     pub fn ivx_depth_profile_build(ctx: *mut IvxCtx, mem: i32, rkey: *const u32, rpos: *const u32, rflags: *const u32,
                                    rmapq: *const u32, cigar_offsets: *const i32, cigar_ops: *const u32, n_reads: u64,
