@@ -368,9 +368,41 @@ class Session:
         finally:
             lib().brh_depth_per_base_close(h)
 
+    def depth_regions(self, reads, regions, prior=None, lengths=None, zero_based=False, end_exclusive=False, thresholds=(),
+                      cols=DEFAULT_COLS, filter_flag=1796, min_mapq=0):
+        """depth summarised per row of `regions` (contig, start, end as `cols` names them; ends inclusive, or BED-style
+        half-open with end_exclusive): -> the regions table with bases Int64 (positions counted), sum Int64 (coverage summed
+        over them: mean depth = sum / bases) and one bases_ge_<t> Int64 per threshold (positions with coverage >= t)
+        appended.  reads / prior / lengths as for depth(); with lengths the positions are those depth_per_base() emits."""
+        tabs = [_Exported(t) if t is not None else None for t in (reads, prior, lengths, regions)]
+        try:
+            b = [t.c if t is not None else _Batch(None, None) for t in tabs]
+            return _regions_call(self, regions, thresholds, lambda *outs: lib().brh_depth_regions(
+                self.h, b[0], b[1], b[2], b[3], _cols(cols), C.c_int(int(bool(zero_based))), C.c_int(int(bool(end_exclusive))),
+                C.c_uint32(int(filter_flag)), C.c_uint32(int(min_mapq)), *outs))
+        finally:
+            for t in tabs:
+                if t is not None:
+                    t.close()
+
     def depth_stream(self, lengths=None, filter_flag=1796, min_mapq=0):
         """depth() over a stream of read batches (brh_depth_push): -> DepthStream"""
         return DepthStream(self, lengths, filter_flag, min_mapq)
+
+
+def _regions_call(session, regions, thresholds, call):
+    """the thresholds and the output structs of brh_depth_regions / brh_depth_push_regions -> regions + the summary columns"""
+    thr = [int(t) for t in thresholds]
+    n = len(thr)
+    cthr = (C.c_int32 * max(n, 1))(*thr)
+    bases, total = _out(), _out()
+    ge, ge_s = (_ArrowArray * max(n, 1))(), (_ArrowSchema * max(n, 1))()
+    session._chk(call(cthr, C.c_uint32(n), C.byref(bases[0]), C.byref(bases[1]), C.byref(total[0]), C.byref(total[1]),
+                      ge if n else None, ge_s if n else None))
+    out = regions.append_column("bases", _import(*bases)).append_column("sum", _import(*total))
+    for j, t in enumerate(thr):
+        out = out.append_column(f"bases_ge_{t}", _import(ge[j], ge_s[j]))
+    return out
 
 
 class DepthStream:
@@ -395,6 +427,15 @@ class DepthStream:
             self.session._chk(lib().brh_depth_push_batch(self.h, T.c))
         finally:
             T.close()
+
+    def depth_regions(self, regions, zero_based=False, end_exclusive=False, thresholds=(), cols=DEFAULT_COLS):
+        """Session.depth_regions over everything pushed so far; the stream stays open"""
+        R = _Exported(regions)
+        try:
+            return _regions_call(self.session, regions, thresholds, lambda *outs: lib().brh_depth_push_regions(
+                self.h, R.c, _cols(cols), C.c_int(int(bool(zero_based))), C.c_int(int(bool(end_exclusive))), *outs))
+        finally:
+            R.close()
 
     def finish(self):
         """-> contig Utf8, pos_start Int32, pos_end Int32, coverage Int16 of everything pushed"""

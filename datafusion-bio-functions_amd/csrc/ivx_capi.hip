@@ -1558,6 +1558,81 @@ extern "C" ivx_status ivx_depth_profile_blocks(ivx_ctx *ctx, const ivx_index *p,
     return IVX_OK;
 }
 
+// the checks the two summary calls share, and their three output columns
+static ivx_status summary_check(ivx_ctx *ctx, const ivx_index *p, int mem, const int32_t *thresholds, uint32_t n_thr,
+                                const int64_t *out_len, const int64_t *out_sum, const int64_t *out_ge)
+{
+    IVX_TRY(check_profile_args(ctx, p, mem));
+    if (n_thr > IVX_DEPTH_MAX_THRESHOLDS) return ctx->fail(IVX_ERR_INVALID, "depth profile: more than 8 thresholds");
+    if (n_thr && !thresholds) return ctx->fail(IVX_ERR_INVALID, "depth profile: null thresholds");
+    if (mem == IVX_MEM_DEVICE && ((((uintptr_t)out_len) | ((uintptr_t)out_sum) | ((uintptr_t)out_ge)) & 7u))
+        return ctx->fail(IVX_ERR_INVALID, "depth profile: output pointer not aligned to its element size");
+    ctx->sub_plan.valid = false; ctx->join_plan.valid = false;
+    return IVX_OK;
+}
+
+extern "C" ivx_status ivx_depth_profile_summarize(ivx_ctx *ctx, const ivx_index *p, int mem,
+                                                  const uint32_t *qkey, const uint32_t *qstart, const uint32_t *qend, uint64_t n,
+                                                  uint32_t pos_lo, const uint32_t *key_hi, int skip_pos0,
+                                                  const int32_t *thresholds, uint32_t n_thr,
+                                                  int64_t *out_len, int64_t *out_sum, int64_t *out_ge)
+{
+    if (!ctx) return IVX_ERR_INVALID;
+    IVX_TRY(summary_check(ctx, p, mem, thresholds, n_thr, out_len, out_sum, out_ge));
+    if (n && (!qstart || !qend)) return ctx->fail(IVX_ERR_INVALID, "null coordinate column");
+    if (mem == IVX_MEM_DEVICE && ((((uintptr_t)qkey) | ((uintptr_t)qstart) | ((uintptr_t)qend) | ((uintptr_t)key_hi)) & 3u))
+        return ctx->fail(IVX_ERR_INVALID, "depth profile: input pointer not aligned to its element size");
+    CallMetrics cm(ctx, false, n);
+    if (n == 0) return IVX_OK;
+    const u32 *dk, *ds, *de, *dh; i64 *ol, *os, *og;
+    IVX_TRY(stage_in(ctx, mem, WS_IN_KEY, qkey, n, &dk));
+    IVX_TRY(stage_in(ctx, mem, WS_IN_START, qstart, n, &ds));
+    IVX_TRY(stage_in(ctx, mem, WS_IN_END, qend, n, &de));
+    IVX_TRY(stage_in(ctx, mem, WS_IN_KEYLEN, key_hi, p->nkeys, &dh));
+    IVX_TRY(stage_out(ctx, mem, WS_OUT_A, out_len, n, &ol));
+    IVX_TRY(stage_out(ctx, mem, WS_OUT_B, out_sum, n, &os));
+    IVX_TRY(stage_out(ctx, mem, WS_OUT_C, out_ge, (u64)n_thr * n, &og));
+    {
+        KernelTimer t(ctx);
+        IVX_TRY(ivx_depth_regions_device(ctx, p->dp, p->nkeys, dk, ds, de, n, pos_lo, dh, skip_pos0 != 0, thresholds, n_thr, ol, os, og));
+    }
+    cm.out(n);
+    IVX_TRY(copy_out(ctx, mem, out_len, ol, n));
+    IVX_TRY(copy_out(ctx, mem, out_sum, os, n));
+    IVX_TRY(copy_out(ctx, mem, out_ge, og, (u64)n_thr * n));
+    if (mem == IVX_MEM_HOST) IVX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return IVX_OK;
+}
+
+extern "C" ivx_status ivx_depth_profile_windows(ivx_ctx *ctx, const ivx_index *p, int mem, uint32_t key,
+                                                uint32_t first_pos, uint32_t last_pos, uint32_t width, uint64_t n, int skip_pos0,
+                                                const int32_t *thresholds, uint32_t n_thr,
+                                                int64_t *out_len, int64_t *out_sum, int64_t *out_ge)
+{
+    if (!ctx) return IVX_ERR_INVALID;
+    IVX_TRY(summary_check(ctx, p, mem, thresholds, n_thr, out_len, out_sum, out_ge));
+    if (width == 0) return ctx->fail(IVX_ERR_INVALID, "depth profile: window width 0");
+    if (key >= p->nkeys) return ctx->fail(IVX_ERR_INVALID, "depth profile: key id >= n_keys");
+    if (n && (n - 1) > (0xFFFFFFFFull - first_pos) / width)
+        return ctx->fail(IVX_ERR_INVALID, "depth profile: a window starts beyond position 2^32 - 1");
+    CallMetrics cm(ctx, false, n);
+    if (n == 0) return IVX_OK;
+    i64 *ol, *os, *og;
+    IVX_TRY(stage_out(ctx, mem, WS_OUT_A, out_len, n, &ol));
+    IVX_TRY(stage_out(ctx, mem, WS_OUT_B, out_sum, n, &os));
+    IVX_TRY(stage_out(ctx, mem, WS_OUT_C, out_ge, (u64)n_thr * n, &og));
+    {
+        KernelTimer t(ctx);
+        IVX_TRY(ivx_depth_windows_device(ctx, p->dp, key, first_pos, last_pos, width, n, skip_pos0 != 0, thresholds, n_thr, ol, os, og));
+    }
+    cm.out(n);
+    IVX_TRY(copy_out(ctx, mem, out_len, ol, n));
+    IVX_TRY(copy_out(ctx, mem, out_sum, os, n));
+    IVX_TRY(copy_out(ctx, mem, out_ge, og, (u64)n_thr * n));
+    if (mem == IVX_MEM_HOST) IVX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return IVX_OK;
+}
+
 extern "C" ivx_status ivx_take_fixed(ivx_ctx *ctx, int mem, const void *src, uint32_t width, uint64_t n_src,
                                      const uint8_t *src_valid_bits, const uint32_t *idx, uint64_t n, void *out, uint8_t *out_valid)
 {

@@ -351,5 +351,12 @@ ivx_status ivx_depth_expand_device(ivx_ctx *ctx, const DepthProfileView &dp, u32
 // ivx_depth_merge.hip: ix (from ivx_depth_profile_begin, nkeys = the larger of the two) = a + b; the coverage blocks of a profile
 ivx_status ivx_depth_profile_merge_device(ivx_ctx *ctx, const DepthProfileView &a, u32 nka, const DepthProfileView &b, u32 nkb, ivx_index *ix);
 ivx_status ivx_depth_profile_blocks_device(ivx_ctx *ctx, const DepthProfileView &dp, u32 *ok, u32 *os, u32 *oe, i32 *oc, u64 cap, u64 *n_out);
+// ivx_depth_regions.hip: bases, coverage sum and bases at or above each threshold per region / per fixed-width window of a
+// profile (thresholds: host memory; out_ge threshold-major [n_thr * n]; any output may be null)
+ivx_status ivx_depth_regions_device(ivx_ctx *ctx, const DepthProfileView &dp, u32 nkeys, const u32 *qkey, const u32 *qs, const u32 *qe, u64 n,
+                                    u32 pos_lo, const u32 *key_hi, int skip_pos0, const i32 *thresholds, u32 n_thr,
+                                    i64 *out_len, i64 *out_sum, i64 *out_ge);
+ivx_status ivx_depth_windows_device(ivx_ctx *ctx, const DepthProfileView &dp, u32 key, u32 first_pos, u32 last_pos, u32 width, u64 n,
+                                    int skip_pos0, const i32 *thresholds, u32 n_thr, i64 *out_len, i64 *out_sum, i64 *out_ge);
 
 ivx_status ivx_index_alloc(ivx_ctx *ctx, ivx_index *ix, size_t bytes, void **out);

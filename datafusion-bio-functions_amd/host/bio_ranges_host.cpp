@@ -8,6 +8,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <deque>
+#include <functional>
 #include <memory>
 #include <string>
 #include <string_view>
@@ -993,6 +994,7 @@ struct brh_depth_push {
     std::unordered_map<std::string, uint32_t> ids;
     std::vector<uint32_t> key_len;                      // dense only
     std::vector<ivx_index *> stack;                     // profiles not yet merged, the oldest first
+    uint32_t built_nk = 0;                              // the most keys a profile of the stack was built with
     uint32_t nk() const { return (uint32_t)std::max<size_t>(names.size(), 1); }
 };
 
@@ -1026,6 +1028,7 @@ int depth_push_merge_all(brh_depth_push *dp)
                                                       dp->filter_flag, dp->min_mapq, &e);
         if (st != IVX_OK) return fail_ivx(dp->s, st);
         dp->stack.push_back(e);
+        dp->built_nk = std::max(dp->built_nk, dp->nk());
     }
     return 0;
 }
@@ -1091,6 +1094,7 @@ extern "C" int brh_depth_push_batch(brh_depth_push *dp, brh_batch reads)
                                      dp->filter_flag, dp->min_mapq, &p);
     if (st != IVX_OK) return fail_ivx(s, st);
     dp->stack.push_back(p);
+    dp->built_nk = std::max(dp->built_nk, dp->nk());
     // a binary counter: merge while the new top has at least half the steps of the profile below it
     while (dp->stack.size() > 1 &&
            2 * ivx_depth_profile_steps(dp->stack.back()) >= ivx_depth_profile_steps(dp->stack[dp->stack.size() - 2]))
@@ -1165,6 +1169,125 @@ extern "C" void brh_depth_push_close(brh_depth_push *dp)
     if (!dp) return;
     for (ivx_index *p : dp->stack) ivx_depth_profile_free(p);
     delete dp;
+}
+
+// ---- depth region summaries (ivx_depth_profile_summarize): bases, coverage sum and bases at or above each threshold per row
+// of a regions table -- mean depth per target, bases at 10x / 20x / 30x (samtools bedcov, mosdepth --by / --thresholds)
+namespace {
+
+// one coordinate column as int64, a UInt64 beyond that saturated (every value is clamped to [0, 2^32-1] afterwards anyway)
+int region_coords(brh_session *s, const PosCol &p, std::vector<int64_t> *out)
+{
+    if (null_count(p.a) > 0) return fail(s, "coordinate column contains null values; requires non-null coordinates");
+    const int64_t n = p.a->length, o = p.a->offset;
+    out->resize((size_t)n);
+    for (int64_t i = 0; i < n; i++) {
+        switch (p.fmt) {
+        case 'i': (*out)[i] = ((const int32_t *)p.a->buffers[1])[o + i]; break;
+        case 'l': (*out)[i] = ((const int64_t *)p.a->buffers[1])[o + i]; break;
+        case 'I': (*out)[i] = ((const uint32_t *)p.a->buffers[1])[o + i]; break;
+        default: { const uint64_t v = ((const uint64_t *)p.a->buffers[1])[o + i]; (*out)[i] = v > (uint64_t)INT64_MAX ? INT64_MAX : (int64_t)v; }
+        }
+    }
+    return 0;
+}
+
+// The regions of `regions` summarised over `profile`, whose keys are the ids `id_of` gives (IVX_NULL_IDX, or an id of
+// n_keys or more: a contig the profile does not know, coverage 0 everywhere).  key_len (null: no length table) gives the domain
+// the per-base rows have: [0, len - 1] when zero_based, else [1, len] without the step at position 0.
+int summarize_regions(brh_session *s, const ivx_index *profile, uint32_t n_keys, const std::function<uint32_t(std::string_view)> &id_of,
+                      const std::vector<uint32_t> *key_len, int zero_based, brh_batch regions, brh_columns cols, int end_exclusive,
+                      const int32_t *thresholds, uint32_t n_thr,
+                      ArrowArray *bases, ArrowSchema *bases_schema, ArrowArray *sum, ArrowSchema *sum_schema, ArrowArray *ge, ArrowSchema *ge_schemas)
+{
+    if (!regions.array || !regions.schema) return fail(s, "depth_regions: null regions batch");
+    if (cols.n_keys != 1 || !cols.keys || !cols.start || !cols.end) return fail(s, "depth_regions: the regions take one contig, one start and one end column");
+    if (n_thr > IVX_DEPTH_MAX_THRESHOLDS) return fail(s, "depth_regions: more than 8 thresholds");
+    if (n_thr && (!thresholds || !ge || !ge_schemas)) return fail(s, "depth_regions: null thresholds or threshold outputs");
+    StrCol contig; PosCol ps, pe;
+    std::vector<int64_t> s64, e64;
+    if (get_contig(s, regions, cols.keys[0], &contig) || get_pos(s, regions, cols.start, "start", &ps) || get_pos(s, regions, cols.end, "end", &pe) ||
+        region_coords(s, ps, &s64) || region_coords(s, pe, &e64)) return 1;
+    const uint64_t n = (uint64_t)regions.array->length;
+    // ---- closed u32 regions; a region that is empty whatever the coverage gets the skip mark, an unknown contig is answered here
+    std::vector<uint32_t> qk(n ? n : 1), qs(n ? n : 1), qe(n ? n : 1);
+    std::vector<uint8_t> unknown(n ? n : 1, 0);
+    const uint32_t pos_lo = (key_len && !zero_based) ? 1u : 0u;
+    std::vector<uint32_t> key_hi;
+    if (key_len) {
+        key_hi.assign(std::max<size_t>(key_len->size(), n_keys), 0);
+        for (size_t k = 0; k < key_len->size(); k++) key_hi[k] = zero_based ? ((*key_len)[k] ? (*key_len)[k] - 1u : 0u) : (*key_len)[k];
+    }
+    std::string_view last; uint32_t last_id = IVX_NULL_IDX; bool have = false;
+    for (uint64_t i = 0; i < n; i++) {
+        int64_t a = s64[i], b = e64[i];
+        bool empty = false;
+        if (end_exclusive) { if (b <= a) empty = true; else b -= 1; }
+        a = std::min<int64_t>(std::max<int64_t>(a, 0), (int64_t)UINT32_MAX);
+        b = std::min<int64_t>(std::max<int64_t>(b, 0), (int64_t)UINT32_MAX);
+        qs[i] = (uint32_t)a; qe[i] = (uint32_t)b;
+        uint32_t k = IVX_NULL_IDX;
+        if (!contig.null_at((int64_t)i)) {
+            const std::string_view name = contig.at((int64_t)i);
+            if (!have || name != last) { last_id = id_of(name); last = name; have = true; }
+            k = last_id;
+        }
+        if (k >= n_keys) { unknown[i] = !empty && b >= a; k = IVX_NULL_IDX; }
+        else if (empty || (key_len && zero_based && (*key_len)[k] == 0)) k = IVX_NULL_IDX;        // (a contig of length 0 has no position)
+        qk[i] = k;
+    }
+    std::vector<int64_t> ol(n ? n : 1, 0), os(n ? n : 1, 0), og((size_t)n_thr * n + 1, 0);
+    const ivx_status st = ivx_depth_profile_summarize(s->ctx, profile, IVX_MEM_HOST, qk.data(), qs.data(), qe.data(), n, pos_lo,
+                                                      key_len ? key_hi.data() : nullptr, key_len && !zero_based, thresholds, n_thr,
+                                                      ol.data(), os.data(), n_thr ? og.data() : nullptr);
+    if (st != IVX_OK) return fail_ivx(s, st);
+    for (uint64_t i = 0; i < n; i++) {
+        if (!unknown[i]) continue;
+        ol[i] = (int64_t)qe[i] - (int64_t)qs[i] + 1;
+        for (uint32_t j = 0; j < n_thr; j++) og[(size_t)j * n + i] = thresholds[j] <= 0 ? ol[i] : 0;
+    }
+    make_primitive<int64_t>(bases, ol.data(), (int64_t)n, nullptr); make_schema(bases_schema, "l", "bases", false);
+    make_primitive<int64_t>(sum, os.data(), (int64_t)n, nullptr); make_schema(sum_schema, "l", "sum", false);
+    for (uint32_t j = 0; j < n_thr; j++) {
+        make_primitive<int64_t>(&ge[j], og.data() + (size_t)j * n, (int64_t)n, nullptr);
+        make_schema(&ge_schemas[j], "l", ("bases_ge_" + std::to_string(thresholds[j])).c_str(), false);
+    }
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int brh_depth_regions(brh_session *s, brh_batch reads, brh_batch prior, brh_batch lengths, brh_batch regions, brh_columns region_cols,
+                                 int zero_based, int end_exclusive, uint32_t filter_flag, uint32_t min_mapq,
+                                 const int32_t *thresholds, uint32_t n_thr,
+                                 ArrowArray *bases, ArrowSchema *bases_schema, ArrowArray *sum, ArrowSchema *sum_schema,
+                                 ArrowArray *ge, ArrowSchema *ge_schemas)
+{
+    if (!s) return 1;
+    DepthInputs in;
+    if (in.load(s, reads, prior, lengths)) return 1;
+    IndexGuard g;
+    const ivx_status st = in.profile(s->ctx, in.has_prior ? in.skey.data() : nullptr, in.ss.data(), in.se.data(), in.has_prior ? in.sw.data() : nullptr,
+                                     in.n_seg, in.nk, in.has_len ? in.key_len.data() : nullptr, filter_flag, min_mapq, &g.ix);
+    if (st != IVX_OK) return fail_ivx(s, st);
+    const uint32_t known = (uint32_t)in.dict.names.size();           // (an empty dictionary: key 0 stands for no contig)
+    return summarize_regions(s, g.ix, known, [&](std::string_view k) { return in.dict.id_of(k); }, in.has_len ? &in.key_len : nullptr, zero_based,
+                             regions, region_cols, end_exclusive, thresholds, n_thr, bases, bases_schema, sum, sum_schema, ge, ge_schemas);
+}
+
+extern "C" int brh_depth_push_regions(brh_depth_push *dp, brh_batch regions, brh_columns region_cols, int zero_based, int end_exclusive,
+                                      const int32_t *thresholds, uint32_t n_thr,
+                                      ArrowArray *bases, ArrowSchema *bases_schema, ArrowArray *sum, ArrowSchema *sum_schema,
+                                      ArrowArray *ge, ArrowSchema *ge_schemas)
+{
+    if (!dp) return 1;
+    brh_session *s = dp->s;
+    if (depth_push_check(dp) || depth_push_merge_all(dp)) return 1;            // the merged profile stays the stack's only entry
+    const uint32_t known = std::min<uint32_t>((uint32_t)dp->names.size(), dp->built_nk);
+    return summarize_regions(s, dp->stack[0], known,
+                             [&](std::string_view k) { auto it = dp->ids.find(std::string(k)); return it == dp->ids.end() ? IVX_NULL_IDX : it->second; },
+                             dp->dense ? &dp->key_len : nullptr, zero_based, regions, region_cols, end_exclusive, thresholds, n_thr,
+                             bases, bases_schema, sum, sum_schema, ge, ge_schemas);
 }
 
 // ---- f3: payload gather

@@ -32,12 +32,17 @@ SYMBOLS = [
     "ivx_depth_profile_build", "ivx_depth_profile_free", "ivx_depth_profile_steps", "ivx_depth_profile_device_bytes",
     "ivx_depth_profile_read", "ivx_depth_profile_expand", "ivx_depth_profile_merge", "ivx_depth_profile_blocks",
     "ivx_cigar_parse", "ivx_depth_text", "ivx_depth_profile_build_text",
+    "ivx_depth_profile_summarize", "ivx_depth_profile_windows",
 ]
 
 # outputs one workgroup of the expand kernel makes (csrc/ivx_depth_expand.hip DEPTH_EXPAND_TILE; tests/test_depth_per_base_tile.py)
 DEPTH_EXPAND_TILE = 4096
 # merged steps one workgroup of the merge kernel makes (csrc/ivx_depth_merge.hip DEPTH_MERGE_TILE; tests/test_depth_merge_cpu.py)
 DEPTH_MERGE_TILE = 2048
+# steps one tile aggregate of the region summaries covers (csrc/ivx_depth_regions.hip DEPTH_REGION_TILE; tests/test_depth_regions_cpu.py)
+DEPTH_REGION_TILE = 1024
+# thresholds one summary call takes (include/ivx.h IVX_DEPTH_MAX_THRESHOLDS)
+DEPTH_MAX_THRESHOLDS = 8
 # bytes one thread / one workgroup of the text-CIGAR parser takes (csrc/ivx_cigar.hip CIGAR_B, CIGAR_TILE)
 CIGAR_B = 16
 CIGAR_TILE = 4096
@@ -117,6 +122,12 @@ def lib():
         L.ivx_depth_profile_merge.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
         L.ivx_depth_profile_blocks.restype = C.c_int
         L.ivx_depth_profile_blocks.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_uint64, C.POINTER(C.c_uint64)]
+        L.ivx_depth_profile_summarize.restype = C.c_int
+        L.ivx_depth_profile_summarize.argtypes = ([C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 3 + [C.c_uint64, C.c_uint32, C.c_void_p, C.c_int,
+                                                  C.c_void_p, C.c_uint32] + [C.c_void_p] * 3)
+        L.ivx_depth_profile_windows.restype = C.c_int
+        L.ivx_depth_profile_windows.argtypes = ([C.c_void_p, C.c_void_p, C.c_int] + [C.c_uint32] * 4 + [C.c_uint64, C.c_int, C.c_void_p, C.c_uint32] +
+                                                [C.c_void_p] * 3)
         # test hook of csrc/ivx_sweep.hip (not in include/ivx.h): what subtract's count pass did (tests/test_gpu_subtract_edges.py)
         L.ivx_debug_subtract_paths.restype = C.c_int
         L.ivx_debug_subtract_paths.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
@@ -273,6 +284,44 @@ class DepthProfile:
             raise IvxError(st, f"{lib().ivx_last_error(ctx.h).decode()} (needed {m2.value})")
         ctx._chk(st)
         return tuple(None if o is None else o[:m2.value] for o in out)
+
+    def _summary_out(self, n, n_thr, device, dev, outputs):
+        shapes = ((n,), (n,), (n_thr, n))
+        if device:
+            import torch
+            return [torch.empty(sh, dtype=torch.int64, device=dev) if w else None for w, sh in zip(outputs, shapes)]
+        return [np.empty(sh, np.int64) if w else None for w, sh in zip(outputs, shapes)]
+
+    def summarize(self, key, start, end, thresholds=(), pos_lo=0, key_hi=None, skip_pos0=False, ctx=None, outputs=(True, True, True)):
+        """per region [start[i], end[i]] (closed, clipped to the key's domain [pos_lo, key_hi[key]]) of key[i] (None: key 0)
+        -> (bases int64[n], coverage sum int64[n], bases at or above each threshold int64[n_thr, n]); None where `outputs`
+        does not ask.  numpy arrays, or torch device tensors (then the results are device tensors and the call may return
+        with kernels in flight); a mix is a ValueError."""
+        ctx = ctx or self.ctx
+        mem = _mem_of(key, start, end, key_hi)
+        thr = np.ascontiguousarray(thresholds, dtype=np.int32).reshape(-1)
+        if mem == MEM_DEVICE:
+            assert all(a is None or a.is_contiguous() for a in (key, start, end, key_hi))
+            n, dev = int(start.numel()), start.device
+        else:
+            key, start, end, key_hi = (_np(a, np.uint32) for a in (key, start, end, key_hi))
+            n, dev = len(start), None
+        out = self._summary_out(n, len(thr), mem == MEM_DEVICE, dev, outputs)
+        ctx._chk(lib().ivx_depth_profile_summarize(ctx.h, self.h, mem, _ptr(key), _ptr(start), _ptr(end), n, int(pos_lo), _ptr(key_hi),
+                                                   int(bool(skip_pos0)), _ptr(thr), len(thr), *[_ptr(o) for o in out]))
+        return tuple(out)
+
+    def windows(self, key, first_pos, last_pos, width, n=None, thresholds=(), skip_pos0=False, device=False, ctx=None, outputs=(True, True, True)):
+        """the same three outputs for the windows [first_pos + i * width, + width - 1] of `key`, cut at last_pos; n defaults
+        to the count that covers [first_pos, last_pos].  numpy arrays, or torch device tensors with device=True."""
+        ctx = ctx or self.ctx
+        if n is None:
+            n = (int(last_pos) - int(first_pos)) // int(width) + 1 if int(last_pos) >= int(first_pos) and int(width) > 0 else 0
+        thr = np.ascontiguousarray(thresholds, dtype=np.int32).reshape(-1)
+        out = self._summary_out(int(n), len(thr), device, self.device or "cuda:0", outputs)
+        ctx._chk(lib().ivx_depth_profile_windows(ctx.h, self.h, MEM_DEVICE if device else MEM_HOST, int(key), int(first_pos), int(last_pos),
+                                                 int(width), int(n), int(bool(skip_pos0)), _ptr(thr), len(thr), *[_ptr(o) for o in out]))
+        return tuple(out)
 
     def free(self):
         if self.h:

@@ -215,6 +215,35 @@ int  brh_depth_push_finish(brh_depth_push *dp,
 int  brh_depth_push_finish_per_base(brh_depth_push *dp, int zero_based, brh_depth_stream **out);
 void brh_depth_push_close(brh_depth_push *dp);
 
+/* Depth region summaries: per row of a regions table the number of bases, the sum of the coverage over them and the number of
+ * bases at or above each threshold (ivx.h ivx_depth_profile_summarize) -- mean depth per target, bases at 10x / 20x / 30x,
+ * coverage in bins (samtools bedcov, mosdepth --by / --thresholds).  The reference has no counterpart: its coverage() counts
+ * merged build intervals, not read depth.
+ * brh_depth_regions: reads / prior / lengths as for brh_depth; builds ONE depth profile, summarises and frees it.
+ * regions: region_cols names one contig column (Utf8 / LargeUtf8 / Utf8View) and the start and end columns (Int32, Int64, UInt32
+ *   or UInt64, each on its own); a value outside [0, 2^32-1] is clamped; a NULL coordinate is the error "coordinate column
+ *   contains null values; requires non-null coordinates".  Ends are inclusive; end_exclusive = 1 reads BED-style half-open ends
+ *   (end <= start: an empty region).  A contig the dictionary lacks has coverage 0 everywhere (and no domain).
+ * Domain: with lengths it is the one brh_depth_per_base_next emits -- [0, len - 1] when zero_based, else [1, len] without the
+ *   step at position 0 -- so `sum` equals the sum of the per-base rows inside the region whenever those fit Int16; the part of
+ *   a region outside it counts nowhere.  Without lengths it is the whole u32 range (zero_based is not read).
+ * Outputs: one row per region, in region order, all Int64 and non-null: bases, sum, and n_thr (<= 8) arrays ge[j] named
+ *   bases_ge_<thresholds[j]>; ge / ge_schemas point at n_thr structs (NULL when n_thr = 0).  No floating point: the caller divides.
+ * brh_depth_push_regions: the same over everything pushed so far.  Merges the stack down to one profile, which stays the
+ *   stack's only entry: the stream stays open, can be pushed to and finished as ever; after a finish it fails with "depth stream:
+ *   already finished". */
+int  brh_depth_regions(brh_session *s, brh_batch reads, brh_batch prior, brh_batch lengths, brh_batch regions, brh_columns region_cols,
+                       int zero_based, int end_exclusive, uint32_t filter_flag, uint32_t min_mapq,
+                       const int32_t *thresholds, uint32_t n_thr,
+                       struct ArrowArray *bases, struct ArrowSchema *bases_schema,
+                       struct ArrowArray *sum, struct ArrowSchema *sum_schema,
+                       struct ArrowArray *ge, struct ArrowSchema *ge_schemas);
+int  brh_depth_push_regions(brh_depth_push *dp, brh_batch regions, brh_columns region_cols, int zero_based, int end_exclusive,
+                            const int32_t *thresholds, uint32_t n_thr,
+                            struct ArrowArray *bases, struct ArrowSchema *bases_schema,
+                            struct ArrowArray *sum, struct ArrowSchema *sum_schema,
+                            struct ArrowArray *ge, struct ArrowSchema *ge_schemas);
+
 /* compute::take of ONE payload column with an index array a join / nearest call returned
  * (interval_join.rs:1655-1667, nearest.rs:469-482), on the device.  column: any fixed-width primitive
  * (ints, floats, date/time/timestamp/duration, decimal128/256, fixed-size binary of 1/2/4/8/16/32 bytes),

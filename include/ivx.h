@@ -471,6 +471,43 @@ ivx_status ivx_depth_profile_blocks(ivx_ctx *ctx, const ivx_index *profile, int 
                                     uint32_t *out_key, uint32_t *out_start, uint32_t *out_end, int32_t *out_cov,
                                     uint64_t cap, uint64_t *n_out);
 
+/*      REGION SUMMARIES of a profile: bases, coverage sum and bases at or above each threshold per region -- mean depth per
+ *      target, bases at 10x / 20x / 30x, coverage in fixed bins (samtools bedcov, mosdepth --by / --thresholds; the
+ *      reference has nothing here beyond coverage(), which counts merged build intervals, not read depth).
+ *      With C(p) and c0(k) as for ivx_depth_profile_expand, v(p) = (int32)(C(p) - c0(k)) with int32 wrap-around: expand's
+ *      value BEFORE its cast to Int16; the summaries use the exact int32.  The domain of key k is D(k) = [pos_lo,
+ *      key_hi ? key_hi[k] : 2^32-1], empty if key_hi[k] < pos_lo.  Region i is the closed interval [qstart[i], qend[i]] on
+ *      qkey[i] intersected with D(qkey[i]): R_i, empty when qend[i] < qstart[i], when qkey[i] == IVX_NULL_IDX or when the
+ *      domain cuts it away.
+ *        out_len[i]       = |R_i|                                     (int64_t[n], nullable)
+ *        out_sum[i]       = sum of v(p) over p in R_i                 (int64_t[n], nullable; always fits: 2^32 * 2^31 <= 2^63)
+ *        out_ge[j*n + i]  = #{p in R_i : v(p) >= thresholds[j]}       (int64_t[n_thr * n], threshold-major, nullable)
+ *      The zero-coverage stretches before a key's first step and on a key without steps count whenever thresholds[j] <= 0.
+ *      A key's last step extends to the end of its domain (the open block of a clipped or saturated contig that ivx_depth
+ *      drops).  Output order = input order; n = 0 is a no-op; any output may be NULL on its own; a valid empty profile
+ *      gives zeros and the lengths.  thresholds is HOST memory in both modes.  key_hi: [n_keys], where `mem` says.
+ *      IVX_ERR_INVALID: a key id >= n_keys other than IVX_NULL_IDX (found on the device before it indexes anything, as in
+ *      ivx_depth; nothing is written then); n_thr > IVX_DEPTH_MAX_THRESHOLDS; in device mode a pointer that is not aligned
+ *      to its element.  IVX_ERR_UNSUPPORTED: any index that is not a profile.  Usable from any context on the profile's
+ *      device; IVX_MEM_DEVICE calls may return with kernels in flight; drops the state a sizing call of another operation
+ *      left on the context; the scratch (8 * (1 + n_thr) bytes per 1024 steps, and the staged columns in host mode) counts
+ *      against the context's memory limit.  Cost per region: two searches in the key's steps and at most two tiles of
+ *      steps, whatever the region's length. */
+#define IVX_DEPTH_MAX_THRESHOLDS 8
+ivx_status ivx_depth_profile_summarize(ivx_ctx *ctx, const ivx_index *profile, int mem,
+                                       const uint32_t *qkey /* nullable: every region on key 0 */, const uint32_t *qstart, const uint32_t *qend, uint64_t n,
+                                       uint32_t pos_lo, const uint32_t *key_hi /* nullable */, int skip_pos0,
+                                       const int32_t *thresholds /* host memory */, uint32_t n_thr,
+                                       int64_t *out_len /* nullable */, int64_t *out_sum /* nullable */, int64_t *out_ge /* nullable */);
+/*      The same three outputs for n fixed-width windows of one key: window i = [first_pos + i * width, first_pos + i * width
+ *      + width - 1] intersected with [first_pos, last_pos] (the domain is the whole position range); no region arrays are
+ *      made.  With width = 1 it is ivx_depth_profile_expand in int32.  IVX_ERR_INVALID: width = 0; key >= n_keys;
+ *      first_pos + (n - 1) * width > 2^32 - 1; and the cases above. */
+ivx_status ivx_depth_profile_windows(ivx_ctx *ctx, const ivx_index *profile, int mem, uint32_t key,
+                                     uint32_t first_pos, uint32_t last_pos, uint32_t width, uint64_t n, int skip_pos0,
+                                     const int32_t *thresholds /* host memory */, uint32_t n_thr,
+                                     int64_t *out_len /* nullable */, int64_t *out_sum /* nullable */, int64_t *out_ge /* nullable */);
+
 /* ---- f3: `compute::take` of payload columns with the index arrays the probes return
  *      (interval_join.rs:1655-1667, nearest.rs:469-482).  idx[i] == IVX_NULL_IDX or a null source
  *      slot (src_valid_bits: Arrow validity bitmap of the source, bit offset 0, nullable) gives

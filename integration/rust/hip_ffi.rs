@@ -125,6 +125,15 @@ extern "C" {
     pub fn ivx_depth_profile_merge(ctx: *mut IvxCtx, a: *const IvxIndex, b: *const IvxIndex, out: *mut *mut IvxIndex) -> i32;
     pub fn ivx_depth_profile_blocks(ctx: *mut IvxCtx, profile: *const IvxIndex, mem: i32, out_key: *mut u32, out_start: *mut u32,
                                     out_end: *mut u32, out_cov: *mut i32, cap: u64, n_out: *mut u64) -> i32;
+    // region summaries of a profile: bases, coverage sum, bases at or above each threshold (thresholds: host memory;
+    // out_ge is threshold-major [n_thr * n]); per region, or per fixed-width window of one key
+    pub fn ivx_depth_profile_summarize(ctx: *mut IvxCtx, profile: *const IvxIndex, mem: i32, qkey: *const u32, qstart: *const u32,
+                                       qend: *const u32, n: u64, pos_lo: u32, key_hi: *const u32, skip_pos0: i32,
+                                       thresholds: *const i32, n_thr: u32, out_len: *mut i64, out_sum: *mut i64,
+                                       out_ge: *mut i64) -> i32;
+    pub fn ivx_depth_profile_windows(ctx: *mut IvxCtx, profile: *const IvxIndex, mem: i32, key: u32, first_pos: u32, last_pos: u32,
+                                     width: u32, n: u64, skip_pos0: i32, thresholds: *const i32, n_thr: u32,
+                                     out_len: *mut i64, out_sum: *mut i64, out_ge: *mut i64) -> i32;
     pub fn ivx_take_fixed(ctx: *mut IvxCtx, mem: i32, src: *const c_void, width: u32, n_src: u64, src_valid_bits: *const u8,
                           idx: *const u32, n: u64, out: *mut c_void, out_valid: *mut u8) -> i32;
     pub fn ivx_scatter_fixed(ctx: *mut IvxCtx, mem: i32, src: *const c_void, width: u32, idx: *const u32, n: u64,

@@ -67,6 +67,19 @@ extern "C" {
                                  coverage: *mut FFI_ArrowArray, coverage_schema: *mut FFI_ArrowSchema) -> c_int;
     pub fn brh_depth_push_finish_per_base(dp: *mut BrhDepthPush, zero_based: c_int, out: *mut *mut BrhDepthStream) -> c_int;
     pub fn brh_depth_push_close(dp: *mut BrhDepthPush);
+    // depth region summaries: bases, coverage sum and bases at or above each threshold per row of a regions table (all Int64);
+    // ge / ge_schemas point at n_thr structs.  The push form leaves the stream open.
+    pub fn brh_depth_regions(s: *mut BrhSession, reads: BrhBatch, prior: BrhBatch, lengths: BrhBatch, regions: BrhBatch, region_cols: BrhColumns,
+                             zero_based: c_int, end_exclusive: c_int, filter_flag: u32, min_mapq: u32,
+                             thresholds: *const i32, n_thr: u32,
+                             bases: *mut FFI_ArrowArray, bases_schema: *mut FFI_ArrowSchema,
+                             sum: *mut FFI_ArrowArray, sum_schema: *mut FFI_ArrowSchema,
+                             ge: *mut FFI_ArrowArray, ge_schemas: *mut FFI_ArrowSchema) -> c_int;
+    pub fn brh_depth_push_regions(dp: *mut BrhDepthPush, regions: BrhBatch, region_cols: BrhColumns, zero_based: c_int, end_exclusive: c_int,
+                                  thresholds: *const i32, n_thr: u32,
+                                  bases: *mut FFI_ArrowArray, bases_schema: *mut FFI_ArrowSchema,
+                                  sum: *mut FFI_ArrowArray, sum_schema: *mut FFI_ArrowSchema,
+                                  ge: *mut FFI_ArrowArray, ge_schemas: *mut FFI_ArrowSchema) -> c_int;
 }
 
 /// What `IntervalJoinStream` keeps per partition when `Algorithm::Hip` is selected.
