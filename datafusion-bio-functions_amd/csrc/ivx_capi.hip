@@ -248,8 +248,11 @@ extern "C" ivx_status ivx_ctx_create(int device_ordinal, ivx_ctx **out)
               hipEventCreateWithFlags(&c->tail_ev, hipEventDisableTiming) == hipSuccess &&
               hipEventCreate(&c->ev0) == hipSuccess && hipEventCreate(&c->ev1) == hipSuccess &&
               hipMalloc((void **)&c->d_scalars, 64 * sizeof(u64)) == hipSuccess &&
-              hipHostMalloc((void **)&c->h_scalars, 64 * sizeof(u64), hipHostMallocDefault) == hipSuccess;
+              // mapped and coherent: a kernel's stores through hd_scalars are in h_scalars once the kernel has completed
+              hipHostMalloc((void **)&c->h_scalars, IVX_HS_WORDS * sizeof(u64), hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess &&
+              hipHostGetDevicePointer((void **)&c->hd_scalars, c->h_scalars, 0) == hipSuccess;
     if (!ok) { ivx_ctx_free(c); return IVX_ERR_HIP; }
+    memset(c->h_scalars, 0, IVX_HS_WORDS * sizeof(u64));
     c->stream = c->own_stream;
     if (const char *e = getenv("IVX_BUILD_OVERLAP")) c->overlap = e[0] == '1';
     *out = c;
@@ -509,24 +512,29 @@ static ivx_status overlap_common(ivx_ctx *ctx, const ivx_index *ix, int mem, int
     // pair cursor | probe fault flags: zeroed here, or -- a region probe that routes its rows -- by the routing pass's clearing kernel
     const bool defer_clear = regions && !planned;
     if (!defer_clear) IVX_HIP(ctx, hipMemsetAsync(ctx->d_scalars, 0, 2 * sizeof(u64), ctx->stream));
+    ivx_probe_note note;
+    note.ix_serial = ix->serial;
     {
         KernelTimer t(ctx);
         if (regions) {
             if (!planned) pl.valid = false;                 // whatever an earlier count call left is gone now
             const ivx_status st = ivx_join_probe_regions(ctx, ix->jv, ix->jv_nreg, mode, dk, ds, de, n, d_b, d_p, cap, ctx->d_scalars, planned, ix->jv_filter, ix->jv_pk24,
-                                                         ix->jv_fast_unknown ? 2 : (ix->jv_fast ? 1 : 0), planned ? nullptr : ix->ready, defer_clear);
+                                                         ix->jv_lean.load(std::memory_order_relaxed), planned ? nullptr : ix->ready, defer_clear, &note);
+            // the call waited for the index's build tail and read hdr[HDR_SLOW] from the header mirror: known from here on
+            if (note.fast >= 0) ix->jv_lean.store(note.fast, std::memory_order_relaxed);
             if (st != IVX_OK) { pl.valid = false; return st; }
             if (mode == JP_COUNT && pl.valid) { memcpy(pl.in, in, sizeof(in)); pl.mem = mem; pl.n = n; pl.ix = ix; pl.ix_serial = ix->serial; pl.stream = ctx->stream; }
         }
         else if (rowval) IVX_TRY(ivx_rowval_probe_regions(ctx, ix->jv, ix->jv_nreg, mode == JP_PER_ROW ? IVX_RV_PER_ROW : IVX_RV_EXISTS, dk, ds, de, n, 0,
-                                                          mode == JP_PER_ROW ? (void *)d_row : (void *)d_ex, ctx->d_scalars, ix->jv_filter, ix->jv_pk24, ix->jv_fast && !ix->jv_fast_unknown));
+                                                          mode == JP_PER_ROW ? (void *)d_row : (void *)d_ex, ctx->d_scalars, ix->jv_filter, ix->jv_pk24, ix->jv_lean.load(std::memory_order_relaxed) == 1));
         else if (n && (mode == JP_PER_ROW || mode == JP_EXISTS) && ix->nroute_nreg > 0 && rowval_routed_ok(n))
             IVX_TRY(ivx_join_rowval_routed(ctx, ix, mode, dk, ds, de, n, d_row, d_ex, ctx->d_scalars));   // too many regions for the LDS slices: route, gather, put back
         else IVX_TRY(ivx_join_probe(ctx, ix->jv, mode, dk, ds, de, n, d_row, d_ex, d_b, d_p, cap, ctx->d_scalars));
     }
     u64 tot = 0;
     if (mode != JP_EXISTS) {
-        IVX_HIP(ctx, hipMemcpyAsync(ctx->h_scalars, ctx->d_scalars, 2 * sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
+        // (a lean fill's last kernel has left both words in the mapped mirror itself: k_fill_rest)
+        if (!note.totals_on_host) IVX_HIP(ctx, hipMemcpyAsync(ctx->h_scalars, ctx->d_scalars, 2 * sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
         IVX_HIP(ctx, hipStreamSynchronize(ctx->stream));
         tot = ctx->h_scalars[0];
         // a probe kernel met a routed-row page that the partition never published (it substituted a valid page, so nothing
@@ -759,7 +767,7 @@ ivx_status mark_common(ivx_ctx *ctx, const ivx_index *ix, int mem, const u32 *ke
     {
         KernelTimer t(ctx);
         bool took = false;
-        if (regions) IVX_TRY(ivx_mark_probe_regions(ctx, ix->jv, ix->jv_nreg, dk, ds, de, n, dm, ix->jv_filter, ix->jv_pk24, ix->jv_fast && !ix->jv_fast_unknown, &took));
+        if (regions) IVX_TRY(ivx_mark_probe_regions(ctx, ix->jv, ix->jv_nreg, dk, ds, de, n, dm, ix->jv_filter, ix->jv_pk24, ix->jv_lean.load(std::memory_order_relaxed) == 1, &took));
         if (!took) IVX_TRY(ivx_mark_probe(ctx, ix->jv, dk, ds, de, n, dm));
     }
     return marks_or_back(ctx, mem, marks, dm, nw);

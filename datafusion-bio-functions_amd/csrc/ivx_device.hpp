@@ -17,6 +17,11 @@ __device__ __forceinline__ u32 mask_rank(u64 mask)
     return __builtin_amdgcn_mbcnt_hi((u32)(mask >> 32), __builtin_amdgcn_mbcnt_lo((u32)mask, 0u));
 }
 
+// a word into host memory that is mapped into the device's address space (ivx_ctx::hd_scalars): an ordinary vector store
+// at system scope; the host reads it after it has waited for the kernel (a stream or an event), never before
+template <typename T>
+__device__ __forceinline__ void host_store(T *p, T v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); }
+
 // 32-bit wavefront scans on the DPP path (row shifts, then the row broadcasts of gfx9): no LDS round trip per step as with
 // ds_bpermute.  Lanes without a source take `old` = 0, the identity of both operators used here.
 template <int CTRL, int ROWS>

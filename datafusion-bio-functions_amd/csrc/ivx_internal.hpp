@@ -20,6 +20,8 @@ typedef int64_t i64;
 struct ivx_buf { void *p = nullptr; size_t cap = 0; };
 
 enum { IVX_NSCRATCH = 56, IVX_NPIN = 4 };
+// h_scalars: the words that mirror d_scalars, then words of its own (IVX_HS_HDR: an overlap index's header, HDR_WORDS u32)
+enum { IVX_HS_HDR = 64, IVX_HS_WORDS = 80 };
 
 // What a subtract sizing call leaves behind for the fill call that follows it: the sorted sides, the right
 // side's running max / gap heads and the scanned per-row output counts all sit in scratch slots (`slots` =
@@ -49,7 +51,8 @@ struct PageTab { u32 *ptab; u32 pstride, lgpg; };     // [region][page slot] -> 
 struct ivx_route_ctl {
     u32 rcur[1024];                     // rows routed to every region
     u32 pool_next, pad0[3];             // pages taken from the pool
-    u32 rest_n[2], pad1[2];             // the lean probes' rest lists: batches, rows
+    u32 rest_n[2];                      // the lean probes' rest lists: batches, rows
+    u32 fill_done, pad1;                // workgroups of k_fill_rest that have left (the last one publishes the call's totals); zeroed with rest_n
     u32 rfirst[1032];                   // first routed row of every region (k_page_bounds / k_chunk_bounds)
     u32 cfirst[1032];                   // first 8192-row chunk of every region (k_chunk_bounds)
 };
@@ -70,6 +73,7 @@ struct ivx_routed {
     PageTab pt{nullptr, 0u, 0u};
     bool packed = false;                // 8-byte routed rows (start in region | length | row), else (start,end) + row id
     u32 rowbits = 32;                   // bits of a packed row's id (the rest of the word's upper half extends the length)
+    bool tables_due = false;            // PAGED: rfirst and ctl->cfirst are NOT computed yet (ivx_paged_opts::defer_bounds): whoever reads them queues ivx_route_paged_bounds first
     bool all_routed = false;            // no occupancy bitmap in use: every row was routed (the fill's rows-per-lane rule is then known on the host)
     ivx_route_ctl *ctl = nullptr;
     FpRest *rest = nullptr; u64 *rest_rows = nullptr;   // the lean probes' rest lists (batches: fill only; single rows), or null
@@ -103,7 +107,10 @@ struct ivx_ctx {
     ivx_buf scratch[IVX_NSCRATCH];      // grow-only device scratch, one slot per use
     ivx_buf pinned[IVX_NPIN];           // grow-only pinned host staging
     u64 *d_scalars = nullptr;           // 64 device words for counters / totals
-    u64 *h_scalars = nullptr;           // pinned mirror
+    u64 *h_scalars = nullptr;           // pinned mirror: mapped and coherent, so that a kernel can leave a few words in it itself
+    u64 *hd_scalars = nullptr;          // ... its device pointer (words 0..1: a lean fill's pair total and fault word; from word IVX_HS_HDR: the
+                                        // header of the overlap index built last, ivx_join_build -- words nothing else uses)
+    u64 hdr_mirror_serial = 0;          // the index whose header that is (its HDR_SLOW arrives with the build's tail: ivx_join_probe_regions)
     ivx_sub_plan sub_plan;
     ivx_join_plan join_plan;
     ivx_metrics metrics{};              // BuildProbeJoinMetrics, see ivx.h
@@ -179,6 +186,7 @@ enum { HDR_SH0 = 0, HDR_NLEV = 1, HDR_NBINS = 2, HDR_CS = 3 /* log2(cells per re
        HDR_LBUILD = 12 + IVX_MAXL /* 1: the build's tail sorts every region's rows in LDS (ivx_join.hip: k_lbuild_*); 0: the global counting sort */,
        HDR_BADKEY = 13 + IVX_MAXL /* != 0: a build row's key id is >= n_keys (the key statistics' flag: one copy brings it to the host with the layout) */,
        HDR_WORDS = 14 + IVX_MAXL };
+static_assert(IVX_HS_HDR * sizeof(u64) + HDR_WORDS * sizeof(u32) <= IVX_HS_WORDS * sizeof(u64), "the header mirror fits the host words");
 // Occupancy bitmap of the build side ("can a probe row match anything at all"): per key one bit per 2^g-wide block of
 // [origin, origin + span] plus one overflow block behind it; a bit is set when some build row touches the block.  Sized to
 // stay resident in an XCD's 4 MiB L2 next to the streamed probe rows.
@@ -267,8 +275,11 @@ struct ivx_index {
     u32 jv_nreg = 0;            // >0: the region-partitioned probe is available
     bool jv_filter = false;     // jv carries an occupancy bitmap (hdr[HDR_FG] != ~0u)
     bool jv_pk24 = false;       // hdr[HDR_PK24]
-    bool jv_fast = false;       // !hdr[HDR_SLOW]
-    bool jv_fast_unknown = false;   // built with the tail overlapped: hdr[HDR_SLOW] is final only behind `ready` (kernels test it themselves)
+    // May the lean probes run on this index: 0 no (hdr[HDR_SLOW] is set or there are no regions), 1 yes, 2 not known on the
+    // host yet -- built with the tail overlapped, hdr[HDR_SLOW] is final only behind `ready` (kernels test it themselves).
+    // The one field a probe call writes: the first region fill or count that waits for the tail settles 2 to 0 or 1.  Other
+    // contexts and threads may probe the index meanwhile, hence an atomic (relaxed: either value they read is right).
+    mutable std::atomic<int> jv_lean{0};
     hipEvent_t ready = nullptr; // set when the build's tail ran on the aux stream: everything but the routing tables is valid behind it
     RankGridView gs{}, ge{};
     CoverageView cv{};
@@ -292,11 +303,18 @@ ivx_status ivx_join_probe(ivx_ctx *ctx, const JoinIndexView &jv, int mode,
                           u32 *per_row, u8 *exists, u32 *ob, u32 *op, u64 cap, u64 *d_cursor);
 enum { JP_COUNT = 0, JP_PER_ROW = 1, JP_EXISTS = 2, JP_FILL = 3 };
 // ivx_regions_probe.hip: partition the probe rows by index region (ivx_regions_route.hip), probe each region from LDS
+// what a call tells its caller besides its status
+struct ivx_probe_note {
+    u64 ix_serial = 0;          // in: the index probed (fast == 2: is the context's header mirror this index's?)
+    int fast = -1;              // out: 0 / 1 when the call came in with fast == 2 and learnt hdr[HDR_SLOW] on the host, else -1
+    bool totals_on_host = false;    // out: the call's last kernel leaves d_cursor[0..1] in h_scalars[0..1] itself (no copy needed, only the synchronisation)
+};
 ivx_status ivx_join_probe_regions(ivx_ctx *ctx, const JoinIndexView &jv, u32 nreg, int mode,
                                   const u32 *key, const i32 *s, const i32 *e, u64 n,
                                   u32 *ob, u32 *op, u64 cap, u64 *d_cursor, bool planned = false, bool has_filter = false, bool pk24 = false,
                                   int fast = 0 /* 0 no, 1 yes, 2 the kernels test hdr[HDR_SLOW] themselves */, hipEvent_t ready = nullptr,
-                                  bool clear_cursor = false /* d_cursor[0..1] are still to be zeroed (with the routing pass's own clears) */);
+                                  bool clear_cursor = false /* d_cursor[0..1] are still to be zeroed (with the routing pass's own clears) */,
+                                  ivx_probe_note *note = nullptr);
 
 // per-row-output operators through the same partition (count_overlaps: jv over the build rows, no row with
 // end < start; coverage: jv over the merged nodes)

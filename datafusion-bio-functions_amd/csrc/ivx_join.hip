@@ -51,7 +51,8 @@ __device__ __forceinline__ u32 cells_of(u32 cnt, u32 span, u32 sh) { return cnt 
 // lay out the (level,key) cell ranges.  hdr: sh0, #levels, #cells.
 __global__ __launch_bounds__(1024) void k_join_layout(const i32 *kmin, const i32 *kmax, const u32 *kcnt, u32 nkeys, u64 n,
                                                       i32 *origin, u32 *span, u32 *lbase, u32 *hdr, u64 maxcells,
-                                                      u32 *kreg, u32 *rkey, const u32 *lenhist, u32 regmax, u32 *fbase, int filter_mode, int lbuild_ok, const u32 *badkey)
+                                                      u32 *kreg, u32 *rkey, const u32 *lenhist, u32 regmax, u32 *fbase, int filter_mode, int lbuild_ok, const u32 *badkey,
+                                                      u32 *hmirror)
 {
     __shared__ u64 red[1024 / IVX_WAVE + 1];
     __shared__ u32 s_sh0;
@@ -268,6 +269,17 @@ __global__ __launch_bounds__(1024) void k_join_layout(const i32 *kmin, const i32
         // length bits) and the regions are what one workgroup handles: one digit of them, a cell table that fits
         hdr[HDR_BADKEY] = *badkey;
         hdr[HDR_LBUILD] = (lbuild_ok && R && R <= LB_CCAP && rrun && rrun <= IVX_MAXREG_WIDE && s_cum[33] == s_cum[sh0 + 1]) ? 1u : 0u;
+        // The header as it stands (every word of it is this thread's own, or still the zero it was cleared to: the level
+        // flags and HDR_SLOW are the tail's), once more in the context's mapped host words: the build's host side reads it
+        // there after its wait, without a copy in between.  One build per context is in flight up to that wait, so one
+        // mirror per context is enough.
+        // (all loads first, then the stores, two words each: none of them waits for another)
+        static_assert(HDR_WORDS % 2 == 0, "the mirror is written in 8-byte words");
+        u32 hv[HDR_WORDS];
+#pragma unroll
+        for (u32 w = 0; w < HDR_WORDS; w++) hv[w] = hdr[w];
+#pragma unroll
+        for (u32 w = 0; w < HDR_WORDS; w += 2) host_store((u64 *)hmirror + w / 2, (u64)hv[w] | ((u64)hv[w + 1] << 32));
     }
 }
 
@@ -409,14 +421,16 @@ __global__ __launch_bounds__(LB_T) void k_lbuild_regions(const i32 *origin, cons
 }
 
 // one thread per probe region: the level-0 cell window a workgroup stages for it and its entry range
+// hslow: HDR_SLOW of the context's header mirror (mapped host memory; zero before the tail is queued), set wherever the
+// device's word is -- by several threads, to the same value
 __global__ __launch_bounds__(256) void k_join_regdesc(const i32 *origin, const u32 *span, const u32 *lbase, u32 *hdr,
-                                                      const u32 *kreg, const u32 *rkey, const u32 *binstart, ivx_regdesc *rdesc)
+                                                      const u32 *kreg, const u32 *rkey, const u32 *binstart, ivx_regdesc *rdesc, u32 *hslow)
 {
     const u32 r = threadIdx.x + blockIdx.x * 256;
     if (r == 0) {                                               // rows outside level 0: the regions are not one LDS-resident level
         bool upper = hdr[HDR_LEVCNT] == 0;
         for (u32 l = 1; l < hdr[HDR_NLEV]; l++) upper |= hdr[HDR_LEVCNT + l] != 0;
-        if (upper) hdr[HDR_SLOW] = 1u;
+        if (upper) { hdr[HDR_SLOW] = 1u; host_store(hslow, 1u); }
     }
     if (r >= hdr[HDR_NREG]) return;
     const u32 sh0 = hdr[HDR_SH0];
@@ -433,7 +447,7 @@ __global__ __launch_bounds__(256) void k_join_regdesc(const i32 *origin, const u
     d.e0 = binstart[d.lb + d.slo];
     d.ne = binstart[d.lb + d.shi] - d.e0;
     d.rbase = (i32)((i64)d.origin + (i64)(rc0w << sh0));           // (rc0 < cells0: at most the key's largest start)
-    if (d.ne > IVX_RP_ECAP || d.shi - d.slo + 1u > 8192u + IVX_RP_HALO + 2u) hdr[HDR_SLOW] = 1u;   // the slice does not fit LDS (ivx_regions_probe.hip)
+    if (d.ne > IVX_RP_ECAP || d.shi - d.slo + 1u > 8192u + IVX_RP_HALO + 2u) { hdr[HDR_SLOW] = 1u; host_store(hslow, 1u); }   // the slice does not fit LDS (ivx_regions_probe.hip)
     rdesc[r] = d;
 }
 
@@ -743,8 +757,13 @@ ivx_status ivx_join_build(ivx_ctx *ctx, ivx_index *ix, const u32 *key, const i32
     IVX_TRY(ivx_keystats_len(ctx, key, s, n, nkeys, kmin, kmax, kcnt, errflag, 1u, e, lenhist, &zr));   // + the length classes for the layout
     // (every row's atomic returns a value, its loads depend on nothing: a row or two per thread, not a loop of eight round trips)
     const u32 grid = ivx_stream_grid(n, BT * 2, 16384);
-    hipLaunchKernelGGL(k_join_layout, dim3(1), dim3(1024), 0, st, kmin, kmax, kcnt, nkeys, n, origin, span, lbase, hdr, maxcells, kreg, rkey, (const u32 *)lenhist, (u32)(regcap - 1), fbase, filter_mode, lb_try ? 1 : 0, (const u32 *)errflag);
-    if (filter_mode) hipLaunchKernelGGL(k_join_filter, dim3(grid), dim3(BT), 0, st, key, s, e, n, nkeys, (const i32 *)origin, (const u32 *)span, (const u32 *)fbase, (const u32 *)hdr, fbits);
+    // the header's host mirror (k_join_layout, k_join_regdesc): this index's from here on
+    u32 *hmirror = (u32 *)(ctx->h_scalars + IVX_HS_HDR), *hmirror_d = (u32 *)(ctx->hd_scalars + IVX_HS_HDR);
+    ctx->hdr_mirror_serial = ix->serial;
+    hipLaunchKernelGGL(k_join_layout, dim3(1), dim3(1024), 0, st, kmin, kmax, kcnt, nkeys, n, origin, span, lbase, hdr, maxcells, kreg, rkey, (const u32 *)lenhist, (u32)(regcap - 1), fbase, filter_mode, lb_try ? 1 : 0, (const u32 *)errflag, hmirror_d);
+    auto launch_filter = [&]() {
+        hipLaunchKernelGGL(k_join_filter, dim3(grid), dim3(BT), 0, st, key, s, e, n, nkeys, (const i32 *)origin, (const u32 *)span, (const u32 *)fbase, (const u32 *)hdr, fbits);
+    };
     // routing regions for the per-row modes of build sides that outgrow the LDS-slice pipeline (more than 1023 regions
     // takes > 5 M rows); count / coverage / nearest indexes route on their rank grids
     const bool want_route = ix->kind == IVX_KIND_OVERLAP && n >= (4u << 20);
@@ -752,6 +771,9 @@ ivx_status ivx_join_build(ivx_ctx *ctx, ivx_index *ix, const u32 *key, const i32
     // the per-key tables, the region layout and the occupancy bitmap are final here.  With the build overlap on it goes to
     // the aux stream and the caller gets its index back as soon as the layout has reached the host.
     overlap = overlap && ctx->overlap && ctx->aux != nullptr && !want_route && n >= (1u << 16);
+    // The bitmap's kernel reads hdr[HDR_FG] and leaves when the layout asked for none.  Without the overlap it is queued
+    // here, before the host knows that word; with it, behind the header wait and only if there is a bitmap to fill.
+    if (filter_mode && !overlap) launch_filter();
     hipStream_t tail_st = st;
     // an error exit behind the fork must not hand the index's buffers and the scratch back while the aux stream may still
     // write them (ivx_index_build frees the index at once): such an exit waits for that stream first
@@ -769,13 +791,16 @@ ivx_status ivx_join_build(ivx_ctx *ctx, ivx_index *ix, const u32 *key, const i32
         tail_st = ctx->aux;
         // the words the caller waits for are final: the one synchronisation of a build comes before the tail is queued,
         // which then is the tail the layout asks for and nothing else, and a bad key id ends the build with nothing in flight
-        IVX_HIP(ctx, hipMemcpyAsync(ctx->h_scalars + 32, hdr, HDR_WORDS * sizeof(u32), hipMemcpyDeviceToHost, st));
+        // (they are in the mirror once k_join_layout has completed)
         IVX_HIP(ctx, hipStreamSynchronize(st));
-        if (((const u32 *)(ctx->h_scalars + 32))[HDR_BADKEY]) return ctx->fail(IVX_ERR_INVALID, "build key id >= n_keys");
-        q_lds = lb_try && ((const u32 *)(ctx->h_scalars + 32))[HDR_LBUILD] != 0;
+        if (hmirror[HDR_BADKEY]) return ctx->fail(IVX_ERR_INVALID, "build key id >= n_keys");
+        q_lds = lb_try && hmirror[HDR_LBUILD] != 0;
         q_global = !q_lds;
+        // on the launch stream, where the routing pass that reads the bitmap follows it
+        if (filter_mode && hmirror[HDR_FG] != 0xFFFFFFFFu) launch_filter();
         guard.armed = true;
     }
+    hmirror[HDR_SLOW] = 0;                                      // (the layout left a zero there; the tail's last kernel raises it)
     if (q_lds)
         hipLaunchKernelGGL(k_lbuild_tiles, dim3(lb_tiles), dim3(LB_T), 0, tail_st, key, s, e, n, nkeys, (const i32 *)origin, (const u32 *)kreg, hdr,
                            (ivx_ent *)cellid, rank, lb_tstride(lb_tiles), binstart, maxcells + 1);
@@ -795,28 +820,26 @@ ivx_status ivx_join_build(ivx_ctx *ctx, ivx_index *ix, const u32 *key, const i32
         hipLaunchKernelGGL(k_lbuild_regions, dim3(rgrid), dim3(LB_T), 0, tail_st, (const i32 *)origin, (const u32 *)span, (const u32 *)lbase, (const u32 *)kreg,
                            (const u32 *)rkey, (const u32 *)hdr, nkeys, (const ivx_ent *)cellid, (const u32 *)rank, lb_tiles, lb_tstride(lb_tiles), binstart, ent);
     }
-    hipLaunchKernelGGL(k_join_regdesc, dim3((u32)((regcap + 255) / 256)), dim3(256), 0, tail_st, origin, span, lbase, hdr, kreg, rkey, binstart, rdesc);
+    hipLaunchKernelGGL(k_join_regdesc, dim3((u32)((regcap + 255) / 256)), dim3(256), 0, tail_st, origin, span, lbase, hdr, kreg, rkey, binstart, rdesc, hmirror_d + HDR_SLOW);
     IVX_HIP(ctx, hipGetLastError());
     if (overlap) {
         if (ix->ready == nullptr) IVX_HIP(ctx, hipEventCreateWithFlags(&ix->ready, hipEventDisableTiming));
         IVX_HIP(ctx, hipEventRecord(ix->ready, ctx->aux));
         IVX_HIP(ctx, hipEventRecord(ctx->tail_ev, ctx->aux));    // (the context's own event: the index, and its event, may be freed first)
         ctx->tail_pending = true;
-        ix->jv_fast_unknown = true;
     }
     if (want_route) IVX_TRY(ivx_route_view_build(ctx, ix, origin, span, kcnt));
 
-    // key ids are validated on the device; the flag comes with the header (one small D2H).  (With the tail overlapped the header copy
-    // carries the layout's words -- regions, bitmap, packed rows -- but not yet the two flags the tail sets.)
-    if (!overlap) {
-        IVX_HIP(ctx, hipMemcpyAsync(ctx->h_scalars + 32, hdr, HDR_WORDS * sizeof(u32), hipMemcpyDeviceToHost, st));
-        IVX_HIP(ctx, hipStreamSynchronize(st));
-    }
-    if (((const u32 *)(ctx->h_scalars + 32))[HDR_BADKEY]) return ctx->fail(IVX_ERR_INVALID, "build key id >= n_keys");
-    ix->jv_nreg = ((const u32 *)(ctx->h_scalars + 32))[HDR_NREG];
-    ix->jv_filter = ((const u32 *)(ctx->h_scalars + 32))[HDR_FG] != 0xFFFFFFFFu;
-    ix->jv_pk24 = ((const u32 *)(ctx->h_scalars + 32))[HDR_PK24] != 0;
-    ix->jv_fast = ((const u32 *)(ctx->h_scalars + 32))[HDR_SLOW] == 0 && ix->jv_nreg > 0;
+    // key ids are validated on the device; the flag comes with the header mirror.  (With the tail overlapped the mirror
+    // holds the layout's words -- regions, bitmap, packed rows -- but not yet HDR_SLOW, which the tail sets: the first
+    // region probe of the index reads it behind `ready`.  Without the overlap the tail has run when the wait returns; the
+    // level flags stay on the device, nothing on the host reads them.)
+    if (!overlap) IVX_HIP(ctx, hipStreamSynchronize(st));
+    if (hmirror[HDR_BADKEY]) return ctx->fail(IVX_ERR_INVALID, "build key id >= n_keys");
+    ix->jv_nreg = hmirror[HDR_NREG];
+    ix->jv_filter = hmirror[HDR_FG] != 0xFFFFFFFFu;
+    ix->jv_pk24 = hmirror[HDR_PK24] != 0;
+    ix->jv_lean.store(overlap ? 2 : (hmirror[HDR_SLOW] == 0 && ix->jv_nreg > 0 ? 1 : 0), std::memory_order_relaxed);
     if (want_route) ivx_route_view_ready(ctx, ix);
     guard.armed = false;                                        // (the tail is the index's from here: `ready`, tail_ev)
 

@@ -72,9 +72,13 @@ ivx_status ivx_route_flat(ivx_ctx *ctx, const JoinIndexView &jv, const u32 *key,
 // one-pass partition into region pages (nreg <= IVX_MAXREG_WIDE).  rowval (per-row-value consumers; always packed, nreg <=
 // IVX_MAXREG): also vtab for the un-permute.  lean: the consumer may run the lean kernels (rest lists, chunk table)
 // zero2 (nullable): two 64-bit words of the caller's that the pass's clearing kernel zeroes on the way (a memset launch less)
-struct ivx_paged_opts { bool filter, packed, rowval, lean; u32 adj; u64 *zero2 = nullptr; };
+// defer_bounds: the regions' first rows and first chunks (R->rfirst, ctl->cfirst: k_chunk_bounds) are not computed and
+// R->tables_due says so; a probe that reads them queues ivx_route_paged_bounds behind the pass first (probe_pairs does, on
+// every way but the lean pair alone: k_fill_fast scans the regions' row counts itself)
+struct ivx_paged_opts { bool filter, packed, rowval, lean; u32 adj; u64 *zero2 = nullptr; bool defer_bounds = false; };
 ivx_status ivx_route_paged(ivx_ctx *ctx, const JoinIndexView &jv, u32 nreg, const u32 *key, const i32 *s, const i32 *e, u64 n,
                            const ivx_paged_opts &o, ivx_routed *R);
+ivx_status ivx_route_paged_bounds(ivx_ctx *ctx, const ivx_routed &R, u32 nreg);
 // more than IVX_MAXREG_WIDE regions: two partition passes (super-region, then region inside it) and a global region table
 ivx_status ivx_route_two_level(ivx_ctx *ctx, const JoinIndexView &jv, u32 nreg, const u32 *key, const i32 *s, const i32 *e, u64 n, ivx_routed *R);
 // one u32 value per routed row back into input order, as kind (IVX_RV_*) wants it: FLAT, val[] in routed order; PAGED (rowval),

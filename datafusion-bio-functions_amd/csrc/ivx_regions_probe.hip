@@ -639,7 +639,27 @@ struct LeanRows {
         nreg = ix.hdr[HDR_NREG];
         for (u32 t = threadIdx.x; t <= nreg; t += RP_T) s_cf[t] = cfirst[t];
         __syncthreads();
-        const u32 nchunk = s_cf[nreg];
+        return share();
+    }
+    // The same without a table: the workgroup scans the regions' chunk counts itself, thread t region t's (every workgroup
+    // the same 4 KB of counters out of L2, instead of a one-workgroup kernel in front of this one and the boundary it
+    // costs).  red: RP_W + 1 words of LDS that hold nothing yet.
+    __device__ __forceinline__ bool init_scan(const JoinIndexView &ix, u32 *s_cf, u32 *red, const u32 *rcur_, const PageTab &pt_, W *pool_, u32 rowbits_)
+    {
+        static_assert(IVX_MAXREG_WIDE < RP_T, "init_scan: one region per thread, and thread nreg for the total");
+        s_cfirst = s_cf; rcur = rcur_; pt = pt_; pool = pool_; rowbits = rowbits_; maxlen = pk_maxlen(rowbits_);
+        wv = __builtin_amdgcn_readfirstlane(threadIdx.x / IVX_WAVE); ln = lane_id();
+        nreg = ix.hdr[HDR_NREG];
+        const u32 t = threadIdx.x;
+        u32 tot;
+        const u32 ex = block_excl_scan<u32, RP_T>(t < nreg ? (rcur_[t] + FP_CHUNK - 1) / FP_CHUNK : 0u, red, &tot);
+        if (t <= nreg) s_cf[t] = ex;                                     // (thread nreg: everything before it, the total)
+        __syncthreads();
+        return share();
+    }
+    __device__ __forceinline__ bool share()
+    {
+        const u32 nchunk = s_cfirst[nreg];
         c_lo = (u32)((u64)nchunk * blockIdx.x / gridDim.x);
         const u32 c_hi = (u32)((u64)nchunk * (blockIdx.x + 1) / gridDim.x);
         nbatch = (c_hi - c_lo) * SUB;
@@ -762,7 +782,7 @@ __device__ __forceinline__ RestRow<W> rest_row(const JoinIndexView &ix, const Pa
 //  * the last wavefront to arrive in a round leaves every wavefront's output position, not just the round's base.
 template <int B, bool DRAIN>
 __global__ __launch_bounds__(RP_T) void k_fill_fast(JoinIndexView ix, const u64 *__restrict__ pool, const u32 *__restrict__ rcur,
-                                                    const u32 *__restrict__ cfirst, PageTab pt, u32 *__restrict__ ob, u32 *__restrict__ op, u64 cap,
+                                                    PageTab pt, u32 *__restrict__ ob, u32 *__restrict__ op, u64 cap,
                                                     unsigned long long *cursor, const u32 *bsel, u32 rowbits, FpRest *__restrict__ rest, u64 *__restrict__ rest_rows, u32 *rest_n,
                                                     u32 drain)
 {
@@ -775,7 +795,7 @@ __global__ __launch_bounds__(RP_T) void k_fill_fast(JoinIndexView ix, const u64 
     const u32 wv = __builtin_amdgcn_readfirstlane(threadIdx.x / IVX_WAVE), ln = lane_id();
     auto miss = [&]() { if (ln == 0) atomicOr((unsigned int *)(cursor + 1), 1u); };     // a page never published: the host is told
     LeanRows<B, const u64> rows;
-    if (!rows.init(ix, s_cfirst, cfirst, rcur, pt, pool, rowbits)) return;
+    if (!rows.init_scan(ix, s_cfirst, &s_wat[0][0], rcur, pt, pool, rowbits)) return;     // (s_wat: not in use before the first round)
     Slice S;
     slice_init(ix, S, L);
     rows.start(miss);
@@ -926,17 +946,21 @@ __global__ __launch_bounds__(RP_T) void k_fill_fast(JoinIndexView ix, const u64 
 __global__ __launch_bounds__(256) void k_fill_rest(JoinIndexView ix, const u64 *__restrict__ pool, PageTab pt, const FpRest *__restrict__ rest,
                                                    const u64 *__restrict__ rest_rows, const u32 *__restrict__ rest_n, u32 *__restrict__ ob,
                                                    u32 *__restrict__ op, u64 cap, unsigned long long *cursor, const i32 *__restrict__ ps_in,
-                                                   const i32 *__restrict__ pe_in, u32 rowbits)
+                                                   const i32 *__restrict__ pe_in, u32 rowbits, u32 *done, u64 *host_totals)
 {
     const u32 nbat = rest_n[0], nrow = rest_n[1];
-    if (nbat == 0 && nrow == 0) return;
     const u32 wpb = blockDim.x / IVX_WAVE, ln = lane_id();
     const u32 sh0 = ix.hdr[HDR_SH0], nlev = ix.hdr[HDR_NLEV];
     // 64 routed rows, one per lane: (region, virtual row) or nothing
     auto rows64 = [&](bool ok, u32 r, u32 v) {
         i32 qs = 0, qe = -1; u32 row = 0, k = 0;
         if (ok) {
-            const auto e = rest_row(ix, pt, pool, r, v, rowbits, ps_in, pe_in, 0u, [&]() { atomicOr((unsigned int *)(cursor + 1), 1u); });
+            // (the fault word's atomic returns its value and the lane takes it: performed before the lane goes on, as the
+            //  exit below needs it)
+            const auto e = rest_row(ix, pt, pool, r, v, rowbits, ps_in, pe_in, 0u, [&]() {
+                const u32 was = atomicOr((unsigned int *)(cursor + 1), 1u);
+                asm volatile("" ::"v"(was));
+            });
             qs = e.qs; qe = e.qe; row = e.row;
             k = ix.rkey[r];
         }
@@ -961,6 +985,21 @@ __global__ __launch_bounds__(256) void k_fill_rest(JoinIndexView ix, const u64 *
     for (u32 b = wave; b < nbat; b += nwave) {
         const FpRest w = rest[b];
         for (u32 t0 = 0; t0 < w.cnt; t0 += IVX_WAVE) rows64(t0 + ln < w.cnt, w.r, w.first + t0 + ln);
+    }
+    // host_totals (nullable; mapped host memory): this kernel is the call's last device work, and its last workgroup to
+    // leave hands the pair total and the fault word to the host -- no copy kernel behind it, the host only waits for the
+    // stream.  What orders the accesses: both words change by device-scope atomics only, which are performed at the memory's
+    // coherent point, not in an XCD's L2, and EVERY one of this kernel's atomics on them returns its value to a lane that
+    // uses it (the cursor's addend base; the fault word's old value, taken by an empty asm) -- so the wavefront has waited for
+    // it, i.e. it is performed, before the wavefront reaches the barrier below.  Thread 0 counts its workgroup after that
+    // barrier with a returning atomic of the same scope, and the workgroup that counts last reads both words with loads of
+    // that scope, issued after its count has returned.  No release fence: one per wavefront wrote its XCD's L2 back behind
+    // k_fill_fast's output and took the kernel from 15 to 49 us.  No workgroup waits for another.
+    if (host_totals == nullptr) return;
+    __syncthreads();
+    if (threadIdx.x == 0 && __hip_atomic_fetch_add(done, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1u) {
+        host_store(host_totals, (u64)__hip_atomic_load(cursor, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+        host_store(host_totals + 1, (u64)__hip_atomic_load(cursor + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
     }
 }
 
@@ -1370,6 +1409,9 @@ bool lean_rows_ok(const ivx_routed &R)
     return R.form == IVX_ROWS_PAGED && R.packed && R.pt.lgpg >= 13 && R.rest_rows != nullptr;
 }
 
+// ... and the lean fill pair (k_fill_fast + k_fill_rest), which also wants the batch list
+bool lean_fill_ok(const ivx_routed &R, const RegionKnobs &K) { return lean_rows_ok(R) && !K.lean_off && R.rest != nullptr; }
+
 template <int V> using int_tag = std::integral_constant<int, V>;
 // rows per lane in {1, 2, 4, 8} as a template argument: f(int_tag<B>)
 template <class F> void with_rows_per_lane(int b, F &&f)
@@ -1428,22 +1470,28 @@ ivx_status dense_fill(ivx_ctx *ctx, const JoinIndexView &jv, u32 nreg, const ivx
 // COUNT / FILL over routed rows of any form.  hint: the pairs to expect (how dense the matches are); fast: 0 no, 1 every
 // region is one LDS-resident level, 2 the kernels test hdr[HDR_SLOW] themselves; reused: R served an earlier fill already
 ivx_status probe_pairs(ivx_ctx *ctx, const JoinIndexView &jv, u32 nreg, int mode, const ivx_routed &R, u64 n, u32 *ob, u32 *op, u64 cap,
-                       u64 *d_cursor, u64 hint, int fast, bool reused, const RegionKnobs &K)
+                       u64 *d_cursor, u64 hint, int fast, bool reused, const RegionKnobs &K, ivx_probe_note *note)
 {
     hipStream_t st = ctx->stream;
     unsigned long long *cur = (unsigned long long *)d_cursor;
+    // R.tables_due: the routing pass left rfirst / cfirst to whoever reads them.  Everything below but the lean pair does:
+    // each such way calls tables() before its first launch (k_chunk_bounds reads only rcur, final behind the partition)
+    bool due = R.tables_due;
+    auto tables = [&]() -> ivx_status { if (due) { due = false; return ivx_route_paged_bounds(ctx, R, nreg); } return IVX_OK; };
     if (mode != JP_FILL) {
+        IVX_TRY(tables());
         launch_probe_regions<0, RP_B>(st, jv, R, RP_VGRID, ob, op, cap, cur);
         IVX_HIP(ctx, hipGetLastError());
         return IVX_OK;
     }
     // (the rows the probe walks are the routed ones: the density hint is pairs per INPUT row, as the caller sized it)
-    if (dense_fill_wanted(K, hint, n)) return dense_fill(ctx, jv, nreg, R, n, ob, op, cap, d_cursor);
+    if (dense_fill_wanted(K, hint, n)) { IVX_TRY(tables()); return dense_fill(ctx, jv, nreg, R, n, ob, op, cap, d_cursor); }
     // single walk: pairs staged per wavefront, one output reservation per workgroup and round.  Rows per lane follow from the
     // pairs per ROUTED row: known here when every row was routed; with the occupancy bitmap in use the count sits on the
     // device, k_pick_rows decides there and every variant is launched (three exit)
     const bool paged = R.form == IVX_ROWS_PAGED;
     u32 *bsel = paged && !R.all_routed ? (u32 *)(ctx->d_scalars + 11) : nullptr;
+    if (bsel) IVX_TRY(tables());
     if (bsel) hipLaunchKernelGGL(k_pick_rows, dim3(1), dim3(1), 0, st, R.rfirst, nreg, hint, K.rp_rows ? (u32)atoi(K.rp_rows) : 0u, bsel);
     auto every_b = [&](auto &&f) {
         if (bsel) { f(int_tag<8>{}); f(int_tag<4>{}); f(int_tag<2>{}); f(int_tag<1>{}); }
@@ -1452,24 +1500,30 @@ ivx_status probe_pairs(ivx_ctx *ctx, const JoinIndexView &jv, u32 nreg, int mode
     // packed rows over an index whose every region is one LDS-resident level: the lean kernel, then whatever batches it
     // left to the generic walk (IVX_FILL=old: the general kernel, for A/B runs and the tests that pin both)
     const u32 *slow_gate = nullptr;
-    if (lean_rows_ok(R) && fast != 0 && !K.lean_off && R.rest != nullptr) {
+    if (fast != 0 && lean_fill_ok(R, K)) {
         u32 *rest_n = R.ctl->rest_n;                                    // batches, rows
-        if (reused) IVX_HIP(ctx, hipMemsetAsync(rest_n, 0, 2 * sizeof(u32), st));   // (else: zeroed with the routing pass's counters just now)
+        static_assert(offsetof(ivx_route_ctl, fill_done) == offsetof(ivx_route_ctl, rest_n) + 2 * sizeof(u32), "one memset clears the rest counts and the done-counter");
+        if (reused) IVX_HIP(ctx, hipMemsetAsync(rest_n, 0, 3 * sizeof(u32), st));   // (else: zeroed with the routing pass's counters just now)
+        // fast == 1: the lean pair is all this call runs, and k_fill_rest leaves the totals on the host itself
+        const bool publish = fast == 1 && note != nullptr && ctx->hd_scalars != nullptr;
         every_b([&](auto b) {
             const u32 drain = fill_drain_of(K, decltype(b)::value);
             with_bools([&](auto dr) {
-                hipLaunchKernelGGL((k_fill_fast<decltype(b)::value, IVX_B(dr)>), dim3(RP_GRID), dim3(RP_T), 0, st, jv, R.se, (const u32 *)R.ctl->rcur, (const u32 *)R.ctl->cfirst, R.pt, ob, op, cap, cur,
+                hipLaunchKernelGGL((k_fill_fast<decltype(b)::value, IVX_B(dr)>), dim3(RP_GRID), dim3(RP_T), 0, st, jv, R.se, (const u32 *)R.ctl->rcur, R.pt, ob, op, cap, cur,
                                    (const u32 *)bsel, R.rowbits, R.rest, R.rest_rows, rest_n, drain);
             }, drain != 0);
         });
-        hipLaunchKernelGGL(k_fill_rest, dim3(512), dim3(256), 0, st, jv, R.se, R.pt, (const FpRest *)R.rest, (const u64 *)R.rest_rows, (const u32 *)rest_n, ob, op, cap, cur, R.ds, R.de, R.rowbits);
+        hipLaunchKernelGGL(k_fill_rest, dim3(512), dim3(256), 0, st, jv, R.se, R.pt, (const FpRest *)R.rest, (const u64 *)R.rest_rows, (const u32 *)rest_n, ob, op, cap, cur, R.ds, R.de, R.rowbits,
+                           &R.ctl->fill_done, publish ? ctx->hd_scalars : (u64 *)nullptr);
         IVX_HIP(ctx, hipGetLastError());
+        if (publish) note->totals_on_host = true;
         if (fast == 1) return IVX_OK;
         // fast == 2: whether every region is one LDS-resident level is known on the device only (the index's build
         // tail set hdr[HDR_SLOW] after the host had its copy): k_fill_fast has left at once if not, and the
         // general kernel below leaves at once if so
         slow_gate = jv.hdr + HDR_SLOW;
     }
+    IVX_TRY(tables());
     every_b([&](auto b) { launch_probe_regions<1, decltype(b)::value>(st, jv, R, RP_GRID, ob, op, cap, cur, bsel, slow_gate); });
     IVX_HIP(ctx, hipGetLastError());
     return IVX_OK;
@@ -1479,7 +1533,8 @@ ivx_status probe_pairs(ivx_ctx *ctx, const JoinIndexView &jv, u32 nreg, int mode
 
 ivx_status ivx_join_probe_regions(ivx_ctx *ctx, const JoinIndexView &jv, u32 nreg, int mode,
                                   const u32 *key, const i32 *s, const i32 *e, u64 n,
-                                  u32 *ob, u32 *op, u64 cap, u64 *d_cursor, bool planned, bool has_filter, bool pk24, int fast, hipEvent_t ready, bool clear_cursor)
+                                  u32 *ob, u32 *op, u64 cap, u64 *d_cursor, bool planned, bool has_filter, bool pk24, int fast, hipEvent_t ready, bool clear_cursor,
+                                  ivx_probe_note *note)
 {
     // `ready` (an index whose build tail may still run on another stream): the routing pass reads only what was final
     // before that tail started; the probe kernels come behind the event
@@ -1502,14 +1557,27 @@ ivx_status ivx_join_probe_regions(ivx_ctx *ctx, const JoinIndexView &jv, u32 nre
             IVX_TRY(ivx_route_flat(ctx, jv, key, s, e, n, 0u, nreg > IVX_MAXREG ? 1024u : 256u, false, 4, &R));
         } else {
             // 8-byte routed rows whenever a region's coordinates fit 24 bits
-            IVX_TRY(ivx_route_paged(ctx, jv, nreg, key, s, e, n, ivx_paged_opts{has_filter && !K.filter_off, pk24 && !K.pack_off, false, fast != 0, 0u, clear_cursor ? d_cursor : nullptr}, &R));
+            // a fill whose every row is routed may run the lean pair alone, which reads neither rfirst nor the chunk table
+            // (k_fill_fast scans the regions' row counts itself): probe_pairs queues k_chunk_bounds where it turns out otherwise
+            const bool bounds_due = mode == JP_FILL && !(has_filter && !K.filter_off);
+            IVX_TRY(ivx_route_paged(ctx, jv, nreg, key, s, e, n, ivx_paged_opts{has_filter && !K.filter_off, pk24 && !K.pack_off, false, fast != 0, 0u, clear_cursor ? d_cursor : nullptr, bounds_due}, &R));
+            // fast == 2, an index whose build tail may still be running: hdr[HDR_SLOW] is that tail's last word.  The routing
+            // pass is queued and keeps the device busy; the host waits for the tail here -- the probe kernels had to wait for
+            // the same event -- and reads the word from the header mirror the tail's last kernel wrote it to, if that mirror
+            // (this context's, one per context) still is this index's.  The call then launches the lean pair or the general
+            // kernel, not both with the device choosing, and the index's later calls know.
+            if (fast == 2 && ready != nullptr && note != nullptr && note->ix_serial != 0 && ctx->hdr_mirror_serial == note->ix_serial) {
+                IVX_HIP(ctx, hipEventSynchronize(ready));
+                fast = ((const u32 *)(ctx->h_scalars + IVX_HS_HDR))[HDR_SLOW] == 0 ? 1 : 0;
+                note->fast = fast;
+            }
         }
         if (mode == JP_COUNT) { pl.rows = R; pl.valid = true; }     // leave the routed rows for the fill call (ivx_capi.hip fills in whose they are)
     }
     IVX_TRY(wait_ready());
     // how dense the matches are: from the caller's capacity, or -- planned -- from what the count call found
     const u64 hint = ctx->fill_hint ? ctx->fill_hint : (planned && pl.total < cap ? pl.total : cap);
-    return probe_pairs(ctx, jv, nreg, mode, R, n, ob, op, cap, d_cursor, hint, fast, planned, K);
+    return probe_pairs(ctx, jv, nreg, mode, R, n, ob, op, cap, d_cursor, hint, fast, planned, K, note);
 }
 
 // One value per probe row, in input order, through the region partition.  kind: IVX_RV_COUNT (count_overlaps,

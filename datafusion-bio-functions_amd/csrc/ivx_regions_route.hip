@@ -1044,12 +1044,21 @@ ivx_status ivx_route_paged(ivx_ctx *ctx, const JoinIndexView &jv, u32 nreg, cons
         else if (wide) part(k_part_onepass<IVX_B(vec), 1024, 8, IVX_B(klds), IVX_B(filt), IVX_B(pk)>, (u32)PA_T);
         else part(k_part_onepass<IVX_B(vec), 256, 12, IVX_B(klds), IVX_B(filt), IVX_B(pk)>, (u32)PA_T);
     }, cols_aligned16(key, s, e), jv.nkeys <= KT_MAX, o.filter, o.packed);
-    // (per-row-value consumers that do not run the lean kernel need no chunk table)
+    // (per-row-value consumers that do not run the lean kernel need no chunk table; defer_bounds: the caller queues
+    //  ivx_route_paged_bounds itself if its probe turns out to read the tables)
     if (o.rowval && !o.lean) hipLaunchKernelGGL(k_page_bounds, dim3(1), dim3(1024), 0, st, (const u32 *)ctl->rcur, nreg, ctl->rfirst);
-    else hipLaunchKernelGGL(k_chunk_bounds, dim3(1), dim3(1024), 0, st, (const u32 *)ctl->rcur, nreg, ctl->rfirst, ctl->cfirst);
+    else if (!o.defer_bounds) hipLaunchKernelGGL(k_chunk_bounds, dim3(1), dim3(1024), 0, st, (const u32 *)ctl->rcur, nreg, ctl->rfirst, ctl->cfirst);
     IVX_HIP(ctx, hipGetLastError());
     R->form = IVX_ROWS_PAGED; R->se = pool; R->ids = prow; R->rfirst = ctl->rfirst; R->pt = pt; R->packed = o.packed; R->rowbits = rowbits;
+    R->tables_due = o.defer_bounds && !(o.rowval && !o.lean);
     R->all_routed = !o.filter; R->ctl = ctl; R->vtab = vtab; R->ds = s; R->de = e; R->adj = o.adj;
+    return IVX_OK;
+}
+
+ivx_status ivx_route_paged_bounds(ivx_ctx *ctx, const ivx_routed &R, u32 nreg)
+{
+    hipLaunchKernelGGL(k_chunk_bounds, dim3(1), dim3(1024), 0, ctx->stream, (const u32 *)R.ctl->rcur, nreg, R.ctl->rfirst, R.ctl->cfirst);
+    IVX_HIP(ctx, hipGetLastError());
     return IVX_OK;
 }
 

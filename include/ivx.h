@@ -98,7 +98,9 @@ ivx_status ivx_ctx_synchronize(ivx_ctx *ctx);
  * IVX_KIND_OVERLAP index from IVX_MEM_DEVICE columns returns as soon as the per-key tables and the region layout are final --
  * all that the routing pass of a big probe batch reads -- and lets the rest of the build (cell count, scan, scatter, region
  * descriptors) run on a second stream of the context.  The next big ivx_probe_overlap_count / _fill call routes its rows
- * beside that tail and only its probe kernel waits for it; every other use of the index (any context) and every other call
+ * beside that tail and only its probe kernel waits for it (the call itself waits on the host for the tail once its routing
+ * pass is queued, to learn which probe kernel the finished index takes, and notes that in the index -- the one thing a probe
+ * call writes in an index, atomically: other contexts and threads may go on probing it); every other use of the index (any context) and every other call
  * on this context is ordered behind the tail first, so results never change.  What changes is the caller's side of the
  * IVX_MEM_DEVICE contract: the build columns must stay unchanged until the index's first probe call has returned, or
  * ivx_ctx_synchronize (which waits for the tail too) -- as IntervalJoinExec keeps the build batches alive in JoinLeftData
