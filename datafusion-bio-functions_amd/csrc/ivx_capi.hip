@@ -167,14 +167,6 @@ ivx_status copy_out(ivx_ctx *ctx, int mem, T *dst, const T *dev, u64 n)
     return IVX_OK;
 }
 
-ivx_status read_scalar(ivx_ctx *ctx, int word, u64 *out)
-{
-    IVX_HIP(ctx, hipMemcpyAsync(ctx->h_scalars + word, ctx->d_scalars + word, sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
-    IVX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    *out = ctx->h_scalars[word];
-    return IVX_OK;
-}
-
 ivx_status check_probe_args(ivx_ctx *ctx, const ivx_index *ix, int kind, int mem, const void *s, const void *e, u64 n, bool defer_ready = false)
 {
     if (!ctx) return IVX_ERR_INVALID;
@@ -247,12 +239,12 @@ extern "C" ivx_status ivx_ctx_create(int device_ordinal, ivx_ctx **out)
               hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) == hipSuccess &&
               hipEventCreateWithFlags(&c->tail_ev, hipEventDisableTiming) == hipSuccess &&
               hipEventCreate(&c->ev0) == hipSuccess && hipEventCreate(&c->ev1) == hipSuccess &&
-              hipMalloc((void **)&c->d_scalars, 64 * sizeof(u64)) == hipSuccess &&
+              hipMalloc((void **)&c->d_scalars, SC_DEVICE_WORDS * sizeof(u64)) == hipSuccess &&
               // mapped and coherent: a kernel's stores through hd_scalars are in h_scalars once the kernel has completed
-              hipHostMalloc((void **)&c->h_scalars, IVX_HS_WORDS * sizeof(u64), hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess &&
+              hipHostMalloc((void **)&c->h_scalars, SC_HOST_WORDS * sizeof(u64), hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess &&
               hipHostGetDevicePointer((void **)&c->hd_scalars, c->h_scalars, 0) == hipSuccess;
     if (!ok) { ivx_ctx_free(c); return IVX_ERR_HIP; }
-    memset(c->h_scalars, 0, IVX_HS_WORDS * sizeof(u64));
+    memset(c->h_scalars, 0, SC_HOST_WORDS * sizeof(u64));
     c->stream = c->own_stream;
     if (const char *e = getenv("IVX_BUILD_OVERLAP")) c->overlap = e[0] == '1';
     *out = c;
@@ -511,14 +503,14 @@ static ivx_status overlap_common(ivx_ctx *ctx, const ivx_index *ix, int mem, int
     IVX_TRY(stage_out(ctx, mem, WS_OUT_D, pidx, cap, &d_p));
     // pair cursor | probe fault flags: zeroed here, or -- a region probe that routes its rows -- by the routing pass's clearing kernel
     const bool defer_clear = regions && !planned;
-    if (!defer_clear) IVX_HIP(ctx, hipMemsetAsync(ctx->d_scalars, 0, 2 * sizeof(u64), ctx->stream));
+    if (!defer_clear) IVX_HIP(ctx, hipMemsetAsync(ctx->dword(SC_PAIRS), 0, 2 * sizeof(u64), ctx->stream));
     ivx_probe_note note;
     note.ix_serial = ix->serial;
     {
         KernelTimer t(ctx);
         if (regions) {
             if (!planned) pl.valid = false;                 // whatever an earlier count call left is gone now
-            const ivx_status st = ivx_join_probe_regions(ctx, ix->jv, ix->jv_nreg, mode, dk, ds, de, n, d_b, d_p, cap, ctx->d_scalars, planned, ix->jv_filter, ix->jv_pk24,
+            const ivx_status st = ivx_join_probe_regions(ctx, ix->jv, ix->jv_nreg, mode, dk, ds, de, n, d_b, d_p, cap, ctx->dword(SC_PAIRS), planned, ix->jv_filter, ix->jv_pk24,
                                                          ix->jv_lean.load(std::memory_order_relaxed), planned ? nullptr : ix->ready, defer_clear, &note);
             // the call waited for the index's build tail and read hdr[HDR_SLOW] from the header mirror: known from here on
             if (note.fast >= 0) ix->jv_lean.store(note.fast, std::memory_order_relaxed);
@@ -526,20 +518,20 @@ static ivx_status overlap_common(ivx_ctx *ctx, const ivx_index *ix, int mem, int
             if (mode == JP_COUNT && pl.valid) { memcpy(pl.in, in, sizeof(in)); pl.mem = mem; pl.n = n; pl.ix = ix; pl.ix_serial = ix->serial; pl.stream = ctx->stream; }
         }
         else if (rowval) IVX_TRY(ivx_rowval_probe_regions(ctx, ix->jv, ix->jv_nreg, mode == JP_PER_ROW ? IVX_RV_PER_ROW : IVX_RV_EXISTS, dk, ds, de, n, 0,
-                                                          mode == JP_PER_ROW ? (void *)d_row : (void *)d_ex, ctx->d_scalars, ix->jv_filter, ix->jv_pk24, ix->jv_lean.load(std::memory_order_relaxed) == 1));
+                                                          mode == JP_PER_ROW ? (void *)d_row : (void *)d_ex, ctx->dword(SC_PAIRS), ix->jv_filter, ix->jv_pk24, ix->jv_lean.load(std::memory_order_relaxed) == 1));
         else if (n && (mode == JP_PER_ROW || mode == JP_EXISTS) && ix->nroute_nreg > 0 && rowval_routed_ok(n))
-            IVX_TRY(ivx_join_rowval_routed(ctx, ix, mode, dk, ds, de, n, d_row, d_ex, ctx->d_scalars));   // too many regions for the LDS slices: route, gather, put back
-        else IVX_TRY(ivx_join_probe(ctx, ix->jv, mode, dk, ds, de, n, d_row, d_ex, d_b, d_p, cap, ctx->d_scalars));
+            IVX_TRY(ivx_join_rowval_routed(ctx, ix, mode, dk, ds, de, n, d_row, d_ex, ctx->dword(SC_PAIRS)));   // too many regions for the LDS slices: route, gather, put back
+        else IVX_TRY(ivx_join_probe(ctx, ix->jv, mode, dk, ds, de, n, d_row, d_ex, d_b, d_p, cap, ctx->dword(SC_PAIRS)));
     }
     u64 tot = 0;
     if (mode != JP_EXISTS) {
         // (a lean fill's last kernel has left both words in the mapped mirror itself: k_fill_rest)
-        if (!note.totals_on_host) IVX_HIP(ctx, hipMemcpyAsync(ctx->h_scalars, ctx->d_scalars, 2 * sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
+        if (!note.totals_on_host) IVX_HIP(ctx, ctx->fetch(SC_PAIRS, ctx->stream, 2));
         IVX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        tot = ctx->h_scalars[0];
+        tot = *ctx->hword(SC_PAIRS);
         // a probe kernel met a routed-row page that the partition never published (it substituted a valid page, so nothing
         // was read out of bounds): an internal error, reported instead of returning wrong pairs
-        if (ctx->h_scalars[1]) { ctx->join_plan.valid = false; return ctx->fail(IVX_ERR_HIP, "internal error: the probe met an unpublished page of routed rows"); }
+        if (*ctx->hword(SC_FAULT)) { ctx->join_plan.valid = false; return ctx->fail(IVX_ERR_HIP, "internal error: the probe met an unpublished page of routed rows"); }
     }
     if (mode == JP_COUNT && regions && pl.valid) pl.total = tot;
     if (total) *total = tot;

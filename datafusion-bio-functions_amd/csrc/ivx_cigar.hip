@@ -38,21 +38,20 @@ constexpr int CIGAR_TILE = ivxscan::T_ * CIGAR_B;            // bytes per workgr
 constexpr u64 CCAP = 1ull << 32;
 constexpr int CT = 256;
 
-// scalar slots of the context used here (64-bit words)
-enum { CS_BAD = 40, CS_OFF0 = 41, CS_OFFN = 42, CS_BADREAD = 43 };
-
 template <class OT>
 __global__ __launch_bounds__(CT) void k_cigar_check(const OT *__restrict__ off, u64 n_reads, u64 *sc)
 {
     const u64 i = (u64)blockIdx.x * CT + threadIdx.x;
     if (i > n_reads) return;
     const i64 o = (i64)off[i];
-    if (o < 0 || (i > 0 && o < (i64)off[i - 1])) atomicOr((u32 *)(sc + CS_BAD), 1u);
-    if (i == 0) sc[CS_OFF0] = (u64)o;
-    if (i == n_reads) sc[CS_OFFN] = (u64)o;
+    if (o < 0 || (i > 0 && o < (i64)off[i - 1])) atomicOr((u32 *)(sc + SC_CIG_BAD), 1u);
+    if (i == 0) sc[SC_CIG_OFF0] = (u64)o;
+    if (i == n_reads) sc[SC_CIG_OFFN] = (u64)o;
 }
 
 struct CigState { u64 v, p; u32 ops, reset; };
+IVX_SC_FITS(CigState, SC_CIG_IDENT, SC_ROUTE_HDR);
+IVX_SC_FITS(CigState, SC_LANDING, SC_LANDING + SC_LANDING_WORDS);
 struct CigScan {
     using T = CigState;
     __host__ __device__ static T identity() { T t; t.v = 0; t.p = 1; t.ops = 0; t.reset = 0; return t; }
@@ -258,17 +257,16 @@ ivx_status cigar_count_t(ivx_ctx *ctx, const OT *off, ivx_cigar_plan *P)
     CigState *tsum;                                         // [0] = identity, [1 + t] = the scan up to and including tile t
     IVX_TRY(ctx->get_scratch(WS_SCAN0, (nblk + 1) * sizeof(CigState), (void **)&tsum));
     const CigState id = CigScan::identity();
-    CigState *hid = (CigState *)(ctx->h_scalars + 44);      // pinned: the async copy may read it later
+    CigState *hid = ctx->hword<CigState>(SC_CIG_IDENT);     // pinned: the async copy may read it later
     *hid = id;
     IVX_HIP(ctx, hipMemcpyAsync(tsum, hid, sizeof(CigState), hipMemcpyHostToDevice, st));
     CigarText<OT> X{off, P->txt, P->n_reads, P->n_bytes, P->off0, P->mis};
     hipLaunchKernelGGL((k_cigar_reduce<OT>), dim3((u32)nblk), dim3(T_), 0, st, X, tsum + 1);
     IVX_TRY((scan_rec<CigScan, true>(ctx, tsum + 1, nblk, 1, WS_SCAN0)));
     IVX_HIP(ctx, hipGetLastError());
-    CigState *htot = (CigState *)(ctx->h_scalars + 48);
-    IVX_HIP(ctx, hipMemcpyAsync(htot, tsum + nblk, sizeof(CigState), hipMemcpyDeviceToHost, st));
-    IVX_HIP(ctx, hipStreamSynchronize(st));
-    P->n_ops = htot->ops;
+    CigState tot;
+    IVX_TRY(ctx->fetch_wait((const CigState *)tsum + nblk, st, &tot));
+    P->n_ops = tot.ops;
     P->tsum = tsum; P->nblk = nblk;
     return IVX_OK;
 }
@@ -278,17 +276,17 @@ ivx_status cigar_write_t(ivx_ctx *ctx, const OT *off, const ivx_cigar_plan &P, i
 {
     using namespace ivxscan;
     hipStream_t st = ctx->stream;
-    u64 *sc = ctx->d_scalars, *hs = ctx->h_scalars;
-    IVX_HIP(ctx, hipMemsetAsync(sc + CS_BADREAD, 0xFF, sizeof(u64), st));
+    u64 *badread = ctx->dword(SC_CIG_BADREAD);
+    IVX_HIP(ctx, hipMemsetAsync(badread, 0xFF, sizeof(u64), st));
     CigarText<OT> X{off, P.txt, P.n_reads, P.n_bytes, P.off0, P.mis};
-    hipLaunchKernelGGL((k_cigar_apply<OT>), dim3((u32)P.nblk), dim3(T_), 0, st, X, (const CigState *)P.tsum, out_off, out_ops, sc + CS_BADREAD);
+    hipLaunchKernelGGL((k_cigar_apply<OT>), dim3((u32)P.nblk), dim3(T_), 0, st, X, (const CigState *)P.tsum, out_off, out_ops, badread);
     if (out_off)
         hipLaunchKernelGGL((k_cigar_fill<OT>), dim3((u32)((P.n_reads + CT) / CT)), dim3(CT), 0, st, off, P.n_reads, out_off, (u32)P.n_ops);
     IVX_HIP(ctx, hipGetLastError());
-    IVX_HIP(ctx, hipMemcpyAsync(hs + CS_BADREAD, sc + CS_BADREAD, sizeof(u64), hipMemcpyDeviceToHost, st));
-    IVX_HIP(ctx, hipStreamSynchronize(st));
-    if (hs[CS_BADREAD] != ~0ull)
-        return ctx->fail(IVX_ERR_INVALID, "cigar: an op length of 2^28 or more cannot be packed (read " + std::to_string(hs[CS_BADREAD]) + ")");
+    u64 read;
+    IVX_TRY(ctx->fetch_wait(SC_CIG_BADREAD, st, &read));
+    if (read != ~0ull)
+        return ctx->fail(IVX_ERR_INVALID, "cigar: an op length of 2^28 or more cannot be packed (read " + std::to_string(read) + ")");
     return IVX_OK;
 }
 
@@ -303,21 +301,21 @@ ivx_status ivx_cigar_count(ivx_ctx *ctx, int large, const void *text_offsets, co
     P->txt = nullptr; P->off0 = 0; P->mis = 0;
     if (n_reads == 0) return IVX_OK;
     hipStream_t st = ctx->stream;
-    u64 *sc = ctx->d_scalars, *hs = ctx->h_scalars;
-    IVX_HIP(ctx, hipMemsetAsync(sc + CS_BAD, 0, 3 * sizeof(u64), st));
+    IVX_HIP(ctx, hipMemsetAsync(ctx->dword(SC_CIG_BAD), 0, SC_CIG_CHECK_WORDS * sizeof(u64), st));
     const u32 grid = (u32)((n_reads + CT) / CT);
-    if (large) hipLaunchKernelGGL((k_cigar_check<i64>), dim3(grid), dim3(CT), 0, st, (const i64 *)text_offsets, n_reads, sc);
-    else hipLaunchKernelGGL((k_cigar_check<i32>), dim3(grid), dim3(CT), 0, st, (const i32 *)text_offsets, n_reads, sc);
+    if (large) hipLaunchKernelGGL((k_cigar_check<i64>), dim3(grid), dim3(CT), 0, st, (const i64 *)text_offsets, n_reads, ctx->d_scalars);
+    else hipLaunchKernelGGL((k_cigar_check<i32>), dim3(grid), dim3(CT), 0, st, (const i32 *)text_offsets, n_reads, ctx->d_scalars);
     IVX_HIP(ctx, hipGetLastError());
-    IVX_HIP(ctx, hipMemcpyAsync(hs + CS_BAD, sc + CS_BAD, 3 * sizeof(u64), hipMemcpyDeviceToHost, st));
+    IVX_HIP(ctx, ctx->fetch(SC_CIG_BAD, st, SC_CIG_CHECK_WORDS));
     IVX_HIP(ctx, hipStreamSynchronize(st));
-    if ((u32)hs[CS_BAD]) return ctx->fail(IVX_ERR_INVALID, "cigar: text offsets must ascend and be non-negative");
-    const u64 nb = hs[CS_OFFN] - hs[CS_OFF0];
+    const u64 off0 = *ctx->hword(SC_CIG_OFF0), offn = *ctx->hword(SC_CIG_OFFN);
+    if (*ctx->hword<u32>(SC_CIG_BAD)) return ctx->fail(IVX_ERR_INVALID, "cigar: text offsets must ascend and be non-negative");
+    const u64 nb = offn - off0;
     if (nb >= CCAP) return ctx->fail(IVX_ERR_INVALID, "cigar: 2^32 or more bytes of CIGAR text in one call");
     if (nb == 0) return IVX_OK;
     if (!text) return ctx->fail(IVX_ERR_INVALID, "cigar: null text buffer");
-    P->n_bytes = nb; P->off0 = (i64)hs[CS_OFF0];
-    P->txt = text_at_off0 ? text : text + hs[CS_OFF0];
+    P->n_bytes = nb; P->off0 = (i64)off0;
+    P->txt = text_at_off0 ? text : text + off0;
     P->mis = (u32)((uintptr_t)P->txt & 15u);
     IVX_TRY(large ? cigar_count_t<i64>(ctx, (const i64 *)text_offsets, P) : cigar_count_t<i32>(ctx, (const i32 *)text_offsets, P));
     if (P->n_ops > 0x1FFFFFFFull) return ctx->fail(IVX_ERR_INVALID, "cigar: more than 2^29-1 ops in one call");

@@ -32,9 +32,6 @@ constexpr u64 HEADBIT = 1ull << 63;
 
 static inline u32 dgrid(u64 n) { return (u32)((n + DT - 1) / DT); }
 
-// scalar slots of the context used here (64-bit words)
-enum { DS_BAD = 8, DS_MAXPOS = 10, DS_TOTAL = 11, DS_OFF0 = 12, DS_OFFN = 13 };
-
 __device__ __forceinline__ u32 sat32(u64 x) { return x > 0xFFFFFFFFull ? 0xFFFFFFFFu : (u32)x; }
 
 __global__ __launch_bounds__(DT) void k_depth_check(const i32 *__restrict__ off, u64 n_reads, const u32 *__restrict__ rkey,
@@ -45,12 +42,12 @@ __global__ __launch_bounds__(DT) void k_depth_check(const i32 *__restrict__ off,
     if (off && i <= n_reads) {
         const i32 o = off[i];
         if (o < 0 || (o & 3) || (i > 0 && o < off[i - 1])) bad |= 1u;
-        if (i == 0) sc[DS_OFF0] = (u64)(u32)o;
-        if (i == n_reads) sc[DS_OFFN] = (u64)(u32)o;
+        if (i == 0) sc[SC_DEPTH_OFF0] = (u64)(u32)o;
+        if (i == n_reads) sc[SC_DEPTH_OFFN] = (u64)(u32)o;
     }
     if (i < n_reads) { const u32 k = rkey ? rkey[i] : 0u; if (k >= nkeys && k != IVX_NULL_IDX) bad |= 2u; }
     if (i < n_seg) { const u32 k = skey ? skey[i] : 0u; if (k >= nkeys && k != IVX_NULL_IDX) bad |= 2u; }
-    if (bad) atomicOr((u32 *)(sc + DS_BAD), bad);
+    if (bad) atomicOr((u32 *)(sc + SC_DEPTH_BAD), bad);
 }
 
 // ------------------------------------------------------------------------------------------------ the scan over ops
@@ -67,6 +64,7 @@ struct DepthReads {
 // sf: bit 63 = the range holds the first op of a read; low bits = reference length consumed since that op (or, without
 // one, by the whole range).  cnt: events emitted.
 struct OpState { u64 sf; u32 cnt; u32 pad; };
+IVX_SC_FITS(OpState, SC_LANDING, SC_LANDING + SC_LANDING_WORDS);
 struct OpScan {
     using T = OpState;
     __host__ __device__ static T identity() { T t; t.sf = 0; t.cnt = 0; t.pad = 0; return t; }
@@ -339,17 +337,17 @@ ivx_status ivx_depth_events(ivx_ctx *ctx, const u32 *rkey, const u32 *rpos, cons
     out->n = 0; out->ev = nullptr; out->cg = nullptr;
     if (n_reads == 0 && n_seg == 0) return IVX_OK;
     hipStream_t st = ctx->stream;
-    u64 *sc = ctx->d_scalars, *hs = ctx->h_scalars;
-    IVX_HIP(ctx, hipMemsetAsync(sc + DS_BAD, 0, 6 * sizeof(u64), st));
+    IVX_HIP(ctx, hipMemsetAsync(ctx->dword(SC_DEPTH_BAD), 0, SC_DEPTH_WORDS * sizeof(u64), st));
     const u64 nchk = (n_reads + 1 > n_seg ? n_reads + 1 : n_seg);
-    hipLaunchKernelGGL(k_depth_check, dim3(dgrid(nchk)), dim3(DT), 0, st, n_reads ? off : (const i32 *)nullptr, n_reads, rkey, skey, n_seg, nkeys, sc);
+    hipLaunchKernelGGL(k_depth_check, dim3(dgrid(nchk)), dim3(DT), 0, st, n_reads ? off : (const i32 *)nullptr, n_reads, rkey, skey, n_seg, nkeys, ctx->d_scalars);
     IVX_HIP(ctx, hipGetLastError());
-    IVX_HIP(ctx, hipMemcpyAsync(hs + DS_BAD, sc + DS_BAD, 6 * sizeof(u64), hipMemcpyDeviceToHost, st));
+    IVX_HIP(ctx, ctx->fetch(SC_DEPTH_BAD, st, SC_DEPTH_WORDS));
     IVX_HIP(ctx, hipStreamSynchronize(st));
-    const u32 bad = (u32)hs[DS_BAD];
+    const u32 bad = *ctx->hword<u32>(SC_DEPTH_BAD);
+    const u64 off0 = *ctx->hword(SC_DEPTH_OFF0), offn = *ctx->hword(SC_DEPTH_OFFN);
     if (bad & 1u) return ctx->fail(IVX_ERR_INVALID, "depth: cigar_offsets must ascend and be non-negative multiples of 4");
     if (bad & 2u) return ctx->fail(IVX_ERR_INVALID, "depth: key id >= n_keys");
-    const u64 n_ops = n_reads ? (hs[DS_OFFN] - hs[DS_OFF0]) / 4 : 0;
+    const u64 n_ops = n_reads ? (offn - off0) / 4 : 0;
     if (n_ops && !ops) return ctx->fail(IVX_ERR_INVALID, "depth: null CIGAR data buffer");
 
     // ---- the scan over ops, first half: how many events the reads emit
@@ -358,17 +356,16 @@ ivx_status ivx_depth_events(ivx_ctx *ctx, const u32 *rkey, const u32 *rpos, cons
     OpState *tsum = nullptr;                                // [0] = identity, [1 + t] = the scan up to and including tile t
     u64 n_rev = 0;
     if (n_ops) {
-        R.off0 = (i64)hs[DS_OFF0];
-        R.ops = ops + hs[DS_OFF0] / 4;
+        R.off0 = (i64)off0;
+        R.ops = ops + off0 / 4;
         IVX_TRY(ctx->get_scratch(WS_SCAN0, (nblk + 1) * sizeof(OpState), (void **)&tsum));
         IVX_HIP(ctx, hipMemsetAsync(tsum, 0, sizeof(OpState), st));
         hipLaunchKernelGGL(k_ops_reduce, dim3((u32)nblk), dim3(T_), 0, st, R, n_ops, tsum + 1);
         IVX_TRY((scan_rec<OpScan, true>(ctx, tsum + 1, nblk, 1, WS_SCAN0)));
         IVX_HIP(ctx, hipGetLastError());
-        OpState *htot = (OpState *)(hs + DS_OFF0);          // (the offsets are consumed: two words)
-        IVX_HIP(ctx, hipMemcpyAsync(htot, tsum + nblk, sizeof(OpState), hipMemcpyDeviceToHost, st));
-        IVX_HIP(ctx, hipStreamSynchronize(st));
-        n_rev = htot->cnt;
+        OpState tot;
+        IVX_TRY(ctx->fetch_wait((const OpState *)tsum + nblk, st, &tot));
+        n_rev = tot.cnt;
         // (the 32-bit count cannot wrap: 2^29 ops at most, two events each)
     }
     const u64 E = 2 * n_seg + n_rev;
@@ -381,16 +378,16 @@ ivx_status ivx_depth_events(ivx_ctx *ctx, const u32 *rkey, const u32 *rpos, cons
     IVX_TRY(ctx->get_scratch(WS_SB0, E * sizeof(u64), (void **)&wb));
     IVX_TRY(ctx->get_scratch(WS_SA1, E * sizeof(u32), (void **)&da));
     IVX_TRY(ctx->get_scratch(WS_SB1, E * sizeof(u32), (void **)&db));
-    u32 *maxpos = (u32 *)(sc + DS_MAXPOS);
+    u32 *maxpos = ctx->dword<u32>(SC_DEPTH_MAXPOS);
     if (n_seg) hipLaunchKernelGGL(k_seg_events, dim3(dgrid(n_seg)), dim3(DT), 0, st, skey, ss, se, sw, n_seg, key_len, wa, da, maxpos, seen);
     if (n_rev) hipLaunchKernelGGL(k_ops_apply, dim3((u32)nblk), dim3(T_), 0, st, R, n_ops, (const OpState *)tsum, wa, da, 2 * n_seg, maxpos, seen);
     IVX_HIP(ctx, hipGetLastError());
-    IVX_HIP(ctx, hipMemcpyAsync(hs + DS_MAXPOS, sc + DS_MAXPOS, sizeof(u64), hipMemcpyDeviceToHost, st));
-    IVX_HIP(ctx, hipStreamSynchronize(st));
+    u32 hmaxpos;
+    IVX_TRY(ctx->fetch_wait(SC_DEPTH_MAXPOS, st, &hmaxpos));
 
     // ---- sort by (key, position): only the bits that can vary
     int pbits = 0, kbits = 0;
-    for (u64 x = (u32)hs[DS_MAXPOS]; x; x >>= 1) pbits++;
+    for (u64 x = hmaxpos; x; x >>= 1) pbits++;
     for (u64 x = nkeys ? nkeys - 1 : 0; x; x >>= 1) kbits++;
     ivx_sort_field f[2]; int nf = 0;
     if (pbits) f[nf++] = ivx_sort_field{0, 0, pbits};
@@ -422,16 +419,13 @@ ivx_status ivx_depth_device(ivx_ctx *ctx, const u32 *rkey, const u32 *rpos, cons
     const u64 E = evs.n;
     if (E == 0) return IVX_OK;
     hipStream_t st = ctx->stream;
-    u64 *sc = ctx->d_scalars, *hs = ctx->h_scalars;
     const u64 *ev = evs.ev; const uint2 *cg = evs.cg;
 
     // ---- scan 2 (its output pass writes the blocks)
     const BlkIn bin{ev, cg, E};
-    IVX_TRY((inclusive_f<BlkScan>(ctx, bin, BlkOut{bin, ok, os, oe, oc, cap, sc + DS_TOTAL}, E)));
+    IVX_TRY((inclusive_f<BlkScan>(ctx, bin, BlkOut{bin, ok, os, oe, oc, cap, ctx->dword(SC_DEPTH_TOTAL)}, E)));
     IVX_HIP(ctx, hipGetLastError());
-    IVX_HIP(ctx, hipMemcpyAsync(hs + DS_TOTAL, sc + DS_TOTAL, sizeof(u64), hipMemcpyDeviceToHost, st));
-    IVX_HIP(ctx, hipStreamSynchronize(st));
-    *n_out = hs[DS_TOTAL];
+    IVX_TRY(ctx->fetch_wait(SC_DEPTH_TOTAL, st, n_out));
     if (cap == 0 && !ok && !os && !oe && !oc) return IVX_OK;            // count only
     if (*n_out > cap) return ctx->fail(IVX_ERR_CAPACITY, "depth: output buffers too small");
     return IVX_OK;

@@ -27,7 +27,6 @@ constexpr int XW = XT / IVX_WAVE;
 static_assert(XT % IVX_WAVE == 0 && XT <= 1024, "one 16-byte coverage line per thread");
 
 constexpr int PT = 256;
-enum { PS_TOTAL = 11 };                         // scalar slot of the context (64-bit words)
 
 // ------------------------------------------------------------------------------------------------ events -> steps
 struct CntScan {
@@ -199,20 +198,19 @@ ivx_status ivx_depth_profile_finish(ivx_ctx *ctx, ivx_index *ix, const ivx_depth
     using namespace ivxscan;
     if (evs.n == 0) return IVX_OK;
     hipStream_t st = ctx->stream;
-    u64 *sc = ctx->d_scalars, *hs = ctx->h_scalars;
+    u64 *d_total = ctx->dword(SC_STEPS_TOTAL);
     const StepIn in{evs.ev, evs.cg, evs.n};
-    IVX_TRY((inclusive_f<CntScan>(ctx, in, StepOut{in, nullptr, nullptr, nullptr, sc + PS_TOTAL}, evs.n)));
+    IVX_TRY((inclusive_f<CntScan>(ctx, in, StepOut{in, nullptr, nullptr, nullptr, d_total}, evs.n)));
     IVX_HIP(ctx, hipGetLastError());
-    IVX_HIP(ctx, hipMemcpyAsync(hs + PS_TOTAL, sc + PS_TOTAL, sizeof(u64), hipMemcpyDeviceToHost, st));
-    IVX_HIP(ctx, hipStreamSynchronize(st));
-    const u64 S = hs[PS_TOTAL];
+    u64 S;
+    IVX_TRY(ctx->fetch_wait(SC_STEPS_TOTAL, st, &S));
     if (S == 0) return IVX_OK;
     if (S >= 0xFFFFFF00ull) return ctx->fail(IVX_ERR_INVALID, "depth profile: more than 2^32-257 steps");     // (the expand kernel's search is 32-bit)
     u32 *sk, *sp; i32 *sv;
     IVX_TRY(ivx_index_alloc(ctx, ix, S * sizeof(u32), (void **)&sk));
     IVX_TRY(ivx_index_alloc(ctx, ix, S * sizeof(u32), (void **)&sp));
     IVX_TRY(ivx_index_alloc(ctx, ix, S * sizeof(i32), (void **)&sv));
-    IVX_TRY((inclusive_f<CntScan>(ctx, in, StepOut{in, sk, sp, sv, sc + PS_TOTAL}, evs.n)));
+    IVX_TRY((inclusive_f<CntScan>(ctx, in, StepOut{in, sk, sp, sv, d_total}, evs.n)));
     u32 *koff = const_cast<u32 *>(ix->dp.koff);
     IVX_TRY(ivx_depth_profile_koff(ctx, sk, (u32)S, ix->nkeys, koff));
     ix->dp.key = sk; ix->dp.pos = sp; ix->dp.cov = sv; ix->dp.steps = S;

@@ -26,7 +26,6 @@ constexpr int MI = DEPTH_MERGE_TILE / MT;       // consecutive merged elements p
 static_assert(DEPTH_MERGE_TILE % MT == 0 && MT == ivxscan::T_, "whole elements per thread; the scan's workgroup size");
 
 constexpr int KT = 256;
-enum { MS_TOTAL = 11 };                         // scalar slot of the context (64-bit words)
 
 struct CntScan {
     using T = u32;
@@ -197,11 +196,9 @@ ivx_status ivx_depth_profile_merge_device(ivx_ctx *ctx, const DepthProfileView &
     IVX_HIP(ctx, hipGetLastError());
     IVX_TRY(ivx_scan_exclusive_u32(ctx, cnt, (u64)ntiles + 1));
     IVX_HIP(ctx, hipGetLastError());
-    u64 *hs = ctx->h_scalars;
-    hs[MS_TOTAL] = 0;
-    IVX_HIP(ctx, hipMemcpyAsync(hs + MS_TOTAL, cnt + ntiles, sizeof(u32), hipMemcpyDeviceToHost, st));
-    IVX_HIP(ctx, hipStreamSynchronize(st));
-    const u64 S = (u32)hs[MS_TOTAL];
+    u32 S32;
+    IVX_TRY(ctx->fetch_wait((const u32 *)cnt + ntiles, st, &S32));
+    const u64 S = S32;
     if (S == 0) return IVX_OK;
     u32 *sk, *sp; i32 *sv;
     IVX_TRY(ivx_index_alloc(ctx, ix, S * sizeof(u32), (void **)&sk));
@@ -222,17 +219,15 @@ ivx_status ivx_depth_profile_blocks_device(ivx_ctx *ctx, const DepthProfileView 
     *n_out = 0;
     if (dp.steps < 2) return IVX_OK;                        // (a key's last step never gives a block)
     hipStream_t st = ctx->stream;
-    u64 *sc = ctx->d_scalars, *hs = ctx->h_scalars;
+    u64 *d_total = ctx->dword(SC_BLOCKS_TOTAL);
     const BlockIn in{dp.key, dp.cov, dp.steps};
-    IVX_TRY((inclusive_f<CntScan>(ctx, in, BlockOut{in, dp.pos, nullptr, nullptr, nullptr, nullptr, false, sc + MS_TOTAL}, dp.steps)));
+    IVX_TRY((inclusive_f<CntScan>(ctx, in, BlockOut{in, dp.pos, nullptr, nullptr, nullptr, nullptr, false, d_total}, dp.steps)));
     IVX_HIP(ctx, hipGetLastError());
-    IVX_HIP(ctx, hipMemcpyAsync(hs + MS_TOTAL, sc + MS_TOTAL, sizeof(u64), hipMemcpyDeviceToHost, st));
-    IVX_HIP(ctx, hipStreamSynchronize(st));
-    *n_out = hs[MS_TOTAL];
+    IVX_TRY(ctx->fetch_wait(SC_BLOCKS_TOTAL, st, n_out));
     if (cap == 0 && !ok && !os && !oe && !oc) return IVX_OK;            // count only
     if (*n_out > cap) return ctx->fail(IVX_ERR_CAPACITY, "depth profile blocks: output buffers too small");
     if (*n_out == 0 || (!ok && !os && !oe && !oc)) return IVX_OK;
-    IVX_TRY((inclusive_f<CntScan>(ctx, in, BlockOut{in, dp.pos, ok, os, oe, oc, true, sc + MS_TOTAL}, dp.steps)));
+    IVX_TRY((inclusive_f<CntScan>(ctx, in, BlockOut{in, dp.pos, ok, os, oe, oc, true, d_total}, dp.steps)));
     IVX_HIP(ctx, hipGetLastError());
     return IVX_OK;
 }

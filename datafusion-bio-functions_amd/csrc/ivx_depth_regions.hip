@@ -30,7 +30,6 @@ constexpr int MAXT = 8;                         // IVX_DEPTH_MAX_THRESHOLDS
 static_assert(DEPTH_REGION_TILE % RT == 0 && RT % IVX_WAVE == 0 && 1 + MAXT <= RT, "whole steps per thread; a thread per aggregate word");
 static_assert(MAXT == IVX_DEPTH_MAX_THRESHOLDS, "the header's limit");
 
-enum { RS_BAD = 8 };                            // scalar slot of the context (64-bit words)
 constexpr u64 QUERY_CHUNK = (u64)RW << 23;      // regions per launch: the grid times the workgroup stays below 2^32 threads
 
 struct Thr { i32 t[MAXT]; u32 n; };
@@ -100,7 +99,7 @@ __global__ __launch_bounds__(RT) void k_region_check(const u32 *__restrict__ qke
 {
     for (u64 i = (u64)blockIdx.x * RT + threadIdx.x; i < n; i += (u64)gridDim.x * RT) {
         const u32 k = qkey[i];
-        if (k >= nkeys && k != IVX_NULL_IDX) sc[RS_BAD] = 1ull;
+        if (k >= nkeys && k != IVX_NULL_IDX) sc[SC_REGIONS_BAD] = 1ull;
     }
 }
 
@@ -271,13 +270,10 @@ ivx_status ivx_depth_regions_device(ivx_ctx *ctx, const DepthProfileView &dp, u3
     if (n == 0) return IVX_OK;
     if (qkey) {
         hipStream_t st = ctx->stream;
-        u64 *sc = ctx->d_scalars, *hs = ctx->h_scalars;
-        IVX_HIP(ctx, hipMemsetAsync(sc + RS_BAD, 0, sizeof(u64), st));
-        hipLaunchKernelGGL(k_region_check, dim3(ivx_stream_grid(n, RT)), dim3(RT), 0, st, qkey, n, nkeys, sc);
+        IVX_HIP(ctx, hipMemsetAsync(ctx->dword(SC_REGIONS_BAD), 0, sizeof(u64), st));
+        hipLaunchKernelGGL(k_region_check, dim3(ivx_stream_grid(n, RT)), dim3(RT), 0, st, qkey, n, nkeys, ctx->d_scalars);
         IVX_HIP(ctx, hipGetLastError());
-        IVX_HIP(ctx, hipMemcpyAsync(hs + RS_BAD, sc + RS_BAD, sizeof(u64), hipMemcpyDeviceToHost, st));
-        IVX_HIP(ctx, hipStreamSynchronize(st));
-        if (hs[RS_BAD]) return ctx->fail(IVX_ERR_INVALID, "depth profile: key id >= n_keys");
+        IVX_TRY(ctx->check_flag(SC_REGIONS_BAD, st, "depth profile: key id >= n_keys"));
     } else if (nkeys == 0) return ctx->fail(IVX_ERR_INVALID, "depth profile: key id >= n_keys");
     if (!out_len && !out_sum && !(out_ge && n_thr)) return IVX_OK;
     return region_query(ctx, dp, RegionsIn{qkey, qs, qe, key_hi, pos_lo}, qkey ? IVX_NULL_IDX : 0u, n, skip_pos0, make_thr(thresholds, n_thr), out_len, out_sum, out_ge);

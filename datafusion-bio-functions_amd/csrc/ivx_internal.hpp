@@ -20,8 +20,6 @@ typedef int64_t i64;
 struct ivx_buf { void *p = nullptr; size_t cap = 0; };
 
 enum { IVX_NSCRATCH = 56, IVX_NPIN = 4 };
-// h_scalars: the words that mirror d_scalars, then words of its own (IVX_HS_HDR: an overlap index's header, HDR_WORDS u32)
-enum { IVX_HS_HDR = 64, IVX_HS_WORDS = 80 };
 
 // What a subtract sizing call leaves behind for the fill call that follows it: the sorted sides, the right
 // side's running max / gap heads and the scanned per-row output counts all sit in scratch slots (`slots` =
@@ -69,7 +67,8 @@ struct ivx_routed {
     const unsigned short *cidx = nullptr;   // ... or its index inside its workgroup's chunk (per-row-value consumers: k_unpermute)
     const u32 *rfirst = nullptr;
     u32 nblk = 1, chunk = 0, ndig = 0;  // FLAT: workgroups of the partition, rows each took, digits of the histogram (256 / 1024)
-    const u32 *unsorted = nullptr;      // FLAT / TABLE: *unsorted == 0: the rows came in region order, nothing was moved (read ds / de in place)
+    const u32 *unsorted = nullptr;      // FLAT / TABLE: *unsorted == 0: the rows came in region order, nothing was moved (read ds / de in place);
+                                        // the context's word SC_UNSORTED (ivx_scalars.hpp), which is the routing pass's alone: a plan may hold this
     PageTab pt{nullptr, 0u, 0u};
     bool packed = false;                // 8-byte routed rows (start in region | length | row), else (start,end) + row id
     u32 rowbits = 32;                   // bits of a packed row's id (the rest of the word's upper half extends the length)
@@ -106,10 +105,21 @@ struct ivx_ctx {
     std::string err;
     ivx_buf scratch[IVX_NSCRATCH];      // grow-only device scratch, one slot per use
     ivx_buf pinned[IVX_NPIN];           // grow-only pinned host staging
-    u64 *d_scalars = nullptr;           // 64 device words for counters / totals
-    u64 *h_scalars = nullptr;           // pinned mirror: mapped and coherent, so that a kernel can leave a few words in it itself
-    u64 *hd_scalars = nullptr;          // ... its device pointer (words 0..1: a lean fill's pair total and fault word; from word IVX_HS_HDR: the
-                                        // header of the overlap index built last, ivx_join_build -- words nothing else uses)
+    // the scalar words: ivx_scalars.hpp names every one of them (SC_*) and says whose it is
+    u64 *d_scalars = nullptr;           // SC_DEVICE_WORDS device words for flags / counters / totals
+    u64 *h_scalars = nullptr;           // SC_HOST_WORDS words, the pinned mirror: mapped and coherent, so that a kernel can leave a few words in it itself
+    u64 *hd_scalars = nullptr;          // ... its device pointer (SC_PAIRS / SC_FAULT: a lean fill's totals; SC_HDR_MIRROR: the header of the overlap
+                                        // index built last)
+    template <typename T = u64> T *dword(int w) const { return (T *)(d_scalars + w); }     // device word w, and its mirror word
+    template <typename T = u64> T *hword(int w) const { return (T *)(h_scalars + w); }
+    template <typename T = u64> T *hdword(int w) const { return (T *)(hd_scalars + w); }   // the mirror word, for a kernel
+    // queue the copy of device words w .. w + words - 1 into their mirror words; of `bytes` device bytes at src into mirror word w
+    hipError_t fetch(int w, hipStream_t st, int words = 1) { return hipMemcpyAsync(h_scalars + w, d_scalars + w, words * sizeof(u64), hipMemcpyDeviceToHost, st); }
+    hipError_t fetch(int w, const void *src, size_t bytes, hipStream_t st) { return hipMemcpyAsync(h_scalars + w, src, bytes, hipMemcpyDeviceToHost, st); }
+    // ... and wait for it: *out = device word w, as a T; = *src (device memory), landed in SC_LANDING
+    template <typename T> ivx_status fetch_wait(int w, hipStream_t st, T *out);
+    template <typename T> ivx_status fetch_wait(const T *src, hipStream_t st, T *out);
+    ivx_status check_flag(int w, hipStream_t st, const char *what);    // fetch_wait of a u32 flag: IVX_ERR_INVALID with `what` if it is raised
     u64 hdr_mirror_serial = 0;          // the index whose header that is (its HDR_SLOW arrives with the build's tail: ivx_join_probe_regions)
     ivx_sub_plan sub_plan;
     ivx_join_plan join_plan;
@@ -186,7 +196,7 @@ enum { HDR_SH0 = 0, HDR_NLEV = 1, HDR_NBINS = 2, HDR_CS = 3 /* log2(cells per re
        HDR_LBUILD = 12 + IVX_MAXL /* 1: the build's tail sorts every region's rows in LDS (ivx_join.hip: k_lbuild_*); 0: the global counting sort */,
        HDR_BADKEY = 13 + IVX_MAXL /* != 0: a build row's key id is >= n_keys (the key statistics' flag: one copy brings it to the host with the layout) */,
        HDR_WORDS = 14 + IVX_MAXL };
-static_assert(IVX_HS_HDR * sizeof(u64) + HDR_WORDS * sizeof(u32) <= IVX_HS_WORDS * sizeof(u64), "the header mirror fits the host words");
+#include "ivx_scalars.hpp"
 // Occupancy bitmap of the build side ("can a probe row match anything at all"): per key one bit per 2^g-wide block of
 // [origin, origin + span] plus one overflow block behind it; a bit is set when some build row touches the block.  Sized to
 // stay resident in an XCD's 4 MiB L2 next to the streamed probe rows.
@@ -307,7 +317,7 @@ enum { JP_COUNT = 0, JP_PER_ROW = 1, JP_EXISTS = 2, JP_FILL = 3 };
 struct ivx_probe_note {
     u64 ix_serial = 0;          // in: the index probed (fast == 2: is the context's header mirror this index's?)
     int fast = -1;              // out: 0 / 1 when the call came in with fast == 2 and learnt hdr[HDR_SLOW] on the host, else -1
-    bool totals_on_host = false;    // out: the call's last kernel leaves d_cursor[0..1] in h_scalars[0..1] itself (no copy needed, only the synchronisation)
+    bool totals_on_host = false;    // out: the call's last kernel leaves d_cursor[0..1] in the mirror words SC_PAIRS / SC_FAULT itself (no copy needed, only the synchronisation)
 };
 ivx_status ivx_join_probe_regions(ivx_ctx *ctx, const JoinIndexView &jv, u32 nreg, int mode,
                                   const u32 *key, const i32 *s, const i32 *e, u64 n,

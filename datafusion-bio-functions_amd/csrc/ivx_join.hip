@@ -673,14 +673,14 @@ ivx_status ivx_route_view_build(ivx_ctx *ctx, ivx_index *ix, const i32 *origin, 
     IVX_TRY(ivx_index_alloc(ctx, ix, HDR_WORDS * sizeof(u32), (void **)&rhdr));
     IVX_HIP(ctx, hipMemsetAsync(rhdr, 0, HDR_WORDS * sizeof(u32), st));
     hipLaunchKernelGGL(k_nroute_layout, dim3(1), dim3(1024), 0, st, origin, span, kcnt, nkeys, kreg, rkey, rhdr);
-    IVX_HIP(ctx, hipMemcpyAsync(ctx->h_scalars + 48, rhdr, HDR_WORDS * sizeof(u32), hipMemcpyDeviceToHost, st));
+    IVX_HIP(ctx, ctx->fetch(SC_ROUTE_HDR, rhdr, HDR_WORDS * sizeof(u32), st));
     ix->nroute = JoinIndexView{};
     ix->nroute.origin = origin; ix->nroute.span = span; ix->nroute.kcnt = kcnt; ix->nroute.kreg = kreg; ix->nroute.rkey = rkey;
     ix->nroute.hdr = rhdr; ix->nroute.nkeys = nkeys;
     IVX_HIP(ctx, hipGetLastError());
     return IVX_OK;
 }
-void ivx_route_view_ready(ivx_ctx *ctx, ivx_index *ix) { ix->nroute_nreg = ((const u32 *)(ctx->h_scalars + 48))[HDR_NREG]; }
+void ivx_route_view_ready(ivx_ctx *ctx, ivx_index *ix) { ix->nroute_nreg = ctx->hword<u32>(SC_ROUTE_HDR)[HDR_NREG]; }
 
 // rle_right / exists of a big probe batch on an index with too many regions for the LDS-slice pipeline
 ivx_status ivx_join_rowval_routed(ivx_ctx *ctx, const ivx_index *ix, int mode, const u32 *key, const i32 *s, const i32 *e, u64 n,
@@ -745,10 +745,10 @@ ivx_status ivx_join_build(ivx_ctx *ctx, ivx_index *ix, const u32 *key, const i32
     IVX_TRY(ctx->get_scratch(WS_GRID2, (n ? n : 1) * (lb_try ? sizeof(ivx_ent) : sizeof(u32)), (void **)&cellid));
     const size_t tabbytes = (size_t)lb_tstride(lb_tiles) * LB_STRIDE * sizeof(u32);
     IVX_TRY(ctx->get_scratch(WS_T9, (n ? n : 1) * sizeof(u32) > tabbytes ? (n ? n : 1) * sizeof(u32) : tabbytes, (void **)&rank));
-    errflag = (u32 *)(ctx->d_scalars + 8);
-    u32 *lenhist = (u32 *)(ctx->d_scalars + 32);                        // 33 counters
+    errflag = ctx->dword<u32>(SC_JOIN_BAD);
+    u32 *lenhist = ctx->dword<u32>(SC_JOIN_LENHIST);                    // 33 counters
 
-    ivx_zero_ranges zr{{errflag, lenhist, hdr}, {1u, 34u, (u32)HDR_WORDS}};     // cleared by the key-statistics' first kernel
+    ivx_zero_ranges zr{{errflag, lenhist, hdr}, {1u, (u32)SC_LENHIST_N, (u32)HDR_WORDS}};     // cleared by the key-statistics' first kernel
     // IVX_FILTER=0: no occupancy bitmap; =force: whenever it fits (tests); default: when it would reject most probe rows
     const char *fenv = getenv("IVX_FILTER");
     const int filter_mode = !fenv ? 1 : !strcmp(fenv, "0") ? 0 : !strcmp(fenv, "force") ? 2 : 1;
@@ -758,7 +758,7 @@ ivx_status ivx_join_build(ivx_ctx *ctx, ivx_index *ix, const u32 *key, const i32
     // (every row's atomic returns a value, its loads depend on nothing: a row or two per thread, not a loop of eight round trips)
     const u32 grid = ivx_stream_grid(n, BT * 2, 16384);
     // the header's host mirror (k_join_layout, k_join_regdesc): this index's from here on
-    u32 *hmirror = (u32 *)(ctx->h_scalars + IVX_HS_HDR), *hmirror_d = (u32 *)(ctx->hd_scalars + IVX_HS_HDR);
+    u32 *hmirror = ctx->hword<u32>(SC_HDR_MIRROR), *hmirror_d = ctx->hdword<u32>(SC_HDR_MIRROR);
     ctx->hdr_mirror_serial = ix->serial;
     hipLaunchKernelGGL(k_join_layout, dim3(1), dim3(1024), 0, st, kmin, kmax, kcnt, nkeys, n, origin, span, lbase, hdr, maxcells, kreg, rkey, (const u32 *)lenhist, (u32)(regcap - 1), fbase, filter_mode, lb_try ? 1 : 0, (const u32 *)errflag, hmirror_d);
     auto launch_filter = [&]() {

@@ -96,14 +96,11 @@ ivx_status ivx_bits_mark_device(ivx_ctx *ctx, const u32 *idx, u64 n, u32 *bits, 
 {
     if (n == 0) return IVX_OK;
     hipStream_t st = ctx->stream;
-    u32 *bad = (u32 *)(ctx->d_scalars + 8);                            // the out-of-range flag, as the take kernels'
-    IVX_HIP(ctx, hipMemsetAsync(ctx->d_scalars + 8, 0, sizeof(u64), st));
+    u32 *bad = ctx->dword<u32>(SC_MARK_BAD);                           // the out-of-range flag, as the take kernels'
+    IVX_HIP(ctx, hipMemsetAsync(bad, 0, sizeof(u64), st));
     hipLaunchKernelGGL(k_bits_mark, dim3(ivx_stream_grid(n, MT * 4, 256 * 16)), dim3(MT), 0, st, idx, n, bits, n_bits, bad);
     IVX_HIP(ctx, hipGetLastError());
-    IVX_HIP(ctx, hipMemcpyAsync(ctx->h_scalars + 8, ctx->d_scalars + 8, sizeof(u64), hipMemcpyDeviceToHost, st));
-    IVX_HIP(ctx, hipStreamSynchronize(st));
-    if (*(u32 *)(ctx->h_scalars + 8)) return ctx->fail(IVX_ERR_INVALID, "bits_mark: index out of bounds");
-    return IVX_OK;
+    return ctx->check_flag(SC_MARK_BAD, st, "bits_mark: index out of bounds");
 }
 
 // out == nullptr: count only.  *n_out = the positions there are; more than cap: IVX_ERR_CAPACITY, nothing written
@@ -121,10 +118,9 @@ ivx_status ivx_bits_select_device(ivx_ctx *ctx, const u32 *bits, u64 n_bits, int
     hipLaunchKernelGGL(k_bits_count, dim3((u32)nblk), dim3(MT), 0, st, bits, nw, n_bits, flip, counts);
     IVX_TRY(ivx_scan_exclusive_u32(ctx, counts, nblk + 1));            // counts[nblk] = the total
     IVX_HIP(ctx, hipGetLastError());
-    ctx->h_scalars[12] = 0;
-    IVX_HIP(ctx, hipMemcpyAsync(ctx->h_scalars + 12, counts + nblk, sizeof(u32), hipMemcpyDeviceToHost, st));
-    IVX_HIP(ctx, hipStreamSynchronize(st));
-    const u64 total = ctx->h_scalars[12];
+    u32 total32;
+    IVX_TRY(ctx->fetch_wait((const u32 *)counts + nblk, st, &total32));
+    const u64 total = total32;
     *n_out = total;
     if (out == nullptr && cap == 0) return IVX_OK;
     if (total > cap) return ctx->fail(IVX_ERR_CAPACITY, "bits_select: output buffer too small");

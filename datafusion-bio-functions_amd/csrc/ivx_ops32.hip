@@ -23,14 +23,7 @@ constexpr u32 SIGN = 0x80000000u;
 __device__ __forceinline__ i32 wadd(i32 a, i32 b) { return (i32)((u32)a + (u32)b); }
 __device__ __forceinline__ i32 wsub(i32 a, i32 b) { return (i32)((u32)a - (u32)b); }
 
-ivx_status check_keyflag(ivx_ctx *ctx)
-{
-    u32 *errflag = (u32 *)(ctx->d_scalars + 8);
-    IVX_HIP(ctx, hipMemcpyAsync(ctx->h_scalars + 8, errflag, sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
-    IVX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (*(u32 *)(ctx->h_scalars + 8)) return ctx->fail(IVX_ERR_INVALID, "build key id >= n_keys");
-    return IVX_OK;
-}
+ivx_status check_keyflag(ivx_ctx *ctx) { return ctx->check_flag(SC_BUILD_FLAG, ctx->stream, "build key id >= n_keys"); }
 
 // ======================================================================= a4
 
@@ -654,15 +647,15 @@ ivx_status nearest_sorted_records_lin(ivx_ctx *ctx, const u32 *key, const i32 *s
     IVX_TRY(ctx->get_scratch(WS_GRID1, nkeys * sizeof(i32), (void **)&kmax));
     IVX_TRY(ctx->get_scratch(WS_T3, nkeys * sizeof(i32), (void **)&origin));
     IVX_TRY(ctx->get_scratch(WS_T4, ((size_t)nkeys + 1) * sizeof(u64), (void **)&base));
-    u32 *flags = (u32 *)(ctx->d_scalars + 8);                           // [0] bad key, [1] unsorted / run too long
-    u32 *hdr = (u32 *)(ctx->d_scalars + 10);
+    u32 *flags = ctx->dword<u32>(SC_BUILD_FLAG);                        // [0] bad key, [1] unsorted / run too long
+    u32 *hdr = ctx->dword<u32>(SC_NEAR_HDR);
     hipLaunchKernelGGL(k_init_minmax, dim3((nkeys + OT - 1) / OT), dim3(OT), 0, st, kmin, kmax, nkeys);
     const size_t shm = nkeys <= NLIN_KEYS_LDS ? (size_t)nkeys * 8 : 0;
     hipLaunchKernelGGL(k_nstats, dim3(ivx_stream_grid(n, OT * 16, 4096)), dim3(OT), shm, st, key, s, e, n, nkeys, kmin, kmax, flags);
     hipLaunchKernelGGL(k_nlin_layout, dim3(1), dim3(1024), 0, st, (const i32 *)kmin, (const i32 *)kmax, nkeys, n, origin, base, hdr);
-    IVX_HIP(ctx, hipMemcpyAsync(ctx->h_scalars + 8, ctx->d_scalars + 8, 4 * sizeof(u64), hipMemcpyDeviceToHost, st));
+    IVX_HIP(ctx, ctx->fetch(SC_BUILD_FLAG, st, SC_BUILD_WORDS));     // the flags and the header
     IVX_HIP(ctx, hipStreamSynchronize(st));
-    const u32 *hf = (const u32 *)(ctx->h_scalars + 8), *hh = (const u32 *)(ctx->h_scalars + 10);
+    const u32 *hf = ctx->hword<u32>(SC_BUILD_FLAG), *hh = ctx->hword<u32>(SC_NEAR_HDR);
     if (hf[0]) return ctx->fail(IVX_ERR_INVALID, "build key id >= n_keys");
     const bool presorted = hf[1] == 0 && !getenv("IVX_FORCE_SORT");
     const u32 linbits = hh[0], rowbits = hh[1];
@@ -683,7 +676,7 @@ ivx_status nearest_sorted_records_lin(ivx_ctx *ctx, const u32 *key, const i32 *s
     a[0] = y; b[0] = w;
     IVX_TRY(ivx_radix_sort(ctx, 1, a, b, n, f, 1, &in_b, true));
     hipLaunchKernelGGL(k_unpack_lin_end, dim3(grid1(n)), dim3(OT), 0, st, (const u64 *)(in_b ? b[0] : a[0]), n, rowbits, (const ivx_nrec *)rs, re);
-    IVX_HIP(ctx, hipMemcpyAsync(ctx->h_scalars + 8, ctx->d_scalars + 8, sizeof(u64), hipMemcpyDeviceToHost, st));
+    IVX_HIP(ctx, ctx->fetch(SC_BUILD_FLAG, st));
     IVX_HIP(ctx, hipStreamSynchronize(st));
     if (hf[1]) return IVX_OK;                                           // a run of equal (key, start) beyond NLIN_MAXRUN rows
     IVX_HIP(ctx, hipGetLastError());
@@ -703,20 +696,19 @@ ivx_status nearest_sorted_records(ivx_ctx *ctx, const u32 *key, const i32 *s, co
         bool done = false;
         IVX_TRY(nearest_sorted_records_lin(ctx, key, s, e, n, nkeys, ks, rs, re, &done));
         if (done) return IVX_OK;
-        IVX_HIP(ctx, hipMemsetAsync(ctx->d_scalars + 8, 0, sizeof(u64), ctx->stream));
+        IVX_HIP(ctx, hipMemsetAsync(ctx->dword(SC_BUILD_FLAG), 0, sizeof(u64), ctx->stream));
     }
     u64 *a[2], *b[2];
     IVX_TRY(ctx->get_scratch(WS_SA0, n * sizeof(u64), (void **)&a[0]));
     IVX_TRY(ctx->get_scratch(WS_SA1, n * sizeof(u64), (void **)&a[1]));
     IVX_TRY(ctx->get_scratch(WS_SB0, n * sizeof(u64), (void **)&b[0]));
     IVX_TRY(ctx->get_scratch(WS_SB1, n * sizeof(u64), (void **)&b[1]));
-    u32 *flags = (u32 *)(ctx->d_scalars + 8);
+    u32 *flags = ctx->dword<u32>(SC_BUILD_FLAG);
+    const u32 *hf = ctx->hword<u32>(SC_BUILD_FLAG);
     hipLaunchKernelGGL(k_pack_se, dim3(grid1(n)), dim3(OT), 0, ctx->stream, key, s, e, n, nkeys, a[0], a[1], flags);
     // build rows that already come in (key,start,end) order need no first sort
-    IVX_HIP(ctx, hipMemcpyAsync(ctx->h_scalars + 8, flags, sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
-    IVX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (((const u32 *)(ctx->h_scalars + 8))[0]) return ctx->fail(IVX_ERR_INVALID, "build key id >= n_keys");
-    const bool presorted = ((const u32 *)(ctx->h_scalars + 8))[1] == 0 && !getenv("IVX_FORCE_SORT");
+    IVX_TRY(check_keyflag(ctx));
+    const bool presorted = hf[1] == 0 && !getenv("IVX_FORCE_SORT");
     int in_b = 0;
     if (!presorted) {
         // (key,start) first -- equal (key,start) rows are rare -- then the short runs by end in place; all three
@@ -728,9 +720,9 @@ ivx_status nearest_sorted_records(ivx_ctx *ctx, const u32 *key, const i32 *s, co
             u64 *const *o = in_b ? b : a;
             IVX_HIP(ctx, hipMemsetAsync(flags + 1, 0, sizeof(u32), ctx->stream));
             hipLaunchKernelGGL(k_fix_runs_se, dim3(grid1(n)), dim3(OT), 0, ctx->stream, o[0], o[1], n, flags + 1);
-            IVX_HIP(ctx, hipMemcpyAsync(ctx->h_scalars + 8, flags, sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
+            IVX_HIP(ctx, ctx->fetch(SC_BUILD_FLAG, ctx->stream));
             IVX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            done = ((const u32 *)(ctx->h_scalars + 8))[1] == 0;
+            done = hf[1] == 0;
             if (!done) {
                 IVX_HIP(ctx, hipMemsetAsync(flags + 1, 0, sizeof(u32), ctx->stream));
                 hipLaunchKernelGGL(k_pack_se, dim3(grid1(n)), dim3(OT), 0, ctx->stream, key, s, e, n, nkeys, a[0], a[1], flags);
@@ -767,14 +759,14 @@ ivx_status ivx_count_build(ivx_ctx *ctx, ivx_index *ix, const u32 *key, const i3
     // predicate matches as long as no build row has end < start, and then big probe batches can take the
     // region-partitioned path (validates the key ids too)
     IVX_TRY(ivx_join_build(ctx, ix, key, s, e, n));
-    IVX_HIP(ctx, hipMemsetAsync(ctx->d_scalars + 8, 0, 2 * sizeof(u64), ctx->stream));
-    if (n) hipLaunchKernelGGL(k_any_inverted, dim3(grid1(n)), dim3(OT), 0, ctx->stream, s, e, n, (u32 *)(ctx->d_scalars + 9));
+    IVX_HIP(ctx, hipMemsetAsync(ctx->dword(SC_BUILD_FLAG), 0, 2 * sizeof(u64), ctx->stream));      // and SC_BUILD_INVERTED
+    if (n) hipLaunchKernelGGL(k_any_inverted, dim3(grid1(n)), dim3(OT), 0, ctx->stream, s, e, n, ctx->dword<u32>(SC_BUILD_INVERTED));
     IVX_TRY(ivx_grid_build(ctx, ix, key, s, n, ix->nkeys, &ix->gs));     // starts, sorted independently (:35)
     IVX_TRY(ivx_grid_build(ctx, ix, key, e, n, ix->nkeys, &ix->ge));     // ends (:36)
     IVX_TRY(build_route_view(ctx, ix, ix->gs));
-    IVX_HIP(ctx, hipMemcpyAsync(ctx->h_scalars + 9, ctx->d_scalars + 9, sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
+    IVX_HIP(ctx, ctx->fetch(SC_BUILD_INVERTED, ctx->stream));
     IVX_TRY(check_keyflag(ctx));                                          // synchronises
-    if (*(u32 *)(ctx->h_scalars + 9) == 0) ix->flags |= IVX_IXF_REGION_ROWVAL;
+    if (*ctx->hword<u32>(SC_BUILD_INVERTED) == 0) ix->flags |= IVX_IXF_REGION_ROWVAL;
     route_view_ready(ctx, ix);
     return IVX_OK;
 }
@@ -783,7 +775,7 @@ ivx_status ivx_coverage_build(ivx_ctx *ctx, ivx_index *ix, const u32 *key, const
 {
     hipStream_t st = ctx->stream;
     const u32 nkeys = ix->nkeys;
-    u32 *flags = (u32 *)(ctx->d_scalars + 8);
+    u32 *flags = ctx->dword<u32>(SC_BUILD_FLAG);
     IVX_HIP(ctx, hipMemsetAsync(flags, 0, sizeof(u64), st));
     u64 m = 0;
     i64 *rs = nullptr, *re = nullptr; u32 *rk = nullptr;
@@ -810,11 +802,8 @@ ivx_status ivx_coverage_build(ivx_ctx *ctx, ivx_index *ix, const u32 *key, const
         ivx_runs_out ro{rk, rs, re, nullptr};
         IVX_TRY(ivx_merge_runs(ctx, ks, ss, es, n, 0, 0, ro, &m));       // first <= current.last merges (:63)
     }
-    IVX_HIP(ctx, hipMemcpyAsync(ctx->h_scalars + 8, flags, sizeof(u64), hipMemcpyDeviceToHost, st));
-    IVX_HIP(ctx, hipStreamSynchronize(st));
-    const u32 *hf = (const u32 *)(ctx->h_scalars + 8);
-    if (hf[0]) return ctx->fail(IVX_ERR_INVALID, "build key id >= n_keys");
-    if (hf[1]) return ctx->fail(IVX_ERR_UNSUPPORTED, "coverage: a build interval has end < start (the reference's result for it is unspecified)");
+    IVX_TRY(check_keyflag(ctx));
+    if (ctx->hword<u32>(SC_BUILD_FLAG)[1]) return ctx->fail(IVX_ERR_UNSUPPORTED, "coverage: a build interval has end < start (the reference's result for it is unspecified)");
     i32 *nfirst, *nlast; u64 *pw;
     IVX_TRY(ivx_index_alloc(ctx, ix, (m ? m : 1) * sizeof(i32), (void **)&nfirst));
     IVX_TRY(ivx_index_alloc(ctx, ix, (m ? m : 1) * sizeof(i32), (void **)&nlast));
@@ -837,7 +826,7 @@ ivx_status ivx_nearest_build(ivx_ctx *ctx, ivx_index *ix, const u32 *key, const 
 {
     hipStream_t st = ctx->stream;
     const u32 nkeys = ix->nkeys;
-    IVX_HIP(ctx, hipMemsetAsync(ctx->d_scalars + 8, 0, sizeof(u64), st));
+    IVX_HIP(ctx, hipMemsetAsync(ctx->dword(SC_BUILD_FLAG), 0, sizeof(u64), st));
     const u64 na = n ? n : 1;
     ivx_nrec *rs, *re; u32 *ks;
     IVX_TRY(ivx_index_alloc(ctx, ix, na * sizeof(ivx_nrec), (void **)&rs));
@@ -960,9 +949,8 @@ ivx_status ivx_nearest_probe(ivx_ctx *ctx, const ivx_index *ix, const u32 *key, 
     hipLaunchKernelGGL(k_probe_nearestk, dim3(ivx_stream_grid(n, OT * 2)), dim3(OT), 0, st, ix->nv, key, s, e, n, strict, include_overlaps, k, tmp, tmpd, cnt);
     hipLaunchKernelGGL(k_rows_of, dim3(grid1(n + 1)), dim3(OT), 0, st, (const u32 *)cnt, n, offs);
     IVX_TRY(ivx_scan_exclusive_u64(ctx, offs, n + 1));
-    IVX_HIP(ctx, hipMemcpyAsync(ctx->h_scalars + 3, offs + n, sizeof(u64), hipMemcpyDeviceToHost, st));
-    IVX_HIP(ctx, hipStreamSynchronize(st));
-    const u64 total = ctx->h_scalars[3];
+    u64 total;
+    IVX_TRY(ctx->fetch_wait((const u64 *)offs + n, st, &total));
     *rows = total;
     if (total > cap) return ctx->fail(IVX_ERR_CAPACITY, "nearest: output buffers too small");
     hipLaunchKernelGGL(k_nearest_emit, dim3(ivx_stream_grid(n, OT * 2)), dim3(OT), 0, st, n, k, (const u32 *)tmp, (const i64 *)tmpd, (const u32 *)cnt, (const u64 *)offs, cap, ob, op, od);

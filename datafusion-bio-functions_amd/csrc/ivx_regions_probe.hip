@@ -1490,7 +1490,7 @@ ivx_status probe_pairs(ivx_ctx *ctx, const JoinIndexView &jv, u32 nreg, int mode
     // pairs per ROUTED row: known here when every row was routed; with the occupancy bitmap in use the count sits on the
     // device, k_pick_rows decides there and every variant is launched (three exit)
     const bool paged = R.form == IVX_ROWS_PAGED;
-    u32 *bsel = paged && !R.all_routed ? (u32 *)(ctx->d_scalars + 11) : nullptr;
+    u32 *bsel = paged && !R.all_routed ? ctx->dword<u32>(SC_BSEL) : nullptr;
     if (bsel) IVX_TRY(tables());
     if (bsel) hipLaunchKernelGGL(k_pick_rows, dim3(1), dim3(1), 0, st, R.rfirst, nreg, hint, K.rp_rows ? (u32)atoi(K.rp_rows) : 0u, bsel);
     auto every_b = [&](auto &&f) {
@@ -1514,7 +1514,7 @@ ivx_status probe_pairs(ivx_ctx *ctx, const JoinIndexView &jv, u32 nreg, int mode
             }, drain != 0);
         });
         hipLaunchKernelGGL(k_fill_rest, dim3(512), dim3(256), 0, st, jv, R.se, R.pt, (const FpRest *)R.rest, (const u64 *)R.rest_rows, (const u32 *)rest_n, ob, op, cap, cur, R.ds, R.de, R.rowbits,
-                           &R.ctl->fill_done, publish ? ctx->hd_scalars : (u64 *)nullptr);
+                           &R.ctl->fill_done, publish ? ctx->hdword(SC_PAIRS) : (u64 *)nullptr);
         IVX_HIP(ctx, hipGetLastError());
         if (publish) note->totals_on_host = true;
         if (fast == 1) return IVX_OK;
@@ -1568,7 +1568,7 @@ ivx_status ivx_join_probe_regions(ivx_ctx *ctx, const JoinIndexView &jv, u32 nre
             // kernel, not both with the device choosing, and the index's later calls know.
             if (fast == 2 && ready != nullptr && note != nullptr && note->ix_serial != 0 && ctx->hdr_mirror_serial == note->ix_serial) {
                 IVX_HIP(ctx, hipEventSynchronize(ready));
-                fast = ((const u32 *)(ctx->h_scalars + IVX_HS_HDR))[HDR_SLOW] == 0 ? 1 : 0;
+                fast = ctx->hword<u32>(SC_HDR_MIRROR)[HDR_SLOW] == 0 ? 1 : 0;
                 note->fast = fast;
             }
         }

@@ -971,7 +971,7 @@ ivx_status ivx_route_flat(ivx_ctx *ctx, const JoinIndexView &jv, const u32 *key,
     IVX_TRY(ctx->get_scratch(WS_SORTHIST, nh * sizeof(u32), (void **)&hist));
     IVX_TRY(ctx->get_scratch(WS_T0, n * sizeof(u64), (void **)&pse));
     IVX_TRY(ctx->get_scratch(WS_T1, n * (ids16 ? sizeof(unsigned short) : sizeof(u32)), &ids));
-    u32 *unsorted = (u32 *)(ctx->d_scalars + 10);                       // stays 0 if the rows already come in region order
+    u32 *unsorted = ctx->dword<u32>(SC_UNSORTED);                      // stays 0 if the rows already come in region order
     IVX_HIP(ctx, hipMemsetAsync(hist + (nh - 1), 0, sizeof(u32), st));
     IVX_HIP(ctx, hipMemsetAsync(unsorted, 0, sizeof(u32), st));
     ivx_status scan = IVX_OK;
@@ -1065,7 +1065,7 @@ ivx_status ivx_route_paged_bounds(ivx_ctx *ctx, const ivx_routed &R, u32 nreg)
 ivx_status ivx_route_two_level(ivx_ctx *ctx, const JoinIndexView &jv, u32 nreg, const u32 *key, const i32 *s, const i32 *e, u64 n, ivx_routed *R)
 {
     hipStream_t st = ctx->stream;
-    u32 *unsorted = (u32 *)(ctx->d_scalars + 10);
+    u32 *unsorted = ctx->dword<u32>(SC_UNSORTED);
     const u32 G = (nreg + IVX_MAXREG_WIDE - 1) / IVX_MAXREG_WIDE;       // regions per super-region
     if (G > P2_SUBMAX) return ctx->fail(IVX_ERR_INVALID, "overlap index with too many probe regions");
     const u32 nsuper = (nreg + G - 1) / G;

@@ -233,12 +233,12 @@ static ivx_status sweep(ivx_ctx *ctx, const SortedRows &rows, u64 n,
     const CurEnd ce{cur_end, (rows.s32 != nullptr && !want_ha) ? (u32 *)cur_end : nullptr, rows.min_e};
     hipLaunchKernelGGL(k_merge_apply, dim3((u32)nblk), dim3(T_), 0, stq, in, CurEndOut{ce}, n, nblk > 1 ? (const MState *)sums : (const MState *)nullptr, hsums);
     if (nblk > 1) IVX_TRY((scan_rec<HeadOp, false>(ctx, hsums, nblk, 1, WS_SCAN0)));
-    u64 *d_m = ctx->d_scalars + 2;
+    u64 *d_m = ctx->dword(SC_RUNS);
     const HeadIn hin{rows, ce, min_dist, strict};
     const HeadEmitOut hout{ha, rows, ce, min_dist, strict, n, out, d_m};
     hipLaunchKernelGGL(k_head_apply, dim3((u32)nblk), dim3(T_), 0, stq, hin, hout, n, nblk > 1 ? (const HeadAcc *)hsums : (const HeadAcc *)nullptr);
     IVX_HIP(ctx, hipGetLastError());
-    IVX_HIP(ctx, hipMemcpyAsync(ctx->h_scalars + 2, d_m, sizeof(u64), hipMemcpyDeviceToHost, stq));
+    IVX_HIP(ctx, ctx->fetch(SC_RUNS, stq));
     *ha_out = ha;
     (void)m;
     return IVX_OK;
@@ -639,7 +639,7 @@ ivx_status runs_packed(ivx_ctx *ctx, const u64 *w, u64 n, const Pack64 &p, i64 m
     const u64 ntile = (n + FTILE - 1) / FTILE;
     u64 *agg;                                                           // [0, ntile): V maxima, [ntile, 2 ntile): head summaries
     IVX_TRY(ctx->get_scratch(WS_T5, 2 * ntile * sizeof(u64), (void **)&agg));
-    u64 *d_m = ctx->d_scalars + 2;
+    u64 *d_m = ctx->dword(SC_RUNS);
     const size_t tab = LIN ? ((size_t)p.nkeys * 2 + 1) * sizeof(u64) : 0;
     u32 bk = 0;
     for (u64 x = p.nkeys ? p.nkeys - 1 : 0; x; x >>= 1) bk++;
@@ -700,9 +700,7 @@ ivx_status ivx_merge_runs_packed(ivx_ctx *ctx, const u64 *w, u64 n, const Pack64
     if (n == 0) return IVX_OK;
     if (p.lin) IVX_TRY(runs_packed<true>(ctx, w, n, p, min_dist, strict, out, nullptr));
     else IVX_TRY(runs_packed<false>(ctx, w, n, p, min_dist, strict, out, nullptr));
-    IVX_HIP(ctx, hipMemcpyAsync(ctx->h_scalars + 2, ctx->d_scalars + 2, sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
-    IVX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    *m = ctx->h_scalars[2];
+    IVX_TRY(ctx->fetch_wait(SC_RUNS, ctx->stream, m));
     return IVX_OK;
 }
 
@@ -720,7 +718,7 @@ ivx_status ivx_merge_runs_rows(ivx_ctx *ctx, const SortedRows &rows, u64 n, i64 
     const HeadAcc *ha;
     IVX_TRY(sweep(ctx, rows, n, min_dist, strict, out, &ha, m, false));
     IVX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    *m = ctx->h_scalars[2];
+    *m = *ctx->hword(SC_RUNS);
     return IVX_OK;
 }
 
@@ -790,9 +788,8 @@ ivx_status ivx_cluster_rows_packed(ivx_ctx *ctx, const u64 *w, const Pack64 &p, 
     if (out.key_clusters)
         hipLaunchKernelGGL(k_key_clusters, dim3((nkeys + RT - 1) / RT), dim3(RT), 0, stq, (const u32 *)kfirst, (const u32 *)klast, nkeys, out.key_clusters);
     IVX_HIP(ctx, hipGetLastError());
-    IVX_HIP(ctx, hipMemcpyAsync(ctx->h_scalars + 2, ctx->d_scalars + 2, sizeof(u64), hipMemcpyDeviceToHost, stq));
-    IVX_HIP(ctx, hipStreamSynchronize(stq));
-    *m = n ? ctx->h_scalars[2] : 0;
+    IVX_TRY(ctx->fetch_wait(SC_RUNS, stq, m));
+    if (!n) *m = 0;
     return IVX_OK;
 }
 
@@ -822,6 +819,6 @@ ivx_status ivx_cluster_rows(ivx_ctx *ctx, const u32 *ks, const i64 *ss, const i6
         hipLaunchKernelGGL(k_key_clusters, dim3((nkeys + RT - 1) / RT), dim3(RT), 0, stq, (const u32 *)kfirst, (const u32 *)klast, nkeys, out.key_clusters);
     IVX_HIP(ctx, hipGetLastError());
     IVX_HIP(ctx, hipStreamSynchronize(stq));
-    *m = n ? ctx->h_scalars[2] : 0;
+    *m = n ? *ctx->hword(SC_RUNS) : 0;
     return IVX_OK;
 }

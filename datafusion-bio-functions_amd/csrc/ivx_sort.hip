@@ -301,14 +301,14 @@ ivx_status sort_impl(ivx_ctx *ctx, u64 *const *a, u64 *const *b, u64 n, const iv
     hipStream_t st = ctx->stream;
     // which bits vary at all (per sorted word)
     // (tight: the caller packed the fields from the columns' value ranges, every digit varies -- no need to look)
-    unsigned long long *d_var = (unsigned long long *)(ctx->d_scalars + 16);
+    unsigned long long *d_var = ctx->dword<unsigned long long>(SC_SORT_VAR);
     if (tight) {
-        for (int f = 0; f < nfields; f++) ctx->h_scalars[16 + f] = ~0ull;
+        for (int f = 0; f < nfields; f++) ctx->hword(SC_SORT_VAR)[f] = ~0ull;
     } else {
-        IVX_HIP(ctx, hipMemsetAsync(d_var, 0, 8 * sizeof(u64), st));
+        IVX_HIP(ctx, hipMemsetAsync(d_var, 0, SC_SORT_FIELDS * sizeof(u64), st));
         for (int f = 0; f < nfields; f++)
             hipLaunchKernelGGL(k_varbits, dim3(ivx_stream_grid(n, RS_HT * 16, 1024)), dim3(RS_HT), 0, st, (const u64 *)a[fields[f].word], n, d_var + f);
-        IVX_HIP(ctx, hipMemcpyAsync(ctx->h_scalars + 16, d_var, 8 * sizeof(u64), hipMemcpyDeviceToHost, st));
+        IVX_HIP(ctx, ctx->fetch(SC_SORT_VAR, st, SC_SORT_FIELDS));
         IVX_HIP(ctx, hipStreamSynchronize(st));
     }
 
@@ -318,7 +318,7 @@ ivx_status sort_impl(ivx_ctx *ctx, u64 *const *a, u64 *const *b, u64 n, const iv
     IVX_TRY(ctx->get_scratch(WS_SORTHIST, (size_t)256 * nblk * sizeof(u32), (void **)&hist));
     int cur = 0;
     for (int f = 0; f < nfields; f++) {
-        const u64 var = ctx->h_scalars[16 + f];
+        const u64 var = ctx->hword(SC_SORT_VAR)[f];
         for (int sh = fields[f].lo; sh < fields[f].hi; sh += 8) {
             const u64 window = (sh + 8 >= 64 ? ~0ull : ((1ull << (sh + 8)) - 1)) & ~((1ull << sh) - 1);
             u64 fieldmask = fields[f].hi >= 64 ? ~0ull : ((1ull << fields[f].hi) - 1);
@@ -367,7 +367,7 @@ ivx_status ivx_radix_sort(ivx_ctx *ctx, int nw, u64 *const *a, u64 *const *b, u6
 extern "C" ivx_status ivx_debug_sort_geom(ivx_ctx *ctx, int nw, u64 *w0, u64 *w1, u64 *w2, u32 *pay, u64 n,
                                           const int *field_words, const int *field_lo, const int *field_hi, int nfields, int tight, u64 *geom)
 {
-    if (!ctx || nw < 1 || nw > 3 || nfields < 0 || nfields > 8) return IVX_ERR_INVALID;
+    if (!ctx || nw < 1 || nw > 3 || nfields < 0 || nfields > SC_SORT_FIELDS) return IVX_ERR_INVALID;
     IVX_HIP(ctx, hipSetDevice(ctx->device));
     u64 *host[3] = {w0, w1, w2};
     u64 *a[3], *b[3]; u32 *p[2] = {nullptr, nullptr};
@@ -382,7 +382,7 @@ extern "C" ivx_status ivx_debug_sort_geom(ivx_ctx *ctx, int nw, u64 *w0, u64 *w1
         IVX_TRY(ctx->get_scratch(WS_SB1, n * sizeof(u32), (void **)&p[1]));
         IVX_HIP(ctx, hipMemcpyAsync(p[0], pay, n * sizeof(u32), hipMemcpyHostToDevice, ctx->stream));
     }
-    ivx_sort_field f[8];
+    ivx_sort_field f[SC_SORT_FIELDS];
     for (int i = 0; i < nfields; i++) { f[i].word = field_words[i]; f[i].lo = field_lo[i]; f[i].hi = field_hi[i]; }
     int in_b = 0;
     IVX_TRY(ivx_radix_sort(ctx, nw, a, b, n, f, nfields, &in_b, tight != 0, pay ? p : nullptr));

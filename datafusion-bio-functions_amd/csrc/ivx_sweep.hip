@@ -63,6 +63,8 @@ __global__ __launch_bounds__(ST) void k_unpack64(const u64 *__restrict__ w0, con
 struct Range64 { long long min_s, max_s, min_e, max_e; unsigned long long unsorted, odd; };   // unsorted: some row sorts before its predecessor;
                                                                                                 // odd: bit 0 some end < start, bit 1 some end == start,
                                                                                                 // bit 2 some row's (key, start) below its predecessor's
+static_assert(sizeof(Range64) == (size_t)(SC_LIN - SC_RANGE) * sizeof(u64), "Range64 is the words of SC_RANGE: one copy fetches it and the lin words behind it");
+IVX_SC_FITS(Range64, SC_RANGE_INIT, SC_TAKE_TOTAL);
 
 // kmin / kmax (nullable; nkeys <= LIN_KEYS): also every key's own range of starts, for the linearised sort word below --
 // privatised in LDS, and a bound is touched by an atomic only when a row moves it (a plain read comes first)
@@ -357,14 +359,14 @@ ivx_status sort64(ivx_ctx *ctx, int slot_a, int slot_b, const u32 *key, const i6
     if (n == 0) return IVX_OK;
     bool narrow = sw != nullptr && rows == nullptr && !getenv("IVX_NO_NARROW_SWEEP");
     hipStream_t st = ctx->stream;
-    u32 *flags = (u32 *)(ctx->d_scalars + 8);
-    Range64 *d_rng = (Range64 *)(ctx->d_scalars + 24);
-    Range64 *h_init = (Range64 *)(ctx->h_scalars + 48);                   // pinned, so the async copy may read it later
+    u32 *flags = ctx->dword<u32>(SC_SWEEP_FLAG);
+    Range64 *d_rng = ctx->dword<Range64>(SC_RANGE);
+    Range64 *h_init = ctx->hword<Range64>(SC_RANGE_INIT);               // pinned, so the async copy may read it later
     *h_init = Range64{INT64_MAX, INT64_MIN, INT64_MAX, INT64_MIN, 0ull, 0ull};
     IVX_HIP(ctx, hipMemcpyAsync(d_rng, h_init, sizeof(Range64), hipMemcpyHostToDevice, st));
     // every key's own range of starts as well, when the key table fits LDS (the linearised sort word, Pack64)
     long long *kmin = nullptr, *kmax = nullptr; u64 *base = nullptr;
-    u64 *d_lin = ctx->d_scalars + 30;                                   // {usable, (key, start) positions in all}
+    u64 *d_lin = ctx->dword(SC_LIN);                                    // {usable, (key, start) positions in all}
     const bool try_lin = nkeys <= LIN_KEYS && !getenv("IVX_NO_LIN");
     if (try_lin) {
         // (the third record slots: free whenever the one-word form is in use, and owned by this call -- the callers keep
@@ -377,12 +379,11 @@ ivx_status sort64(ivx_ctx *ctx, int slot_a, int slot_b, const u32 *key, const i6
     hipLaunchKernelGGL(k_range64, dim3(ivx_stream_grid(n, ST * 4, 2048)), dim3(ST), try_lin ? (size_t)nkeys * 16 : 0, st, key, s, e, n, nkeys, d_rng, flags,
                        kmin, kmax);
     if (try_lin) hipLaunchKernelGGL(k_lin_layout64, dim3(1), dim3(1024), 0, st, (const long long *)kmin, (const long long *)kmax, nkeys, base, d_lin);
-    IVX_HIP(ctx, hipMemcpyAsync(ctx->h_scalars + 24, d_rng, 8 * sizeof(u64), hipMemcpyDeviceToHost, st));   // Range64 (6 words), d_lin (2 words)
-    IVX_HIP(ctx, hipMemcpyAsync(ctx->h_scalars + 8, flags, sizeof(u64), hipMemcpyDeviceToHost, st));        // + the key flag k_range64 raised
-    IVX_HIP(ctx, hipStreamSynchronize(st));
-    // a key id >= nkeys fails here, before the pack kernels index the per-key tables (base / kmin) with it
-    if (*(const u32 *)(ctx->h_scalars + 8)) return ctx->fail(IVX_ERR_INVALID, "key id >= n_keys");
-    const Range64 r = *(const Range64 *)(ctx->h_scalars + 24);
+    IVX_HIP(ctx, ctx->fetch(SC_RANGE, st, SC_RANGE_LIN_WORDS));         // Range64 and the two lin words
+    // + the key flag k_range64 raised: a key id >= nkeys fails here, before the pack kernels index the per-key tables (base / kmin) with it
+    IVX_TRY(ctx->check_flag(SC_SWEEP_FLAG, st, "key id >= n_keys"));
+    const Range64 r = *ctx->hword<Range64>(SC_RANGE);
+    const u64 *h_lin = ctx->hword(SC_LIN);
     // coordinate-sorted input (the usual state of BED / VCF / BAM-derived tables): nothing to sort, and equal
     // rows already are in ascending row order
     // (the sweep over packed words asks less: (key, start) order -- coordinate-sorted files rarely order the ends of equal starts)
@@ -396,9 +397,9 @@ ivx_status sort64(ivx_ctx *ctx, int slot_a, int slot_b, const u32 *key, const i6
     p.bits_s = bits_of((u64)r.max_s - (u64)r.min_s); p.bits_e = bits_of((u64)r.max_e - (u64)r.min_e);
     u32 bits_k = bits_of(nkeys ? nkeys - 1 : 0);
     double positions = (double)(nkeys ? nkeys : 1) * (p.bits_s >= 62 ? 4.6e18 : (double)(1ull << p.bits_s));
-    if (try_lin && ctx->h_scalars[30] && ctx->h_scalars[31]) {
-        const u32 bits_lin = bits_of(ctx->h_scalars[31] - 1);
-        if (bits_lin < bits_k + p.bits_s) { p.lin = 1; p.bits_s = bits_lin; bits_k = 0; positions = (double)ctx->h_scalars[31]; }
+    if (try_lin && h_lin[0] && h_lin[1]) {
+        const u32 bits_lin = bits_of(h_lin[1] - 1);
+        if (bits_lin < bits_k + p.bits_s) { p.lin = 1; p.bits_s = bits_lin; bits_k = 0; positions = (double)h_lin[1]; }
     }
     const u32 total = p.bits_s + p.bits_e + bits_k;
     u64 *a[3] = {nullptr, nullptr, nullptr}, *b[3] = {nullptr, nullptr, nullptr};
@@ -488,9 +489,9 @@ ivx_status sort64(ivx_ctx *ctx, int slot_a, int slot_b, const u32 *key, const i6
             else
             hipLaunchKernelGGL((k_unpack1<true>), dim3((grid1(n) + UNPACK_TILES - 1) / UNPACK_TILES), dim3(ST), 0, st, (const u64 *)o[0], (const u32 *)pay[in_b], n, p, ks, ss, es, rows,
                                p.bits_e, toolong);
-            IVX_HIP(ctx, hipMemcpyAsync(ctx->h_scalars + 8, flags, sizeof(u64), hipMemcpyDeviceToHost, st));
+            IVX_HIP(ctx, ctx->fetch(SC_SWEEP_FLAG, st));
             IVX_HIP(ctx, hipStreamSynchronize(st));
-            if (((const u32 *)(ctx->h_scalars + 8))[1]) {                // a long run of equal (key,start): the plain way after all
+            if (ctx->hword<u32>(SC_SWEEP_FLAG)[1]) {                    // a long run of equal (key,start): the plain way after all
                 IVX_HIP(ctx, hipMemsetAsync(toolong, 0, sizeof(u32), st));
                 IVX_TRY(pack_for_sort(0, pay[0]));
                 two_step = false;
@@ -831,13 +832,7 @@ __global__ __launch_bounds__(ST) void k_sub_fill(const u32 *__restrict__ lk, con
     }
 }
 
-ivx_status keyflag(ivx_ctx *ctx, const char *what)
-{
-    IVX_HIP(ctx, hipMemcpyAsync(ctx->h_scalars + 8, ctx->d_scalars + 8, sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
-    IVX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (*(u32 *)(ctx->h_scalars + 8)) return ctx->fail(IVX_ERR_INVALID, what);
-    return IVX_OK;
-}
+ivx_status keyflag(ivx_ctx *ctx, const char *what) { return ctx->check_flag(SC_SWEEP_FLAG, ctx->stream, what); }
 
 // ---------------------------------------------------------------- complement
 //
@@ -1005,7 +1000,7 @@ ivx_status ivx_merge_device(ivx_ctx *ctx, const u32 *key, const i64 *s, const i6
 {
     *m = 0;
     if (n == 0) return IVX_OK;
-    IVX_HIP(ctx, hipMemsetAsync(ctx->d_scalars + 8, 0, sizeof(u64), ctx->stream));
+    IVX_HIP(ctx, hipMemsetAsync(ctx->dword(SC_SWEEP_FLAG), 0, sizeof(u64), ctx->stream));
     u32 *ks; i64 *ss, *es;
     IVX_TRY(ctx->get_scratch(WS_T0, n * sizeof(u32), (void **)&ks));
     IVX_TRY(ctx->get_scratch(WS_T1, n * sizeof(i64), (void **)&ss));
@@ -1028,7 +1023,7 @@ ivx_status ivx_subtract_device(ivx_ctx *ctx, const u32 *lkey, const i64 *ls, con
     *n_out = 0;
     if (nl == 0) return IVX_OK;
     hipStream_t st = ctx->stream;
-    IVX_HIP(ctx, hipMemsetAsync(ctx->d_scalars + 8, 0, sizeof(u64), st));
+    IVX_HIP(ctx, hipMemsetAsync(ctx->dword(SC_SWEEP_FLAG), 0, sizeof(u64), st));
     u32 *lk, *lrow, *rk; i64 *lsv, *lev, *rsv, *rev;
     IVX_TRY(ctx->get_scratch(WS_T0, nl * sizeof(u32), (void **)&lk));
     IVX_TRY(ctx->get_scratch(WS_T1, nl * sizeof(i64), (void **)&lsv));
@@ -1041,7 +1036,7 @@ ivx_status ivx_subtract_device(ivx_ctx *ctx, const u32 *lkey, const i64 *ls, con
     IVX_TRY(ctx->get_scratch(WS_T6, nra * sizeof(i64), (void **)&rev));
     IVX_TRY(sort64(ctx, WS_RA0, WS_RB0, rkey, rs, re, nr, nkeys, rk, rsv, rev, nullptr));
     // (sort64 left the right side's Range64 in the pinned scalars: odd bit 0 = some right row has end < start)
-    const int wf = (nr == 0 || (ctx->h_scalars[29] & 1ull) == 0) && !getenv("IVX_SUB_GENERAL");
+    const int wf = (nr == 0 || (ctx->hword<Range64>(SC_RANGE)->odd & 1ull) == 0) && !getenv("IVX_SUB_GENERAL");
     IVX_TRY(keyflag(ctx, "subtract: key id >= n_keys"));
 
     // right side: running max of ends per key, gap heads
@@ -1054,9 +1049,9 @@ ivx_status ivx_subtract_device(ivx_ctx *ctx, const u32 *lkey, const i64 *ls, con
         IVX_TRY(ivxscan::inclusive<SegMax64Op>(ctx, sm, nr));
         hipLaunchKernelGGL(k_gap_flags, dim3(grid1(nr + 1)), dim3(ST), 0, st, (const u32 *)rk, (const i64 *)rsv, (const SegMax64 *)sm, nr, hid);
         IVX_TRY(ivx_scan_exclusive_u32(ctx, hid, nr + 1));
-        IVX_HIP(ctx, hipMemcpyAsync(ctx->h_scalars + 4, hid + nr, sizeof(u32), hipMemcpyDeviceToHost, st));
-        IVX_HIP(ctx, hipStreamSynchronize(st));
-        nh = *(u32 *)(ctx->h_scalars + 4);
+        u32 nh32;
+        IVX_TRY(ctx->fetch_wait((const u32 *)hid + nr, st, &nh32));
+        nh = nh32;
     }
     const u64 nha = nh ? nh : 1;
     // the sorted right ends are no longer needed: reuse their slot for the heads' keys
@@ -1078,9 +1073,8 @@ ivx_status ivx_subtract_device(ivx_ctx *ctx, const u32 *lkey, const i64 *ls, con
                        (const u32 *)hk, (const i64 *)hrs, (const u32 *)hj, (u32)nh, (const u32 *)rk, (const i64 *)rsv, (const SegMax64 *)sm, (u32)nr, cnt,
                        plan_hlo, plan_tail, (const u32 *)brk, wf, (u32 *)nullptr, (u8 *)nullptr, (const u32 *)nullptr);
     IVX_TRY(ivx_scan_exclusive_u64(ctx, cnt, nl + 1));
-    IVX_HIP(ctx, hipMemcpyAsync(ctx->h_scalars + 5, cnt + nl, sizeof(u64), hipMemcpyDeviceToHost, st));
-    IVX_HIP(ctx, hipStreamSynchronize(st));
-    const u64 total = ctx->h_scalars[5];
+    u64 total;
+    IVX_TRY(ctx->fetch_wait((const u64 *)cnt + nl, st, &total));
     *n_out = total;
     ivx_sub_plan &pl = ctx->sub_plan;
     pl.nl = nl; pl.nr = nr; pl.nh = nh; pl.total = total; pl.nkeys = nkeys; pl.strict = strict; pl.stream = st;
@@ -1152,7 +1146,7 @@ ivx_status ivx_cluster_device(ivx_ctx *ctx, const u32 *key, const i64 *s, const 
                               u32 *ok, i64 *os, i64 *oe, u32 *orow, i64 *oc, i64 *ocs, i64 *oce, u64 *key_clusters, u64 *m)
 {
     *m = 0;
-    IVX_HIP(ctx, hipMemsetAsync(ctx->d_scalars + 8, 0, sizeof(u64), ctx->stream));
+    IVX_HIP(ctx, hipMemsetAsync(ctx->dword(SC_SWEEP_FLAG), 0, sizeof(u64), ctx->stream));
     // the sorted rows ARE output columns; scratch only for the ones the caller did not ask for
     u32 *ks = ok, *rows = orow; i64 *ss = os, *es = oe;
     if (n) {
@@ -1174,8 +1168,8 @@ ivx_status ivx_complement_device(ivx_ctx *ctx, const u32 *key, const i64 *s, con
 {
     *n_out = 0;
     hipStream_t st = ctx->stream;
-    IVX_HIP(ctx, hipMemsetAsync(ctx->d_scalars + 8, 0, 2 * sizeof(u64), st));
-    u32 *bad = (u32 *)(ctx->d_scalars + 8), *irregular = (u32 *)(ctx->d_scalars + 9);
+    u32 *bad = ctx->dword<u32>(SC_SWEEP_FLAG), *irregular = ctx->dword<u32>(SC_SWEEP_IRREGULAR);
+    IVX_HIP(ctx, hipMemsetAsync(bad, 0, 2 * sizeof(u64), st));             // both
 
     // which keys have input rows / view rows; implicit views for input keys without one
     u32 *has_in, *has_view, *need;
@@ -1188,9 +1182,9 @@ ivx_status ivx_complement_device(ivx_ctx *ctx, const u32 *key, const i64 *s, con
     if (nv) hipLaunchKernelGGL(k_mark_keys, dim3(grid1(nv)), dim3(ST), 0, st, vkey, nv, nkeys, has_view, bad);
     hipLaunchKernelGGL(k_need_implicit, dim3(grid1((u64)nkeys + 1)), dim3(ST), 0, st, (const u32 *)has_in, (const u32 *)has_view, nkeys, need);
     IVX_TRY(ivx_scan_exclusive_u32(ctx, need, (u64)nkeys + 1));
-    IVX_HIP(ctx, hipMemcpyAsync(ctx->h_scalars + 4, need + nkeys, sizeof(u32), hipMemcpyDeviceToHost, st));
+    IVX_HIP(ctx, ctx->fetch(SC_COMP_IMPLICIT, need + nkeys, sizeof(u32), st));
     IVX_TRY(keyflag(ctx, "complement: key id >= n_keys"));                  // synchronises
-    const u64 nw = nv + *(u32 *)(ctx->h_scalars + 4);
+    const u64 nw = nv + *ctx->hword<u32>(SC_COMP_IMPLICIT);
     if (nw >= 0xFFFFFFFFull) return ctx->fail(IVX_ERR_INVALID, "complement: more than 2^32-1 view rows");
     if (nw == 0) return IVX_OK;
 
@@ -1240,16 +1234,15 @@ ivx_status ivx_complement_device(ivx_ctx *ctx, const u32 *key, const i64 *s, con
     IVX_TRY(ctx->get_scratch(WS_RB2, (nw + 1) * sizeof(u64), (void **)&cnt));
     hipLaunchKernelGGL(k_view_flags, dim3(grid1(nw + 1)), dim3(ST), 0, st, (const u32 *)wk, nw, (const u32 *)has_in, A);
     IVX_TRY(ivx_scan_exclusive_u32(ctx, A, nw + 1));
-    IVX_HIP(ctx, hipMemcpyAsync(ctx->h_scalars + 9, irregular, sizeof(u64), hipMemcpyDeviceToHost, st));
-    IVX_HIP(ctx, hipStreamSynchronize(st));
-    const int irr = *(u32 *)(ctx->h_scalars + 9) != 0;
+    u32 irr32;
+    IVX_TRY(ctx->fetch_wait(SC_SWEEP_IRREGULAR, st, &irr32));
+    const int irr = irr32 != 0;
     const CompRuns R{mk, ms, me, (u32)m, G, cg};
     hipLaunchKernelGGL(k_comp_count, dim3(grid1(nw + 1)), dim3(ST), 0, st, (const u32 *)wk, (const i64 *)ws, (const i64 *)we, nw,
                        (const u32 *)has_in, (const u32 *)A, R, irr, cnt, inv, pa, pb);
     IVX_TRY(ivx_scan_exclusive_u64(ctx, cnt, nw + 1));
-    IVX_HIP(ctx, hipMemcpyAsync(ctx->h_scalars + 5, cnt + nw, sizeof(u64), hipMemcpyDeviceToHost, st));
-    IVX_HIP(ctx, hipStreamSynchronize(st));
-    const u64 total = ctx->h_scalars[5];
+    u64 total;
+    IVX_TRY(ctx->fetch_wait((const u64 *)cnt + nw, st, &total));
     *n_out = total;
     if (cap == 0 && !ok && !os && !oe) return IVX_OK;                       // count only
     if (total > cap) return ctx->fail(IVX_ERR_CAPACITY, "complement: output buffers too small");

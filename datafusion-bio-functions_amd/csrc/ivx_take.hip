@@ -174,13 +174,7 @@ __global__ __launch_bounds__(TK) void k_view_copy(const View16 *__restrict__ vie
 
 u32 take_grid(u64 n) { return ivx_stream_grid(n, TK * 4, 256 * 16); }
 
-ivx_status take_flag(ivx_ctx *ctx, const char *what = "take: index out of bounds")
-{
-    IVX_HIP(ctx, hipMemcpyAsync(ctx->h_scalars + 8, ctx->d_scalars + 8, sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
-    IVX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (*(u32 *)(ctx->h_scalars + 8)) return ctx->fail(IVX_ERR_INVALID, what);
-    return IVX_OK;
-}
+ivx_status take_flag(ivx_ctx *ctx, const char *what = "take: index out of bounds") { return ctx->check_flag(SC_TAKE_BAD, ctx->stream, what); }
 
 }  // namespace
 
@@ -188,8 +182,8 @@ ivx_status ivx_take_fixed_device(ivx_ctx *ctx, const void *src, u32 width, u64 n
                                  const u32 *idx, u64 n, void *out, u8 *out_valid)
 {
     hipStream_t st = ctx->stream;
-    IVX_HIP(ctx, hipMemsetAsync(ctx->d_scalars + 8, 0, sizeof(u64), st));
-    u32 *bad = (u32 *)(ctx->d_scalars + 8);
+    IVX_HIP(ctx, hipMemsetAsync(ctx->dword(SC_TAKE_BAD), 0, sizeof(u64), st));
+    u32 *bad = ctx->dword<u32>(SC_TAKE_BAD);
     if (n) {
         const u32 grid = take_grid(n);
 #define IVX_TAKE(V) hipLaunchKernelGGL(k_take_fixed<V>, dim3(grid), dim3(TK), 0, st, (const V *)src, n_src, src_valid, idx, n, (V *)out, out_valid, bad)
@@ -211,8 +205,8 @@ ivx_status ivx_take_fixed_device(ivx_ctx *ctx, const void *src, u32 width, u64 n
 ivx_status ivx_scatter_fixed_device(ivx_ctx *ctx, const void *src, u32 width, const u32 *idx, u64 n, void *out, u64 n_out)
 {
     hipStream_t st = ctx->stream;
-    IVX_HIP(ctx, hipMemsetAsync(ctx->d_scalars + 8, 0, sizeof(u64), st));
-    u32 *bad = (u32 *)(ctx->d_scalars + 8);
+    IVX_HIP(ctx, hipMemsetAsync(ctx->dword(SC_TAKE_BAD), 0, sizeof(u64), st));
+    u32 *bad = ctx->dword<u32>(SC_TAKE_BAD);
     if (n) {
         const u32 grid = take_grid(n);
 #define IVX_SCAT(V) hipLaunchKernelGGL(k_scatter_fixed<V>, dim3(grid), dim3(TK), 0, st, (const V *)src, idx, n, (V *)out, n_out, bad)
@@ -234,8 +228,8 @@ ivx_status ivx_scatter_fixed_device(ivx_ctx *ctx, const void *src, u32 width, co
 ivx_status ivx_take_bits_device(ivx_ctx *ctx, const u8 *src_bits, u64 n_src, const u8 *src_valid, const u32 *idx, u64 n, u8 *out_bits, u8 *out_valid)
 {
     hipStream_t st = ctx->stream;
-    IVX_HIP(ctx, hipMemsetAsync(ctx->d_scalars + 8, 0, sizeof(u64), st));
-    if (n) hipLaunchKernelGGL(k_take_bits, dim3(take_grid((n + 7) / 8)), dim3(TK), 0, st, src_bits, n_src, src_valid, idx, n, out_bits, out_valid, (u32 *)(ctx->d_scalars + 8));
+    IVX_HIP(ctx, hipMemsetAsync(ctx->dword(SC_TAKE_BAD), 0, sizeof(u64), st));
+    if (n) hipLaunchKernelGGL(k_take_bits, dim3(take_grid((n + 7) / 8)), dim3(TK), 0, st, src_bits, n_src, src_valid, idx, n, out_bits, out_valid, ctx->dword<u32>(SC_TAKE_BAD));
     IVX_HIP(ctx, hipGetLastError());
     return take_flag(ctx);
 }
@@ -247,17 +241,17 @@ ivx_status ivx_take_utf8_device(ivx_ctx *ctx, int large, const void *offsets, co
 {
     hipStream_t st = ctx->stream;
     *data_bytes = 0;
-    IVX_HIP(ctx, hipMemsetAsync(ctx->d_scalars + 8, 0, sizeof(u64), st));
-    u32 *bad = (u32 *)(ctx->d_scalars + 8);
+    IVX_HIP(ctx, hipMemsetAsync(ctx->dword(SC_TAKE_BAD), 0, sizeof(u64), st));
+    u32 *bad = ctx->dword<u32>(SC_TAKE_BAD);
     u64 *pos;
     IVX_TRY(ctx->get_scratch(WS_T0, (n + 1) * sizeof(u64), (void **)&pos));
     const u32 grid = take_grid(n + 1);
     if (large) hipLaunchKernelGGL(k_take_len<i64>, dim3(grid), dim3(TK), 0, st, (const i64 *)offsets, n_src, src_valid, idx, n, pos, out_valid, bad);
     else hipLaunchKernelGGL(k_take_len<i32>, dim3(grid), dim3(TK), 0, st, (const i32 *)offsets, n_src, src_valid, idx, n, pos, out_valid, bad);
     IVX_TRY(ivx_scan_exclusive_u64(ctx, pos, n + 1));
-    IVX_HIP(ctx, hipMemcpyAsync(ctx->h_scalars + 5, pos + n, sizeof(u64), hipMemcpyDeviceToHost, st));
+    IVX_HIP(ctx, ctx->fetch(SC_TAKE_TOTAL, pos + n, sizeof(u64), st));
     IVX_TRY(take_flag(ctx));                                                    // synchronises
-    const u64 total = ctx->h_scalars[5];
+    const u64 total = *ctx->hword(SC_TAKE_TOTAL);
     *data_bytes = total;
     if (!large && total > 0x7FFFFFFFull) return ctx->fail(IVX_ERR_INVALID, "take: Utf8 offsets overflow i32 (use LargeUtf8)");
     if (out_offsets) {
@@ -283,16 +277,16 @@ ivx_status ivx_take_view_device(ivx_ctx *ctx, const void *views, const u8 *const
 {
     hipStream_t st = ctx->stream;
     *data_bytes = 0;
-    IVX_HIP(ctx, hipMemsetAsync(ctx->d_scalars + 8, 0, sizeof(u64), st));
-    u32 *bad = (u32 *)(ctx->d_scalars + 8);
+    IVX_HIP(ctx, hipMemsetAsync(ctx->dword(SC_TAKE_BAD), 0, sizeof(u64), st));
+    u32 *bad = ctx->dword<u32>(SC_TAKE_BAD);
     u64 *pos;
     IVX_TRY(ctx->get_scratch(WS_T0, (n + 1) * sizeof(u64), (void **)&pos));
     const u32 grid = take_grid(n + 1);
     hipLaunchKernelGGL(k_view_len, dim3(grid), dim3(TK), 0, st, (const View16 *)views, n_src, src_valid, idx, n, pos, out_valid, bad);
     IVX_TRY(ivx_scan_exclusive_u64(ctx, pos, n + 1));
-    IVX_HIP(ctx, hipMemcpyAsync(ctx->h_scalars + 5, pos + n, sizeof(u64), hipMemcpyDeviceToHost, st));
+    IVX_HIP(ctx, ctx->fetch(SC_TAKE_TOTAL, pos + n, sizeof(u64), st));
     IVX_TRY(take_flag(ctx));
-    const u64 total = ctx->h_scalars[5];
+    const u64 total = *ctx->hword(SC_TAKE_TOTAL);
     *data_bytes = total;
     if (total > 0x7FFFFFFFull) return ctx->fail(IVX_ERR_UNSUPPORTED, "take: gathered view data exceeds one 2 GiB buffer");
     if (!out_views || (total && !out_data)) return IVX_OK;                      // sizing call
