@@ -457,6 +457,33 @@ extern "C" ivx_status ivx_index_layout(ivx_ctx *ctx, const ivx_index *ix, uint32
     return IVX_OK;
 }
 
+// TEST HOOK (exported, not in include/ivx.h; tests/test_gpu_rank_edges.py): the forms a count / coverage / nearest index
+// took -- the routing view's region count, what the nearest build's sorts did (host fields of the index) and every rank
+// grid's header {shift, cells} (read back here: builds and probes never pay for it).  Reads only; words: IVX_FORMS_*
+extern "C" ivx_status ivx_debug_index_forms(ivx_ctx *ctx, const ivx_index *ix, uint32_t *out, uint32_t n_out)
+{
+    if (!ctx) return IVX_ERR_INVALID;
+    if (!ix) return ctx->fail(IVX_ERR_INVALID, "null index");
+    if (n_out && !out) return ctx->fail(IVX_ERR_INVALID, "null out");
+    if (ix->device != ctx->device) return ctx->fail(IVX_ERR_INVALID, "index lives on another device");
+    u32 w[IVX_FORMS_WORDS] = {};
+    w[IVX_FORMS_KIND] = (u32)ix->kind;
+    w[IVX_FORMS_NROUTE_NREG] = ix->nroute_nreg;
+    const RankGridView *g[3] = {nullptr, nullptr, nullptr};
+    if (ix->kind == IVX_KIND_COUNT) { g[0] = &ix->gs; g[1] = &ix->ge; }
+    else if (ix->kind == IVX_KIND_COVERAGE) { g[0] = &ix->cv.first; g[1] = &ix->cv.last; }
+    else if (ix->kind == IVX_KIND_NEAREST) {
+        g[0] = &ix->nv.by_start; g[1] = &ix->nv.by_end; g[2] = &ix->nv.pmax;
+        w[IVX_FORMS_NEAR_WORDS] = ix->near_words; w[IVX_FORMS_NEAR_ORDER] = ix->near_order; w[IVX_FORMS_NEAR_FALLBACK] = ix->near_fallback;
+    }
+    IVX_HIP(ctx, hipSetDevice(ctx->device));
+    for (int i = 0; i < 3; i++)
+        if (g[i] && g[i]->hdr) IVX_HIP(ctx, hipMemcpyAsync(&w[IVX_FORMS_GRID0 + 2 * i], g[i]->hdr, 2 * sizeof(u32), hipMemcpyDeviceToHost, ctx->stream));
+    IVX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (u32 i = 0; i < n_out && i < (u32)IVX_FORMS_WORDS; i++) out[i] = w[i];
+    return IVX_OK;
+}
+
 // ---------------------------------------------------------------- a3 probes
 
 static bool rowval_routed_ok(u64 n)

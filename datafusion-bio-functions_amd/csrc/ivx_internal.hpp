@@ -296,10 +296,22 @@ struct ivx_index {
     NearestView nv{};
     JoinIndexView nroute{};     // nearest index: regions that only ROUTE big probe batches (origin/span/kcnt/kreg/rkey/hdr; no cells)
     u32 nroute_nreg = 0;
+    // nearest index: the form its build's sorts took (ivx_ops32.hip: nearest_sorted_records; read by ivx_debug_index_forms)
+    u32 near_words = 0;         // sort words per row: 0 no rows, 1 linearised (key, coordinate) ‖ row, 2 (start, end) + (key, row)
+    u32 near_order = 0;         // IVX_NEAR_ORDER_*: how the (key, start, end) order was reached
+    u32 near_fallback = 0;      // IVX_NEAR_FB_* bits: forms the build tried and left
     DepthProfileView dp{};      // IVX_KIND_DEPTH_PROFILE
     int flags = 0;              // IVX_IXF_*
 };
 enum { IVX_IXF_REGION_ROWVAL = 1 };   // count/coverage index: jv is usable for the region-partitioned per-row probe
+enum { IVX_NEAR_ORDER_PRESORTED = 0 /* no sort: the rows came in order */, IVX_NEAR_ORDER_REPAIR = 1 /* sort on the leading fields, runs of equal (key, start) put in end order afterwards */,
+       IVX_NEAR_ORDER_FULL = 2 /* one sort on all three fields */ };
+enum { IVX_NEAR_FB_NOFIT = 1 /* the one-word form did not fit 64 bits */, IVX_NEAR_FB_LIN_RUN = 2 /* the one-word unpack met a run above NLIN_MAXRUN */,
+       IVX_NEAR_FB_SE_RUN = 4 /* the two-word run repair met a run above NFIX_MAXRUN */ };
+// words of ivx_debug_index_forms (ivx_capi.hip; tests only, not in include/ivx.h): kind, routing regions, the three near_* fields,
+// then (shift, cells) of up to three rank grids -- count: starts, ends; coverage: first, last; nearest: by_start, by_end, pmax
+enum { IVX_FORMS_KIND = 0, IVX_FORMS_NROUTE_NREG = 1, IVX_FORMS_NEAR_WORDS = 2, IVX_FORMS_NEAR_ORDER = 3, IVX_FORMS_NEAR_FALLBACK = 4,
+       IVX_FORMS_GRID0 = 5, IVX_FORMS_WORDS = 11 };
 
 // ---------------------------------------------------------------- internal API
 // scan.hip

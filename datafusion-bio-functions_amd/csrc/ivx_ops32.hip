@@ -636,7 +636,8 @@ __global__ __launch_bounds__(OT) void k_unpack_lin_end(const u64 *__restrict__ y
 
 // IVX_OK with *done = false: the input does not fit the one-word form (coordinate spans, or a long run of equal
 // (key, start)) -- the caller takes the two-word sorts
-ivx_status nearest_sorted_records_lin(ivx_ctx *ctx, const u32 *key, const i32 *s, const i32 *e, u64 n, u32 nkeys,
+// (ix: only its near_* fields are written -- what the build did, for ivx_debug_index_forms)
+ivx_status nearest_sorted_records_lin(ivx_ctx *ctx, ivx_index *ix, const u32 *key, const i32 *s, const i32 *e, u64 n, u32 nkeys,
                                       u32 *ks, ivx_nrec *rs, ivx_nrec *re, bool *done)
 {
     *done = false;
@@ -659,7 +660,7 @@ ivx_status nearest_sorted_records_lin(ivx_ctx *ctx, const u32 *key, const i32 *s
     if (hf[0]) return ctx->fail(IVX_ERR_INVALID, "build key id >= n_keys");
     const bool presorted = hf[1] == 0 && !getenv("IVX_FORCE_SORT");
     const u32 linbits = hh[0], rowbits = hh[1];
-    if (!hh[2]) return IVX_OK;
+    if (!hh[2]) { ix->near_fallback |= IVX_NEAR_FB_NOFIT; return IVX_OK; }
     u64 *a[1], *b[1]; u32 *pay[2];
     IVX_TRY(ctx->get_scratch(WS_SA0, n * sizeof(u64), (void **)&a[0]));
     IVX_TRY(ctx->get_scratch(WS_SB0, n * sizeof(u64), (void **)&b[0]));
@@ -678,8 +679,9 @@ ivx_status nearest_sorted_records_lin(ivx_ctx *ctx, const u32 *key, const i32 *s
     hipLaunchKernelGGL(k_unpack_lin_end, dim3(grid1(n)), dim3(OT), 0, st, (const u64 *)(in_b ? b[0] : a[0]), n, rowbits, (const ivx_nrec *)rs, re);
     IVX_HIP(ctx, ctx->fetch(SC_BUILD_FLAG, st));
     IVX_HIP(ctx, hipStreamSynchronize(st));
-    if (hf[1]) return IVX_OK;                                           // a run of equal (key, start) beyond NLIN_MAXRUN rows
+    if (hf[1]) { ix->near_fallback |= IVX_NEAR_FB_LIN_RUN; return IVX_OK; }   // a run of equal (key, start) beyond NLIN_MAXRUN rows
     IVX_HIP(ctx, hipGetLastError());
+    ix->near_words = 1; ix->near_order = presorted ? IVX_NEAR_ORDER_PRESORTED : IVX_NEAR_ORDER_REPAIR;
     *done = true;
     return IVX_OK;
 }
@@ -688,13 +690,14 @@ ivx_status nearest_sorted_records_lin(ivx_ctx *ctx, const u32 *key, const i32 *s
 // (key,end,start,row) (:77-82), ks = the key column (the same in both orders).  The second order is a STABLE
 // sort of the first by (key,end) alone -- ties keep their (start,row) order -- which is 5 digit passes
 // instead of 9 for human-genome coordinates.
-ivx_status nearest_sorted_records(ivx_ctx *ctx, const u32 *key, const i32 *s, const i32 *e, u64 n, u32 nkeys,
+ivx_status nearest_sorted_records(ivx_ctx *ctx, ivx_index *ix, const u32 *key, const i32 *s, const i32 *e, u64 n, u32 nkeys,
                                   u32 *ks, ivx_nrec *rs, ivx_nrec *re)
 {
+    ix->near_words = 0; ix->near_order = IVX_NEAR_ORDER_PRESORTED; ix->near_fallback = 0;
     if (n == 0) return IVX_OK;
     {
         bool done = false;
-        IVX_TRY(nearest_sorted_records_lin(ctx, key, s, e, n, nkeys, ks, rs, re, &done));
+        IVX_TRY(nearest_sorted_records_lin(ctx, ix, key, s, e, n, nkeys, ks, rs, re, &done));
         if (done) return IVX_OK;
         IVX_HIP(ctx, hipMemsetAsync(ctx->dword(SC_BUILD_FLAG), 0, sizeof(u64), ctx->stream));
     }
@@ -709,6 +712,7 @@ ivx_status nearest_sorted_records(ivx_ctx *ctx, const u32 *key, const i32 *s, co
     // build rows that already come in (key,start,end) order need no first sort
     IVX_TRY(check_keyflag(ctx));
     const bool presorted = hf[1] == 0 && !getenv("IVX_FORCE_SORT");
+    ix->near_words = 2; ix->near_order = presorted ? IVX_NEAR_ORDER_PRESORTED : IVX_NEAR_ORDER_FULL;
     int in_b = 0;
     if (!presorted) {
         // (key,start) first -- equal (key,start) rows are rare -- then the short runs by end in place; all three
@@ -723,7 +727,9 @@ ivx_status nearest_sorted_records(ivx_ctx *ctx, const u32 *key, const i32 *s, co
             IVX_HIP(ctx, ctx->fetch(SC_BUILD_FLAG, ctx->stream));
             IVX_HIP(ctx, hipStreamSynchronize(ctx->stream));
             done = hf[1] == 0;
-            if (!done) {
+            if (done) ix->near_order = IVX_NEAR_ORDER_REPAIR;
+            else {
+                ix->near_fallback |= IVX_NEAR_FB_SE_RUN;
                 IVX_HIP(ctx, hipMemsetAsync(flags + 1, 0, sizeof(u32), ctx->stream));
                 hipLaunchKernelGGL(k_pack_se, dim3(grid1(n)), dim3(OT), 0, ctx->stream, key, s, e, n, nkeys, a[0], a[1], flags);
                 in_b = 0;
@@ -832,7 +838,7 @@ ivx_status ivx_nearest_build(ivx_ctx *ctx, ivx_index *ix, const u32 *key, const 
     IVX_TRY(ivx_index_alloc(ctx, ix, na * sizeof(ivx_nrec), (void **)&rs));
     IVX_TRY(ivx_index_alloc(ctx, ix, na * sizeof(ivx_nrec), (void **)&re));
     IVX_TRY(ctx->get_scratch(WS_T0, na * 4, (void **)&ks));
-    IVX_TRY(nearest_sorted_records(ctx, key, s, e, n, nkeys, ks, rs, re));
+    IVX_TRY(nearest_sorted_records(ctx, ix, key, s, e, n, nkeys, ks, rs, re));
     if (n) {
         SegMaxIn in{ks, rs}; SegMaxOut out{rs};
         IVX_TRY((ivxscan::inclusive_f<SegMaxOp>(ctx, in, out, n)));                      // prefix_max_end :58-63

@@ -50,6 +50,12 @@ CIGAR_TILE = 4096
 # slots of ivx_index_layout (include/ivx.h IVX_LAYOUT_*), in order
 LAYOUT_SLOTS = ["kind", "sh0", "nlev", "levrows", "rcells", "rcs", "nreg", "pk24", "slow", "fg", "fbits", "nroute_nreg", "lbuild"]
 
+# words of the test hook ivx_debug_index_forms (csrc/ivx_internal.hpp IVX_FORMS_*): these scalars, then (shift, cells) per rank grid
+FORMS_SLOTS = ["kind", "nroute_nreg", "near_words", "near_order", "near_fallback"]
+FORMS_GRIDS = {KIND_COUNT: ("starts", "ends"), KIND_COVERAGE: ("first", "last"), KIND_NEAREST: ("by_start", "by_end", "pmax")}
+NEAR_ORDER_PRESORTED, NEAR_ORDER_REPAIR, NEAR_ORDER_FULL = 0, 1, 2      # near_order
+NEAR_FB_NOFIT, NEAR_FB_LIN_RUN, NEAR_FB_SE_RUN = 1, 2, 4                # near_fallback bits
+
 
 class Metrics(C.Structure):
     _fields_ = [("build_time", C.c_double), ("join_time", C.c_double), ("build_input_batches", C.c_uint64),
@@ -131,6 +137,9 @@ def lib():
         # test hook of csrc/ivx_sweep.hip (not in include/ivx.h): what subtract's count pass did (tests/test_gpu_subtract_edges.py)
         L.ivx_debug_subtract_paths.restype = C.c_int
         L.ivx_debug_subtract_paths.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        # test hook of csrc/ivx_capi.hip (not in include/ivx.h): the forms a count / coverage / nearest index took (tests/test_gpu_rank_edges.py)
+        L.ivx_debug_index_forms.restype = C.c_int
+        L.ivx_debug_index_forms.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32), C.c_uint32]
         _lib = L
     return _lib
 
@@ -184,6 +193,16 @@ class Index:
         out = (C.c_uint32 * len(LAYOUT_SLOTS))()
         self.ctx._chk(lib().ivx_index_layout(self.ctx.h, self.h, out, C.c_uint32(len(LAYOUT_SLOTS))))
         return dict(zip(LAYOUT_SLOTS, list(out)))
+
+    def forms(self):
+        """the forms a count / coverage / nearest index took (test hook ivx_debug_index_forms) as a dict: the scalar
+        FORMS_SLOTS, and "grids": {name: (shift, cells)} of the kind's rank grids"""
+        n = len(FORMS_SLOTS) + 6
+        out = (C.c_uint32 * n)()
+        self.ctx._chk0(lib().ivx_debug_index_forms(self.ctx.h, self.h, out, C.c_uint32(n)))
+        f = dict(zip(FORMS_SLOTS, list(out)))
+        f["grids"] = {g: (out[len(FORMS_SLOTS) + 2 * i], out[len(FORMS_SLOTS) + 2 * i + 1]) for i, g in enumerate(FORMS_GRIDS.get(self.kind, ()))}
+        return f
 
     def free(self):
         if self.h:
