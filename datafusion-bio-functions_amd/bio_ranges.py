@@ -385,6 +385,23 @@ class Session:
                 if t is not None:
                     t.close()
 
+    def depth_region_quantiles(self, reads, regions, prior=None, lengths=None, zero_based=False, end_exclusive=False, q_num=(1,), q_den=2,
+                               cols=DEFAULT_COLS, filter_flag=1796, min_mapq=0):
+        """order statistics of the depth per row of `regions` (read as for depth_regions): -> the regions table with bases
+        Int64 and min, max and one q_<num>_<den> per quantile appended, Int32 and null where bases is 0.  Quantile num / den
+        is element floor((bases - 1) * num / den) of the region's per-base coverage sorted ascending: the default (1,) / 2
+        is the lower median."""
+        tabs = [_Exported(t) if t is not None else None for t in (reads, prior, lengths, regions)]
+        try:
+            b = [t.c if t is not None else _Batch(None, None) for t in tabs]
+            return _quantiles_call(self, regions, q_num, q_den, lambda *outs: lib().brh_depth_region_quantiles(
+                self.h, b[0], b[1], b[2], b[3], _cols(cols), C.c_int(int(bool(zero_based))), C.c_int(int(bool(end_exclusive))),
+                C.c_uint32(int(filter_flag)), C.c_uint32(int(min_mapq)), *outs))
+        finally:
+            for t in tabs:
+                if t is not None:
+                    t.close()
+
     def depth_stream(self, lengths=None, filter_flag=1796, min_mapq=0):
         """depth() over a stream of read batches (brh_depth_push): -> DepthStream"""
         return DepthStream(self, lengths, filter_flag, min_mapq)
@@ -402,6 +419,21 @@ def _regions_call(session, regions, thresholds, call):
     out = regions.append_column("bases", _import(*bases)).append_column("sum", _import(*total))
     for j, t in enumerate(thr):
         out = out.append_column(f"bases_ge_{t}", _import(ge[j], ge_s[j]))
+    return out
+
+
+def _quantiles_call(session, regions, q_num, q_den, call):
+    """the fractions and the output structs of brh_depth_region_quantiles / brh_depth_push_region_quantiles -> regions + the columns"""
+    qn = [int(q) for q in q_num]
+    n = len(qn)
+    cq = (C.c_uint32 * max(n, 1))(*qn)
+    bases, mn, mx = _out(), _out(), _out()
+    q, q_s = (_ArrowArray * max(n, 1))(), (_ArrowSchema * max(n, 1))()
+    session._chk(call(cq, C.c_uint32(n), C.c_uint32(int(q_den)), C.byref(bases[0]), C.byref(bases[1]), C.byref(mn[0]), C.byref(mn[1]),
+                      C.byref(mx[0]), C.byref(mx[1]), q if n else None, q_s if n else None))
+    out = regions.append_column("bases", _import(*bases)).append_column("min", _import(*mn)).append_column("max", _import(*mx))
+    for j, t in enumerate(qn):
+        out = out.append_column(f"q_{t}_{int(q_den)}", _import(q[j], q_s[j]))
     return out
 
 
@@ -433,6 +465,15 @@ class DepthStream:
         R = _Exported(regions)
         try:
             return _regions_call(self.session, regions, thresholds, lambda *outs: lib().brh_depth_push_regions(
+                self.h, R.c, _cols(cols), C.c_int(int(bool(zero_based))), C.c_int(int(bool(end_exclusive))), *outs))
+        finally:
+            R.close()
+
+    def depth_region_quantiles(self, regions, zero_based=False, end_exclusive=False, q_num=(1,), q_den=2, cols=DEFAULT_COLS):
+        """Session.depth_region_quantiles over everything pushed so far; the stream stays open"""
+        R = _Exported(regions)
+        try:
+            return _quantiles_call(self.session, regions, q_num, q_den, lambda *outs: lib().brh_depth_push_region_quantiles(
                 self.h, R.c, _cols(cols), C.c_int(int(bool(zero_based))), C.c_int(int(bool(end_exclusive))), *outs))
         finally:
             R.close()

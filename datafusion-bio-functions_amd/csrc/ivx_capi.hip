@@ -1660,6 +1660,88 @@ extern "C" ivx_status ivx_depth_profile_windows(ivx_ctx *ctx, const ivx_index *p
     return IVX_OK;
 }
 
+// the checks the two order-statistics calls share, and their four output columns
+static ivx_status ranks_check(ivx_ctx *ctx, const ivx_index *p, int mem, const uint32_t *q_num, uint32_t n_q, uint32_t q_den,
+                              const int64_t *out_len, const int32_t *out_min, const int32_t *out_max, const int32_t *out_q)
+{
+    IVX_TRY(check_profile_args(ctx, p, mem));
+    if (n_q > IVX_DEPTH_MAX_QUANTILES) return ctx->fail(IVX_ERR_INVALID, "depth profile: more than 8 quantiles");
+    if (n_q && !q_num) return ctx->fail(IVX_ERR_INVALID, "depth profile: null q_num");
+    if (q_den == 0 || q_den > 65536u) return ctx->fail(IVX_ERR_INVALID, "depth profile: q_den outside 1 .. 65536");
+    for (uint32_t j = 0; j < n_q; j++)
+        if (q_num[j] > q_den) return ctx->fail(IVX_ERR_INVALID, "depth profile: a q_num above q_den");
+    if (mem == IVX_MEM_DEVICE && ((((uintptr_t)out_len) & 7u) || ((((uintptr_t)out_min) | ((uintptr_t)out_max) | ((uintptr_t)out_q)) & 3u)))
+        return ctx->fail(IVX_ERR_INVALID, "depth profile: output pointer not aligned to its element size");
+    ctx->sub_plan.valid = false; ctx->join_plan.valid = false;
+    return IVX_OK;
+}
+
+extern "C" ivx_status ivx_depth_profile_quantiles(ivx_ctx *ctx, const ivx_index *p, int mem,
+                                                  const uint32_t *qkey, const uint32_t *qstart, const uint32_t *qend, uint64_t n,
+                                                  uint32_t pos_lo, const uint32_t *key_hi, int skip_pos0,
+                                                  const uint32_t *q_num, uint32_t n_q, uint32_t q_den,
+                                                  int64_t *out_len, int32_t *out_min, int32_t *out_max, int32_t *out_q)
+{
+    if (!ctx) return IVX_ERR_INVALID;
+    IVX_TRY(ranks_check(ctx, p, mem, q_num, n_q, q_den, out_len, out_min, out_max, out_q));
+    if (n && (!qstart || !qend)) return ctx->fail(IVX_ERR_INVALID, "null coordinate column");
+    if (mem == IVX_MEM_DEVICE && ((((uintptr_t)qkey) | ((uintptr_t)qstart) | ((uintptr_t)qend) | ((uintptr_t)key_hi)) & 3u))
+        return ctx->fail(IVX_ERR_INVALID, "depth profile: input pointer not aligned to its element size");
+    CallMetrics cm(ctx, false, n);
+    if (n == 0) return IVX_OK;
+    const u32 *dk, *ds, *de, *dh; i64 *ol; i32 *omn, *omx, *oq;
+    IVX_TRY(stage_in(ctx, mem, WS_IN_KEY, qkey, n, &dk));
+    IVX_TRY(stage_in(ctx, mem, WS_IN_START, qstart, n, &ds));
+    IVX_TRY(stage_in(ctx, mem, WS_IN_END, qend, n, &de));
+    IVX_TRY(stage_in(ctx, mem, WS_IN_KEYLEN, key_hi, p->nkeys, &dh));
+    IVX_TRY(stage_out(ctx, mem, WS_OUT_A, out_len, n, &ol));
+    IVX_TRY(stage_out(ctx, mem, WS_OUT_B, out_min, n, &omn));
+    IVX_TRY(stage_out(ctx, mem, WS_OUT_C, out_max, n, &omx));
+    IVX_TRY(stage_out(ctx, mem, WS_OUT_D, out_q, (u64)n_q * n, &oq));
+    {
+        KernelTimer t(ctx);
+        IVX_TRY(ivx_depth_region_ranks_device(ctx, p->dp, p->nkeys, dk, ds, de, n, pos_lo, dh, skip_pos0 != 0, q_num, n_q, q_den, ol, omn, omx, oq));
+    }
+    cm.out(n);
+    IVX_TRY(copy_out(ctx, mem, out_len, ol, n));
+    IVX_TRY(copy_out(ctx, mem, out_min, omn, n));
+    IVX_TRY(copy_out(ctx, mem, out_max, omx, n));
+    IVX_TRY(copy_out(ctx, mem, out_q, oq, (u64)n_q * n));
+    if (mem == IVX_MEM_HOST) IVX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return IVX_OK;
+}
+
+extern "C" ivx_status ivx_depth_profile_window_quantiles(ivx_ctx *ctx, const ivx_index *p, int mem, uint32_t key,
+                                                         uint32_t first_pos, uint32_t last_pos, uint32_t width, uint64_t n, int skip_pos0,
+                                                         const uint32_t *q_num, uint32_t n_q, uint32_t q_den,
+                                                         int64_t *out_len, int32_t *out_min, int32_t *out_max, int32_t *out_q)
+{
+    if (!ctx) return IVX_ERR_INVALID;
+    IVX_TRY(ranks_check(ctx, p, mem, q_num, n_q, q_den, out_len, out_min, out_max, out_q));
+    if (width == 0) return ctx->fail(IVX_ERR_INVALID, "depth profile: window width 0");
+    if (key >= p->nkeys) return ctx->fail(IVX_ERR_INVALID, "depth profile: key id >= n_keys");
+    if (n && (n - 1) > (0xFFFFFFFFull - first_pos) / width)
+        return ctx->fail(IVX_ERR_INVALID, "depth profile: a window starts beyond position 2^32 - 1");
+    CallMetrics cm(ctx, false, n);
+    if (n == 0) return IVX_OK;
+    i64 *ol; i32 *omn, *omx, *oq;
+    IVX_TRY(stage_out(ctx, mem, WS_OUT_A, out_len, n, &ol));
+    IVX_TRY(stage_out(ctx, mem, WS_OUT_B, out_min, n, &omn));
+    IVX_TRY(stage_out(ctx, mem, WS_OUT_C, out_max, n, &omx));
+    IVX_TRY(stage_out(ctx, mem, WS_OUT_D, out_q, (u64)n_q * n, &oq));
+    {
+        KernelTimer t(ctx);
+        IVX_TRY(ivx_depth_window_ranks_device(ctx, p->dp, key, first_pos, last_pos, width, n, skip_pos0 != 0, q_num, n_q, q_den, ol, omn, omx, oq));
+    }
+    cm.out(n);
+    IVX_TRY(copy_out(ctx, mem, out_len, ol, n));
+    IVX_TRY(copy_out(ctx, mem, out_min, omn, n));
+    IVX_TRY(copy_out(ctx, mem, out_max, omx, n));
+    IVX_TRY(copy_out(ctx, mem, out_q, oq, (u64)n_q * n));
+    if (mem == IVX_MEM_HOST) IVX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return IVX_OK;
+}
+
 extern "C" ivx_status ivx_take_fixed(ivx_ctx *ctx, int mem, const void *src, uint32_t width, uint64_t n_src,
                                      const uint8_t *src_valid_bits, const uint32_t *idx, uint64_t n, void *out, uint8_t *out_valid)
 {

@@ -11,14 +11,14 @@
 //             modulo 2^64, so the rows need no scan of their own.  A key's last step has no length until the region's
 //             domain gives it one: it adds nothing here.
 //   query     one wavefront per region.  Two 64-ary wavefront searches inside the key's slice (the search of the expand
-//             kernel, restated) find b, the last step at or before the clipped end, and a, the last step at or before the
+//             kernel, restated; in ivx_depth_regions.hpp with the regions' bounds, shared with ivx_depth_rank.hip) find b, the last step at or before the clipped end, and a, the last step at or before the
 //             clipped start.  With a and b in one tile or in adjacent tiles the lanes stride over the steps a..b, the first
 //             and the last segment clipped; otherwise they walk a's tile tail and b's tile head, and the tiles strictly
 //             between come from the scanned aggregates (every step there has a same-key successor, b at the latest).  A
 //             wavefront reduction, and lane 0 stores the region's row.  No atomics, no LDS.
 //             The region index is made wave-uniform for the compiler, so the region's bounds and the key's slice arrive
 //             through scalar loads and every branch on them is a scalar branch.
-#include "ivx_device.hpp"
+#include "ivx_depth_regions.hpp"
 
 namespace {
 
@@ -33,12 +33,6 @@ static_assert(MAXT == IVX_DEPTH_MAX_THRESHOLDS, "the header's limit");
 constexpr u64 QUERY_CHUNK = (u64)RW << 23;      // regions per launch: the grid times the workgroup stays below 2^32 threads
 
 struct Thr { i32 t[MAXT]; u32 n; };
-
-// c0 of a key with steps: the coverage of its step at position 0 when skip_pos0 is set and that step exists
-__device__ __forceinline__ u32 key_c0(const DepthProfileView &dp, u32 first, int skip_pos0)
-{
-    return (skip_pos0 && dp.pos[first] == 0u) ? (u32)dp.cov[first] : 0u;
-}
 
 __device__ __forceinline__ void wave_reduce(u64 &sum, u64 (&ge)[MAXT], const Thr &thr)
 {
@@ -101,51 +95,6 @@ __global__ __launch_bounds__(RT) void k_region_check(const u32 *__restrict__ qke
         const u32 k = qkey[i];
         if (k >= nkeys && k != IVX_NULL_IDX) sc[SC_REGIONS_BAD] = 1ull;
     }
-}
-
-// where a region's key and closed bounds come from; get() returns false for an empty region
-struct RegionsIn {
-    const u32 *qkey, *qs, *qe, *key_hi; u32 pos_lo;
-    __device__ __forceinline__ bool get(u64 i, u32 &k, u32 &lo, u32 &hi) const
-    {
-        k = qkey ? qkey[i] : 0u;
-        if (k == IVX_NULL_IDX) return false;
-        const u32 s = qs[i], e = qe[i];
-        if (e < s) return false;
-        const u32 dh = key_hi ? key_hi[k] : 0xFFFFFFFFu;
-        lo = s > pos_lo ? s : pos_lo;
-        hi = e < dh ? e : dh;
-        return lo <= hi;                                    // (false also for a domain that ends below pos_lo)
-    }
-};
-struct WindowsIn {
-    u32 key, first, last, width;
-    __device__ __forceinline__ bool get(u64 i, u32 &k, u32 &lo, u32 &hi) const
-    {
-        k = key;
-        const u64 s = (u64)first + i * width;               // (<= 2^32 - 1: checked by the caller)
-        if (s > last) return false;
-        const u64 e = s + width - 1u;
-        lo = (u32)s;
-        hi = e > last ? last : (u32)e;
-        return true;
-    }
-};
-
-// the first step of [lo, lo + len) at a position >= x, lo + len if there is none: 64 probes a round, every lane of the
-// wavefront with the same arguments.  (32-bit throughout: a profile holds fewer than 2^32 - 256 steps.)
-__device__ __forceinline__ u32 wave_first_at_or_after(const u32 *__restrict__ pos, u32 lo, u32 len, u64 x, u32 l)
-{
-    while (len) {
-        const u32 stride = (len + 63u) >> 6;
-        const u32 off = (l + 1u) * stride - 1u;
-        const bool less = off < len && (u64)pos[lo + off] < x;
-        const u32 cnt = (u32)__popcll(__ballot(less));      // the probes before the answer: a prefix of the lanes
-        const u32 skip = min(cnt * stride, len);            // steps known to lie before the answer
-        lo += skip;
-        len = min(len - skip, stride - 1u);                 // the first probe that is not before it bounds the answer
-    }
-    return lo;
 }
 
 // the lanes stride over the steps from..to (from <= to <= b): step j covers [max(pos[j], lo), j < b ? pos[j + 1] - 1 : hi]
@@ -261,13 +210,9 @@ Thr make_thr(const i32 *thresholds, u32 n_thr)
 
 }  // namespace
 
-// thresholds: host memory, n_thr <= 8; every other pointer on the device.  Reads one word back when qkey is given: a key id
-// >= nkeys other than the skip mark is found before anything is indexed with it, and nothing is written then.
-ivx_status ivx_depth_regions_device(ivx_ctx *ctx, const DepthProfileView &dp, u32 nkeys, const u32 *qkey, const u32 *qs, const u32 *qe, u64 n,
-                                    u32 pos_lo, const u32 *key_hi, int skip_pos0, const i32 *thresholds, u32 n_thr,
-                                    i64 *out_len, i64 *out_sum, i64 *out_ge)
+// the regions' key ids (qkey nullable: every region on key 0) against nkeys, before anything is indexed with them: one word read back
+ivx_status ivx_depth_regions_check_keys(ivx_ctx *ctx, const u32 *qkey, u64 n, u32 nkeys)
 {
-    if (n == 0) return IVX_OK;
     if (qkey) {
         hipStream_t st = ctx->stream;
         IVX_HIP(ctx, hipMemsetAsync(ctx->dword(SC_REGIONS_BAD), 0, sizeof(u64), st));
@@ -275,6 +220,17 @@ ivx_status ivx_depth_regions_device(ivx_ctx *ctx, const DepthProfileView &dp, u3
         IVX_HIP(ctx, hipGetLastError());
         IVX_TRY(ctx->check_flag(SC_REGIONS_BAD, st, "depth profile: key id >= n_keys"));
     } else if (nkeys == 0) return ctx->fail(IVX_ERR_INVALID, "depth profile: key id >= n_keys");
+    return IVX_OK;
+}
+
+// thresholds: host memory, n_thr <= 8; every other pointer on the device.  Reads one word back when qkey is given: a key id
+// >= nkeys other than the skip mark is found before anything is indexed with it, and nothing is written then.
+ivx_status ivx_depth_regions_device(ivx_ctx *ctx, const DepthProfileView &dp, u32 nkeys, const u32 *qkey, const u32 *qs, const u32 *qe, u64 n,
+                                    u32 pos_lo, const u32 *key_hi, int skip_pos0, const i32 *thresholds, u32 n_thr,
+                                    i64 *out_len, i64 *out_sum, i64 *out_ge)
+{
+    if (n == 0) return IVX_OK;
+    IVX_TRY(ivx_depth_regions_check_keys(ctx, qkey, n, nkeys));
     if (!out_len && !out_sum && !(out_ge && n_thr)) return IVX_OK;
     return region_query(ctx, dp, RegionsIn{qkey, qs, qe, key_hi, pos_lo}, qkey ? IVX_NULL_IDX : 0u, n, skip_pos0, make_thr(thresholds, n_thr), out_len, out_sum, out_ge);
 }

@@ -398,5 +398,14 @@ ivx_status ivx_depth_regions_device(ivx_ctx *ctx, const DepthProfileView &dp, u3
                                     i64 *out_len, i64 *out_sum, i64 *out_ge);
 ivx_status ivx_depth_windows_device(ivx_ctx *ctx, const DepthProfileView &dp, u32 key, u32 first_pos, u32 last_pos, u32 width, u64 n,
                                     int skip_pos0, const i32 *thresholds, u32 n_thr, i64 *out_len, i64 *out_sum, i64 *out_ge);
+ivx_status ivx_depth_regions_check_keys(ivx_ctx *ctx, const u32 *qkey, u64 n, u32 nkeys);    // a key id >= nkeys other than the skip mark: IVX_ERR_INVALID (reads one word back)
+// ivx_depth_rank.hip: bases, min, max and up to 8 lower quantiles of the per-base coverage per region / per window (q_num:
+// host memory, rank = floor((bases - 1) * q_num / q_den); out_q quantile-major [n_q * n]; any output may be null)
+ivx_status ivx_depth_region_ranks_device(ivx_ctx *ctx, const DepthProfileView &dp, u32 nkeys, const u32 *qkey, const u32 *qs, const u32 *qe, u64 n,
+                                         u32 pos_lo, const u32 *key_hi, int skip_pos0, const u32 *q_num, u32 n_q, u32 q_den,
+                                         i64 *out_len, i32 *out_min, i32 *out_max, i32 *out_q);
+ivx_status ivx_depth_window_ranks_device(ivx_ctx *ctx, const DepthProfileView &dp, u32 key, u32 first_pos, u32 last_pos, u32 width, u64 n,
+                                         int skip_pos0, const u32 *q_num, u32 n_q, u32 q_den,
+                                         i64 *out_len, i32 *out_min, i32 *out_max, i32 *out_q);
 
 ivx_status ivx_index_alloc(ivx_ctx *ctx, ivx_index *ix, size_t bytes, void **out);

@@ -70,7 +70,10 @@ enum {
     SC_CIG_OFFN = SC_CIG_OFF0 + 1,              // 1 word, u64: the last one
     // ---- overlap index build, see SC_JOIN_BAD
     SC_JOIN_LENHIST = SC_CIG_OFFN + 1,          // SC_LENHIST_N u32: rows per length class
-    SC_DEVICE_WORDS = SC_JOIN_LENHIST + (SC_LENHIST_N + 1) / 2,     // ---- length of d_scalars
+    // ---- depth region order statistics (ivx_depth_rank.hip).  Call-local: cleared ahead of the query kernel, read by the select
+    // kernel on the device only.
+    SC_RANK_LONG = SC_JOIN_LENHIST + (SC_LENHIST_N + 1) / 2,        // 1 word, u64: regions of more than 64 segments listed for the select kernel
+    SC_DEVICE_WORDS = SC_RANK_LONG + 1,         // ---- length of d_scalars
 
     // ---- host only
     SC_LANDING = SC_DEVICE_WORDS,               // SC_LANDING_WORDS words, any T: where ivx_ctx::fetch_wait(src, ...) lands a value from scratch; dead when it returns
@@ -103,7 +106,7 @@ static_assert(SC_RANGE - SC_SORT_VAR == SC_SORT_FIELDS && SC_SORT_VAR % 2 == 0, 
 static_assert(SC_LIN == SC_RANGE + 6 && SC_DEPTH_BAD == SC_LIN + 2, "sort64 fetches the ranges and the two lin words as eight words");
 static_assert(SC_DEPTH_SPARE == SC_DEPTH_BAD + 5 && SC_STEPS_TOTAL == SC_DEPTH_BAD + 6 && SC_DEPTH_BAD % 2 == 0, "depth()'s six words are cleared and fetched as one");
 static_assert(SC_CIG_OFF0 == SC_CIG_BAD + 1 && SC_CIG_OFFN == SC_CIG_BAD + 2 && SC_CIG_BAD % 2 == 0, "the CIGAR check's three words are cleared and fetched as one");
-static_assert(SC_LENHIST_N * sizeof(u32) <= (size_t)(SC_DEVICE_WORDS - SC_JOIN_LENHIST) * sizeof(u64), "the length-class counters fit their words");
+static_assert(SC_LENHIST_N * sizeof(u32) <= (size_t)(SC_RANK_LONG - SC_JOIN_LENHIST) * sizeof(u64), "the length-class counters fit their words");
 static_assert(HDR_WORDS * sizeof(u32) <= (size_t)(SC_HDR_MIRROR - SC_ROUTE_HDR) * sizeof(u64), "a routing view's header ends at or below the header mirror");
 static_assert(SC_HDR_MIRROR * sizeof(u64) + HDR_WORDS * sizeof(u32) <= SC_HOST_WORDS * sizeof(u64), "the header mirror fits the host words");
 

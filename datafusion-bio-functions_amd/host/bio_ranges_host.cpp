@@ -1192,9 +1192,61 @@ int region_coords(brh_session *s, const PosCol &p, std::vector<int64_t> *out)
     return 0;
 }
 
-// The regions of `regions` summarised over `profile`, whose keys are the ids `id_of` gives (IVX_NULL_IDX, or an id of
-// n_keys or more: a contig the profile does not know, coverage 0 everywhere).  key_len (null: no length table) gives the domain
-// the per-base rows have: [0, len - 1] when zero_based, else [1, len] without the step at position 0.
+// The rows of a regions table as the closed u32 regions the profile calls take.  The keys are the ids `id_of` gives
+// (IVX_NULL_IDX, or an id of n_keys or more: a contig the profile does not know, coverage 0 everywhere: `unknown`, answered by
+// the caller).  A region that is empty whatever the coverage gets the skip mark.  key_len (null: no length table) gives the
+// domain the per-base rows have: [0, len - 1] when zero_based, else [1, len] without the step at position 0.
+struct RegionRows {
+    uint64_t n = 0;
+    std::vector<uint32_t> qk, qs, qe, key_hi;
+    std::vector<uint8_t> unknown;
+    uint32_t pos_lo = 0;
+    bool has_len = false, skip_pos0 = false;
+
+    int load(brh_session *s, const char *what, uint32_t n_keys, const std::function<uint32_t(std::string_view)> &id_of,
+             const std::vector<uint32_t> *key_len, int zero_based, brh_batch regions, brh_columns cols, int end_exclusive)
+    {
+        if (!regions.array || !regions.schema) return fail(s, std::string(what) + ": null regions batch");
+        if (cols.n_keys != 1 || !cols.keys || !cols.start || !cols.end)
+            return fail(s, std::string(what) + ": the regions take one contig, one start and one end column");
+        StrCol contig; PosCol ps, pe;
+        std::vector<int64_t> s64, e64;
+        if (get_contig(s, regions, cols.keys[0], &contig) || get_pos(s, regions, cols.start, "start", &ps) || get_pos(s, regions, cols.end, "end", &pe) ||
+            region_coords(s, ps, &s64) || region_coords(s, pe, &e64)) return 1;
+        n = (uint64_t)regions.array->length;
+        qk.assign(n ? n : 1, 0); qs.assign(n ? n : 1, 0); qe.assign(n ? n : 1, 0);
+        unknown.assign(n ? n : 1, 0);
+        has_len = key_len != nullptr;
+        pos_lo = (key_len && !zero_based) ? 1u : 0u;
+        skip_pos0 = key_len && !zero_based;
+        if (key_len) {
+            key_hi.assign(std::max<size_t>(key_len->size(), n_keys), 0);
+            for (size_t k = 0; k < key_len->size(); k++) key_hi[k] = zero_based ? ((*key_len)[k] ? (*key_len)[k] - 1u : 0u) : (*key_len)[k];
+        }
+        std::string_view last; uint32_t last_id = IVX_NULL_IDX; bool have = false;
+        for (uint64_t i = 0; i < n; i++) {
+            int64_t a = s64[i], b = e64[i];
+            bool empty = false;
+            if (end_exclusive) { if (b <= a) empty = true; else b -= 1; }
+            a = std::min<int64_t>(std::max<int64_t>(a, 0), (int64_t)UINT32_MAX);
+            b = std::min<int64_t>(std::max<int64_t>(b, 0), (int64_t)UINT32_MAX);
+            qs[i] = (uint32_t)a; qe[i] = (uint32_t)b;
+            uint32_t k = IVX_NULL_IDX;
+            if (!contig.null_at((int64_t)i)) {
+                const std::string_view name = contig.at((int64_t)i);
+                if (!have || name != last) { last_id = id_of(name); last = name; have = true; }
+                k = last_id;
+            }
+            if (k >= n_keys) { unknown[i] = !empty && b >= a; k = IVX_NULL_IDX; }
+            else if (empty || (key_len && zero_based && (*key_len)[k] == 0)) k = IVX_NULL_IDX;        // (a contig of length 0 has no position)
+            qk[i] = k;
+        }
+        return 0;
+    }
+    const uint32_t *hi() const { return has_len ? key_hi.data() : nullptr; }
+};
+
+// The regions of `regions` summarised over `profile` (RegionRows for the keys, the domain and the unknown contigs)
 int summarize_regions(brh_session *s, const ivx_index *profile, uint32_t n_keys, const std::function<uint32_t(std::string_view)> &id_of,
                       const std::vector<uint32_t> *key_len, int zero_based, brh_batch regions, brh_columns cols, int end_exclusive,
                       const int32_t *thresholds, uint32_t n_thr,
@@ -1204,46 +1256,17 @@ int summarize_regions(brh_session *s, const ivx_index *profile, uint32_t n_keys,
     if (cols.n_keys != 1 || !cols.keys || !cols.start || !cols.end) return fail(s, "depth_regions: the regions take one contig, one start and one end column");
     if (n_thr > IVX_DEPTH_MAX_THRESHOLDS) return fail(s, "depth_regions: more than 8 thresholds");
     if (n_thr && (!thresholds || !ge || !ge_schemas)) return fail(s, "depth_regions: null thresholds or threshold outputs");
-    StrCol contig; PosCol ps, pe;
-    std::vector<int64_t> s64, e64;
-    if (get_contig(s, regions, cols.keys[0], &contig) || get_pos(s, regions, cols.start, "start", &ps) || get_pos(s, regions, cols.end, "end", &pe) ||
-        region_coords(s, ps, &s64) || region_coords(s, pe, &e64)) return 1;
-    const uint64_t n = (uint64_t)regions.array->length;
-    // ---- closed u32 regions; a region that is empty whatever the coverage gets the skip mark, an unknown contig is answered here
-    std::vector<uint32_t> qk(n ? n : 1), qs(n ? n : 1), qe(n ? n : 1);
-    std::vector<uint8_t> unknown(n ? n : 1, 0);
-    const uint32_t pos_lo = (key_len && !zero_based) ? 1u : 0u;
-    std::vector<uint32_t> key_hi;
-    if (key_len) {
-        key_hi.assign(std::max<size_t>(key_len->size(), n_keys), 0);
-        for (size_t k = 0; k < key_len->size(); k++) key_hi[k] = zero_based ? ((*key_len)[k] ? (*key_len)[k] - 1u : 0u) : (*key_len)[k];
-    }
-    std::string_view last; uint32_t last_id = IVX_NULL_IDX; bool have = false;
-    for (uint64_t i = 0; i < n; i++) {
-        int64_t a = s64[i], b = e64[i];
-        bool empty = false;
-        if (end_exclusive) { if (b <= a) empty = true; else b -= 1; }
-        a = std::min<int64_t>(std::max<int64_t>(a, 0), (int64_t)UINT32_MAX);
-        b = std::min<int64_t>(std::max<int64_t>(b, 0), (int64_t)UINT32_MAX);
-        qs[i] = (uint32_t)a; qe[i] = (uint32_t)b;
-        uint32_t k = IVX_NULL_IDX;
-        if (!contig.null_at((int64_t)i)) {
-            const std::string_view name = contig.at((int64_t)i);
-            if (!have || name != last) { last_id = id_of(name); last = name; have = true; }
-            k = last_id;
-        }
-        if (k >= n_keys) { unknown[i] = !empty && b >= a; k = IVX_NULL_IDX; }
-        else if (empty || (key_len && zero_based && (*key_len)[k] == 0)) k = IVX_NULL_IDX;        // (a contig of length 0 has no position)
-        qk[i] = k;
-    }
+    RegionRows r;
+    if (r.load(s, "depth_regions", n_keys, id_of, key_len, zero_based, regions, cols, end_exclusive)) return 1;
+    const uint64_t n = r.n;
     std::vector<int64_t> ol(n ? n : 1, 0), os(n ? n : 1, 0), og((size_t)n_thr * n + 1, 0);
-    const ivx_status st = ivx_depth_profile_summarize(s->ctx, profile, IVX_MEM_HOST, qk.data(), qs.data(), qe.data(), n, pos_lo,
-                                                      key_len ? key_hi.data() : nullptr, key_len && !zero_based, thresholds, n_thr,
+    const ivx_status st = ivx_depth_profile_summarize(s->ctx, profile, IVX_MEM_HOST, r.qk.data(), r.qs.data(), r.qe.data(), n, r.pos_lo,
+                                                      r.hi(), r.skip_pos0, thresholds, n_thr,
                                                       ol.data(), os.data(), n_thr ? og.data() : nullptr);
     if (st != IVX_OK) return fail_ivx(s, st);
     for (uint64_t i = 0; i < n; i++) {
-        if (!unknown[i]) continue;
-        ol[i] = (int64_t)qe[i] - (int64_t)qs[i] + 1;
+        if (!r.unknown[i]) continue;
+        ol[i] = (int64_t)r.qe[i] - (int64_t)r.qs[i] + 1;
         for (uint32_t j = 0; j < n_thr; j++) og[(size_t)j * n + i] = thresholds[j] <= 0 ? ol[i] : 0;
     }
     make_primitive<int64_t>(bases, ol.data(), (int64_t)n, nullptr); make_schema(bases_schema, "l", "bases", false);
@@ -1251,6 +1274,39 @@ int summarize_regions(brh_session *s, const ivx_index *profile, uint32_t n_keys,
     for (uint32_t j = 0; j < n_thr; j++) {
         make_primitive<int64_t>(&ge[j], og.data() + (size_t)j * n, (int64_t)n, nullptr);
         make_schema(&ge_schemas[j], "l", ("bases_ge_" + std::to_string(thresholds[j])).c_str(), false);
+    }
+    return 0;
+}
+
+// The same rows ranked over `profile` (ivx_depth_profile_quantiles): bases, and min / max / the quantiles, NULL where bases = 0
+int rank_regions(brh_session *s, const ivx_index *profile, uint32_t n_keys, const std::function<uint32_t(std::string_view)> &id_of,
+                 const std::vector<uint32_t> *key_len, int zero_based, brh_batch regions, brh_columns cols, int end_exclusive,
+                 const uint32_t *q_num, uint32_t n_q, uint32_t q_den,
+                 ArrowArray *bases, ArrowSchema *bases_schema, ArrowArray *mn, ArrowSchema *mn_schema, ArrowArray *mx, ArrowSchema *mx_schema,
+                 ArrowArray *q, ArrowSchema *q_schemas)
+{
+    if (n_q > IVX_DEPTH_MAX_QUANTILES) return fail(s, "depth_region_quantiles: more than 8 quantiles");
+    if (n_q && (!q_num || !q || !q_schemas)) return fail(s, "depth_region_quantiles: null q_num or quantile outputs");
+    RegionRows r;
+    if (r.load(s, "depth_region_quantiles", n_keys, id_of, key_len, zero_based, regions, cols, end_exclusive)) return 1;
+    const uint64_t n = r.n;
+    std::vector<int64_t> ol(n ? n : 1, 0);
+    std::vector<int32_t> omn(n ? n : 1, 0), omx(n ? n : 1, 0), oq((size_t)n_q * n + 1, 0);
+    const ivx_status st = ivx_depth_profile_quantiles(s->ctx, profile, IVX_MEM_HOST, r.qk.data(), r.qs.data(), r.qe.data(), n, r.pos_lo,
+                                                      r.hi(), r.skip_pos0, q_num, n_q, q_den,
+                                                      ol.data(), omn.data(), omx.data(), n_q ? oq.data() : nullptr);
+    if (st != IVX_OK) return fail_ivx(s, st);
+    std::vector<uint8_t> valid(n ? n : 1, 0);
+    for (uint64_t i = 0; i < n; i++) {
+        if (r.unknown[i]) ol[i] = (int64_t)r.qe[i] - (int64_t)r.qs[i] + 1;      // (coverage 0 everywhere: the zeros are in place)
+        valid[i] = ol[i] > 0;
+    }
+    make_primitive<int64_t>(bases, ol.data(), (int64_t)n, nullptr); make_schema(bases_schema, "l", "bases", false);
+    make_primitive<int32_t>(mn, omn.data(), (int64_t)n, valid.data()); make_schema(mn_schema, "i", "min", true);
+    make_primitive<int32_t>(mx, omx.data(), (int64_t)n, valid.data()); make_schema(mx_schema, "i", "max", true);
+    for (uint32_t j = 0; j < n_q; j++) {
+        make_primitive<int32_t>(&q[j], oq.data() + (size_t)j * n, (int64_t)n, valid.data());
+        make_schema(&q_schemas[j], "i", ("q_" + std::to_string(q_num[j]) + "_" + std::to_string(q_den)).c_str(), true);
     }
     return 0;
 }
@@ -1288,6 +1344,39 @@ extern "C" int brh_depth_push_regions(brh_depth_push *dp, brh_batch regions, brh
                              [&](std::string_view k) { auto it = dp->ids.find(std::string(k)); return it == dp->ids.end() ? IVX_NULL_IDX : it->second; },
                              dp->dense ? &dp->key_len : nullptr, zero_based, regions, region_cols, end_exclusive, thresholds, n_thr,
                              bases, bases_schema, sum, sum_schema, ge, ge_schemas);
+}
+
+extern "C" int brh_depth_region_quantiles(brh_session *s, brh_batch reads, brh_batch prior, brh_batch lengths, brh_batch regions, brh_columns region_cols,
+                                          int zero_based, int end_exclusive, uint32_t filter_flag, uint32_t min_mapq,
+                                          const uint32_t *q_num, uint32_t n_q, uint32_t q_den,
+                                          ArrowArray *bases, ArrowSchema *bases_schema, ArrowArray *mn, ArrowSchema *mn_schema,
+                                          ArrowArray *mx, ArrowSchema *mx_schema, ArrowArray *q, ArrowSchema *q_schemas)
+{
+    if (!s) return 1;
+    DepthInputs in;
+    if (in.load(s, reads, prior, lengths)) return 1;
+    IndexGuard g;
+    const ivx_status st = in.profile(s->ctx, in.has_prior ? in.skey.data() : nullptr, in.ss.data(), in.se.data(), in.has_prior ? in.sw.data() : nullptr,
+                                     in.n_seg, in.nk, in.has_len ? in.key_len.data() : nullptr, filter_flag, min_mapq, &g.ix);
+    if (st != IVX_OK) return fail_ivx(s, st);
+    const uint32_t known = (uint32_t)in.dict.names.size();           // (an empty dictionary: key 0 stands for no contig)
+    return rank_regions(s, g.ix, known, [&](std::string_view k) { return in.dict.id_of(k); }, in.has_len ? &in.key_len : nullptr, zero_based,
+                        regions, region_cols, end_exclusive, q_num, n_q, q_den, bases, bases_schema, mn, mn_schema, mx, mx_schema, q, q_schemas);
+}
+
+extern "C" int brh_depth_push_region_quantiles(brh_depth_push *dp, brh_batch regions, brh_columns region_cols, int zero_based, int end_exclusive,
+                                               const uint32_t *q_num, uint32_t n_q, uint32_t q_den,
+                                               ArrowArray *bases, ArrowSchema *bases_schema, ArrowArray *mn, ArrowSchema *mn_schema,
+                                               ArrowArray *mx, ArrowSchema *mx_schema, ArrowArray *q, ArrowSchema *q_schemas)
+{
+    if (!dp) return 1;
+    brh_session *s = dp->s;
+    if (depth_push_check(dp) || depth_push_merge_all(dp)) return 1;            // the merged profile stays the stack's only entry
+    const uint32_t known = std::min<uint32_t>((uint32_t)dp->names.size(), dp->built_nk);
+    return rank_regions(s, dp->stack[0], known,
+                        [&](std::string_view k) { auto it = dp->ids.find(std::string(k)); return it == dp->ids.end() ? IVX_NULL_IDX : it->second; },
+                        dp->dense ? &dp->key_len : nullptr, zero_based, regions, region_cols, end_exclusive, q_num, n_q, q_den,
+                        bases, bases_schema, mn, mn_schema, mx, mx_schema, q, q_schemas);
 }
 
 // ---- f3: payload gather

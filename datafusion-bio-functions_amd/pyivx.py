@@ -33,6 +33,7 @@ SYMBOLS = [
     "ivx_depth_profile_read", "ivx_depth_profile_expand", "ivx_depth_profile_merge", "ivx_depth_profile_blocks",
     "ivx_cigar_parse", "ivx_depth_text", "ivx_depth_profile_build_text",
     "ivx_depth_profile_summarize", "ivx_depth_profile_windows",
+    "ivx_depth_profile_quantiles", "ivx_depth_profile_window_quantiles",
 ]
 
 # outputs one workgroup of the expand kernel makes (csrc/ivx_depth_expand.hip DEPTH_EXPAND_TILE; tests/test_depth_per_base_tile.py)
@@ -43,6 +44,13 @@ DEPTH_MERGE_TILE = 2048
 DEPTH_REGION_TILE = 1024
 # thresholds one summary call takes (include/ivx.h IVX_DEPTH_MAX_THRESHOLDS)
 DEPTH_MAX_THRESHOLDS = 8
+# the region order statistics (csrc/ivx_depth_rank.hip; tests/test_depth_quantiles_cpu.py): steps per (min, max) tile, segments
+# one wavefront ranks in registers (more go to the select kernel), workgroups of the select kernel
+DEPTH_RANK_TILE = 1024
+DEPTH_RANK_SEGS = 64
+DEPTH_RANK_SELECT_GRID = 512
+# quantiles one call takes (include/ivx.h IVX_DEPTH_MAX_QUANTILES)
+DEPTH_MAX_QUANTILES = 8
 # bytes one thread / one workgroup of the text-CIGAR parser takes (csrc/ivx_cigar.hip CIGAR_B, CIGAR_TILE)
 CIGAR_B = 16
 CIGAR_TILE = 4096
@@ -134,6 +142,12 @@ def lib():
         L.ivx_depth_profile_windows.restype = C.c_int
         L.ivx_depth_profile_windows.argtypes = ([C.c_void_p, C.c_void_p, C.c_int] + [C.c_uint32] * 4 + [C.c_uint64, C.c_int, C.c_void_p, C.c_uint32] +
                                                 [C.c_void_p] * 3)
+        L.ivx_depth_profile_quantiles.restype = C.c_int
+        L.ivx_depth_profile_quantiles.argtypes = ([C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 3 + [C.c_uint64, C.c_uint32, C.c_void_p, C.c_int,
+                                                  C.c_void_p, C.c_uint32, C.c_uint32] + [C.c_void_p] * 4)
+        L.ivx_depth_profile_window_quantiles.restype = C.c_int
+        L.ivx_depth_profile_window_quantiles.argtypes = ([C.c_void_p, C.c_void_p, C.c_int] + [C.c_uint32] * 4 + [C.c_uint64, C.c_int, C.c_void_p, C.c_uint32,
+                                                         C.c_uint32] + [C.c_void_p] * 4)
         # test hook of csrc/ivx_sweep.hip (not in include/ivx.h): what subtract's count pass did (tests/test_gpu_subtract_edges.py)
         L.ivx_debug_subtract_paths.restype = C.c_int
         L.ivx_debug_subtract_paths.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
@@ -340,6 +354,45 @@ class DepthProfile:
         out = self._summary_out(int(n), len(thr), device, self.device or "cuda:0", outputs)
         ctx._chk(lib().ivx_depth_profile_windows(ctx.h, self.h, MEM_DEVICE if device else MEM_HOST, int(key), int(first_pos), int(last_pos),
                                                  int(width), int(n), int(bool(skip_pos0)), _ptr(thr), len(thr), *[_ptr(o) for o in out]))
+        return tuple(out)
+
+    def _rank_out(self, n, n_q, device, dev, outputs):
+        shapes, dts = ((n,), (n,), (n,), (n_q, n)), ("int64", "int32", "int32", "int32")
+        if device:
+            import torch
+            return [torch.empty(sh, dtype=getattr(torch, dt), device=dev) if w else None for w, sh, dt in zip(outputs, shapes, dts)]
+        return [np.empty(sh, dt) if w else None for w, sh, dt in zip(outputs, shapes, dts)]
+
+    def quantiles(self, key, start, end, q_num=(), q_den=2, pos_lo=0, key_hi=None, skip_pos0=False, ctx=None, outputs=(True,) * 4):
+        """per region of summarize() -> (bases int64[n], min int32[n], max int32[n], quantiles int32[n_q, n]) of its per-base
+        coverage; quantile j is element floor((bases - 1) * q_num[j] / q_den) of the sorted values (q_num=(1,), q_den=2: the
+        lower median), and a region without bases gives 0.  None where `outputs` does not ask.  numpy arrays, or torch
+        device tensors (then the results are device tensors and the call may return with kernels in flight)."""
+        ctx = ctx or self.ctx
+        mem = _mem_of(key, start, end, key_hi)
+        qn = np.ascontiguousarray(q_num, dtype=np.uint32).reshape(-1)
+        if mem == MEM_DEVICE:
+            assert all(a is None or a.is_contiguous() for a in (key, start, end, key_hi))
+            n, dev = int(start.numel()), start.device
+        else:
+            key, start, end, key_hi = (_np(a, np.uint32) for a in (key, start, end, key_hi))
+            n, dev = len(start), None
+        out = self._rank_out(n, len(qn), mem == MEM_DEVICE, dev, outputs)
+        ctx._chk(lib().ivx_depth_profile_quantiles(ctx.h, self.h, mem, _ptr(key), _ptr(start), _ptr(end), n, int(pos_lo), _ptr(key_hi),
+                                                   int(bool(skip_pos0)), _ptr(qn), len(qn), int(q_den), *[_ptr(o) for o in out]))
+        return tuple(out)
+
+    def window_quantiles(self, key, first_pos, last_pos, width, n=None, q_num=(), q_den=2, skip_pos0=False, device=False, ctx=None,
+                         outputs=(True,) * 4):
+        """the same four outputs for the windows of windows()"""
+        ctx = ctx or self.ctx
+        if n is None:
+            n = (int(last_pos) - int(first_pos)) // int(width) + 1 if int(last_pos) >= int(first_pos) and int(width) > 0 else 0
+        qn = np.ascontiguousarray(q_num, dtype=np.uint32).reshape(-1)
+        out = self._rank_out(int(n), len(qn), device, self.device or "cuda:0", outputs)
+        ctx._chk(lib().ivx_depth_profile_window_quantiles(ctx.h, self.h, MEM_DEVICE if device else MEM_HOST, int(key), int(first_pos),
+                                                          int(last_pos), int(width), int(n), int(bool(skip_pos0)), _ptr(qn), len(qn),
+                                                          int(q_den), *[_ptr(o) for o in out]))
         return tuple(out)
 
     def free(self):

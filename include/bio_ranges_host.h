@@ -244,6 +244,31 @@ int  brh_depth_push_regions(brh_depth_push *dp, brh_batch regions, brh_columns r
                             struct ArrowArray *sum, struct ArrowSchema *sum_schema,
                             struct ArrowArray *ge, struct ArrowSchema *ge_schemas);
 
+/* Depth region order statistics: per row of a regions table the number of bases and the minimum, the maximum and up to 8
+ * quantiles of the per-base coverage over them (ivx.h ivx_depth_profile_quantiles) -- minimum and median coverage per target or
+ * bin (bedtools map -o min,max, Picard MIN_ / MEDIAN_TARGET_COVERAGE, mosdepth --use-median).
+ * brh_depth_region_quantiles / brh_depth_push_region_quantiles take the arguments of brh_depth_regions / brh_depth_push_regions
+ * one for one (reads / prior / lengths / regions / region_cols / zero_based / end_exclusive / the read filter; the same domain,
+ * the same unknown contigs, the stream stays open), with q_num[n_q] (n_q <= 8) and q_den (1 .. 65536, every q_num <= q_den) in
+ * place of the thresholds: quantile j is element floor((bases - 1) * q_num[j] / q_den) of the region's per-base values sorted
+ * ascending -- q_num = 1, q_den = 2 is the lower median -- which equals that element of the sorted per-base rows inside the
+ * region whenever those fit Int16.
+ * Outputs: one row per region, in region order: bases Int64, non-null; min, max and n_q arrays q[j] named q_<q_num[j]>_<q_den>,
+ *   all Int32 and NULL exactly where bases = 0; q / q_schemas point at n_q structs (NULL when n_q = 0). */
+int  brh_depth_region_quantiles(brh_session *s, brh_batch reads, brh_batch prior, brh_batch lengths, brh_batch regions, brh_columns region_cols,
+                                int zero_based, int end_exclusive, uint32_t filter_flag, uint32_t min_mapq,
+                                const uint32_t *q_num, uint32_t n_q, uint32_t q_den,
+                                struct ArrowArray *bases, struct ArrowSchema *bases_schema,
+                                struct ArrowArray *min, struct ArrowSchema *min_schema,
+                                struct ArrowArray *max, struct ArrowSchema *max_schema,
+                                struct ArrowArray *q, struct ArrowSchema *q_schemas);
+int  brh_depth_push_region_quantiles(brh_depth_push *dp, brh_batch regions, brh_columns region_cols, int zero_based, int end_exclusive,
+                                     const uint32_t *q_num, uint32_t n_q, uint32_t q_den,
+                                     struct ArrowArray *bases, struct ArrowSchema *bases_schema,
+                                     struct ArrowArray *min, struct ArrowSchema *min_schema,
+                                     struct ArrowArray *max, struct ArrowSchema *max_schema,
+                                     struct ArrowArray *q, struct ArrowSchema *q_schemas);
+
 /* compute::take of ONE payload column with an index array a join / nearest call returned
  * (interval_join.rs:1655-1667, nearest.rs:469-482), on the device.  column: any fixed-width primitive
  * (ints, floats, date/time/timestamp/duration, decimal128/256, fixed-size binary of 1/2/4/8/16/32 bytes),

@@ -510,6 +510,48 @@ ivx_status ivx_depth_profile_windows(ivx_ctx *ctx, const ivx_index *profile, int
                                      const int32_t *thresholds /* host memory */, uint32_t n_thr,
                                      int64_t *out_len /* nullable */, int64_t *out_sum /* nullable */, int64_t *out_ge /* nullable */);
 
+/*      REGION ORDER STATISTICS of a profile: the smallest and the largest per-base coverage of a region and up to 8 of its
+ *      quantiles -- minimum coverage per target, median depth per target or bin (bedtools map -o min,max, Picard MIN_ /
+ *      MEDIAN_TARGET_COVERAGE, mosdepth --use-median).  Exact and bit-reproducible.  v(p), D(k), R_i, the zero stretches,
+ *      the last step that extends to the end of its domain, skip_pos0 and the null key are those of REGION SUMMARIES above.
+ *      With L = |R_i| > 0:
+ *        out_len[i]       = L                                         (int64_t[n], nullable)
+ *        out_min[i]       = min of v(p) over p in R_i                 (int32_t[n], nullable)
+ *        out_max[i]       = max of v(p) over p in R_i                 (int32_t[n], nullable)
+ *        out_q[j*n + i]   = element r of the L values v(p), p in R_i, sorted ascending,
+ *                           r = floor((L - 1) * q_num[j] / q_den)     (int32_t[n_q * n], quantile-major, nullable)
+ *      in integers (L - 1 < 2^32, q_num <= 2^16): the "lower" quantile, the lower median for q = 1/2 and an even L; q_num = 0
+ *      is the minimum and q_num = q_den the maximum.  L = 0 (an empty region, the null key, a domain that cuts the region
+ *      away) gives 0 in all three, and out_len tells.  Output order = input order; n = 0 is a no-op; any output may be NULL
+ *      on its own.  q_num is HOST memory in both modes.
+ *      IVX_ERR_INVALID: n_q > IVX_DEPTH_MAX_QUANTILES; q_den = 0 or q_den > 65536; a q_num[j] > q_den; and every case of
+ *      ivx_depth_profile_summarize / _windows (a key id >= n_keys is found on the device before it indexes anything, and
+ *      nothing is written then; out_len aligned to 8 bytes, the other pointers to 4 in device mode; width = 0, ...).
+ *      IVX_ERR_UNSUPPORTED: any index that is not a profile.  Usable from any context on the profile's device;
+ *      IVX_MEM_DEVICE calls may return with kernels in flight; no host round trip between the kernels of a call beyond the
+ *      key check's; drops the state a sizing call of another operation left on the context.  Scratch, counted against the
+ *      context's memory limit: 8 bytes per 1024 steps and level of a sparse table of (min, max), at most log2(steps / 1024)
+ *      levels; 24 bytes per region when quantiles are asked for; the staged columns in host mode.
+ *      Cost per region: min and max take two searches in the key's steps, at most two tiles of steps and two table entries,
+ *      whatever the region's length; so do the quantiles of a region of at most 64 segments (its steps, plus the zero
+ *      stretch ahead of the key's first step), ranked in one wavefront's registers.  A region of more segments is selected
+ *      by one workgroup in 1 to 4 passes over its steps (one per 8 bits of max - min; a coverage span below 256 is one pass
+ *      for all quantiles): linear in the region's steps, times the passes. */
+#define IVX_DEPTH_MAX_QUANTILES 8
+ivx_status ivx_depth_profile_quantiles(ivx_ctx *ctx, const ivx_index *profile, int mem,
+                                       const uint32_t *qkey /* nullable: every region on key 0 */, const uint32_t *qstart, const uint32_t *qend, uint64_t n,
+                                       uint32_t pos_lo, const uint32_t *key_hi /* nullable */, int skip_pos0,
+                                       const uint32_t *q_num /* host memory */, uint32_t n_q, uint32_t q_den,
+                                       int64_t *out_len /* nullable */, int32_t *out_min /* nullable */, int32_t *out_max /* nullable */,
+                                       int32_t *out_q /* nullable */);
+/*      The same four outputs for the windows of ivx_depth_profile_windows.  With width = 1, min = max = every quantile =
+ *      ivx_depth_profile_expand in int32. */
+ivx_status ivx_depth_profile_window_quantiles(ivx_ctx *ctx, const ivx_index *profile, int mem, uint32_t key,
+                                              uint32_t first_pos, uint32_t last_pos, uint32_t width, uint64_t n, int skip_pos0,
+                                              const uint32_t *q_num /* host memory */, uint32_t n_q, uint32_t q_den,
+                                              int64_t *out_len /* nullable */, int32_t *out_min /* nullable */, int32_t *out_max /* nullable */,
+                                              int32_t *out_q /* nullable */);
+
 /* ---- f3: `compute::take` of payload columns with the index arrays the probes return
  *      (interval_join.rs:1655-1667, nearest.rs:469-482).  idx[i] == IVX_NULL_IDX or a null source
  *      slot (src_valid_bits: Arrow validity bitmap of the source, bit offset 0, nullable) gives

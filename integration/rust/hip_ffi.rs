@@ -134,6 +134,16 @@ extern "C" {
     pub fn ivx_depth_profile_windows(ctx: *mut IvxCtx, profile: *const IvxIndex, mem: i32, key: u32, first_pos: u32, last_pos: u32,
                                      width: u32, n: u64, skip_pos0: i32, thresholds: *const i32, n_thr: u32,
                                      out_len: *mut i64, out_sum: *mut i64, out_ge: *mut i64) -> i32;
+    // order statistics of a profile's regions / windows: bases, min, max and up to 8 lower quantiles of the per-base coverage
+    // (q_num: host memory, rank = floor((bases - 1) * q_num / q_den); out_q is quantile-major [n_q * n])
+    pub fn ivx_depth_profile_quantiles(ctx: *mut IvxCtx, profile: *const IvxIndex, mem: i32, qkey: *const u32, qstart: *const u32,
+                                       qend: *const u32, n: u64, pos_lo: u32, key_hi: *const u32, skip_pos0: i32,
+                                       q_num: *const u32, n_q: u32, q_den: u32, out_len: *mut i64, out_min: *mut i32,
+                                       out_max: *mut i32, out_q: *mut i32) -> i32;
+    pub fn ivx_depth_profile_window_quantiles(ctx: *mut IvxCtx, profile: *const IvxIndex, mem: i32, key: u32, first_pos: u32,
+                                              last_pos: u32, width: u32, n: u64, skip_pos0: i32, q_num: *const u32, n_q: u32,
+                                              q_den: u32, out_len: *mut i64, out_min: *mut i32, out_max: *mut i32,
+                                              out_q: *mut i32) -> i32;
     pub fn ivx_take_fixed(ctx: *mut IvxCtx, mem: i32, src: *const c_void, width: u32, n_src: u64, src_valid_bits: *const u8,
                           idx: *const u32, n: u64, out: *mut c_void, out_valid: *mut u8) -> i32;
     pub fn ivx_scatter_fixed(ctx: *mut IvxCtx, mem: i32, src: *const c_void, width: u32, idx: *const u32, n: u64,

@@ -80,6 +80,22 @@ extern "C" {
                                   bases: *mut FFI_ArrowArray, bases_schema: *mut FFI_ArrowSchema,
                                   sum: *mut FFI_ArrowArray, sum_schema: *mut FFI_ArrowSchema,
                                   ge: *mut FFI_ArrowArray, ge_schemas: *mut FFI_ArrowSchema) -> c_int;
+    // depth region order statistics: bases (Int64) and min, max and n_q quantiles (Int32, NULL where bases = 0) per row of a
+    // regions table; quantile j = element floor((bases - 1) * q_num[j] / q_den) of the sorted per-base values; q / q_schemas point
+    // at n_q structs.  The push form leaves the stream open.
+    pub fn brh_depth_region_quantiles(s: *mut BrhSession, reads: BrhBatch, prior: BrhBatch, lengths: BrhBatch, regions: BrhBatch,
+                                      region_cols: BrhColumns, zero_based: c_int, end_exclusive: c_int, filter_flag: u32, min_mapq: u32,
+                                      q_num: *const u32, n_q: u32, q_den: u32,
+                                      bases: *mut FFI_ArrowArray, bases_schema: *mut FFI_ArrowSchema,
+                                      min: *mut FFI_ArrowArray, min_schema: *mut FFI_ArrowSchema,
+                                      max: *mut FFI_ArrowArray, max_schema: *mut FFI_ArrowSchema,
+                                      q: *mut FFI_ArrowArray, q_schemas: *mut FFI_ArrowSchema) -> c_int;
+    pub fn brh_depth_push_region_quantiles(dp: *mut BrhDepthPush, regions: BrhBatch, region_cols: BrhColumns, zero_based: c_int,
+                                           end_exclusive: c_int, q_num: *const u32, n_q: u32, q_den: u32,
+                                           bases: *mut FFI_ArrowArray, bases_schema: *mut FFI_ArrowSchema,
+                                           min: *mut FFI_ArrowArray, min_schema: *mut FFI_ArrowSchema,
+                                           max: *mut FFI_ArrowArray, max_schema: *mut FFI_ArrowSchema,
+                                           q: *mut FFI_ArrowArray, q_schemas: *mut FFI_ArrowSchema) -> c_int;
 }
 
 /// What `IntervalJoinStream` keeps per partition when `Algorithm::Hip` is selected.
