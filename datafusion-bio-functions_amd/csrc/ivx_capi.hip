@@ -2,9 +2,9 @@
 // Host-side plumbing only: argument checks, staging of host buffers, stream and
 // scratch management.  All arithmetic happens in the HIP kernels.
 #include "ivx_internal.hpp"
+#include "ivx_call.hpp"
 #include <cstdlib>
 #include <atomic>
-#include <chrono>
 #include <cstring>
 #include <mutex>
 #include <new>
@@ -134,76 +134,54 @@ ivx_status ivx_index_alloc(ivx_ctx *ctx, ivx_index *ix, size_t bytes, void **out
 
 namespace {
 
-// stage one input column: host -> device scratch, or pass the device pointer through
-template <typename T>
-ivx_status stage_in(ivx_ctx *ctx, int mem, int slot, const T *src, u64 n, const T **dev)
+// the head of every probe call (the frame's begin() and check_mem() around the index checks), then the device
+ivx_status check_probe_args(Frame &f, const ivx_index *ix, int kind, const void *s, const void *e, u64 n, bool defer_ready = false)
 {
-    if (src == nullptr) { *dev = nullptr; return IVX_OK; }
-    if (mem == IVX_MEM_DEVICE) { *dev = src; return IVX_OK; }
-    T *d;
-    IVX_TRY(ctx->get_scratch(slot, (size_t)n * sizeof(T), (void **)&d));
-    if (n) IVX_HIP(ctx, hipMemcpyAsync(d, src, (size_t)n * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
-    *dev = d;
-    return IVX_OK;
-}
-
-// output column: device scratch (host mode) or the caller's device pointer
-template <typename T>
-ivx_status stage_out(ivx_ctx *ctx, int mem, int slot, T *dst, u64 n, T **dev)
-{
-    if (dst == nullptr) { *dev = nullptr; return IVX_OK; }
-    if (mem == IVX_MEM_DEVICE) { *dev = dst; return IVX_OK; }
-    T *d;
-    IVX_TRY(ctx->get_scratch(slot, (size_t)n * sizeof(T), (void **)&d));
-    *dev = d;
-    return IVX_OK;
-}
-
-template <typename T>
-ivx_status copy_out(ivx_ctx *ctx, int mem, T *dst, const T *dev, u64 n)
-{
-    if (mem == IVX_MEM_DEVICE || dst == nullptr || n == 0) return IVX_OK;
-    IVX_HIP(ctx, hipMemcpyAsync(dst, dev, (size_t)n * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
-    return IVX_OK;
-}
-
-ivx_status check_probe_args(ivx_ctx *ctx, const ivx_index *ix, int kind, int mem, const void *s, const void *e, u64 n, bool defer_ready = false)
-{
-    if (!ctx) return IVX_ERR_INVALID;
+    IVX_TRY(f.begin());
+    ivx_ctx *ctx = f.ctx;
     if (!ix) return ctx->fail(IVX_ERR_INVALID, "null index");
     if (ix->kind != kind) return ctx->fail(IVX_ERR_UNSUPPORTED, "index kind does not match this probe");
     if (ix->device != ctx->device) return ctx->fail(IVX_ERR_INVALID, "index lives on another device");
-    if (mem != IVX_MEM_HOST && mem != IVX_MEM_DEVICE) return ctx->fail(IVX_ERR_INVALID, "bad mem");
+    IVX_TRY(f.check_mem());
     if (n && (!s || !e)) return ctx->fail(IVX_ERR_INVALID, "null coordinate column");
     if (n > 0xFFFFFFFFull) return ctx->fail(IVX_ERR_INVALID, "probe batch exceeds UInt32 index capacity");
-    IVX_HIP(ctx, hipSetDevice(ctx->device));
+    IVX_TRY(f.device());
     // an index whose build tail ran beside other work is complete behind its `ready` event: this context's stream is
     // ordered behind it here, unless the caller takes care of that itself (the region path: after its routing pass)
     if (ix->ready != nullptr && !defer_ready) IVX_HIP(ctx, hipStreamWaitEvent(ctx->stream, ix->ready, 0));
     return IVX_OK;
 }
 
-// BuildProbeJoinMetrics bookkeeping of one call (host wall time, as the reference's timers)
-struct CallMetrics {
-    ivx_ctx *c; bool build; std::chrono::steady_clock::time_point t0;
-    CallMetrics(ivx_ctx *ctx, bool is_build, u64 rows) : c(ctx), build(is_build), t0(std::chrono::steady_clock::now())
-    {
-        if (build) { c->metrics.build_input_batches++; c->metrics.build_input_rows += rows; }
-        else { c->metrics.input_batches++; c->metrics.input_rows += rows; }
-    }
-    void out(u64 rows) { if (rows) { c->metrics.output_batches++; c->metrics.output_rows += rows; } }
-    ~CallMetrics()
-    {
-        const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        (build ? c->metrics.build_time : c->metrics.join_time) += ms;
-    }
-};
+// An index object in the making (an index, a depth profile): what its device buffers take is counted in
+// ctx->building_bytes until index_commit
+ivx_status index_new(ivx_ctx *ctx, int kind, u64 n, u32 nkeys, ivx_index **out)
+{
+    ivx_index *ix = new (std::nothrow) ivx_index();
+    if (!ix) return ctx->fail(IVX_ERR_OOM, "host allocation failed");
+    static std::atomic<u64> next_serial{1};
+    ix->serial = next_serial.fetch_add(1);
+    ix->kind = kind; ix->device = ctx->device; ix->n = n; ix->nkeys = nkeys;
+    ctx->building_bytes = 0;
+    *out = ix;
+    return IVX_OK;
+}
 
-struct KernelTimer {
-    ivx_ctx *c;
-    explicit KernelTimer(ivx_ctx *ctx) : c(ctx) { (void)hipEventRecord(c->ev0, c->stream); c->last_ms = -1.0; }
-    ~KernelTimer() { (void)hipEventRecord(c->ev1, c->stream); }
-};
+// ... built (st = what the build said): wait for the device, `what` being the error if that fails; then the object is the
+// caller's, or freed
+ivx_status index_commit(ivx_ctx *ctx, ivx_index *ix, ivx_status st, const char *what, ivx_index **out)
+{
+    if (st == IVX_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) st = ctx->fail(IVX_ERR_HIP, what);
+    ctx->building_bytes = 0;
+    if (st != IVX_OK) { ivx_index_free(ix); return st; }
+    if (ix->kind == IVX_KIND_DEPTH_PROFILE) ix->n = ix->dp.steps;
+    // the finished index stays reserved against the context's limit until ivx_index_free (the reference holds the
+    // build side's MemoryReservation until the join stream ends, interval_join.rs:614-639)
+    ix->owner_bytes = ctx->live_index_bytes;
+    ix->owner_bytes->fetch_add(ix->bytes, std::memory_order_relaxed);
+    ctx->metrics.build_mem_used += ix->bytes;
+    *out = ix;
+    return IVX_OK;
+}
 
 }  // namespace
 
@@ -356,55 +334,34 @@ extern "C" double ivx_ctx_last_kernel_ms(const ivx_ctx *cc)
 
 // ---------------------------------------------------------------- index
 
-ivx_status ivx_count_build(ivx_ctx *ctx, ivx_index *ix, const u32 *key, const i32 *s, const i32 *e, u64 n);
-ivx_status ivx_coverage_build(ivx_ctx *ctx, ivx_index *ix, const u32 *key, const i32 *s, const i32 *e, u64 n);
-ivx_status ivx_nearest_build(ivx_ctx *ctx, ivx_index *ix, const u32 *key, const i32 *s, const i32 *e, u64 n);
-
 extern "C" ivx_status ivx_index_build(ivx_ctx *ctx, int kind, int mem, const uint32_t *key, const int32_t *start,
                                       const int32_t *end, uint64_t n, uint32_t n_keys, ivx_index **out)
 {
-    if (!ctx) return IVX_ERR_INVALID;
-    if (!out) return ctx->fail(IVX_ERR_INVALID, "null out");
-    *out = nullptr;
+    Frame f(ctx, mem);
+    IVX_TRY(f.begin(out, "null out"));
     if (kind < IVX_KIND_OVERLAP || kind > IVX_KIND_NEAREST) return ctx->fail(IVX_ERR_INVALID, "bad index kind");
-    if (mem != IVX_MEM_HOST && mem != IVX_MEM_DEVICE) return ctx->fail(IVX_ERR_INVALID, "bad mem");
+    IVX_TRY(f.check_mem());
     if (n && (!start || !end)) return ctx->fail(IVX_ERR_INVALID, "null coordinate column");
     if (n > 0xFFFFFFFEull) return ctx->fail(IVX_ERR_INVALID, "build side exceeds UInt32 index capacity");   // interval_join.rs:759
     if (n_keys == 0) n_keys = 1;
     if (!key) n_keys = 1;
     if (kind == IVX_KIND_NEAREST && n >= 0x80000000ull) return ctx->fail(IVX_ERR_INVALID, "nearest index: more than 2^31-1 rows");
-    IVX_HIP(ctx, hipSetDevice(ctx->device));
-    ivx_index *ix = new (std::nothrow) ivx_index();
-    static std::atomic<u64> next_serial{1};
-    if (ix) ix->serial = next_serial.fetch_add(1);
-    if (!ix) return ctx->fail(IVX_ERR_OOM, "host allocation failed");
-    ix->kind = kind; ix->device = ctx->device; ix->n = n; ix->nkeys = n_keys;
-    CallMetrics cm(ctx, true, n);
-    ctx->building_bytes = 0;
-    const u32 *dk; const i32 *ds, *de;
-    ivx_status st = stage_in(ctx, mem, WS_IN_KEY, key, n, &dk);
-    if (st == IVX_OK) st = stage_in(ctx, mem, WS_IN_START, start, n, &ds);
-    if (st == IVX_OK) st = stage_in(ctx, mem, WS_IN_END, end, n, &de);
-    if (st == IVX_OK) {
-        KernelTimer t(ctx);
+    IVX_TRY(f.device());
+    ivx_index *ix;
+    IVX_TRY(index_new(ctx, kind, n, n_keys, &ix));
+    f.meter(true, n);
+    const u32 *dk = f.in(key, n);
+    const i32 *ds = f.in(start, n), *de = f.in(end, n);
+    const ivx_status st = f.run([&]() -> ivx_status {
         switch (kind) {
         // (overlapped tail: device-resident columns only -- staged host columns live in scratch the next call reuses)
-        case IVX_KIND_OVERLAP: st = ivx_join_build(ctx, ix, dk, ds, de, n, mem == IVX_MEM_DEVICE); break;
-        case IVX_KIND_COUNT: st = ivx_count_build(ctx, ix, dk, ds, de, n); break;
-        case IVX_KIND_COVERAGE: st = ivx_coverage_build(ctx, ix, dk, ds, de, n); break;
-        default: st = ivx_nearest_build(ctx, ix, dk, ds, de, n); break;
+        case IVX_KIND_OVERLAP: return ivx_join_build(ctx, ix, dk, ds, de, n, mem == IVX_MEM_DEVICE);
+        case IVX_KIND_COUNT: return ivx_count_build(ctx, ix, dk, ds, de, n);
+        case IVX_KIND_COVERAGE: return ivx_coverage_build(ctx, ix, dk, ds, de, n);
+        default: return ivx_nearest_build(ctx, ix, dk, ds, de, n);
         }
-    }
-    if (st == IVX_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) st = ctx->fail(IVX_ERR_HIP, "index build failed on device");
-    ctx->building_bytes = 0;
-    if (st != IVX_OK) { ivx_index_free(ix); return st; }
-    // the finished index stays reserved against the context's limit until ivx_index_free (the reference holds the
-    // build side's MemoryReservation until the join stream ends, interval_join.rs:614-639)
-    ix->owner_bytes = ctx->live_index_bytes;
-    ix->owner_bytes->fetch_add(ix->bytes, std::memory_order_relaxed);
-    ctx->metrics.build_mem_used += ix->bytes;
-    *out = ix;
-    return IVX_OK;
+    });
+    return index_commit(ctx, ix, st, "index build failed on device", out);
 }
 
 extern "C" void ivx_index_free(ivx_index *ix)
@@ -496,17 +453,17 @@ static ivx_status overlap_common(ivx_ctx *ctx, const ivx_index *ix, int mem, int
                                  const u32 *key, const i32 *start, const i32 *end, u64 n,
                                  u32 *per_row, u8 *exists, u32 *bidx, u32 *pidx, u64 cap, u64 *total)
 {
-    IVX_TRY(check_probe_args(ctx, ix, IVX_KIND_OVERLAP, mem, start, end, n, true));
-    CallMetrics cm(ctx, false, n);
-    const u32 *dk = nullptr; const i32 *ds = nullptr, *de = nullptr;
+    Frame f(ctx, mem);
+    IVX_TRY(check_probe_args(f, ix, IVX_KIND_OVERLAP, start, end, n, true));
+    f.meter(false, n);
     // large COUNT/FILL batches: partition the probe rows by index region and probe from LDS;
     // small batches and the per-row modes gather straight from the index
     bool regions = ix->jv_nreg > 0 && (mode == JP_COUNT || mode == JP_FILL) && n >= (1u << 21);   // measured crossover (tools/crossover.py)
     // the per-row modes (rle_right, semi / anti) of big batches: same partition, one value per row, un-permuted
     bool rowval = ix->jv_nreg > 0 && ix->jv_nreg <= IVX_MAXREG_WIDE && (mode == JP_PER_ROW || mode == JP_EXISTS) && n >= (1u << 21);
-    if (const char *f = getenv("IVX_JOIN_PATH")) {
-        if (!strcmp(f, "direct")) regions = rowval = false;
-        else if (!strcmp(f, "regions")) {
+    if (const char *p = getenv("IVX_JOIN_PATH")) {
+        if (!strcmp(p, "direct")) regions = rowval = false;
+        else if (!strcmp(p, "regions")) {
             regions = ix->jv_nreg > 0 && (mode == JP_COUNT || mode == JP_FILL);
             rowval = ix->jv_nreg > 0 && ix->jv_nreg <= IVX_MAXREG_WIDE && (mode == JP_PER_ROW || mode == JP_EXISTS);
         }
@@ -518,23 +475,17 @@ static ivx_status overlap_common(ivx_ctx *ctx, const ivx_index *ix, int mem, int
                          pl.ix == (const void *)ix && pl.ix_serial == ix->serial && pl.stream == ctx->stream;
     // (the region path orders itself behind the index's build tail after its routing pass; everything else here)
     if (ix->ready != nullptr && !(regions && !planned)) IVX_HIP(ctx, hipStreamWaitEvent(ctx->stream, ix->ready, 0));
-    if (!planned) {
-        IVX_TRY(stage_in(ctx, mem, WS_IN_KEY, key, n, &dk));
-        IVX_TRY(stage_in(ctx, mem, WS_IN_START, start, n, &ds));
-        IVX_TRY(stage_in(ctx, mem, WS_IN_END, end, n, &de));
-    }
-    u32 *d_row = nullptr, *d_b = nullptr, *d_p = nullptr; u8 *d_ex = nullptr;
-    IVX_TRY(stage_out(ctx, mem, WS_OUT_A, per_row, n, &d_row));
-    IVX_TRY(stage_out(ctx, mem, WS_OUT_B, exists, n, &d_ex));
-    IVX_TRY(stage_out(ctx, mem, WS_OUT_C, bidx, cap, &d_b));
-    IVX_TRY(stage_out(ctx, mem, WS_OUT_D, pidx, cap, &d_p));
+    const u32 *dk = nullptr; const i32 *ds = nullptr, *de = nullptr;
+    if (!planned) { dk = f.in(key, n); ds = f.in(start, n); de = f.in(end, n); }
+    u32 *d_row = f.out(per_row, n); u8 *d_ex = f.out(exists, n);
+    u32 *d_b = f.out(bidx, cap), *d_p = f.out(pidx, cap);
+    IVX_TRY(f.st);
     // pair cursor | probe fault flags: zeroed here, or -- a region probe that routes its rows -- by the routing pass's clearing kernel
     const bool defer_clear = regions && !planned;
     if (!defer_clear) IVX_HIP(ctx, hipMemsetAsync(ctx->dword(SC_PAIRS), 0, 2 * sizeof(u64), ctx->stream));
     ivx_probe_note note;
     note.ix_serial = ix->serial;
-    {
-        KernelTimer t(ctx);
+    IVX_TRY(f.run([&]() -> ivx_status {
         if (regions) {
             if (!planned) pl.valid = false;                 // whatever an earlier count call left is gone now
             const ivx_status st = ivx_join_probe_regions(ctx, ix->jv, ix->jv_nreg, mode, dk, ds, de, n, d_b, d_p, cap, ctx->dword(SC_PAIRS), planned, ix->jv_filter, ix->jv_pk24,
@@ -543,13 +494,14 @@ static ivx_status overlap_common(ivx_ctx *ctx, const ivx_index *ix, int mem, int
             if (note.fast >= 0) ix->jv_lean.store(note.fast, std::memory_order_relaxed);
             if (st != IVX_OK) { pl.valid = false; return st; }
             if (mode == JP_COUNT && pl.valid) { memcpy(pl.in, in, sizeof(in)); pl.mem = mem; pl.n = n; pl.ix = ix; pl.ix_serial = ix->serial; pl.stream = ctx->stream; }
+            return IVX_OK;
         }
-        else if (rowval) IVX_TRY(ivx_rowval_probe_regions(ctx, ix->jv, ix->jv_nreg, mode == JP_PER_ROW ? IVX_RV_PER_ROW : IVX_RV_EXISTS, dk, ds, de, n, 0,
-                                                          mode == JP_PER_ROW ? (void *)d_row : (void *)d_ex, ctx->dword(SC_PAIRS), ix->jv_filter, ix->jv_pk24, ix->jv_lean.load(std::memory_order_relaxed) == 1));
-        else if (n && (mode == JP_PER_ROW || mode == JP_EXISTS) && ix->nroute_nreg > 0 && rowval_routed_ok(n))
-            IVX_TRY(ivx_join_rowval_routed(ctx, ix, mode, dk, ds, de, n, d_row, d_ex, ctx->dword(SC_PAIRS)));   // too many regions for the LDS slices: route, gather, put back
-        else IVX_TRY(ivx_join_probe(ctx, ix->jv, mode, dk, ds, de, n, d_row, d_ex, d_b, d_p, cap, ctx->dword(SC_PAIRS)));
-    }
+        if (rowval) return ivx_rowval_probe_regions(ctx, ix->jv, ix->jv_nreg, mode == JP_PER_ROW ? IVX_RV_PER_ROW : IVX_RV_EXISTS, dk, ds, de, n, 0,
+                                                    mode == JP_PER_ROW ? (void *)d_row : (void *)d_ex, ctx->dword(SC_PAIRS), ix->jv_filter, ix->jv_pk24, ix->jv_lean.load(std::memory_order_relaxed) == 1);
+        if (n && (mode == JP_PER_ROW || mode == JP_EXISTS) && ix->nroute_nreg > 0 && rowval_routed_ok(n))
+            return ivx_join_rowval_routed(ctx, ix, mode, dk, ds, de, n, d_row, d_ex, ctx->dword(SC_PAIRS));   // too many regions for the LDS slices: route, gather, put back
+        return ivx_join_probe(ctx, ix->jv, mode, dk, ds, de, n, d_row, d_ex, d_b, d_p, cap, ctx->dword(SC_PAIRS));
+    }));
     u64 tot = 0;
     if (mode != JP_EXISTS) {
         // (a lean fill's last kernel has left both words in the mapped mirror itself: k_fill_rest)
@@ -563,13 +515,11 @@ static ivx_status overlap_common(ivx_ctx *ctx, const ivx_index *ix, int mem, int
     if (mode == JP_COUNT && regions && pl.valid) pl.total = tot;
     if (total) *total = tot;
     if (mode == JP_FILL && tot > cap) return ctx->fail(IVX_ERR_CAPACITY, "pair buffers too small");   // (a plan survives this: the retry with bigger buffers reuses it)
-    cm.out(mode == JP_FILL ? tot : (mode == JP_COUNT ? 0 : n));
+    f.rows_out(mode == JP_FILL ? tot : (mode == JP_COUNT ? 0 : n));
     if (planned) pl.valid = false;                          // a plan serves ONE successful fill: a caller that refills the same buffers with its next batch must not get this batch's rows
-    IVX_TRY(copy_out(ctx, mem, per_row, d_row, n));
-    IVX_TRY(copy_out(ctx, mem, exists, d_ex, n));
-    if (mode == JP_FILL) { IVX_TRY(copy_out(ctx, mem, bidx, d_b, tot)); IVX_TRY(copy_out(ctx, mem, pidx, d_p, tot)); }
-    if (mem == IVX_MEM_HOST) IVX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return IVX_OK;
+    f.back(per_row); f.back(exists);                        // (one value per probe row, in whichever mode asked for them)
+    if (mode == JP_FILL) { f.back(bidx, tot); f.back(pidx, tot); }
+    return f.finish();
 }
 
 extern "C" ivx_status ivx_probe_overlap_count(ivx_ctx *ctx, const ivx_index *ix, int mem, const uint32_t *key,
@@ -579,16 +529,11 @@ extern "C" ivx_status ivx_probe_overlap_count(ivx_ctx *ctx, const ivx_index *ix,
     return overlap_common(ctx, ix, mem, per_row ? JP_PER_ROW : JP_COUNT, key, start, end, n, per_row, nullptr, nullptr, nullptr, 0, total);
 }
 
-// ---- host-resident fill of a big batch: chunks, so that the link runs in both directions at once
+// ---- host-resident columns of a big batch: chunks, so that the link runs in both directions at once
 // The columns of 100 M probe rows cross the link in ~21 ms, the pairs come back in ~5 ms, the kernels take 1.3 ms: done one
-// after the other that is what the call costs.  Cut into chunks, the pairs of chunk c go back to the host (a helper thread
+// after the other that is what the call costs.  Cut into chunks, the results of chunk c go back to the host (a helper thread
 // on a stream of its own: a copy from or to pageable memory occupies the thread that issues it) while the columns of chunk
-// c + 1 come in.  Every chunk is a device-resident fill of its own that appends to the same pair buffers; probe row ids
-// are shifted by the chunk's first row afterwards.  Order of the pairs is free, as everywhere.
-__global__ void k_add_base(u32 *__restrict__ p, u64 n, u32 base)
-{
-    for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (u64)gridDim.x * blockDim.x) p[i] += base;
-}
+// c + 1 come in.  Every chunk is a device-resident call of its own.
 
 // device -> host copies on a thread and stream of their own, each after an event of the compute stream
 struct HostCopier {
@@ -645,16 +590,35 @@ struct HostCopier {
     ~HostCopier() { (void)finish(); }
 };
 
-static ivx_status overlap_fill_host_chunked(ivx_ctx *ctx, const ivx_index *ix, const u32 *key, const i32 *start, const i32 *end, u64 n,
-                                            u32 *bidx, u32 *pidx, u64 cap, u64 *written, u32 nchunk)
+// IVX_HOST_CHUNKS = number of chunks, 1 switches chunking off; default 4 from 16 M rows; a chunk is a multiple of 65 536 rows
+static u32 host_chunks(u64 n)
 {
-    IVX_TRY(check_probe_args(ctx, ix, IVX_KIND_OVERLAP, IVX_MEM_HOST, start, end, n));
+    const char *ce = getenv("IVX_HOST_CHUNKS");
+    const u32 nchunk = ce ? (u32)atoi(ce) : (n >= (16ull << 20) ? 4u : 1u);
+    return nchunk > 1 && n >= (u64)nchunk * 65536 ? nchunk : 1u;
+}
+
+// one chunk, as its device call sees it: rows [c0, c0 + n) of the batch, their columns on the device, and what the call
+// wants copied back to the host once everything it has enqueued is done
+struct HostChunk {
+    u32 c; int set; u64 c0, n;
+    const u32 *key; const i32 *start, *end;
+    struct Copy { void *dst; const void *src; size_t bytes; } back[2];
+    int n_back = 0;
+    void push(void *dst, const void *src, size_t bytes) { back[n_back++] = Copy{dst, src, bytes}; }
+};
+
+// The pipeline: two sets of staged columns (WS_IN* / WS_IN2*: chunk c + 1 arrives while the kernels of chunk c may still
+// read theirs), per_chunk(HostChunk &) for the device call of every chunk, the copies it pushes handed to the helper thread.
+// out_sets: the per_chunk calls write their results into two alternating buffers of their own (chunk c into set c & 1), so
+// the device call of chunk c waits for the copies of chunk c - 2; false: nothing a chunk writes is written again.
+// copy_what names the copies in an error.  Errors: the first of per_chunk's, the stream's, the copies'.
+template <typename PerChunk>
+static ivx_status host_chunked(ivx_ctx *ctx, const u32 *key, const i32 *start, const i32 *end, u64 n, u32 nchunk, bool out_sets,
+                               const char *copy_what, PerChunk &&per_chunk)
+{
     hipStream_t st = ctx->stream;
     const u64 rows = ((n + nchunk - 1) / nchunk + 65535) & ~65535ull;           // rows per chunk
-    u32 *d_b, *d_p;
-    IVX_TRY(ctx->get_scratch(WS_OUT_C, (size_t)(cap ? cap : 1) * sizeof(u32), (void **)&d_b));
-    IVX_TRY(ctx->get_scratch(WS_OUT_D, (size_t)(cap ? cap : 1) * sizeof(u32), (void **)&d_p));
-    // two sets of staged columns: chunk c + 1 arrives while the kernels of chunk c may still read theirs
     u32 *dk[2] = {nullptr, nullptr}; i32 *ds[2], *de[2];
     for (int b = 0; b < 2; b++) {
         if (key) IVX_TRY(ctx->get_scratch(b ? WS_IN2_KEY : WS_IN_KEY, rows * sizeof(u32), (void **)&dk[b]));
@@ -663,49 +627,83 @@ static ivx_status overlap_fill_host_chunked(ivx_ctx *ctx, const ivx_index *ix, c
     }
     HostCopier hc;
     IVX_HIP(ctx, hc.start(ctx->device));
-    const ivx_metrics m0 = ctx->metrics;                                        // (the chunks are one batch to the caller)
-    u64 cum = 0, need = 0;
+    u64 pushed = 0, pushed_by[2] = {0, 0};                                      // copies pushed so far; ... up to the last chunk of either set
     ivx_status rc = IVX_OK;
-    bool over = false;                                                          // the pair buffers ran out: only count from here on
     for (u32 c = 0; c < nchunk && rc == IVX_OK; c++) {
-        const u64 c0 = (u64)c * rows, c1 = c0 + rows < n ? c0 + rows : n;
-        if (c0 >= c1) break;
-        const int b = (int)(c & 1u);
-        const u64 nc = c1 - c0;
+        HostChunk ch;
+        ch.c = c; ch.set = (int)(c & 1u); ch.c0 = (u64)c * rows;
+        const u64 c1 = ch.c0 + rows < n ? ch.c0 + rows : n;
+        if (ch.c0 >= c1) break;
+        ch.n = c1 - ch.c0;
+        const int b = ch.set;
+        // (input set b was last read by the kernels of chunk c - 2, earlier on this stream; an output set b by the COPY of
+        //  chunk c - 2, on the helper's stream: that one is awaited before this chunk's kernels are enqueued)
         hipError_t e = hipSuccess;
-        if (key) e = hipMemcpyAsync(dk[b], key + c0, nc * sizeof(u32), hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(ds[b], start + c0, nc * sizeof(i32), hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(de[b], end + c0, nc * sizeof(i32), hipMemcpyHostToDevice, st);
+        if (key) e = hipMemcpyAsync(dk[b], key + ch.c0, ch.n * sizeof(u32), hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(ds[b], start + ch.c0, ch.n * sizeof(i32), hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(de[b], end + ch.c0, ch.n * sizeof(i32), hipMemcpyHostToDevice, st);
         if (e != hipSuccess) { rc = ctx->fail_hip("hipMemcpyAsync(chunk)", e); break; }
-        u64 tot = 0;
-        if (!over) {
-            ctx->fill_hint = (u64)((double)cap * (double)nc / (double)n) + 1;    // (the chunk's share of the pairs the caller expects: cap - cum would read as a dense join)
-            rc = overlap_common(ctx, ix, IVX_MEM_DEVICE, JP_FILL, dk[b], ds[b], de[b], nc, nullptr, nullptr, d_b + cum, d_p + cum, cap - cum, &tot);
-            ctx->fill_hint = 0;
-            if (rc == IVX_ERR_CAPACITY) { over = true; rc = IVX_OK; need = cum + tot; continue; }
-            if (rc != IVX_OK) break;
-            if (tot && c0) hipLaunchKernelGGL(k_add_base, dim3(1024), dim3(256), 0, st, d_p + cum, tot, (u32)c0);
-            hipEvent_t ev;
-            e = hc.mark(st, &ev);
-            if (e != hipSuccess) { rc = ctx->fail_hip("hipEventRecord(chunk)", e); break; }
-            hc.push(bidx + cum, d_b + cum, tot * sizeof(u32), ev);
-            hc.push(pidx + cum, d_p + cum, tot * sizeof(u32), ev);
-            cum += tot;
-        } else {
-            rc = overlap_common(ctx, ix, IVX_MEM_DEVICE, JP_COUNT, dk[b], ds[b], de[b], nc, nullptr, nullptr, nullptr, nullptr, 0, &tot);
-            need += tot;
-        }
+        if (out_sets && c >= 2) hc.wait_until(pushed_by[b]);
+        ch.key = dk[b]; ch.start = ds[b]; ch.end = de[b];
+        rc = per_chunk(ch);
+        if (rc != IVX_OK || ch.n_back == 0) continue;
+        hipEvent_t ev;
+        e = hc.mark(st, &ev);
+        if (e != hipSuccess) { rc = ctx->fail_hip("hipEventRecord(chunk)", e); break; }
+        for (int i = 0; i < ch.n_back; i++) hc.push(ch.back[i].dst, ch.back[i].src, ch.back[i].bytes, ev);
+        pushed += (u64)ch.n_back;
+        pushed_by[b] = pushed;
     }
     // (the staged columns of the last chunks must not be reused before their kernels are done: the stream is idle here)
     const hipError_t es = hipStreamSynchronize(st);
     const hipError_t herr = hc.finish();
+    if (rc != IVX_OK) return rc;
+    if (es != hipSuccess) return ctx->fail_hip("hipStreamSynchronize", es);
+    if (herr != hipSuccess) return ctx->fail_hip(copy_what, herr);
+    return IVX_OK;
+}
+
+// the overlap fill, chunked: every chunk appends to the same pair buffers; probe row ids are shifted by the chunk's first
+// row afterwards.  Order of the pairs is free, as everywhere.
+__global__ void k_add_base(u32 *__restrict__ p, u64 n, u32 base)
+{
+    for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (u64)gridDim.x * blockDim.x) p[i] += base;
+}
+
+static ivx_status overlap_fill_host_chunked(ivx_ctx *ctx, const ivx_index *ix, const u32 *key, const i32 *start, const i32 *end, u64 n,
+                                            u32 *bidx, u32 *pidx, u64 cap, u64 *written, u32 nchunk)
+{
+    Frame f(ctx, IVX_MEM_HOST);
+    IVX_TRY(check_probe_args(f, ix, IVX_KIND_OVERLAP, start, end, n));
+    u32 *d_b, *d_p;
+    IVX_TRY(ctx->get_scratch(WS_OUT_C, (size_t)(cap ? cap : 1) * sizeof(u32), (void **)&d_b));
+    IVX_TRY(ctx->get_scratch(WS_OUT_D, (size_t)(cap ? cap : 1) * sizeof(u32), (void **)&d_p));
+    const ivx_metrics m0 = ctx->metrics;                                        // (the chunks are one batch to the caller)
+    u64 cum = 0, need = 0;
+    bool over = false;                                                          // the pair buffers ran out: only count from here on
+    const ivx_status rc = host_chunked(ctx, key, start, end, n, nchunk, false, "hipMemcpyAsync(pairs)", [&](HostChunk &ch) -> ivx_status {
+        u64 tot = 0;
+        if (over) {
+            const ivx_status st = overlap_common(ctx, ix, IVX_MEM_DEVICE, JP_COUNT, ch.key, ch.start, ch.end, ch.n, nullptr, nullptr, nullptr, nullptr, 0, &tot);
+            need += tot;
+            return st;
+        }
+        ctx->fill_hint = (u64)((double)cap * (double)ch.n / (double)n) + 1;     // (the chunk's share of the pairs the caller expects: cap - cum would read as a dense join)
+        const ivx_status st = overlap_common(ctx, ix, IVX_MEM_DEVICE, JP_FILL, ch.key, ch.start, ch.end, ch.n, nullptr, nullptr, d_b + cum, d_p + cum, cap - cum, &tot);
+        ctx->fill_hint = 0;
+        if (st == IVX_ERR_CAPACITY) { over = true; need = cum + tot; return IVX_OK; }
+        if (st != IVX_OK) return st;
+        if (tot && ch.c0) hipLaunchKernelGGL(k_add_base, dim3(1024), dim3(256), 0, ctx->stream, d_p + cum, tot, (u32)ch.c0);
+        ch.push(bidx + cum, d_b + cum, tot * sizeof(u32));
+        ch.push(pidx + cum, d_p + cum, tot * sizeof(u32));
+        cum += tot;
+        return IVX_OK;
+    });
     ctx->join_plan.valid = false;                                               // (the count calls above may have left one: it refers to a chunk)
     ctx->metrics.input_batches = m0.input_batches + 1;
     ctx->metrics.output_batches = m0.output_batches + ((rc == IVX_OK && !over && cum) ? 1 : 0);
     if (over) ctx->metrics.output_rows = m0.output_rows;
     if (rc != IVX_OK) return rc;
-    if (es != hipSuccess) return ctx->fail_hip("hipStreamSynchronize", es);
-    if (herr != hipSuccess) return ctx->fail_hip("hipMemcpyAsync(pairs)", herr);
     if (written) *written = over ? need : cum;
     if (over) return ctx->fail(IVX_ERR_CAPACITY, "pair buffers too small");
     return IVX_OK;
@@ -717,14 +715,12 @@ extern "C" ivx_status ivx_probe_overlap_fill(ivx_ctx *ctx, const ivx_index *ix, 
 {
     if (ctx && cap && (!build_idx || !probe_idx)) return ctx->fail(IVX_ERR_INVALID, "null pair buffers");
     // host-resident columns of a big batch, and no count call left its routed rows (and device copies) behind: chunked
-    // (IVX_HOST_CHUNKS = number of chunks, 1 switches it off; default 4 from 16 M rows)
     if (ctx && ix && mem == IVX_MEM_HOST && cap && start && end) {
-        const char *ce = getenv("IVX_HOST_CHUNKS");
-        const u32 nchunk = ce ? (u32)atoi(ce) : (n >= (16ull << 20) ? 4u : 1u);
+        const u32 nchunk = host_chunks(n);
         const void *in[3] = {key, start, end};
         const ivx_join_plan &pl = ctx->join_plan;
         const bool planned = pl.valid && pl.mem == mem && memcmp(pl.in, in, sizeof(in)) == 0 && pl.n == n && pl.ix == (const void *)ix && pl.ix_serial == ix->serial;
-        if (nchunk > 1 && n >= (u64)nchunk * 65536 && !planned && ix->kind == IVX_KIND_OVERLAP)
+        if (nchunk > 1 && !planned && ix->kind == IVX_KIND_OVERLAP)
             return overlap_fill_host_chunked(ctx, ix, key, start, end, n, build_idx, probe_idx, cap, written, nchunk);
     }
     return overlap_common(ctx, ix, mem, JP_FILL, key, start, end, n, nullptr, nullptr, build_idx, probe_idx, cap, written);
@@ -739,207 +735,102 @@ extern "C" ivx_status ivx_probe_exists(ivx_ctx *ctx, const ivx_index *ix, int me
 
 // ---------------------------------------------------------------- a3'': build-side match marks
 
-namespace {
-
-// the bitmap a mark call's kernels OR into: the caller's own words (device mode), or a zeroed scratch bitmap that
-// marks_or_back copies to the host and ORs into the caller's words (the caller's set bits survive)
-ivx_status marks_stage(ivx_ctx *ctx, int mem, u32 *caller, u64 nw, u32 **dev)
-{
-    if (mem == IVX_MEM_DEVICE) { *dev = caller; return IVX_OK; }
-    IVX_TRY(ctx->get_scratch(WS_OUT_A, (size_t)nw * sizeof(u32), (void **)dev));
-    if (nw) IVX_HIP(ctx, hipMemsetAsync(*dev, 0, (size_t)nw * sizeof(u32), ctx->stream));
-    return IVX_OK;
-}
-
-ivx_status marks_or_back(ivx_ctx *ctx, int mem, u32 *caller, const u32 *dev, u64 nw)
-{
-    if (mem == IVX_MEM_DEVICE || nw == 0) return IVX_OK;
-    std::vector<u32> got;
-    try { got.resize((size_t)nw); } catch (const std::bad_alloc &) { return ctx->fail(IVX_ERR_OOM, "host allocation failed"); }
-    IVX_HIP(ctx, hipMemcpyAsync(got.data(), dev, (size_t)nw * sizeof(u32), hipMemcpyDeviceToHost, ctx->stream));
-    IVX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    for (u64 w = 0; w < nw; w++) caller[w] |= got[w];
-    return IVX_OK;
-}
-
 // Beside overlap_common: the same two ways through the index, the match recorded by BUILD row.  Big batches over a lean
 // index (the form ivx_rowval_probe_regions runs k_rv_fast on) take the region kernel; everything else the direct one.
-ivx_status mark_common(ivx_ctx *ctx, const ivx_index *ix, int mem, const u32 *key, const i32 *start, const i32 *end, u64 n, u32 *marks)
+extern "C" ivx_status ivx_probe_mark_build(ivx_ctx *ctx, const ivx_index *ix, int mem, const uint32_t *key,
+                                           const int32_t *start, const int32_t *end, uint64_t n, uint32_t *marks)
 {
-    IVX_TRY(check_probe_args(ctx, ix, IVX_KIND_OVERLAP, mem, start, end, n));       // (orders the stream behind a build tail, too)
+    Frame f(ctx, mem);
+    IVX_TRY(check_probe_args(f, ix, IVX_KIND_OVERLAP, start, end, n));             // (orders the stream behind a build tail, too)
     if (n && ix->n && !marks) return ctx->fail(IVX_ERR_INVALID, "null mark bitmap");
-    CallMetrics cm(ctx, false, n);
-    ctx->join_plan.valid = false;                           // as any other call between a count call and its fill
+    f.meter(false, n);
+    f.drop_join_plan();                                     // as any other call between a count call and its fill
     const u64 nw = (ix->n + 31) / 32;
     if (n == 0 || nw == 0) return IVX_OK;
     // thresholds and override of overlap_common's per-row branch
     bool regions = ix->jv_nreg > 0 && ix->jv_nreg <= IVX_MAXREG_WIDE && n >= (1u << 21);
-    if (const char *f = getenv("IVX_JOIN_PATH")) {
-        if (!strcmp(f, "direct")) regions = false;
-        else if (!strcmp(f, "regions")) regions = ix->jv_nreg > 0 && ix->jv_nreg <= IVX_MAXREG_WIDE;
+    if (const char *p = getenv("IVX_JOIN_PATH")) {
+        if (!strcmp(p, "direct")) regions = false;
+        else if (!strcmp(p, "regions")) regions = ix->jv_nreg > 0 && ix->jv_nreg <= IVX_MAXREG_WIDE;
     }
-    const u32 *dk = nullptr; const i32 *ds = nullptr, *de = nullptr; u32 *dm = nullptr;
-    IVX_TRY(stage_in(ctx, mem, WS_IN_KEY, key, n, &dk));
-    IVX_TRY(stage_in(ctx, mem, WS_IN_START, start, n, &ds));
-    IVX_TRY(stage_in(ctx, mem, WS_IN_END, end, n, &de));
-    IVX_TRY(marks_stage(ctx, mem, marks, nw, &dm));
-    {
-        KernelTimer t(ctx);
+    const u32 *dk = f.in(key, n);
+    const i32 *ds = f.in(start, n), *de = f.in(end, n);
+    u32 *dm = f.out_or(marks, nw);
+    IVX_TRY(f.run([&]() -> ivx_status {
         bool took = false;
         if (regions) IVX_TRY(ivx_mark_probe_regions(ctx, ix->jv, ix->jv_nreg, dk, ds, de, n, dm, ix->jv_filter, ix->jv_pk24, ix->jv_lean.load(std::memory_order_relaxed) == 1, &took));
-        if (!took) IVX_TRY(ivx_mark_probe(ctx, ix->jv, dk, ds, de, n, dm));
-    }
-    return marks_or_back(ctx, mem, marks, dm, nw);
-}
-
-}  // namespace
-
-extern "C" ivx_status ivx_probe_mark_build(ivx_ctx *ctx, const ivx_index *ix, int mem, const uint32_t *key,
-                                           const int32_t *start, const int32_t *end, uint64_t n, uint32_t *marks)
-{
-    return mark_common(ctx, ix, mem, key, start, end, n, marks);
+        return took ? IVX_OK : ivx_mark_probe(ctx, ix->jv, dk, ds, de, n, dm);
+    }));
+    f.or_back(marks);                                       // (synchronises: nothing is left for finish())
+    return f.st;
 }
 
 extern "C" ivx_status ivx_bits_mark(ivx_ctx *ctx, int mem, const uint32_t *idx, uint64_t n, uint32_t *bits, uint64_t n_bits)
 {
-    if (!ctx) return IVX_ERR_INVALID;
-    if (mem != IVX_MEM_HOST && mem != IVX_MEM_DEVICE) return ctx->fail(IVX_ERR_INVALID, "bad mem");
+    Frame f(ctx, mem);
+    IVX_TRY(f.enter());
     if (n && !idx) return ctx->fail(IVX_ERR_INVALID, "bits_mark: null idx");
     if (n_bits && !bits) return ctx->fail(IVX_ERR_INVALID, "bits_mark: null bitmap");
     if (n_bits > 0xFFFFFFFFull) return ctx->fail(IVX_ERR_INVALID, "bits_mark: bitmap exceeds UInt32 index capacity");
     if (n == 0) return IVX_OK;
-    IVX_HIP(ctx, hipSetDevice(ctx->device));
-    const u64 nw = (n_bits + 31) / 32;
-    const u32 *didx; u32 *dbits;
-    IVX_TRY(stage_in(ctx, mem, WS_IN_KEY, idx, n, &didx));
-    IVX_TRY(marks_stage(ctx, mem, bits, nw, &dbits));
-    {
-        KernelTimer t(ctx);
-        IVX_TRY(ivx_bits_mark_device(ctx, didx, n, dbits, n_bits));
-    }
-    return marks_or_back(ctx, mem, bits, dbits, nw);
+    const u32 *didx = f.in(idx, n);
+    u32 *dbits = f.out_or(bits, (n_bits + 31) / 32);
+    IVX_TRY(f.run([&] { return ivx_bits_mark_device(ctx, didx, n, dbits, n_bits); }));
+    f.or_back(bits);
+    return f.st;
 }
 
 extern "C" ivx_status ivx_bits_select(ivx_ctx *ctx, int mem, const uint32_t *bits, uint64_t n_bits, int want_set,
                                       uint32_t *out, uint64_t cap, uint64_t *n_out)
 {
-    if (!ctx) return IVX_ERR_INVALID;
-    if (!n_out) return ctx->fail(IVX_ERR_INVALID, "null n_out");
-    *n_out = 0;
-    if (mem != IVX_MEM_HOST && mem != IVX_MEM_DEVICE) return ctx->fail(IVX_ERR_INVALID, "bad mem");
+    Frame f(ctx, mem);
+    IVX_TRY(f.enter(n_out, "null n_out"));
     if (n_bits && !bits) return ctx->fail(IVX_ERR_INVALID, "bits_select: null bitmap");
     if (cap && !out) return ctx->fail(IVX_ERR_INVALID, "bits_select: null out");
     if (n_bits > 0xFFFFFFFFull) return ctx->fail(IVX_ERR_INVALID, "bits_select: bitmap exceeds UInt32 index capacity");
-    IVX_HIP(ctx, hipSetDevice(ctx->device));
-    const u32 *dbits; u32 *dout;
-    IVX_TRY(stage_in(ctx, mem, WS_IN_KEY, bits, (n_bits + 31) / 32, &dbits));
-    IVX_TRY(stage_out(ctx, mem, WS_OUT_A, out, cap, &dout));
+    const u32 *dbits = f.in(bits, (n_bits + 31) / 32);
+    u32 *dout = f.out(out, cap);
     u64 m = 0;
-    {
-        KernelTimer t(ctx);
-        const ivx_status st = ivx_bits_select_device(ctx, dbits, n_bits, want_set, dout, cap, &m);
-        *n_out = m;
-        if (st != IVX_OK) return st;
-    }
-    if (cap) IVX_TRY(copy_out(ctx, mem, out, dout, m));
-    if (mem == IVX_MEM_HOST) IVX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return IVX_OK;
+    const ivx_status st = f.run([&] { return ivx_bits_select_device(ctx, dbits, n_bits, want_set, dout, cap, &m); });
+    *n_out = m;
+    if (st != IVX_OK) return st;
+    f.back(out, m);
+    return f.finish();
 }
 
 // ---------------------------------------------------------------- a4 / a5 / a6 probes
 
-ivx_status ivx_count_probe(ivx_ctx *ctx, const ivx_index *ix, const u32 *key, const i32 *s, const i32 *e, u64 n, int strict, i64 *out);
-ivx_status ivx_coverage_probe(ivx_ctx *ctx, const ivx_index *ix, const u32 *key, const i32 *s, const i32 *e, u64 n, int strict, i64 *out);
-ivx_status ivx_nearest_probe(ivx_ctx *ctx, const ivx_index *ix, const u32 *key, const i32 *s, const i32 *e, u64 n,
-                             int strict, u32 k, int include_overlaps, u32 *ob, u32 *op, i64 *od, u64 cap, u64 *rows);
-ivx_status ivx_merge_device(ivx_ctx *ctx, const u32 *key, const i64 *s, const i64 *e, u64 n, u32 nkeys,
-                            i64 min_dist, int strict, u32 *ok, i64 *os, i64 *oe, i64 *on, u64 *m);
-ivx_status ivx_subtract_device(ivx_ctx *ctx, const u32 *lkey, const i64 *ls, const i64 *le, u64 nl,
-                               const u32 *rkey, const i64 *rs, const i64 *re, u64 nr, u32 nkeys, int strict,
-                               u32 *ok, i64 *os, i64 *oe, u32 *orow, u64 cap, u64 *n_out);
-ivx_status ivx_subtract_fill_planned(ivx_ctx *ctx, u32 *ok, i64 *os, i64 *oe, u32 *orow, u64 cap, u64 *n_out);
-ivx_status ivx_cluster_device(ivx_ctx *ctx, const u32 *key, const i64 *s, const i64 *e, u64 n, u32 nkeys,
-                              i64 min_dist, int strict, const i64 *key_base,
-                              u32 *ok, i64 *os, i64 *oe, u32 *orow, i64 *oc, i64 *ocs, i64 *oce, u64 *key_clusters, u64 *m);
-ivx_status ivx_complement_device(ivx_ctx *ctx, const u32 *key, const i64 *s, const i64 *e, u64 n,
-                                 const u32 *vkey, const i64 *vs, const i64 *ve, u64 nv, u32 nkeys, int strict,
-                                 u32 *ok, i64 *os, i64 *oe, u64 cap, u64 *n_out);
-ivx_status ivx_take_fixed_device(ivx_ctx *ctx, const void *src, u32 width, u64 n_src, const u8 *src_valid,
-                                 const u32 *idx, u64 n, void *out, u8 *out_valid);
-ivx_status ivx_take_view_device(ivx_ctx *ctx, const void *views, const u8 *const *bufs, u64 n_src, const u8 *src_valid,
-                                const u32 *idx, u64 n, void *out_views, u8 *out_data, u64 data_cap, u64 *data_bytes, u8 *out_valid);
-ivx_status ivx_take_bits_device(ivx_ctx *ctx, const u8 *src_bits, u64 n_src, const u8 *src_valid, const u32 *idx, u64 n, u8 *out_bits, u8 *out_valid);
-ivx_status ivx_take_utf8_device(ivx_ctx *ctx, int large, const void *offsets, const u8 *data, u64 n_src, const u8 *src_valid,
-                                const u32 *idx, u64 n, void *out_offsets, u8 *out_data, u64 data_cap, u64 *data_bytes, u8 *out_valid);
-
 static ivx_status per_row_i64(ivx_ctx *ctx, const ivx_index *ix, int kind, int mem, const u32 *key, const i32 *start,
                               const i32 *end, u64 n, int strict, i64 *out)
 {
-    IVX_TRY(check_probe_args(ctx, ix, kind, mem, start, end, n));
+    Frame f(ctx, mem);
+    IVX_TRY(check_probe_args(f, ix, kind, start, end, n));
     if (n && !out) return ctx->fail(IVX_ERR_INVALID, "null output column");
-    CallMetrics cm(ctx, false, n);
-    cm.out(n);
-    // host-resident columns of a big batch: in chunks, the values of chunk c go back (helper thread, own stream) while the
-    // columns of chunk c + 1 come in -- see overlap_fill_host_chunked
-    const char *ce = getenv("IVX_HOST_CHUNKS");
-    const u32 nchunk = ce ? (u32)atoi(ce) : (n >= (16ull << 20) ? 4u : 1u);
-    if (mem == IVX_MEM_HOST && nchunk > 1 && n >= (u64)nchunk * 65536) {
-        hipStream_t st = ctx->stream;
+    f.meter(false, n);
+    f.rows_out(n);
+    const auto probe = [&](const u32 *dk, const i32 *ds, const i32 *de, u64 rows, i64 *dout) {
+        return kind == IVX_KIND_COUNT ? ivx_count_probe(ctx, ix, dk, ds, de, rows, strict, dout) : ivx_coverage_probe(ctx, ix, dk, ds, de, rows, strict, dout);
+    };
+    // host-resident columns of a big batch: in chunks, the values of chunk c go back while the columns of chunk c + 1 come in
+    const u32 nchunk = mem == IVX_MEM_HOST ? host_chunks(n) : 1u;
+    if (nchunk > 1) {
         const u64 rows = ((n + nchunk - 1) / nchunk + 65535) & ~65535ull;
-        u32 *dkk[2] = {nullptr, nullptr}; i32 *dss[2], *dee[2]; i64 *doo[2];
-        for (int b = 0; b < 2; b++) {
-            if (key) IVX_TRY(ctx->get_scratch(b ? WS_IN2_KEY : WS_IN_KEY, rows * sizeof(u32), (void **)&dkk[b]));
-            IVX_TRY(ctx->get_scratch(b ? WS_IN2_START : WS_IN_START, rows * sizeof(i32), (void **)&dss[b]));
-            IVX_TRY(ctx->get_scratch(b ? WS_IN2_END : WS_IN_END, rows * sizeof(i32), (void **)&dee[b]));
-            IVX_TRY(ctx->get_scratch(b ? WS_OUT_B : WS_OUT_A, rows * sizeof(i64), (void **)&doo[b]));
-        }
-        HostCopier hc;
-        IVX_HIP(ctx, hc.start(ctx->device));
-        ivx_status rc = IVX_OK;
-        for (u32 c = 0; c < nchunk && rc == IVX_OK; c++) {
-            const u64 c0 = (u64)c * rows, c1 = c0 + rows < n ? c0 + rows : n;
-            if (c0 >= c1) break;
-            const int b = (int)(c & 1u);
-            const u64 nc = c1 - c0;
-            // (input set b was last read by the kernels of chunk c - 2, earlier on this stream; output set b by the COPY of
-            //  chunk c - 2, on the helper's stream: that one is awaited before this chunk's kernels are enqueued)
-            hipError_t e = hipSuccess;
-            if (key) e = hipMemcpyAsync(dkk[b], key + c0, nc * sizeof(u32), hipMemcpyHostToDevice, st);
-            if (e == hipSuccess) e = hipMemcpyAsync(dss[b], start + c0, nc * sizeof(i32), hipMemcpyHostToDevice, st);
-            if (e == hipSuccess) e = hipMemcpyAsync(dee[b], end + c0, nc * sizeof(i32), hipMemcpyHostToDevice, st);
-            if (e != hipSuccess) { rc = ctx->fail_hip("hipMemcpyAsync(chunk)", e); break; }
-            if (c >= 2) hc.wait_until(c - 1);
-            {
-                KernelTimer t(ctx);
-                rc = kind == IVX_KIND_COUNT ? ivx_count_probe(ctx, ix, dkk[b], dss[b], dee[b], nc, strict, doo[b])
-                                            : ivx_coverage_probe(ctx, ix, dkk[b], dss[b], dee[b], nc, strict, doo[b]);
-            }
-            if (rc != IVX_OK) break;
-            hipEvent_t ev;
-            e = hc.mark(st, &ev);
-            if (e != hipSuccess) { rc = ctx->fail_hip("hipEventRecord(chunk)", e); break; }
-            hc.push(out + c0, doo[b], nc * sizeof(i64), ev);
-        }
-        const hipError_t es = hipStreamSynchronize(st);
-        const hipError_t herr = hc.finish();
-        if (rc != IVX_OK) return rc;
-        if (es != hipSuccess) return ctx->fail_hip("hipStreamSynchronize", es);
-        if (herr != hipSuccess) return ctx->fail_hip("hipMemcpyAsync(values)", herr);
-        return IVX_OK;
+        i64 *doo[2];
+        IVX_TRY(ctx->get_scratch(WS_OUT_A, rows * sizeof(i64), (void **)&doo[0]));
+        IVX_TRY(ctx->get_scratch(WS_OUT_B, rows * sizeof(i64), (void **)&doo[1]));
+        return host_chunked(ctx, key, start, end, n, nchunk, true, "hipMemcpyAsync(values)", [&](HostChunk &ch) -> ivx_status {
+            KernelTimer t(ctx);
+            IVX_TRY(probe(ch.key, ch.start, ch.end, ch.n, doo[ch.set]));
+            ch.push(out + ch.c0, doo[ch.set], ch.n * sizeof(i64));
+            return IVX_OK;
+        });
     }
-    const u32 *dk; const i32 *ds, *de; i64 *dout;
-    IVX_TRY(stage_in(ctx, mem, WS_IN_KEY, key, n, &dk));
-    IVX_TRY(stage_in(ctx, mem, WS_IN_START, start, n, &ds));
-    IVX_TRY(stage_in(ctx, mem, WS_IN_END, end, n, &de));
-    IVX_TRY(stage_out(ctx, mem, WS_OUT_A, out, n, &dout));
-    {
-        KernelTimer t(ctx);
-        if (kind == IVX_KIND_COUNT) IVX_TRY(ivx_count_probe(ctx, ix, dk, ds, de, n, strict, dout));
-        else IVX_TRY(ivx_coverage_probe(ctx, ix, dk, ds, de, n, strict, dout));
-    }
-    IVX_TRY(copy_out(ctx, mem, out, dout, n));
-    if (mem == IVX_MEM_HOST) IVX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return IVX_OK;
+    const u32 *dk = f.in(key, n);
+    const i32 *ds = f.in(start, n), *de = f.in(end, n);
+    i64 *dout = f.out(out, n);
+    IVX_TRY(f.run([&] { return probe(dk, ds, de, n, dout); }));
+    f.back_all();
+    return f.finish();
 }
 
 extern "C" ivx_status ivx_probe_count(ivx_ctx *ctx, const ivx_index *ix, int mem, const uint32_t *key, const int32_t *start,
@@ -958,31 +849,24 @@ extern "C" ivx_status ivx_probe_nearest(ivx_ctx *ctx, const ivx_index *ix, int m
                                         const int32_t *end, uint64_t n, int strict, uint32_t k, int include_overlaps,
                                         uint32_t *build_idx, uint32_t *probe_idx, int64_t *distance, uint64_t cap, uint64_t *rows)
 {
-    IVX_TRY(check_probe_args(ctx, ix, IVX_KIND_NEAREST, mem, start, end, n));
+    Frame f(ctx, mem);
+    IVX_TRY(check_probe_args(f, ix, IVX_KIND_NEAREST, start, end, n));
     if (!rows) return ctx->fail(IVX_ERR_INVALID, "null rows");
     if (n && (!build_idx || !probe_idx)) return ctx->fail(IVX_ERR_INVALID, "null output column");
     if ((u64)k * n > 0xFFFFFFFFFFull) return ctx->fail(IVX_ERR_INVALID, "nearest: k * rows too large");
-    CallMetrics cm(ctx, false, n);
-    const u32 *dk; const i32 *ds, *de; u32 *db, *dp; i64 *dd;
-    IVX_TRY(stage_in(ctx, mem, WS_IN_KEY, key, n, &dk));
-    IVX_TRY(stage_in(ctx, mem, WS_IN_START, start, n, &ds));
-    IVX_TRY(stage_in(ctx, mem, WS_IN_END, end, n, &de));
-    IVX_TRY(stage_out(ctx, mem, WS_OUT_A, build_idx, cap, &db));
-    IVX_TRY(stage_out(ctx, mem, WS_OUT_B, probe_idx, cap, &dp));
-    IVX_TRY(stage_out(ctx, mem, WS_OUT_C, distance, cap, &dd));
+    f.meter(false, n);
+    const u32 *dk = f.in(key, n);
+    const i32 *ds = f.in(start, n), *de = f.in(end, n);
+    u32 *db = f.out(build_idx, cap), *dp = f.out(probe_idx, cap);
+    i64 *dd = f.out(distance, cap);
+    IVX_TRY(f.st);
     u64 r = 0;
-    {
-        KernelTimer t(ctx);
-        ivx_status st = ivx_nearest_probe(ctx, ix, dk, ds, de, n, strict, k, include_overlaps, db, dp, dd, cap, &r);
-        *rows = r;
-        if (st != IVX_OK) return st;
-    }
-    cm.out(r);
-    IVX_TRY(copy_out(ctx, mem, build_idx, db, r));
-    IVX_TRY(copy_out(ctx, mem, probe_idx, dp, r));
-    IVX_TRY(copy_out(ctx, mem, distance, dd, r));
-    if (mem == IVX_MEM_HOST) IVX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return IVX_OK;
+    const ivx_status st = f.run([&] { return ivx_nearest_probe(ctx, ix, dk, ds, de, n, strict, k, include_overlaps, db, dp, dd, cap, &r); });
+    *rows = r;
+    if (st != IVX_OK) return st;
+    f.rows_out(r);
+    f.back_all(r);
+    return f.finish();
 }
 
 // ---------------------------------------------------------------- a7..a9
@@ -992,36 +876,22 @@ extern "C" ivx_status ivx_merge(ivx_ctx *ctx, int mem, const uint32_t *key, cons
                                 uint32_t *out_key, int64_t *out_start, int64_t *out_end, int64_t *out_n,
                                 uint64_t cap, uint64_t *n_out)
 {
-    if (!ctx) return IVX_ERR_INVALID;
-    if (!n_out) return ctx->fail(IVX_ERR_INVALID, "null n_out");
-    *n_out = 0;
-    if (mem != IVX_MEM_HOST && mem != IVX_MEM_DEVICE) return ctx->fail(IVX_ERR_INVALID, "bad mem");
+    Frame f(ctx, mem);
+    IVX_TRY(f.enter(n_out, "null n_out"));
     if (n && (!start || !end)) return ctx->fail(IVX_ERR_INVALID, "null coordinate column");
     if (min_dist < 0) return ctx->fail(IVX_ERR_INVALID, "merge() min_dist must be >= 0, got " + std::to_string(min_dist));   // table_function.rs:237
     if (cap < n) return ctx->fail(IVX_ERR_CAPACITY, "merge: output buffers need capacity n");
     if (n >= 0xFFFFFFFFull) return ctx->fail(IVX_ERR_INVALID, "merge: more than 2^32-1 rows in one call");
     if (!key || n_keys == 0) n_keys = 1;
-    IVX_HIP(ctx, hipSetDevice(ctx->device));
-    const u32 *dk; const i64 *ds, *de; u32 *ok; i64 *os, *oe, *on;
-    IVX_TRY(stage_in(ctx, mem, WS_IN_KEY, key, n, &dk));
-    IVX_TRY(stage_in(ctx, mem, WS_IN_START, start, n, &ds));
-    IVX_TRY(stage_in(ctx, mem, WS_IN_END, end, n, &de));
-    IVX_TRY(stage_out(ctx, mem, WS_OUT_A, out_key, n, &ok));
-    IVX_TRY(stage_out(ctx, mem, WS_OUT_B, out_start, n, &os));
-    IVX_TRY(stage_out(ctx, mem, WS_OUT_C, out_end, n, &oe));
-    IVX_TRY(stage_out(ctx, mem, WS_OUT_D, out_n, n, &on));
+    const u32 *dk = f.in(key, n);
+    const i64 *ds = f.in(start, n), *de = f.in(end, n);
+    u32 *ok = f.out(out_key, n);
+    i64 *os = f.out(out_start, n), *oe = f.out(out_end, n), *on = f.out(out_n, n);
     u64 m = 0;
-    {
-        KernelTimer t(ctx);
-        IVX_TRY(ivx_merge_device(ctx, dk, ds, de, n, n_keys, min_dist, strict, ok, os, oe, on, &m));
-    }
+    IVX_TRY(f.run([&] { return ivx_merge_device(ctx, dk, ds, de, n, n_keys, min_dist, strict, ok, os, oe, on, &m); }));
     *n_out = m;
-    IVX_TRY(copy_out(ctx, mem, out_key, ok, m));
-    IVX_TRY(copy_out(ctx, mem, out_start, os, m));
-    IVX_TRY(copy_out(ctx, mem, out_end, oe, m));
-    IVX_TRY(copy_out(ctx, mem, out_n, on, m));
-    if (mem == IVX_MEM_HOST) IVX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return IVX_OK;
+    f.back_all(m);
+    return f.finish();
 }
 
 extern "C" ivx_status ivx_subtract(ivx_ctx *ctx, int mem,
@@ -1031,16 +901,13 @@ extern "C" ivx_status ivx_subtract(ivx_ctx *ctx, int mem,
                                    uint32_t *out_key, int64_t *out_start, int64_t *out_end, uint32_t *out_row,
                                    uint64_t cap, uint64_t *n_out)
 {
-    if (!ctx) return IVX_ERR_INVALID;
-    if (!n_out) return ctx->fail(IVX_ERR_INVALID, "null n_out");
-    *n_out = 0;
-    if (mem != IVX_MEM_HOST && mem != IVX_MEM_DEVICE) return ctx->fail(IVX_ERR_INVALID, "bad mem");
+    Frame f(ctx, mem);
+    IVX_TRY(f.enter(n_out, "null n_out"));
     if ((nl && (!lstart || !lend)) || (nr && (!rstart || !rend))) return ctx->fail(IVX_ERR_INVALID, "null coordinate column");
     if (nl >= 0xFFFFFFFFull || nr >= 0xFFFFFFFFull) return ctx->fail(IVX_ERR_INVALID, "subtract: more than 2^32-1 rows in one call");
     if ((lkey == nullptr) != (rkey == nullptr) && nl && nr) return ctx->fail(IVX_ERR_INVALID, "subtract: key given for one side only");
     if (n_keys == 0 || (!lkey && !rkey)) n_keys = 1;
-    IVX_HIP(ctx, hipSetDevice(ctx->device));
-    const u32 *dlk = nullptr, *drk = nullptr; const i64 *dls = nullptr, *dle = nullptr, *drs = nullptr, *dre = nullptr; u32 *ok, *orow; i64 *os, *oe;
+    IVX_TRY(f.device());
     // a fill call right after the sizing call for the same arguments: the sorted sides, gap heads and output
     // offsets are still in the context (nothing else ran in between), only the output pass is left
     const void *in[6] = {lkey, lstart, lend, rkey, rstart, rend};
@@ -1048,37 +915,27 @@ extern "C" ivx_status ivx_subtract(ivx_ctx *ctx, int mem,
     const bool sizing = cap == 0 && !out_key && !out_start && !out_end && !out_row;
     const bool planned = !sizing && nl && pl.valid && !getenv("IVX_NO_PLAN") && pl.mem == mem && memcmp(pl.in, in, sizeof(in)) == 0 && pl.nl == nl && pl.nr == nr &&
                          pl.nkeys == n_keys && pl.strict == strict && pl.stream == ctx->stream;
+    const u32 *dlk = nullptr, *drk = nullptr; const i64 *dls = nullptr, *dle = nullptr, *drs = nullptr, *dre = nullptr;
     if (!planned) {
-        IVX_TRY(stage_in(ctx, mem, WS_IN_KEY, lkey, nl, &dlk));
-        IVX_TRY(stage_in(ctx, mem, WS_IN_START, lstart, nl, &dls));
-        IVX_TRY(stage_in(ctx, mem, WS_IN_END, lend, nl, &dle));
-        IVX_TRY(stage_in(ctx, mem, WS_IN2_KEY, rkey, nr, &drk));
-        IVX_TRY(stage_in(ctx, mem, WS_IN2_START, rstart, nr, &drs));
-        IVX_TRY(stage_in(ctx, mem, WS_IN2_END, rend, nr, &dre));
+        dlk = f.in(lkey, nl); dls = f.in(lstart, nl); dle = f.in(lend, nl);
+        drk = f.in(rkey, nr); drs = f.in(rstart, nr); dre = f.in(rend, nr);
     }
-    IVX_TRY(stage_out(ctx, mem, WS_OUT_A, out_key, cap, &ok));
-    IVX_TRY(stage_out(ctx, mem, WS_OUT_B, out_start, cap, &os));
-    IVX_TRY(stage_out(ctx, mem, WS_OUT_C, out_end, cap, &oe));
-    IVX_TRY(stage_out(ctx, mem, WS_OUT_D, out_row, cap, &orow));
+    u32 *ok = f.out(out_key, cap);
+    i64 *os = f.out(out_start, cap), *oe = f.out(out_end, cap);
+    u32 *orow = f.out(out_row, cap);
+    IVX_TRY(f.st);
     u64 m = 0;
-    {
-        KernelTimer t(ctx);
+    const ivx_status st = f.run([&]() -> ivx_status {
         if (!planned) pl.valid = false;                     // whatever an earlier sizing call left is gone now
-        ivx_status st = planned ? ivx_subtract_fill_planned(ctx, ok, os, oe, orow, cap, &m)
-                                : ivx_subtract_device(ctx, dlk, dls, dle, nl, drk, drs, dre, nr, n_keys, strict, ok, os, oe, orow, cap, &m);
-        *n_out = m;
-        if (st != IVX_OK) { if (st != IVX_ERR_CAPACITY) pl.valid = false; return st; }
-        if (planned) pl.valid = false;                      // consumed: the next fill call sorts and counts again (its input columns may have been refilled in place)
-        if (sizing && pl.valid) { memcpy(pl.in, in, sizeof(in)); pl.mem = mem; }
-    }
-    if (cap) {
-        IVX_TRY(copy_out(ctx, mem, out_key, ok, m));
-        IVX_TRY(copy_out(ctx, mem, out_start, os, m));
-        IVX_TRY(copy_out(ctx, mem, out_end, oe, m));
-        IVX_TRY(copy_out(ctx, mem, out_row, orow, m));
-    }
-    if (mem == IVX_MEM_HOST) IVX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return IVX_OK;
+        return planned ? ivx_subtract_fill_planned(ctx, ok, os, oe, orow, cap, &m)
+                       : ivx_subtract_device(ctx, dlk, dls, dle, nl, drk, drs, dre, nr, n_keys, strict, ok, os, oe, orow, cap, &m);
+    });
+    *n_out = m;
+    if (st != IVX_OK) { if (st != IVX_ERR_CAPACITY) pl.valid = false; return st; }
+    if (planned) pl.valid = false;                          // consumed: the next fill call sorts and counts again (its input columns may have been refilled in place)
+    if (sizing && pl.valid) { memcpy(pl.in, in, sizeof(in)); pl.mem = mem; }
+    if (cap) f.back_all(m);
+    return f.finish();
 }
 
 extern "C" ivx_status ivx_cluster(ivx_ctx *ctx, int mem, const uint32_t *key, const int64_t *start, const int64_t *end, uint64_t n,
@@ -1087,44 +944,24 @@ extern "C" ivx_status ivx_cluster(ivx_ctx *ctx, int mem, const uint32_t *key, co
                                   int64_t *out_cluster, int64_t *out_cluster_start, int64_t *out_cluster_end,
                                   uint64_t *key_clusters, uint64_t *n_clusters)
 {
-    if (!ctx) return IVX_ERR_INVALID;
-    if (!n_clusters) return ctx->fail(IVX_ERR_INVALID, "null n_clusters");
-    *n_clusters = 0;
-    if (mem != IVX_MEM_HOST && mem != IVX_MEM_DEVICE) return ctx->fail(IVX_ERR_INVALID, "bad mem");
+    Frame f(ctx, mem);
+    IVX_TRY(f.enter(n_clusters, "null n_clusters"));
     if (n && (!start || !end)) return ctx->fail(IVX_ERR_INVALID, "null coordinate column");
     if (min_dist < 0) return ctx->fail(IVX_ERR_INVALID, "cluster() min_dist must be >= 0, got " + std::to_string(min_dist));   // table_function.rs:237
     if (n >= 0xFFFFFFFFull) return ctx->fail(IVX_ERR_INVALID, "cluster: more than 2^32-1 rows in one call");
     if (!key || n_keys == 0) n_keys = 1;
-    IVX_HIP(ctx, hipSetDevice(ctx->device));
-    const u32 *dk; const i64 *ds, *de, *dbase; u32 *ok, *orow; i64 *os, *oe, *oc, *ocs, *oce; u64 *okc;
-    IVX_TRY(stage_in(ctx, mem, WS_IN_KEY, key, n, &dk));
-    IVX_TRY(stage_in(ctx, mem, WS_IN_START, start, n, &ds));
-    IVX_TRY(stage_in(ctx, mem, WS_IN_END, end, n, &de));
-    IVX_TRY(stage_in(ctx, mem, WS_IN2_KEY, key_base, (u64)n_keys, &dbase));
-    IVX_TRY(stage_out(ctx, mem, WS_OUT_A, out_key, n, &ok));
-    IVX_TRY(stage_out(ctx, mem, WS_OUT_B, out_start, n, &os));
-    IVX_TRY(stage_out(ctx, mem, WS_OUT_C, out_end, n, &oe));
-    IVX_TRY(stage_out(ctx, mem, WS_OUT_D, out_row, n, &orow));
-    IVX_TRY(stage_out(ctx, mem, WS_OUT_E, out_cluster, n, &oc));
-    IVX_TRY(stage_out(ctx, mem, WS_OUT_F, out_cluster_start, n, &ocs));
-    IVX_TRY(stage_out(ctx, mem, WS_OUT_G, out_cluster_end, n, &oce));
-    IVX_TRY(stage_out(ctx, mem, WS_OUT_H, key_clusters, (u64)n_keys, &okc));
+    const u32 *dk = f.in(key, n);
+    const i64 *ds = f.in(start, n), *de = f.in(end, n), *dbase = f.in(key_base, (u64)n_keys);
+    u32 *ok = f.out(out_key, n);
+    i64 *os = f.out(out_start, n), *oe = f.out(out_end, n);
+    u32 *orow = f.out(out_row, n);
+    i64 *oc = f.out(out_cluster, n), *ocs = f.out(out_cluster_start, n), *oce = f.out(out_cluster_end, n);
+    u64 *okc = f.out(key_clusters, (u64)n_keys);
     u64 m = 0;
-    {
-        KernelTimer t(ctx);
-        IVX_TRY(ivx_cluster_device(ctx, dk, ds, de, n, n_keys, min_dist, strict, dbase, ok, os, oe, orow, oc, ocs, oce, okc, &m));
-    }
+    IVX_TRY(f.run([&] { return ivx_cluster_device(ctx, dk, ds, de, n, n_keys, min_dist, strict, dbase, ok, os, oe, orow, oc, ocs, oce, okc, &m); }));
     *n_clusters = m;
-    IVX_TRY(copy_out(ctx, mem, out_key, ok, n));
-    IVX_TRY(copy_out(ctx, mem, out_start, os, n));
-    IVX_TRY(copy_out(ctx, mem, out_end, oe, n));
-    IVX_TRY(copy_out(ctx, mem, out_row, orow, n));
-    IVX_TRY(copy_out(ctx, mem, out_cluster, oc, n));
-    IVX_TRY(copy_out(ctx, mem, out_cluster_start, ocs, n));
-    IVX_TRY(copy_out(ctx, mem, out_cluster_end, oce, n));
-    IVX_TRY(copy_out(ctx, mem, key_clusters, okc, (u64)n_keys));
-    if (mem == IVX_MEM_HOST) IVX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return IVX_OK;
+    f.back_all();                                           // (every row column in full: n rows; key_clusters: n_keys)
+    return f.finish();
 }
 
 extern "C" ivx_status ivx_complement(ivx_ctx *ctx, int mem, const uint32_t *key, const int64_t *start, const int64_t *end, uint64_t n,
@@ -1132,94 +969,86 @@ extern "C" ivx_status ivx_complement(ivx_ctx *ctx, int mem, const uint32_t *key,
                                      uint32_t n_keys, int strict, uint32_t *out_key, int64_t *out_start, int64_t *out_end,
                                      uint64_t cap, uint64_t *n_out)
 {
-    if (!ctx) return IVX_ERR_INVALID;
-    if (!n_out) return ctx->fail(IVX_ERR_INVALID, "null n_out");
-    *n_out = 0;
-    if (mem != IVX_MEM_HOST && mem != IVX_MEM_DEVICE) return ctx->fail(IVX_ERR_INVALID, "bad mem");
+    Frame f(ctx, mem);
+    IVX_TRY(f.enter(n_out, "null n_out"));
     if ((n && (!start || !end)) || (nv && (!vstart || !vend))) return ctx->fail(IVX_ERR_INVALID, "null coordinate column");
     if (n >= 0xFFFFFFFFull || nv >= 0xFFFFFFFFull) return ctx->fail(IVX_ERR_INVALID, "complement: more than 2^32-1 rows in one call");
     if ((key == nullptr) != (vkey == nullptr) && n && nv) return ctx->fail(IVX_ERR_INVALID, "complement: key given for one side only");
     if (n_keys == 0 || (!key && !vkey)) n_keys = 1;
-    IVX_HIP(ctx, hipSetDevice(ctx->device));
-    const u32 *dk, *dvk; const i64 *ds, *de, *dvs, *dve; u32 *ok; i64 *os, *oe;
-    IVX_TRY(stage_in(ctx, mem, WS_IN_KEY, key, n, &dk));
-    IVX_TRY(stage_in(ctx, mem, WS_IN_START, start, n, &ds));
-    IVX_TRY(stage_in(ctx, mem, WS_IN_END, end, n, &de));
-    IVX_TRY(stage_in(ctx, mem, WS_IN2_KEY, vkey, nv, &dvk));
-    IVX_TRY(stage_in(ctx, mem, WS_IN2_START, vstart, nv, &dvs));
-    IVX_TRY(stage_in(ctx, mem, WS_IN2_END, vend, nv, &dve));
-    IVX_TRY(stage_out(ctx, mem, WS_OUT_A, out_key, cap, &ok));
-    IVX_TRY(stage_out(ctx, mem, WS_OUT_B, out_start, cap, &os));
-    IVX_TRY(stage_out(ctx, mem, WS_OUT_C, out_end, cap, &oe));
+    const u32 *dk = f.in(key, n);
+    const i64 *ds = f.in(start, n), *de = f.in(end, n);
+    const u32 *dvk = f.in(vkey, nv);
+    const i64 *dvs = f.in(vstart, nv), *dve = f.in(vend, nv);
+    u32 *ok = f.out(out_key, cap);
+    i64 *os = f.out(out_start, cap), *oe = f.out(out_end, cap);
     u64 m = 0;
-    {
-        KernelTimer t(ctx);
-        ivx_status st = ivx_complement_device(ctx, dk, ds, de, n, dvk, dvs, dve, nv, n_keys, strict, ok, os, oe, cap, &m);
-        *n_out = m;
-        if (st != IVX_OK) return st;
-    }
-    if (cap) {
-        IVX_TRY(copy_out(ctx, mem, out_key, ok, m));
-        IVX_TRY(copy_out(ctx, mem, out_start, os, m));
-        IVX_TRY(copy_out(ctx, mem, out_end, oe, m));
-    }
-    if (mem == IVX_MEM_HOST) IVX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return IVX_OK;
+    const ivx_status st = f.run([&] { return ivx_complement_device(ctx, dk, ds, de, n, dvk, dvs, dve, nv, n_keys, strict, ok, os, oe, cap, &m); });
+    *n_out = m;
+    if (st != IVX_OK) return st;
+    if (cap) f.back_all(m);
+    return f.finish();
 }
+
+// ---------------------------------------------------------------- g: depth()
 
 namespace {
-
-// the 17 input arguments of ivx_depth / ivx_depth_profile_build: the checks made on the host, then the columns on the device
-struct DepthIn {
-    const u32 *rkey, *rpos, *rflags, *rmapq, *ops, *skey, *ss, *se, *key_len; const i32 *off, *sw;
-};
-
-ivx_status depth_check_args(ivx_ctx *ctx, int mem, const uint32_t *rkey, const uint32_t *rpos, const int32_t *cigar_offsets, uint64_t n_reads,
-                            const uint32_t *skey, const uint32_t *sstart, const uint32_t *send, uint64_t n_seg, uint32_t *n_keys)
-{
-    if (mem != IVX_MEM_HOST && mem != IVX_MEM_DEVICE) return ctx->fail(IVX_ERR_INVALID, "bad mem");
-    if (n_reads && (!rpos || !cigar_offsets)) return ctx->fail(IVX_ERR_INVALID, "depth: null read position or CIGAR offset column");
-    if (n_seg && (!sstart || !send)) return ctx->fail(IVX_ERR_INVALID, "depth: null segment coordinate column");
-    if (n_reads >= 0xFFFFFFFFull || n_seg >= 0x7FFFFFFFull) return ctx->fail(IVX_ERR_INVALID, "depth: too many rows in one call");
-    if (*n_keys == 0 && !rkey && !skey) *n_keys = 1;
-    return IVX_OK;
-}
-
-ivx_status depth_stage_in(ivx_ctx *ctx, int mem,
-                          const uint32_t *rkey, const uint32_t *rpos, const uint32_t *rflags, const uint32_t *rmapq,
-                          const int32_t *cigar_offsets, const uint32_t *cigar_ops, uint64_t n_reads,
-                          const uint32_t *skey, const uint32_t *sstart, const uint32_t *send, const int32_t *sweight, uint64_t n_seg,
-                          uint32_t n_keys, const uint32_t *key_len, DepthIn *d)
-{
-    IVX_HIP(ctx, hipSetDevice(ctx->device));
-    // IVX_MEM_HOST: the ops column is staged up to the last offset (the device checks the offsets before it reads an op)
-    u64 n_ops_host = 0;
-    if (mem == IVX_MEM_HOST && n_reads && cigar_offsets && cigar_offsets[n_reads] > 0) n_ops_host = (u64)cigar_offsets[n_reads] / 4;   // (null: the text calls)
-    if (n_ops_host && !cigar_ops) return ctx->fail(IVX_ERR_INVALID, "depth: null CIGAR data buffer");
-    IVX_TRY(stage_in(ctx, mem, WS_IN_KEY, rkey, n_reads, &d->rkey));
-    IVX_TRY(stage_in(ctx, mem, WS_IN_START, rpos, n_reads, &d->rpos));
-    IVX_TRY(stage_in(ctx, mem, WS_IN_END, rflags, n_reads, &d->rflags));
-    IVX_TRY(stage_in(ctx, mem, WS_IN2_KEY, rmapq, n_reads, &d->rmapq));
-    IVX_TRY(stage_in(ctx, mem, WS_IN2_START, n_reads ? cigar_offsets : nullptr, n_reads + 1, &d->off));
-    IVX_TRY(stage_in(ctx, mem, WS_IN2_END, cigar_ops, n_ops_host, &d->ops));
-    IVX_TRY(stage_in(ctx, mem, WS_IN3_KEY, skey, n_seg, &d->skey));
-    IVX_TRY(stage_in(ctx, mem, WS_IN3_START, sstart, n_seg, &d->ss));
-    IVX_TRY(stage_in(ctx, mem, WS_IN3_END, send, n_seg, &d->se));
-    IVX_TRY(stage_in(ctx, mem, WS_IN3_WEIGHT, sweight, n_seg, &d->sw));
-    IVX_TRY(stage_in(ctx, mem, WS_IN_KEYLEN, key_len, (u64)n_keys, &d->key_len));
-    return IVX_OK;
-}
 
 // the cigar column of the text calls: an Arrow Utf8 (large = 0) / LargeUtf8 (1) column
 struct TextIn { int large; const void *off; const uint8_t *text; };
 
+// the caller's columns of a depth() call: the reads with their cigar column as packed ops (cigar_offsets / cigar_ops) or as
+// text (text, the other two null), the weighted segments, the key table and the read filters
+struct DepthArgs {
+    const u32 *rkey, *rpos, *rflags, *rmapq; const i32 *cigar_offsets; const u32 *cigar_ops; const TextIn *text; u64 n_reads;
+    const u32 *skey, *sstart, *send; const i32 *sweight; u64 n_seg;
+    u32 n_keys; const u32 *key_len; u32 filter_flag, min_mapq;
+};
+
+// ... and the same columns on the device
+struct DepthIn {
+    const u32 *rkey, *rpos, *rflags, *rmapq, *ops, *skey, *ss, *se, *key_len; const i32 *off, *sw;
+};
+
+// the checks made on the host, from check_mem() on
+ivx_status depth_check_args(Frame &f, DepthArgs *a)
+{
+    ivx_ctx *ctx = f.ctx;
+    const void *offsets = a->cigar_offsets;
+    if (a->text) {
+        if (a->text->large != 0 && a->text->large != 1) return ctx->fail(IVX_ERR_INVALID, "cigar: large must be 0 (Utf8) or 1 (LargeUtf8)");
+        offsets = a->text->off;                                 // (for the null check only)
+    }
+    IVX_TRY(f.check_mem());
+    if (a->n_reads && (!a->rpos || !offsets)) return ctx->fail(IVX_ERR_INVALID, "depth: null read position or CIGAR offset column");
+    if (a->n_seg && (!a->sstart || !a->send)) return ctx->fail(IVX_ERR_INVALID, "depth: null segment coordinate column");
+    if (a->n_reads >= 0xFFFFFFFFull || a->n_seg >= 0x7FFFFFFFull) return ctx->fail(IVX_ERR_INVALID, "depth: too many rows in one call");
+    if (a->n_keys == 0 && !a->rkey && !a->skey) a->n_keys = 1;
+    return IVX_OK;
+}
+
+ivx_status depth_stage_in(Frame &f, const DepthArgs &a, DepthIn *d)
+{
+    IVX_TRY(f.device());
+    // IVX_MEM_HOST: the ops column is staged up to the last offset (the device checks the offsets before it reads an op)
+    u64 n_ops_host = 0;
+    if (f.mem == IVX_MEM_HOST && a.n_reads && a.cigar_offsets && a.cigar_offsets[a.n_reads] > 0) n_ops_host = (u64)a.cigar_offsets[a.n_reads] / 4;   // (null: the text calls)
+    if (n_ops_host && !a.cigar_ops) return f.ctx->fail(IVX_ERR_INVALID, "depth: null CIGAR data buffer");
+    d->rkey = f.in(a.rkey, a.n_reads); d->rpos = f.in(a.rpos, a.n_reads); d->rflags = f.in(a.rflags, a.n_reads); d->rmapq = f.in(a.rmapq, a.n_reads);
+    d->off = f.in(a.n_reads ? a.cigar_offsets : nullptr, a.n_reads + 1);
+    d->ops = f.in(a.cigar_ops, n_ops_host);
+    d->skey = f.in(a.skey, a.n_seg); d->ss = f.in(a.sstart, a.n_seg); d->se = f.in(a.send, a.n_seg); d->sw = f.in(a.sweight, a.n_seg);
+    d->key_len = f.in(a.key_len, (u64)a.n_keys);
+    return f.st;
+}
+
 // the text column on the device.  IVX_MEM_HOST: the offsets, and the bytes between the first and the last offset (the extent
 // is read from the host offsets, as depth_stage_in does for ops; the device checks the offsets before it reads a byte
 // through one, and offsets that pass name bytes inside the extent) -- *at_off0: *dtext is the byte at offset off[0]
-ivx_status cigar_stage_text(ivx_ctx *ctx, int mem, const TextIn &t, u64 n_reads, const void **doff, const u8 **dtext, bool *at_off0)
+ivx_status cigar_stage_text(Frame &f, const TextIn &t, u64 n_reads, const void **doff, const u8 **dtext, bool *at_off0)
 {
+    ivx_ctx *ctx = f.ctx;
     *at_off0 = false;
-    if (mem == IVX_MEM_DEVICE) { *doff = t.off; *dtext = t.text; return IVX_OK; }
+    if (f.mem == IVX_MEM_DEVICE) { *doff = t.off; *dtext = t.text; return IVX_OK; }
     const i64 o0 = t.large ? ((const i64 *)t.off)[0] : (i64)((const i32 *)t.off)[0];
     const i64 oN = t.large ? ((const i64 *)t.off)[n_reads] : (i64)((const i32 *)t.off)[n_reads];
     u64 extent = 0;
@@ -1228,21 +1057,21 @@ ivx_status cigar_stage_text(ivx_ctx *ctx, int mem, const TextIn &t, u64 n_reads,
         if (extent >= (1ull << 32)) return ctx->fail(IVX_ERR_INVALID, "cigar: 2^32 or more bytes of CIGAR text in one call");
         if (!t.text) return ctx->fail(IVX_ERR_INVALID, "cigar: null text buffer");
     }
-    const u8 *o8;
-    IVX_TRY(stage_in(ctx, mem, WS_IN_TEXTOFF, (const u8 *)t.off, (n_reads + 1) * (t.large ? 8 : 4), &o8));
-    *doff = o8;
+    *doff = f.in_at(WS_IN_TEXTOFF, (const u8 *)t.off, (n_reads + 1) * (t.large ? 8 : 4));
     *dtext = nullptr;
-    if (extent) { IVX_TRY(stage_in(ctx, mem, WS_IN_TEXT, t.text + o0, extent, dtext)); *at_off0 = true; }
-    return IVX_OK;
+    if (extent) { *dtext = f.in_at(WS_IN_TEXT, t.text + o0, extent); *at_off0 = true; }
+    return f.st;
 }
 
-// the text column parsed into context scratch: d->off / d->ops as the binary calls take them
-ivx_status depth_parse_text(ivx_ctx *ctx, int mem, const TextIn &t, u64 n_reads, DepthIn *d)
+// the text column parsed into context scratch (the slots of the binary cigar column, which a text call leaves empty):
+// d->off / d->ops as the binary calls take them
+ivx_status depth_parse_text(Frame &f, const TextIn &t, u64 n_reads, DepthIn *d)
 {
+    ivx_ctx *ctx = f.ctx;
     d->off = nullptr; d->ops = nullptr;
     if (n_reads == 0) return IVX_OK;
     const void *doff; const u8 *dtext; bool at0;
-    IVX_TRY(cigar_stage_text(ctx, mem, t, n_reads, &doff, &dtext, &at0));
+    IVX_TRY(cigar_stage_text(f, t, n_reads, &doff, &dtext, &at0));
     ivx_cigar_plan P;
     IVX_TRY(ivx_cigar_count(ctx, t.large, doff, dtext, at0, n_reads, &P));
     i32 *off; u32 *ops;
@@ -1253,19 +1082,57 @@ ivx_status depth_parse_text(ivx_ctx *ctx, int mem, const TextIn &t, u64 n_reads,
     return IVX_OK;
 }
 
-ivx_status depth_call(ivx_ctx *ctx, int mem,
-                      const uint32_t *rkey, const uint32_t *rpos, const uint32_t *rflags, const uint32_t *rmapq,
-                      const int32_t *cigar_offsets, const uint32_t *cigar_ops, const TextIn *text, uint64_t n_reads,
-                      const uint32_t *skey, const uint32_t *sstart, const uint32_t *send, const int32_t *sweight, uint64_t n_seg,
-                      uint32_t n_keys, const uint32_t *key_len, uint32_t filter_flag, uint32_t min_mapq,
-                      uint32_t *out_key, uint32_t *out_start, uint32_t *out_end, int32_t *out_cov,
-                      uint64_t cap, uint64_t *n_out);
-ivx_status depth_profile_call(ivx_ctx *ctx, int mem,
-                              const uint32_t *rkey, const uint32_t *rpos, const uint32_t *rflags, const uint32_t *rmapq,
-                              const int32_t *cigar_offsets, const uint32_t *cigar_ops, const TextIn *text, uint64_t n_reads,
-                              const uint32_t *skey, const uint32_t *sstart, const uint32_t *send, const int32_t *sweight, uint64_t n_seg,
-                              uint32_t n_keys, const uint32_t *key_len, uint32_t filter_flag, uint32_t min_mapq,
-                              ivx_index **out);
+// ivx_depth (a.text = null) and ivx_depth_text (the cigar column as text, parsed into context scratch first)
+ivx_status depth_call(ivx_ctx *ctx, int mem, DepthArgs a,
+                      uint32_t *out_key, uint32_t *out_start, uint32_t *out_end, int32_t *out_cov, uint64_t cap, uint64_t *n_out)
+{
+    Frame f(ctx, mem);
+    IVX_TRY(f.begin(n_out, "null n_out"));
+    IVX_TRY(depth_check_args(f, &a));
+    f.drop_plans();                                         // as any other call between a sizing call and its fill
+    f.meter(false, a.n_reads + a.n_seg);
+    if (a.n_reads == 0 && a.n_seg == 0) return IVX_OK;
+    DepthIn d;
+    IVX_TRY(depth_stage_in(f, a, &d));
+    u32 *ok = f.out(out_key, cap), *os = f.out(out_start, cap), *oe = f.out(out_end, cap);
+    i32 *oc = f.out(out_cov, cap);
+    const bool sizing = cap == 0 && !out_key && !out_start && !out_end && !out_cov;
+    u64 m = 0;
+    const ivx_status st = f.run([&]() -> ivx_status {
+        if (a.text) IVX_TRY(depth_parse_text(f, *a.text, a.n_reads, &d));
+        return ivx_depth_device(ctx, d.rkey, d.rpos, d.rflags, d.rmapq, d.off, d.ops, a.n_reads, d.skey, d.ss, d.se, d.sw, a.n_seg,
+                                a.n_keys, d.key_len, a.filter_flag, a.min_mapq, ok, os, oe, oc, cap, &m);
+    });
+    *n_out = m;
+    if (st != IVX_OK) return st;
+    if (!sizing) { f.rows_out(m); f.back_all(m); }
+    return f.finish();
+}
+
+// ivx_depth_profile_build and its text form: the same inputs, kept as a depth profile on the device
+ivx_status depth_profile_call(ivx_ctx *ctx, int mem, DepthArgs a, ivx_index **out)
+{
+    Frame f(ctx, mem);
+    IVX_TRY(f.begin(out, "null out"));
+    IVX_TRY(depth_check_args(f, &a));
+    f.drop_plans();                                         // as any other call between a sizing call and its fill
+    f.meter(true, a.n_reads + a.n_seg);
+    DepthIn d{};
+    if (a.n_reads || a.n_seg) IVX_TRY(depth_stage_in(f, a, &d));
+    else IVX_TRY(f.device());
+    ivx_index *ix;
+    IVX_TRY(index_new(ctx, IVX_KIND_DEPTH_PROFILE, 0, a.n_keys, &ix));
+    u8 *seen = nullptr;
+    ivx_depth_evs evs{0, nullptr, nullptr};
+    ivx_status st = ivx_depth_profile_begin(ctx, ix, &seen);
+    if (st == IVX_OK) st = f.run([&]() -> ivx_status {
+        if (a.text) IVX_TRY(depth_parse_text(f, *a.text, a.n_reads, &d));
+        IVX_TRY(ivx_depth_events(ctx, d.rkey, d.rpos, d.rflags, d.rmapq, d.off, d.ops, a.n_reads, d.skey, d.ss, d.se, d.sw, a.n_seg,
+                                 a.n_keys, d.key_len, a.filter_flag, a.min_mapq, seen, &evs));
+        return ivx_depth_profile_finish(ctx, ix, evs);
+    });
+    return index_commit(ctx, ix, st, "depth profile build failed on device", out);
+}
 
 }  // namespace
 
@@ -1277,8 +1144,8 @@ extern "C" ivx_status ivx_depth(ivx_ctx *ctx, int mem,
                                 uint32_t *out_key, uint32_t *out_start, uint32_t *out_end, int32_t *out_cov,
                                 uint64_t cap, uint64_t *n_out)
 {
-    return depth_call(ctx, mem, rkey, rpos, rflags, rmapq, cigar_offsets, cigar_ops, nullptr, n_reads, skey, sstart, send, sweight, n_seg,
-                      n_keys, key_len, filter_flag, min_mapq, out_key, out_start, out_end, out_cov, cap, n_out);
+    const DepthArgs a{rkey, rpos, rflags, rmapq, cigar_offsets, cigar_ops, nullptr, n_reads, skey, sstart, send, sweight, n_seg, n_keys, key_len, filter_flag, min_mapq};
+    return depth_call(ctx, mem, a, out_key, out_start, out_end, out_cov, cap, n_out);
 }
 
 extern "C" ivx_status ivx_depth_text(ivx_ctx *ctx, int mem,
@@ -1290,107 +1157,40 @@ extern "C" ivx_status ivx_depth_text(ivx_ctx *ctx, int mem,
                                      uint64_t cap, uint64_t *n_out)
 {
     const TextIn t{large, text_offsets, text};
-    return depth_call(ctx, mem, rkey, rpos, rflags, rmapq, nullptr, nullptr, &t, n_reads, skey, sstart, send, sweight, n_seg,
-                      n_keys, key_len, filter_flag, min_mapq, out_key, out_start, out_end, out_cov, cap, n_out);
-}
-
-extern "C" ivx_status ivx_depth_profile_build_text(ivx_ctx *ctx, int mem,
-                                                   const uint32_t *rkey, const uint32_t *rpos, const uint32_t *rflags, const uint32_t *rmapq,
-                                                   int large, const void *text_offsets, const uint8_t *text, uint64_t n_reads,
-                                                   const uint32_t *skey, const uint32_t *sstart, const uint32_t *send, const int32_t *sweight, uint64_t n_seg,
-                                                   uint32_t n_keys, const uint32_t *key_len, uint32_t filter_flag, uint32_t min_mapq,
-                                                   ivx_index **out)
-{
-    const TextIn t{large, text_offsets, text};
-    return depth_profile_call(ctx, mem, rkey, rpos, rflags, rmapq, nullptr, nullptr, &t, n_reads, skey, sstart, send, sweight, n_seg,
-                              n_keys, key_len, filter_flag, min_mapq, out);
+    const DepthArgs a{rkey, rpos, rflags, rmapq, nullptr, nullptr, &t, n_reads, skey, sstart, send, sweight, n_seg, n_keys, key_len, filter_flag, min_mapq};
+    return depth_call(ctx, mem, a, out_key, out_start, out_end, out_cov, cap, n_out);
 }
 
 extern "C" ivx_status ivx_cigar_parse(ivx_ctx *ctx, int mem, int large, const void *text_offsets, const uint8_t *text, uint64_t n_reads,
                                       int32_t *out_offsets, uint32_t *out_ops, uint64_t cap_ops, uint64_t *n_ops)
 {
-    if (!ctx) return IVX_ERR_INVALID;
-    if (!n_ops) return ctx->fail(IVX_ERR_INVALID, "null n_ops");
-    *n_ops = 0;
-    if (mem != IVX_MEM_HOST && mem != IVX_MEM_DEVICE) return ctx->fail(IVX_ERR_INVALID, "bad mem");
+    Frame f(ctx, mem);
+    IVX_TRY(f.enter(n_ops, "null n_ops"));
     if (large != 0 && large != 1) return ctx->fail(IVX_ERR_INVALID, "cigar: large must be 0 (Utf8) or 1 (LargeUtf8)");
     if (n_reads >= 0xFFFFFFFFull) return ctx->fail(IVX_ERR_INVALID, "cigar: too many rows in one call");
-    ctx->sub_plan.valid = false; ctx->join_plan.valid = false;   // as any other call between a sizing call and its fill
+    f.drop_plans();                                         // as any other call between a sizing call and its fill
     if (n_reads == 0) return IVX_OK;
     if (!text_offsets) return ctx->fail(IVX_ERR_INVALID, "cigar: null text offset column");
-    IVX_HIP(ctx, hipSetDevice(ctx->device));
+    IVX_TRY(f.device());
     const TextIn t{large, text_offsets, text};
     const void *doff; const u8 *dtext; bool at0;
-    IVX_TRY(cigar_stage_text(ctx, mem, t, n_reads, &doff, &dtext, &at0));
+    IVX_TRY(cigar_stage_text(f, t, n_reads, &doff, &dtext, &at0));
     ivx_cigar_plan P;
     IVX_TRY(ivx_cigar_count(ctx, large, doff, dtext, at0, n_reads, &P));
     *n_ops = P.n_ops;
     // the op lengths are checked in every call, a counting call included; ops are written only into a buffer that holds all
     const bool fits = out_ops && cap_ops >= P.n_ops;
-    i32 *ooff; u32 *oops = nullptr;
-    IVX_TRY(stage_out(ctx, mem, WS_OUT_A, out_offsets, n_reads + 1, &ooff));
-    if (fits) IVX_TRY(stage_out(ctx, mem, WS_OUT_B, out_ops, P.n_ops, &oops));
+    i32 *ooff = f.out(out_offsets, n_reads + 1);
+    u32 *oops = fits ? f.out(out_ops, P.n_ops) : nullptr;
+    IVX_TRY(f.st);
     IVX_TRY(ivx_cigar_write(ctx, P, ooff, oops));
-    IVX_TRY(copy_out(ctx, mem, out_offsets, ooff, n_reads + 1));
-    if (fits) IVX_TRY(copy_out(ctx, mem, out_ops, oops, P.n_ops));
-    IVX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    f.back_all();
+    IVX_TRY(f.st);
+    IVX_HIP(ctx, hipStreamSynchronize(ctx->stream));        // (in both modes)
     if (out_ops && !fits) return ctx->fail(IVX_ERR_CAPACITY, "cigar: op buffer too small");
     if (!out_ops && cap_ops && cap_ops < P.n_ops) return ctx->fail(IVX_ERR_CAPACITY, "cigar: op buffer too small");
     return IVX_OK;
 }
-
-namespace {
-
-// ivx_depth (text = null) and ivx_depth_text (the cigar column as text, parsed into context scratch first)
-ivx_status depth_call(ivx_ctx *ctx, int mem,
-                      const uint32_t *rkey, const uint32_t *rpos, const uint32_t *rflags, const uint32_t *rmapq,
-                      const int32_t *cigar_offsets, const uint32_t *cigar_ops, const TextIn *text, uint64_t n_reads,
-                      const uint32_t *skey, const uint32_t *sstart, const uint32_t *send, const int32_t *sweight, uint64_t n_seg,
-                      uint32_t n_keys, const uint32_t *key_len, uint32_t filter_flag, uint32_t min_mapq,
-                      uint32_t *out_key, uint32_t *out_start, uint32_t *out_end, int32_t *out_cov,
-                      uint64_t cap, uint64_t *n_out)
-{
-    if (!ctx) return IVX_ERR_INVALID;
-    if (!n_out) return ctx->fail(IVX_ERR_INVALID, "null n_out");
-    *n_out = 0;
-    if (text) {
-        if (text->large != 0 && text->large != 1) return ctx->fail(IVX_ERR_INVALID, "cigar: large must be 0 (Utf8) or 1 (LargeUtf8)");
-        cigar_offsets = (const int32_t *)text->off;             // (for the null check only)
-    }
-    IVX_TRY(depth_check_args(ctx, mem, rkey, rpos, cigar_offsets, n_reads, skey, sstart, send, n_seg, &n_keys));
-    ctx->sub_plan.valid = false; ctx->join_plan.valid = false;   // as any other call between a sizing call and its fill
-    CallMetrics cm(ctx, false, n_reads + n_seg);
-    if (n_reads == 0 && n_seg == 0) return IVX_OK;
-    DepthIn d;
-    u32 *ok, *os, *oe; i32 *oc;
-    IVX_TRY(depth_stage_in(ctx, mem, rkey, rpos, rflags, rmapq, text ? nullptr : cigar_offsets, text ? nullptr : cigar_ops, n_reads,
-                           skey, sstart, send, sweight, n_seg, n_keys, key_len, &d));
-    IVX_TRY(stage_out(ctx, mem, WS_OUT_A, out_key, cap, &ok));
-    IVX_TRY(stage_out(ctx, mem, WS_OUT_B, out_start, cap, &os));
-    IVX_TRY(stage_out(ctx, mem, WS_OUT_C, out_end, cap, &oe));
-    IVX_TRY(stage_out(ctx, mem, WS_OUT_D, out_cov, cap, &oc));
-    const bool sizing = cap == 0 && !out_key && !out_start && !out_end && !out_cov;
-    u64 m = 0;
-    {
-        KernelTimer t(ctx);
-        if (text) IVX_TRY(depth_parse_text(ctx, mem, *text, n_reads, &d));
-        ivx_status st = ivx_depth_device(ctx, d.rkey, d.rpos, d.rflags, d.rmapq, d.off, d.ops, n_reads, d.skey, d.ss, d.se, d.sw, n_seg,
-                                         n_keys, d.key_len, filter_flag, min_mapq, ok, os, oe, oc, cap, &m);
-        *n_out = m;
-        if (st != IVX_OK) return st;
-    }
-    if (!sizing) {
-        cm.out(m);
-        IVX_TRY(copy_out(ctx, mem, out_key, ok, m));
-        IVX_TRY(copy_out(ctx, mem, out_start, os, m));
-        IVX_TRY(copy_out(ctx, mem, out_end, oe, m));
-        IVX_TRY(copy_out(ctx, mem, out_cov, oc, m));
-    }
-    if (mem == IVX_MEM_HOST) IVX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return IVX_OK;
-}
-
-}  // namespace
 
 // ---------------------------------------------------------------- g': depth profiles (per-base depth())
 
@@ -1401,83 +1201,44 @@ extern "C" ivx_status ivx_depth_profile_build(ivx_ctx *ctx, int mem,
                                               uint32_t n_keys, const uint32_t *key_len, uint32_t filter_flag, uint32_t min_mapq,
                                               ivx_index **out)
 {
-    return depth_profile_call(ctx, mem, rkey, rpos, rflags, rmapq, cigar_offsets, cigar_ops, nullptr, n_reads, skey, sstart, send, sweight, n_seg,
-                              n_keys, key_len, filter_flag, min_mapq, out);
+    const DepthArgs a{rkey, rpos, rflags, rmapq, cigar_offsets, cigar_ops, nullptr, n_reads, skey, sstart, send, sweight, n_seg, n_keys, key_len, filter_flag, min_mapq};
+    return depth_profile_call(ctx, mem, a, out);
 }
 
-namespace {
-
-ivx_status depth_profile_call(ivx_ctx *ctx, int mem,
-                              const uint32_t *rkey, const uint32_t *rpos, const uint32_t *rflags, const uint32_t *rmapq,
-                              const int32_t *cigar_offsets, const uint32_t *cigar_ops, const TextIn *text, uint64_t n_reads,
-                              const uint32_t *skey, const uint32_t *sstart, const uint32_t *send, const int32_t *sweight, uint64_t n_seg,
-                              uint32_t n_keys, const uint32_t *key_len, uint32_t filter_flag, uint32_t min_mapq,
-                              ivx_index **out)
+extern "C" ivx_status ivx_depth_profile_build_text(ivx_ctx *ctx, int mem,
+                                                   const uint32_t *rkey, const uint32_t *rpos, const uint32_t *rflags, const uint32_t *rmapq,
+                                                   int large, const void *text_offsets, const uint8_t *text, uint64_t n_reads,
+                                                   const uint32_t *skey, const uint32_t *sstart, const uint32_t *send, const int32_t *sweight, uint64_t n_seg,
+                                                   uint32_t n_keys, const uint32_t *key_len, uint32_t filter_flag, uint32_t min_mapq,
+                                                   ivx_index **out)
 {
-    if (!ctx) return IVX_ERR_INVALID;
-    if (!out) return ctx->fail(IVX_ERR_INVALID, "null out");
-    *out = nullptr;
-    if (text) {
-        if (text->large != 0 && text->large != 1) return ctx->fail(IVX_ERR_INVALID, "cigar: large must be 0 (Utf8) or 1 (LargeUtf8)");
-        cigar_offsets = (const int32_t *)text->off;             // (for the null check only)
-    }
-    IVX_TRY(depth_check_args(ctx, mem, rkey, rpos, cigar_offsets, n_reads, skey, sstart, send, n_seg, &n_keys));
-    ctx->sub_plan.valid = false; ctx->join_plan.valid = false;   // as any other call between a sizing call and its fill
-    CallMetrics cm(ctx, true, n_reads + n_seg);
-    DepthIn d{};
-    if (n_reads || n_seg)
-        IVX_TRY(depth_stage_in(ctx, mem, rkey, rpos, rflags, rmapq, text ? nullptr : cigar_offsets, text ? nullptr : cigar_ops, n_reads,
-                               skey, sstart, send, sweight, n_seg, n_keys, key_len, &d));
-    else IVX_HIP(ctx, hipSetDevice(ctx->device));
-    ivx_index *ix = new (std::nothrow) ivx_index();
-    if (!ix) return ctx->fail(IVX_ERR_OOM, "host allocation failed");
-    ix->kind = IVX_KIND_DEPTH_PROFILE; ix->device = ctx->device; ix->n = 0; ix->nkeys = n_keys;
-    ctx->building_bytes = 0;
-    u8 *seen = nullptr;
-    ivx_depth_evs evs{0, nullptr, nullptr};
-    ivx_status st = ivx_depth_profile_begin(ctx, ix, &seen);
-    if (st == IVX_OK) {
-        KernelTimer t(ctx);
-        if (text) st = depth_parse_text(ctx, mem, *text, n_reads, &d);
-        if (st == IVX_OK) st = ivx_depth_events(ctx, d.rkey, d.rpos, d.rflags, d.rmapq, d.off, d.ops, n_reads, d.skey, d.ss, d.se, d.sw, n_seg,
-                              n_keys, d.key_len, filter_flag, min_mapq, seen, &evs);
-        if (st == IVX_OK) st = ivx_depth_profile_finish(ctx, ix, evs);
-    }
-    if (st == IVX_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) st = ctx->fail(IVX_ERR_HIP, "depth profile build failed on device");
-    ctx->building_bytes = 0;
-    if (st != IVX_OK) { ivx_index_free(ix); return st; }
-    ix->n = ix->dp.steps;
-    ix->owner_bytes = ctx->live_index_bytes;                    // reserved against this context's limit until the profile is freed
-    ix->owner_bytes->fetch_add(ix->bytes, std::memory_order_relaxed);
-    ctx->metrics.build_mem_used += ix->bytes;
-    *out = ix;
-    return IVX_OK;
+    const TextIn t{large, text_offsets, text};
+    const DepthArgs a{rkey, rpos, rflags, rmapq, nullptr, nullptr, &t, n_reads, skey, sstart, send, sweight, n_seg, n_keys, key_len, filter_flag, min_mapq};
+    return depth_profile_call(ctx, mem, a, out);
 }
-
-}  // namespace
 
 extern "C" void ivx_depth_profile_free(ivx_index *p) { if (p && p->kind == IVX_KIND_DEPTH_PROFILE) ivx_index_free(p); }
 extern "C" uint64_t ivx_depth_profile_steps(const ivx_index *p) { return p && p->kind == IVX_KIND_DEPTH_PROFILE ? p->dp.steps : 0; }
 extern "C" uint64_t ivx_depth_profile_device_bytes(const ivx_index *p) { return p && p->kind == IVX_KIND_DEPTH_PROFILE ? p->bytes : 0; }
 
-static ivx_status check_profile_args(ivx_ctx *ctx, const ivx_index *p, int mem)
+// the head of every call on a profile, after the frame's begin(): the profile, check_mem(), the device
+static ivx_status check_profile_args(Frame &f, const ivx_index *p)
 {
+    ivx_ctx *ctx = f.ctx;
     if (!p) return ctx->fail(IVX_ERR_INVALID, "null depth profile");
     if (p->kind != IVX_KIND_DEPTH_PROFILE) return ctx->fail(IVX_ERR_UNSUPPORTED, "not a depth profile");
     if (p->device != ctx->device) return ctx->fail(IVX_ERR_INVALID, "depth profile lives on another device");
-    if (mem != IVX_MEM_HOST && mem != IVX_MEM_DEVICE) return ctx->fail(IVX_ERR_INVALID, "bad mem");
-    IVX_HIP(ctx, hipSetDevice(ctx->device));
-    return IVX_OK;
+    IVX_TRY(f.check_mem());
+    return f.device();
 }
 
 extern "C" ivx_status ivx_depth_profile_read(ivx_ctx *ctx, const ivx_index *p, int mem,
                                              uint32_t *out_key, uint32_t *out_pos, int32_t *out_cov, uint8_t *key_seen,
                                              uint64_t cap, uint64_t *n_out)
 {
-    if (!ctx) return IVX_ERR_INVALID;
-    if (!n_out) return ctx->fail(IVX_ERR_INVALID, "null n_out");
-    *n_out = 0;
-    IVX_TRY(check_profile_args(ctx, p, mem));
+    Frame f(ctx, mem);
+    IVX_TRY(f.begin(n_out, "null n_out"));
+    IVX_TRY(check_profile_args(f, p));
     const DepthProfileView &dp = p->dp;
     const hipMemcpyKind kind = mem == IVX_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
     *n_out = dp.steps;
@@ -1490,7 +1251,7 @@ extern "C" ivx_status ivx_depth_profile_read(ivx_ctx *ctx, const ivx_index *p, i
         if (out_pos) IVX_HIP(ctx, hipMemcpyAsync(out_pos, dp.pos, dp.steps * sizeof(u32), kind, ctx->stream));
         if (out_cov) IVX_HIP(ctx, hipMemcpyAsync(out_cov, dp.cov, dp.steps * sizeof(i32), kind, ctx->stream));
     }
-    if (mem == IVX_MEM_HOST) IVX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    IVX_TRY(f.finish());                                    // (key_seen has gone out whatever st says)
     return st;
 }
 
@@ -1498,173 +1259,141 @@ extern "C" ivx_status ivx_depth_profile_expand(ivx_ctx *ctx, const ivx_index *p,
                                                uint32_t key, uint32_t first_pos, uint64_t n, int skip_pos0,
                                                int32_t *out_pos, void *out_cov)
 {
-    if (!ctx) return IVX_ERR_INVALID;
-    IVX_TRY(check_profile_args(ctx, p, mem));
+    Frame f(ctx, mem);
+    IVX_TRY(f.begin());
+    IVX_TRY(check_profile_args(f, p));
     if (key >= p->nkeys) return ctx->fail(IVX_ERR_INVALID, "depth profile: key id >= n_keys");
     if (n > 0x100000000ull || (u64)first_pos + n > 0x100000000ull) return ctx->fail(IVX_ERR_INVALID, "depth profile: window ends beyond position 2^32 - 1");
     if (mem == IVX_MEM_DEVICE && ((((uintptr_t)out_pos) & 3u) || (((uintptr_t)out_cov) & 1u)))
         return ctx->fail(IVX_ERR_INVALID, "depth profile: output pointer not aligned to its element size");
-    ctx->sub_plan.valid = false; ctx->join_plan.valid = false;
+    f.drop_plans();
     if (n == 0) return IVX_OK;
-    i32 *dpos; int16_t *dcov;
-    IVX_TRY(stage_out(ctx, mem, WS_OUT_A, out_pos, n, &dpos));
-    IVX_TRY(stage_out(ctx, mem, WS_OUT_B, (int16_t *)out_cov, n, &dcov));
-    {
-        KernelTimer t(ctx);
-        IVX_TRY(ivx_depth_expand_device(ctx, p->dp, key, first_pos, n, skip_pos0 != 0, dpos, dcov));
-    }
-    IVX_TRY(copy_out(ctx, mem, out_pos, dpos, n));
-    IVX_TRY(copy_out(ctx, mem, (int16_t *)out_cov, dcov, n));
-    if (mem == IVX_MEM_HOST) IVX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return IVX_OK;
+    i32 *dpos = f.out(out_pos, n);
+    int16_t *dcov = f.out((int16_t *)out_cov, n);
+    IVX_TRY(f.run([&] { return ivx_depth_expand_device(ctx, p->dp, key, first_pos, n, skip_pos0 != 0, dpos, dcov); }));
+    f.back_all();
+    return f.finish();
 }
 
 extern "C" ivx_status ivx_depth_profile_merge(ivx_ctx *ctx, const ivx_index *a, const ivx_index *b, ivx_index **out)
 {
-    if (!ctx) return IVX_ERR_INVALID;
-    if (!out) return ctx->fail(IVX_ERR_INVALID, "null out");
-    *out = nullptr;
-    IVX_TRY(check_profile_args(ctx, a, IVX_MEM_DEVICE));
-    IVX_TRY(check_profile_args(ctx, b, IVX_MEM_DEVICE));
-    ctx->sub_plan.valid = false; ctx->join_plan.valid = false;   // as any other call between a sizing call and its fill
+    Frame f(ctx, IVX_MEM_DEVICE);
+    IVX_TRY(f.begin(out, "null out"));
+    IVX_TRY(check_profile_args(f, a));
+    IVX_TRY(check_profile_args(f, b));
+    f.drop_plans();                                         // as any other call between a sizing call and its fill
     if (a->dp.steps + b->dp.steps >= 0xFFFFFF00ull)
         return ctx->fail(IVX_ERR_INVALID, "depth profile merge: more than 2^32-257 steps in the two profiles");
-    CallMetrics cm(ctx, true, a->dp.steps + b->dp.steps);
-    ivx_index *ix = new (std::nothrow) ivx_index();
-    if (!ix) return ctx->fail(IVX_ERR_OOM, "host allocation failed");
-    ix->kind = IVX_KIND_DEPTH_PROFILE; ix->device = ctx->device; ix->n = 0; ix->nkeys = a->nkeys > b->nkeys ? a->nkeys : b->nkeys;
-    ctx->building_bytes = 0;
+    f.meter(true, a->dp.steps + b->dp.steps);
+    ivx_index *ix;
+    IVX_TRY(index_new(ctx, IVX_KIND_DEPTH_PROFILE, 0, a->nkeys > b->nkeys ? a->nkeys : b->nkeys, &ix));
     u8 *seen = nullptr;
     ivx_status st = ivx_depth_profile_begin(ctx, ix, &seen);
-    if (st == IVX_OK) {
-        KernelTimer t(ctx);
-        st = ivx_depth_profile_merge_device(ctx, a->dp, a->nkeys, b->dp, b->nkeys, ix);
-    }
-    if (st == IVX_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) st = ctx->fail(IVX_ERR_HIP, "depth profile merge failed on device");
-    ctx->building_bytes = 0;
-    if (st != IVX_OK) { ivx_index_free(ix); return st; }
-    ix->n = ix->dp.steps;
-    ix->owner_bytes = ctx->live_index_bytes;                    // reserved against this context's limit until the profile is freed
-    ix->owner_bytes->fetch_add(ix->bytes, std::memory_order_relaxed);
-    ctx->metrics.build_mem_used += ix->bytes;
-    *out = ix;
-    return IVX_OK;
+    if (st == IVX_OK) st = f.run([&] { return ivx_depth_profile_merge_device(ctx, a->dp, a->nkeys, b->dp, b->nkeys, ix); });
+    return index_commit(ctx, ix, st, "depth profile merge failed on device", out);
 }
 
 extern "C" ivx_status ivx_depth_profile_blocks(ivx_ctx *ctx, const ivx_index *p, int mem,
                                                uint32_t *out_key, uint32_t *out_start, uint32_t *out_end, int32_t *out_cov,
                                                uint64_t cap, uint64_t *n_out)
 {
-    if (!ctx) return IVX_ERR_INVALID;
-    if (!n_out) return ctx->fail(IVX_ERR_INVALID, "null n_out");
-    *n_out = 0;
-    IVX_TRY(check_profile_args(ctx, p, mem));
-    ctx->sub_plan.valid = false; ctx->join_plan.valid = false;
-    CallMetrics cm(ctx, false, p->dp.steps);
-    u32 *ok, *os, *oe; i32 *oc;
-    IVX_TRY(stage_out(ctx, mem, WS_OUT_A, out_key, cap, &ok));
-    IVX_TRY(stage_out(ctx, mem, WS_OUT_B, out_start, cap, &os));
-    IVX_TRY(stage_out(ctx, mem, WS_OUT_C, out_end, cap, &oe));
-    IVX_TRY(stage_out(ctx, mem, WS_OUT_D, out_cov, cap, &oc));
+    Frame f(ctx, mem);
+    IVX_TRY(f.begin(n_out, "null n_out"));
+    IVX_TRY(check_profile_args(f, p));
+    f.drop_plans();
+    f.meter(false, p->dp.steps);
+    u32 *ok = f.out(out_key, cap), *os = f.out(out_start, cap), *oe = f.out(out_end, cap);
+    i32 *oc = f.out(out_cov, cap);
     const bool sizing = cap == 0 && !out_key && !out_start && !out_end && !out_cov;
     u64 m = 0;
-    {
-        KernelTimer t(ctx);
-        ivx_status st = ivx_depth_profile_blocks_device(ctx, p->dp, ok, os, oe, oc, cap, &m);
-        *n_out = m;
-        if (st != IVX_OK) return st;
+    const ivx_status st = f.run([&] { return ivx_depth_profile_blocks_device(ctx, p->dp, ok, os, oe, oc, cap, &m); });
+    *n_out = m;
+    if (st != IVX_OK) return st;
+    if (!sizing) { f.rows_out(m); f.back_all(m); }
+    return f.finish();
+}
+
+// ---- region statistics of a profile.  Where the regions come from: a table of (key, start, end) rows, clipped to the key's
+// domain [pos_lo, key_hi[key]], or n windows of `width` positions of one key from first_pos on, cut at last_pos
+namespace {
+
+struct RegionSrc {
+    bool windows;
+    const u32 *qkey, *qstart, *qend; u32 pos_lo; const u32 *key_hi;         // the table
+    u32 key, first_pos, last_pos, width;                                    // the windows
+    u64 n; int skip_pos0;
+};
+RegionSrc region_table(const u32 *qkey, const u32 *qstart, const u32 *qend, u64 n, u32 pos_lo, const u32 *key_hi, int skip_pos0)
+{
+    return RegionSrc{false, qkey, qstart, qend, pos_lo, key_hi, 0, 0, 0, 0, n, skip_pos0};
+}
+RegionSrc region_windows(u32 key, u32 first_pos, u32 last_pos, u32 width, u64 n, int skip_pos0)
+{
+    return RegionSrc{true, nullptr, nullptr, nullptr, 0, nullptr, key, first_pos, last_pos, width, n, skip_pos0};
+}
+
+// the table's columns on the device (windows: none)
+struct RegionCols { const u32 *key = nullptr, *start = nullptr, *end = nullptr, *hi = nullptr; };
+
+// the checks of the source, after the statistic's own; then the call counts as made (the caller returns if it has no region)
+ivx_status regions_begin(Frame &f, const ivx_index *p, const RegionSrc &r)
+{
+    ivx_ctx *ctx = f.ctx;
+    f.drop_plans();
+    if (r.windows) {
+        if (r.width == 0) return ctx->fail(IVX_ERR_INVALID, "depth profile: window width 0");
+        if (r.key >= p->nkeys) return ctx->fail(IVX_ERR_INVALID, "depth profile: key id >= n_keys");
+        if (r.n && (r.n - 1) > (0xFFFFFFFFull - r.first_pos) / r.width)
+            return ctx->fail(IVX_ERR_INVALID, "depth profile: a window starts beyond position 2^32 - 1");
+    } else {
+        if (r.n && (!r.qstart || !r.qend)) return ctx->fail(IVX_ERR_INVALID, "null coordinate column");
+        if (f.mem == IVX_MEM_DEVICE && ((((uintptr_t)r.qkey) | ((uintptr_t)r.qstart) | ((uintptr_t)r.qend) | ((uintptr_t)r.key_hi)) & 3u))
+            return ctx->fail(IVX_ERR_INVALID, "depth profile: input pointer not aligned to its element size");
     }
-    if (!sizing) {
-        cm.out(m);
-        IVX_TRY(copy_out(ctx, mem, out_key, ok, m));
-        IVX_TRY(copy_out(ctx, mem, out_start, os, m));
-        IVX_TRY(copy_out(ctx, mem, out_end, oe, m));
-        IVX_TRY(copy_out(ctx, mem, out_cov, oc, m));
-    }
-    if (mem == IVX_MEM_HOST) IVX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    f.meter(false, r.n);
     return IVX_OK;
 }
 
-// the checks the two summary calls share, and their three output columns
-static ivx_status summary_check(ivx_ctx *ctx, const ivx_index *p, int mem, const int32_t *thresholds, uint32_t n_thr,
-                                const int64_t *out_len, const int64_t *out_sum, const int64_t *out_ge)
+RegionCols regions_stage(Frame &f, const ivx_index *p, const RegionSrc &r)
 {
-    IVX_TRY(check_profile_args(ctx, p, mem));
+    RegionCols c;
+    if (r.windows) return c;
+    c.key = f.in(r.qkey, r.n); c.start = f.in(r.qstart, r.n); c.end = f.in(r.qend, r.n);
+    c.hi = f.in_at(WS_IN_KEYLEN, r.key_hi, p->nkeys);
+    return c;
+}
+
+// bases, coverage sum and bases at or above each threshold, per region
+ivx_status depth_summary(ivx_ctx *ctx, const ivx_index *p, int mem, const RegionSrc &r, const int32_t *thresholds, uint32_t n_thr,
+                         int64_t *out_len, int64_t *out_sum, int64_t *out_ge)
+{
+    Frame f(ctx, mem);
+    IVX_TRY(f.begin());
+    IVX_TRY(check_profile_args(f, p));
     if (n_thr > IVX_DEPTH_MAX_THRESHOLDS) return ctx->fail(IVX_ERR_INVALID, "depth profile: more than 8 thresholds");
     if (n_thr && !thresholds) return ctx->fail(IVX_ERR_INVALID, "depth profile: null thresholds");
     if (mem == IVX_MEM_DEVICE && ((((uintptr_t)out_len) | ((uintptr_t)out_sum) | ((uintptr_t)out_ge)) & 7u))
         return ctx->fail(IVX_ERR_INVALID, "depth profile: output pointer not aligned to its element size");
-    ctx->sub_plan.valid = false; ctx->join_plan.valid = false;
-    return IVX_OK;
+    IVX_TRY(regions_begin(f, p, r));
+    if (r.n == 0) return IVX_OK;
+    const RegionCols c = regions_stage(f, p, r);
+    i64 *ol = f.out(out_len, r.n), *os = f.out(out_sum, r.n), *og = f.out(out_ge, (u64)n_thr * r.n);
+    IVX_TRY(f.run([&] {
+        return r.windows ? ivx_depth_windows_device(ctx, p->dp, r.key, r.first_pos, r.last_pos, r.width, r.n, r.skip_pos0 != 0, thresholds, n_thr, ol, os, og)
+                         : ivx_depth_regions_device(ctx, p->dp, p->nkeys, c.key, c.start, c.end, r.n, r.pos_lo, c.hi, r.skip_pos0 != 0, thresholds, n_thr, ol, os, og);
+    }));
+    f.rows_out(r.n);
+    f.back_all();
+    return f.finish();
 }
 
-extern "C" ivx_status ivx_depth_profile_summarize(ivx_ctx *ctx, const ivx_index *p, int mem,
-                                                  const uint32_t *qkey, const uint32_t *qstart, const uint32_t *qend, uint64_t n,
-                                                  uint32_t pos_lo, const uint32_t *key_hi, int skip_pos0,
-                                                  const int32_t *thresholds, uint32_t n_thr,
-                                                  int64_t *out_len, int64_t *out_sum, int64_t *out_ge)
+// bases, min, max and the quantiles q_num[j] / q_den of the per-base coverage, per region
+ivx_status depth_ranks(ivx_ctx *ctx, const ivx_index *p, int mem, const RegionSrc &r, const uint32_t *q_num, uint32_t n_q, uint32_t q_den,
+                       int64_t *out_len, int32_t *out_min, int32_t *out_max, int32_t *out_q)
 {
-    if (!ctx) return IVX_ERR_INVALID;
-    IVX_TRY(summary_check(ctx, p, mem, thresholds, n_thr, out_len, out_sum, out_ge));
-    if (n && (!qstart || !qend)) return ctx->fail(IVX_ERR_INVALID, "null coordinate column");
-    if (mem == IVX_MEM_DEVICE && ((((uintptr_t)qkey) | ((uintptr_t)qstart) | ((uintptr_t)qend) | ((uintptr_t)key_hi)) & 3u))
-        return ctx->fail(IVX_ERR_INVALID, "depth profile: input pointer not aligned to its element size");
-    CallMetrics cm(ctx, false, n);
-    if (n == 0) return IVX_OK;
-    const u32 *dk, *ds, *de, *dh; i64 *ol, *os, *og;
-    IVX_TRY(stage_in(ctx, mem, WS_IN_KEY, qkey, n, &dk));
-    IVX_TRY(stage_in(ctx, mem, WS_IN_START, qstart, n, &ds));
-    IVX_TRY(stage_in(ctx, mem, WS_IN_END, qend, n, &de));
-    IVX_TRY(stage_in(ctx, mem, WS_IN_KEYLEN, key_hi, p->nkeys, &dh));
-    IVX_TRY(stage_out(ctx, mem, WS_OUT_A, out_len, n, &ol));
-    IVX_TRY(stage_out(ctx, mem, WS_OUT_B, out_sum, n, &os));
-    IVX_TRY(stage_out(ctx, mem, WS_OUT_C, out_ge, (u64)n_thr * n, &og));
-    {
-        KernelTimer t(ctx);
-        IVX_TRY(ivx_depth_regions_device(ctx, p->dp, p->nkeys, dk, ds, de, n, pos_lo, dh, skip_pos0 != 0, thresholds, n_thr, ol, os, og));
-    }
-    cm.out(n);
-    IVX_TRY(copy_out(ctx, mem, out_len, ol, n));
-    IVX_TRY(copy_out(ctx, mem, out_sum, os, n));
-    IVX_TRY(copy_out(ctx, mem, out_ge, og, (u64)n_thr * n));
-    if (mem == IVX_MEM_HOST) IVX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return IVX_OK;
-}
-
-extern "C" ivx_status ivx_depth_profile_windows(ivx_ctx *ctx, const ivx_index *p, int mem, uint32_t key,
-                                                uint32_t first_pos, uint32_t last_pos, uint32_t width, uint64_t n, int skip_pos0,
-                                                const int32_t *thresholds, uint32_t n_thr,
-                                                int64_t *out_len, int64_t *out_sum, int64_t *out_ge)
-{
-    if (!ctx) return IVX_ERR_INVALID;
-    IVX_TRY(summary_check(ctx, p, mem, thresholds, n_thr, out_len, out_sum, out_ge));
-    if (width == 0) return ctx->fail(IVX_ERR_INVALID, "depth profile: window width 0");
-    if (key >= p->nkeys) return ctx->fail(IVX_ERR_INVALID, "depth profile: key id >= n_keys");
-    if (n && (n - 1) > (0xFFFFFFFFull - first_pos) / width)
-        return ctx->fail(IVX_ERR_INVALID, "depth profile: a window starts beyond position 2^32 - 1");
-    CallMetrics cm(ctx, false, n);
-    if (n == 0) return IVX_OK;
-    i64 *ol, *os, *og;
-    IVX_TRY(stage_out(ctx, mem, WS_OUT_A, out_len, n, &ol));
-    IVX_TRY(stage_out(ctx, mem, WS_OUT_B, out_sum, n, &os));
-    IVX_TRY(stage_out(ctx, mem, WS_OUT_C, out_ge, (u64)n_thr * n, &og));
-    {
-        KernelTimer t(ctx);
-        IVX_TRY(ivx_depth_windows_device(ctx, p->dp, key, first_pos, last_pos, width, n, skip_pos0 != 0, thresholds, n_thr, ol, os, og));
-    }
-    cm.out(n);
-    IVX_TRY(copy_out(ctx, mem, out_len, ol, n));
-    IVX_TRY(copy_out(ctx, mem, out_sum, os, n));
-    IVX_TRY(copy_out(ctx, mem, out_ge, og, (u64)n_thr * n));
-    if (mem == IVX_MEM_HOST) IVX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return IVX_OK;
-}
-
-// the checks the two order-statistics calls share, and their four output columns
-static ivx_status ranks_check(ivx_ctx *ctx, const ivx_index *p, int mem, const uint32_t *q_num, uint32_t n_q, uint32_t q_den,
-                              const int64_t *out_len, const int32_t *out_min, const int32_t *out_max, const int32_t *out_q)
-{
-    IVX_TRY(check_profile_args(ctx, p, mem));
+    Frame f(ctx, mem);
+    IVX_TRY(f.begin());
+    IVX_TRY(check_profile_args(f, p));
     if (n_q > IVX_DEPTH_MAX_QUANTILES) return ctx->fail(IVX_ERR_INVALID, "depth profile: more than 8 quantiles");
     if (n_q && !q_num) return ctx->fail(IVX_ERR_INVALID, "depth profile: null q_num");
     if (q_den == 0 || q_den > 65536u) return ctx->fail(IVX_ERR_INVALID, "depth profile: q_den outside 1 .. 65536");
@@ -1672,8 +1401,37 @@ static ivx_status ranks_check(ivx_ctx *ctx, const ivx_index *p, int mem, const u
         if (q_num[j] > q_den) return ctx->fail(IVX_ERR_INVALID, "depth profile: a q_num above q_den");
     if (mem == IVX_MEM_DEVICE && ((((uintptr_t)out_len) & 7u) || ((((uintptr_t)out_min) | ((uintptr_t)out_max) | ((uintptr_t)out_q)) & 3u)))
         return ctx->fail(IVX_ERR_INVALID, "depth profile: output pointer not aligned to its element size");
-    ctx->sub_plan.valid = false; ctx->join_plan.valid = false;
-    return IVX_OK;
+    IVX_TRY(regions_begin(f, p, r));
+    if (r.n == 0) return IVX_OK;
+    const RegionCols c = regions_stage(f, p, r);
+    i64 *ol = f.out(out_len, r.n);
+    i32 *omn = f.out(out_min, r.n), *omx = f.out(out_max, r.n), *oq = f.out(out_q, (u64)n_q * r.n);
+    IVX_TRY(f.run([&] {
+        return r.windows ? ivx_depth_window_ranks_device(ctx, p->dp, r.key, r.first_pos, r.last_pos, r.width, r.n, r.skip_pos0 != 0, q_num, n_q, q_den, ol, omn, omx, oq)
+                         : ivx_depth_region_ranks_device(ctx, p->dp, p->nkeys, c.key, c.start, c.end, r.n, r.pos_lo, c.hi, r.skip_pos0 != 0, q_num, n_q, q_den, ol, omn, omx, oq);
+    }));
+    f.rows_out(r.n);
+    f.back_all();
+    return f.finish();
+}
+
+}  // namespace
+
+extern "C" ivx_status ivx_depth_profile_summarize(ivx_ctx *ctx, const ivx_index *p, int mem,
+                                                  const uint32_t *qkey, const uint32_t *qstart, const uint32_t *qend, uint64_t n,
+                                                  uint32_t pos_lo, const uint32_t *key_hi, int skip_pos0,
+                                                  const int32_t *thresholds, uint32_t n_thr,
+                                                  int64_t *out_len, int64_t *out_sum, int64_t *out_ge)
+{
+    return depth_summary(ctx, p, mem, region_table(qkey, qstart, qend, n, pos_lo, key_hi, skip_pos0), thresholds, n_thr, out_len, out_sum, out_ge);
+}
+
+extern "C" ivx_status ivx_depth_profile_windows(ivx_ctx *ctx, const ivx_index *p, int mem, uint32_t key,
+                                                uint32_t first_pos, uint32_t last_pos, uint32_t width, uint64_t n, int skip_pos0,
+                                                const int32_t *thresholds, uint32_t n_thr,
+                                                int64_t *out_len, int64_t *out_sum, int64_t *out_ge)
+{
+    return depth_summary(ctx, p, mem, region_windows(key, first_pos, last_pos, width, n, skip_pos0), thresholds, n_thr, out_len, out_sum, out_ge);
 }
 
 extern "C" ivx_status ivx_depth_profile_quantiles(ivx_ctx *ctx, const ivx_index *p, int mem,
@@ -1682,33 +1440,7 @@ extern "C" ivx_status ivx_depth_profile_quantiles(ivx_ctx *ctx, const ivx_index 
                                                   const uint32_t *q_num, uint32_t n_q, uint32_t q_den,
                                                   int64_t *out_len, int32_t *out_min, int32_t *out_max, int32_t *out_q)
 {
-    if (!ctx) return IVX_ERR_INVALID;
-    IVX_TRY(ranks_check(ctx, p, mem, q_num, n_q, q_den, out_len, out_min, out_max, out_q));
-    if (n && (!qstart || !qend)) return ctx->fail(IVX_ERR_INVALID, "null coordinate column");
-    if (mem == IVX_MEM_DEVICE && ((((uintptr_t)qkey) | ((uintptr_t)qstart) | ((uintptr_t)qend) | ((uintptr_t)key_hi)) & 3u))
-        return ctx->fail(IVX_ERR_INVALID, "depth profile: input pointer not aligned to its element size");
-    CallMetrics cm(ctx, false, n);
-    if (n == 0) return IVX_OK;
-    const u32 *dk, *ds, *de, *dh; i64 *ol; i32 *omn, *omx, *oq;
-    IVX_TRY(stage_in(ctx, mem, WS_IN_KEY, qkey, n, &dk));
-    IVX_TRY(stage_in(ctx, mem, WS_IN_START, qstart, n, &ds));
-    IVX_TRY(stage_in(ctx, mem, WS_IN_END, qend, n, &de));
-    IVX_TRY(stage_in(ctx, mem, WS_IN_KEYLEN, key_hi, p->nkeys, &dh));
-    IVX_TRY(stage_out(ctx, mem, WS_OUT_A, out_len, n, &ol));
-    IVX_TRY(stage_out(ctx, mem, WS_OUT_B, out_min, n, &omn));
-    IVX_TRY(stage_out(ctx, mem, WS_OUT_C, out_max, n, &omx));
-    IVX_TRY(stage_out(ctx, mem, WS_OUT_D, out_q, (u64)n_q * n, &oq));
-    {
-        KernelTimer t(ctx);
-        IVX_TRY(ivx_depth_region_ranks_device(ctx, p->dp, p->nkeys, dk, ds, de, n, pos_lo, dh, skip_pos0 != 0, q_num, n_q, q_den, ol, omn, omx, oq));
-    }
-    cm.out(n);
-    IVX_TRY(copy_out(ctx, mem, out_len, ol, n));
-    IVX_TRY(copy_out(ctx, mem, out_min, omn, n));
-    IVX_TRY(copy_out(ctx, mem, out_max, omx, n));
-    IVX_TRY(copy_out(ctx, mem, out_q, oq, (u64)n_q * n));
-    if (mem == IVX_MEM_HOST) IVX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return IVX_OK;
+    return depth_ranks(ctx, p, mem, region_table(qkey, qstart, qend, n, pos_lo, key_hi, skip_pos0), q_num, n_q, q_den, out_len, out_min, out_max, out_q);
 }
 
 extern "C" ivx_status ivx_depth_profile_window_quantiles(ivx_ctx *ctx, const ivx_index *p, int mem, uint32_t key,
@@ -1716,170 +1448,104 @@ extern "C" ivx_status ivx_depth_profile_window_quantiles(ivx_ctx *ctx, const ivx
                                                          const uint32_t *q_num, uint32_t n_q, uint32_t q_den,
                                                          int64_t *out_len, int32_t *out_min, int32_t *out_max, int32_t *out_q)
 {
-    if (!ctx) return IVX_ERR_INVALID;
-    IVX_TRY(ranks_check(ctx, p, mem, q_num, n_q, q_den, out_len, out_min, out_max, out_q));
-    if (width == 0) return ctx->fail(IVX_ERR_INVALID, "depth profile: window width 0");
-    if (key >= p->nkeys) return ctx->fail(IVX_ERR_INVALID, "depth profile: key id >= n_keys");
-    if (n && (n - 1) > (0xFFFFFFFFull - first_pos) / width)
-        return ctx->fail(IVX_ERR_INVALID, "depth profile: a window starts beyond position 2^32 - 1");
-    CallMetrics cm(ctx, false, n);
-    if (n == 0) return IVX_OK;
-    i64 *ol; i32 *omn, *omx, *oq;
-    IVX_TRY(stage_out(ctx, mem, WS_OUT_A, out_len, n, &ol));
-    IVX_TRY(stage_out(ctx, mem, WS_OUT_B, out_min, n, &omn));
-    IVX_TRY(stage_out(ctx, mem, WS_OUT_C, out_max, n, &omx));
-    IVX_TRY(stage_out(ctx, mem, WS_OUT_D, out_q, (u64)n_q * n, &oq));
-    {
-        KernelTimer t(ctx);
-        IVX_TRY(ivx_depth_window_ranks_device(ctx, p->dp, key, first_pos, last_pos, width, n, skip_pos0 != 0, q_num, n_q, q_den, ol, omn, omx, oq));
-    }
-    cm.out(n);
-    IVX_TRY(copy_out(ctx, mem, out_len, ol, n));
-    IVX_TRY(copy_out(ctx, mem, out_min, omn, n));
-    IVX_TRY(copy_out(ctx, mem, out_max, omx, n));
-    IVX_TRY(copy_out(ctx, mem, out_q, oq, (u64)n_q * n));
-    if (mem == IVX_MEM_HOST) IVX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return IVX_OK;
+    return depth_ranks(ctx, p, mem, region_windows(key, first_pos, last_pos, width, n, skip_pos0), q_num, n_q, q_den, out_len, out_min, out_max, out_q);
 }
+
+// ---------------------------------------------------------------- f3: take / scatter of payload columns
 
 extern "C" ivx_status ivx_take_fixed(ivx_ctx *ctx, int mem, const void *src, uint32_t width, uint64_t n_src,
                                      const uint8_t *src_valid_bits, const uint32_t *idx, uint64_t n, void *out, uint8_t *out_valid)
 {
-    if (!ctx) return IVX_ERR_INVALID;
-    if (mem != IVX_MEM_HOST && mem != IVX_MEM_DEVICE) return ctx->fail(IVX_ERR_INVALID, "bad mem");
+    Frame f(ctx, mem);
+    IVX_TRY(f.enter());
     if (n && (!idx || !out)) return ctx->fail(IVX_ERR_INVALID, "take: null idx or out");
     if (n_src && !src) return ctx->fail(IVX_ERR_INVALID, "take: null source column");
     if (width == 0 || width > 32 || (width & (width - 1))) return ctx->fail(IVX_ERR_UNSUPPORTED, "take: fixed width must be 1, 2, 4, 8, 16 or 32 bytes");
-    IVX_HIP(ctx, hipSetDevice(ctx->device));
-    const u8 *dsrc, *dvalid; const u32 *didx; u8 *dout, *dov;
-    IVX_TRY(stage_in(ctx, mem, WS_IN_KEY, (const u8 *)src, n_src * width, &dsrc));
-    IVX_TRY(stage_in(ctx, mem, WS_IN_START, src_valid_bits, (n_src + 7) / 8, &dvalid));
-    IVX_TRY(stage_in(ctx, mem, WS_IN_END, idx, n, &didx));
-    IVX_TRY(stage_out(ctx, mem, WS_OUT_A, (u8 *)out, n * width, &dout));
-    IVX_TRY(stage_out(ctx, mem, WS_OUT_B, out_valid, n, &dov));
-    {
-        KernelTimer t(ctx);
-        IVX_TRY(ivx_take_fixed_device(ctx, dsrc, width, n_src, dvalid, didx, n, dout, dov));
-    }
-    IVX_TRY(copy_out(ctx, mem, (u8 *)out, dout, n * width));
-    IVX_TRY(copy_out(ctx, mem, out_valid, dov, n));
-    if (mem == IVX_MEM_HOST) IVX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return IVX_OK;
+    const u8 *dsrc = f.in((const u8 *)src, n_src * width), *dvalid = f.in(src_valid_bits, (n_src + 7) / 8);
+    const u32 *didx = f.in(idx, n);
+    u8 *dout = f.out((u8 *)out, n * width), *dov = f.out(out_valid, n);
+    IVX_TRY(f.run([&] { return ivx_take_fixed_device(ctx, dsrc, width, n_src, dvalid, didx, n, dout, dov); }));
+    f.back_all();
+    return f.finish();
 }
-
-ivx_status ivx_scatter_fixed_device(ivx_ctx *ctx, const void *src, u32 width, const u32 *idx, u64 n, void *out, u64 n_out);
 
 extern "C" ivx_status ivx_scatter_fixed(ivx_ctx *ctx, int mem, const void *src, uint32_t width, const uint32_t *idx, uint64_t n,
                                         void *out, uint64_t n_out)
 {
-    if (!ctx) return IVX_ERR_INVALID;
-    if (mem != IVX_MEM_HOST && mem != IVX_MEM_DEVICE) return ctx->fail(IVX_ERR_INVALID, "bad mem");
+    Frame f(ctx, mem);
+    IVX_TRY(f.enter());
     if (n && (!idx || !src || !out)) return ctx->fail(IVX_ERR_INVALID, "scatter: null src, idx or out");
     if (width == 0 || width > 32 || (width & (width - 1))) return ctx->fail(IVX_ERR_UNSUPPORTED, "scatter: fixed width must be 1, 2, 4, 8, 16 or 32 bytes");
-    IVX_HIP(ctx, hipSetDevice(ctx->device));
-    const u8 *dsrc; const u32 *didx; u8 *dout;
-    IVX_TRY(stage_in(ctx, mem, WS_IN_KEY, (const u8 *)src, n * width, &dsrc));
-    IVX_TRY(stage_in(ctx, mem, WS_IN_END, idx, n, &didx));
-    IVX_TRY(stage_out(ctx, mem, WS_OUT_A, (u8 *)out, n_out * width, &dout));
+    const u8 *dsrc = f.in((const u8 *)src, n * width);
+    const u32 *didx = f.in_at(WS_IN_END, idx, n);
+    u8 *dout = f.out((u8 *)out, n_out * width);
+    IVX_TRY(f.st);
     // host mode: rows that no index names keep what the caller's buffer holds
     if (mem == IVX_MEM_HOST && n_out) IVX_HIP(ctx, hipMemcpyAsync(dout, out, (size_t)n_out * width, hipMemcpyHostToDevice, ctx->stream));
-    {
-        KernelTimer t(ctx);
-        IVX_TRY(ivx_scatter_fixed_device(ctx, dsrc, width, didx, n, dout, n_out));
-    }
-    IVX_TRY(copy_out(ctx, mem, (u8 *)out, dout, n_out * width));
-    if (mem == IVX_MEM_HOST) IVX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return IVX_OK;
+    IVX_TRY(f.run([&] { return ivx_scatter_fixed_device(ctx, dsrc, width, didx, n, dout, n_out); }));
+    f.back_all();
+    return f.finish();
 }
 
 extern "C" ivx_status ivx_take_utf8(ivx_ctx *ctx, int mem, int large, const void *offsets, const uint8_t *data, uint64_t n_src,
                                     uint64_t src_data_bytes, const uint8_t *src_valid_bits, const uint32_t *idx, uint64_t n,
                                     void *out_offsets, uint8_t *out_data, uint64_t data_cap, uint64_t *data_bytes, uint8_t *out_valid)
 {
-    if (!ctx) return IVX_ERR_INVALID;
-    if (!data_bytes) return ctx->fail(IVX_ERR_INVALID, "null data_bytes");
-    *data_bytes = 0;
-    if (mem != IVX_MEM_HOST && mem != IVX_MEM_DEVICE) return ctx->fail(IVX_ERR_INVALID, "bad mem");
+    Frame f(ctx, mem);
+    IVX_TRY(f.enter(data_bytes, "null data_bytes"));
     if (n && !idx) return ctx->fail(IVX_ERR_INVALID, "take: null idx");
     if (!offsets || (src_data_bytes && !data)) return ctx->fail(IVX_ERR_INVALID, "take: null source column");
-    IVX_HIP(ctx, hipSetDevice(ctx->device));
     const size_t ow = large ? 8 : 4;
-    const u8 *doff, *ddata, *dvalid; const u32 *didx; u8 *dooff, *dodata, *dov;
-    IVX_TRY(stage_in(ctx, mem, WS_IN_KEY, (const u8 *)offsets, (n_src + 1) * ow, &doff));
-    IVX_TRY(stage_in(ctx, mem, WS_IN_START, data, src_data_bytes, &ddata));
-    IVX_TRY(stage_in(ctx, mem, WS_IN_END, src_valid_bits, (n_src + 7) / 8, &dvalid));
-    IVX_TRY(stage_in(ctx, mem, WS_IN2_KEY, idx, n, &didx));
-    IVX_TRY(stage_out(ctx, mem, WS_OUT_A, (u8 *)out_offsets, (n + 1) * ow, &dooff));
-    IVX_TRY(stage_out(ctx, mem, WS_OUT_B, out_data, data_cap, &dodata));
-    IVX_TRY(stage_out(ctx, mem, WS_OUT_C, out_valid, n, &dov));
+    const u8 *doff = f.in((const u8 *)offsets, (n_src + 1) * ow), *ddata = f.in(data, src_data_bytes), *dvalid = f.in(src_valid_bits, (n_src + 7) / 8);
+    const u32 *didx = f.in(idx, n);
+    u8 *dooff = f.out((u8 *)out_offsets, (n + 1) * ow), *dodata = f.out(out_data, data_cap), *dov = f.out(out_valid, n);
     u64 total = 0;
-    ivx_status st;
-    {
-        KernelTimer t(ctx);
-        st = ivx_take_utf8_device(ctx, large, doff, ddata, n_src, dvalid, didx, n, dooff, dodata, data_cap, &total, dov);
-        *data_bytes = total;
-    }
+    const ivx_status st = f.run([&] { return ivx_take_utf8_device(ctx, large, doff, ddata, n_src, dvalid, didx, n, dooff, dodata, data_cap, &total, dov); });
+    *data_bytes = total;
     // a short data buffer leaves the offsets and out_valid final (the device has written them): they go out as in device mode
     if (st != IVX_OK && st != IVX_ERR_CAPACITY) return st;
-    IVX_TRY(copy_out(ctx, mem, (u8 *)out_offsets, dooff, (n + 1) * ow));
-    if (st == IVX_ERR_CAPACITY) {
-        IVX_TRY(copy_out(ctx, mem, out_valid, dov, n));
-        if (mem == IVX_MEM_HOST) IVX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        return st;
-    }
-    if (out_data) IVX_TRY(copy_out(ctx, mem, out_data, dodata, total));
-    IVX_TRY(copy_out(ctx, mem, out_valid, dov, n));
-    if (mem == IVX_MEM_HOST) IVX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return IVX_OK;
+    f.back((u8 *)out_offsets);
+    if (st == IVX_ERR_CAPACITY) f.withhold(out_data);
+    else f.back(out_data, total);
+    f.back(out_valid);
+    const ivx_status fin = f.finish();
+    return fin != IVX_OK ? fin : st;
 }
 
 extern "C" ivx_status ivx_take_bits(ivx_ctx *ctx, int mem, const uint8_t *src_bits, uint64_t n_src, const uint8_t *src_valid_bits,
                                     const uint32_t *idx, uint64_t n, uint8_t *out_bits, uint8_t *out_valid)
 {
-    if (!ctx) return IVX_ERR_INVALID;
-    if (mem != IVX_MEM_HOST && mem != IVX_MEM_DEVICE) return ctx->fail(IVX_ERR_INVALID, "bad mem");
+    Frame f(ctx, mem);
+    IVX_TRY(f.enter());
     if (n && (!idx || !out_bits)) return ctx->fail(IVX_ERR_INVALID, "take: null idx or out");
     if (n_src && !src_bits) return ctx->fail(IVX_ERR_INVALID, "take: null source column");
-    IVX_HIP(ctx, hipSetDevice(ctx->device));
-    const u8 *dsrc, *dvalid; const u32 *didx; u8 *dout, *dov;
-    IVX_TRY(stage_in(ctx, mem, WS_IN_KEY, src_bits, (n_src + 7) / 8, &dsrc));
-    IVX_TRY(stage_in(ctx, mem, WS_IN_START, src_valid_bits, (n_src + 7) / 8, &dvalid));
-    IVX_TRY(stage_in(ctx, mem, WS_IN_END, idx, n, &didx));
-    IVX_TRY(stage_out(ctx, mem, WS_OUT_A, out_bits, (n + 7) / 8, &dout));
-    IVX_TRY(stage_out(ctx, mem, WS_OUT_B, out_valid, n, &dov));
-    {
-        KernelTimer t(ctx);
-        IVX_TRY(ivx_take_bits_device(ctx, dsrc, n_src, dvalid, didx, n, dout, dov));
-    }
-    IVX_TRY(copy_out(ctx, mem, out_bits, dout, (n + 7) / 8));
-    IVX_TRY(copy_out(ctx, mem, out_valid, dov, n));
-    if (mem == IVX_MEM_HOST) IVX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return IVX_OK;
+    const u8 *dsrc = f.in(src_bits, (n_src + 7) / 8), *dvalid = f.in(src_valid_bits, (n_src + 7) / 8);
+    const u32 *didx = f.in(idx, n);
+    u8 *dout = f.out(out_bits, (n + 7) / 8), *dov = f.out(out_valid, n);
+    IVX_TRY(f.run([&] { return ivx_take_bits_device(ctx, dsrc, n_src, dvalid, didx, n, dout, dov); }));
+    f.back_all();
+    return f.finish();
 }
 
 extern "C" ivx_status ivx_take_view(ivx_ctx *ctx, int mem, const void *views, const uint8_t *const *data_bufs, const uint64_t *data_buf_bytes,
                                     uint32_t n_bufs, uint64_t n_src, const uint8_t *src_valid_bits, const uint32_t *idx, uint64_t n,
                                     void *out_views, uint8_t *out_data, uint64_t data_cap, uint64_t *data_bytes, uint8_t *out_valid)
 {
-    if (!ctx) return IVX_ERR_INVALID;
-    if (!data_bytes) return ctx->fail(IVX_ERR_INVALID, "null data_bytes");
-    *data_bytes = 0;
-    if (mem != IVX_MEM_HOST && mem != IVX_MEM_DEVICE) return ctx->fail(IVX_ERR_INVALID, "bad mem");
+    Frame f(ctx, mem);
+    IVX_TRY(f.enter(data_bytes, "null data_bytes"));
     if (n && !idx) return ctx->fail(IVX_ERR_INVALID, "take: null idx");
     if ((n_src && !views) || (n_bufs && (!data_bufs || !data_buf_bytes))) return ctx->fail(IVX_ERR_INVALID, "take: null source column");
     if (n_bufs > 4096) return ctx->fail(IVX_ERR_UNSUPPORTED, "take: more than 4096 view data buffers");
-    IVX_HIP(ctx, hipSetDevice(ctx->device));
-    const u8 *dviews, *dvalid; const u32 *didx; u8 *doviews, *dodata, *dov;
-    IVX_TRY(stage_in(ctx, mem, WS_IN_KEY, (const u8 *)views, n_src * 16, &dviews));
-    IVX_TRY(stage_in(ctx, mem, WS_IN_START, src_valid_bits, (n_src + 7) / 8, &dvalid));
-    IVX_TRY(stage_in(ctx, mem, WS_IN_END, idx, n, &didx));
+    const u8 *dviews = f.in((const u8 *)views, n_src * 16), *dvalid = f.in(src_valid_bits, (n_src + 7) / 8);
+    const u32 *didx = f.in(idx, n);
+    IVX_TRY(f.st);
     // the variadic data buffers: device pointers in one small device table (host mode: one staging area for all)
     std::vector<const u8 *> ptrs(n_bufs ? n_bufs : 1, nullptr);
     if (mem == IVX_MEM_HOST) {
         u64 tot = 0;
         for (u32 b = 0; b < n_bufs; b++) tot += (data_buf_bytes[b] + 15) & ~15ull;
         u8 *area;
-        IVX_TRY(ctx->get_scratch(WS_IN2_START, tot ? tot : 16, (void **)&area));
+        IVX_TRY(f.scratch_at(WS_IN2_START, tot ? tot : 16, (void **)&area));
         u64 at = 0;
         for (u32 b = 0; b < n_bufs; b++) {
             if (data_buf_bytes[b]) IVX_HIP(ctx, hipMemcpyAsync(area + at, data_bufs[b], data_buf_bytes[b], hipMemcpyHostToDevice, ctx->stream));
@@ -1890,22 +1556,18 @@ extern "C" ivx_status ivx_take_view(ivx_ctx *ctx, int mem, const void *views, co
         for (u32 b = 0; b < n_bufs; b++) ptrs[b] = data_bufs[b];
     }
     const u8 **dtable;
-    IVX_TRY(ctx->get_scratch(WS_IN2_KEY, ptrs.size() * sizeof(u8 *), (void **)&dtable));
+    IVX_TRY(f.scratch_at(WS_IN2_KEY, ptrs.size() * sizeof(u8 *), (void **)&dtable));
     IVX_HIP(ctx, hipMemcpyAsync(dtable, ptrs.data(), ptrs.size() * sizeof(u8 *), hipMemcpyHostToDevice, ctx->stream));
     IVX_HIP(ctx, hipStreamSynchronize(ctx->stream));                            // `ptrs` is pageable host memory
-    IVX_TRY(stage_out(ctx, mem, WS_OUT_A, (u8 *)out_views, n * 16, &doviews));
-    IVX_TRY(stage_out(ctx, mem, WS_OUT_B, out_data, data_cap, &dodata));
-    IVX_TRY(stage_out(ctx, mem, WS_OUT_C, out_valid, n, &dov));
+    u8 *doviews = f.out((u8 *)out_views, n * 16), *dodata = f.out(out_data, data_cap), *dov = f.out(out_valid, n);
     u64 total = 0;
-    {
-        KernelTimer t(ctx);
-        ivx_status st = ivx_take_view_device(ctx, dviews, dtable, n_src, dvalid, didx, n, doviews, dodata, data_cap, &total, dov);
-        *data_bytes = total;
-        if (st != IVX_OK) return st;
-    }
-    if (out_views && (out_data || total == 0)) IVX_TRY(copy_out(ctx, mem, (u8 *)out_views, doviews, n * 16));
-    if (out_data) IVX_TRY(copy_out(ctx, mem, out_data, dodata, total));
-    IVX_TRY(copy_out(ctx, mem, out_valid, dov, n));
-    if (mem == IVX_MEM_HOST) IVX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return IVX_OK;
+    const ivx_status st = f.run([&] { return ivx_take_view_device(ctx, dviews, dtable, n_src, dvalid, didx, n, doviews, dodata, data_cap, &total, dov); });
+    *data_bytes = total;
+    if (st != IVX_OK) return st;
+    // a sizing call that was given out_views: the views go out only with the data they point into
+    if (out_data || total == 0) f.back((u8 *)out_views);
+    else f.withhold((u8 *)out_views);
+    f.back(out_data, total);
+    f.back(out_valid);
+    return f.finish();
 }
