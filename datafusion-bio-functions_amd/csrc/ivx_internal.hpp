@@ -123,6 +123,7 @@ struct ivx_ctx {
     u64 hdr_mirror_serial = 0;          // the index whose header that is (its HDR_SLOW arrives with the build's tail: ivx_join_probe_regions)
     ivx_sub_plan sub_plan;
     ivx_join_plan join_plan;
+    u32 sweep_form[16] = {};            // IVX_SWEEP_* (below): what the last sweep's sort and packed sweep decided on the host (test hook)
     ivx_metrics metrics{};              // BuildProbeJoinMetrics, see ivx.h
     u64 mem_limit = 0;                  // device bytes of scratch + the index being built (0 = unlimited)
     u64 fill_hint = 0;                  // pairs a fill call should expect instead of its cap (a chunk of a host-resident batch writes into the whole batch's buffers)
@@ -312,6 +313,18 @@ enum { IVX_NEAR_FB_NOFIT = 1 /* the one-word form did not fit 64 bits */, IVX_NE
 // then (shift, cells) of up to three rank grids -- count: starts, ends; coverage: first, last; nearest: by_start, by_end, pmax
 enum { IVX_FORMS_KIND = 0, IVX_FORMS_NROUTE_NREG = 1, IVX_FORMS_NEAR_WORDS = 2, IVX_FORMS_NEAR_ORDER = 3, IVX_FORMS_NEAR_FALLBACK = 4,
        IVX_FORMS_GRID0 = 5, IVX_FORMS_WORDS = 11 };
+// words of ivx_debug_sweep_form (ivx_sweep.hip; tests only, not in include/ivx.h): the decisions the last sort64 of a sweep's
+// input rows (ivx_sweep.hip) and the packed sweep behind it (ivx_runs.hip runs_packed) took ON THE HOST -- nothing is written by
+// a kernel.  merge / cluster / complement clear them at entry; after a subtract they describe its last sort64 call.
+enum { IVX_SWEEP_SORT_WORDS = 0 /* words of the radix sort that ran: 0 none, 1, 3 */, IVX_SWEEP_NW = 1 /* words the sort key takes: 1 or 3 */,
+       IVX_SWEEP_LIN = 2, IVX_SWEEP_BITS_S = 3, IVX_SWEEP_BITS_E = 4, IVX_SWEEP_BITS_K = 5,
+       IVX_SWEEP_SORTED_IN = 6 /* the rows were taken as already in order */, IVX_SWEEP_TWO_STEP = 7 /* sort on (key, start), equal starts repaired: tried */,
+       IVX_SWEEP_TOOLONG = 8 /* ... and left for the full sort after a run above FIX_MAXRUN */,
+       IVX_SWEEP_NARROW_ROWS = 9 /* the sweep's rows are 32-bit offsets */, IVX_SWEEP_K8 = 10 /* ... with one-byte keys */,
+       IVX_SWEEP_PACKED = 11 /* 0 the sweep reads rows, 1 packed words instead of rows, 2 packed words beside rows (cluster) */,
+       IVX_SWEEP_NARROW_RUNS = 12 /* k_pk_runs<..., NARROW = true> */, IVX_SWEEP_NTILE = 13 /* tiles of the packed sweep */,
+       IVX_SWEEP_WORDS = 14 };
+static_assert(IVX_SWEEP_WORDS <= sizeof(ivx_ctx::sweep_form) / sizeof(u32), "ivx_ctx::sweep_form holds the IVX_SWEEP_* words");
 
 // ---------------------------------------------------------------- internal API
 // scan.hip

@@ -645,6 +645,7 @@ ivx_status runs_packed(ivx_ctx *ctx, const u64 *w, u64 n, const Pack64 &p, i64 m
     for (u64 x = p.nkeys ? p.nkeys - 1 : 0; x; x >>= 1) bk++;
     const bool narrow = p.small && p.bits_e <= 32 && (LIN ? p.bits_s <= 32 : p.bits_s + bk <= 32) &&
                         min_dist < (1ll << 61) && !getenv("IVX_NO_NARROW_RUNS");
+    ctx->sweep_form[IVX_SWEEP_NARROW_RUNS] = narrow; ctx->sweep_form[IVX_SWEEP_NTILE] = (u32)ntile;   // (test hook ivx_debug_sweep_form)
     const PkCluster none{nullptr, nullptr, nullptr, nullptr, nullptr};
     const dim3 grid((u32)ntile), blk(FT);
     const u64 *pre1 = agg, *pre2 = agg + ntile;

@@ -352,10 +352,14 @@ u32 bits_of(u64 x) { u32 b = 0; while (x) { b++; x >>= 1; } return b; }
 // nothing is unpacked then; without (cluster) the rows are unpacked as always and pk->w stays valid beside them.
 struct PackedWant { i64 d; int strict; bool ok; const u64 *w; Pack64 p; };
 ivx_status sort64(ivx_ctx *ctx, int slot_a, int slot_b, const u32 *key, const i64 *s, const i64 *e, u64 n, u32 nkeys,
-                  u32 *ks, i64 *ss, i64 *es, u32 *rows, SortedRows *sw = nullptr, PackedWant *pk = nullptr)
+                  u32 *ks, i64 *ss, i64 *es, u32 *rows, SortedRows *sw = nullptr, PackedWant *pk = nullptr, bool note = true)
 {
     if (sw) { *sw = SortedRows{}; sw->ks = ks; sw->ss = ss; sw->es = es; }
     if (pk) pk->ok = false;
+    // note: this call's decisions go to ctx->sweep_form (IVX_SWEEP_*, the test hook ivx_debug_sweep_form); f_: nowhere
+    u32 f_[IVX_SWEEP_WORDS];
+    u32 *const form = note ? ctx->sweep_form : f_;
+    for (int i = 0; i < IVX_SWEEP_WORDS; i++) form[i] = 0;
     if (n == 0) return IVX_OK;
     bool narrow = sw != nullptr && rows == nullptr && !getenv("IVX_NO_NARROW_SWEEP");
     hipStream_t st = ctx->stream;
@@ -406,6 +410,7 @@ ivx_status sort64(ivx_ctx *ctx, int slot_a, int slot_b, const u32 *key, const i6
     // packed: one 64-bit sort word, plus the row ids -- a 32-bit payload -- only when the caller wants them back (merge /
     // complement / the right side of subtract do not: equal words are equal rows, and the record is 8 bytes instead of 12)
     const int nw = total <= 64 ? 1 : 3;
+    form[IVX_SWEEP_NW] = (u32)nw; form[IVX_SWEEP_LIN] = p.lin; form[IVX_SWEEP_BITS_S] = p.bits_s; form[IVX_SWEEP_BITS_E] = p.bits_e; form[IVX_SWEEP_BITS_K] = bits_k;
     // (the packed sweep takes sorted input as well: one pack pass instead of a 20-byte copy and three passes over wide rows)
     const bool packed = nw == 1 && pk && sw && !rows && !getenv("IVX_NO_FUSED_SWEEP") &&
                         ivx_merge_packed_ok(p, n, nkeys, pk->d, pk->strict, (r.odd & 1) != 0, (r.odd & 2) != 0);
@@ -413,6 +418,7 @@ ivx_status sort64(ivx_ctx *ctx, int slot_a, int slot_b, const u32 *key, const i6
     const bool also = nw == 1 && pk && !sw && !getenv("IVX_NO_FUSED_SWEEP") &&
                       ivx_merge_packed_ok(p, n, nkeys, pk->d, pk->strict, (r.odd & 1) != 0, (r.odd & 2) != 0);
     if (packed && (r.odd & 4) == 0 && !getenv("IVX_FORCE_SORT")) sorted_in = true;
+    form[IVX_SWEEP_SORTED_IN] = sorted_in; form[IVX_SWEEP_PACKED] = packed ? 1u : (also ? 2u : 0u);
     if (sorted_in && !packed) {
         hipLaunchKernelGGL(k_copy_sorted, dim3(grid1(n)), dim3(ST), 0, st, key, s, e, n, ks, ss, es, rows);
         if (also) {
@@ -426,6 +432,7 @@ ivx_status sort64(ivx_ctx *ctx, int slot_a, int slot_b, const u32 *key, const i6
     }
     narrow = narrow && nw == 1 && (u64)r.max_s - (u64)r.min_s <= 0xFFFFFFFFull && (u64)r.max_e - (u64)r.min_e <= 0xFFFFFFFFull;
     const bool k8 = narrow && nkeys <= 256 && !getenv("IVX_NO_K8");
+    form[IVX_SWEEP_NARROW_ROWS] = narrow; form[IVX_SWEEP_K8] = k8;
     if (narrow) { sw->s32 = (const u32 *)ss; sw->e32 = (const u32 *)es; sw->min_s = r.min_s; sw->min_e = r.min_e; if (k8) sw->k8 = (const u8 *)ks; }
     for (int q = 0; q < nw; q++) {
         IVX_TRY(ctx->get_scratch(slot_a + q, n * sizeof(u64), (void **)&a[q]));
@@ -455,6 +462,7 @@ ivx_status sort64(ivx_ctx *ctx, int slot_a, int slot_b, const u32 *key, const i6
             const ivx_sort_field f[1] = {{0, lo, lo + (int)((total - p.bits_e + 7) / 8 * 8)}};
             IVX_TRY(pack_for_sort(lo, nullptr));
             IVX_TRY(ivx_radix_sort(ctx, 1, a, b, n, f, 1, &in_b, true, nullptr, f[0].hi > f[0].lo && pack_counts));
+            form[IVX_SWEEP_SORT_WORDS] = 1;
         }
         pk->ok = true; pk->w = in_b ? b[0] : a[0]; pk->p = p;
         IVX_HIP(ctx, hipGetLastError());
@@ -470,6 +478,7 @@ ivx_status sort64(ivx_ctx *ctx, int slot_a, int slot_b, const u32 *key, const i6
         const bool ks_sorted = (r.odd & 4) == 0 && !getenv("IVX_FORCE_SORT");
         bool two_step = ks_sorted || (p.bits_e >= 8 && n >= (1u << 16) && per_pos <= 0.25 && !getenv("IVX_FORCE_SORT"));
         u64 *const *o = a;
+        form[IVX_SWEEP_TWO_STEP] = two_step;
         if (two_step) {
             const int lo = (int)p.bits_e;
             const ivx_sort_field f[1] = {{0, lo, lo + (int)((total - p.bits_e + 7) / 8 * 8)}};
@@ -477,6 +486,7 @@ ivx_status sort64(ivx_ctx *ctx, int slot_a, int slot_b, const u32 *key, const i6
             else {
                 IVX_TRY(pack_for_sort(lo, pay[0]));
                 IVX_TRY(ivx_radix_sort(ctx, 1, a, b, n, f, 1, &in_b, true, with_rows ? pay : nullptr, f[0].hi > f[0].lo && pack_counts));
+                form[IVX_SWEEP_SORT_WORDS] = 1;
             }
             o = in_b ? b : a;
             u32 *toolong = flags + 1;                                   // (upper half of the key-flag word; zeroed by the caller)
@@ -495,12 +505,14 @@ ivx_status sort64(ivx_ctx *ctx, int slot_a, int slot_b, const u32 *key, const i6
                 IVX_HIP(ctx, hipMemsetAsync(toolong, 0, sizeof(u32), st));
                 IVX_TRY(pack_for_sort(0, pay[0]));
                 two_step = false;
+                form[IVX_SWEEP_TOOLONG] = 1;
             }
         }
         else IVX_TRY(pack_for_sort(0, pay[0]));
         if (!two_step) {
             const ivx_sort_field f[1] = {{0, 0, (int)((total + 7) / 8 * 8)}};
             IVX_TRY(ivx_radix_sort(ctx, 1, a, b, n, f, 1, &in_b, true, with_rows ? pay : nullptr, total > 0 && pack_counts));
+            form[IVX_SWEEP_SORT_WORDS] = 1;
             o = in_b ? b : a;
             if (narrow && k8)
             hipLaunchKernelGGL((k_unpack1<false, true, true>), dim3((grid1(n) + UNPACK_TILES - 1) / UNPACK_TILES), dim3(ST), 0, st, (const u64 *)o[0], (const u32 *)pay[in_b], n, p, ks, ss, es, rows,
@@ -517,6 +529,7 @@ ivx_status sort64(ivx_ctx *ctx, int slot_a, int slot_b, const u32 *key, const i6
         hipLaunchKernelGGL(k_pack64, dim3(grid1(n)), dim3(ST), 0, st, key, s, e, n, nkeys, a[0], a[1], a[2], flags);
         const ivx_sort_field f[3] = {{0, 0, 64}, {1, 0, 64}, {2, 32, 64}};
         IVX_TRY(ivx_radix_sort(ctx, 3, a, b, n, f, 3, &in_b));
+        form[IVX_SWEEP_SORT_WORDS] = 3;
         u64 *const *o = in_b ? b : a;
         hipLaunchKernelGGL(k_unpack64, dim3(grid1(n)), dim3(ST), 0, st, (const u64 *)o[0], (const u64 *)o[1], (const u64 *)o[2], n, ks, ss, es, rows);
     }
@@ -999,6 +1012,7 @@ ivx_status ivx_merge_device(ivx_ctx *ctx, const u32 *key, const i64 *s, const i6
                             i64 min_dist, int strict, u32 *ok, i64 *os, i64 *oe, i64 *on, u64 *m)
 {
     *m = 0;
+    for (u32 &f : ctx->sweep_form) f = 0;
     if (n == 0) return IVX_OK;
     IVX_HIP(ctx, hipMemsetAsync(ctx->dword(SC_SWEEP_FLAG), 0, sizeof(u64), ctx->stream));
     u32 *ks; i64 *ss, *es;
@@ -1139,11 +1153,22 @@ extern "C" ivx_status ivx_debug_subtract_paths(ivx_ctx *ctx, u32 *wg, u64 wg_cap
     return IVX_OK;
 }
 
+// Test hook (not in include/ivx.h; tests/test_gpu_run_edges.py): which forms the last merge / cluster / complement took -- the
+// words sort64 and runs_packed noted on the host while they decided (IVX_SWEEP_*, ivx_internal.hpp).  Reads host memory only.
+extern "C" ivx_status ivx_debug_sweep_form(ivx_ctx *ctx, uint32_t *out, uint32_t n_out)
+{
+    if (!ctx) return IVX_ERR_INVALID;
+    if (n_out && !out) return ctx->fail(IVX_ERR_INVALID, "null out");
+    for (u32 i = 0; i < n_out && i < (u32)IVX_SWEEP_WORDS; i++) out[i] = ctx->sweep_form[i];
+    return IVX_OK;
+}
+
 ivx_status ivx_cluster_device(ivx_ctx *ctx, const u32 *key, const i64 *s, const i64 *e, u64 n, u32 nkeys,
                               i64 min_dist, int strict, const i64 *key_base,
                               u32 *ok, i64 *os, i64 *oe, u32 *orow, i64 *oc, i64 *ocs, i64 *oce, u64 *key_clusters, u64 *m)
 {
     *m = 0;
+    for (u32 &f : ctx->sweep_form) f = 0;
     IVX_HIP(ctx, hipMemsetAsync(ctx->dword(SC_SWEEP_FLAG), 0, sizeof(u64), ctx->stream));
     // the sorted rows ARE output columns; scratch only for the ones the caller did not ask for
     u32 *ks = ok, *rows = orow; i64 *ss = os, *es = oe;
@@ -1165,6 +1190,7 @@ ivx_status ivx_complement_device(ivx_ctx *ctx, const u32 *key, const i64 *s, con
                                  u32 *ok, i64 *os, i64 *oe, u64 cap, u64 *n_out)
 {
     *n_out = 0;
+    for (u32 &f : ctx->sweep_form) f = 0;
     hipStream_t st = ctx->stream;
     u32 *bad = ctx->dword<u32>(SC_SWEEP_FLAG), *irregular = ctx->dword<u32>(SC_SWEEP_IRREGULAR);
     IVX_HIP(ctx, hipMemsetAsync(bad, 0, 2 * sizeof(u64), st));             // both
@@ -1222,7 +1248,7 @@ ivx_status ivx_complement_device(ivx_ctx *ctx, const u32 *key, const i64 *s, con
     IVX_TRY(ctx->get_scratch(WS_T0, nw * sizeof(u32), (void **)&wk));            // the sorted input rows are dead by now
     IVX_TRY(ctx->get_scratch(WS_T1, nw * sizeof(i64), (void **)&ws));
     IVX_TRY(ctx->get_scratch(WS_T2, nw * sizeof(i64), (void **)&we));
-    IVX_TRY(sort64(ctx, WS_SA0, WS_SB0, uk, us, ue, nw, nkeys, wk, ws, we, nullptr));
+    IVX_TRY(sort64(ctx, WS_SA0, WS_SB0, uk, us, ue, nw, nkeys, wk, ws, we, nullptr, nullptr, nullptr, false));   // (the form words stay the input rows')
 
     u32 *A, *inv, *pa, *pb; u64 *cnt;
     IVX_TRY(ctx->get_scratch(WS_T8, (nw + 1) * sizeof(u32), (void **)&A));

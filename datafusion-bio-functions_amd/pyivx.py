@@ -64,6 +64,11 @@ FORMS_GRIDS = {KIND_COUNT: ("starts", "ends"), KIND_COVERAGE: ("first", "last"),
 NEAR_ORDER_PRESORTED, NEAR_ORDER_REPAIR, NEAR_ORDER_FULL = 0, 1, 2      # near_order
 NEAR_FB_NOFIT, NEAR_FB_LIN_RUN, NEAR_FB_SE_RUN = 1, 2, 4                # near_fallback bits
 
+# words of the test hook ivx_debug_sweep_form (csrc/ivx_internal.hpp IVX_SWEEP_*), in order
+SWEEP_SLOTS = ["sort_words", "nw", "lin", "bits_s", "bits_e", "bits_k", "sorted_in", "two_step", "toolong", "narrow_rows", "k8",
+               "packed", "narrow_runs", "ntile"]
+SWEEP_ROWS, SWEEP_PACKED, SWEEP_PACKED_BESIDE_ROWS = 0, 1, 2            # packed
+
 
 class Metrics(C.Structure):
     _fields_ = [("build_time", C.c_double), ("join_time", C.c_double), ("build_input_batches", C.c_uint64),
@@ -154,6 +159,9 @@ def lib():
         # test hook of csrc/ivx_capi.hip (not in include/ivx.h): the forms a count / coverage / nearest index took (tests/test_gpu_rank_edges.py)
         L.ivx_debug_index_forms.restype = C.c_int
         L.ivx_debug_index_forms.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32), C.c_uint32]
+        # test hook of csrc/ivx_sweep.hip (not in include/ivx.h): the forms the last merge / cluster / complement took (tests/test_gpu_run_edges.py)
+        L.ivx_debug_sweep_form.restype = C.c_int
+        L.ivx_debug_sweep_form.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.c_uint32]
         _lib = L
     return _lib
 
@@ -681,6 +689,13 @@ class Ctx:
         self._chk(lib().ivx_subtract(self.h, *args, _ptr(ok), _ptr(os_), _ptr(oe), _ptr(orow), C.c_uint64(cap), C.byref(m2)))
         m2 = m2.value
         return ok[:m2], os_[:m2], oe[:m2], orow[:m2]
+
+    def sweep_form(self):
+        """the forms the last merge / cluster / complement of this context took (test hook ivx_debug_sweep_form) as a dict of
+        the SWEEP_SLOTS: what its sort and its packed sweep decided on the host.  After a subtract: its last sort's."""
+        out = (C.c_uint32 * len(SWEEP_SLOTS))()
+        self._chk0(lib().ivx_debug_sweep_form(self.h, out, C.c_uint32(len(SWEEP_SLOTS))))
+        return dict(zip(SWEEP_SLOTS, list(out)))
 
     # ---- f1, f2 ----
     def cluster(self, key, start, end, n_keys=None, min_dist=0, strict=False, key_base=None, rows=True):

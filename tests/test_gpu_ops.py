@@ -488,8 +488,9 @@ def test_sweeps_sort_on_key_start_then_fix_runs(ctx, dups):
 
 @pytest.mark.parametrize("shape", ["sparse", "dense", "one_key", "many_keys", "empties", "scaffolds"])
 def test_merge_one_pass_sweep(ctx, shape):
-    """Well-formed rows go through the one-pass sweep over the sort's packed words (ivx_runs.hip k_merge_fused: several
-    hundred tiles, look-back windows beyond 64 tiles, runs and keys that straddle tiles); IVX_NO_FUSED_SWEEP=1 is the
+    """Well-formed rows go through the sweep over the sort's packed words (ivx_runs.hip: the three kernels k_pk_max,
+    k_pk_runs<0> and k_pk_runs<1> with a one-word-per-tile scan between them; several hundred tiles, runs and keys that
+    straddle tiles); IVX_NO_FUSED_SWEEP=1 is the
     three-pass sweep over unpacked rows.  Both must give the oracle's runs; strict + min_dist 0 with empty rows (whose
     order inside a start matters) must fall back by itself."""
     rng = np.random.default_rng(4242)

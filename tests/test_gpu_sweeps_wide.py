@@ -355,6 +355,14 @@ def _same_cluster(got, want, what):
     assert np.array_equal(_host(got["key_clusters"]), want["key_clusters"].astype(np.int64)), what
 
 
+def _agrees(got, form, what):
+    """the forms a merge call took (pyivx.Ctx.sweep_form(), noted by sort64 and runs_packed as they decide) against
+    expected_form's restatement of them"""
+    read = dict(lin=bool(got["lin"]), one_word=got["nw"] == 1, narrow_rows=bool(got["narrow_rows"]), k8=bool(got["k8"]),
+                packed=got["packed"] == pyivx.SWEEP_PACKED, narrow_runs=bool(got["narrow_runs"]))
+    assert read == {w: form[w] for w in read}, f"{what}: the call took {got}, expected_form says {form}"
+
+
 # ---------------------------------------------------------------- every regime, every knob
 
 @pytest.mark.parametrize("name", list(CASES))
@@ -365,6 +373,8 @@ def test_sweeps_wide_forms_and_knobs(ctx, monkeypatch, name):
         assert form[key_] == v, f"{name} reaches {key_}={form[key_]} (wanted {v}): {form}"
     if name == "R2_keys_2e40_apart":                      # without lin the word is key || start: three words
         assert not expected_form(k, s, e, nk, no_lin=True)["one_word"]
+    ctx.merge(k, s, e, n_keys=nk)
+    _agrees(ctx.sweep_form(), form, name)                 # ... and the device's host code decided the same
     (lk, ls, le), (rk, rs, re) = sub_sides(name)
     want_m = {st: orc.merge(k, s, e, strict=st) for st in (False, True)}
     want_c = orc.cluster(k, s, e, n_keys=nk)
@@ -417,6 +427,8 @@ def test_min_dist_saturation(ctx, monkeypatch, name):
                     if knob:
                         m.setenv(knob, "1")
                     _same(ctx.merge(k, s, e, n_keys=nk, min_dist=md, strict=st), wm, f"merge md={md} strict={st} {knob}")
+                    if knob is None and not st:
+                        _agrees(ctx.sweep_form(), form, f"{name} md={md}")
                     _same_cluster(ctx.cluster(k, s, e, n_keys=nk, min_dist=md, strict=st), wc, f"cluster md={md} strict={st} {knob}")
 
 
