@@ -441,6 +441,86 @@ extern "C" ivx_status ivx_debug_index_forms(ivx_ctx *ctx, const ivx_index *ix, u
     return IVX_OK;
 }
 
+// TEST HOOK (exported, not in include/ivx.h; tests/test_gpu_entry_state.py): what the context carries from one call to the next
+// -- both plans and their slot masks, the pending build tail, the scratch slots that hold memory, the free buffers of the index
+// pool, the fill calls that a plan served.  Reads host fields only:
+// nothing is launched, no scratch is taken.  Words: IVX_STATE_*
+extern "C" ivx_status ivx_debug_ctx_state(ivx_ctx *ctx, uint64_t *out, uint32_t n_out)
+{
+    if (!ctx) return IVX_ERR_INVALID;
+    if (n_out && !out) return ctx->fail(IVX_ERR_INVALID, "null out");
+    u64 w[IVX_STATE_WORDS] = {};
+    w[IVX_STATE_JOIN_VALID] = ctx->join_plan.valid ? 1 : 0;
+    w[IVX_STATE_JOIN_SLOTS] = ctx->join_plan.rows.slots;
+    w[IVX_STATE_SUB_VALID] = ctx->sub_plan.valid ? 1 : 0;
+    w[IVX_STATE_SUB_SLOTS] = ctx->sub_plan.slots;
+    w[IVX_STATE_TAIL_PENDING] = ctx->tail_pending ? 1 : 0;
+    w[IVX_STATE_JOIN_FILLS_PLANNED] = ctx->join_fills_planned;
+    w[IVX_STATE_SUB_FILLS_PLANNED] = ctx->sub_fills_planned;
+    for (int i = 0; i < IVX_NSCRATCH; i++) if (ctx->scratch[i].p) w[IVX_STATE_SCRATCH_HELD] |= 1ull << i;
+    {
+        std::lock_guard<std::mutex> lk(g_pool_mu);
+        for (const PoolBuf &b : g_pool) if (b.device == ctx->device) w[IVX_STATE_POOL_FREE]++;
+    }
+    for (u32 i = 0; i < n_out && i < (u32)IVX_STATE_WORDS; i++) out[i] = w[i];
+    return IVX_OK;
+}
+
+// TEST HOOK (exported, not in include/ivx.h; tests/test_gpu_entry_state.py): `word` (0 or 1) into every 32-bit word of the
+// state `what` selects (IVX_POISON_* bits), so that a kernel that reads what an earlier call left -- a scratch slot, a
+// call-local scalar word, a recycled index buffer -- gives a wrong answer instead of a right one by luck.  Left alone: the
+// slots a valid plan names (unless IVX_POISON_DROP_PLANS), the scalar words of SC_OUTLIVES, the memory of live indexes; and a
+// running build tail is refused, not waited for (the caller synchronises first).  Takes no scratch, allocates nothing and,
+// without IVX_POISON_DROP_PLANS, leaves both plans as they are.  slots_written (nullable): the scratch slots written.
+extern "C" ivx_status ivx_debug_poison(ivx_ctx *ctx, uint32_t word, int what, uint64_t *slots_written)
+{
+    if (!ctx) return IVX_ERR_INVALID;
+    if (slots_written) *slots_written = 0;
+    if (word > 1u) return ctx->fail(IVX_ERR_INVALID, "debug_poison: the word is 0 or 1");
+    if (ctx->tail_pending) return ctx->fail(IVX_ERR_INVALID, "debug_poison: a build tail is pending");
+    IVX_HIP(ctx, hipSetDevice(ctx->device));
+    IVX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    hipStream_t st = ctx->stream;
+    const auto fill_host = [word](void *p, size_t bytes) { u32 *q = (u32 *)p; for (size_t i = 0; i < bytes / sizeof(u32); i++) q[i] = word; };
+    if (what & IVX_POISON_DROP_PLANS) { ctx->sub_plan.valid = false; ctx->join_plan.valid = false; }
+    if (what & IVX_POISON_SCRATCH) {
+        const u64 keep = (ctx->sub_plan.valid ? ctx->sub_plan.slots : 0) | (ctx->join_plan.valid ? ctx->join_plan.rows.slots : 0);
+        u64 wrote = 0;
+        for (int i = 0; i < IVX_NSCRATCH; i++) {
+            const ivx_buf &b = ctx->scratch[i];
+            if (!b.p || ((keep >> i) & 1)) continue;
+            IVX_HIP(ctx, hipMemsetD32Async((hipDeviceptr_t)b.p, (int)word, b.cap / sizeof(u32), st));
+            wrote |= 1ull << i;
+        }
+        if (slots_written) *slots_written = wrote;
+    }
+    if (what & IVX_POISON_SCALARS) {
+        // every run of words between two entries of SC_OUTLIVES (ascending): the device words, then their mirror and the host-only words
+        int w = 0;
+        for (size_t k = 0; k <= sizeof(SC_OUTLIVES) / sizeof(SC_OUTLIVES[0]); k++) {
+            const bool last = k == sizeof(SC_OUTLIVES) / sizeof(SC_OUTLIVES[0]);
+            const int stop = last ? (int)SC_HOST_WORDS : SC_OUTLIVES[k].first;
+            if (w < stop) {
+                const int dstop = stop < (int)SC_DEVICE_WORDS ? stop : (int)SC_DEVICE_WORDS;
+                if (w < dstop) IVX_HIP(ctx, hipMemsetD32Async((hipDeviceptr_t)ctx->dword(w), (int)word, (size_t)(dstop - w) * 2, st));
+                fill_host(ctx->hword(w), (size_t)(stop - w) * sizeof(u64));
+            }
+            if (!last) w = SC_OUTLIVES[k].first + SC_OUTLIVES[k].words;
+        }
+    }
+    if (what & IVX_POISON_PINNED)
+        for (const ivx_buf &b : ctx->pinned) if (b.p) fill_host(b.p, b.cap);
+    if (what & IVX_POISON_POOL) {
+        // (under the pool's lock up to the wait: no build of another thread takes a buffer while it is being written)
+        std::lock_guard<std::mutex> lk(g_pool_mu);
+        for (const PoolBuf &b : g_pool)
+            if (b.device == ctx->device) IVX_HIP(ctx, hipMemsetD32Async((hipDeviceptr_t)b.p, (int)word, b.cap / sizeof(u32), st));
+        IVX_HIP(ctx, hipStreamSynchronize(st));
+    }
+    IVX_HIP(ctx, hipStreamSynchronize(st));
+    return IVX_OK;
+}
+
 // ---------------------------------------------------------------- a3 probes
 
 static bool rowval_routed_ok(u64 n)
@@ -516,6 +596,7 @@ static ivx_status overlap_common(ivx_ctx *ctx, const ivx_index *ix, int mem, int
     if (total) *total = tot;
     if (mode == JP_FILL && tot > cap) return ctx->fail(IVX_ERR_CAPACITY, "pair buffers too small");   // (a plan survives this: the retry with bigger buffers reuses it)
     f.rows_out(mode == JP_FILL ? tot : (mode == JP_COUNT ? 0 : n));
+    if (planned) ctx->join_fills_planned++;
     if (planned) pl.valid = false;                          // a plan serves ONE successful fill: a caller that refills the same buffers with its next batch must not get this batch's rows
     f.back(per_row); f.back(exists);                        // (one value per probe row, in whichever mode asked for them)
     if (mode == JP_FILL) { f.back(bidx, tot); f.back(pidx, tot); }
@@ -932,6 +1013,7 @@ extern "C" ivx_status ivx_subtract(ivx_ctx *ctx, int mem,
     });
     *n_out = m;
     if (st != IVX_OK) { if (st != IVX_ERR_CAPACITY) pl.valid = false; return st; }
+    if (planned) ctx->sub_fills_planned++;
     if (planned) pl.valid = false;                          // consumed: the next fill call sorts and counts again (its input columns may have been refilled in place)
     if (sizing && pl.valid) { memcpy(pl.in, in, sizeof(in)); pl.mem = mem; }
     if (cap) f.back_all(m);

@@ -123,6 +123,7 @@ struct ivx_ctx {
     u64 hdr_mirror_serial = 0;          // the index whose header that is (its HDR_SLOW arrives with the build's tail: ivx_join_probe_regions)
     ivx_sub_plan sub_plan;
     ivx_join_plan join_plan;
+    u64 join_fills_planned = 0, sub_fills_planned = 0;     // fill calls a plan served (test hook ivx_debug_ctx_state)
     u32 sweep_form[16] = {};            // IVX_SWEEP_* (below): what the last sweep's sort and packed sweep decided on the host (test hook)
     ivx_metrics metrics{};              // BuildProbeJoinMetrics, see ivx.h
     u64 mem_limit = 0;                  // device bytes of scratch + the index being built (0 = unlimited)
@@ -325,6 +326,17 @@ enum { IVX_SWEEP_SORT_WORDS = 0 /* words of the radix sort that ran: 0 none, 1, 
        IVX_SWEEP_NARROW_RUNS = 12 /* k_pk_runs<..., NARROW = true> */, IVX_SWEEP_NTILE = 13 /* tiles of the packed sweep */,
        IVX_SWEEP_WORDS = 14 };
 static_assert(IVX_SWEEP_WORDS <= sizeof(ivx_ctx::sweep_form) / sizeof(u32), "ivx_ctx::sweep_form holds the IVX_SWEEP_* words");
+// words of ivx_debug_ctx_state (ivx_capi.hip; tests only, not in include/ivx.h), u64 each: what a context carries from one call
+// to the next.  The slot masks have a bit per scratch slot (WS_*) and are meaningful while their plan is valid.
+enum { IVX_STATE_JOIN_VALID = 0, IVX_STATE_JOIN_SLOTS = 1 /* ivx_join_plan::rows.slots */, IVX_STATE_SUB_VALID = 2, IVX_STATE_SUB_SLOTS = 3,
+       IVX_STATE_TAIL_PENDING = 4, IVX_STATE_SCRATCH_HELD = 5 /* scratch slots that hold memory */,
+       IVX_STATE_POOL_FREE = 6 /* free buffers of the index pool on the context's device */,
+       IVX_STATE_JOIN_FILLS_PLANNED = 7, IVX_STATE_SUB_FILLS_PLANNED = 8 /* fill calls so far that a plan served */, IVX_STATE_WORDS = 9 };
+// bits of ivx_debug_poison's `what` (ivx_capi.hip; tests only, not in include/ivx.h)
+enum { IVX_POISON_SCRATCH = 1 /* every scratch slot that holds memory and that no valid plan names, over its full capacity */,
+       IVX_POISON_DROP_PLANS = 2 /* both plans dropped first: IVX_POISON_SCRATCH then covers every slot */,
+       IVX_POISON_SCALARS = 4 /* the call-local scalar words, device and mirror: all but SC_OUTLIVES (ivx_scalars.hpp) */,
+       IVX_POISON_PINNED = 8 /* the pinned staging buffers */, IVX_POISON_POOL = 16 /* this device's free buffers of the index pool */ };
 
 // ---------------------------------------------------------------- internal API
 // scan.hip

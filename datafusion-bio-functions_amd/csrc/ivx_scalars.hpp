@@ -91,6 +91,14 @@ enum {
     SC_HOST_WORDS = SC_HDR_MIRROR + (HDR_WORDS + 1) / 2     // ---- length of h_scalars
 };
 
+// The words that outlive their call, in ascending order, as {first word, words}: every word above whose comment says OUTLIVES,
+// and no other, each with the length the table gives it (tests/test_scalar_words.py compares both).  The test hook ivx_debug_poison (ivx_capi.hip) overwrites every word of both
+// arrays but these.
+struct ivx_sc_span { int first, words; };
+static constexpr ivx_sc_span SC_OUTLIVES[] = {{SC_UNSORTED, 1}, {SC_HDR_MIRROR, (HDR_WORDS + 1) / 2}};
+static_assert(SC_OUTLIVES[0].first + SC_OUTLIVES[0].words <= SC_OUTLIVES[1].first && SC_OUTLIVES[1].first + SC_OUTLIVES[1].words <= SC_HOST_WORDS,
+              "the outliving words ascend and lie inside the host words");
+
 // the blocks that one memset or one copy covers, in words
 enum { SC_BUILD_WORDS = SC_SWEEP_FLAG - SC_BUILD_FLAG, SC_RANGE_LIN_WORDS = SC_DEPTH_BAD - SC_RANGE, SC_DEPTH_WORDS = SC_STEPS_TOTAL - SC_DEPTH_BAD,
        SC_CIG_CHECK_WORDS = SC_JOIN_LENHIST - SC_CIG_BAD };

@@ -69,6 +69,12 @@ SWEEP_SLOTS = ["sort_words", "nw", "lin", "bits_s", "bits_e", "bits_k", "sorted_
                "packed", "narrow_runs", "ntile"]
 SWEEP_ROWS, SWEEP_PACKED, SWEEP_PACKED_BESIDE_ROWS = 0, 1, 2            # packed
 
+# words of the test hook ivx_debug_ctx_state (csrc/ivx_internal.hpp IVX_STATE_*), in order; the masks have a bit per scratch slot
+STATE_SLOTS = ["join_valid", "join_slots", "sub_valid", "sub_slots", "tail_pending", "scratch_held", "pool_free", "join_fills_planned",
+               "sub_fills_planned"]
+# bits of the test hook ivx_debug_poison's `what` (csrc/ivx_internal.hpp IVX_POISON_*)
+POISON_SCRATCH, POISON_DROP_PLANS, POISON_SCALARS, POISON_PINNED, POISON_POOL = 1, 2, 4, 8, 16
+
 
 class Metrics(C.Structure):
     _fields_ = [("build_time", C.c_double), ("join_time", C.c_double), ("build_input_batches", C.c_uint64),
@@ -162,6 +168,12 @@ def lib():
         # test hook of csrc/ivx_sweep.hip (not in include/ivx.h): the forms the last merge / cluster / complement took (tests/test_gpu_run_edges.py)
         L.ivx_debug_sweep_form.restype = C.c_int
         L.ivx_debug_sweep_form.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.c_uint32]
+        # test hooks of csrc/ivx_capi.hip (not in include/ivx.h): what a context carries between calls, and a fixed word written
+        # over all of it that no plan and no outliving scalar word needs (tests/test_gpu_entry_state.py)
+        L.ivx_debug_ctx_state.restype = C.c_int
+        L.ivx_debug_ctx_state.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.c_uint32]
+        L.ivx_debug_poison.restype = C.c_int
+        L.ivx_debug_poison.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_uint64)]
         _lib = L
     return _lib
 
@@ -696,6 +708,21 @@ class Ctx:
         out = (C.c_uint32 * len(SWEEP_SLOTS))()
         self._chk0(lib().ivx_debug_sweep_form(self.h, out, C.c_uint32(len(SWEEP_SLOTS))))
         return dict(zip(SWEEP_SLOTS, list(out)))
+
+    def debug_state(self):
+        """what this context carries from one call to the next (test hook ivx_debug_ctx_state) as a dict of the STATE_SLOTS:
+        both plans and their scratch-slot masks, the pending build tail, the slots that hold memory, the free buffers of
+        the index pool on this device, the fill calls so far that a plan served"""
+        out = (C.c_uint64 * len(STATE_SLOTS))()
+        self._chk0(lib().ivx_debug_ctx_state(self.h, out, C.c_uint32(len(STATE_SLOTS))))
+        return dict(zip(STATE_SLOTS, list(out)))
+
+    def debug_poison(self, word, what):
+        """word (0 or 1) into every 32-bit word of what the POISON_* bits of `what` select (test hook ivx_debug_poison);
+        refused while a build tail is pending.  -> the mask of scratch slots written"""
+        wrote = C.c_uint64(0)
+        self._chk0(lib().ivx_debug_poison(self.h, C.c_uint32(int(word)), C.c_int(int(what)), C.byref(wrote)))
+        return wrote.value
 
     # ---- f1, f2 ----
     def cluster(self, key, start, end, n_keys=None, min_dist=0, strict=False, key_base=None, rows=True):

@@ -11,124 +11,14 @@ No bad argument here reaches a kernel: each is one the entry layer rejects on th
 pyivx.lib() with ctypes directly: pyivx's wrappers would allocate, retry or reject first.
 """
 import ctypes as C
-import os
-import sys
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
-
-sys.path.insert(0, os.path.join(ROOT, "datafusion-bio-functions_amd"))
-import pyivx  # noqa: E402
-import cigar_text_oracle as cto  # noqa: E402
+from entry_cases import (CAPACITY, CASES, INVALID, NK, NULL, OK, SIZES, UNSUPPORTED, Buf, Env, Mode, _same, cint, i64, ivals,
+                         pyivx, cto, reads, sized, u32, u64, untouched)  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-OK, INVALID, CAPACITY, UNSUPPORTED = pyivx.OK, pyivx.ERR_INVALID, pyivx.ERR_CAPACITY, pyivx.ERR_UNSUPPORTED
-NULL = pyivx.NULL_IDX
-NK = 3                      # keys
-SIZES = [1000, 0, 1]
-PATTERN = 0xA5              # what every output buffer holds before a call
-u32, u64, i64, cint = C.c_uint32, C.c_uint64, C.c_int64, C.c_int
-_SIGNED = {np.dtype(np.uint32): np.int32, np.dtype(np.uint64): np.int64, np.dtype(np.uint16): np.int16}
-
-
-class Buf:
-    """an array in one memory mode: numpy on the host, a torch tensor on the device (unsigned types as their signed bits);
-    never empty, so that its pointer is never null (the element count goes to the entry separately)"""
-
-    def __init__(self, a, dev):
-        a = np.ascontiguousarray(a)
-        self.dt, self.n = a.dtype, a.size
-        if a.size == 0:
-            a = np.zeros(1, a.dtype)
-        if dev:
-            import torch
-            self.h = torch.from_numpy(a.view(_SIGNED.get(a.dtype, a.dtype)).copy()).to("cuda:0")
-        else:
-            self.h = a.copy()
-
-    @property
-    def p(self):
-        return pyivx._ptr(self.h)
-
-    def np(self):
-        a = self.h.cpu().numpy() if pyivx._is_torch(self.h) else self.h
-        return a.view(self.dt).reshape(-1)
-
-
-class Mode:
-    def __init__(self, dev):
-        self.dev, self.mem = dev, cint(pyivx.MEM_DEVICE if dev else pyivx.MEM_HOST)
-
-    def put(self, a):
-        return Buf(a, self.dev)
-
-    def out(self, n, dt):
-        """an output buffer of n elements (at least one), every byte PATTERN"""
-        return Buf(np.full(max(int(n), 1) * np.dtype(dt).itemsize, PATTERN, np.uint8).view(dt), self.dev)
-
-
-def untouched(buf):
-    return bool((buf.np().view(np.uint8) == PATTERN).all())
-
-
-def ivals(n, seed, dt=np.int32, span=20_000):
-    rng = np.random.default_rng(seed)
-    key = rng.integers(0, NK, n).astype(np.uint32)
-    s = rng.integers(0, span, n)
-    e = s + rng.integers(0, 300, n)
-    return key, s.astype(dt), e.astype(dt)
-
-
-def reads(n, seed):
-    """n reads with 1..3 CIGAR ops each (M, I, D, N, S) and n // 4 weighted segments, as the ABI's columns"""
-    rng = np.random.default_rng(seed)
-    off = np.zeros(n + 1, np.int32)
-    ops = []
-    for i in range(n):
-        for _ in range(int(rng.integers(1, 4))):
-            ops.append((int(rng.integers(1, 60)) << 4) | int(rng.choice([0, 0, 0, 1, 2, 3, 4])))
-        off[i + 1] = 4 * len(ops)
-    ns = n // 4
-    ss = rng.integers(0, 5000, ns)
-    return dict(rkey=rng.integers(0, NK, n).astype(np.uint32), rpos=rng.integers(0, 5000, n).astype(np.uint32),
-                rflags=np.where(rng.random(n) < 0.1, 4, 0).astype(np.uint32), rmapq=rng.integers(0, 61, n).astype(np.uint32),
-                off=off, ops=np.array(ops, np.uint32).reshape(-1),
-                skey=rng.integers(0, NK, ns).astype(np.uint32), ss=ss.astype(np.uint32), se=(ss + rng.integers(0, 80, ns)).astype(np.uint32),
-                sw=rng.integers(-2, 4, ns).astype(np.int32))
-
-
-class Env:
-    """one context, one index of every kind and one depth profile, built once from host columns"""
-
-    def __init__(self):
-        import torch
-        torch.zeros(1, device="cuda:0")                         # (torch's own start-up: here, not in the first case that puts a tensor)
-        self.ctx = pyivx.Ctx(0)
-        self.h = self.ctx.h
-        self.L = pyivx.lib()
-        self.build_cols = ivals(1000, 1)
-        self.ix = [self.ctx.build(kind, *self.build_cols, n_keys=NK) for kind in range(4)]
-        r = reads(1000, 7)
-        self.profile = self.ctx.depth_profile(r["rkey"], r["rpos"], r["rflags"], r["rmapq"], r["off"], r["ops"],
-                                              r["skey"], r["ss"], r["se"], r["sw"], n_keys=NK)
-
-    def call(self, name, *args):
-        """the entry's status; the context's stream drained, so that device-mode outputs can be read"""
-        st = getattr(self.L, name)(self.h, *args)
-        assert self.L.ivx_ctx_synchronize(self.h) == OK
-        return st
-
-    def err(self):
-        return self.L.ivx_last_error(self.h).decode()
-
-    def close(self):
-        self.profile.free()
-        for ix in self.ix:
-            ix.free()
-        self.ctx.close()
 
 
 @pytest.fixture(scope="module")
@@ -138,488 +28,7 @@ def env():
     e.close()
 
 
-# ------------------------------------------------------------------ 1. host mode equals device mode
-
-CASES = {}
-
-
-def case(f):
-    CASES[f.__name__] = f
-    return f
-
-
-def sized(res, name, call):
-    """the three calls of a sizing / fill pair.  call(cap, with_buffers) -> (status, count, [output Bufs]); the one-short
-    fill must give IVX_ERR_CAPACITY (with the same count in both modes: the caller compares `res`)"""
-    st, m, _ = call(0, False)
-    res[name + ".sizing"] = (st, m)
-    st, m1, outs = call(m, True)
-    assert st == OK and m1 == m, (name, st, m1, m)
-    res[name + ".fill"] = (st, m1)
-    for i, o in enumerate(outs):
-        res[f"{name}.fill.{i}"] = o.np()[:m]
-    if m:
-        st, m2, _ = call(m - 1, True)
-        assert st == CAPACITY, (name, st)
-        res[name + ".short"] = (st, m2)
-
-
-@case
-def index_build(E, M, n):
-    res = {}
-    k, s, e = (M.put(a) for a in ivals(n, 3))
-    pk, ps, pe = ivals(200, 4)
-    for kind in range(4):
-        h = C.c_void_p()
-        st = E.call("ivx_index_build", cint(kind), M.mem, k.p, s.p, e.p, u64(n), u32(NK), C.byref(h))
-        assert st == OK, E.err()
-        ix = pyivx.Index(E.ctx, h, kind)
-        res[f"{kind}.rows"], res[f"{kind}.bytes"] = ix.rows, ix.device_bytes
-        if n:
-            if kind == pyivx.KIND_OVERLAP:
-                res["0.total"], res["0.per_row"] = E.ctx.overlap_count(ix, pk, ps, pe, per_row=True)
-            elif kind == pyivx.KIND_COUNT:
-                res["1.count"] = E.ctx.count_overlaps(ix, pk, ps, pe)
-            elif kind == pyivx.KIND_COVERAGE:
-                res["2.coverage"] = E.ctx.coverage(ix, pk, ps, pe)
-            else:
-                res["3.b"], res["3.p"], res["3.d"] = E.ctx.nearest(ix, pk, ps, pe, k=2)
-        ix.free()
-    return res
-
-
-@case
-def probe_overlap_count(E, M, n):
-    k, s, e = (M.put(a) for a in ivals(n, 5))
-    res = {}
-    tot = u64(0xDEAD)
-    res["st"] = E.call("ivx_probe_overlap_count", E.ix[0].h, M.mem, k.p, s.p, e.p, u64(n), None, C.byref(tot))
-    res["total"] = tot.value
-    pr = M.out(n, np.uint32)
-    tot2 = u64(0xDEAD)
-    res["st2"] = E.call("ivx_probe_overlap_count", E.ix[0].h, M.mem, k.p, s.p, e.p, u64(n), pr.p, C.byref(tot2))
-    res["total2"], res["per_row"] = tot2.value, pr.np()[:n]
-    return res
-
-
-@case
-def probe_overlap_fill(E, M, n):
-    k, s, e = (M.put(a) for a in ivals(n, 5))
-    res = {}
-
-    def call(cap, bufs):
-        w = u64(0xDEAD)
-        if not bufs:        # (the sizing call of a fill is the count call)
-            st = E.call("ivx_probe_overlap_count", E.ix[0].h, M.mem, k.p, s.p, e.p, u64(n), None, C.byref(w))
-            return st, w.value, []
-        b, p = M.out(cap, np.uint32), M.out(cap, np.uint32)
-        st = E.call("ivx_probe_overlap_fill", E.ix[0].h, M.mem, k.p, s.p, e.p, u64(n), b.p, p.p, u64(cap), C.byref(w))
-        m = min(w.value, cap)
-        pairs = np.sort((b.np()[:m].astype(np.uint64) << np.uint64(32)) | p.np()[:m].astype(np.uint64))   # (the order of the pairs is free)
-        return st, w.value, [Buf(pairs, False)]
-    sized(res, "fill", call)
-    return res
-
-
-@case
-def probe_exists(E, M, n):
-    k, s, e = (M.put(a) for a in ivals(n, 6))
-    out = M.out(n, np.uint8)
-    st = E.call("ivx_probe_exists", E.ix[0].h, M.mem, k.p, s.p, e.p, u64(n), out.p)
-    return {"st": st, "exists": out.np()[:n]}
-
-
-@case
-def probe_mark_build(E, M, n):
-    k, s, e = (M.put(a) for a in ivals(n, 6, span=4000))
-    nw = (1000 + 31) // 32
-    mine = np.zeros(nw, np.uint32)
-    mine[::3] = 0x00010001                                  # bits the caller had set: they survive
-    marks = M.put(mine)
-    st = E.call("ivx_probe_mark_build", E.ix[0].h, M.mem, k.p, s.p, e.p, u64(n), marks.p)
-    got = marks.np()
-    assert ((got & mine) == mine).all()
-    return {"st": st, "marks": got}
-
-
-@case
-def bits_mark(E, M, n):
-    rng = np.random.default_rng(8)
-    idx = rng.integers(0, 5000, n).astype(np.uint32)
-    idx[::7] = NULL
-    mine = np.zeros((5000 + 31) // 32, np.uint32)
-    mine[::5] = 0x80000001
-    d_idx, bits = M.put(idx), M.put(mine)
-    st = E.call("ivx_bits_mark", M.mem, d_idx.p, u64(n), bits.p, u64(5000))
-    got = bits.np()
-    assert ((got & mine) == mine).all()
-    return {"st": st, "bits": got}
-
-
-@case
-def bits_select(E, M, n):
-    rng = np.random.default_rng(9)
-    bits = M.put(rng.integers(0, 1 << 32, (n + 31) // 32, dtype=np.uint64).astype(np.uint32))
-    res = {}
-    for want in (1, 0):
-        def call(cap, bufs):
-            m = u64(0xDEAD)
-            out = M.out(cap, np.uint32)
-            st = E.call("ivx_bits_select", M.mem, bits.p, u64(n), cint(want), out.p if bufs else None, u64(cap), C.byref(m))
-            return st, m.value, [out]
-        sized(res, f"select{want}", call)
-    return res
-
-
-def _per_row(entry, kind):
-    def f(E, M, n):
-        k, s, e = (M.put(a) for a in ivals(n, 10))
-        res = {}
-        for strict in (0, 1):
-            out = M.out(n, np.int64)
-            res[f"st{strict}"] = E.call(entry, E.ix[kind].h, M.mem, k.p, s.p, e.p, u64(n), cint(strict), out.p)
-            res[f"out{strict}"] = out.np()[:n]
-        return res
-    f.__name__ = entry[4:]
-    return case(f)
-
-
-_per_row("ivx_probe_count", pyivx.KIND_COUNT)
-_per_row("ivx_probe_coverage", pyivx.KIND_COVERAGE)
-
-
-@case
-def probe_nearest(E, M, n):
-    k, s, e = (M.put(a) for a in ivals(n, 11))
-    cap = 2 * n
-    b, p, d = M.out(cap, np.uint32), M.out(cap, np.uint32), M.out(cap, np.int64)
-    rows = u64(0xDEAD)
-    st = E.call("ivx_probe_nearest", E.ix[3].h, M.mem, k.p, s.p, e.p, u64(n), cint(0), u32(2), cint(1), b.p, p.p, d.p, u64(cap), C.byref(rows))
-    r = rows.value
-    return {"st": st, "rows": r, "b": b.np()[:r], "p": p.np()[:r], "d": d.np()[:r]}
-
-
-@case
-def merge(E, M, n):
-    k, s, e = (M.put(a) for a in ivals(n, 12, np.int64))
-    outs = [M.out(n, dt) for dt in (np.uint32, np.int64, np.int64, np.int64)]
-    m = u64(0xDEAD)
-    st = E.call("ivx_merge", M.mem, k.p, s.p, e.p, u64(n), u32(NK), i64(0), cint(0), *[o.p for o in outs], u64(n), C.byref(m))
-    res = {"st": st, "n_out": m.value}
-    res.update({f"o{i}": o.np()[:m.value] for i, o in enumerate(outs)})
-    return res
-
-
-@case
-def subtract(E, M, n):
-    lk, ls, le = (M.put(a) for a in ivals(n, 13, np.int64))
-    nr = n // 2 if n > 1 else n
-    rk, rs, re = (M.put(a) for a in ivals(nr, 14, np.int64))
-    res = {}
-
-    def call(cap, bufs):
-        outs = [M.out(cap, dt) for dt in (np.uint32, np.int64, np.int64, np.uint32)]
-        m = u64(0xDEAD)
-        st = E.call("ivx_subtract", M.mem, lk.p, ls.p, le.p, u64(n), rk.p, rs.p, re.p, u64(nr), u32(NK), cint(0),
-                    *[o.p if bufs else None for o in outs], u64(cap), C.byref(m))
-        return st, m.value, outs
-    sized(res, "subtract", call)
-    return res
-
-
-@case
-def cluster(E, M, n):
-    k, s, e = (M.put(a) for a in ivals(n, 15, np.int64))
-    base = M.put(np.array([0, 1000, 5000], np.int64))
-    dts = (np.uint32, np.int64, np.int64, np.uint32, np.int64, np.int64, np.int64)
-    outs = [M.out(n, dt) for dt in dts]
-    kc = M.out(NK, np.uint64)
-    m = u64(0xDEAD)
-    st = E.call("ivx_cluster", M.mem, k.p, s.p, e.p, u64(n), u32(NK), i64(5), cint(0), base.p, *[o.p for o in outs], kc.p, C.byref(m))
-    res = {"st": st, "n_clusters": m.value, "key_clusters": kc.np()[:NK]}
-    res.update({f"o{i}": o.np()[:n] for i, o in enumerate(outs)})
-    return res
-
-
-@case
-def complement(E, M, n):
-    k, s, e = (M.put(a) for a in ivals(n, 16, np.int64))
-    nv = min(n, 4)
-    vk, vs, ve = (M.put(a) for a in (np.arange(nv, dtype=np.uint32) % NK, np.full(nv, 100, np.int64), np.full(nv, 19_000, np.int64)))
-    res = {}
-
-    def call(cap, bufs):
-        outs = [M.out(cap, dt) for dt in (np.uint32, np.int64, np.int64)]
-        m = u64(0xDEAD)
-        st = E.call("ivx_complement", M.mem, k.p, s.p, e.p, u64(n), vk.p, vs.p, ve.p, u64(nv), u32(NK), cint(0),
-                    *[o.p if bufs else None for o in outs], u64(cap), C.byref(m))
-        return st, m.value, outs
-    sized(res, "complement", call)
-    return res
-
-
-def _depth_in(M, n, text, large=0):
-    r = reads(n, 17)
-    d = {c: M.put(r[c]) for c in ("rkey", "rpos", "rflags", "rmapq", "skey", "ss", "se", "sw")}
-    if text:
-        toff, ttext = cto.text_column(cto.render_reads(r["off"], r["ops"]), large=bool(large), first=3)
-        d["cig"] = (M.put(toff), M.put(ttext))
-        cig = (cint(large), d["cig"][0].p, d["cig"][1].p)
-    else:
-        d["cig"] = (M.put(r["off"]), M.put(r["ops"]))
-        cig = (d["cig"][0].p, d["cig"][1].p)
-    klen = M.put(np.array([4000, 6000, 5200], np.uint32))
-    args = (M.mem, d["rkey"].p, d["rpos"].p, d["rflags"].p, d["rmapq"].p, *cig, n,
-            d["skey"].p, d["ss"].p, d["se"].p, d["sw"].p, n // 4, NK, klen.p, 1796, 20)
-    return args, (d, klen)
-
-
-def _depth(entry, text):
-    def f(E, M, n):
-        args, keep = _depth_in(M, n, text)
-        res = {}
-
-        def call(cap, bufs):
-            outs = [M.out(cap, dt) for dt in (np.uint32, np.uint32, np.uint32, np.int32)]
-            m = u64(0xDEAD)
-            st = E.call(entry, *args, *[o.p if bufs else None for o in outs], cap, C.byref(m))
-            return st, m.value, outs
-        sized(res, entry, call)
-        return res
-    f.__name__ = entry[4:]
-    return case(f)
-
-
-_depth("ivx_depth", False)
-_depth("ivx_depth_text", True)
-
-
-def _profile_build(entry, text):
-    def f(E, M, n):
-        args, keep = _depth_in(M, n, text, large=1 if text else 0)
-        h = C.c_void_p()
-        st = E.call(entry, *args, C.byref(h))
-        assert st == OK, E.err()
-        p = pyivx.DepthProfile(E.ctx, h, NK, None)
-        key, pos, cov, seen = p.read()
-        res = {"steps": p.steps(), "bytes": p.device_bytes, "key": key, "pos": pos, "cov": cov, "seen": seen}
-        p.free()
-        return res
-    f.__name__ = entry[4:]
-    return case(f)
-
-
-_profile_build("ivx_depth_profile_build", False)
-_profile_build("ivx_depth_profile_build_text", True)
-
-
-@case
-def cigar_parse(E, M, n):
-    r = reads(n, 18)
-    res = {}
-    for large in (0, 1):
-        toff, ttext = (M.put(a) for a in cto.text_column(cto.render_reads(r["off"], r["ops"]), large=bool(large)))
-        head = (M.mem, cint(large), toff.p, ttext.p, u64(n))
-
-        def call(cap, bufs):
-            off, ops = M.out(n + 1, np.int32), M.out(cap, np.uint32)
-            m = u64(0xDEAD)
-            st = E.call("ivx_cigar_parse", *head, off.p if bufs else None, ops.p if bufs else None, u64(cap), C.byref(m))
-            if bufs and n:
-                res[f"{large}.off@{cap}"] = off.np()[:n + 1]       # (the offsets go out whether the ops fitted or not)
-            return st, m.value, [ops]
-        sized(res, f"parse{large}", call)
-    return res
-
-
-@case
-def depth_profile_read(E, M, n):
-    steps = E.profile.steps()
-    res = {}
-    for cap in (steps, steps - 1):
-        outs = [M.out(steps, dt) for dt in (np.uint32, np.uint32, np.int32)]
-        seen = M.out(NK, np.uint8)
-        m = u64(0xDEAD)
-        st = E.call("ivx_depth_profile_read", E.profile.h, M.mem, *[o.p for o in outs], seen.p, u64(cap), C.byref(m))
-        assert st == (OK if cap == steps else CAPACITY)
-        res[f"{cap}"] = (st, m.value)
-        res[f"{cap}.seen"] = seen.np()[:NK]
-        res.update({f"{cap}.o{i}": o.np() for i, o in enumerate(outs)})     # (one short: all of it still the pattern)
-    return res
-
-
-@case
-def depth_profile_expand(E, M, n):
-    pos, cov = M.out(n, np.int32), M.out(n, np.int16)
-    st = E.call("ivx_depth_profile_expand", E.profile.h, M.mem, 1, 100, n, 0, pos.p, cov.p)
-    return {"st": st, "pos": pos.np()[:n], "cov": cov.np()[:n]}
-
-
-@case
-def depth_profile_blocks(E, M, n):
-    res = {}
-
-    def call(cap, bufs):
-        outs = [M.out(cap, dt) for dt in (np.uint32, np.uint32, np.uint32, np.int32)]
-        m = u64(0xDEAD)
-        st = E.call("ivx_depth_profile_blocks", E.profile.h, M.mem, *[o.p if bufs else None for o in outs], u64(cap), C.byref(m))
-        return st, m.value, outs
-    sized(res, "blocks", call)
-    return res
-
-
-def _regions(M, n):
-    rng = np.random.default_rng(19)
-    qs = rng.integers(0, 5000, n)
-    return [M.put(a) for a in (rng.integers(0, NK, n).astype(np.uint32), qs.astype(np.uint32), (qs + rng.integers(0, 400, n)).astype(np.uint32),
-                               np.array([4000, 6000, 5200], np.uint32))]
-
-
-@case
-def depth_profile_summarize(E, M, n):
-    qk, qs, qe, hi = _regions(M, n)
-    thr = np.array([1, 3, 10], np.int32)
-    outs = [M.out(n, np.int64), M.out(n, np.int64), M.out(3 * n, np.int64)]
-    st = E.call("ivx_depth_profile_summarize", E.profile.h, M.mem, qk.p, qs.p, qe.p, n, 0, hi.p, 0, pyivx._ptr(thr), 3, *[o.p for o in outs])
-    return {"st": st, "len": outs[0].np()[:n], "sum": outs[1].np()[:n], "ge": outs[2].np()[:3 * n]}
-
-
-@case
-def depth_profile_windows(E, M, n):
-    thr = np.array([1, 3, 10], np.int32)
-    outs = [M.out(n, np.int64), M.out(n, np.int64), M.out(3 * n, np.int64)]
-    st = E.call("ivx_depth_profile_windows", E.profile.h, M.mem, 2, 50, 50 + 7 * max(n, 1) - 4, 7, n, 1, pyivx._ptr(thr), 3, *[o.p for o in outs])
-    return {"st": st, "len": outs[0].np()[:n], "sum": outs[1].np()[:n], "ge": outs[2].np()[:3 * n]}
-
-
-@case
-def depth_profile_quantiles(E, M, n):
-    qk, qs, qe, hi = _regions(M, n)
-    qn = np.array([1, 3], np.uint32)
-    outs = [M.out(n, np.int64), M.out(n, np.int32), M.out(n, np.int32), M.out(2 * n, np.int32)]
-    st = E.call("ivx_depth_profile_quantiles", E.profile.h, M.mem, qk.p, qs.p, qe.p, n, 0, hi.p, 0, pyivx._ptr(qn), 2, 4, *[o.p for o in outs])
-    return {"st": st, "len": outs[0].np()[:n], "min": outs[1].np()[:n], "max": outs[2].np()[:n], "q": outs[3].np()[:2 * n]}
-
-
-@case
-def depth_profile_window_quantiles(E, M, n):
-    qn = np.array([1, 3], np.uint32)
-    outs = [M.out(n, np.int64), M.out(n, np.int32), M.out(n, np.int32), M.out(2 * n, np.int32)]
-    st = E.call("ivx_depth_profile_window_quantiles", E.profile.h, M.mem, 2, 50, 50 + 7 * max(n, 1) - 4, 7, n, 1, pyivx._ptr(qn), 2, 4,
-                *[o.p for o in outs])
-    return {"st": st, "len": outs[0].np()[:n], "min": outs[1].np()[:n], "max": outs[2].np()[:n], "q": outs[3].np()[:2 * n]}
-
-
-N_SRC = 300
-
-
-def _take_idx(n, seed):
-    rng = np.random.default_rng(seed)
-    idx = rng.integers(0, N_SRC, n).astype(np.uint32)
-    idx[::9] = NULL
-    return idx, np.packbits(rng.random(N_SRC) < 0.9, bitorder="little")
-
-
-@case
-def take_fixed(E, M, n):
-    idx, valid = _take_idx(n, 20)
-    src, d_idx, svb = M.put(np.random.default_rng(21).integers(0, 1 << 62, N_SRC).astype(np.int64)), M.put(idx), M.put(valid)
-    out, ov = M.out(n, np.int64), M.out(n, np.uint8)
-    st = E.call("ivx_take_fixed", M.mem, src.p, u32(8), u64(N_SRC), svb.p, d_idx.p, u64(n), out.p, ov.p)
-    return {"st": st, "out": out.np()[:n], "valid": ov.np()[:n]}
-
-
-@case
-def scatter_fixed(E, M, n):
-    rng = np.random.default_rng(22)
-    n_out = 2000
-    idx = rng.permutation(n_out)[:n].astype(np.uint32)
-    src, d_idx = M.put(rng.integers(0, 1 << 30, n).astype(np.int32)), M.put(idx)
-    out = M.out(n_out, np.int32)
-    st = E.call("ivx_scatter_fixed", M.mem, src.p, u32(4), d_idx.p, u64(n), out.p, u64(n_out))
-    got = out.np()
-    rest = np.ones(n_out, bool)
-    rest[idx] = False
-    assert (got[rest].view(np.uint8) == PATTERN).all()        # rows no index names keep the caller's bytes
-    return {"st": st, "out": got}
-
-
-def _strings(seed):
-    rng = np.random.default_rng(seed)
-    return [bytes(rng.integers(97, 123, int(rng.integers(0, 31)), dtype=np.uint8)) for _ in range(N_SRC)]
-
-
-@case
-def take_utf8(E, M, n):
-    res = {}
-    idx, valid = _take_idx(n, 23)
-    d_idx, svb = M.put(idx), M.put(valid)
-    for large in (0, 1):
-        off, data = cto.text_column(_strings(24), large=bool(large))
-        d_off, d_data = M.put(off), M.put(data)
-        head = (M.mem, cint(large), d_off.p, d_data.p, u64(N_SRC), u64(len(data)), svb.p, d_idx.p, u64(n))
-
-        def call(cap, bufs):
-            ooff, odata, ov = M.out(n + 1, off.dtype), M.out(cap, np.uint8), M.out(n, np.uint8)
-            need = u64(0xDEAD)
-            st = E.call("ivx_take_utf8", *head, ooff.p, odata.p if bufs else None, u64(cap), C.byref(need), ov.p)
-            # a short data buffer (and the sizing call) still returns the offsets and the validity
-            res[f"{large}.off@{cap},{bufs}"], res[f"{large}.valid@{cap},{bufs}"] = ooff.np()[:n + 1], ov.np()[:n]
-            return st, need.value, [odata]
-        sized(res, f"utf8_{large}", call)
-    return res
-
-
-@case
-def take_bits(E, M, n):
-    idx, valid = _take_idx(n, 25)
-    src = M.put(np.packbits(np.random.default_rng(26).random(N_SRC) < 0.5, bitorder="little"))
-    d_idx, svb = M.put(idx), M.put(valid)
-    out, ov = M.out((n + 7) // 8, np.uint8), M.out(n, np.uint8)
-    st = E.call("ivx_take_bits", M.mem, src.p, u64(N_SRC), svb.p, d_idx.p, u64(n), out.p, ov.p)
-    return {"st": st, "bits": out.np()[:(n + 7) // 8], "valid": ov.np()[:n]}
-
-
-@case
-def take_view(E, M, n):
-    strings = _strings(27)
-    views = np.zeros((N_SRC, 16), np.uint8)
-    bufs = [bytearray(), bytearray()]
-    for i, s in enumerate(strings):
-        views[i, :4] = np.frombuffer(np.uint32(len(s)).tobytes(), np.uint8)
-        if len(s) <= 12:
-            views[i, 4:4 + len(s)] = np.frombuffer(s, np.uint8)
-        else:
-            b = i & 1
-            views[i, 4:8] = np.frombuffer(s[:4], np.uint8)
-            views[i, 8:16] = np.frombuffer(np.array([b, len(bufs[b])], np.uint32).tobytes(), np.uint8)
-            bufs[b] += s
-    idx, valid = _take_idx(n, 28)
-    d_views, d_idx, svb = M.put(views.reshape(-1)), M.put(idx), M.put(valid)
-    d_bufs = [M.put(np.frombuffer(bytes(b), np.uint8)) for b in bufs]
-    table = (C.c_void_p * 2)(*[b.p.value for b in d_bufs])      # a host table of the buffers' pointers, in either mode
-    sizes = (C.c_uint64 * 2)(*[len(b) for b in bufs])
-    head = (M.mem, d_views.p, table, sizes, u32(2), u64(N_SRC), svb.p, d_idx.p, u64(n))
-    res = {}
-
-    def call(cap, with_data):
-        ov16, odata, ov = M.out(16 * n, np.uint8), M.out(cap, np.uint8), M.out(n, np.uint8)
-        need = u64(0xDEAD)
-        st = E.call("ivx_take_view", *head, ov16.p, odata.p if with_data else None, u64(cap), C.byref(need), ov.p)
-        if not with_data and need.value:
-            assert untouched(ov16)                             # the views are withheld when the data did not fit
-        res[f"views@{cap},{with_data}"] = ov16.np()[:16 * n]
-        if st != CAPACITY:                                     # (a short buffer: host mode copies nothing back, device mode has the validity)
-            res[f"valid@{cap},{with_data}"] = ov.np()[:n]
-        return st, need.value, [odata]
-    sized(res, "view", call)
-    return res
-
-
-def _same(a, b):
-    if isinstance(a, np.ndarray):
-        return isinstance(b, np.ndarray) and a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
-    return a == b
+# ------------------------------------------------------------------ 1. host mode equals device mode (the cases: entry_cases.py)
 
 
 @pytest.mark.parametrize("n", SIZES)
