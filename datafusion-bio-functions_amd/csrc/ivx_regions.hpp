@@ -70,12 +70,13 @@ template <class F, class... B> inline void with_bools(F &&f, bool b, B... rest)
 ivx_status ivx_route_flat(ivx_ctx *ctx, const JoinIndexView &jv, const u32 *key, const i32 *s, const i32 *e, u64 n, u32 adj,
                           u32 ndig, bool ids16, u32 max_tiles, ivx_routed *R);
 // one-pass partition into region pages (nreg <= IVX_MAXREG_WIDE).  rowval (per-row-value consumers; always packed, nreg <=
-// IVX_MAXREG): also vtab for the un-permute.  lean: the consumer may run the lean kernels (rest lists, chunk table)
+// IVX_MAXREG): also vtab for the un-permute (no_vtab: a consumer that never un-permutes, the marks: no table, and the
+// 16384-row tiles stay open to it).  lean: the consumer may run the lean kernels (rest lists, chunk table)
 // zero2 (nullable): two 64-bit words of the caller's that the pass's clearing kernel zeroes on the way (a memset launch less)
 // defer_bounds: the regions' first rows and first chunks (R->rfirst, ctl->cfirst: k_chunk_bounds) are not computed and
 // R->tables_due says so; a probe that reads them queues ivx_route_paged_bounds behind the pass first (probe_pairs does, on
 // every way but the lean pair alone: k_fill_fast scans the regions' row counts itself)
-struct ivx_paged_opts { bool filter, packed, rowval, lean; u32 adj; u64 *zero2 = nullptr; bool defer_bounds = false; };
+struct ivx_paged_opts { bool filter, packed, rowval, lean; u32 adj; u64 *zero2 = nullptr; bool defer_bounds = false; bool no_vtab = false; };
 ivx_status ivx_route_paged(ivx_ctx *ctx, const JoinIndexView &jv, u32 nreg, const u32 *key, const i32 *s, const i32 *e, u64 n,
                            const ivx_paged_opts &o, ivx_routed *R);
 ivx_status ivx_route_paged_bounds(ivx_ctx *ctx, const ivx_routed &R, u32 nreg);

@@ -1630,7 +1630,7 @@ ivx_status ivx_mark_probe_regions(ivx_ctx *ctx, const JoinIndexView &jv, u32 nre
     if (n == 0 || nreg == 0 || nreg > IVX_MAXREG || !pk24 || !fast || K.two_pass || K.pack_off || K.lean_off) return IVX_OK;
     hipStream_t st = ctx->stream;
     ivx_routed R;
-    IVX_TRY(ivx_route_paged(ctx, jv, nreg, key, s, e, n, ivx_paged_opts{has_filter && !K.filter_off, true, true, true, 0u}, &R));
+    IVX_TRY(ivx_route_paged(ctx, jv, nreg, key, s, e, n, ivx_paged_opts{has_filter && !K.filter_off, true, true, true, 0u, nullptr, false, true}, &R));
     if (!lean_rows_ok(R)) return IVX_OK;
     hipLaunchKernelGGL((k_mark_fast<IVX_RV_B>), dim3(RP_GRID * (IVX_RV_WPS / 4)), dim3(RP_T), 0, st, jv, R.se, (const u32 *)R.ctl->rcur, (const u32 *)R.ctl->cfirst, R.pt, R.rowbits,
                        R.rest_rows, R.ctl->rest_n, marks);

@@ -471,6 +471,10 @@ constexpr bool part_loads_ahead() { return !(VEC && (I == 12 || (I == 16 && FILT
 // ND digits (256 / 1024), T threads, I rows per thread and tile (tile = T * I rows <= one page).  Packed rows need no
 // slot array in LDS: two 512-thread workgroups with 8192-row tiles then share a CU, and one's loads overlap the other's
 // LDS phases (the kernel is bound by those phases, not by HBM: 8-byte instead of 12-byte rows alone changed nothing)
+// Big batches of the join's packed, unfiltered form take 16384-row tiles in ONE 1024-thread workgroup per CU instead
+// (T = 1024, 153 672 B of LDS; ivx_route_paged): the runs written to HBM double and what a tile pays per REGION -- the
+// rcur atomic, the page look-up, the wtab entry -- is shared by twice the rows, which at 80 M rows and more outweighs the
+// partner workgroup (the rank of a row in its tile still fits the 14 bits beside the digit: 16383)
 // PK: a routed row is ONE 8-byte word, (start inside its region | length) and the row id (route_prep), instead of
 // (start, end) in one array and the row id in another: a third fewer bytes written here and read by the probe
 //
@@ -684,6 +688,13 @@ __global__ __launch_bounds__(256) void k_route_clear(u32 *__restrict__ ctl, u32 
     for (u64 j = i; j < nptab / 4; j += step) p4[j] = make_uint4(0u, 0u, 0u, 0u);
     if (i < (nptab & 3)) ptab[(nptab & ~3ull) + i] = 0;
 }
+
+// the one-pass partition's 16384-row tiles (ivx_route_paged): from this many rows on, this many tiles per workgroup.
+// Measured (profiles/route_bigtile_ab.txt): at 50 M and 64 M rows the form times like the 8192-row one with four tiles
+// per workgroup and is 2-5 % behind it with one or two (one workgroup per CU: nothing covers a workgroup's first tile,
+// the only one not loaded ahead); from 80 M rows on it is ahead, by 3 % at 100 M
+constexpr u64 PART_BIG_ROWS = 80ull * 1000 * 1000;
+constexpr u32 PART_BIG_TILES = 4;
 
 // rows one partition workgroup takes: 1, 2 or 4 tiles, so that mid-size batches still spread over all CUs
 static inline u32 part_chunk(u64 n, u32 max_tiles = 4) { const u32 t = n >= (16u << 20) ? 4u : n >= (4u << 20) ? 2u : 1u; return (u32)PA_TILE * (t < max_tiles ? t : max_tiles); }
@@ -998,7 +1009,16 @@ ivx_status ivx_route_paged(ivx_ctx *ctx, const JoinIndexView &jv, u32 nreg, cons
     hipStream_t st = ctx->stream;
     const bool wide = nreg > IVX_MAXREG;
     const bool half = o.packed && !wide;                                // two 512-thread workgroups per CU, 8192-row tiles
-    const u32 tile = wide ? PA_T * 8u : half ? 512u * 16u : PA_T * 12u;
+    // 16384-row tiles in one 1024-thread workgroup per CU for the join's packed, unfiltered form (fill, count, marks): runs
+    // twice as long, and a tile's cost per region (the rcur atomic, the page look-up) shared by twice the rows.
+    // Only the instantiation that loads ahead without scratch (aligned columns, key tables in LDS, no bitmap), and never
+    // with a vtab: the un-permute indexes it by 8192-row tiles.  From PART_BIG_ROWS rows on.
+    // (tests: IVX_PART_BIG=1 takes it whatever n is and IVX_PART_BIG=0 never, where the other conditions hold)
+    const bool big_ok = half && !o.filter && !(o.rowval && !o.no_vtab) && cols_aligned16(key, s, e) && jv.nkeys <= KT_MAX;
+    bool big = big_ok && n >= PART_BIG_ROWS;
+    if (const char *benv = getenv("IVX_PART_BIG"))
+        if ((benv[0] == '0' || benv[0] == '1') && benv[1] == 0) big = big_ok && benv[0] == '1';
+    const u32 tile = wide ? PA_T * 8u : big ? PA_T * 16u : half ? 512u * 16u : PA_T * 12u;
     u32 rowbits = 1;
     while (rowbits < 32 && (n - 1) >> rowbits) rowbits++;              // bits of the largest row id (the rest of the word's upper half extends the length)
     if (o.filter) rowbits = 32;                                         // (see pk_maxlen)
@@ -1015,7 +1035,7 @@ ivx_status ivx_route_paged(ivx_ctx *ctx, const JoinIndexView &jv, u32 nreg, cons
     IVX_TRY(ctx->get_scratch(WS_T0, (size_t)(npages << lgpg) * sizeof(u64), (void **)&pool));
     // WS_T1: the row ids of unpacked rows, or the un-permute's table, or the lean fill's rest lists (batches, then rows); the
     // lean per-row-value kernel lists single rows only, in WS_T3
-    if (o.rowval) IVX_TRY(ctx->get_scratch(WS_T1, (size_t)ntiles * 256 * sizeof(uint2), (void **)&vtab));
+    if (o.rowval) { if (!o.no_vtab) IVX_TRY(ctx->get_scratch(WS_T1, (size_t)ntiles * 256 * sizeof(uint2), (void **)&vtab)); }
     else if (!o.packed) IVX_TRY(ctx->get_scratch(WS_T1, (size_t)(npages << lgpg) * sizeof(u32), (void **)&prow));
     else if (o.lean) IVX_TRY(ctx->get_scratch(WS_T1, (size_t)fp_max_batches(n, nreg) * sizeof(FpRest) + (size_t)(n + 64) * sizeof(u64), &rest));
     if (rest) { R->rest = (FpRest *)rest; R->rest_rows = (u64 *)(R->rest + fp_max_batches(n, nreg)); }
@@ -1031,7 +1051,7 @@ ivx_status ivx_route_paged(ivx_ctx *ctx, const JoinIndexView &jv, u32 nreg, cons
     // tiles per workgroup: every tile but a workgroup's first finds its first rows loaded ahead (k_part_onepass)
     // (tests: IVX_PART_TILES=t, t in 1, 2, 4, 8, makes it t tiles whatever n is, so that a small batch walks several tiles per
     //  workgroup)
-    u32 tiles = n >= (16u << 20) ? 4u : n >= (4u << 20) ? 2u : 1u;
+    u32 tiles = big ? PART_BIG_TILES : n >= (16u << 20) ? 4u : n >= (4u << 20) ? 2u : 1u;
     if (const char *tenv = getenv("IVX_PART_TILES"))
         if ((tenv[0] == '1' || tenv[0] == '2' || tenv[0] == '4' || tenv[0] == '8') && tenv[1] == 0) tiles = (u32)(tenv[0] - '0');
     const u32 chunk1 = tile * tiles;
@@ -1040,7 +1060,8 @@ ivx_status ivx_route_paged(ivx_ctx *ctx, const JoinIndexView &jv, u32 nreg, cons
         auto part = [&](auto kern, u32 threads) {
             hipLaunchKernelGGL(kern, dim3(nblk1), dim3(threads), 0, st, jv, key, s, e, n, chunk1, ctl->rcur, pt, &ctl->pool_next, pool, prow, rowbits, o.adj, vtab);
         };
-        if (half) part(k_part_onepass<IVX_B(vec), 256, 16, IVX_B(klds), IVX_B(filt), true, 512>, 512u);
+        if (big) part(k_part_onepass<true, 256, 16, true, false, true, PA_T>, (u32)PA_T);
+        else if (half) part(k_part_onepass<IVX_B(vec), 256, 16, IVX_B(klds), IVX_B(filt), true, 512>, 512u);
         else if (wide) part(k_part_onepass<IVX_B(vec), 1024, 8, IVX_B(klds), IVX_B(filt), IVX_B(pk)>, (u32)PA_T);
         else part(k_part_onepass<IVX_B(vec), 256, 12, IVX_B(klds), IVX_B(filt), IVX_B(pk)>, (u32)PA_T);
     }, cols_aligned16(key, s, e), jv.nkeys <= KT_MAX, o.filter, o.packed);
