@@ -28,6 +28,8 @@ WEAK, STRICT = 0, 1
 JOIN_INNER, JOIN_RIGHT_SEMI, JOIN_RIGHT_ANTI = 0, 1, 2
 # (3 = BRH_JOIN_NEAREST, join stream only)  The build-side and outer types: SQL semantics over the build side's match marks
 JOIN_LEFT_SEMI, JOIN_LEFT_ANTI, JOIN_LEFT, JOIN_RIGHT, JOIN_FULL = 4, 5, 6, 7, 8
+# the outputs of overlap_aggregate, in the order of the BRH_AGG_* bits (include/bio_ranges_host.h)
+AGG_OPS = ("count", "sum", "min", "max", "bases", "wsum")
 
 
 class _ArrowSchema(C.Structure):
@@ -199,6 +201,26 @@ class Session:
         finally:
             B.close(); P.close()
         return _import(ba, bs), _import(pa_, ps)
+
+    # ---- overlap aggregates: the join grouped by probe row, a build-side value aggregated (no pairs are made)
+    def overlap_aggregate(self, build, probe, value, ops=AGG_OPS, cols_build=DEFAULT_COLS, cols_probe=DEFAULT_COLS,
+                          strict_predicate=False):
+        """per row of `probe`, over the rows of `build` it overlaps: aggregates of build's column `value` (Int8 .. Int64 or
+        UInt8 .. UInt32) -> a table of Int64 columns named after `ops` (AGG_OPS), one row per probe row in probe order.
+        count and bases are non-null; sum, min, max and wsum are NULL where count is 0."""
+        unknown = [o for o in ops if o not in AGG_OPS]
+        if unknown or not ops:
+            raise BioRangesError(f"overlap_aggregate: ops is a non-empty subset of {AGG_OPS}, got {tuple(ops)}")
+        mask = sum(1 << AGG_OPS.index(o) for o in set(ops))
+        B, P = _Exported(build), _Exported(probe)
+        arrs, schs = (_ArrowArray * len(AGG_OPS))(), (_ArrowSchema * len(AGG_OPS))()
+        try:
+            self._chk(lib().brh_overlap_aggregate(self.h, B.c, _cols(cols_build), value.encode(), P.c, _cols(cols_probe),
+                                                  C.c_int(int(strict_predicate)), C.c_uint32(mask), arrs, schs))
+        finally:
+            B.close(); P.close()
+        got = {o: _import(arrs[i], schs[i]) for i, o in enumerate(AGG_OPS) if mask & (1 << i)}
+        return pa.table({o: got[o] for o in ops})
 
     def sql_range_join(self, build, probe, cols_build=DEFAULT_COLS, cols_probe=DEFAULT_COLS, strict_predicate=False,
                        nearest_algorithm=False, device_take=False):

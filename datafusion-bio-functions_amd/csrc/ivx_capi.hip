@@ -846,6 +846,53 @@ extern "C" ivx_status ivx_probe_mark_build(ivx_ctx *ctx, const ivx_index *ix, in
     return f.st;
 }
 
+// ---------------------------------------------------------------- a3''': overlap aggregates
+
+// Beside ivx_probe_mark_build, and with its path choice: big batches over a lean index take the region kernels
+// (ivx_agg_probe_regions), everything else the direct one.  One value per probe row and wanted output, in input order.
+// The switch between the two, measured (tools/overlap_agg_timing.py, profiles/overlap_agg_timing.txt): the region path's
+// un-permute makes one pass per output, so what it saves on the walk it loses again with every 8-byte output wanted.  By
+// the number of those: the batch size from which the region path won by more than the repeats' spread, or never.
+static u64 agg_regions_rows(int n64)
+{
+    return n64 <= 1 ? 1ull << 23 : n64 <= 3 ? 1ull << 24 : ~0ull;
+}
+extern "C" ivx_status ivx_probe_overlap_agg(ivx_ctx *ctx, const ivx_index *ix, int mem, const uint32_t *key,
+                                            const int32_t *start, const int32_t *end, uint64_t n, const void *val, uint32_t val_bytes,
+                                            uint32_t *count, int64_t *sum, int64_t *vmin, int64_t *vmax, int64_t *bases, int64_t *wsum)
+{
+    Frame f(ctx, mem);
+    IVX_TRY(check_probe_args(f, ix, IVX_KIND_OVERLAP, start, end, n));             // (orders the stream behind a build tail, too)
+    if (!count && !sum && !vmin && !vmax && !bases && !wsum) return ctx->fail(IVX_ERR_INVALID, "overlap_agg: no output wanted");
+    if (val_bytes != 4 && val_bytes != 8) return ctx->fail(IVX_ERR_INVALID, "overlap_agg: val_bytes is 4 or 8");
+    if (ix->n && !val) return ctx->fail(IVX_ERR_INVALID, "overlap_agg: null value column");
+    f.meter(false, n);
+    f.rows_out(n);
+    f.drop_join_plan();                                     // as any other call between a count call and its fill
+    if (n == 0) return IVX_OK;
+    // the override of ivx_probe_mark_build, thresholds of its own
+    const int n64 = (sum != nullptr) + (vmin != nullptr) + (vmax != nullptr) + (bases != nullptr) + (wsum != nullptr);
+    bool regions = ix->jv_nreg > 0 && ix->jv_nreg <= IVX_MAXREG_WIDE && n >= agg_regions_rows(n64);
+    if (const char *p = getenv("IVX_JOIN_PATH")) {
+        if (!strcmp(p, "direct")) regions = false;
+        else if (!strcmp(p, "regions")) regions = ix->jv_nreg > 0 && ix->jv_nreg <= IVX_MAXREG_WIDE;
+    }
+    const u32 *dk = f.in(key, n);
+    const i32 *ds = f.in(start, n), *de = f.in(end, n);
+    const void *dv = f.in((const u8 *)val, (u64)ix->n * val_bytes);
+    AggOut o;
+    o.count = f.out(count, n); o.sum = f.out(sum, n); o.vmin = f.out(vmin, n); o.vmax = f.out(vmax, n);
+    o.bases = f.out(bases, n); o.wsum = f.out(wsum, n);
+    IVX_TRY(f.st);
+    IVX_TRY(f.run([&]() -> ivx_status {
+        bool took = false;
+        if (regions) IVX_TRY(ivx_agg_probe_regions(ctx, ix->jv, ix->jv_nreg, dk, ds, de, n, dv, val_bytes, o, ix->jv_filter, ix->jv_pk24, ix->jv_lean.load(std::memory_order_relaxed) == 1, &took));
+        return took ? IVX_OK : ivx_agg_probe(ctx, ix->jv, dk, ds, de, n, dv, val_bytes, o);
+    }));
+    f.back_all();
+    return f.finish();
+}
+
 extern "C" ivx_status ivx_bits_mark(ivx_ctx *ctx, int mem, const uint32_t *idx, uint64_t n, uint32_t *bits, uint64_t n_bits)
 {
     Frame f(ctx, mem);

@@ -381,6 +381,14 @@ ivx_status ivx_rowval_probe_regions(ivx_ctx *ctx, const JoinIndexView &jv, u32 n
 ivx_status ivx_mark_probe(ivx_ctx *ctx, const JoinIndexView &jv, const u32 *key, const i32 *s, const i32 *e, u64 n, u32 *marks);
 ivx_status ivx_mark_probe_regions(ivx_ctx *ctx, const JoinIndexView &jv, u32 nreg, const u32 *key, const i32 *s, const i32 *e, u64 n,
                                   u32 *marks, bool has_filter, bool pk24, bool fast, bool *took);
+// overlap aggregates (ivx_agg.hip; the lean region form in ivx_regions_probe.hip): per probe row, over the build rows the
+// join pairs it with, aggregates of a build-side value column (val_bytes: 4 or 8, signed).  The call's output columns, one
+// element per probe row in input order; null: not wanted, neither computed nor stored
+struct AggOut { u32 *count; i64 *sum, *vmin, *vmax, *bases, *wsum; };
+ivx_status ivx_agg_probe(ivx_ctx *ctx, const JoinIndexView &jv, const u32 *key, const i32 *s, const i32 *e, u64 n,
+                         const void *val, u32 val_bytes, const AggOut &out);
+ivx_status ivx_agg_probe_regions(ivx_ctx *ctx, const JoinIndexView &jv, u32 nreg, const u32 *key, const i32 *s, const i32 *e, u64 n,
+                                 const void *val, u32 val_bytes, const AggOut &out, bool has_filter, bool pk24, bool fast, bool *took);
 ivx_status ivx_bits_mark_device(ivx_ctx *ctx, const u32 *idx, u64 n, u32 *bits, u64 n_bits);
 ivx_status ivx_bits_select_device(ivx_ctx *ctx, const u32 *bits, u64 n_bits, int want_set, u32 *out, u64 cap, u64 *n_out);
 

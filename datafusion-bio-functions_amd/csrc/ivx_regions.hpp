@@ -85,3 +85,6 @@ ivx_status ivx_route_two_level(ivx_ctx *ctx, const JoinIndexView &jv, u32 nreg, 
 // one u32 value per routed row back into input order, as kind (IVX_RV_*) wants it: FLAT, val[] in routed order; PAGED (rowval),
 // the values sit in the low halves of the rows' own words.  *d_total += the values (IVX_RV_PER_ROW)
 ivx_status ivx_unroute_values(ivx_ctx *ctx, const ivx_routed &R, u32 nreg, int kind, const u32 *val, u64 n, void *out, u64 *d_total, int sorted_done = 0);
+// the overlap aggregates' records back into input order (PAGED, rowval): rec.* are indexed like the page pool, one array per
+// wanted output of `out` (null: not wanted); rows that were never routed get the empty result (0, and the min / max identities)
+ivx_status ivx_unroute_records(ivx_ctx *ctx, const ivx_routed &R, u32 nreg, u64 n, const AggOut &rec, const AggOut &out);

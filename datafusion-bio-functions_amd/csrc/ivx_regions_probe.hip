@@ -16,11 +16,13 @@
 // Host side: region_knobs (the IVX_* environment settings, read once per call), probe_pairs (count / fill over any
 // ivx_routed), and the entry points ivx_join_probe_regions (COUNT / FILL; a COUNT call leaves its routed rows to the
 // FILL call that follows: ivx_join_plan), ivx_rowval_probe_regions (one value per probe row, in input order) and
-// ivx_mark_probe_regions (one bit per matched BUILD row, ORed into the caller's bitmap; lean form only).
+// ivx_mark_probe_regions (one bit per matched BUILD row, ORed into the caller's bitmap; lean form only) and
+// ivx_agg_probe_regions (per probe row, aggregates of a build-side value column; lean form only).
 //
 // HBM traffic per probe row behind the routing: 12 B or 8 B (probe) + 8 B per pair, all streaming (measured:
 // profiles/r1_d_regions_pipeline_pmc.txt).
 #include "ivx_regions.hpp"
+#include "ivx_agg.hpp"
 
 namespace {
 
@@ -1167,6 +1169,84 @@ __global__ __launch_bounds__(256) void k_mark_rest(JoinIndexView ix, const u64 *
     }
 }
 
+// ------------------------------------------------------------------ lean overlap aggregates
+// Per probe row, aggregates of a build-side value over the row's matches (ivx_probe_overlap_agg), over LeanRows and lean_cells
+// as k_rv_fast.  Beside the slice the workgroup stages the slice's VALUES in LDS at slice load, s_val[j] = val[row of slice
+// entry j] (the slice stages no row ids: ix.ent again, as k_mark_fast's sweep), so the candidate loop reads LDS only.  A
+// row's result is up to 44 bytes and no longer fits the low half of its packed word: it goes to a RECORD, one array per
+// wanted output (`rec`, scratch) indexed like the page pool -- the row's word is pool[i], its record rec.*[i] -- so a
+// wavefront's stores are as contiguous as its row loads.  ivx_unroute_records brings the records into input order and gives
+// the rows the routing pass dropped the empty result.  Rows the packed form cannot carry are listed as in k_rv_fast;
+// k_agg_rest walks them with global value reads and writes their records.
+#ifndef IVX_AGG_B
+#define IVX_AGG_B 4
+#endif
+template <int B, int VB, bool MM, bool WT>
+__global__ __launch_bounds__(RP_T, IVX_RV_WPS) void k_agg_fast(JoinIndexView ix, const u64 *__restrict__ pool, const u32 *__restrict__ rcur, const u32 *__restrict__ cfirst,
+                                                   PageTab pt, u32 rowbits, u64 *__restrict__ rest_rows, u32 *rest_n, const void *__restrict__ val, AggOut rec)
+{
+    using VT = typename std::conditional<VB == 4, i32, i64>::type;
+    __shared__ unsigned short s_off[RP_CCAP];
+    __shared__ u64 s_ent[RP_ECAP];
+    __shared__ u32 s_cfirst[IVX_MAXREG_WIDE + 2];
+    __shared__ VT s_val[RP_ECAP];
+    ProbeLds L{s_off, s_ent, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    const u32 ln = lane_id();
+    auto miss = []() {};                                                 // (a page never published: stay in bounds, silently)
+    LeanRows<B, const u64> rows;
+    if (!rows.init(ix, s_cfirst, cfirst, rcur, pt, pool, rowbits)) return;
+    Slice S;
+    slice_init(ix, S, L);
+    rows.start(miss);
+    u32 loaded_r = 0xFFFFFFFFu;
+    for (u32 i = 0; i < rows.nbatch; i++) {
+        const u32 r = rows.r;
+        if (r != loaded_r) {
+            slice_load(ix, S, L, r, true);                               // (its first barrier: nobody reads the old values any more)
+            const u32 ne = ix.rdesc[r].ne;
+            if (S.inlds) for (u32 j = threadIdx.x; j < ne; j += RP_T) s_val[j] = ((const VT *)val)[ix.ent[S.e0 + j].row];
+            __syncthreads();
+            loaded_r = r;
+        }
+        u32 rel[B], len[B], roww[B];                                     // (roww: not used, the un-permute reads the row ids)
+        const auto bt = rows.take(i, rel, len, roww, miss);
+        const u64 at = (u64)(bt.src - pool) + ln;                        // the lane's first row of the batch: its word's place in the pool
+        const i32 rbase = S.rbase;
+        u32 ca[B], cb[B], slow, okm;
+        lean_cells<B>(S, rel, len, rows.maxlen, bt.cnt, ln, ca, cb, slow, okm);
+#pragma unroll
+        for (int q = 0; q < B; q++) {
+            const i32 qs = (i32)((u32)rbase + rel[q]), qe = (i32)((u32)qs + len[q]);
+            AggAcc<MM, WT> a;
+            for (u32 j = ca[q]; j < cb[q]; j++) {
+                const u64 x = s_ent[j];
+                const i32 xs = (i32)(u32)x, xe = (i32)(u32)(x >> 32);
+                if (xs <= qe && xe >= qs) a.add((i64)s_val[j], qs, qe, xs, xe);
+            }
+            if ((okm >> q) & 1u) a.store(rec, at + (u32)q * IVX_WAVE);
+        }
+        if (__builtin_expect(slow != 0, 0)) lean_list_slow<B>(slow, r, bt.first, ln, rest_rows, rest_n);
+    }
+}
+
+template <int VB, bool MM, bool WT>
+__global__ __launch_bounds__(256) void k_agg_rest(JoinIndexView ix, const u64 *__restrict__ pool, PageTab pt, const u64 *__restrict__ rest_rows,
+                                                  const u32 *__restrict__ rest_n, const i32 *__restrict__ ps_in, const i32 *__restrict__ pe_in,
+                                                  u32 rowbits, const void *__restrict__ val, AggOut rec)
+{
+    const u32 nrow = rest_n[1];
+    const u32 sh0 = ix.hdr[HDR_SH0], nlev = ix.hdr[HDR_NLEV];
+    for (u32 i = blockIdx.x * blockDim.x + threadIdx.x; i < nrow; i += gridDim.x * blockDim.x) {
+        const u64 ent = rest_rows[i];
+        const u32 r = (u32)(ent >> 32);
+        const auto e = rest_row(ix, pt, pool, r, (u32)ent, rowbits, ps_in, pe_in, 0u, []() {});
+        const i32 qs = e.qs, qe = e.qe;
+        AggAcc<MM, WT> a;
+        walk_ent(ix, sh0, 0, nlev, ix.rkey[r], qs, qe, [&](const ivx_ent &x) { a.add(agg_val<VB>(val, x.row), qs, qe, x.s, x.e); });
+        a.store(rec, (u64)(e.slot - pool));
+    }
+}
+
 // ------------------------------------------------------------------ match-dense fill: count, scan, write
 // With several pairs per probe row the staging ring holds only one 64-row batch per wavefront and the 16
 // wavefronts of a workgroup end up in lock step, round after round.  For such joins the pairs are written in two
@@ -1636,6 +1716,46 @@ ivx_status ivx_mark_probe_regions(ivx_ctx *ctx, const JoinIndexView &jv, u32 nre
                        R.rest_rows, R.ctl->rest_n, marks);
     hipLaunchKernelGGL(k_mark_rest, dim3(256), dim3(256), 0, st, jv, R.se, R.pt, (const u64 *)R.rest_rows, (const u32 *)R.ctl->rest_n, s, e, R.rowbits, marks);
     IVX_HIP(ctx, hipGetLastError());
+    *took = true;
+    return IVX_OK;
+}
+
+// Per-row aggregates of `val` over each probe row's matches, through the region partition -- the lean form only, as
+// ivx_mark_probe_regions: *took = false (nothing launched, no scratch taken) when the index or the settings do not qualify,
+// and the caller runs the direct kernel (ivx_agg_probe).  The outputs are device columns in input order.
+ivx_status ivx_agg_probe_regions(ivx_ctx *ctx, const JoinIndexView &jv, u32 nreg, const u32 *key, const i32 *s, const i32 *e, u64 n,
+                                 const void *val, u32 val_bytes, const AggOut &out, bool has_filter, bool pk24, bool fast, bool *took)
+{
+    *took = false;
+    const RegionKnobs K = region_knobs();
+    if (n == 0 || nreg == 0 || nreg > IVX_MAXREG || !pk24 || !fast || K.two_pass || K.pack_off || K.lean_off) return IVX_OK;
+    hipStream_t st = ctx->stream;
+    ivx_routed R;
+    IVX_TRY(ivx_route_paged(ctx, jv, nreg, key, s, e, n, ivx_paged_opts{has_filter && !K.filter_off, true, true, true, 0u}, &R));
+    if (!lean_rows_ok(R)) return IVX_OK;
+    // the records: one array per wanted output, a cell per word of the page pool (ivx_route_paged's own size of it)
+    const u64 cells = ((n >> R.pt.lgpg) + nreg + 1) << R.pt.lgpg;
+    const int n64 = (out.sum != nullptr) + (out.vmin != nullptr) + (out.vmax != nullptr) + (out.bases != nullptr) + (out.wsum != nullptr);
+    u8 *buf;
+    IVX_TRY(ctx->get_scratch(WS_T4, (size_t)cells * (8u * (size_t)n64 + (out.count ? 4u : 0u)), (void **)&buf));
+    AggOut rec{};
+    auto carve = [&](auto *&p, const void *wanted) {
+        if (!wanted) return;
+        p = reinterpret_cast<std::remove_reference_t<decltype(p)>>(buf);
+        buf += cells * sizeof(*p);
+    };
+    carve(rec.sum, out.sum); carve(rec.vmin, out.vmin); carve(rec.vmax, out.vmax); carve(rec.bases, out.bases); carve(rec.wsum, out.wsum);
+    carve(rec.count, out.count);                                        // (the 4-byte array last: the others stay 8-byte aligned)
+    const bool mm = out.vmin || out.vmax, wt = out.bases || out.wsum;
+    with_bools([&](auto wide, auto m, auto w) {
+        constexpr int VB = IVX_B(wide) ? 8 : 4;
+        hipLaunchKernelGGL((k_agg_fast<IVX_AGG_B, VB, IVX_B(m), IVX_B(w)>), dim3(RP_GRID * (IVX_RV_WPS / 4)), dim3(RP_T), 0, st, jv, R.se, (const u32 *)R.ctl->rcur,
+                           (const u32 *)R.ctl->cfirst, R.pt, R.rowbits, R.rest_rows, R.ctl->rest_n, val, rec);
+        hipLaunchKernelGGL((k_agg_rest<VB, IVX_B(m), IVX_B(w)>), dim3(256), dim3(256), 0, st, jv, R.se, R.pt, (const u64 *)R.rest_rows, (const u32 *)R.ctl->rest_n, s, e,
+                           R.rowbits, val, rec);
+    }, val_bytes == 8, mm, wt);
+    IVX_HIP(ctx, hipGetLastError());
+    IVX_TRY(ivx_unroute_records(ctx, R, nreg, n, rec, out));
     *took = true;
     return IVX_OK;
 }

@@ -17,8 +17,8 @@
 //                        k_page_bounds / k_chunk_bounds   the regions' first rows (and first 8192-row chunks)
 //   ivx_route_two_level  k_part_*<SPLIT> + k_p2_* + k_sorted_bounds   more regions than one digit holds
 //
-// and the way back for consumers that answer per row: k_unpermute / k_unpermute_paged / k_unpermute_pair
-// (ivx_unroute_*).  ivx_route_rows is the flat form for operators with a probe kernel of their own (nearest, the
+// and the way back for consumers that answer per row: k_unpermute / k_unpermute_paged / k_unpermute_pair /
+// k_unpermute_records (ivx_unroute_*).  ivx_route_rows is the flat form for operators with a probe kernel of their own (nearest, the
 // rank-grid operators, the join's per-row counts over many regions).
 //
 // HBM traffic per probe row of the flat form: 8 B (hist) + 12 B + 12 B (scatter), all streaming (measured:
@@ -810,6 +810,61 @@ __global__ __launch_bounds__(512) void k_unpermute_paged(const u64 *__restrict__
     if (OUT == UP_U32 && total) { const u64 b = block_sum<u64, T>(mysum, s_sum); if (tid == 0 && b) atomicAdd(total, (unsigned long long)b); }
 }
 
+// The record-wide sibling (the overlap aggregates: a row's result does not fit its word).  rec.* hold one value per word of
+// the page pool, at the word's own index; the tile's words are walked as above, once per wanted output: the output's records
+// are dropped at row - tile start in LDS, over the empty result's value for the rows that were never routed, and written out
+// in input order.  The words' second and later reads hit the cache (64 KB a tile).
+template <int TILE>
+__global__ __launch_bounds__(512) void k_unpermute_records(const u64 *__restrict__ pool, const uint2 *__restrict__ vtab, PageTab pt, u32 nreg, u32 rowbits,
+                                                           u64 n, AggOut rec, AggOut out)
+{
+    constexpr int T = 512, ND = 256;
+    __shared__ u64 s_val[TILE];
+    __shared__ u32 s_pre[ND + 1], s_v[ND], s_pg0[ND];
+    __shared__ u32 scan_lds[T / IVX_WAVE + 1];
+    const u32 tid = threadIdx.x;
+    const u64 t0 = (u64)blockIdx.x * TILE;
+    const u32 len = (u32)(t0 + TILE < n ? (u64)TILE : n - t0);
+    const u32 rowmask = rowbits >= 32 ? 0xFFFFFFFFu : (1u << rowbits) - 1u;
+    const u32 pmask = (1u << pt.lgpg) - 1u;
+    u32 v = 0, c = 0;
+    if (tid < nreg) { const uint2 vc = vtab[(u64)blockIdx.x * ND + tid]; v = vc.x; c = vc.y; }
+    u32 tot;
+    const u32 ex = block_excl_scan<u32, T>(c, scan_lds, &tot);
+    if (tid < ND) { s_pre[tid] = ex; s_v[tid] = v; s_pg0[tid] = c ? pt.ptab[(u64)tid * pt.pstride + (v >> pt.lgpg)] - 1u : 0u; }
+    if (tid == 0) s_pre[ND] = tot;
+    const u32 wv = tid / IVX_WAVE, ln = lane_id();
+    const u32 per = (tot + T / IVX_WAVE - 1) / (T / IVX_WAVE);
+    const u32 j_lo = wv * per, j_hi = j_lo + per < tot ? j_lo + per : tot;
+    // one output: src = its records, dst = the caller's column (null: not wanted; the same for every thread)
+    auto pass = [&](auto *src, auto *dst, u64 none) {
+        using E = std::remove_pointer_t<decltype(dst)>;
+        if (dst == nullptr) return;
+        for (u32 t = tid; t < TILE; t += T) s_val[t] = none;
+        __syncthreads();                                        // (the first pass: s_pre / s_v / s_pg0 are complete behind it, too)
+        u32 r = 0;
+        if (j_lo < j_hi) { u32 a = 0, b = ND; while (a < b) { const u32 m = (a + b + 1) >> 1; if (m < ND && s_pre[m] <= j_lo + ln) a = m; else b = m - 1; } r = a; }
+        for (u32 j = j_lo + ln; j < j_hi; j += IVX_WAVE) {
+            while (r + 1 < ND && s_pre[r + 1] <= j) r++;
+            const u32 x = s_v[r] + (j - s_pre[r]);                  // virtual row number in region r
+            u32 pg = s_pg0[r];
+            if ((x >> pt.lgpg) != (s_v[r] >> pt.lgpg)) pg = pt.ptab[(u64)r * pt.pstride + (x >> pt.lgpg)] - 1u;   // the run's second page
+            const u64 at = ((u64)pg << pt.lgpg) + (x & pmask);
+            const u32 slot = ((u32)(pool[at] >> 32) & rowmask) - (u32)t0;
+            if (slot < (u32)TILE) s_val[slot] = (u64)src[at];
+        }
+        __syncthreads();
+        for (u32 t = tid; t < len; t += T) dst[t0 + t] = (E)s_val[t];
+        __syncthreads();
+    };
+    pass(rec.count, out.count, 0ull);
+    pass(rec.sum, out.sum, 0ull);
+    pass(rec.vmin, out.vmin, (u64)INT64_MAX);
+    pass(rec.vmax, out.vmax, (u64)INT64_MIN);
+    pass(rec.bases, out.bases, 0ull);
+    pass(rec.wsum, out.wsum, 0ull);
+}
+
 // two values per row back into input order: the un-permute above for (u32, i64) pairs with one-tile chunks; rows that
 // were never routed get (IVX_NULL_IDX, dflt); op = the row's own index; vb / ob / op may be null (one i64 value per row)
 __global__ __launch_bounds__(PA_T) void k_unpermute_pair(const u32 *__restrict__ vb, const i64 *__restrict__ vd, const unsigned short *__restrict__ cidx,
@@ -1176,6 +1231,15 @@ ivx_status ivx_unroute_u32(ivx_ctx *ctx, const ivx_routed &r, u64 n, const u32 *
 ivx_status ivx_unroute_pair(ivx_ctx *ctx, const ivx_routed &r, u64 n, const u32 *vb, const i64 *vd, u32 *ob, u32 *op, i64 *od, i64 dflt)
 {
     hipLaunchKernelGGL(k_unpermute_pair, dim3(r.nblk), dim3(PA_T), 0, ctx->stream, vb, vd, r.cidx, r.rfirst, r.nblk, n, ob, op, od, r.unsorted, dflt);
+    IVX_HIP(ctx, hipGetLastError());
+    return IVX_OK;
+}
+
+ivx_status ivx_unroute_records(ivx_ctx *ctx, const ivx_routed &R, u32 nreg, u64 n, const AggOut &rec, const AggOut &out)
+{
+    if (R.form != IVX_ROWS_PAGED || R.vtab == nullptr || nreg > IVX_MAXREG) return ctx->fail(IVX_ERR_INVALID, "internal error: records are un-permuted from region pages with a tile table");
+    constexpr u32 TILE = 512u * 16u;                                    // the one-pass partition's tile for packed rows
+    hipLaunchKernelGGL((k_unpermute_records<(int)TILE>), dim3((u32)((n + TILE - 1) / TILE)), dim3(512), 0, ctx->stream, R.se, R.vtab, R.pt, nreg, R.rowbits, n, rec, out);
     IVX_HIP(ctx, hipGetLastError());
     return IVX_OK;
 }

@@ -571,6 +571,90 @@ extern "C" int brh_interval_join(brh_session *s, brh_batch build, brh_columns bc
     return 0;
 }
 
+// ---- overlap aggregates: join on overlap, group by probe row, aggregate a build-side value (ivx.h ivx_probe_overlap_agg)
+namespace {
+
+// the build side's value column, widened to what the device takes: int32 (Int8, Int16, Int32, UInt8, UInt16) or int64
+// (UInt32, Int64).  Everything else is refused by name
+int load_agg_values(brh_session *s, brh_batch t, const char *name, std::vector<int32_t> *v32, std::vector<int64_t> *v64, uint32_t *val_bytes)
+{
+    const int c = find_col(t.schema, name);
+    if (c < 0) return fail(s, "overlap_aggregate: value column '" + std::string(name) + "' not found in batch with columns: " + column_list(t.schema));
+    const char *f = t.schema->children[c]->format;
+    const std::string what = "overlap_aggregate: unsupported data type " + std::string(f) + " for value column '" + name + "'";
+    if (!std::strcmp(f, "L")) return fail(s, what + ": UInt64 values do not fit the Int64 aggregates");
+    if (!std::strcmp(f, "e") || !std::strcmp(f, "f") || !std::strcmp(f, "g"))
+        return fail(s, what + ": float values are not supported (their sums would not be bit-reproducible)");
+    if (std::strlen(f) != 1 || !std::strchr("csilCSI", f[0])) return fail(s, what + "; expected Int8, Int16, Int32, Int64, UInt8, UInt16 or UInt32");
+    const ArrowArray *a = t.array->children[c];
+    if (null_count(a) > 0) return fail(s, "overlap_aggregate: value column '" + std::string(name) + "' contains null values");
+    const int64_t n = a->length, o = a->offset;
+    const void *d = a->n_buffers >= 2 ? a->buffers[1] : nullptr;
+    const bool wide = f[0] == 'l' || f[0] == 'I';
+    *val_bytes = wide ? 8u : 4u;
+    if (wide) v64->resize((size_t)n); else v32->resize((size_t)n);
+    for (int64_t i = 0; i < n; i++) {
+        switch (f[0]) {
+        case 'c': (*v32)[i] = ((const int8_t *)d)[o + i]; break;
+        case 's': (*v32)[i] = ((const int16_t *)d)[o + i]; break;
+        case 'i': (*v32)[i] = ((const int32_t *)d)[o + i]; break;
+        case 'C': (*v32)[i] = ((const uint8_t *)d)[o + i]; break;
+        case 'S': (*v32)[i] = ((const uint16_t *)d)[o + i]; break;
+        case 'I': (*v64)[i] = ((const uint32_t *)d)[o + i]; break;
+        default: (*v64)[i] = ((const int64_t *)d)[o + i]; break;
+        }
+    }
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int brh_overlap_aggregate(brh_session *s, brh_batch build, brh_columns bcols, const char *value_column,
+                                     brh_batch probe, brh_columns pcols, int strict_predicate, uint32_t ops,
+                                     ArrowArray *out, ArrowSchema *out_schema)
+{
+    if (!s) return 1;
+    if (!value_column) return fail(s, "overlap_aggregate: null value column name");
+    if (!out || !out_schema) return fail(s, "overlap_aggregate: null outputs");
+    if (ops == 0 || (ops & ~(uint32_t)BRH_AGG_ALL)) return fail(s, "overlap_aggregate: ops is a non-empty set of BRH_AGG_* bits");
+    KeyDict kd; Side32 B, P;
+    std::vector<int32_t> v32; std::vector<int64_t> v64; uint32_t vb = 4;
+    if (load_agg_values(s, build, value_column, &v32, &v64, &vb)) return 1;
+    if (build_keys(s, {{build, bcols}, {probe, pcols}}, &kd, true) || load_side32(s, build, bcols, &B) || load_side32(s, probe, pcols, &P)) return 1;
+    if (strict_predicate) {                                       // as brh_interval_join: end - 1 on both sides, and the lengths follow
+        for (auto &v : B.e) v = (int32_t)((uint32_t)v - 1u);
+        for (auto &v : P.e) v = (int32_t)((uint32_t)v - 1u);
+    }
+    const uint32_t nk = (uint32_t)std::max<size_t>(kd.names.size(), 1);
+    IndexGuard g;
+    ivx_status st = ivx_index_build(s->ctx, IVX_KIND_OVERLAP, IVX_MEM_HOST, kd.ids[0].data(), B.s.data(), B.e.data(), B.s.size(), nk, &g.ix);
+    if (st != IVX_OK) return fail_ivx(s, st);
+    const uint64_t np = P.s.size(), na = np ? np : 1;
+    // the count says where sum / min / max / wsum are NULL: fetched whenever one of them is wanted
+    const bool nullable = (ops & (BRH_AGG_SUM | BRH_AGG_MIN | BRH_AGG_MAX | BRH_AGG_WSUM)) != 0;
+    std::vector<uint32_t> cnt((ops & BRH_AGG_COUNT) || nullable ? na : 0);
+    std::vector<int64_t> col[BRH_AGG_N];
+    for (int k = 1; k < BRH_AGG_N; k++) if (ops & (1u << k)) col[k].resize(na);
+    auto ptr = [&](int k) { return col[k].empty() ? nullptr : col[k].data(); };
+    const void *val = vb == 4 ? (const void *)v32.data() : (const void *)v64.data();     // (may be null for an empty build side: never read)
+    st = ivx_probe_overlap_agg(s->ctx, g.ix, IVX_MEM_HOST, kd.ids[1].data(), P.s.data(), P.e.data(), np, val, vb,
+                               cnt.empty() ? nullptr : cnt.data(), ptr(1), ptr(2), ptr(3), ptr(4), ptr(5));
+    if (st != IVX_OK) return fail_ivx(s, st);
+    std::vector<uint8_t> valid(nullable ? na : 0);
+    for (uint64_t i = 0; nullable && i < np; i++) valid[i] = cnt[i] != 0;
+    static const char *const names[BRH_AGG_N] = {"count", "sum", "min", "max", "bases", "wsum"};
+    for (int k = 0; k < BRH_AGG_N; k++) {
+        std::memset(&out[k], 0, sizeof out[k]); std::memset(&out_schema[k], 0, sizeof out_schema[k]);
+        if (!(ops & (1u << k))) continue;
+        const bool nulls = k != 0 && k != 4;                      // count and bases: 0 without a match; the others NULL, as SQL over a left join
+        if (k == 0) { col[0].resize(na); for (uint64_t i = 0; i < np; i++) col[0][i] = (int64_t)cnt[i]; }
+        else if (nulls) for (uint64_t i = 0; i < np; i++) if (!valid[i]) col[k][i] = 0;     // (a NULL slot's value)
+        make_primitive<int64_t>(&out[k], col[k].data(), (int64_t)np, nulls ? valid.data() : nullptr);
+        make_schema(&out_schema[k], "l", names[k], nulls);
+    }
+    return 0;
+}
+
 extern "C" int brh_merge(brh_session *s, brh_batch table, brh_columns cols, int64_t min_dist, int filter_op,
                          ArrowArray *contig, ArrowSchema *contig_schema, ArrowArray *start, ArrowSchema *start_schema,
                          ArrowArray *end, ArrowSchema *end_schema, ArrowArray *n_intervals, ArrowSchema *n_schema)

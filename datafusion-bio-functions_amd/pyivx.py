@@ -28,7 +28,7 @@ SYMBOLS = [
     "ivx_cluster", "ivx_complement", "ivx_take_fixed", "ivx_take_utf8", "ivx_take_bits", "ivx_take_view",
     "ivx_ctx_metrics", "ivx_ctx_reset_metrics", "ivx_ctx_set_memory_limit", "ivx_ctx_trim", "ivx_scatter_fixed",
     "ivx_ctx_reserved_bytes", "ivx_ctx_set_build_overlap", "ivx_index_layout",
-    "ivx_probe_mark_build", "ivx_bits_mark", "ivx_bits_select", "ivx_depth",
+    "ivx_probe_mark_build", "ivx_bits_mark", "ivx_bits_select", "ivx_depth", "ivx_probe_overlap_agg",
     "ivx_depth_profile_build", "ivx_depth_profile_free", "ivx_depth_profile_steps", "ivx_depth_profile_device_bytes",
     "ivx_depth_profile_read", "ivx_depth_profile_expand", "ivx_depth_profile_merge", "ivx_depth_profile_blocks",
     "ivx_cigar_parse", "ivx_depth_text", "ivx_depth_profile_build_text",
@@ -54,6 +54,9 @@ DEPTH_MAX_QUANTILES = 8
 # bytes one thread / one workgroup of the text-CIGAR parser takes (csrc/ivx_cigar.hip CIGAR_B, CIGAR_TILE)
 CIGAR_B = 16
 CIGAR_TILE = 4096
+
+# outputs of ivx_probe_overlap_agg, in the order of its pointers, and their element types
+AGG_OUTPUTS = ("count", "sum", "min", "max", "bases", "wsum")
 
 # slots of ivx_index_layout (include/ivx.h IVX_LAYOUT_*), in order
 LAYOUT_SLOTS = ["kind", "sh0", "nlev", "levrows", "rcells", "rcs", "nreg", "pk24", "slow", "fg", "fbits", "nroute_nreg", "lbuild"]
@@ -119,6 +122,8 @@ def lib():
         L.ivx_index_rows.restype = C.c_uint64
         L.ivx_index_device_bytes.restype = C.c_uint64
         L.ivx_ctx_reserved_bytes.restype = C.c_uint64
+        L.ivx_probe_overlap_agg.restype = C.c_int
+        L.ivx_probe_overlap_agg.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 3 + [C.c_uint64, C.c_void_p, C.c_uint32] + [C.c_void_p] * 6
         L.ivx_depth.restype = C.c_int
         L.ivx_depth.argtypes = ([C.c_void_p, C.c_int] + [C.c_void_p] * 6 + [C.c_uint64] + [C.c_void_p] * 4 + [C.c_uint64] +
                                 [C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32] + [C.c_void_p] * 4 +
@@ -571,6 +576,43 @@ class Ctx:
             raise ValueError("mix of host and device buffers in one call")
         self._chk(lib().ivx_probe_mark_build(self.h, ix.h, C.c_int(mem), _ptr(key), _ptr(s), _ptr(e), C.c_uint64(n), _ptr(marks)))
         return marks
+
+    # ---- a3''': overlap aggregates ----
+    def overlap_agg(self, ix, key, start, end, val, outputs=AGG_OUTPUTS):
+        """per probe row, over the build rows the join pairs it with: aggregates of `val` (one int32 or int64 per build row
+        of `ix`) -> {name: column} for the names in `outputs` (AGG_OUTPUTS): "count" uint32, the others int64 (min / max of
+        a row without a match: INT64_MAX / INT64_MIN).  numpy arrays, or device tensors ("count" then as its int32 bits)."""
+        key, s, e, n, mem = _cols(key, start, end, np.int32)
+        unknown = [o for o in outputs if o not in AGG_OUTPUTS]
+        if unknown:
+            raise ValueError(f"overlap_agg: unknown outputs {unknown}")
+        if val is not None and _is_torch(val) != (mem == MEM_DEVICE):
+            raise ValueError("mix of host and device buffers in one call")
+        vb = 8
+        if val is not None:
+            if mem == MEM_DEVICE:
+                import torch
+                if val.dtype not in (torch.int32, torch.int64) or not val.is_contiguous():
+                    raise ValueError("overlap_agg: val is a contiguous int32 or int64 tensor")
+                vb = 4 if val.dtype == torch.int32 else 8
+            else:
+                val = np.asarray(val)
+                if val.dtype not in (np.dtype(np.int32), np.dtype(np.int64)):
+                    raise ValueError("overlap_agg: val is an int32 or int64 array")
+                val = np.ascontiguousarray(val)
+                vb = val.dtype.itemsize
+        out = {}
+        for name in AGG_OUTPUTS:
+            if name not in outputs:
+                out[name] = None
+            elif mem == MEM_DEVICE:
+                import torch
+                out[name] = torch.empty(max(n, 1), dtype=torch.int32 if name == "count" else torch.int64, device=s.device)
+            else:
+                out[name] = np.empty(max(n, 1), np.uint32 if name == "count" else np.int64)
+        self._chk(lib().ivx_probe_overlap_agg(self.h, ix.h, mem, _ptr(key), _ptr(s), _ptr(e), n, _ptr(val), vb,
+                                              *[_ptr(out[name]) for name in AGG_OUTPUTS]))
+        return {name: out[name][:n] for name in AGG_OUTPUTS if out[name] is not None}
 
     def bits_mark(self, idx, bits, n_bits):
         """OR bit idx[i] into `bits` (NULL_IDX skipped, anything else >= n_bits raises ERR_INVALID); -> bits"""

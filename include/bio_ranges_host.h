@@ -101,6 +101,24 @@ int brh_interval_join(brh_session *s, brh_batch build, brh_columns bcols, brh_ba
                       struct ArrowArray *build_idx, struct ArrowSchema *build_idx_schema,
                       struct ArrowArray *probe_idx, struct ArrowSchema *probe_idx_schema);
 
+/* Overlap aggregates: join `probe` to `build` on overlap (same keys, closed intervals), group by probe row and aggregate the
+ * build side's `value_column` -- SELECT p.*, COUNT(*), SUM(b.v), MIN(b.v), MAX(b.v) ... GROUP BY the probe row, bedtools map,
+ * the mean of a signal track over targets -- in one ivx_probe_overlap_agg call: no pair is ever made.  The reference has no
+ * counterpart.  Tables and strict_predicate as in brh_interval_join (end - 1 on both sides; bases and wsum are computed on
+ * the adjusted coordinates).
+ * The value column is Int8 .. Int64 or UInt8 .. UInt32, widened to int32 or int64 on the host; UInt64, floats (their sums
+ * would not be bit-reproducible) and value columns with nulls are refused, each with its own message.
+ * ops: a non-empty set of BRH_AGG_* bits.  out / out_schema: arrays of BRH_AGG_N slots in the order of the bits; the slot of
+ * an op that was not asked for stays released (zeroed).  Every output is an Int64 column with one value per probe row, in
+ * probe order: count (matches) and bases (sum over the matches of the closed overlap length) are non-null, 0 without a match;
+ * sum, min, max and wsum (sum of value * overlap length) are NULL where count is 0, as in SQL over a left join.  Sums wrap
+ * in int64. */
+enum { BRH_AGG_COUNT = 1, BRH_AGG_SUM = 2, BRH_AGG_MIN = 4, BRH_AGG_MAX = 8, BRH_AGG_BASES = 16, BRH_AGG_WSUM = 32,
+       BRH_AGG_ALL = 63, BRH_AGG_N = 6 };
+int brh_overlap_aggregate(brh_session *s, brh_batch build, brh_columns bcols, const char *value_column,
+                          brh_batch probe, brh_columns pcols, int strict_predicate, uint32_t ops,
+                          struct ArrowArray *out, struct ArrowSchema *out_schema);
+
 /* merge('table'[,min_dist]...): MergeProvider/MergeStream (R/src/merge.rs:84-112, :263-350).
  * Outputs contig Utf8, start Int64, end Int64, n_intervals Int64. */
 int brh_merge(brh_session *s, brh_batch table, brh_columns cols, int64_t min_dist, int filter_op,

@@ -238,6 +238,29 @@ ivx_status ivx_bits_mark(ivx_ctx *ctx, int mem, const uint32_t *idx, uint64_t n,
 ivx_status ivx_bits_select(ivx_ctx *ctx, int mem, const uint32_t *bits, uint64_t n_bits, int want_set,
                            uint32_t *out, uint64_t cap, uint64_t *n_out);
 
+/* a3''': overlap aggregates -- join on overlap, group by probe row, aggregate a build-side value (SQL's COUNT / SUM / MIN /
+ *      MAX over the join, bedtools map, the mean of a signal track over targets) without ever writing a pair.  The reference
+ *      has no counterpart; the contract is stated against the join's own pairs.  Index kind OVERLAP.
+ *      `val` is one signed integer per BUILD row, val_bytes = 4 (int32, sign-extended) or 8 (int64), ivx_index_rows(ix)
+ *      elements, living where `mem` says.  For probe row i let M(i) be exactly the build rows ivx_probe_overlap_fill pairs
+ *      with i for the same (already adjusted) columns: same key, bs <= qe && be >= qs.  Then, one element per probe row in
+ *      input order:
+ *        count[i] = |M(i)|                       (uint32; what ivx_probe_overlap_count's per_row gives)
+ *        sum[i]   = sum of val[b] over M(i)      (int64, two's-complement wrapping)
+ *        vmin[i], vmax[i]                        (int64, signed; INT64_MAX / INT64_MIN when M(i) is empty)
+ *        bases[i] = sum of len(b, i)             with len = min(qe, be) - max(qs, bs) + 1 in int64, not clamped (the plain
+ *                                                closed count: neither coverage's formula nor a union)
+ *        wsum[i]  = sum of val[b] * len(b, i)    (int64, wrapping)
+ *      A row without a match gets count, sum, bases and wsum 0 and the two identities, on every path.
+ *      Every output pointer may be NULL: only the others are computed and stored.  All six NULL, val = NULL with a non-empty
+ *      index, or val_bytes other than 4 or 8: IVX_ERR_INVALID.  Another index kind: IVX_ERR_UNSUPPORTED.  n = 0 is a no-op.
+ *      The call waits for an index whose build tail still runs, drops the state a count call left for its fill call, and
+ *      feeds ivx_ctx_metrics like ivx_probe_count: one input batch, n input and n output rows. */
+ivx_status ivx_probe_overlap_agg(ivx_ctx *ctx, const ivx_index *ix, int mem,
+                                 const uint32_t *key, const int32_t *start, const int32_t *end, uint64_t n,
+                                 const void *val, uint32_t val_bytes,
+                                 uint32_t *count, int64_t *sum, int64_t *vmin, int64_t *vmax, int64_t *bases, int64_t *wsum);
+
 /* ---- a4: CountOverlapIndex::query_count in get_count_stream
  *      (interval_tree.rs:41-49, :249-267).  Index kind COUNT. */
 ivx_status ivx_probe_count(ivx_ctx *ctx, const ivx_index *ix, int mem,

@@ -67,6 +67,11 @@ extern "C" {
     pub fn ivx_bits_mark(ctx: *mut IvxCtx, mem: i32, idx: *const u32, n: u64, bits: *mut u32, n_bits: u64) -> i32;
     pub fn ivx_bits_select(ctx: *mut IvxCtx, mem: i32, bits: *const u32, n_bits: u64, want_set: i32, out: *mut u32,
                            cap: u64, n_out: *mut u64) -> i32;
+    // overlap aggregates: per probe row, count / sum / min / max / bases / weighted sum of a build-side value column
+    // (val: i32 or i64 by val_bytes); every output nullable
+    pub fn ivx_probe_overlap_agg(ctx: *mut IvxCtx, ix: *const IvxIndex, mem: i32, key: *const u32, start: *const i32,
+                                 end: *const i32, n: u64, val: *const c_void, val_bytes: u32, count: *mut u32,
+                                 sum: *mut i64, vmin: *mut i64, vmax: *mut i64, bases: *mut i64, wsum: *mut i64) -> i32;
     pub fn ivx_probe_count(ctx: *mut IvxCtx, ix: *const IvxIndex, mem: i32, key: *const u32, start: *const i32,
                            end: *const i32, n: u64, strict: i32, out: *mut i64) -> i32;
     pub fn ivx_probe_coverage(ctx: *mut IvxCtx, ix: *const IvxIndex, mem: i32, key: *const u32, start: *const i32,
