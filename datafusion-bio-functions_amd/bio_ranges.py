@@ -424,6 +424,39 @@ class Session:
                 if t is not None:
                     t.close()
 
+    def depth_quantize(self, reads, cuts, emit=None, prior=None, lengths=None, zero_based=False, end_exclusive=False, touched_only=False,
+                       filter_flag=1796, min_mapq=0):
+        """the maximal intervals whose depth stays in one bin (mosdepth --quantize; "the intervals at 10x or more"): bin(v) =
+        the number of `cuts` (ascending, at most 31) that are <= v.  emit: the bins to return (None: all); the others still
+        separate their neighbours.  -> contig Utf8, start Int64, end Int64 (inclusive; half-open with end_exclusive: mosdepth's
+        BED is zero_based + end_exclusive), bin Int32, ordered by (contig, start).  reads / prior / lengths and the domain as for
+        depth_regions(); touched_only: only contigs that kept a read."""
+        tabs = [_Exported(t) if t is not None else None for t in (reads, prior, lengths)]
+        try:
+            b = [t.c if t is not None else _Batch(None, None) for t in tabs]
+            return _quantize_call(self, cuts, emit, lambda *a: lib().brh_depth_quantize(
+                self.h, b[0], b[1], b[2], C.c_int(int(bool(zero_based))), C.c_int(int(bool(end_exclusive))), C.c_int(int(bool(touched_only))),
+                C.c_uint32(int(filter_flag)), C.c_uint32(int(min_mapq)), *a))
+        finally:
+            for t in tabs:
+                if t is not None:
+                    t.close()
+
+    def depth_dist(self, reads, v_lo=0, n_bins=256, prior=None, lengths=None, zero_based=False, touched_only=False, filter_flag=1796, min_mapq=0):
+        """the bases of every contig at each depth (bedtools genomecov, mosdepth's dist): -> contig Utf8, coverage Int32, bases
+        Int64, one row per contig and depth with bases > 0, ordered by (contig, coverage).  The depths are v_lo .. v_lo + n_bins
+        - 1; the first stands for "v_lo or less", the last for "that or more".  The rest as for depth_quantize()."""
+        tabs = [_Exported(t) if t is not None else None for t in (reads, prior, lengths)]
+        try:
+            b = [t.c if t is not None else _Batch(None, None) for t in tabs]
+            return _dist_call(self, lambda *a: lib().brh_depth_dist(
+                self.h, b[0], b[1], b[2], C.c_int(int(bool(zero_based))), C.c_int(int(bool(touched_only))),
+                C.c_uint32(int(filter_flag)), C.c_uint32(int(min_mapq)), C.c_int32(int(v_lo)), C.c_uint32(int(n_bins)), *a))
+        finally:
+            for t in tabs:
+                if t is not None:
+                    t.close()
+
     def depth_stream(self, lengths=None, filter_flag=1796, min_mapq=0):
         """depth() over a stream of read batches (brh_depth_push): -> DepthStream"""
         return DepthStream(self, lengths, filter_flag, min_mapq)
@@ -457,6 +490,32 @@ def _quantiles_call(session, regions, q_num, q_den, call):
     for j, t in enumerate(qn):
         out = out.append_column(f"q_{t}_{int(q_den)}", _import(q[j], q_s[j]))
     return out
+
+
+def _quantize_call(session, cuts, emit, call):
+    """the cuts, the emit mask and the output structs of brh_depth_quantize / brh_depth_push_quantize -> the interval table"""
+    c = [int(x) for x in cuts]
+    n = len(c)
+    if emit is None:
+        mask = (1 << (n + 1)) - 1 if n < 32 else 0xFFFFFFFF
+    elif isinstance(emit, int):
+        mask = emit
+    else:
+        mask = 0
+        for j in emit:
+            mask |= 1 << int(j)
+    if mask >> 32:
+        raise BioRangesError("depth_quantize() emit names a bin above 31")
+    ccuts = (C.c_int32 * max(n, 1))(*c)
+    outs = [_out() for _ in range(4)]
+    session._chk(call(ccuts, C.c_uint32(n), C.c_uint32(mask), *[C.byref(x) for pair in outs for x in pair]))
+    return pa.table([_import(*o) for o in outs], names=["contig", "start", "end", "bin"])
+
+
+def _dist_call(session, call):
+    outs = [_out() for _ in range(3)]
+    session._chk(call(*[C.byref(x) for pair in outs for x in pair]))
+    return pa.table([_import(*o) for o in outs], names=["contig", "coverage", "bases"])
 
 
 class DepthStream:
@@ -499,6 +558,16 @@ class DepthStream:
                 self.h, R.c, _cols(cols), C.c_int(int(bool(zero_based))), C.c_int(int(bool(end_exclusive))), *outs))
         finally:
             R.close()
+
+    def depth_quantize(self, cuts, emit=None, zero_based=False, end_exclusive=False, touched_only=False):
+        """Session.depth_quantize over everything pushed so far; the stream stays open"""
+        return _quantize_call(self.session, cuts, emit, lambda *a: lib().brh_depth_push_quantize(
+            self.h, C.c_int(int(bool(zero_based))), C.c_int(int(bool(end_exclusive))), C.c_int(int(bool(touched_only))), *a))
+
+    def depth_dist(self, v_lo=0, n_bins=256, zero_based=False, touched_only=False):
+        """Session.depth_dist over everything pushed so far; the stream stays open"""
+        return _dist_call(self.session, lambda *a: lib().brh_depth_push_dist(
+            self.h, C.c_int(int(bool(zero_based))), C.c_int(int(bool(touched_only))), C.c_int32(int(v_lo)), C.c_uint32(int(n_bins)), *a))
 
     def finish(self):
         """-> contig Utf8, pos_start Int32, pos_end Int32, coverage Int16 of everything pushed"""

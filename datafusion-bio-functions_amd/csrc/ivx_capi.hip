@@ -1580,6 +1580,61 @@ extern "C" ivx_status ivx_depth_profile_window_quantiles(ivx_ctx *ctx, const ivx
     return depth_ranks(ctx, p, mem, region_windows(key, first_pos, last_pos, width, n, skip_pos0), q_num, n_q, q_den, out_len, out_min, out_max, out_q);
 }
 
+// ---- coverage classes of a profile: maximal runs of one class per key, and the per-key histogram of the per-base coverage
+extern "C" ivx_status ivx_depth_profile_quantize(ivx_ctx *ctx, const ivx_index *p, int mem,
+                                                 uint32_t pos_lo, const uint32_t *key_hi, int skip_pos0, int seen_only,
+                                                 const int32_t *cuts, uint32_t n_cuts, uint32_t emit_mask,
+                                                 uint32_t *out_key, uint32_t *out_start, uint32_t *out_end, uint32_t *out_class,
+                                                 uint64_t cap, uint64_t *n_out)
+{
+    Frame f(ctx, mem);
+    IVX_TRY(f.begin(n_out, "null n_out"));
+    IVX_TRY(check_profile_args(f, p));
+    if (n_cuts > IVX_DEPTH_MAX_CUTS) return ctx->fail(IVX_ERR_INVALID, "depth profile: more than 31 cuts");
+    if (n_cuts && !cuts) return ctx->fail(IVX_ERR_INVALID, "depth profile: null cuts");
+    for (uint32_t j = 1; j < n_cuts; j++)
+        if (cuts[j] <= cuts[j - 1]) return ctx->fail(IVX_ERR_INVALID, "depth profile: cuts not strictly ascending");
+    if (n_cuts < 31 && (emit_mask >> (n_cuts + 1))) return ctx->fail(IVX_ERR_INVALID, "depth profile: emit_mask names a class above n_cuts");
+    if (mem == IVX_MEM_DEVICE && ((((uintptr_t)key_hi) | ((uintptr_t)out_key) | ((uintptr_t)out_start) | ((uintptr_t)out_end) | ((uintptr_t)out_class)) & 3u))
+        return ctx->fail(IVX_ERR_INVALID, "depth profile: pointer not aligned to its element size");
+    f.drop_plans();
+    f.meter(false, p->dp.steps);
+    const u32 *hi = f.in_at(WS_IN_KEYLEN, key_hi, p->nkeys);
+    u32 *ok = f.out(out_key, cap), *os = f.out(out_start, cap), *oe = f.out(out_end, cap), *oc = f.out(out_class, cap);
+    const bool sizing = cap == 0 && !out_key && !out_start && !out_end && !out_class;
+    u64 m = 0;
+    const ivx_status st = f.run([&] {
+        return ivx_depth_quantize_device(ctx, p->dp, p->nkeys, pos_lo, hi, skip_pos0, seen_only, cuts, n_cuts, emit_mask, ok, os, oe, oc, cap, &m);
+    });
+    *n_out = m;
+    if (st != IVX_OK) return st;
+    if (!sizing) { f.rows_out(m); f.back_all(m); }
+    return f.finish();
+}
+
+extern "C" ivx_status ivx_depth_profile_hist(ivx_ctx *ctx, const ivx_index *p, int mem,
+                                             uint32_t pos_lo, const uint32_t *key_hi, int skip_pos0, int seen_only,
+                                             int32_t v_lo, uint32_t n_bins, int64_t *out_hist)
+{
+    Frame f(ctx, mem);
+    IVX_TRY(f.begin());
+    IVX_TRY(check_profile_args(f, p));
+    if (n_bins == 0 || n_bins > IVX_DEPTH_MAX_BINS) return ctx->fail(IVX_ERR_INVALID, "depth profile: n_bins outside 1 .. 65536");
+    if (p->nkeys && !out_hist) return ctx->fail(IVX_ERR_INVALID, "depth profile: null out_hist");
+    if (mem == IVX_MEM_DEVICE && ((((uintptr_t)key_hi) & 3u) || (((uintptr_t)out_hist) & 7u)))
+        return ctx->fail(IVX_ERR_INVALID, "depth profile: pointer not aligned to its element size");
+    f.drop_plans();
+    f.meter(false, p->dp.steps);
+    if (p->nkeys == 0) return IVX_OK;
+    const u64 words = (u64)p->nkeys * n_bins;
+    const u32 *hi = f.in_at(WS_IN_KEYLEN, key_hi, p->nkeys);
+    i64 *oh = f.out(out_hist, words);
+    IVX_TRY(f.run([&] { return ivx_depth_hist_device(ctx, p->dp, p->nkeys, pos_lo, hi, skip_pos0, seen_only, v_lo, n_bins, oh); }));
+    f.rows_out(words);
+    f.back_all();
+    return f.finish();
+}
+
 // ---------------------------------------------------------------- f3: take / scatter of payload columns
 
 extern "C" ivx_status ivx_take_fixed(ivx_ctx *ctx, int mem, const void *src, uint32_t width, uint64_t n_src,

@@ -440,6 +440,12 @@ ivx_status ivx_depth_region_ranks_device(ivx_ctx *ctx, const DepthProfileView &d
 ivx_status ivx_depth_window_ranks_device(ivx_ctx *ctx, const DepthProfileView &dp, u32 key, u32 first_pos, u32 last_pos, u32 width, u64 n,
                                          int skip_pos0, const u32 *q_num, u32 n_q, u32 q_den,
                                          i64 *out_len, i32 *out_min, i32 *out_max, i32 *out_q);
+// ivx_depth_classes.hip: the maximal runs of one coverage class per key (cuts: host memory, checked by the caller; any output
+// may be null; synchronises for the count), and the per-key histogram of the per-base coverage (out: [nkeys * n_bins])
+ivx_status ivx_depth_quantize_device(ivx_ctx *ctx, const DepthProfileView &dp, u32 nkeys, u32 pos_lo, const u32 *key_hi, int skip_pos0, int seen_only,
+                                     const i32 *cuts, u32 n_cuts, u32 emit_mask, u32 *ok, u32 *os, u32 *oe, u32 *oc, u64 cap, u64 *n_out);
+ivx_status ivx_depth_hist_device(ivx_ctx *ctx, const DepthProfileView &dp, u32 nkeys, u32 pos_lo, const u32 *key_hi, int skip_pos0, int seen_only,
+                                 i32 v_lo, u32 n_bins, i64 *out);
 
 // ivx_ops32.hip: the count_overlaps / coverage / nearest indexes and their probes (device pointers)
 ivx_status ivx_count_build(ivx_ctx *ctx, ivx_index *ix, const u32 *key, const i32 *s, const i32 *e, u64 n);

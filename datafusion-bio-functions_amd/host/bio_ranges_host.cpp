@@ -1463,6 +1463,173 @@ extern "C" int brh_depth_push_region_quantiles(brh_depth_push *dp, brh_batch reg
                         bases, bases_schema, mn, mn_schema, mx, mx_schema, q, q_schemas);
 }
 
+// ---- depth coverage classes (ivx_depth_profile_quantize / ivx_depth_profile_hist): the maximal intervals of one coverage bin,
+// and the bases per coverage value of every contig (mosdepth --quantize / dist, bedtools genomecov)
+namespace {
+
+// The domain of every key of a profile of nk keys, as RegionRows has it for the regions: key_len (null: no length table) gives
+// [0, len - 1] when zero_based, else [1, len] without the step at position 0.  `drop` marks the keys that never go out: the
+// ones the dictionary does not name (key 0 of an empty dictionary) and, zero_based, a contig of length 0, which has no position.
+struct ClassDomain {
+    std::vector<uint32_t> key_hi;
+    std::vector<uint8_t> drop;
+    uint32_t pos_lo = 0;
+    bool has_len = false, skip_pos0 = false;
+    ClassDomain(uint32_t nk, uint32_t known, const std::vector<uint32_t> *key_len, int zero_based)
+    {
+        has_len = key_len != nullptr;
+        pos_lo = (key_len && !zero_based) ? 1u : 0u;
+        skip_pos0 = key_len && !zero_based;
+        drop.assign(nk, 0);
+        for (uint32_t k = known; k < nk; k++) drop[k] = 1;
+        if (!key_len) return;
+        key_hi.assign(std::max<size_t>(key_len->size(), nk), 0);
+        for (size_t k = 0; k < key_len->size(); k++) {
+            const uint32_t len = (*key_len)[k];
+            key_hi[k] = zero_based ? (len ? len - 1u : 0u) : len;
+            if (zero_based && !len && k < nk) drop[k] = 1;
+        }
+    }
+    const uint32_t *hi() const { return has_len ? key_hi.data() : nullptr; }
+};
+
+// the keys < known in the order their rows go out: ascending ids, or (by_name) the byte order of their names
+std::vector<uint32_t> class_key_order(const std::vector<std::string> &names, uint32_t known, bool by_name)
+{
+    std::vector<uint32_t> order(known);
+    for (uint32_t k = 0; k < known; k++) order[k] = k;
+    if (by_name) std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return names[a] < names[b]; });
+    return order;
+}
+
+int quantize_profile(brh_session *s, const ivx_index *profile, uint32_t nk, uint32_t known, const std::vector<std::string> &names,
+                     const std::vector<uint32_t> *key_len, bool by_name, int zero_based, int end_exclusive, int touched_only,
+                     const int32_t *cuts, uint32_t n_cuts, uint32_t emit_mask,
+                     ArrowArray *contig, ArrowSchema *contig_schema, ArrowArray *start, ArrowSchema *start_schema,
+                     ArrowArray *end, ArrowSchema *end_schema, ArrowArray *bin, ArrowSchema *bin_schema)
+{
+    const ClassDomain d(nk, known, key_len, zero_based);
+    auto call = [&](uint32_t *ok, uint32_t *os, uint32_t *oe, uint32_t *oc, uint64_t cap, uint64_t *m) {
+        return ivx_depth_profile_quantize(s->ctx, profile, IVX_MEM_HOST, d.pos_lo, d.hi(), d.skip_pos0, touched_only != 0, cuts, n_cuts, emit_mask,
+                                          ok, os, oe, oc, cap, m);
+    };
+    uint64_t m = 0, m2 = 0;
+    ivx_status st = call(nullptr, nullptr, nullptr, nullptr, 0, &m);
+    if (st != IVX_OK) return fail_ivx(s, st);
+    std::vector<uint32_t> ok(m ? m : 1), os(m ? m : 1), oe(m ? m : 1), oc(m ? m : 1);
+    if (m) {
+        st = call(ok.data(), os.data(), oe.data(), oc.data(), m, &m2);
+        if (st != IVX_OK) return fail_ivx(s, st);
+    }
+    // the rows are grouped by key ascending: [lo[k], lo[k + 1]) are key k's
+    std::vector<uint64_t> lo((size_t)nk + 1, m2);
+    for (uint64_t i = m2; i-- > 0;) if (ok[i] < nk) lo[ok[i]] = i;
+    for (size_t k = nk; k-- > 0;) if (lo[k] > lo[k + 1]) lo[k] = lo[k + 1];
+    std::vector<uint32_t> oid; std::vector<int64_t> o64s, o64e; std::vector<int32_t> obin;
+    for (uint32_t k : class_key_order(names, known, by_name)) {
+        if (d.drop[k]) continue;
+        for (uint64_t i = lo[k]; i < lo[k + 1]; i++) {
+            oid.push_back(k); o64s.push_back((int64_t)os[i]); o64e.push_back((int64_t)oe[i] + (end_exclusive ? 1 : 0)); obin.push_back((int32_t)oc[i]);
+        }
+    }
+    const int64_t n = (int64_t)oid.size();
+    if (!n) { oid.push_back(0); o64s.push_back(0); o64e.push_back(0); obin.push_back(0); }
+    make_utf8(contig, names, oid.data(), n); make_schema(contig_schema, "u", "contig", true);
+    make_primitive<int64_t>(start, o64s.data(), n, nullptr); make_schema(start_schema, "l", "start", false);
+    make_primitive<int64_t>(end, o64e.data(), n, nullptr); make_schema(end_schema, "l", "end", false);
+    make_primitive<int32_t>(bin, obin.data(), n, nullptr); make_schema(bin_schema, "i", "bin", false);
+    return 0;
+}
+
+int dist_profile(brh_session *s, const ivx_index *profile, uint32_t nk, uint32_t known, const std::vector<std::string> &names,
+                 const std::vector<uint32_t> *key_len, bool by_name, int zero_based, int touched_only, int32_t v_lo, uint32_t n_bins,
+                 ArrowArray *contig, ArrowSchema *contig_schema, ArrowArray *coverage, ArrowSchema *coverage_schema,
+                 ArrowArray *bases, ArrowSchema *bases_schema)
+{
+    if (n_bins == 0 || n_bins > IVX_DEPTH_MAX_BINS) return fail(s, "depth_dist: n_bins outside 1 .. 65536");
+    const ClassDomain d(nk, known, key_len, zero_based);
+    std::vector<int64_t> h((size_t)nk * n_bins, 0);
+    const ivx_status st = ivx_depth_profile_hist(s->ctx, profile, IVX_MEM_HOST, d.pos_lo, d.hi(), d.skip_pos0, touched_only != 0, v_lo, n_bins, h.data());
+    if (st != IVX_OK) return fail_ivx(s, st);
+    std::vector<uint32_t> oid; std::vector<int32_t> ocov; std::vector<int64_t> obases;
+    for (uint32_t k : class_key_order(names, known, by_name)) {
+        if (d.drop[k]) continue;
+        for (uint32_t b = 0; b < n_bins; b++) {
+            const int64_t c = h[(size_t)k * n_bins + b];
+            if (c <= 0) continue;
+            oid.push_back(k); ocov.push_back((int32_t)std::min<int64_t>((int64_t)v_lo + b, INT32_MAX)); obases.push_back(c);
+        }
+    }
+    const int64_t n = (int64_t)oid.size();
+    if (!n) { oid.push_back(0); ocov.push_back(0); obases.push_back(0); }
+    make_utf8(contig, names, oid.data(), n); make_schema(contig_schema, "u", "contig", true);
+    make_primitive<int32_t>(coverage, ocov.data(), n, nullptr); make_schema(coverage_schema, "i", "coverage", false);
+    make_primitive<int64_t>(bases, obases.data(), n, nullptr); make_schema(bases_schema, "l", "bases", false);
+    return 0;
+}
+
+// ONE profile of the inputs of a depth() call
+int depth_one_profile(brh_session *s, DepthInputs *in, brh_batch reads, brh_batch prior, brh_batch lengths, uint32_t filter_flag, uint32_t min_mapq,
+                      IndexGuard *g)
+{
+    if (in->load(s, reads, prior, lengths)) return 1;
+    const ivx_status st = in->profile(s->ctx, in->has_prior ? in->skey.data() : nullptr, in->ss.data(), in->se.data(), in->has_prior ? in->sw.data() : nullptr,
+                                      in->n_seg, in->nk, in->has_len ? in->key_len.data() : nullptr, filter_flag, min_mapq, &g->ix);
+    return st != IVX_OK ? fail_ivx(s, st) : 0;
+}
+
+}  // namespace
+
+extern "C" int brh_depth_quantize(brh_session *s, brh_batch reads, brh_batch prior, brh_batch lengths, int zero_based, int end_exclusive,
+                                  int touched_only, uint32_t filter_flag, uint32_t min_mapq,
+                                  const int32_t *cuts, uint32_t n_cuts, uint32_t emit_mask,
+                                  ArrowArray *contig, ArrowSchema *contig_schema, ArrowArray *start, ArrowSchema *start_schema,
+                                  ArrowArray *end, ArrowSchema *end_schema, ArrowArray *bin, ArrowSchema *bin_schema)
+{
+    if (!s) return 1;
+    DepthInputs in; IndexGuard g;
+    if (depth_one_profile(s, &in, reads, prior, lengths, filter_flag, min_mapq, &g)) return 1;
+    return quantize_profile(s, g.ix, in.nk, (uint32_t)in.dict.names.size(), in.dict.names, in.has_len ? &in.key_len : nullptr, false,
+                            zero_based, end_exclusive, touched_only, cuts, n_cuts, emit_mask,
+                            contig, contig_schema, start, start_schema, end, end_schema, bin, bin_schema);
+}
+
+extern "C" int brh_depth_push_quantize(brh_depth_push *dp, int zero_based, int end_exclusive, int touched_only,
+                                       const int32_t *cuts, uint32_t n_cuts, uint32_t emit_mask,
+                                       ArrowArray *contig, ArrowSchema *contig_schema, ArrowArray *start, ArrowSchema *start_schema,
+                                       ArrowArray *end, ArrowSchema *end_schema, ArrowArray *bin, ArrowSchema *bin_schema)
+{
+    if (!dp) return 1;
+    if (depth_push_check(dp) || depth_push_merge_all(dp)) return 1;            // the merged profile stays the stack's only entry
+    const uint32_t known = std::min<uint32_t>((uint32_t)dp->names.size(), dp->built_nk);
+    return quantize_profile(dp->s, dp->stack[0], dp->built_nk, known, dp->names, dp->dense ? &dp->key_len : nullptr, !dp->dense,
+                            zero_based, end_exclusive, touched_only, cuts, n_cuts, emit_mask,
+                            contig, contig_schema, start, start_schema, end, end_schema, bin, bin_schema);
+}
+
+extern "C" int brh_depth_dist(brh_session *s, brh_batch reads, brh_batch prior, brh_batch lengths, int zero_based, int touched_only,
+                              uint32_t filter_flag, uint32_t min_mapq, int32_t v_lo, uint32_t n_bins,
+                              ArrowArray *contig, ArrowSchema *contig_schema, ArrowArray *coverage, ArrowSchema *coverage_schema,
+                              ArrowArray *bases, ArrowSchema *bases_schema)
+{
+    if (!s) return 1;
+    DepthInputs in; IndexGuard g;
+    if (depth_one_profile(s, &in, reads, prior, lengths, filter_flag, min_mapq, &g)) return 1;
+    return dist_profile(s, g.ix, in.nk, (uint32_t)in.dict.names.size(), in.dict.names, in.has_len ? &in.key_len : nullptr, false,
+                        zero_based, touched_only, v_lo, n_bins, contig, contig_schema, coverage, coverage_schema, bases, bases_schema);
+}
+
+extern "C" int brh_depth_push_dist(brh_depth_push *dp, int zero_based, int touched_only, int32_t v_lo, uint32_t n_bins,
+                                   ArrowArray *contig, ArrowSchema *contig_schema, ArrowArray *coverage, ArrowSchema *coverage_schema,
+                                   ArrowArray *bases, ArrowSchema *bases_schema)
+{
+    if (!dp) return 1;
+    if (depth_push_check(dp) || depth_push_merge_all(dp)) return 1;            // the merged profile stays the stack's only entry
+    const uint32_t known = std::min<uint32_t>((uint32_t)dp->names.size(), dp->built_nk);
+    return dist_profile(dp->s, dp->stack[0], dp->built_nk, known, dp->names, dp->dense ? &dp->key_len : nullptr, !dp->dense,
+                        zero_based, touched_only, v_lo, n_bins, contig, contig_schema, coverage, coverage_schema, bases, bases_schema);
+}
+
 // ---- f3: payload gather
 namespace {
 

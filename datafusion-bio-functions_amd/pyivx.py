@@ -34,6 +34,7 @@ SYMBOLS = [
     "ivx_cigar_parse", "ivx_depth_text", "ivx_depth_profile_build_text",
     "ivx_depth_profile_summarize", "ivx_depth_profile_windows",
     "ivx_depth_profile_quantiles", "ivx_depth_profile_window_quantiles",
+    "ivx_depth_profile_quantize", "ivx_depth_profile_hist",
 ]
 
 # outputs one workgroup of the expand kernel makes (csrc/ivx_depth_expand.hip DEPTH_EXPAND_TILE; tests/test_depth_per_base_tile.py)
@@ -51,6 +52,14 @@ DEPTH_RANK_SEGS = 64
 DEPTH_RANK_SELECT_GRID = 512
 # quantiles one call takes (include/ivx.h IVX_DEPTH_MAX_QUANTILES)
 DEPTH_MAX_QUANTILES = 8
+# the coverage classes (csrc/ivx_depth_classes.hip; tests/test_gpu_depth_classes.py): steps per tile of both passes, the bins a
+# workgroup of the histogram pass keeps in LDS (more go to memory directly), the key ids a tile may span and still use them
+DEPTH_CLASS_TILE = 1024
+DEPTH_HIST_LDS_BINS = 2048
+DEPTH_HIST_TILE_KEYS = 8
+# cuts of one quantize call, bins of one hist call (include/ivx.h IVX_DEPTH_MAX_CUTS, IVX_DEPTH_MAX_BINS)
+DEPTH_MAX_CUTS = 31
+DEPTH_MAX_BINS = 65536
 # bytes one thread / one workgroup of the text-CIGAR parser takes (csrc/ivx_cigar.hip CIGAR_B, CIGAR_TILE)
 CIGAR_B = 16
 CIGAR_TILE = 4096
@@ -164,6 +173,11 @@ def lib():
         L.ivx_depth_profile_window_quantiles.restype = C.c_int
         L.ivx_depth_profile_window_quantiles.argtypes = ([C.c_void_p, C.c_void_p, C.c_int] + [C.c_uint32] * 4 + [C.c_uint64, C.c_int, C.c_void_p, C.c_uint32,
                                                          C.c_uint32] + [C.c_void_p] * 4)
+        L.ivx_depth_profile_quantize.restype = C.c_int
+        L.ivx_depth_profile_quantize.argtypes = ([C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_uint32,
+                                                  C.c_uint32] + [C.c_void_p] * 4 + [C.c_uint64, C.POINTER(C.c_uint64)])
+        L.ivx_depth_profile_hist.restype = C.c_int
+        L.ivx_depth_profile_hist.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_int, C.c_int, C.c_int32, C.c_uint32, C.c_void_p]
         # test hook of csrc/ivx_sweep.hip (not in include/ivx.h): what subtract's count pass did (tests/test_gpu_subtract_edges.py)
         L.ivx_debug_subtract_paths.restype = C.c_int
         L.ivx_debug_subtract_paths.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
@@ -419,6 +433,73 @@ class DepthProfile:
                                                           int(last_pos), int(width), int(n), int(bool(skip_pos0)), _ptr(qn), len(qn),
                                                           int(q_den), *[_ptr(o) for o in out]))
         return tuple(out)
+
+    def _key_hi(self, key_hi, device):
+        """key_hi where the call's memory mode wants it: a torch device tensor passes through in device mode, anything else is
+        made a uint32 numpy array (host mode) or copied to the device as its int32 bits"""
+        if key_hi is None:
+            return None
+        if device:
+            if _is_torch(key_hi):
+                assert key_hi.is_contiguous()
+                return key_hi
+            import torch
+            return torch.from_numpy(np.ascontiguousarray(key_hi, dtype=np.uint32).view(np.int32)).to(self.device or "cuda:0")
+        if _is_torch(key_hi):
+            raise ValueError("mix of host and device buffers in one call")
+        return _np(key_hi, np.uint32)
+
+    def quantize(self, cuts, emit=None, pos_lo=0, key_hi=None, skip_pos0=False, seen_only=False, device=False, ctx=None, cap=None,
+                 outputs=(True, True, True, True)):
+        """the maximal runs of positions whose coverage stays in one class -> (key, start, end, cls), closed intervals ordered
+        by (key, start); class(v) = the number of cuts <= v.  emit: the classes to emit (None: all; an iterable of class
+        numbers, or the bit mask as an int); the runs of the others still separate their neighbours.  numpy arrays, or torch
+        tensors with device=True (as their int32 bits).  cap=None: a sizing call, then the fill call."""
+        ctx = ctx or self.ctx
+        mem = MEM_DEVICE if device else MEM_HOST
+        c = np.ascontiguousarray(cuts, dtype=np.int32).reshape(-1)
+        if emit is None:
+            mask = (1 << (len(c) + 1)) - 1 if len(c) < 32 else 0xFFFFFFFF
+        elif isinstance(emit, (int, np.integer)):
+            mask = int(emit)
+        else:
+            mask = 0
+            for j in emit:
+                mask |= 1 << int(j)
+        if mask >> 32:
+            raise ValueError("emit names a class above 31")
+        hi = self._key_hi(key_hi, device)
+        head = (ctx.h, self.h, mem, int(pos_lo), _ptr(hi), int(bool(skip_pos0)), int(bool(seen_only)), _ptr(c), len(c), mask)
+        if cap is None:
+            m = C.c_uint64(0)
+            ctx._chk(lib().ivx_depth_profile_quantize(*head, None, None, None, None, 0, C.byref(m)))
+            cap = max(m.value, 1)
+        if device:
+            import torch
+            out = [torch.empty(cap, dtype=torch.int32, device=self.device or "cuda:0") if w else None for w in outputs]
+        else:
+            out = [np.empty(cap, np.uint32) if w else None for w in outputs]
+        m2 = C.c_uint64(0)
+        st = lib().ivx_depth_profile_quantize(*head, *[_ptr(o) for o in out], cap, C.byref(m2))
+        if st == ERR_CAPACITY:
+            raise IvxError(st, f"{lib().ivx_last_error(ctx.h).decode()} (needed {m2.value})")
+        ctx._chk(st)
+        return tuple(None if o is None else o[:m2.value] for o in out)
+
+    def hist(self, v_lo=0, n_bins=256, pos_lo=0, key_hi=None, skip_pos0=False, seen_only=False, device=False, ctx=None):
+        """per key the number of positions of its domain at each coverage value -> int64 [n_keys, n_bins]: bin b counts the
+        positions with coverage v_lo + b, the first bin also everything below, the last one everything above.  A numpy array,
+        or a torch tensor with device=True (then the call may return with kernels in flight)."""
+        ctx = ctx or self.ctx
+        hi = self._key_hi(key_hi, device)
+        if device:
+            import torch
+            out = torch.empty((self.n_keys, int(n_bins)), dtype=torch.int64, device=self.device or "cuda:0")
+        else:
+            out = np.empty((self.n_keys, int(n_bins)), np.int64)
+        ctx._chk(lib().ivx_depth_profile_hist(ctx.h, self.h, MEM_DEVICE if device else MEM_HOST, int(pos_lo), _ptr(hi), int(bool(skip_pos0)),
+                                              int(bool(seen_only)), int(v_lo), int(n_bins), _ptr(out) if self.n_keys and n_bins else None))
+        return out
 
     def free(self):
         if self.h:

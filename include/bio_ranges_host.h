@@ -287,6 +287,49 @@ int  brh_depth_push_region_quantiles(brh_depth_push *dp, brh_batch regions, brh_
                                      struct ArrowArray *max, struct ArrowSchema *max_schema,
                                      struct ArrowArray *q, struct ArrowSchema *q_schemas);
 
+/* Depth coverage classes: every base classified by its coverage (ivx.h ivx_depth_profile_quantize / ivx_depth_profile_hist).
+ * brh_depth_quantize: the maximal intervals whose coverage stays in one bin -- mosdepth --quantize, GATK CallableLoci, "the
+ *   intervals at 10x or more".  bin(v) = the number of cuts <= v (cuts[n_cuts], n_cuts <= 31, strictly ascending); a run goes out
+ *   iff bit `bin` of emit_mask is set, and the runs of the other bins still separate their neighbours.
+ *   Outputs, ordered by (contig, start), all non-null but contig's schema: contig Utf8, start and end Int64 (end inclusive;
+ *   end_exclusive = 1 adds 1: mosdepth's BED is zero_based with end_exclusive), bin Int32.  Contigs come in the order brh_depth
+ *   emits them.  The result is an interval table: subtract, complement and the joins take it.
+ * brh_depth_dist: per contig the number of bases at each coverage value -- bedtools genomecov's default output, mosdepth's dist,
+ *   the histogram of Picard CollectWgsMetrics.  Bin b of n_bins (1 .. 65536) counts the bases with coverage v_lo + b.  The two end
+ *   bins are clamped: coverage v_lo stands for "v_lo or less" and coverage v_lo + n_bins - 1 for "that or more"; they keep their
+ *   edge value in the output.  Outputs: contig Utf8, coverage Int32, bases Int64; one row per contig and bin with bases > 0, in
+ *   (contig, coverage) order.  No floating point: cumulative fractions are the caller's division.
+ * Both: reads / prior / lengths and the read filter as for brh_depth_regions; ONE depth profile is built, read and freed.  The
+ *   domain is that of brh_depth_regions: with lengths [0, len - 1] when zero_based, else [1, len] without the step at position 0;
+ *   without lengths the whole u32 range (zero_based is not read).  touched_only = 1: only contigs that kept a read or a prior
+ *   block after the filter and the clipping take part (the contigs brh_depth_per_base_next emits); 0: every contig of the
+ *   dictionary with a non-empty domain, a contig without coverage as one run / one row of coverage 0.
+ * brh_depth_push_quantize / brh_depth_push_dist: the same over everything pushed so far.  They merge the stack down to one
+ *   profile, which stays the stack's only entry: the stream stays open, as with brh_depth_push_regions.
+ * Not built: distributions or runs restricted to a region set, a minimum run length, labels for the bins. */
+int  brh_depth_quantize(brh_session *s, brh_batch reads, brh_batch prior, brh_batch lengths, int zero_based, int end_exclusive,
+                        int touched_only, uint32_t filter_flag, uint32_t min_mapq,
+                        const int32_t *cuts, uint32_t n_cuts, uint32_t emit_mask,
+                        struct ArrowArray *contig, struct ArrowSchema *contig_schema,
+                        struct ArrowArray *start, struct ArrowSchema *start_schema,
+                        struct ArrowArray *end, struct ArrowSchema *end_schema,
+                        struct ArrowArray *bin, struct ArrowSchema *bin_schema);
+int  brh_depth_push_quantize(brh_depth_push *dp, int zero_based, int end_exclusive, int touched_only,
+                             const int32_t *cuts, uint32_t n_cuts, uint32_t emit_mask,
+                             struct ArrowArray *contig, struct ArrowSchema *contig_schema,
+                             struct ArrowArray *start, struct ArrowSchema *start_schema,
+                             struct ArrowArray *end, struct ArrowSchema *end_schema,
+                             struct ArrowArray *bin, struct ArrowSchema *bin_schema);
+int  brh_depth_dist(brh_session *s, brh_batch reads, brh_batch prior, brh_batch lengths, int zero_based, int touched_only,
+                    uint32_t filter_flag, uint32_t min_mapq, int32_t v_lo, uint32_t n_bins,
+                    struct ArrowArray *contig, struct ArrowSchema *contig_schema,
+                    struct ArrowArray *coverage, struct ArrowSchema *coverage_schema,
+                    struct ArrowArray *bases, struct ArrowSchema *bases_schema);
+int  brh_depth_push_dist(brh_depth_push *dp, int zero_based, int touched_only, int32_t v_lo, uint32_t n_bins,
+                         struct ArrowArray *contig, struct ArrowSchema *contig_schema,
+                         struct ArrowArray *coverage, struct ArrowSchema *coverage_schema,
+                         struct ArrowArray *bases, struct ArrowSchema *bases_schema);
+
 /* compute::take of ONE payload column with an index array a join / nearest call returned
  * (interval_join.rs:1655-1667, nearest.rs:469-482), on the device.  column: any fixed-width primitive
  * (ints, floats, date/time/timestamp/duration, decimal128/256, fixed-size binary of 1/2/4/8/16/32 bytes),

@@ -575,6 +575,48 @@ ivx_status ivx_depth_profile_window_quantiles(ivx_ctx *ctx, const ivx_index *pro
                                               int64_t *out_len /* nullable */, int32_t *out_min /* nullable */, int32_t *out_max /* nullable */,
                                               int32_t *out_q /* nullable */);
 
+/*      COVERAGE CLASSES of a profile: every base classified by its coverage -- the maximal intervals whose coverage stays in
+ *      one class (mosdepth --quantize, GATK CallableLoci, "the intervals at 10x or more"), and per key the number of bases at
+ *      each coverage value (bedtools genomecov's default output, mosdepth's dist, the histogram of Picard CollectWgsMetrics;
+ *      the reference has neither).  v(p), c0(k), skip_pos0, pos_lo, key_hi, the domain D(k), the zero stretch before a key's
+ *      first step, the keys without steps (v = 0 on the whole domain) and the last step that extends to the end of its
+ *      domain are those of REGION SUMMARIES above.  seen_only != 0: a key with key_seen[k] == 0 does not take part (the
+ *      reference's "touched" contig, as its per-base emitter uses it); seen_only = 0: every key < n_keys with a non-empty
+ *      domain takes part.  An empty profile is valid: all its keys are keys without steps.
+ *      QUANTIZE.  class(v) = the number of cuts <= v, in 0 .. n_cuts: class 0 is v < cuts[0], class j is cuts[j-1] <= v <
+ *      cuts[j], class n_cuts is v >= cuts[n_cuts-1]; with n_cuts = 0 everything is class 0.  For each key that takes part, in
+ *      ascending order, the output is the maximal runs of consecutive positions of D(k) with the same class, as closed
+ *      intervals [out_start, out_end] with out_class, ordered by (key, start).  A run goes out iff bit `class` of emit_mask
+ *      is set; the runs of a class that is not emitted still separate their neighbours.  The result is an interval set:
+ *      ivx_subtract, ivx_complement, the overlap join and ivx_probe_overlap_agg take it as input.  cuts is HOST memory in
+ *      both modes.  The capacity protocol of ivx_depth_profile_blocks: the count is always made and read back; cap = 0 with
+ *      NULL outputs only counts; cap < *n_out is IVX_ERR_CAPACITY with *n_out = the size needed and nothing written; any
+ *      output may be NULL on its own.
+ *      IVX_ERR_INVALID: n_cuts > IVX_DEPTH_MAX_CUTS; cuts not strictly ascending; a bit of emit_mask above n_cuts; in device
+ *      mode a pointer that is not aligned to its element.  IVX_ERR_UNSUPPORTED: any index that is not a profile.
+ *      HIST.  out_hist[k * n_bins + b] = #{p in D(k) : clamp((int64)v(p) - v_lo, 0, n_bins - 1) = b} (int64_t[n_keys *
+ *      n_bins], key-major): the first bin takes everything at or below v_lo, the last one everything at or above v_lo +
+ *      n_bins - 1.  Every element is written: a key that does not take part, or whose domain is empty, gets zeros.
+ *      IVX_ERR_INVALID: n_bins = 0 or n_bins > IVX_DEPTH_MAX_BINS; in device mode a pointer that is not aligned to its
+ *      element.  IVX_ERR_UNSUPPORTED as above.
+ *      Both: usable from any context on the profile's device; drop the state a sizing call of another operation left on the
+ *      context; IVX_MEM_DEVICE calls may return with kernels in flight (quantize has read back its count by then); key_hi:
+ *      [n_keys], where `mem` says.  Scratch, counted against the context's memory limit: quantize 16 bytes per key and 8
+ *      bytes per 1024 steps; hist none; the staged columns in host mode.  Cost: a quantize sizing call reads the step list
+ *      once, a fill call three times (its own count, then the scan that writes); hist reads it once.
+ *      Not built: distributions or runs restricted to a region set, a minimum run length, labels for the classes, float
+ *      output (cumulative fractions are the caller's division). */
+#define IVX_DEPTH_MAX_CUTS 31
+ivx_status ivx_depth_profile_quantize(ivx_ctx *ctx, const ivx_index *profile, int mem,
+                                      uint32_t pos_lo, const uint32_t *key_hi /* nullable */, int skip_pos0, int seen_only,
+                                      const int32_t *cuts /* host memory, strictly ascending */, uint32_t n_cuts, uint32_t emit_mask,
+                                      uint32_t *out_key, uint32_t *out_start, uint32_t *out_end, uint32_t *out_class,
+                                      uint64_t cap, uint64_t *n_out);
+#define IVX_DEPTH_MAX_BINS 65536
+ivx_status ivx_depth_profile_hist(ivx_ctx *ctx, const ivx_index *profile, int mem,
+                                  uint32_t pos_lo, const uint32_t *key_hi /* nullable */, int skip_pos0, int seen_only,
+                                  int32_t v_lo, uint32_t n_bins, int64_t *out_hist /* [n_keys * n_bins], key-major */);
+
 /* ---- f3: `compute::take` of payload columns with the index arrays the probes return
  *      (interval_join.rs:1655-1667, nearest.rs:469-482).  idx[i] == IVX_NULL_IDX or a null source
  *      slot (src_valid_bits: Arrow validity bitmap of the source, bit offset 0, nullable) gives

@@ -149,6 +149,14 @@ extern "C" {
                                               last_pos: u32, width: u32, n: u64, skip_pos0: i32, q_num: *const u32, n_q: u32,
                                               q_den: u32, out_len: *mut i64, out_min: *mut i32, out_max: *mut i32,
                                               out_q: *mut i32) -> i32;
+    // coverage classes of a profile: the maximal runs of one class per key (cuts: host memory, at most 31, strictly
+    // ascending; the capacity protocol of ivx_depth_profile_blocks), and the per-key histogram [n_keys * n_bins]
+    pub fn ivx_depth_profile_quantize(ctx: *mut IvxCtx, profile: *const IvxIndex, mem: i32, pos_lo: u32, key_hi: *const u32,
+                                      skip_pos0: i32, seen_only: i32, cuts: *const i32, n_cuts: u32, emit_mask: u32,
+                                      out_key: *mut u32, out_start: *mut u32, out_end: *mut u32, out_class: *mut u32,
+                                      cap: u64, n_out: *mut u64) -> i32;
+    pub fn ivx_depth_profile_hist(ctx: *mut IvxCtx, profile: *const IvxIndex, mem: i32, pos_lo: u32, key_hi: *const u32,
+                                  skip_pos0: i32, seen_only: i32, v_lo: i32, n_bins: u32, out_hist: *mut i64) -> i32;
     pub fn ivx_take_fixed(ctx: *mut IvxCtx, mem: i32, src: *const c_void, width: u32, n_src: u64, src_valid_bits: *const u8,
                           idx: *const u32, n: u64, out: *mut c_void, out_valid: *mut u8) -> i32;
     pub fn ivx_scatter_fixed(ctx: *mut IvxCtx, mem: i32, src: *const c_void, width: u32, idx: *const u32, n: u64,
