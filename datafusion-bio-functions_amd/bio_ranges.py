@@ -3,6 +3,7 @@
 
     count_overlaps('l','r'), coverage('l','r'), nearest('l','r',k,overlap,distance),
     overlap('l','r'[,mode]), merge('t'[,min_dist]), subtract('l','r'), cluster('t'[,min_dist]), complement('t'[,'view']),
+    intersect('l','r') -- subtract's dual, which the reference does not have: the parts of the left rows that the right table covers,
     depth('reads') of the pileup crate,
     and the SQL range join handled by IntervalJoinExec
 
@@ -271,11 +272,19 @@ class Session:
 
     # ---- subtract (table_function.rs:574-612); extra left columns are carried along (subtract.rs:501-527)
     def subtract(self, left, right, cols_left=DEFAULT_COLS, cols_right=DEFAULT_COLS, strict=False):
+        return self._left_pieces(lib().brh_subtract, left, right, cols_left, cols_right, strict)
+
+    # ---- intersect: the pieces of the left rows that the right table's merged intervals cover (include/ivx.h ivx_intersect);
+    # schema, order and extra left columns as subtract
+    def intersect(self, left, right, cols_left=DEFAULT_COLS, cols_right=DEFAULT_COLS, strict=False):
+        return self._left_pieces(lib().brh_intersect, left, right, cols_left, cols_right, strict)
+
+    def _left_pieces(self, fn, left, right, cols_left, cols_right, strict):
         L, R = _Exported(left), _Exported(right)
         outs = [_out() for _ in range(4)]
         try:
-            self._chk(lib().brh_subtract(self.h, L.c, _cols(cols_left), R.c, _cols(cols_right), C.c_int(STRICT if strict else WEAK),
-                                         *[C.byref(x) for pair in outs for x in pair]))
+            self._chk(fn(self.h, L.c, _cols(cols_left), R.c, _cols(cols_right), C.c_int(STRICT if strict else WEAK),
+                         *[C.byref(x) for pair in outs for x in pair]))
         finally:
             L.close(); R.close()
         contig, start, end, row = [_import(*o) for o in outs]

@@ -1067,6 +1067,68 @@ extern "C" ivx_status ivx_subtract(ivx_ctx *ctx, int mem,
     return f.finish();
 }
 
+// ivx_intersect, and the same call with the count pass's report (the test hook below)
+static ivx_status intersect_impl(ivx_ctx *ctx, int mem,
+                                 const uint32_t *lkey, const int64_t *lstart, const int64_t *lend, uint64_t nl,
+                                 const uint32_t *rkey, const int64_t *rstart, const int64_t *rend, uint64_t nr,
+                                 uint32_t n_keys, int strict,
+                                 uint32_t *out_key, int64_t *out_start, int64_t *out_end, uint32_t *out_row,
+                                 uint64_t cap, uint64_t *n_out, const ivx_isect_debug *dbg)
+{
+    Frame f(ctx, mem);
+    IVX_TRY(f.enter(n_out, "null n_out"));
+    if ((nl && (!lstart || !lend)) || (nr && (!rstart || !rend))) return ctx->fail(IVX_ERR_INVALID, "null coordinate column");
+    if (nl >= 0xFFFFFFFFull || nr >= 0xFFFFFFFFull) return ctx->fail(IVX_ERR_INVALID, "intersect: more than 2^32-1 rows in one call");
+    if ((lkey == nullptr) != (rkey == nullptr) && nl && nr) return ctx->fail(IVX_ERR_INVALID, "intersect: key given for one side only");
+    if (n_keys == 0 || (!lkey && !rkey)) n_keys = 1;
+    f.drop_plans();                                         // as any other call between a sizing call and its fill
+    const u32 *dlk = f.in(lkey, nl);
+    const i64 *dls = f.in(lstart, nl), *dle = f.in(lend, nl);
+    const u32 *drk = f.in(rkey, nr);
+    const i64 *drs = f.in(rstart, nr), *dre = f.in(rend, nr);
+    u32 *ok = f.out(out_key, cap);
+    i64 *os = f.out(out_start, cap), *oe = f.out(out_end, cap);
+    u32 *orow = f.out(out_row, cap);
+    IVX_TRY(f.st);
+    u64 m = 0;
+    const ivx_status st = f.run([&] { return ivx_intersect_device(ctx, dlk, dls, dle, nl, drk, drs, dre, nr, n_keys, strict, ok, os, oe, orow, cap, &m, dbg); });
+    *n_out = m;
+    if (st != IVX_OK) return st;
+    if (cap) f.back_all(m);
+    return f.finish();
+}
+
+extern "C" ivx_status ivx_intersect(ivx_ctx *ctx, int mem,
+                                    const uint32_t *lkey, const int64_t *lstart, const int64_t *lend, uint64_t nl,
+                                    const uint32_t *rkey, const int64_t *rstart, const int64_t *rend, uint64_t nr,
+                                    uint32_t n_keys, int strict,
+                                    uint32_t *out_key, int64_t *out_start, int64_t *out_end, uint32_t *out_row,
+                                    uint64_t cap, uint64_t *n_out)
+{
+    return intersect_impl(ctx, mem, lkey, lstart, lend, nl, rkey, rstart, rend, nr, n_keys, strict, out_key, out_start, out_end, out_row, cap, n_out, nullptr);
+}
+
+// Test hook (not in include/ivx.h; tests/test_gpu_intersect_edges.py): an intersect SIZING call for these inputs that also says
+// what its count pass did.  wg: ISECT_DBG_WORDS words per workgroup (k_isect_count, ivx_sweep.hip; ivx_debug_intersect_geometry
+// gives the constants), row_esc: one byte per left row at its original index; both HOST buffers in either mode, capacities in
+// workgroups / rows.  *n_wg and *n_rows are set before the capacities are checked (IVX_ERR_CAPACITY); both are 0, and nothing is
+// written, when a side is empty.
+extern "C" ivx_status ivx_debug_intersect_paths(ivx_ctx *ctx, int mem,
+                                                const uint32_t *lkey, const int64_t *lstart, const int64_t *lend, uint64_t nl,
+                                                const uint32_t *rkey, const int64_t *rstart, const int64_t *rend, uint64_t nr,
+                                                uint32_t n_keys, int strict, uint32_t *wg, uint64_t wg_cap, uint8_t *row_esc, uint64_t row_cap,
+                                                uint64_t *n_wg, uint64_t *n_rows, uint64_t *n_out)
+{
+    if (!ctx) return IVX_ERR_INVALID;
+    if (!n_wg || !n_rows) return ctx->fail(IVX_ERR_INVALID, "debug_intersect_paths: null n_wg / n_rows");
+    *n_wg = 0; *n_rows = 0;
+    const ivx_isect_debug dbg{wg, wg_cap, row_esc, row_cap, n_wg, n_rows};
+    const ivx_status st = intersect_impl(ctx, mem, lkey, lstart, lend, nl, rkey, rstart, rend, nr, n_keys, strict, nullptr, nullptr, nullptr, nullptr, 0, n_out, &dbg);
+    if (st != IVX_OK) return st;
+    IVX_HIP(ctx, hipStreamSynchronize(ctx->stream));        // (the two report copies; the count's read-back has waited for them already)
+    return IVX_OK;
+}
+
 extern "C" ivx_status ivx_cluster(ivx_ctx *ctx, int mem, const uint32_t *key, const int64_t *start, const int64_t *end, uint64_t n,
                                   uint32_t n_keys, int64_t min_dist, int strict, const int64_t *key_base,
                                   uint32_t *out_key, int64_t *out_start, int64_t *out_end, uint32_t *out_row,

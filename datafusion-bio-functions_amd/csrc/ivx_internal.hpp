@@ -316,7 +316,8 @@ enum { IVX_FORMS_KIND = 0, IVX_FORMS_NROUTE_NREG = 1, IVX_FORMS_NEAR_WORDS = 2, 
        IVX_FORMS_GRID0 = 5, IVX_FORMS_WORDS = 11 };
 // words of ivx_debug_sweep_form (ivx_sweep.hip; tests only, not in include/ivx.h): the decisions the last sort64 of a sweep's
 // input rows (ivx_sweep.hip) and the packed sweep behind it (ivx_runs.hip runs_packed) took ON THE HOST -- nothing is written by
-// a kernel.  merge / cluster / complement clear them at entry; after a subtract they describe its last sort64 call.
+// a kernel.  merge / cluster / complement / intersect clear them at entry (intersect: they describe its right side's sort and
+// sweep); after a subtract they describe its last sort64 call.
 enum { IVX_SWEEP_SORT_WORDS = 0 /* words of the radix sort that ran: 0 none, 1, 3 */, IVX_SWEEP_NW = 1 /* words the sort key takes: 1 or 3 */,
        IVX_SWEEP_LIN = 2, IVX_SWEEP_BITS_S = 3, IVX_SWEEP_BITS_E = 4, IVX_SWEEP_BITS_K = 5,
        IVX_SWEEP_SORTED_IN = 6 /* the rows were taken as already in order */, IVX_SWEEP_TWO_STEP = 7 /* sort on (key, start), equal starts repaired: tried */,
@@ -324,7 +325,8 @@ enum { IVX_SWEEP_SORT_WORDS = 0 /* words of the radix sort that ran: 0 none, 1, 
        IVX_SWEEP_NARROW_ROWS = 9 /* the sweep's rows are 32-bit offsets */, IVX_SWEEP_K8 = 10 /* ... with one-byte keys */,
        IVX_SWEEP_PACKED = 11 /* 0 the sweep reads rows, 1 packed words instead of rows, 2 packed words beside rows (cluster) */,
        IVX_SWEEP_NARROW_RUNS = 12 /* k_pk_runs<..., NARROW = true> */, IVX_SWEEP_NTILE = 13 /* tiles of the packed sweep */,
-       IVX_SWEEP_WORDS = 14 };
+       IVX_SWEEP_LEFT_NW = 14, IVX_SWEEP_LEFT_SORT_WORDS = 15 /* intersect only: NW and SORT_WORDS of its LEFT side's sort */,
+       IVX_SWEEP_WORDS = 16 };
 static_assert(IVX_SWEEP_WORDS <= sizeof(ivx_ctx::sweep_form) / sizeof(u32), "ivx_ctx::sweep_form holds the IVX_SWEEP_* words");
 // words of ivx_debug_ctx_state (ivx_capi.hip; tests only, not in include/ivx.h), u64 each: what a context carries from one call
 // to the next.  The slot masks have a bit per scratch slot (WS_*) and are meaningful while their plan is valid.
@@ -464,6 +466,13 @@ ivx_status ivx_subtract_device(ivx_ctx *ctx, const u32 *lkey, const i64 *ls, con
                                const u32 *rkey, const i64 *rs, const i64 *re, u64 nr, u32 nkeys, int strict,
                                u32 *ok, i64 *os, i64 *oe, u32 *orow, u64 cap, u64 *n_out);
 ivx_status ivx_subtract_fill_planned(ivx_ctx *ctx, u32 *ok, i64 *os, i64 *oe, u32 *orow, u64 cap, u64 *n_out);
+// intersect; dbg (nullable; the test hook ivx_debug_intersect_paths): HOST buffers for what the count pass did -- `wg`: words
+// per workgroup (k_isect_count), `row_esc`: one byte per left row at its original index -- capacities in workgroups / rows,
+// and where the numbers of both go
+struct ivx_isect_debug { u32 *wg; u64 wg_cap; u8 *row_esc; u64 row_cap; u64 *n_wg, *n_rows; };
+ivx_status ivx_intersect_device(ivx_ctx *ctx, const u32 *lkey, const i64 *ls, const i64 *le, u64 nl,
+                                const u32 *rkey, const i64 *rs, const i64 *re, u64 nr, u32 nkeys, int strict,
+                                u32 *ok, i64 *os, i64 *oe, u32 *orow, u64 cap, u64 *n_out, const ivx_isect_debug *dbg = nullptr);
 ivx_status ivx_cluster_device(ivx_ctx *ctx, const u32 *key, const i64 *s, const i64 *e, u64 n, u32 nkeys,
                               i64 min_dist, int strict, const i64 *key_base,
                               u32 *ok, i64 *os, i64 *oe, u32 *orow, i64 *oc, i64 *ocs, i64 *oce, u64 *key_clusters, u64 *m);

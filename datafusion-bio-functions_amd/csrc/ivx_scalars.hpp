@@ -41,17 +41,18 @@ enum {
     SC_BUILD_FLAG = SC_MARK_BAD + 1,            // 1 word, u32[2]: [0] key id >= n_keys, [1] unsorted / a run too long / end < start
     SC_BUILD_INVERTED = SC_BUILD_FLAG + 1,      // 1 word, u32: count build: some row has end < start
     SC_NEAR_HDR = SC_BUILD_INVERTED + 1,        // 2 words, u32[3]: nearest build (k_nlin_layout): position bits, row bits, usable
-    // ---- sweeps: merge / subtract / cluster / complement and sort64 under them (ivx_sweep.hip).  Call-local.  One family, one
+    // ---- sweeps: merge / subtract / intersect / cluster / complement and sort64 under them (ivx_sweep.hip).  Call-local.  One family, one
     // flag: the operator clears it, sort64 raises it and reads its upper half, the operator reads it back at its end.
     SC_SWEEP_FLAG = SC_NEAR_HDR + 2,            // 1 word, u32[2]: [0] key id >= n_keys, [1] a (key, start) run too long to repair
+                                                // (intersect with one side empty, which sorts nothing: [1] a row with end < start)
     SC_SWEEP_IRREGULAR = SC_SWEEP_FLAG + 1,     // 1 word, u32: complement: the merged runs are not disjoint and ascending (cleared with the flag)
     // ---- depth regions (ivx_depth_regions.hip) and the text CIGARs' write pass (ivx_cigar.hip).  Call-local.
     SC_REGIONS_BAD = SC_SWEEP_IRREGULAR + 1,    // 1 word, u64: a region's key id >= n_keys
     SC_CIG_BADREAD = SC_REGIONS_BAD + 1,        // 1 word, u64: the first read with an op length that cannot be packed, or ~0
     // ---- radix sort (ivx_sort.hip), a callee of the sweeps, the builds, depth() and the routing.  Call-local.
     SC_SORT_VAR = SC_CIG_BADREAD + 1,           // SC_SORT_FIELDS words, u64 each: the bits that vary, per field
-    // ---- sort64 (ivx_sweep.hip).  Call-local, but for the host copy of SC_RANGE, which subtract reads once more after sort64
-    // returned (both inside one subtract call).
+    // ---- sort64 (ivx_sweep.hip).  Call-local, but for the host copy of SC_RANGE, which subtract and intersect read once more
+    // after sort64 returned (inside the same subtract / intersect call, before its next sort64).
     SC_RANGE = SC_SORT_VAR + SC_SORT_FIELDS,    // 6 words, Range64: the value ranges of the rows
     SC_LIN = SC_RANGE + 6,                      // 2 words, u64[2]: {usable, positions} of the linearised sort word; fetched with SC_RANGE
     // ---- depth() (ivx_depth.hip: ivx_depth_events, ivx_depth_device).  Call-local.  Six words cleared and fetched as one.

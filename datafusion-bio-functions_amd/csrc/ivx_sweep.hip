@@ -8,6 +8,8 @@
 //   f1 cluster (cluster.rs:443-477, :598-661)     -> the merge scans + one per-row pass (ivx_runs.hpp)
 //   f2 complement (complement.rs:297-357, :394-465) -> merge, then per view interval two binary
 //      searches over the merged runs + count/scan/fill by output row (see the complement section).
+//   intersect (no counterpart in the reference): subtract's dual -- per left row two partition points over the right side's
+//      merged runs + count/scan/fill by output row (see the intersect section).
 //
 // subtract without the serial cursor.  For one left row [ls,le) the reference
 // walks the rights of the contig in (start,end) order with cursor = ls:
@@ -845,6 +847,170 @@ __global__ __launch_bounds__(ST) void k_sub_fill(const u32 *__restrict__ lk, con
     }
 }
 
+// ---------------------------------------------------------------- intersect
+//
+// The dual of subtract: the pieces of a left row [ls,le) that the right side covers.  The right side goes in as its merged
+// runs (mk, ms, me) -- merge with min_dist = 0 -- whose starts ascend per key and, with rows of end < start refused, whose
+// ends ascend too.  Both halves of the overlap predicate (weak: ms <= le && me >= ls; strict: ms < le && me > ls) are then
+// monotone along the runs of a key, so the runs a row overlaps are the contiguous range
+//     a = first run with me >= ls (strict: > ls),   b = first run with ms > le (strict: >= le)
+// -- two partition points, the second a few runs after the first -- and piece j of the row is run a + j clipped to it.
+// (b < a only for ls == le in strict mode on an empty run at that very point: such a row overlaps nothing.)
+
+// the runs as plan_isect reads them: from global memory ...
+struct IsectGlobal {
+    const u32 *mk; const i64 *ms, *me;
+    __device__ __forceinline__ u32 K(u32 i) const { return mk[i]; }
+    __device__ __forceinline__ i64 S(u32 i) const { return ms[i]; }
+    __device__ __forceinline__ i64 E(u32 i) const { return me[i]; }
+    __device__ __forceinline__ u32 end(u32 m) const { return m; }
+    __device__ __forceinline__ void reached(u32, u32) const {}
+};
+// ... or from the workgroup's LDS copy of runs [w0, w0 + wn).  An index outside raises `esc` and reads slot 0: the caller
+// plans that row again from global memory.  (Two types, as SubGlobal / SubLds and for their reason: every read here is an
+// LDS read.)
+struct IsectLds {
+    const u32 *mk; const i64 *ms, *me;
+    u32 w0, wn;
+    mutable bool esc;
+    __device__ __forceinline__ u32 at(u32 i) const { const u32 x = i - w0; if (x >= wn) { esc = true; return 0u; } return x; }
+    __device__ __forceinline__ u32 K(u32 i) const { return mk[at(i)]; }
+    __device__ __forceinline__ i64 S(u32 i) const { return ms[at(i)]; }
+    __device__ __forceinline__ i64 E(u32 i) const { return me[at(i)]; }
+    // the gallop stops at the stretch's end: an answer AT that end, short of all runs, may lie beyond it
+    __device__ __forceinline__ u32 end(u32 m) const { const u32 we = w0 + wn; return we < m ? we : m; }
+    __device__ __forceinline__ void reached(u32 b, u32 m) const { if (b == w0 + wn && b < m) esc = true; }
+};
+
+// [ha, hb]: bounds of the first search (the caller's workgroup holds consecutive rows of the sorted left side, see k_sub_count)
+template <class A>
+__device__ __forceinline__ void plan_isect(u32 k, i64 ls, i64 le, int strict, const A &r, u32 m, u32 ha, u32 hb, u32 &a, u32 &b)
+{
+    a = bisect(ha, hb, [&](u32 i) { const u32 rk = r.K(i); if (rk != k) return rk < k; const i64 v = r.E(i); return strict ? (v <= ls) : (v < ls); });
+    // (up to r.end(m) only: a row whose range lies inside the staged stretch never leaves it, however its strides fall)
+    const u32 lim = r.end(m);
+    b = rank_near_up(a, lim, [&](u32 i) { const u32 rk = r.K(i); if (rk != k) return rk < k; const i64 v = r.S(i); return strict ? (v < le) : (v <= le); });
+    r.reached(b, m);
+    if (b < a) b = a;
+}
+
+// The runs a workgroup's searches touch are the stretch from its bracket's low end (one below: the gallop looks at its start's
+// predecessor) to ISECT_MARGIN past its high end, staged in LDS as (key, ms, me) when that is at most ISECT_RW runs
+constexpr u32 ISECT_RW = 832, ISECT_MARGIN = 48;                // (16.6 KB of LDS: eight workgroups per CU)
+// brk[b] = the `a` of the first left row of workgroup b, one thread per boundary as k_sub_brackets; a boundary at or behind
+// the last row takes that row's (nl a multiple of ST: the last rows' workgroup is followed by one that owns only cnt[nl])
+__global__ __launch_bounds__(ST) void k_isect_brackets(const u32 *__restrict__ lk, const i64 *__restrict__ lsv, u64 nl, const u32 *mk, const i64 *me, u32 m,
+                                                       int strict, u32 nblk, u32 *__restrict__ brk)
+{
+    const u32 b = blockIdx.x * ST + threadIdx.x;
+    if (b > nblk) return;
+    const u64 r = (u64)b * ST < nl ? (u64)b * ST : nl - 1;              // (nl > 0)
+    brk[b] = lex_rank(mk, me, m, lk[r], lsv[r], strict != 0);
+}
+
+// the checks of the sorts' range pass alone, for the side that faces an empty one (nothing is sorted then): flags[0] a key id
+// >= nkeys, flags[1] a row with end < start
+__global__ __launch_bounds__(ST) void k_isect_check(const u32 *__restrict__ key, const i64 *__restrict__ s, const i64 *__restrict__ e, u64 n, u32 nkeys, u32 *flags)
+{
+    const u64 i = (u64)blockIdx.x * ST + threadIdx.x;
+    if (i >= n) return;
+    if (key && key[i] >= nkeys) flags[0] = 1;
+    if (e[i] < s[i]) flags[1] = 1;
+}
+
+// One thread per sorted left row: cnt[i] = its pieces, plan_a[i] = its first run (the fill pass does not search again).
+// DEBUG (ivx_debug_intersect_paths, tests only): per workgroup ISECT_DBG_WORDS words (brk[b], brk[b+1], w0, wn, lds, rows
+// planned again after `esc`; all 0 for the workgroup that owns only cnt[nl]), zeroed by the caller, and per left row, at
+// its original index, whether its LDS plan raised `esc`.
+constexpr u32 ISECT_DBG_WORDS = 6;
+template <bool DEBUG>
+__global__ __launch_bounds__(ST) void k_isect_count(const u32 *__restrict__ lk, const i64 *__restrict__ lsv, const i64 *__restrict__ lev, u64 nl,
+                                                    int strict, const u32 *mk, const i64 *ms, const i64 *me, u32 m, u64 *cnt,
+                                                    u32 *__restrict__ plan_a, const u32 *__restrict__ brk,
+                                                    u32 *dbg_wg, u8 *dbg_esc, const u32 *dbg_lrow)
+{
+    __shared__ u32 s_h[2], s_win[2];
+    __shared__ u32 l_k[ISECT_RW];
+    __shared__ i64 l_s[ISECT_RW], l_e[ISECT_RW];
+    const u64 i0 = (u64)blockIdx.x * ST;
+    if (threadIdx.x < 2 && i0 < nl) s_h[threadIdx.x] = brk[blockIdx.x + threadIdx.x];
+    __syncthreads();
+    if (threadIdx.x == 0 && i0 < nl) {
+        const u32 w0 = s_h[0] > 0 ? s_h[0] - 1 : 0u;
+        const u32 w1 = m - s_h[1] > ISECT_MARGIN ? s_h[1] + ISECT_MARGIN : m;
+        s_win[0] = w0; s_win[1] = w1 - w0;
+    }
+    __syncthreads();
+    const bool lds = i0 < nl && s_win[1] <= ISECT_RW;                   // (the same for the whole workgroup)
+    if constexpr (DEBUG) {
+        if (threadIdx.x == 0 && i0 < nl) {
+            u32 *w = dbg_wg + (size_t)blockIdx.x * ISECT_DBG_WORDS;
+            w[0] = s_h[0]; w[1] = s_h[1]; w[2] = s_win[0]; w[3] = s_win[1]; w[4] = lds ? 1u : 0u;
+        }
+    }
+    if (lds) {
+        const u32 w0 = s_win[0], wn = s_win[1];
+        for (u32 x = threadIdx.x; x < wn; x += ST) { l_k[x] = mk[w0 + x]; l_s[x] = ms[w0 + x]; l_e[x] = me[w0 + x]; }
+        __syncthreads();
+    }
+    const u64 i = i0 + threadIdx.x;
+    if (i > nl) return;
+    if (i == nl) { cnt[i] = 0; return; }
+    const u32 k = lk[i]; const i64 ls = lsv[i], le = lev[i];
+    u32 a = 0, b = 0;
+    bool redo = !lds;
+    if (lds) {
+        const IsectLds r{l_k, l_s, l_e, s_win[0], s_win[1], false};
+        plan_isect(k, ls, le, strict, r, m, s_h[0], s_h[1], a, b);
+        redo = r.esc;
+    }
+    if constexpr (DEBUG) {
+        const bool esc = lds && redo;
+        dbg_esc[dbg_lrow[i]] = esc ? 1 : 0;
+        if (esc) atomicAdd(dbg_wg + (size_t)blockIdx.x * ISECT_DBG_WORDS + 5, 1u);
+    }
+    if (redo) { const IsectGlobal g{mk, ms, me}; plan_isect(k, ls, le, strict, g, m, s_h[0], s_h[1], a, b); }
+    cnt[i] = (u64)(b - a);
+    plan_a[i] = a;
+}
+
+// Pieces of ST consecutive left rows, one thread per OUTPUT row (as k_sub_fill): the rows, their first runs and their scanned
+// counts are staged in LDS, a thread finds the left row of its piece there by bisection, reads run a + j and writes the run
+// clipped to the row -- a wavefront's stores are consecutive whatever the rows' piece counts are
+__global__ __launch_bounds__(ST) void k_isect_fill(const u32 *__restrict__ lk, const i64 *__restrict__ lsv, const i64 *__restrict__ lev,
+                                                   const u32 *__restrict__ lrow, u64 nl, const i64 *__restrict__ ms, const i64 *__restrict__ me,
+                                                   const u64 *__restrict__ offs, const u32 *__restrict__ plan_a, u64 cap,
+                                                   u32 *ok, i64 *os, i64 *oe, u32 *orow)
+{
+    __shared__ u64 s_off[ST + 1];
+    __shared__ i64 s_ls[ST], s_le[ST];
+    __shared__ u32 s_k[ST], s_row[ST], s_a[ST];
+    const u64 i0 = (u64)blockIdx.x * ST;
+    const u32 nrows = (u32)(nl - i0 < (u64)ST ? nl - i0 : (u64)ST);
+    const u32 t = threadIdx.x;
+    if (t < nrows) {
+        const u64 i = i0 + t;
+        s_off[t] = offs[i]; s_k[t] = lk[i]; s_ls[t] = lsv[i]; s_le[t] = lev[i]; s_row[t] = lrow[i]; s_a[t] = plan_a[i];
+    }
+    if (t == 0) s_off[nrows] = offs[i0 + nrows];
+    __syncthreads();
+    const u64 base = s_off[0];
+    const u64 total = s_off[nrows] - base;
+    for (u64 o = t; o < total; o += ST) {
+        const u64 at = base + o;
+        if (at >= cap) return;
+        u32 lo = 0, hi = nrows - 1;                                     // last row r with s_off[r] <= at
+        while (lo < hi) { const u32 mid = (lo + hi + 1) >> 1; if (s_off[mid] <= at) lo = mid; else hi = mid - 1; }
+        const u32 r = lo;
+        const u32 run = s_a[r] + (u32)(at - s_off[r]);
+        const i64 ls = s_ls[r], le = s_le[r], rs = ms[run], re = me[run];
+        if (ok) ok[at] = s_k[r];
+        if (os) os[at] = rs > ls ? rs : ls;
+        if (oe) oe[at] = re < le ? re : le;
+        if (orow) orow[at] = s_row[r];
+    }
+}
+
 ivx_status keyflag(ivx_ctx *ctx, const char *what) { return ctx->check_flag(SC_SWEEP_FLAG, ctx->stream, what); }
 
 // ---------------------------------------------------------------- complement
@@ -1279,4 +1445,113 @@ ivx_status ivx_complement_device(ivx_ctx *ctx, const u32 *key, const i64 *s, con
                            (const u32 *)has_in, R, (const u64 *)cnt, (const u32 *)inv, (const u32 *)pa, (const u32 *)pb, total, ok, os, oe);
     IVX_HIP(ctx, hipGetLastError());
     return IVX_OK;
+}
+
+// intersect: sort the right side and merge it into runs exactly as complement does its input, sort the left side with its row
+// ids, count (k_isect_brackets, k_isect_count), scan, fill (k_isect_fill).  No plan is kept: a sizing call returns after the
+// scan, and the fill call does all of it again.  With one side empty nothing is sorted, but the other side's rows are checked
+// as the sorts would check them.  The form words (ivx_debug_sweep_form) are the right side's, and two of the left side's
+// sort (IVX_SWEEP_LEFT_*).  dbg (tests only): the count pass also reports what it did.
+ivx_status ivx_intersect_device(ivx_ctx *ctx, const u32 *lkey, const i64 *ls, const i64 *le, u64 nl,
+                                const u32 *rkey, const i64 *rs, const i64 *re, u64 nr, u32 nkeys, int strict,
+                                u32 *ok, i64 *os, i64 *oe, u32 *orow, u64 cap, u64 *n_out, const ivx_isect_debug *dbg)
+{
+    *n_out = 0;
+    for (u32 &f : ctx->sweep_form) f = 0;
+    const u32 nblk_c = grid1(nl + 1);
+    if (dbg) {
+        *dbg->n_wg = nl && nr ? nblk_c : 0; *dbg->n_rows = nl && nr ? nl : 0;
+        if (nl && nr && (dbg->wg_cap < nblk_c || dbg->row_cap < nl || !dbg->wg || !dbg->row_esc))
+            return ctx->fail(IVX_ERR_CAPACITY, "debug_intersect_paths: buffers too small");
+    }
+    if (nl == 0 && nr == 0) return IVX_OK;
+    hipStream_t st = ctx->stream;
+    IVX_HIP(ctx, hipMemsetAsync(ctx->dword(SC_SWEEP_FLAG), 0, sizeof(u64), st));
+    const char *const malformed = "intersect: a row with end < start";
+    if (nl == 0 || nr == 0) {                                               // no piece; the rows that are there still have to be valid
+        const u64 n = nl ? nl : nr;
+        hipLaunchKernelGGL(k_isect_check, dim3(grid1(n)), dim3(ST), 0, st, nl ? lkey : rkey, nl ? ls : rs, nl ? le : re, n, nkeys, ctx->dword<u32>(SC_SWEEP_FLAG));
+        IVX_HIP(ctx, hipGetLastError());
+        IVX_HIP(ctx, ctx->fetch(SC_SWEEP_FLAG, st));
+        IVX_HIP(ctx, hipStreamSynchronize(st));
+        const u32 *f = ctx->hword<u32>(SC_SWEEP_FLAG);
+        if (f[1]) return ctx->fail(IVX_ERR_INVALID, malformed);
+        if (f[0]) return ctx->fail(IVX_ERR_INVALID, "intersect: key id >= n_keys");
+        return IVX_OK;
+    }
+
+    // the right side's merged runs (min_dist = 0): with no row of end < start their ends ascend per key
+    u32 *mk; i64 *ms, *me; u64 m = 0;
+    IVX_TRY(ctx->get_scratch(WS_T3, nr * sizeof(u32), (void **)&mk));
+    IVX_TRY(ctx->get_scratch(WS_T4, nr * sizeof(i64), (void **)&ms));
+    IVX_TRY(ctx->get_scratch(WS_T7, nr * sizeof(i64), (void **)&me));
+    {
+        u32 *ks; i64 *ss, *es;
+        IVX_TRY(ctx->get_scratch(WS_T0, nr * sizeof(u32), (void **)&ks));
+        IVX_TRY(ctx->get_scratch(WS_T1, nr * sizeof(i64), (void **)&ss));
+        IVX_TRY(ctx->get_scratch(WS_T2, nr * sizeof(i64), (void **)&es));
+        SortedRows rows;
+        PackedWant pk{0, strict, false, nullptr, Pack64{}};
+        IVX_TRY(sort64(ctx, WS_SA0, WS_SB0, rkey, rs, re, nr, nkeys, ks, ss, es, nullptr, &rows, &pk));
+        if (ctx->hword<Range64>(SC_RANGE)->odd & 1ull) return ctx->fail(IVX_ERR_INVALID, malformed);
+        const ivx_runs_out ro{mk, ms, me, nullptr};
+        if (pk.ok) IVX_TRY(ivx_merge_runs_packed(ctx, pk.w, nr, pk.p, 0, strict, ro, &m));
+        else IVX_TRY(ivx_merge_runs_rows(ctx, rows, nr, 0, strict, ro, &m));
+    }
+
+    // the left side in (key, start, end, row) order; the sorted right rows and the sweep's scratch are dead by now
+    u32 *lk, *lrow; i64 *lsv, *lev;
+    IVX_TRY(ctx->get_scratch(WS_T0, nl * sizeof(u32), (void **)&lk));
+    IVX_TRY(ctx->get_scratch(WS_T1, nl * sizeof(i64), (void **)&lsv));
+    IVX_TRY(ctx->get_scratch(WS_T2, nl * sizeof(i64), (void **)&lev));
+    IVX_TRY(ctx->get_scratch(WS_T6, nl * sizeof(u32), (void **)&lrow));
+    {
+        // (the form words stay the right side's, but for two: which sort the left side -- the one with the row word -- took)
+        u32 right_form[IVX_SWEEP_WORDS];
+        for (int i = 0; i < IVX_SWEEP_WORDS; i++) right_form[i] = ctx->sweep_form[i];
+        const ivx_status s = sort64(ctx, WS_RA0, WS_RB0, lkey, ls, le, nl, nkeys, lk, lsv, lev, lrow);
+        right_form[IVX_SWEEP_LEFT_NW] = ctx->sweep_form[IVX_SWEEP_NW]; right_form[IVX_SWEEP_LEFT_SORT_WORDS] = ctx->sweep_form[IVX_SWEEP_SORT_WORDS];
+        for (int i = 0; i < IVX_SWEEP_WORDS; i++) ctx->sweep_form[i] = right_form[i];
+        IVX_TRY(s);
+    }
+    if (ctx->hword<Range64>(SC_RANGE)->odd & 1ull) return ctx->fail(IVX_ERR_INVALID, malformed);
+    IVX_TRY(keyflag(ctx, "intersect: key id >= n_keys"));
+
+    u64 *cnt; u32 *plan_a, *brk;
+    IVX_TRY(ctx->get_scratch(WS_T5, (nl + 1) * sizeof(u64), (void **)&cnt));
+    IVX_TRY(ctx->get_scratch(WS_T8, nl * sizeof(u32), (void **)&plan_a));
+    IVX_TRY(ctx->get_scratch(WS_GRID0, ((size_t)nblk_c + 2) * sizeof(u32), (void **)&brk));
+    hipLaunchKernelGGL(k_isect_brackets, dim3(grid1((u64)nblk_c + 1)), dim3(ST), 0, st, (const u32 *)lk, (const i64 *)lsv, nl, (const u32 *)mk, (const i64 *)me, (u32)m,
+                       strict, nblk_c, brk);
+    if (!dbg)
+        hipLaunchKernelGGL(k_isect_count<false>, dim3(nblk_c), dim3(ST), 0, st, (const u32 *)lk, (const i64 *)lsv, (const i64 *)lev, nl, strict,
+                           (const u32 *)mk, (const i64 *)ms, (const i64 *)me, (u32)m, cnt, plan_a, (const u32 *)brk, (u32 *)nullptr, (u8 *)nullptr, (const u32 *)nullptr);
+    else {
+        u32 *d_wg; u8 *d_esc;                                               // (the sorts' record slots are free again)
+        const size_t wg_bytes = (size_t)nblk_c * ISECT_DBG_WORDS * sizeof(u32);
+        IVX_TRY(ctx->get_scratch(WS_SA0, wg_bytes, (void **)&d_wg));
+        IVX_TRY(ctx->get_scratch(WS_SA1, nl, (void **)&d_esc));
+        IVX_HIP(ctx, hipMemsetAsync(d_wg, 0, wg_bytes, st));
+        hipLaunchKernelGGL(k_isect_count<true>, dim3(nblk_c), dim3(ST), 0, st, (const u32 *)lk, (const i64 *)lsv, (const i64 *)lev, nl, strict,
+                           (const u32 *)mk, (const i64 *)ms, (const i64 *)me, (u32)m, cnt, plan_a, (const u32 *)brk, d_wg, d_esc, (const u32 *)lrow);
+        IVX_HIP(ctx, hipMemcpyAsync(dbg->wg, d_wg, wg_bytes, hipMemcpyDeviceToHost, st));
+        IVX_HIP(ctx, hipMemcpyAsync(dbg->row_esc, d_esc, nl, hipMemcpyDeviceToHost, st));
+    }
+    IVX_TRY(ivx_scan_exclusive_u64(ctx, cnt, nl + 1));
+    u64 total;
+    IVX_TRY(ctx->fetch_wait((const u64 *)cnt + nl, st, &total));            // (lands in the scalar table's SC_LANDING; synchronises)
+    *n_out = total;
+    if (cap == 0 && !ok && !os && !oe && !orow) return IVX_OK;              // count only
+    if (total > cap) return ctx->fail(IVX_ERR_CAPACITY, "intersect: output buffers too small");
+    if (total == 0) return IVX_OK;
+    hipLaunchKernelGGL(k_isect_fill, dim3(grid1(nl)), dim3(ST), 0, st, (const u32 *)lk, (const i64 *)lsv, (const i64 *)lev, (const u32 *)lrow, nl,
+                       (const i64 *)ms, (const i64 *)me, (const u64 *)cnt, (const u32 *)plan_a, cap, ok, os, oe, orow);
+    IVX_HIP(ctx, hipGetLastError());
+    return IVX_OK;
+}
+
+// The constants a test needs to build a shape for one path of k_isect_count (ivx_debug_intersect_paths, ivx_capi.hip)
+extern "C" void ivx_debug_intersect_geometry(u32 *rows_per_wg, u32 *staged_runs, u32 *margin, u32 *dbg_words)
+{
+    *rows_per_wg = ST; *staged_runs = ISECT_RW; *margin = ISECT_MARGIN; *dbg_words = ISECT_DBG_WORDS;
 }

@@ -675,27 +675,42 @@ extern "C" int brh_merge(brh_session *s, brh_batch table, brh_columns cols, int6
     return 0;
 }
 
-extern "C" int brh_subtract(brh_session *s, brh_batch left, brh_columns lcols, brh_batch right, brh_columns rcols, int filter_op,
-                            ArrowArray *contig, ArrowSchema *contig_schema, ArrowArray *start, ArrowSchema *start_schema,
-                            ArrowArray *end, ArrowSchema *end_schema, ArrowArray *left_row, ArrowSchema *left_row_schema)
+// subtract and intersect: the same arguments, the same sizing-then-fill protocol, the same schema (the left table's names)
+static int left_pieces(decltype(&ivx_subtract) op, brh_session *s, brh_batch left, brh_columns lcols, brh_batch right, brh_columns rcols, int filter_op,
+                       ArrowArray *contig, ArrowSchema *contig_schema, ArrowArray *start, ArrowSchema *start_schema,
+                       ArrowArray *end, ArrowSchema *end_schema, ArrowArray *left_row, ArrowSchema *left_row_schema)
 {
     if (!s) return 1;
     KeyDict kd; Side64 L, R;
     if (build_keys(s, {{left, lcols}, {right, rcols}}, &kd) || load_side64(s, left, lcols, &L) || load_side64(s, right, rcols, &R)) return 1;
     const uint32_t nk = (uint32_t)std::max<size_t>(kd.names.size(), 1);
     uint64_t m = 0, m2 = 0;                              // sizing call, then the fill call
-    ivx_status st = ivx_subtract(s->ctx, IVX_MEM_HOST, kd.ids[0].data(), L.s.data(), L.e.data(), L.s.size(), kd.ids[1].data(), R.s.data(), R.e.data(),
-                                 R.s.size(), nk, filter_op == BRH_STRICT, nullptr, nullptr, nullptr, nullptr, 0, &m);
+    ivx_status st = op(s->ctx, IVX_MEM_HOST, kd.ids[0].data(), L.s.data(), L.e.data(), L.s.size(), kd.ids[1].data(), R.s.data(), R.e.data(),
+                       R.s.size(), nk, filter_op == BRH_STRICT, nullptr, nullptr, nullptr, nullptr, 0, &m);
     if (st != IVX_OK) return fail_ivx(s, st);
     std::vector<uint32_t> ok(m ? m : 1), orow(m ? m : 1); std::vector<int64_t> os(m ? m : 1), oe(m ? m : 1);
-    st = ivx_subtract(s->ctx, IVX_MEM_HOST, kd.ids[0].data(), L.s.data(), L.e.data(), L.s.size(), kd.ids[1].data(), R.s.data(), R.e.data(),
-                      R.s.size(), nk, filter_op == BRH_STRICT, ok.data(), os.data(), oe.data(), orow.data(), m, &m2);
+    st = op(s->ctx, IVX_MEM_HOST, kd.ids[0].data(), L.s.data(), L.e.data(), L.s.size(), kd.ids[1].data(), R.s.data(), R.e.data(),
+            R.s.size(), nk, filter_op == BRH_STRICT, ok.data(), os.data(), oe.data(), orow.data(), m, &m2);
     if (st != IVX_OK) return fail_ivx(s, st);
     make_utf8(contig, kd.names, ok.data(), (int64_t)m2); make_schema(contig_schema, "u", lcols.keys[0], false);
     make_primitive<int64_t>(start, os.data(), (int64_t)m2, nullptr); make_schema(start_schema, "l", lcols.start, false);   // subtract.rs:57-72
     make_primitive<int64_t>(end, oe.data(), (int64_t)m2, nullptr); make_schema(end_schema, "l", lcols.end, false);
     make_primitive<uint32_t>(left_row, orow.data(), (int64_t)m2, nullptr); make_schema(left_row_schema, "I", "left_row", false);
     return 0;
+}
+
+extern "C" int brh_subtract(brh_session *s, brh_batch left, brh_columns lcols, brh_batch right, brh_columns rcols, int filter_op,
+                            ArrowArray *contig, ArrowSchema *contig_schema, ArrowArray *start, ArrowSchema *start_schema,
+                            ArrowArray *end, ArrowSchema *end_schema, ArrowArray *left_row, ArrowSchema *left_row_schema)
+{
+    return left_pieces(ivx_subtract, s, left, lcols, right, rcols, filter_op, contig, contig_schema, start, start_schema, end, end_schema, left_row, left_row_schema);
+}
+
+extern "C" int brh_intersect(brh_session *s, brh_batch left, brh_columns lcols, brh_batch right, brh_columns rcols, int filter_op,
+                             ArrowArray *contig, ArrowSchema *contig_schema, ArrowArray *start, ArrowSchema *start_schema,
+                             ArrowArray *end, ArrowSchema *end_schema, ArrowArray *left_row, ArrowSchema *left_row_schema)
+{
+    return left_pieces(ivx_intersect, s, left, lcols, right, rcols, filter_op, contig, contig_schema, start, start_schema, end, end_schema, left_row, left_row_schema);
 }
 
 extern "C" int brh_cluster(brh_session *s, brh_batch table, brh_columns cols, int64_t min_dist, int filter_op,

@@ -34,7 +34,7 @@ SYMBOLS = [
     "ivx_cigar_parse", "ivx_depth_text", "ivx_depth_profile_build_text",
     "ivx_depth_profile_summarize", "ivx_depth_profile_windows",
     "ivx_depth_profile_quantiles", "ivx_depth_profile_window_quantiles",
-    "ivx_depth_profile_quantize", "ivx_depth_profile_hist",
+    "ivx_depth_profile_quantize", "ivx_depth_profile_hist", "ivx_intersect",
 ]
 
 # outputs one workgroup of the expand kernel makes (csrc/ivx_depth_expand.hip DEPTH_EXPAND_TILE; tests/test_depth_per_base_tile.py)
@@ -80,6 +80,21 @@ NEAR_FB_NOFIT, NEAR_FB_LIN_RUN, NEAR_FB_SE_RUN = 1, 2, 4                # near_f
 SWEEP_SLOTS = ["sort_words", "nw", "lin", "bits_s", "bits_e", "bits_k", "sorted_in", "two_step", "toolong", "narrow_rows", "k8",
                "packed", "narrow_runs", "ntile"]
 SWEEP_ROWS, SWEEP_PACKED, SWEEP_PACKED_BESIDE_ROWS = 0, 1, 2            # packed
+# ... and the two words behind them that only an intersect sets (IVX_SWEEP_LEFT_*): nw and sort_words of its LEFT side's sort
+SWEEP_LEFT_SLOTS = ["left_nw", "left_sort_words"]
+
+# words per workgroup of the test hook ivx_debug_intersect_paths (csrc/ivx_sweep.hip k_isect_count), in order: the bracket of the
+# workgroup's first searches, the staged window (first run, runs), whether LDS was used, rows planned again from global memory
+ISECT_DBG_SLOTS = ["brk_lo", "brk_hi", "win_first", "win_runs", "lds", "escaped"]
+
+
+def intersect_geometry():
+    """the constants of intersect's count pass (test hook ivx_debug_intersect_geometry): left rows per workgroup, the most
+    runs a workgroup stages in LDS, the runs staged past its bracket, the words of ISECT_DBG_SLOTS"""
+    v = [C.c_uint32(0) for _ in range(4)]
+    lib().ivx_debug_intersect_geometry(*[C.byref(x) for x in v])
+    return dict(zip(("rows_per_wg", "staged_runs", "margin", "dbg_words"), (x.value for x in v)))
+
 
 # words of the test hook ivx_debug_ctx_state (csrc/ivx_internal.hpp IVX_STATE_*), in order; the masks have a bit per scratch slot
 STATE_SLOTS = ["join_valid", "join_slots", "sub_valid", "sub_slots", "tail_pending", "scratch_held", "pool_free", "join_fills_planned",
@@ -181,6 +196,16 @@ def lib():
         # test hook of csrc/ivx_sweep.hip (not in include/ivx.h): what subtract's count pass did (tests/test_gpu_subtract_edges.py)
         L.ivx_debug_subtract_paths.restype = C.c_int
         L.ivx_debug_subtract_paths.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.ivx_intersect.restype = C.c_int
+        L.ivx_intersect.argtypes = ([C.c_void_p, C.c_int] + [C.c_void_p] * 3 + [C.c_uint64] + [C.c_void_p] * 3 + [C.c_uint64, C.c_uint32, C.c_int] +
+                                    [C.c_void_p] * 4 + [C.c_uint64, C.POINTER(C.c_uint64)])
+        # test hooks of csrc/ivx_capi.hip / ivx_sweep.hip (not in include/ivx.h): the same call up to `strict`, then where to report
+        # what its count pass did; the constants of that pass (tests/test_gpu_intersect_edges.py)
+        L.ivx_debug_intersect_paths.restype = C.c_int
+        L.ivx_debug_intersect_paths.argtypes = (L.ivx_intersect.argtypes[:12] + [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64] +
+                                                [C.POINTER(C.c_uint64)] * 3)
+        L.ivx_debug_intersect_geometry.restype = None
+        L.ivx_debug_intersect_geometry.argtypes = [C.POINTER(C.c_uint32)] * 4
         # test hook of csrc/ivx_capi.hip (not in include/ivx.h): the forms a count / coverage / nearest index took (tests/test_gpu_rank_edges.py)
         L.ivx_debug_index_forms.restype = C.c_int
         L.ivx_debug_index_forms.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32), C.c_uint32]
@@ -825,9 +850,71 @@ class Ctx:
         m2 = m2.value
         return ok[:m2], os_[:m2], oe[:m2], orow[:m2]
 
+    def intersect_left_form(self):
+        """after an intersect: which sort its left side took (the words of SWEEP_LEFT_SLOTS behind those of sweep_form()) as a dict"""
+        n = len(SWEEP_SLOTS) + len(SWEEP_LEFT_SLOTS)
+        out = (C.c_uint32 * n)()
+        self._chk0(lib().ivx_debug_sweep_form(self.h, out, C.c_uint32(n)))
+        return dict(zip(SWEEP_LEFT_SLOTS, list(out)[len(SWEEP_SLOTS):]))
+
+    # (Ctx.subtract keeps its own copy of this normalisation inline, as it was before intersect came: the two must stay alike)
+    def _two_sides(self, lkey, ls, le, rkey, rs, re, n_keys, strict):
+        """both sides of subtract / intersect normalised -> (the C arguments from `mem` to `strict`, mem, nl, device or None)"""
+        lkey, ls, le, nl, mem = _cols(lkey, ls, le, np.int64)
+        rkey, rs, re, nr, mem2 = _cols(rkey, rs, re, np.int64)
+        assert mem == mem2
+        if n_keys is None:
+            mk = 0
+            for k_, n_ in ((lkey, nl), (rkey, nr)):
+                if k_ is not None and n_:
+                    mk = max(mk, int(k_.max()))
+            n_keys = mk + 1
+        args = (C.c_int(mem), _ptr(lkey), _ptr(ls), _ptr(le), C.c_uint64(nl), _ptr(rkey), _ptr(rs), _ptr(re),
+                C.c_uint64(nr), C.c_uint32(n_keys), C.c_int(int(strict)))
+        return args, (lkey, ls, le, rkey, rs, re), mem, nl, (ls.device if mem == MEM_DEVICE else None)
+
+    def intersect(self, lkey, ls, le, rkey, rs, re, n_keys=None, strict=False, cap=None):
+        """the pieces of the left rows that the right side covers (include/ivx.h ivx_intersect) -> (key, start, end, left row).
+        cap=None: sizing call, then the fill call (which does the work again: no plan is kept).  cap=N: one call into
+        buffers of N rows."""
+        args, keep, mem, _, dev = self._two_sides(lkey, ls, le, rkey, rs, re, n_keys, strict)
+        if cap is None:
+            m = C.c_uint64(0)
+            self._chk(lib().ivx_intersect(self.h, *args, None, None, None, None, C.c_uint64(0), C.byref(m)))
+            cap = max(m.value, 1)
+        if mem == MEM_DEVICE:
+            import torch
+            ok, os_, oe, orow = (torch.empty(cap, dtype=dt, device=dev) for dt in (torch.int32, torch.int64, torch.int64, torch.int32))
+        else:
+            ok, os_, oe, orow = np.empty(cap, np.uint32), np.empty(cap, np.int64), np.empty(cap, np.int64), np.empty(cap, np.uint32)
+        m2 = C.c_uint64(0)
+        self._chk(lib().ivx_intersect(self.h, *args, _ptr(ok), _ptr(os_), _ptr(oe), _ptr(orow), C.c_uint64(cap), C.byref(m2)))
+        m2 = m2.value
+        return ok[:m2], os_[:m2], oe[:m2], orow[:m2]
+
+    def intersect_count(self, lkey, ls, le, rkey, rs, re, n_keys=None, strict=False):
+        """the sizing call of intersect alone -> the number of pieces"""
+        args, keep, _, _, _ = self._two_sides(lkey, ls, le, rkey, rs, re, n_keys, strict)
+        m = C.c_uint64(0)
+        self._chk(lib().ivx_intersect(self.h, *args, None, None, None, None, C.c_uint64(0), C.byref(m)))
+        return m.value
+
+    def intersect_paths(self, lkey, ls, le, rkey, rs, re, n_keys=None, strict=False):
+        """what the count pass of an intersect sizing call for these inputs does (test hook ivx_debug_intersect_paths) ->
+        (wg, row_esc, n_out): wg uint32 [workgroups, len(ISECT_DBG_SLOTS)], row_esc uint8 per left row at its input index"""
+        args, keep, mem, nl, _ = self._two_sides(lkey, ls, le, rkey, rs, re, n_keys, strict)
+        g = intersect_geometry()
+        nwg = (nl + 1 + g["rows_per_wg"] - 1) // g["rows_per_wg"]
+        wg = np.zeros((nwg, g["dbg_words"]), np.uint32); esc = np.zeros(max(nl, 1), np.uint8)
+        n_wg, n_rows, n_out = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        self._chk(lib().ivx_debug_intersect_paths(self.h, *args, _ptr(wg), C.c_uint64(nwg), _ptr(esc), C.c_uint64(len(esc)),
+                                                   C.byref(n_wg), C.byref(n_rows), C.byref(n_out)))
+        return wg[:n_wg.value], esc[:n_rows.value], n_out.value
+
     def sweep_form(self):
         """the forms the last merge / cluster / complement of this context took (test hook ivx_debug_sweep_form) as a dict of
-        the SWEEP_SLOTS: what its sort and its packed sweep decided on the host.  After a subtract: its last sort's."""
+        the SWEEP_SLOTS: what its sort and its packed sweep decided on the host.  After a subtract: its last sort's; after an
+        intersect: its right side's."""
         out = (C.c_uint32 * len(SWEEP_SLOTS))()
         self._chk0(lib().ivx_debug_sweep_form(self.h, out, C.c_uint32(len(SWEEP_SLOTS))))
         return dict(zip(SWEEP_SLOTS, list(out)))

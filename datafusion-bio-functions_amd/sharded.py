@@ -139,6 +139,11 @@ class ShardedRanges:
         row = self.to_job_rows(rows_l, row)
         return self.splice_by_key(k, (s, e, row)) if gather else (k, s, e, row)
 
+    def intersect(self, left, rows_l, right, strict=False, gather=True):
+        k, s, e, row = self.eng.intersect(*left, *right, n_keys=self.n_keys, strict=strict)
+        row = self.to_job_rows(rows_l, row)
+        return self.splice_by_key(k, (s, e, row)) if gather else (k, s, e, row)
+
     def complement(self, rows, view=None, strict=False, gather=True):
         import torch
         v = view if view is not None else (None, None, None)

@@ -137,6 +137,18 @@ int brh_subtract(brh_session *s, brh_batch left, brh_columns lcols, brh_batch ri
                  struct ArrowArray *end, struct ArrowSchema *end_schema,
                  struct ArrowArray *left_row, struct ArrowSchema *left_row_schema);
 
+/* intersect('left','right'): the pieces of every left row that the right table's merged intervals cover (ivx_intersect,
+ * include/ivx.h; the reference has no such table function).  Schema and behaviour of brh_subtract: contig Utf8, start
+ * Int64, end Int64 named after the LEFT table's columns, in (contig in byte order, start, end, left row) order with a
+ * row's pieces ascending, and left_row UInt32 (the row of `left` each piece came from, for the extra-columns take).  A row
+ * with end < start in either table is an error. */
+int brh_intersect(brh_session *s, brh_batch left, brh_columns lcols, brh_batch right, brh_columns rcols,
+                  int filter_op,
+                  struct ArrowArray *contig, struct ArrowSchema *contig_schema,
+                  struct ArrowArray *start, struct ArrowSchema *start_schema,
+                  struct ArrowArray *end, struct ArrowSchema *end_schema,
+                  struct ArrowArray *left_row, struct ArrowSchema *left_row_schema);
+
 /* cluster('table'[,min_dist]...): ClusterProvider / ClusterStream / ClusterStreamExtra
  * (R/src/cluster.rs:29-82, :517-760, :762-977).  One output row per input row, sorted by
  * (contig, start, end, input row): contig Utf8, start Int64, end Int64, row UInt32 (the input row,

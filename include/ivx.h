@@ -314,6 +314,32 @@ ivx_status ivx_subtract(ivx_ctx *ctx, int mem,
                         uint32_t *out_key, int64_t *out_start, int64_t *out_end, uint32_t *out_row,
                         uint64_t cap, uint64_t *n_out);
 
+/* ---- INTERSECT: the pieces of every left row that the right side covers (bedtools intersect, pyranges intersect, "my
+ *      targets clipped to the callable regions"; the dual of ivx_subtract; the reference has no such table function, so the
+ *      contract is stated against ivx_merge and the join's predicate).  Coordinates are int64, key ids < n_keys, strict as
+ *      everywhere: 0 weak (closed coordinates), 1 strict (half-open).
+ *      Let U = the rows ivx_merge(right, min_dist = 0, strict) returns, (key, ms, me): the right side's merged runs.  The
+ *      left rows are taken in (key, start, end, input row) order, the order of ivx_subtract.  A left row (k, ls, le) overlaps
+ *      a run of key k iff  ms <= le && me >= ls  (strict: ms < le && me > ls), and for every left row in that order and
+ *      every run it overlaps in ascending ms one output row goes out:
+ *          (k, max(ls, ms), min(le, me), left input row)
+ *      and nothing else.  The output order is thereby fully specified.  A left row whose key has no right row emits
+ *      nothing; nr = 0 or nl = 0 gives *n_out = 0 (the rows of the other side are still checked).  start == end is legal
+ *      on both sides.  Together with the fragments ivx_subtract gives a left row, its pieces tile [ls, le].
+ *      A row with end < start on either side: IVX_ERR_INVALID, "intersect: a row with end < start", nothing written.
+ *      Arguments as ivx_subtract: keys nullable on both sides together (one side only, both non-empty: IVX_ERR_INVALID);
+ *      fewer than 2^32 - 1 rows per side; a key id >= n_keys is IVX_ERR_INVALID; cap = 0 with NULL outputs only counts;
+ *      cap < *n_out is IVX_ERR_CAPACITY with *n_out = the size needed and nothing written; any output may be NULL on its
+ *      own.  Drops the state a sizing call of another operation left on the context, and keeps none of its own: the fill
+ *      call after a sizing call sorts, merges and counts again.  Work: two sorts, the merge sweep, per left row two
+ *      partition points over the runs, one thread per output row. */
+ivx_status ivx_intersect(ivx_ctx *ctx, int mem,
+                         const uint32_t *lkey, const int64_t *lstart, const int64_t *lend, uint64_t nl,
+                         const uint32_t *rkey, const int64_t *rstart, const int64_t *rend, uint64_t nr,
+                         uint32_t n_keys, int strict,
+                         uint32_t *out_key, int64_t *out_start, int64_t *out_end, uint32_t *out_row,
+                         uint64_t cap, uint64_t *n_out);
+
 /* ---- f1: ClusterStream / ClusterStreamExtra (cluster.rs:443-477, :598-661, :813-884) and the
  *      ClusterIdCoordinator offsets (cluster.rs:380-420).  Output has exactly n rows, sorted by
  *      (key, start, end, input row): the sorted row itself (out_key/out_start/out_end, and

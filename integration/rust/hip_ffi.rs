@@ -86,6 +86,10 @@ extern "C" {
                         rkey: *const u32, rs: *const i64, re: *const i64, nr: u64, n_keys: u32, strict: i32,
                         out_key: *mut u32, out_start: *mut i64, out_end: *mut i64, out_row: *mut u32, cap: u64,
                         n_out: *mut u64) -> i32;
+    pub fn ivx_intersect(ctx: *mut IvxCtx, mem: i32, lkey: *const u32, ls: *const i64, le: *const i64, nl: u64,
+                         rkey: *const u32, rs: *const i64, re: *const i64, nr: u64, n_keys: u32, strict: i32,
+                         out_key: *mut u32, out_start: *mut i64, out_end: *mut i64, out_row: *mut u32, cap: u64,
+                         n_out: *mut u64) -> i32;
     pub fn ivx_cluster(ctx: *mut IvxCtx, mem: i32, key: *const u32, start: *const i64, end: *const i64, n: u64, n_keys: u32,
                        min_dist: i64, strict: i32, key_base: *const i64, out_key: *mut u32, out_start: *mut i64,
                        out_end: *mut i64, out_row: *mut u32, out_cluster: *mut i64, out_cluster_start: *mut i64,

@@ -1,0 +1,257 @@
+"""-m gpu: intersect at the edges of its count pass's LDS window, of its workgroups and of its fill pass.
+
+k_isect_count (csrc/ivx_sweep.hip) stages for every workgroup of 256 sorted left rows the stretch of merged runs its rows'
+searches touch -- from one below brk[b] to `margin` past brk[b+1] -- when it is at most `staged_runs` runs; a row whose
+searches leave the stretch raises `esc` and is planned again from global memory, and a workgroup whose stretch does not fit
+plans all its rows there.  Every window case here reads what the pass did (Ctx.intersect_paths, the test hook
+ivx_debug_intersect_paths), compares it with the window rule restated below, and asserts the edge it names; a case whose
+readout does not show its edge fails.  All four output columns are compared bit-exactly with restatement (a) of
+tests/intersect_oracle.py, with strict False and True, and once more with the left rows shuffled (output only).
+
+Construction: rights on a lattice, right j = [100j+10, 100j+60] in one key, so every right is a run of its own and run j is
+right j.  A left row [100q+20, 100q+30] overlaps run q alone and its first search ends at q; one at [100q+70, 100q+90] lies in
+the gap behind run q and overlaps nothing.  Lefts are given sorted, so a row's sorted position is its index."""
+import bisect
+import os
+import sys
+
+import numpy as np
+import pytest
+
+from conftest import ROOT
+from oracle import oracle as orc
+
+import intersect_oracle as io
+
+sys.path.insert(0, os.path.join(ROOT, "datafusion-bio-functions_amd"))
+import pyivx  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+B_LO, B_HI, W_FIRST, W_RUNS, W_LDS, W_ESC = range(6)
+KEY = 1
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    c = pyivx.Ctx(0)
+    yield c
+    c.close()
+
+
+@pytest.fixture(scope="module")
+def geo():
+    g = pyivx.intersect_geometry()
+    assert g["rows_per_wg"] == 256 and g["dbg_words"] == 6
+    return g
+
+
+def cols(key, s, e):
+    s = np.asarray(s, np.int64); e = np.asarray(e, np.int64)
+    k = np.full(len(s), key, np.uint32) if np.isscalar(key) else np.asarray(key, np.uint32)
+    return k, s, e
+
+
+def cat(*sides):
+    return tuple(np.concatenate([x[i] for x in sides]) for i in range(3))
+
+
+def lattice(n, key=KEY):
+    j = np.arange(n, dtype=np.int64)
+    return cols(key, 100 * j + 10, 100 * j + 60)
+
+
+def on_runs(q, key=KEY):
+    q = np.asarray(q, np.int64)
+    return cols(key, 100 * q + 20, 100 * q + 30)
+
+
+def in_gaps(q, key=KEY):
+    q = np.asarray(q, np.int64)
+    return cols(key, 100 * q + 70, 100 * q + 90)
+
+
+def sort_rows(side):
+    o = np.lexsort((side[2], side[1], side[0]))
+    return tuple(x[o] for x in side)
+
+
+def is_sorted(side):
+    o = np.lexsort((np.arange(len(side[0])), side[2], side[1], side[0]))
+    return (o == np.arange(len(o))).all()
+
+
+def model(left, right, strict, geo):
+    """words 0..4 of every workgroup for SORTED lefts, from the window rule of k_isect_count"""
+    runs = io.merged_runs(right, strict)
+    keys = [(k, me) for k in sorted(runs) for _, me in runs[k]]
+    m = len(keys)
+    rank = lambda i: (bisect.bisect_right if strict else bisect.bisect_left)(keys, (int(left[0][i]), int(left[1][i])))
+    nl, st = len(left[0]), geo["rows_per_wg"]
+    nwg = (nl + 1 + st - 1) // st
+    brk = [rank(min(b * st, nl - 1)) for b in range(nwg + 1)]
+    out = np.zeros((nwg, 5), np.uint32)
+    for b in range(nwg):
+        if b * st >= nl:
+            continue
+        lo, hi = brk[b], brk[b + 1]
+        w0 = lo - 1 if lo > 0 else 0
+        w1 = hi + geo["margin"] if m - hi > geo["margin"] else m
+        out[b] = [lo, hi, w0, w1 - w0, int(w1 - w0 <= geo["staged_runs"])]
+    return out
+
+
+def same(got, want, what=None):
+    for g, w in zip(got, want):
+        assert len(g) == len(w), (what, len(g), len(w))
+        assert g.dtype == w.dtype and (g == w).all(), what
+
+
+def run_case(ctx, geo, left, right, n_keys=3, expect=None, total=None):
+    assert is_sorted(left)
+    rng = np.random.default_rng(len(left[0]))
+    for strict in (False, True):
+        want = io.walk(left, right, strict)
+        if total is not None:
+            assert len(want[0]) == total, (len(want[0]), total)
+        same(ctx.intersect(*left, *right, n_keys=n_keys, strict=strict), want, strict)
+        wg, esc, n_out = ctx.intersect_paths(*left, *right, n_keys=n_keys, strict=strict)
+        assert n_out == len(want[0]) and len(esc) == len(left[0]) and ((esc == 0) | (esc == 1)).all()
+        want_wg = model(left, right, strict, geo)
+        assert wg.shape[0] == want_wg.shape[0] and (wg[:, :5] == want_wg).all(), (strict, wg, want_wg)
+        assert (wg[:, W_ESC] == [int(esc[b * 256:(b + 1) * 256].sum()) for b in range(len(wg))]).all()
+        if expect is not None:
+            expect(wg, esc, strict)
+        # the same rows shuffled: the same pieces, with the shuffled rows' numbers
+        p = rng.permutation(len(left[0]))
+        shuf = tuple(x[p] for x in left)
+        k, s, e, r = io.walk(shuf, right, strict)
+        same(ctx.intersect(*shuf, *right, n_keys=n_keys, strict=strict), (k, s, e, r), ("shuffled", strict))
+    return want
+
+
+# ------------------------------------------------------------------ the window
+
+def test_lds_path_without_escape(ctx, geo):
+    """one workgroup whose rows touch 256 runs: staged, nobody leaves the stretch"""
+    def expect(wg, esc, strict):
+        assert list(wg[0]) == [0, 255, 0, 255 + geo["margin"], 1, 0] and not esc.any()
+    run_case(ctx, geo, on_runs(np.arange(256)), lattice(400), expect=expect, total=256)
+
+
+def test_a_stretch_that_does_not_fit_goes_to_global_memory(ctx, geo):
+    """256 short rows spread over more runs than a workgroup stages: no LDS, and nothing counts as escaped"""
+    step = geo["staged_runs"] // 255 + 1
+    m = 255 * step + 100
+    def expect(wg, esc, strict):
+        assert wg[0, W_RUNS] > geo["staged_runs"] and wg[0, W_LDS] == 0 and wg[0, W_ESC] == 0 and not esc.any()
+    run_case(ctx, geo, on_runs(np.arange(256) * step), lattice(m), expect=expect, total=256)
+
+
+def test_the_stretch_that_just_fits_and_the_first_that_does_not(ctx, geo):
+    """the window is brk_hi + margin - (brk_lo - 1) runs: exactly `staged_runs` is staged, one more is not"""
+    for extra, lds in ((0, 1), (1, 0)):
+        hi = geo["staged_runs"] - geo["margin"] + extra                     # first row on run 1 (the window starts at run 0), last row on run hi
+        q = np.concatenate([[1], np.sort(np.random.default_rng(3).choice(np.arange(2, hi), 254, replace=False)), [hi]])
+        def expect(wg, esc, strict):
+            assert wg[0, W_RUNS] == geo["staged_runs"] + extra and wg[0, W_LDS] == lds and not esc.any()
+        run_case(ctx, geo, on_runs(q), lattice(hi + 200), expect=expect, total=256)
+
+
+def test_one_long_row_escapes_and_leaves_the_others_on_lds(ctx, geo):
+    short = on_runs(np.arange(255))
+    long_ = cols(KEY, [100 * 100 + 20], [100 * 400 + 30])                 # runs 100 .. 400: far past the stretch's end
+    left = sort_rows(cat(short, long_))
+    at = int(np.flatnonzero(left[2] == 100 * 400 + 30)[0])
+    def expect(wg, esc, strict):
+        assert wg[0, W_LDS] == 1 and wg[0, W_ESC] == 1 and esc[at] == 1 and esc.sum() == 1
+    run_case(ctx, geo, left, lattice(600), expect=expect, total=255 + 301)
+
+
+def test_a_row_whose_range_ends_inside_the_stretch_does_not_escape(ctx, geo):
+    """the last row covers 40 runs from the bracket's high end on: inside the margin of 48, though the gallop's strides
+    (1, 2, 4, .. 32) would step past it -- the second search is bounded by the stretch's end, so the row stays on LDS; a row
+    whose search reaches that end (`margin` runs or more here) cannot know what lies beyond and escapes"""
+    for runs, escapes in ((40, 0), (geo["margin"] - 1, 0), (geo["margin"], 1)):
+        last = cols(KEY, [100 * 254 + 20], [100 * (254 + runs - 1) + 30])
+        left = sort_rows(cat(on_runs(np.arange(255)), last))
+        def expect(wg, esc, strict):
+            assert wg[0, W_LDS] == 1 and wg[0, B_HI] == 254 and wg[0, W_ESC] == escapes and esc.sum() == escapes
+        run_case(ctx, geo, left, lattice(600), expect=expect, total=255 + runs)
+
+
+# ------------------------------------------------------------------ the fill pass
+
+def test_one_row_with_more_pieces_than_a_workgroup_has_threads(ctx, geo):
+    """a row over 1 000 runs in the first of two workgroups: its pieces take four rounds of the fill workgroup's threads and
+    end far behind the next workgroup's base offset in rows, which starts right after them"""
+    short = on_runs(np.arange(400))
+    long_ = cols(KEY, [100 * 50 + 20], [100 * 1049 + 30])
+    left = sort_rows(cat(short, long_))
+    run_case(ctx, geo, left, lattice(1200), total=400 + 1000)
+
+
+def test_rows_without_pieces_at_a_workgroups_first_and_last_position(ctx, geo):
+    q = np.arange(512)
+    left = list(on_runs(q))
+    for at in (0, 255, 256, 511):
+        left[1][at] += 50; left[2][at] += 60                               # into the gap behind its run
+    left = tuple(left)
+    want = run_case(ctx, geo, left, lattice(600), total=508)
+    assert not set(want[3].tolist()) & {0, 255, 256, 511}
+
+
+def test_only_rows_without_pieces(ctx, geo):
+    run_case(ctx, geo, in_gaps(np.arange(300)), lattice(400), total=0)
+
+
+# ------------------------------------------------------------------ key boundaries
+
+@pytest.mark.parametrize("per_key", [128, 256])
+@pytest.mark.parametrize("runs_on", ["both", "first", "second"])
+def test_a_bracket_on_a_key_boundary(ctx, geo, per_key, runs_on):
+    """the last rows of key 0 and the first rows of key 1 share a workgroup (128 each), or key 1 starts a workgroup of its own
+    (256 each): the bracket of that place is the first run of key 1 -- or, with runs on one key only, the end of all runs"""
+    left = cat(on_runs(np.arange(per_key), key=0), on_runs(np.arange(per_key), key=1))
+    right = {"both": cat(lattice(300, 0), lattice(300, 1)), "first": lattice(300, 0), "second": lattice(300, 1)}[runs_on]
+    def expect(wg, esc, strict):
+        assert wg[:len(left[0]) // 256, W_LDS].all() and not esc.any()
+        if per_key == 256:
+            assert wg[1, B_LO] == {"both": 300, "first": 300, "second": 0}[runs_on]
+    run_case(ctx, geo, left, right, expect=expect, total=per_key * (2 if runs_on == "both" else 1))
+
+
+# ------------------------------------------------------------------ the hook itself, and the plans of other calls
+
+def test_hook_reports_sizes_and_refuses_short_buffers(ctx, geo):
+    import ctypes as C
+    left, right = on_runs(np.arange(300)), lattice(400)
+    L = pyivx.lib()
+    p = lambda a: a.ctypes.data_as(C.c_void_p)
+    n_wg, n_rows, n_out = C.c_uint64(9), C.c_uint64(9), C.c_uint64(9)
+    args = (ctx.h, C.c_int(pyivx.MEM_HOST), p(left[0]), p(left[1]), p(left[2]), C.c_uint64(300), p(right[0]), p(right[1]), p(right[2]),
+            C.c_uint64(400), C.c_uint32(3), C.c_int(0))
+    st = L.ivx_debug_intersect_paths(*args, None, C.c_uint64(0), None, C.c_uint64(0), C.byref(n_wg), C.byref(n_rows), C.byref(n_out))
+    assert st == pyivx.ERR_CAPACITY and (n_wg.value, n_rows.value) == (2, 300)
+    st = L.ivx_debug_intersect_paths(*args[:9], C.c_uint64(0), *args[10:], None, C.c_uint64(0), None, C.c_uint64(0),
+                                     C.byref(n_wg), C.byref(n_rows), C.byref(n_out))
+    assert st == pyivx.OK and (n_wg.value, n_rows.value, n_out.value) == (0, 0, 0)         # an empty side: nothing to report
+
+
+def test_an_intersect_call_drops_a_subtract_plan(ctx):
+    """after a subtract sizing call an intersect call in between: the subtract fill does all its work itself, and is right"""
+    left, right = io.random_sides(np.random.default_rng(5), 700, 600, 3, span=4000)
+    want = orc.subtract(*left, *right, strict=False)
+    seen = []
+    def between():
+        assert ctx.debug_state()["sub_valid"] == 1
+        seen.append(ctx.intersect(*left, *right, n_keys=3))
+        assert ctx.debug_state()["sub_valid"] == 0
+    before = ctx.debug_state()["sub_fills_planned"]
+    got = ctx.subtract(*left, *right, n_keys=3, between=between)
+    same(got, want)
+    assert ctx.debug_state()["sub_fills_planned"] == before                # no plan served that fill
+    same(seen[0], io.walk(left, right, False))
+    # ... and without the call in between the plan does serve it (the check above is not vacuous)
+    same(ctx.subtract(*left, *right, n_keys=3), want)
+    assert ctx.debug_state()["sub_fills_planned"] == before + 1
