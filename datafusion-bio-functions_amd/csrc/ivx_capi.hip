@@ -172,7 +172,15 @@ ivx_status index_commit(ivx_ctx *ctx, ivx_index *ix, ivx_status st, const char *
 {
     if (st == IVX_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) st = ctx->fail(IVX_ERR_HIP, what);
     ctx->building_bytes = 0;
-    if (st != IVX_OK) { ivx_index_free(ix); return st; }
+    if (st != IVX_OK) {
+        // a build that was refused half-way has queued kernels that write the buffers it did get, and ivx_index_free hands
+        // those to the pool every context of the process draws from: another context's build could take them on its own
+        // stream while they are still being written.  Wait for this context's streams first -- on this path only
+        (void)hipStreamSynchronize(ctx->stream);
+        if (ctx->aux) (void)hipStreamSynchronize(ctx->aux);
+        ivx_index_free(ix);
+        return st;
+    }
     if (ix->kind == IVX_KIND_DEPTH_PROFILE) ix->n = ix->dp.steps;
     // the finished index stays reserved against the context's limit until ivx_index_free (the reference holds the
     // build side's MemoryReservation until the join stream ends, interval_join.rs:614-639)
@@ -535,6 +543,7 @@ static ivx_status overlap_common(ivx_ctx *ctx, const ivx_index *ix, int mem, int
 {
     Frame f(ctx, mem);
     IVX_TRY(check_probe_args(f, ix, IVX_KIND_OVERLAP, start, end, n, true));
+    if (total) *total = 0;                                  // (as Frame::begin(scalar): a refused call leaves 0, not the caller's word)
     f.meter(false, n);
     // large COUNT/FILL batches: partition the probe rows by index region and probe from LDS;
     // small batches and the per-row modes gather straight from the index
@@ -756,6 +765,7 @@ static ivx_status overlap_fill_host_chunked(ivx_ctx *ctx, const ivx_index *ix, c
 {
     Frame f(ctx, IVX_MEM_HOST);
     IVX_TRY(check_probe_args(f, ix, IVX_KIND_OVERLAP, start, end, n));
+    if (written) *written = 0;
     u32 *d_b, *d_p;
     IVX_TRY(ctx->get_scratch(WS_OUT_C, (size_t)(cap ? cap : 1) * sizeof(u32), (void **)&d_b));
     IVX_TRY(ctx->get_scratch(WS_OUT_D, (size_t)(cap ? cap : 1) * sizeof(u32), (void **)&d_p));
@@ -867,7 +877,6 @@ extern "C" ivx_status ivx_probe_overlap_agg(ivx_ctx *ctx, const ivx_index *ix, i
     if (val_bytes != 4 && val_bytes != 8) return ctx->fail(IVX_ERR_INVALID, "overlap_agg: val_bytes is 4 or 8");
     if (ix->n && !val) return ctx->fail(IVX_ERR_INVALID, "overlap_agg: null value column");
     f.meter(false, n);
-    f.rows_out(n);
     f.drop_join_plan();                                     // as any other call between a count call and its fill
     if (n == 0) return IVX_OK;
     // the override of ivx_probe_mark_build, thresholds of its own
@@ -889,6 +898,7 @@ extern "C" ivx_status ivx_probe_overlap_agg(ivx_ctx *ctx, const ivx_index *ix, i
         if (regions) IVX_TRY(ivx_agg_probe_regions(ctx, ix->jv, ix->jv_nreg, dk, ds, de, n, dv, val_bytes, o, ix->jv_filter, ix->jv_pk24, ix->jv_lean.load(std::memory_order_relaxed) == 1, &took));
         return took ? IVX_OK : ivx_agg_probe(ctx, ix->jv, dk, ds, de, n, dv, val_bytes, o);
     }));
+    f.rows_out(n);                                          // (as ivx_probe_count: not on a refused call)
     f.back_all();
     return f.finish();
 }
@@ -935,7 +945,6 @@ static ivx_status per_row_i64(ivx_ctx *ctx, const ivx_index *ix, int kind, int m
     IVX_TRY(check_probe_args(f, ix, kind, start, end, n));
     if (n && !out) return ctx->fail(IVX_ERR_INVALID, "null output column");
     f.meter(false, n);
-    f.rows_out(n);
     const auto probe = [&](const u32 *dk, const i32 *ds, const i32 *de, u64 rows, i64 *dout) {
         return kind == IVX_KIND_COUNT ? ivx_count_probe(ctx, ix, dk, ds, de, rows, strict, dout) : ivx_coverage_probe(ctx, ix, dk, ds, de, rows, strict, dout);
     };
@@ -946,17 +955,20 @@ static ivx_status per_row_i64(ivx_ctx *ctx, const ivx_index *ix, int kind, int m
         i64 *doo[2];
         IVX_TRY(ctx->get_scratch(WS_OUT_A, rows * sizeof(i64), (void **)&doo[0]));
         IVX_TRY(ctx->get_scratch(WS_OUT_B, rows * sizeof(i64), (void **)&doo[1]));
-        return host_chunked(ctx, key, start, end, n, nchunk, true, "hipMemcpyAsync(values)", [&](HostChunk &ch) -> ivx_status {
+        IVX_TRY(host_chunked(ctx, key, start, end, n, nchunk, true, "hipMemcpyAsync(values)", [&](HostChunk &ch) -> ivx_status {
             KernelTimer t(ctx);
             IVX_TRY(probe(ch.key, ch.start, ch.end, ch.n, doo[ch.set]));
             ch.push(out + ch.c0, doo[ch.set], ch.n * sizeof(i64));
             return IVX_OK;
-        });
+        }));
+        f.rows_out(n);
+        return IVX_OK;
     }
     const u32 *dk = f.in(key, n);
     const i32 *ds = f.in(start, n), *de = f.in(end, n);
     i64 *dout = f.out(out, n);
     IVX_TRY(f.run([&] { return probe(dk, ds, de, n, dout); }));
+    f.rows_out(n);                                          // (an output batch only once it exists: a refused call has none)
     f.back_all();
     return f.finish();
 }
@@ -980,6 +992,7 @@ extern "C" ivx_status ivx_probe_nearest(ivx_ctx *ctx, const ivx_index *ix, int m
     Frame f(ctx, mem);
     IVX_TRY(check_probe_args(f, ix, IVX_KIND_NEAREST, start, end, n));
     if (!rows) return ctx->fail(IVX_ERR_INVALID, "null rows");
+    *rows = 0;                                              // (a refused call leaves 0, not the caller's word)
     if (n && (!build_idx || !probe_idx)) return ctx->fail(IVX_ERR_INVALID, "null output column");
     if ((u64)k * n > 0xFFFFFFFFFFull) return ctx->fail(IVX_ERR_INVALID, "nearest: k * rows too large");
     f.meter(false, n);

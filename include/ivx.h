@@ -125,8 +125,10 @@ void       ivx_ctx_reset_metrics(ivx_ctx *ctx);
  * index it has built that is still alive -- an index stays reserved against the limit of the context that built it until
  * ivx_index_free, as the reference holds the build side's MemoryReservation until the join stream ends
  * (interval_join.rs:614-639; try_grow fails with ResourcesExhausted).  A call that would go over the limit returns
- * IVX_ERR_OOM and allocates nothing.  Not counted: the caller's own buffers, and freed indexes' buffers waiting in the
- * library's recycling pool (ivx_ctx_trim returns those to the device). */
+ * IVX_ERR_OOM and allocates nothing: its out-handle is NULL, its scalar result 0 (or the true count), a host-mode
+ * caller's output buffers are untouched, no output batch is counted, and the same call under a higher limit gives the
+ * full answer ("What a refused reservation leaves behind").  Not counted: the caller's own buffers, and
+ * freed indexes' buffers waiting in the library's recycling pool (ivx_ctx_trim returns those to the device). */
 ivx_status ivx_ctx_set_memory_limit(ivx_ctx *ctx, uint64_t bytes);
 /* What counts against that limit right now (MemoryReservation::size): scratch + the live indexes this context built. */
 uint64_t   ivx_ctx_reserved_bytes(const ivx_ctx *ctx);

@@ -1,6 +1,6 @@
 """The catalogue of the C entry layer (csrc/ivx_capi.hip), shared by the tests that walk every entry: CASES maps an entry's name
 to f(E, M, n) -> dict of all its outputs, the scalar ones included, on a small seeded input of n rows -- E an Env (one context,
-one index of every kind, one depth profile), M a Mode (host arrays or device tensors).  The entries are called through
+one index of every kind, two depth profiles), M a Mode (host arrays or device tensors).  The entries are called through
 pyivx.lib() with ctypes directly: pyivx's wrappers would allocate, retry or reject first.  Importing this needs no GPU."""
 import ctypes as C
 import os
@@ -14,7 +14,7 @@ sys.path.insert(0, os.path.join(ROOT, "datafusion-bio-functions_amd"))
 import pyivx  # noqa: E402
 import cigar_text_oracle as cto  # noqa: E402
 
-OK, INVALID, CAPACITY, UNSUPPORTED = pyivx.OK, pyivx.ERR_INVALID, pyivx.ERR_CAPACITY, pyivx.ERR_UNSUPPORTED
+OK, INVALID, CAPACITY, UNSUPPORTED, OOM = pyivx.OK, pyivx.ERR_INVALID, pyivx.ERR_CAPACITY, pyivx.ERR_UNSUPPORTED, pyivx.ERR_OOM
 NULL = pyivx.NULL_IDX
 NK = 3                      # keys
 SIZES = [1000, 0, 1]
@@ -89,9 +89,25 @@ def reads(n, seed):
                 sw=rng.integers(-2, 4, ns).astype(np.int32))
 
 
+class Refused(Exception):
+    """Env.call met IVX_ERR_OOM while Env.stop_on_oom was set: the case ends at its first refused call"""
+
+
+class Call:
+    """one line of Env.log: the entry, its status and error text (a case makes several calls, and later ones overwrite
+    ivx_last_error), the context's metrics right before and after it, and what the caller registered of its outputs -- the
+    output Bufs ((Buf, array) for a buffer the entry ORs into: what it held before), the scalar count's value after the call,
+    the out-handle's value after the call"""
+
+    def __init__(self, entry, st, text, before, after, outs, count, handle):
+        self.entry, self.st, self.text, self.before, self.after, self.outs = entry, st, text, before, after, tuple(outs)
+        self.count = None if count is None else count.value
+        self.has_handle, self.handle = handle is not None, None if handle is None else handle.value
+
+
 class Env:
-    """one context, one index of every kind (from build_cols, by default 1 000 seeded rows) and one depth profile, built once
-    from host columns"""
+    """one context, one index of every kind (from build_cols, by default 1 000 seeded rows) and two depth profiles, built
+    once from host columns"""
 
     def __init__(self, build_cols=None):
         import torch
@@ -105,11 +121,21 @@ class Env:
         r = reads(1000, 7)
         self.profile = self.ctx.depth_profile(r["rkey"], r["rpos"], r["rflags"], r["rmapq"], r["off"], r["ops"],
                                               r["skey"], r["ss"], r["se"], r["sw"], n_keys=NK)
+        r = reads(64, 9)
+        self.profile2 = self.ctx.depth_profile(r["rkey"], r["rpos"], r["rflags"], r["rmapq"], r["off"], r["ops"],
+                                               r["skey"], r["ss"], r["se"], r["sw"], n_keys=NK)
+        self.log = []                   # a Call per call() since the caller last emptied it
+        self.stop_on_oom = False
 
-    def call(self, name, *args):
-        """the entry's status; the context's stream drained, so that device-mode outputs can be read"""
+    def call(self, name, *args, outs=(), count=None, handle=None):
+        """the entry's status; the context's stream drained, so that device-mode outputs can be read.  The call goes into
+        the log with the outputs the caller names; with stop_on_oom set, IVX_ERR_OOM raises Refused"""
+        before = self.ctx.metrics()
         st = getattr(self.L, name)(self.h, *args)
+        self.log.append(Call(name, st, self.err() if st != OK else "", before, self.ctx.metrics(), outs, count, handle))
         assert self.L.ivx_ctx_synchronize(self.h) == OK
+        if st == OOM and self.stop_on_oom:
+            raise Refused(name)
         return st
 
     def err(self):
@@ -117,6 +143,7 @@ class Env:
 
     def close(self):
         self.profile.free()
+        self.profile2.free()
         for ix in self.ix:
             ix.free()
         self.ctx.close()
@@ -154,21 +181,23 @@ def index_build(E, M, n):
     k, s, e = (M.put(a) for a in ivals(n, 3))
     pk, ps, pe = ivals(200, 4)
     for kind in range(4):
-        h = C.c_void_p()
-        st = E.call("ivx_index_build", cint(kind), M.mem, k.p, s.p, e.p, u64(n), u32(NK), C.byref(h))
+        h = C.c_void_p(0xDEAD)
+        st = E.call("ivx_index_build", cint(kind), M.mem, k.p, s.p, e.p, u64(n), u32(NK), C.byref(h), handle=h)
         assert st == OK, E.err()
         ix = pyivx.Index(E.ctx, h, kind)
-        res[f"{kind}.rows"], res[f"{kind}.bytes"] = ix.rows, ix.device_bytes
-        if n:
-            if kind == pyivx.KIND_OVERLAP:
-                res["0.total"], res["0.per_row"] = E.ctx.overlap_count(ix, pk, ps, pe, per_row=True)
-            elif kind == pyivx.KIND_COUNT:
-                res["1.count"] = E.ctx.count_overlaps(ix, pk, ps, pe)
-            elif kind == pyivx.KIND_COVERAGE:
-                res["2.coverage"] = E.ctx.coverage(ix, pk, ps, pe)
-            else:
-                res["3.b"], res["3.p"], res["3.d"] = E.ctx.nearest(ix, pk, ps, pe, k=2)
-        ix.free()
+        try:                                                    # (a refused probe must not leave the index alive)
+            res[f"{kind}.rows"], res[f"{kind}.bytes"] = ix.rows, ix.device_bytes
+            if n:
+                if kind == pyivx.KIND_OVERLAP:
+                    res["0.total"], res["0.per_row"] = E.ctx.overlap_count(ix, pk, ps, pe, per_row=True)
+                elif kind == pyivx.KIND_COUNT:
+                    res["1.count"] = E.ctx.count_overlaps(ix, pk, ps, pe)
+                elif kind == pyivx.KIND_COVERAGE:
+                    res["2.coverage"] = E.ctx.coverage(ix, pk, ps, pe)
+                else:
+                    res["3.b"], res["3.p"], res["3.d"] = E.ctx.nearest(ix, pk, ps, pe, k=2)
+        finally:
+            ix.free()
     return res
 
 
@@ -177,11 +206,11 @@ def probe_overlap_count(E, M, n):
     k, s, e = (M.put(a) for a in ivals(n, 5))
     res = {}
     tot = u64(0xDEAD)
-    res["st"] = E.call("ivx_probe_overlap_count", E.ix[0].h, M.mem, k.p, s.p, e.p, u64(n), None, C.byref(tot))
+    res["st"] = E.call("ivx_probe_overlap_count", E.ix[0].h, M.mem, k.p, s.p, e.p, u64(n), None, C.byref(tot), count=tot)
     res["total"] = tot.value
     pr = M.out(n, np.uint32)
     tot2 = u64(0xDEAD)
-    res["st2"] = E.call("ivx_probe_overlap_count", E.ix[0].h, M.mem, k.p, s.p, e.p, u64(n), pr.p, C.byref(tot2))
+    res["st2"] = E.call("ivx_probe_overlap_count", E.ix[0].h, M.mem, k.p, s.p, e.p, u64(n), pr.p, C.byref(tot2), outs=[pr], count=tot2)
     res["total2"], res["per_row"] = tot2.value, pr.np()[:n]
     return res
 
@@ -194,10 +223,10 @@ def probe_overlap_fill(E, M, n):
     def call(cap, bufs):
         w = u64(0xDEAD)
         if not bufs:        # (the sizing call of a fill is the count call)
-            st = E.call("ivx_probe_overlap_count", E.ix[0].h, M.mem, k.p, s.p, e.p, u64(n), None, C.byref(w))
+            st = E.call("ivx_probe_overlap_count", E.ix[0].h, M.mem, k.p, s.p, e.p, u64(n), None, C.byref(w), count=w)
             return st, w.value, []
         b, p = M.out(cap, np.uint32), M.out(cap, np.uint32)
-        st = E.call("ivx_probe_overlap_fill", E.ix[0].h, M.mem, k.p, s.p, e.p, u64(n), b.p, p.p, u64(cap), C.byref(w))
+        st = E.call("ivx_probe_overlap_fill", E.ix[0].h, M.mem, k.p, s.p, e.p, u64(n), b.p, p.p, u64(cap), C.byref(w), outs=[b, p], count=w)
         m = min(w.value, cap)
         pairs = np.sort((b.np()[:m].astype(np.uint64) << np.uint64(32)) | p.np()[:m].astype(np.uint64))   # (the order of the pairs is free)
         return st, w.value, [Buf(pairs, False)]
@@ -209,7 +238,7 @@ def probe_overlap_fill(E, M, n):
 def probe_exists(E, M, n):
     k, s, e = (M.put(a) for a in ivals(n, 6))
     out = M.out(n, np.uint8)
-    st = E.call("ivx_probe_exists", E.ix[0].h, M.mem, k.p, s.p, e.p, u64(n), out.p)
+    st = E.call("ivx_probe_exists", E.ix[0].h, M.mem, k.p, s.p, e.p, u64(n), out.p, outs=[out])
     return {"st": st, "exists": out.np()[:n]}
 
 
@@ -220,10 +249,25 @@ def probe_mark_build(E, M, n):
     mine = np.zeros(nw, np.uint32)
     mine[::3] = 0x00010001                                  # bits the caller had set: they survive
     marks = M.put(mine)
-    st = E.call("ivx_probe_mark_build", E.ix[0].h, M.mem, k.p, s.p, e.p, u64(n), marks.p)
+    st = E.call("ivx_probe_mark_build", E.ix[0].h, M.mem, k.p, s.p, e.p, u64(n), marks.p, outs=[(marks, mine)])
     got = marks.np()
     assert ((got & mine) == mine).all()
     return {"st": st, "marks": got}
+
+
+AGG_DTS = (np.uint32,) + (np.int64,) * 5                       # count, sum, vmin, vmax, bases, wsum
+
+
+@case
+def probe_overlap_agg(E, M, n):
+    """all six outputs, an int64 value per build row"""
+    k, s, e = (M.put(a) for a in ivals(n, 29, span=4000))
+    val = M.put(np.random.default_rng(30).integers(-(1 << 40), 1 << 40, E.n_build).astype(np.int64))
+    outs = [M.out(n, dt) for dt in AGG_DTS]
+    st = E.call("ivx_probe_overlap_agg", E.ix[0].h, M.mem, k.p, s.p, e.p, u64(n), val.p, u32(8), *[o.p for o in outs], outs=outs)
+    res = {"st": st}
+    res.update({name: o.np()[:n] for name, o in zip(pyivx.AGG_OUTPUTS, outs)})
+    return res
 
 
 @case
@@ -234,7 +278,7 @@ def bits_mark(E, M, n):
     mine = np.zeros((5000 + 31) // 32, np.uint32)
     mine[::5] = 0x80000001
     d_idx, bits = M.put(idx), M.put(mine)
-    st = E.call("ivx_bits_mark", M.mem, d_idx.p, u64(n), bits.p, u64(5000))
+    st = E.call("ivx_bits_mark", M.mem, d_idx.p, u64(n), bits.p, u64(5000), outs=[(bits, mine)])
     got = bits.np()
     assert ((got & mine) == mine).all()
     return {"st": st, "bits": got}
@@ -249,7 +293,8 @@ def bits_select(E, M, n):
         def call(cap, bufs):
             m = u64(0xDEAD)
             out = M.out(cap, np.uint32)
-            st = E.call("ivx_bits_select", M.mem, bits.p, u64(n), cint(want), out.p if bufs else None, u64(cap), C.byref(m))
+            st = E.call("ivx_bits_select", M.mem, bits.p, u64(n), cint(want), out.p if bufs else None, u64(cap), C.byref(m),
+                        outs=[out], count=m)
             return st, m.value, [out]
         sized(res, f"select{want}", call)
     return res
@@ -261,7 +306,7 @@ def _per_row(entry, kind):
         res = {}
         for strict in (0, 1):
             out = M.out(n, np.int64)
-            res[f"st{strict}"] = E.call(entry, E.ix[kind].h, M.mem, k.p, s.p, e.p, u64(n), cint(strict), out.p)
+            res[f"st{strict}"] = E.call(entry, E.ix[kind].h, M.mem, k.p, s.p, e.p, u64(n), cint(strict), out.p, outs=[out])
             res[f"out{strict}"] = out.np()[:n]
         return res
     f.__name__ = entry[4:]
@@ -278,7 +323,8 @@ def probe_nearest(E, M, n):
     cap = 2 * n
     b, p, d = M.out(cap, np.uint32), M.out(cap, np.uint32), M.out(cap, np.int64)
     rows = u64(0xDEAD)
-    st = E.call("ivx_probe_nearest", E.ix[3].h, M.mem, k.p, s.p, e.p, u64(n), cint(0), u32(2), cint(1), b.p, p.p, d.p, u64(cap), C.byref(rows))
+    st = E.call("ivx_probe_nearest", E.ix[3].h, M.mem, k.p, s.p, e.p, u64(n), cint(0), u32(2), cint(1), b.p, p.p, d.p, u64(cap), C.byref(rows),
+                outs=[b, p, d], count=rows)
     r = rows.value
     return {"st": st, "rows": r, "b": b.np()[:r], "p": p.np()[:r], "d": d.np()[:r]}
 
@@ -288,7 +334,8 @@ def merge(E, M, n):
     k, s, e = (M.put(a) for a in ivals(n, 12, np.int64))
     outs = [M.out(n, dt) for dt in (np.uint32, np.int64, np.int64, np.int64)]
     m = u64(0xDEAD)
-    st = E.call("ivx_merge", M.mem, k.p, s.p, e.p, u64(n), u32(NK), i64(0), cint(0), *[o.p for o in outs], u64(n), C.byref(m))
+    st = E.call("ivx_merge", M.mem, k.p, s.p, e.p, u64(n), u32(NK), i64(0), cint(0), *[o.p for o in outs], u64(n), C.byref(m),
+                outs=outs, count=m)
     res = {"st": st, "n_out": m.value}
     res.update({f"o{i}": o.np()[:m.value] for i, o in enumerate(outs)})
     return res
@@ -305,9 +352,26 @@ def subtract(E, M, n):
         outs = [M.out(cap, dt) for dt in (np.uint32, np.int64, np.int64, np.uint32)]
         m = u64(0xDEAD)
         st = E.call("ivx_subtract", M.mem, lk.p, ls.p, le.p, u64(n), rk.p, rs.p, re.p, u64(nr), u32(NK), cint(0),
-                    *[o.p if bufs else None for o in outs], u64(cap), C.byref(m))
+                    *[o.p if bufs else None for o in outs], u64(cap), C.byref(m), outs=outs, count=m)
         return st, m.value, outs
     sized(res, "subtract", call)
+    return res
+
+
+@case
+def intersect(E, M, n):
+    lk, ls, le = (M.put(a) for a in ivals(n, 31, np.int64))
+    nr = n // 2 if n > 1 else n
+    rk, rs, re = (M.put(a) for a in ivals(nr, 32, np.int64))
+    res = {}
+
+    def call(cap, bufs):
+        outs = [M.out(cap, dt) for dt in (np.uint32, np.int64, np.int64, np.uint32)]
+        m = u64(0xDEAD)
+        st = E.call("ivx_intersect", M.mem, lk.p, ls.p, le.p, u64(n), rk.p, rs.p, re.p, u64(nr), u32(NK), cint(0),
+                    *[o.p if bufs else None for o in outs], u64(cap), C.byref(m), outs=outs, count=m)
+        return st, m.value, outs
+    sized(res, "intersect", call)
     return res
 
 
@@ -319,7 +383,8 @@ def cluster(E, M, n):
     outs = [M.out(n, dt) for dt in dts]
     kc = M.out(NK, np.uint64)
     m = u64(0xDEAD)
-    st = E.call("ivx_cluster", M.mem, k.p, s.p, e.p, u64(n), u32(NK), i64(5), cint(0), base.p, *[o.p for o in outs], kc.p, C.byref(m))
+    st = E.call("ivx_cluster", M.mem, k.p, s.p, e.p, u64(n), u32(NK), i64(5), cint(0), base.p, *[o.p for o in outs], kc.p, C.byref(m),
+                outs=outs + [kc], count=m)
     res = {"st": st, "n_clusters": m.value, "key_clusters": kc.np()[:NK]}
     res.update({f"o{i}": o.np()[:n] for i, o in enumerate(outs)})
     return res
@@ -336,7 +401,7 @@ def complement(E, M, n):
         outs = [M.out(cap, dt) for dt in (np.uint32, np.int64, np.int64)]
         m = u64(0xDEAD)
         st = E.call("ivx_complement", M.mem, k.p, s.p, e.p, u64(n), vk.p, vs.p, ve.p, u64(nv), u32(NK), cint(0),
-                    *[o.p if bufs else None for o in outs], u64(cap), C.byref(m))
+                    *[o.p if bufs else None for o in outs], u64(cap), C.byref(m), outs=outs, count=m)
         return st, m.value, outs
     sized(res, "complement", call)
     return res
@@ -366,7 +431,7 @@ def _depth(entry, text):
         def call(cap, bufs):
             outs = [M.out(cap, dt) for dt in (np.uint32, np.uint32, np.uint32, np.int32)]
             m = u64(0xDEAD)
-            st = E.call(entry, *args, *[o.p if bufs else None for o in outs], cap, C.byref(m))
+            st = E.call(entry, *args, *[o.p if bufs else None for o in outs], cap, C.byref(m), outs=outs, count=m)
             return st, m.value, outs
         sized(res, entry, call)
         return res
@@ -381,13 +446,15 @@ _depth("ivx_depth_text", True)
 def _profile_build(entry, text):
     def f(E, M, n):
         args, keep = _depth_in(M, n, text, large=1 if text else 0)
-        h = C.c_void_p()
-        st = E.call(entry, *args, C.byref(h))
+        h = C.c_void_p(0xDEAD)
+        st = E.call(entry, *args, C.byref(h), handle=h)
         assert st == OK, E.err()
         p = pyivx.DepthProfile(E.ctx, h, NK, None)
-        key, pos, cov, seen = p.read()
-        res = {"steps": p.steps(), "bytes": p.device_bytes, "key": key, "pos": pos, "cov": cov, "seen": seen}
-        p.free()
+        try:
+            key, pos, cov, seen = p.read()
+            res = {"steps": p.steps(), "bytes": p.device_bytes, "key": key, "pos": pos, "cov": cov, "seen": seen}
+        finally:
+            p.free()
         return res
     f.__name__ = entry[4:]
     return case(f)
@@ -408,7 +475,8 @@ def cigar_parse(E, M, n):
         def call(cap, bufs):
             off, ops = M.out(n + 1, np.int32), M.out(cap, np.uint32)
             m = u64(0xDEAD)
-            st = E.call("ivx_cigar_parse", *head, off.p if bufs else None, ops.p if bufs else None, u64(cap), C.byref(m))
+            st = E.call("ivx_cigar_parse", *head, off.p if bufs else None, ops.p if bufs else None, u64(cap), C.byref(m),
+                        outs=[off, ops], count=m)
             if bufs and n:
                 res[f"{large}.off@{cap}"] = off.np()[:n + 1]       # (the offsets go out whether the ops fitted or not)
             return st, m.value, [ops]
@@ -424,7 +492,8 @@ def depth_profile_read(E, M, n):
         outs = [M.out(steps, dt) for dt in (np.uint32, np.uint32, np.int32)]
         seen = M.out(NK, np.uint8)
         m = u64(0xDEAD)
-        st = E.call("ivx_depth_profile_read", E.profile.h, M.mem, *[o.p for o in outs], seen.p, u64(cap), C.byref(m))
+        st = E.call("ivx_depth_profile_read", E.profile.h, M.mem, *[o.p for o in outs], seen.p, u64(cap), C.byref(m),
+                    outs=outs + [seen], count=m)
         assert st == (OK if cap == steps else CAPACITY)
         res[f"{cap}"] = (st, m.value)
         res[f"{cap}.seen"] = seen.np()[:NK]
@@ -435,7 +504,7 @@ def depth_profile_read(E, M, n):
 @case
 def depth_profile_expand(E, M, n):
     pos, cov = M.out(n, np.int32), M.out(n, np.int16)
-    st = E.call("ivx_depth_profile_expand", E.profile.h, M.mem, 1, 100, n, 0, pos.p, cov.p)
+    st = E.call("ivx_depth_profile_expand", E.profile.h, M.mem, 1, 100, n, 0, pos.p, cov.p, outs=[pos, cov])
     return {"st": st, "pos": pos.np()[:n], "cov": cov.np()[:n]}
 
 
@@ -446,7 +515,8 @@ def depth_profile_blocks(E, M, n):
     def call(cap, bufs):
         outs = [M.out(cap, dt) for dt in (np.uint32, np.uint32, np.uint32, np.int32)]
         m = u64(0xDEAD)
-        st = E.call("ivx_depth_profile_blocks", E.profile.h, M.mem, *[o.p if bufs else None for o in outs], u64(cap), C.byref(m))
+        st = E.call("ivx_depth_profile_blocks", E.profile.h, M.mem, *[o.p if bufs else None for o in outs], u64(cap), C.byref(m),
+                    outs=outs, count=m)
         return st, m.value, outs
     sized(res, "blocks", call)
     return res
@@ -464,7 +534,8 @@ def depth_profile_summarize(E, M, n):
     qk, qs, qe, hi = _regions(M, n)
     thr = np.array([1, 3, 10], np.int32)
     outs = [M.out(n, np.int64), M.out(n, np.int64), M.out(3 * n, np.int64)]
-    st = E.call("ivx_depth_profile_summarize", E.profile.h, M.mem, qk.p, qs.p, qe.p, n, 0, hi.p, 0, pyivx._ptr(thr), 3, *[o.p for o in outs])
+    st = E.call("ivx_depth_profile_summarize", E.profile.h, M.mem, qk.p, qs.p, qe.p, n, 0, hi.p, 0, pyivx._ptr(thr), 3, *[o.p for o in outs],
+                outs=outs)
     return {"st": st, "len": outs[0].np()[:n], "sum": outs[1].np()[:n], "ge": outs[2].np()[:3 * n]}
 
 
@@ -472,7 +543,8 @@ def depth_profile_summarize(E, M, n):
 def depth_profile_windows(E, M, n):
     thr = np.array([1, 3, 10], np.int32)
     outs = [M.out(n, np.int64), M.out(n, np.int64), M.out(3 * n, np.int64)]
-    st = E.call("ivx_depth_profile_windows", E.profile.h, M.mem, 2, 50, 50 + 7 * max(n, 1) - 4, 7, n, 1, pyivx._ptr(thr), 3, *[o.p for o in outs])
+    st = E.call("ivx_depth_profile_windows", E.profile.h, M.mem, 2, 50, 50 + 7 * max(n, 1) - 4, 7, n, 1, pyivx._ptr(thr), 3, *[o.p for o in outs],
+                outs=outs)
     return {"st": st, "len": outs[0].np()[:n], "sum": outs[1].np()[:n], "ge": outs[2].np()[:3 * n]}
 
 
@@ -481,7 +553,8 @@ def depth_profile_quantiles(E, M, n):
     qk, qs, qe, hi = _regions(M, n)
     qn = np.array([1, 3], np.uint32)
     outs = [M.out(n, np.int64), M.out(n, np.int32), M.out(n, np.int32), M.out(2 * n, np.int32)]
-    st = E.call("ivx_depth_profile_quantiles", E.profile.h, M.mem, qk.p, qs.p, qe.p, n, 0, hi.p, 0, pyivx._ptr(qn), 2, 4, *[o.p for o in outs])
+    st = E.call("ivx_depth_profile_quantiles", E.profile.h, M.mem, qk.p, qs.p, qe.p, n, 0, hi.p, 0, pyivx._ptr(qn), 2, 4, *[o.p for o in outs],
+                outs=outs)
     return {"st": st, "len": outs[0].np()[:n], "min": outs[1].np()[:n], "max": outs[2].np()[:n], "q": outs[3].np()[:2 * n]}
 
 
@@ -490,8 +563,64 @@ def depth_profile_window_quantiles(E, M, n):
     qn = np.array([1, 3], np.uint32)
     outs = [M.out(n, np.int64), M.out(n, np.int32), M.out(n, np.int32), M.out(2 * n, np.int32)]
     st = E.call("ivx_depth_profile_window_quantiles", E.profile.h, M.mem, 2, 50, 50 + 7 * max(n, 1) - 4, 7, n, 1, pyivx._ptr(qn), 2, 4,
-                *[o.p for o in outs])
+                *[o.p for o in outs], outs=outs)
     return {"st": st, "len": outs[0].np()[:n], "min": outs[1].np()[:n], "max": outs[2].np()[:n], "q": outs[3].np()[:2 * n]}
+
+
+@case
+def depth_profile_merge(E, M, n):
+    """E.profile + E.profile2 (one row: the other way round; the empty call: a profile with itself), the sum read back in
+    mode M and freed here"""
+    a, b = (E.profile, E.profile) if n == 0 else (E.profile2, E.profile) if n == 1 else (E.profile, E.profile2)
+    h = C.c_void_p(0xDEAD)
+    st = E.call("ivx_depth_profile_merge", a.h, b.h, C.byref(h), handle=h)
+    assert st == OK, E.err()
+    try:
+        steps = E.L.ivx_depth_profile_steps(h)
+        res = {"st": st, "steps": steps, "bytes": E.L.ivx_depth_profile_device_bytes(h)}
+        outs = [M.out(steps, dt) for dt in (np.uint32, np.uint32, np.int32)]
+        seen = M.out(NK, np.uint8)
+        m = u64(0xDEAD)
+        res["st2"] = E.call("ivx_depth_profile_read", h, M.mem, *[o.p for o in outs], seen.p, u64(steps), C.byref(m),
+                            outs=outs + [seen], count=m)
+        res["n_out"], res["seen"] = m.value, seen.np()[:NK]
+        res.update({f"o{i}": o.np()[:steps] for i, o in enumerate(outs)})
+    finally:
+        E.L.ivx_depth_profile_free(h)
+    return res
+
+
+def _classes_in(M, n):
+    """the domain arguments quantize and hist share: (pos_lo, key_hi, skip_pos0, seen_only), key_hi kept alive"""
+    hi = M.put(np.array([4000, 6000, 5200], np.uint32))
+    return (0, hi.p, 1, int(n & 1)), hi
+
+
+@case
+def depth_profile_quantize(E, M, n):
+    """min(n, 3) cuts; class 1 is never emitted (its runs still separate their neighbours)"""
+    cuts = np.array([1, 3, 10], np.int32)[:min(n, 3)]
+    emit = 0b1101 & ((1 << (len(cuts) + 1)) - 1)
+    dom, keep = _classes_in(M, n)
+    res = {}
+
+    def call(cap, bufs):
+        outs = [M.out(cap, np.uint32) for _ in range(4)]
+        m = u64(0xDEAD)
+        st = E.call("ivx_depth_profile_quantize", E.profile.h, M.mem, *dom, pyivx._ptr(cuts) if len(cuts) else None, len(cuts), emit,
+                    *[o.p if bufs else None for o in outs], u64(cap), C.byref(m), outs=outs, count=m)
+        return st, m.value, outs
+    sized(res, "quantize", call)
+    return res
+
+
+@case
+def depth_profile_hist(E, M, n):
+    n_bins = max(1, min(n, 16))
+    dom, keep = _classes_in(M, n)
+    out = M.out(NK * n_bins, np.int64)
+    st = E.call("ivx_depth_profile_hist", E.profile.h, M.mem, *dom, 1, n_bins, out.p, outs=[out])
+    return {"st": st, "hist": out.np()[:NK * n_bins]}
 
 
 N_SRC = 300
@@ -509,7 +638,7 @@ def take_fixed(E, M, n):
     idx, valid = _take_idx(n, 20)
     src, d_idx, svb = M.put(np.random.default_rng(21).integers(0, 1 << 62, N_SRC).astype(np.int64)), M.put(idx), M.put(valid)
     out, ov = M.out(n, np.int64), M.out(n, np.uint8)
-    st = E.call("ivx_take_fixed", M.mem, src.p, u32(8), u64(N_SRC), svb.p, d_idx.p, u64(n), out.p, ov.p)
+    st = E.call("ivx_take_fixed", M.mem, src.p, u32(8), u64(N_SRC), svb.p, d_idx.p, u64(n), out.p, ov.p, outs=[out, ov])
     return {"st": st, "out": out.np()[:n], "valid": ov.np()[:n]}
 
 
@@ -520,7 +649,7 @@ def scatter_fixed(E, M, n):
     idx = rng.permutation(n_out)[:n].astype(np.uint32)
     src, d_idx = M.put(rng.integers(0, 1 << 30, n).astype(np.int32)), M.put(idx)
     out = M.out(n_out, np.int32)
-    st = E.call("ivx_scatter_fixed", M.mem, src.p, u32(4), d_idx.p, u64(n), out.p, u64(n_out))
+    st = E.call("ivx_scatter_fixed", M.mem, src.p, u32(4), d_idx.p, u64(n), out.p, u64(n_out), outs=[out])
     got = out.np()
     rest = np.ones(n_out, bool)
     rest[idx] = False
@@ -546,7 +675,8 @@ def take_utf8(E, M, n):
         def call(cap, bufs):
             ooff, odata, ov = M.out(n + 1, off.dtype), M.out(cap, np.uint8), M.out(n, np.uint8)
             need = u64(0xDEAD)
-            st = E.call("ivx_take_utf8", *head, ooff.p, odata.p if bufs else None, u64(cap), C.byref(need), ov.p)
+            st = E.call("ivx_take_utf8", *head, ooff.p, odata.p if bufs else None, u64(cap), C.byref(need), ov.p,
+                        outs=[ooff, odata, ov], count=need)
             # a short data buffer (and the sizing call) still returns the offsets and the validity
             res[f"{large}.off@{cap},{bufs}"], res[f"{large}.valid@{cap},{bufs}"] = ooff.np()[:n + 1], ov.np()[:n]
             return st, need.value, [odata]
@@ -560,7 +690,7 @@ def take_bits(E, M, n):
     src = M.put(np.packbits(np.random.default_rng(26).random(N_SRC) < 0.5, bitorder="little"))
     d_idx, svb = M.put(idx), M.put(valid)
     out, ov = M.out((n + 7) // 8, np.uint8), M.out(n, np.uint8)
-    st = E.call("ivx_take_bits", M.mem, src.p, u64(N_SRC), svb.p, d_idx.p, u64(n), out.p, ov.p)
+    st = E.call("ivx_take_bits", M.mem, src.p, u64(N_SRC), svb.p, d_idx.p, u64(n), out.p, ov.p, outs=[out, ov])
     return {"st": st, "bits": out.np()[:(n + 7) // 8], "valid": ov.np()[:n]}
 
 
@@ -589,7 +719,8 @@ def take_view(E, M, n):
     def call(cap, with_data):
         ov16, odata, ov = M.out(16 * n, np.uint8), M.out(cap, np.uint8), M.out(n, np.uint8)
         need = u64(0xDEAD)
-        st = E.call("ivx_take_view", *head, ov16.p, odata.p if with_data else None, u64(cap), C.byref(need), ov.p)
+        st = E.call("ivx_take_view", *head, ov16.p, odata.p if with_data else None, u64(cap), C.byref(need), ov.p,
+                    outs=[ov16, odata, ov], count=need)
         if not with_data and need.value:
             assert untouched(ov16)                             # the views are withheld when the data did not fit
         res[f"views@{cap},{with_data}"] = ov16.np()[:16 * n]

@@ -63,6 +63,7 @@ class Args:
         self.src = H.put(np.arange(64, dtype=np.int64))
         self.bits = H.put(np.zeros(8, np.uint8))
         self.views = H.put(np.zeros(32 * 16, np.uint8))            # 32 empty strings
+        self.val = H.put(np.arange(E.n_build, dtype=np.int64))     # overlap_agg: one value per build row
         self.o = [H.out(64, np.int64) for _ in range(8)]       # outputs: enough bytes for any column of 8 rows
         self.count = u64(0)
         self.handle = C.c_void_p()
@@ -84,6 +85,7 @@ class Args:
             "ivx_probe_overlap_fill": [E.ix[0].h, H, *cols, o[0], o[1], u64(64), cnt],
             "ivx_probe_exists": [E.ix[0].h, H, *cols, o[0]],
             "ivx_probe_mark_build": [E.ix[0].h, H, *cols, o[0]],
+            "ivx_probe_overlap_agg": [E.ix[0].h, H, *cols, self.val.p, u32(8), *o[:6]],
             "ivx_bits_mark": [H, self.idx.p, u64(n), o[0], u64(64)],
             "ivx_bits_select": [H, self.bits.p, u64(64), cint(1), o[0], u64(64), cnt],
             "ivx_probe_count": [E.ix[1].h, H, *cols, cint(0), o[0]],
@@ -91,6 +93,7 @@ class Args:
             "ivx_probe_nearest": [E.ix[3].h, H, *cols, cint(0), u32(1), cint(1), o[0], o[1], o[2], u64(n), cnt],
             "ivx_merge": [H, *cols64, u32(NK), i64(0), cint(0), o[0], o[1], o[2], o[3], u64(n), cnt],
             "ivx_subtract": [H, *cols64, *cols64, u32(NK), cint(0), o[0], o[1], o[2], o[3], u64(64), cnt],
+            "ivx_intersect": [H, *cols64, *cols64, u32(NK), cint(0), o[0], o[1], o[2], o[3], u64(64), cnt],
             "ivx_cluster": [H, *cols64, u32(NK), i64(0), cint(0), None, *o[:7], o[7], cnt],
             "ivx_complement": [H, *cols64, None, None, None, u64(0), u32(NK), cint(0), o[0], o[1], o[2], u64(64), cnt],
             "ivx_depth": [H, *dcols, r["off"].p, r["ops"].p, *dseg, o[0], o[1], o[2], o[3], 64, cnt],
@@ -100,11 +103,14 @@ class Args:
             "ivx_cigar_parse": [H, 0, self.toff.p, self.ttext.p, n, o[0], o[1], 64, cnt],
             "ivx_depth_profile_read": [prof, H, None, None, None, o[3], 0, cnt],
             "ivx_depth_profile_expand": [prof, H, 0, 0, n, 0, o[0], o[1]],
+            "ivx_depth_profile_merge": [prof, E.profile2.h, C.byref(self.handle)],
             "ivx_depth_profile_blocks": [prof, H, None, None, None, None, 0, cnt],
             "ivx_depth_profile_summarize": [prof, H, *regions, self.thr.p, 2, o[0], o[1], o[2]],
             "ivx_depth_profile_windows": [prof, H, 0, 0, 100, 10, n, 0, self.thr.p, 2, o[0], o[1], o[2]],
             "ivx_depth_profile_quantiles": [prof, H, *regions, self.qn.p, 1, 2, o[0], o[1], o[2], o[3]],
             "ivx_depth_profile_window_quantiles": [prof, H, 0, 0, 100, 10, n, 0, self.qn.p, 1, 2, o[0], o[1], o[2], o[3]],
+            "ivx_depth_profile_quantize": [prof, H, 0, None, 0, 0, self.thr.p, 2, 7, None, None, None, None, 0, cnt],
+            "ivx_depth_profile_hist": [prof, H, 0, None, 0, 0, 0, 4, o[0]],
             "ivx_take_fixed": [H, self.src.p, u32(8), u64(64), None, self.idx.p, u64(n), o[0], o[1]],
             "ivx_scatter_fixed": [H, self.src.p, u32(8), self.idx.p, u64(n), o[0], u64(64)],
             "ivx_take_utf8": [H, cint(0), self.toff.p, self.ttext.p, u64(n), u64(len(self.ttext.np())), None, self.idx.p, u64(n), o[0], o[1], u64(512), cnt, o[2]],
@@ -119,6 +125,8 @@ DEVICE = cint(pyivx.MEM_DEVICE)
 ODD = "odd"                 # stands for a device pointer that is off its element size by one byte
 BAD_MEM = (INVALID, "bad mem")
 ALIGN = (INVALID, "depth profile: output pointer not aligned to its element size")
+ALIGN_ANY = (INVALID, "depth profile: pointer not aligned to its element size")      # quantize and hist check key_hi as well
+DESCENDING = np.array([3, 1], np.int32)                                                # cuts are host memory in both modes
 
 # (entry, {argument position after ctx: bad value}) -> (status, ivx_last_error), the texts as csrc/ivx_capi.hip has them
 ERRORS = [
@@ -134,6 +142,8 @@ ERRORS = [
     ("ivx_depth_profile_quantiles", {1: 2}, BAD_MEM), ("ivx_depth_profile_window_quantiles", {1: 2}, BAD_MEM),
     ("ivx_take_fixed", {0: MEM2}, BAD_MEM), ("ivx_scatter_fixed", {0: MEM2}, BAD_MEM), ("ivx_take_utf8", {0: MEM2}, BAD_MEM),
     ("ivx_take_bits", {0: MEM2}, BAD_MEM), ("ivx_take_view", {0: MEM2}, BAD_MEM),
+    ("ivx_probe_overlap_agg", {1: MEM2}, BAD_MEM), ("ivx_intersect", {0: MEM2}, BAD_MEM),
+    ("ivx_depth_profile_quantize", {1: 2}, BAD_MEM), ("ivx_depth_profile_hist", {1: 2}, BAD_MEM),
     # a null required column with n > 0
     ("ivx_index_build", {3: None}, (INVALID, "null coordinate column")),
     ("ivx_probe_overlap_count", {4: None}, (INVALID, "null coordinate column")),
@@ -168,6 +178,15 @@ ERRORS = [
     ("ivx_take_utf8", {2: None}, (INVALID, "take: null source column")),
     ("ivx_take_bits", {6: None}, (INVALID, "take: null idx or out")),
     ("ivx_take_view", {1: None}, (INVALID, "take: null source column")),
+    ("ivx_probe_overlap_agg", {4: None}, (INVALID, "null coordinate column")),
+    ("ivx_probe_overlap_agg", {6: None}, (INVALID, "overlap_agg: null value column")),
+    ("ivx_probe_overlap_agg", {8: None, 9: None, 10: None, 11: None, 12: None, 13: None}, (INVALID, "overlap_agg: no output wanted")),
+    ("ivx_intersect", {7: None}, (INVALID, "null coordinate column")),
+    ("ivx_intersect", {5: None}, (INVALID, "intersect: key given for one side only")),
+    ("ivx_depth_profile_merge", {0: None}, (INVALID, "null depth profile")),
+    ("ivx_depth_profile_merge", {1: None}, (INVALID, "null depth profile")),
+    ("ivx_depth_profile_quantize", {6: None}, (INVALID, "depth profile: null cuts")),
+    ("ivx_depth_profile_hist", {8: None}, (INVALID, "depth profile: null out_hist")),
     # a null n_out (or the entry's word for it)
     ("ivx_index_build", {7: None}, (INVALID, "null out")), ("ivx_bits_select", {6: None}, (INVALID, "null n_out")),
     ("ivx_probe_nearest", {13: None}, (INVALID, "null rows")), ("ivx_merge", {13: None}, (INVALID, "null n_out")),
@@ -177,10 +196,20 @@ ERRORS = [
     ("ivx_depth_profile_build_text", {18: None}, (INVALID, "null out")), ("ivx_cigar_parse", {8: None}, (INVALID, "null n_ops")),
     ("ivx_depth_profile_read", {7: None}, (INVALID, "null n_out")), ("ivx_depth_profile_blocks", {7: None}, (INVALID, "null n_out")),
     ("ivx_take_utf8", {12: None}, (INVALID, "null data_bytes")), ("ivx_take_view", {12: None}, (INVALID, "null data_bytes")),
+    ("ivx_intersect", {16: None}, (INVALID, "null n_out")), ("ivx_depth_profile_merge", {2: None}, (INVALID, "null out")),
+    ("ivx_depth_profile_quantize", {14: None}, (INVALID, "null n_out")),
     # a misaligned device output pointer
     ("ivx_depth_profile_expand", {1: DEVICE, 6: ODD}, ALIGN), ("ivx_depth_profile_expand", {1: DEVICE, 7: ODD}, ALIGN),
     ("ivx_depth_profile_summarize", {1: DEVICE, 12: ODD}, ALIGN), ("ivx_depth_profile_windows", {1: DEVICE, 11: ODD}, ALIGN),
     ("ivx_depth_profile_quantiles", {1: DEVICE, 13: ODD}, ALIGN), ("ivx_depth_profile_window_quantiles", {1: DEVICE, 14: ODD}, ALIGN),
+    ("ivx_depth_profile_quantize", {1: DEVICE, 9: ODD}, ALIGN_ANY), ("ivx_depth_profile_quantize", {1: DEVICE, 12: ODD}, ALIGN_ANY),
+    ("ivx_depth_profile_hist", {1: DEVICE, 8: ODD}, ALIGN_ANY), ("ivx_depth_profile_hist", {1: DEVICE, 3: ODD}, ALIGN_ANY),
+    # val_bytes = 3, 32 cuts, descending cuts, an emit bit above the last class, n_bins = 0
+    ("ivx_probe_overlap_agg", {7: u32(3)}, (INVALID, "overlap_agg: val_bytes is 4 or 8")),
+    ("ivx_depth_profile_quantize", {7: 32}, (INVALID, "depth profile: more than 31 cuts")),
+    ("ivx_depth_profile_quantize", {6: pyivx._ptr(DESCENDING)}, (INVALID, "depth profile: cuts not strictly ascending")),
+    ("ivx_depth_profile_quantize", {8: 8}, (INVALID, "depth profile: emit_mask names a class above n_cuts")),
+    ("ivx_depth_profile_hist", {7: 0}, (INVALID, "depth profile: n_bins outside 1 .. 65536")),
     # width = 0, n_thr = 9, q_den = 0
     ("ivx_depth_profile_windows", {5: 0}, (INVALID, "depth profile: window width 0")),
     ("ivx_depth_profile_window_quantiles", {5: 0}, (INVALID, "depth profile: window width 0")),
@@ -193,6 +222,9 @@ ERRORS = [
     ("ivx_depth_profile_windows", {1: 2, 5: 0}, BAD_MEM),
     ("ivx_depth_profile_summarize", {1: DEVICE, 10: 9, 12: ODD}, (INVALID, "depth profile: more than 8 thresholds")),
     ("ivx_take_fixed", {0: MEM2, 2: u32(3)}, BAD_MEM),
+    ("ivx_probe_overlap_agg", {1: MEM2, 7: u32(3)}, BAD_MEM),
+    ("ivx_depth_profile_quantize", {1: 2, 7: 32}, BAD_MEM),
+    ("ivx_depth_profile_hist", {1: DEVICE, 7: 0, 8: ODD}, (INVALID, "depth profile: n_bins outside 1 .. 65536")),
 ]
 
 

@@ -78,7 +78,7 @@ def probe_nearest_k1(E, M, n):
     b, p, d = M.out(n, np.uint32), M.out(n, np.uint32), M.out(n, np.int64)
     rows = C.c_uint64(0xDEAD)
     st = E.call("ivx_probe_nearest", E.ix[3].h, M.mem, k.p, s.p, e.p, C.c_uint64(n), C.c_int(0), C.c_uint32(1), C.c_int(1),
-                b.p, p.p, d.p, C.c_uint64(n), C.byref(rows))
+                b.p, p.p, d.p, C.c_uint64(n), C.byref(rows), outs=[b, p, d], count=rows)
     r = rows.value
     return {"st": st, "rows": r, "b": b.np()[:r], "p": p.np()[:r], "d": d.np()[:r]}
 
@@ -192,7 +192,7 @@ NEAREST_KNOBS = [{"IVX_NEAREST_PATH": "direct"}, {"IVX_NEAREST_PATH": "routed"}]
 # k = 1 alone: the catalogue's probe_nearest and index_build ask for k = 2 and run once, probe_nearest_k1 (above) under both
 KNOBS = {
     "probe_overlap_count": JOIN_KNOBS, "probe_overlap_fill": JOIN_KNOBS, "probe_exists": JOIN_KNOBS, "probe_mark_build": JOIN_KNOBS,
-    "probe_count": ROWVAL_KNOBS, "probe_coverage": ROWVAL_KNOBS, "probe_nearest_k1": NEAREST_KNOBS,
+    "probe_overlap_agg": JOIN_KNOBS, "probe_count": ROWVAL_KNOBS, "probe_coverage": ROWVAL_KNOBS, "probe_nearest_k1": NEAREST_KNOBS,
     "index_build": [{**JOIN_KNOBS[0], **ROWVAL_KNOBS[0]}, {**JOIN_KNOBS[1], **ROWVAL_KNOBS[1]}, {**JOIN_KNOBS[2], **ROWVAL_KNOBS[3]}],
 }
 S0_RUNS = [(name, knobs) for name in NAMES + sorted(LOCAL_CASES) for knobs in KNOBS.get(name, [{}])]
@@ -244,16 +244,19 @@ JOIN_AFTER = {
     "probe_overlap_fill": (D, D),               # its own count + fill consume a plan of its own; the one-short fill routes again
     "probe_exists": (D, D),                     # the per-row region probe routes its rows
     "probe_mark_build": (D, D),                 # drop_join_plan()
+    "probe_overlap_agg": (D, D),                # drop_join_plan()
     "bits_mark": (K, K),                        # host: WS_IN_KEY and WS_OUT_A only; no scratch on the device
     "bits_select": (D, D),                      # WS_T0 (ivx_marks.hip)
     "probe_count": (D, K),                      # direct kernel, no scratch; host mode stages three columns
     "probe_coverage": (D, K),
     "probe_nearest": (D, K2),                   # k = 2: WS_T2..WS_T5
     "merge": (D, D), "subtract": (D, D), "cluster": (D, D), "complement": (D, D),      # WS_T0.. (ivx_sweep.hip)
+    "intersect": (D, D),                        # drop_plans()
     "depth": (D, D), "depth_text": (D, D), "depth_profile_build": (D, D), "depth_profile_build_text": (D, D), "cigar_parse": (D, D),   # drop_plans()
     "depth_profile_read": (K, K),               # copies only
     "depth_profile_expand": (D, D), "depth_profile_blocks": (D, D), "depth_profile_summarize": (D, D), "depth_profile_windows": (D, D),
     "depth_profile_quantiles": (D, D), "depth_profile_window_quantiles": (D, D),           # drop_plans()
+    "depth_profile_merge": (D, D), "depth_profile_quantize": (D, D), "depth_profile_hist": (D, D),      # drop_plans()
     "take_fixed": (D, K), "scatter_fixed": (D, K), "take_bits": (D, K),                    # no scratch on the device; host mode stages WS_IN_START / WS_IN_END
     "take_utf8": (D, D), "take_view": (D, D),   # WS_T0 (ivx_take.hip)
 }
@@ -262,15 +265,17 @@ JOIN_AFTER = {
 SUB_AFTER = {
     "index_build": (D, D),                      # the coverage and nearest builds take WS_T0..
     "probe_overlap_count": (K, K), "probe_overlap_fill": (K, K), "probe_exists": (K, K), "probe_mark_build": (K, K),   # direct kernels, no scratch
+    "probe_overlap_agg": (K, K),                # drop_join_plan() only; direct kernel, no scratch (ivx_agg.hip: ivx_agg_probe)
     "bits_mark": (K, K),
     "bits_select": (D, D),                      # WS_T0
     "probe_count": (K, K), "probe_coverage": (K, K),
     "probe_nearest": (D, D),                    # WS_T2..WS_T5
-    "merge": (D, D), "subtract": (D, D), "cluster": (D, D), "complement": (D, D),
+    "merge": (D, D), "subtract": (D, D), "cluster": (D, D), "complement": (D, D), "intersect": (D, D),
     "depth": (D, D), "depth_text": (D, D), "depth_profile_build": (D, D), "depth_profile_build_text": (D, D), "cigar_parse": (D, D),
     "depth_profile_read": (K, K),
     "depth_profile_expand": (D, D), "depth_profile_blocks": (D, D), "depth_profile_summarize": (D, D), "depth_profile_windows": (D, D),
     "depth_profile_quantiles": (D, D), "depth_profile_window_quantiles": (D, D),
+    "depth_profile_merge": (D, D), "depth_profile_quantize": (D, D), "depth_profile_hist": (D, D),
     "take_fixed": (K, K), "scatter_fixed": (K, K), "take_bits": (K, K),
     "take_utf8": (D, D), "take_view": (D, D),
 }
