@@ -22,6 +22,19 @@
  *                     ctx stream.
  *    Scalar out-parameters (`uint64_t *total`, `*n_out`, ...) are always host
  *    pointers; writing them synchronises the ctx stream.
+ *  - An IVX_MEM_DEVICE call is ordered on the ctx stream like a kernel launch
+ *    of the caller's own.  Its input columns may be the product of earlier
+ *    work on that stream that has not run yet when the call is made; its
+ *    output columns may be consumed by work queued on that stream right after
+ *    the call returns, with no host synchronisation (the call may return with
+ *    kernels in flight); work on any other stream is the caller's to order
+ *    against the ctx stream.  Two exceptions, stated with their entries: with
+ *    the build overlap on (ivx_ctx_set_build_overlap) the build columns stay
+ *    unchanged until the index's first probe call has returned, and the input
+ *    columns stay unchanged between a total-only ivx_probe_overlap_count (an
+ *    ivx_subtract sizing call) and the fill call its state serves.
+ *    (tests/test_gpu_entry_stream_order.py; DESIGN.md, "What a device-mode
+ *    call may assume of its stream".)
  *  - Keys never cross the boundary as strings: the host maps the equi-key
  *    column(s) (contig, or contig+strand, ...) to dense ids 0..n_keys-1.  The
  *    reference groups rows by a 64-bit hash of the key columns and never
@@ -45,7 +58,11 @@
  *  - An ivx_index is immutable after build and may be probed concurrently
  *    from several host threads, each with its OWN ivx_ctx on the same device
  *    (the reference shares Arc<JoinLeftData> across partitions,
- *    interval_join.rs:466-480).
+ *    interval_join.rs:466-480).  It is complete when ivx_index_build returns
+ *    (the build has waited for its stream), up to the tail of an overlapped
+ *    build, behind which every probe call of every ctx orders its own stream:
+ *    another ctx on another stream may probe it at once, no
+ *    ivx_ctx_synchronize on the building ctx is owed first.
  *  - There is NO CPU fallback: without a usable gfx950 device
  *    ivx_ctx_create fails with IVX_ERR_NO_DEVICE.
  */

@@ -1,10 +1,17 @@
 """The catalogue of the C entry layer (csrc/ivx_capi.hip), shared by the tests that walk every entry: CASES maps an entry's name
 to f(E, M, n) -> dict of all its outputs, the scalar ones included, on a small seeded input of n rows -- E an Env (one context,
 one index of every kind, two depth profiles), M a Mode (host arrays or device tensors).  The entries are called through
-pyivx.lib() with ctypes directly: pyivx's wrappers would allocate, retry or reject first.  Importing this needs no GPU."""
+pyivx.lib() with ctypes directly: pyivx's wrappers would allocate, retry or reject first.  Importing this needs no GPU.
+
+A third mode, LateMode, is device mode with every column still in flight on the context's stream when the entry is invoked
+(tests/test_gpu_entry_stream_order.py; DESIGN.md, "What a device-mode call may assume of its stream")."""
+import contextlib
 import ctypes as C
+import math
 import os
 import sys
+import time
+import weakref
 
 import numpy as np
 
@@ -42,8 +49,11 @@ class Buf:
     def p(self):
         return pyivx._ptr(self.h)
 
+    clone = None                # LateMode: what a consumer queued right behind the last call saw of this buffer
+
     def np(self):
-        a = self.h.cpu().numpy() if pyivx._is_torch(self.h) else self.h
+        h = self.h if self.clone is None else self.clone
+        a = h.cpu().numpy() if pyivx._is_torch(h) else h
         return a.view(self.dt).reshape(-1)
 
 
@@ -56,16 +66,210 @@ class Mode:
 
     def out(self, n, dt):
         """an output buffer of n elements (at least one), every byte PATTERN"""
-        return Buf(np.full(max(int(n), 1) * np.dtype(dt).itemsize, PATTERN, np.uint8).view(dt), self.dev)
+        return self.put(np.full(max(int(n), 1) * np.dtype(dt).itemsize, PATTERN, np.uint8).view(dt))
+
+    def fixed(self, *bufs):
+        """input columns that the interface wants unchanged from the next call on (between a sizing call and its fill, under
+        a build tail): nothing to do unless the mode rewrites its buffers before every call (LateMode)"""
+
+
+class LateBuf(Buf):
+    """a device Buf of LateMode: `h`, what the entry gets, holds the decoy (zero bytes) until the real content -- `stage`,
+    complete on the device before anything is queued -- is copied over it on the mode's stream"""
+
+    def __init__(self, a):
+        import torch
+        a = np.ascontiguousarray(a)
+        self.dt, self.n = a.dtype, a.size
+        if a.size == 0:
+            a = np.zeros(1, a.dtype)
+        self.stage = torch.from_numpy(a.view(_SIGNED.get(a.dtype, a.dtype)).copy()).to("cuda:0")     # (from pageable memory: synchronous)
+        self.h = torch.zeros_like(self.stage)
+        self.fixed = self.delivered = False
+
+
+class Delay:
+    """a device-side delay of a chosen length, queued on the current stream: torch.cuda._sleep, calibrated once with two
+    timing events (cycles_per_ms), or -- should _sleep not give the length asked for -- a chain of 256 MB fills.  host_cost(nb)
+    is the measured host time between queuing the delay and invoking an entry with nb live buffers: nb copies, one event."""
+    MIN_MS = 10.0               # no delay is shorter
+    FACTOR = 100.0              # ... nor shorter than this many times the host time it has to outlast
+
+    def __init__(self, stream):
+        import torch
+        self.stream = stream
+        self.log = []               # every call made under a LateMode with this delay: LateMode.calls
+        self.n_early = 0            # ... and how many of them returned while their producer was still running
+
+        def timed(queue):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            with torch.cuda.stream(stream):
+                e0.record()
+                queue()
+                e1.record()
+            e1.synchronize()
+            return e0.elapsed_time(e1)
+
+        timed(lambda: torch.cuda._sleep(1000))
+        c1 = 1_000_000
+        t1 = timed(lambda: torch.cuda._sleep(c1))
+        c2 = int(c1 * min(max(20.0 / max(t1, 1e-3), 2.0), 1000.0))      # some 20 ms
+        t2 = timed(lambda: torch.cuda._sleep(c2))
+        self.cycles_per_ms = (c2 - c1) / (t2 - t1) if t2 > t1 else 0.0
+        self.big, self.ms_per_fill = None, 0.0
+        t10 = timed(lambda: self.queue(10.0)) if self.cycles_per_ms > 0 else 0.0
+        if not 9.0 <= t10 <= 15.0:                                      # _sleep misbehaves: fills
+            self.cycles_per_ms = 0.0
+            self.big = torch.empty(1 << 26, dtype=torch.int32, device="cuda:0")
+            timed(lambda: self.big.fill_(0))
+            self.ms_per_fill = timed(lambda: [self.big.fill_(i) for i in range(8)]) / 8
+            t10 = timed(lambda: self.queue(10.0))
+            assert 9.0 <= t10 <= 30.0, f"no usable device-side delay: 10 ms asked for, {t10} ms measured"
+        self.check_ms = t10                                             # what a delay of 10 ms took
+        # the host side: the time nb copies and an event take to queue, at 1 and at 16 buffers (the most a catalogue case has
+        # alive); the slowest of twenty runs each
+        src = [torch.zeros(1000, dtype=torch.int32, device="cuda:0") for _ in range(16)]
+        dst = [torch.zeros_like(t) for t in src]
+        cost = {1: 0.0, 16: 0.0}
+        for rep in range(22):                                           # (the first two: warm-up)
+            for nb in cost:
+                with torch.cuda.stream(stream):
+                    t0 = time.perf_counter()
+                    for a, b in zip(src[:nb], dst[:nb]):
+                        b.copy_(a)
+                    ev = torch.cuda.Event()
+                    ev.record(stream)
+                    ev.query()
+                    dt = time.perf_counter() - t0
+                stream.synchronize()
+                if rep >= 2:
+                    cost[nb] = max(cost[nb], dt)
+        self.host_per_buf = max(cost[16] - cost[1], 0.0) / 15
+        self.host_base = cost[1]
+
+    def host_cost(self, nb):
+        return self.host_base + self.host_per_buf * max(nb - 1, 0)
+
+    def ms_for(self, nb):
+        return max(self.MIN_MS, self.FACTOR * 1e3 * self.host_cost(nb))
+
+    def queue(self, ms):
+        import torch
+        if self.big is None:
+            torch.cuda._sleep(int(ms * self.cycles_per_ms))
+        else:
+            for i in range(int(math.ceil(ms / self.ms_per_fill))):
+                self.big.fill_(i)
+
+
+class LateMode(Mode):
+    """device mode with every column still in flight on the caller's stream when the entry is invoked.  Env.call of the Env
+    this mode is entered on (`with LateMode(E, stream, delay):`; the Env's context runs on `stream`) queues on that stream,
+    and nowhere else, before every entry:
+      1. the decoy -- zero bytes: key 0, position 0, offset 0, row 0, empty strings, an empty bitmap, a valid column of every
+         case here -- into every live buffer of the mode, inputs and outputs alike;
+      2. one delay (Delay.ms_for: at least 100 times the calibrated host time of 3. and 4., at least 10 ms; `ms` sets it by hand);
+      3. the copies of the real contents: the input array, the PATTERN of an output, the caller's prior bits of a bitmap;
+      4. the event `ready`;
+    invokes the entry at once -- `ready` must not have happened by then, or the call proves nothing and fails as such --,
+    queues a clone of every buffer named in outs= behind the entry before any synchronisation, synchronises, and asserts that
+    the buffers still equal their clones.  Buf.np() gives the clone: the walk's results are what a consumer queued behind the
+    call saw.  Inputs are never rewritten after a call returns (half of one valid offset column and half of another is no
+    valid column); columns the interface wants unchanged across calls are named with fixed() and are late once."""
+
+    def __init__(self, E, stream, delay, ms=None):
+        super().__init__(True)
+        self.E, self.stream, self.delay, self.ms = E, stream, delay, ms
+        self.bufs = weakref.WeakSet()
+        self.ready = None
+        self.calls = []             # (entry, live buffers, host seconds between queuing the delay and invoking, the delay's ms)
+        self.early = []             # per call: it returned while the producer was still running (it never waited for it)
+
+    def __enter__(self):
+        self.E.late = self
+        return self
+
+    def __exit__(self, *exc):
+        self.E.late = None
+
+    def put(self, a):
+        b = LateBuf(a)
+        self.bufs.add(b)
+        return b
+
+    def fixed(self, *bufs):
+        for b in bufs:
+            b.fixed = True
+
+    def before(self):
+        import torch
+        live = [b for b in self.bufs if not (b.fixed and b.delivered)]
+        ms = self.ms if self.ms is not None else self.delay.ms_for(len(live))
+        self.stream.wait_stream(torch.cuda.current_stream())    # (the buffers were made on torch's current stream)
+        with torch.cuda.stream(self.stream):
+            for b in live:
+                b.clone = None
+                b.h.zero_()
+            self.delay.queue(ms)
+            self.t0 = time.perf_counter()
+            for b in live:
+                b.h.copy_(b.stage)
+                b.delivered = True
+            self.ready = torch.cuda.Event()
+            self.ready.record(self.stream)
+        self.nb, self.cur_ms = len(live), ms
+
+    def invoke(self, entry):
+        """right before the entry: the validity condition of the call"""
+        self.calls.append((entry, self.nb, time.perf_counter() - self.t0, self.cur_ms))
+        self.delay.log.append(self.calls[-1])
+        assert not self.ready.query(), \
+            f"{entry}: inconclusive -- the producer of the columns ({self.cur_ms:.1f} ms of delay) had finished before the entry was invoked"
+
+    def after(self, outs):
+        """right after the entry returned, nothing synchronised yet: had it waited for the producer?; the consumer's clones"""
+        import torch
+        self.early.append(not self.ready.query())
+        self.delay.n_early += self.early[-1]
+        self.cloned = [o[0] if isinstance(o, tuple) else o for o in outs]
+        with torch.cuda.stream(self.stream):
+            for b in self.cloned:
+                b.clone = b.h.clone()
+
+    def settle(self, entry):
+        import torch
+        self.stream.synchronize()
+        for i, b in enumerate(self.cloned):
+            assert torch.equal(b.h, b.clone), f"{entry}: output {i} changed after the consumer queued behind the call had read it"
 
 
 def untouched(buf):
     return bool((buf.np().view(np.uint8) == PATTERN).all())
 
 
+SHAPE = {"spread": 0, "ops": None, "cols": None}     # see shaped()
+
+
+@contextlib.contextmanager
+def shaped(spread=0, ops=None, cols=None):
+    """the catalogue's columns at a size of the caller's for the with-block: ivals() over at least `spread` coordinates per
+    row (the default 20 000 in all make 200 000 rows one run per key), or as cols(n, seed) gives them (int32 rows that meet
+    the caller's own build); reads() with exactly `ops` CIGAR ops in all"""
+    old = dict(SHAPE)
+    SHAPE.update(spread=spread, ops=ops, cols=cols)
+    try:
+        yield
+    finally:
+        SHAPE.update(old)
+
+
 def ivals(n, seed, dt=np.int32, span=20_000):
+    if SHAPE["cols"] is not None:
+        key, s, e = SHAPE["cols"](n, seed)
+        return key.astype(np.uint32), s.astype(dt), e.astype(dt)
     rng = np.random.default_rng(seed)
     key = rng.integers(0, NK, n).astype(np.uint32)
+    span = max(span, SHAPE["spread"] * n)
     s = rng.integers(0, span, n)
     e = s + rng.integers(0, 300, n)
     return key, s.astype(dt), e.astype(dt)
@@ -76,8 +280,13 @@ def reads(n, seed):
     rng = np.random.default_rng(seed)
     off = np.zeros(n + 1, np.int32)
     ops = []
+    per_read = None
+    if SHAPE["ops"] is not None and n:                      # shaped(ops=): that many ops in all, every read 1 or more
+        assert n <= SHAPE["ops"]
+        per_read = np.full(n, SHAPE["ops"] // n)
+        per_read[:SHAPE["ops"] % n] += 1
     for i in range(n):
-        for _ in range(int(rng.integers(1, 4))):
+        for _ in range(int(rng.integers(1, 4)) if per_read is None else int(per_read[i])):
             ops.append((int(rng.integers(1, 60)) << 4) | int(rng.choice([0, 0, 0, 1, 2, 3, 4])))
         off[i + 1] = 4 * len(ops)
     ns = n // 4
@@ -107,9 +316,9 @@ class Call:
 
 class Env:
     """one context, one index of every kind (from build_cols, by default 1 000 seeded rows) and two depth profiles, built
-    once from host columns"""
+    once from host columns; with `stream` (a torch stream) the context then runs on that caller's stream"""
 
-    def __init__(self, build_cols=None):
+    def __init__(self, build_cols=None, stream=None):
         import torch
         torch.zeros(1, device="cuda:0")                         # (torch's own start-up: here, not in the first case that puts a tensor)
         self.ctx = pyivx.Ctx(0)
@@ -126,14 +335,31 @@ class Env:
                                                r["skey"], r["ss"], r["se"], r["sw"], n_keys=NK)
         self.log = []                   # a Call per call() since the caller last emptied it
         self.stop_on_oom = False
+        self.late = None                # the LateMode entered on this Env, if any
+        self.stream = stream
+        if stream is not None:
+            self.ctx.set_stream(stream.cuda_stream)
 
-    def call(self, name, *args, outs=(), count=None, handle=None):
+    def call(self, name, *args, outs=(), count=None, handle=None, drain=True):
         """the entry's status; the context's stream drained, so that device-mode outputs can be read.  The call goes into
-        the log with the outputs the caller names; with stop_on_oom set, IVX_ERR_OOM raises Refused"""
+        the log with the outputs the caller names; with stop_on_oom set, IVX_ERR_OOM raises Refused.  Under a LateMode the
+        mode's producers are queued in front of the entry and its consumers behind it (see there).  drain=False, for a call
+        without output buffers: nothing is waited for (ivx_ctx_synchronize would wait for a running build tail, too)"""
+        assert drain or not outs
         before = self.ctx.metrics()
-        st = getattr(self.L, name)(self.h, *args)
+        late, fn = self.late, getattr(self.L, name)
+        if late is not None:
+            late.before()
+            late.invoke(name)
+        st = fn(self.h, *args)
+        if late is not None:
+            late.after(outs)
         self.log.append(Call(name, st, self.err() if st != OK else "", before, self.ctx.metrics(), outs, count, handle))
+        if not drain:
+            return st
         assert self.L.ivx_ctx_synchronize(self.h) == OK
+        if late is not None:
+            late.settle(name)
         if st == OOM and self.stop_on_oom:
             raise Refused(name)
         return st
@@ -218,6 +444,8 @@ def probe_overlap_count(E, M, n):
 @case
 def probe_overlap_fill(E, M, n):
     k, s, e = (M.put(a) for a in ivals(n, 5))
+    # (no M.fixed(): without IVX_JOIN_PATH=regions a count call of fewer than 2^21 rows leaves no plan, the fill call reads the
+    # three columns itself and LateMode delivers them late again; a planned fill: test_gpu_entry_stream_order.py, fixed columns)
     res = {}
 
     def call(cap, bufs):
@@ -346,6 +574,7 @@ def subtract(E, M, n):
     lk, ls, le = (M.put(a) for a in ivals(n, 13, np.int64))
     nr = n // 2 if n > 1 else n
     rk, rs, re = (M.put(a) for a in ivals(nr, 14, np.int64))
+    M.fixed(lk, ls, le, rk, rs, re)     # the six columns must not change between the sizing call and its fill: late once
     res = {}
 
     def call(cap, bufs):
