@@ -31,6 +31,8 @@ JOIN_INNER, JOIN_RIGHT_SEMI, JOIN_RIGHT_ANTI = 0, 1, 2
 JOIN_LEFT_SEMI, JOIN_LEFT_ANTI, JOIN_LEFT, JOIN_RIGHT, JOIN_FULL = 4, 5, 6, 7, 8
 # the outputs of overlap_aggregate, in the order of the BRH_AGG_* bits (include/bio_ranges_host.h)
 AGG_OPS = ("count", "sum", "min", "max", "bases", "wsum")
+# the criteria of overlap_select, in the order of the BRH_SEL_* enum (include/bio_ranges_host.h)
+SEL_BY = pyivx.SEL_BY
 
 
 class _ArrowSchema(C.Structure):
@@ -222,6 +224,27 @@ class Session:
             B.close(); P.close()
         got = {o: _import(arrs[i], schs[i]) for i, o in enumerate(AGG_OPS) if mask & (1 << i)}
         return pa.table({o: got[o] for o in ops})
+
+    # ---- overlap select: the join reduced to the one best build row per probe row (no pairs are made)
+    def overlap_select(self, build, probe, by, value=None, cols_build=DEFAULT_COLS, cols_probe=DEFAULT_COLS,
+                       strict_predicate=False):
+        """per row of `probe`, of the rows of `build` it overlaps, the one that is best by `by` (SEL_BY; ties: the smallest
+        build row) -> (build_idx, score), one row per probe row in probe order.  build_idx: UInt32, NULL without a match --
+        take_table(build, build_idx) gives the left join to at most one row.  score: Int64, NULL where build_idx is: the
+        winner's value, closed overlap length or row.  `value` names build's value column for "min_val" / "max_val" (and for
+        them only): Int8 .. Int64, UInt8 .. UInt64, Float32 or Float64 without nulls or NaNs; for UInt64 and float columns
+        score is None (take the value with build_idx)."""
+        if by not in SEL_BY:
+            raise BioRangesError(f"overlap_select: by is one of {SEL_BY}, got {by!r}")
+        B, P = _Exported(build), _Exported(probe)
+        (ia, is_), (sa, ss) = _out(), _out()
+        try:
+            self._chk(lib().brh_overlap_select(self.h, B.c, _cols(cols_build), None if value is None else value.encode(), P.c,
+                                               _cols(cols_probe), C.c_int(int(strict_predicate)), C.c_int(SEL_BY.index(by)),
+                                               C.byref(ia), C.byref(is_), C.byref(sa), C.byref(ss)))
+        finally:
+            B.close(); P.close()
+        return _import(ia, is_), (_import(sa, ss) if sa.release else None)
 
     def sql_range_join(self, build, probe, cols_build=DEFAULT_COLS, cols_probe=DEFAULT_COLS, strict_predicate=False,
                        nearest_algorithm=False, device_take=False):

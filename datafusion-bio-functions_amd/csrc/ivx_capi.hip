@@ -903,6 +903,54 @@ extern "C" ivx_status ivx_probe_overlap_agg(ivx_ctx *ctx, const ivx_index *ix, i
     return f.finish();
 }
 
+// ---------------------------------------------------------------- a3'''': overlap select (include/ivx_select.h)
+
+// Beside ivx_probe_overlap_agg, and with its path choice: big batches over a lean index take the region kernels
+// (ivx_sel_probe_regions), everything else the direct one.  One winner per probe row, in input order.
+// The switch between the two, measured (tools/overlap_select_timing.py, profiles/overlap_select_timing.txt; max_val on int32
+// and max_overlap, with and without the score): from 2^23 rows the region path's slowest repeat beat the direct kernel's
+// fastest in all four variants (0.26 against 0.35 ms with value and score; 2.51 against 3.49 ms at 10^8 rows); at 2^22 rows
+// it did in three of them and lost with max_overlap and score; at 2^21 it lost in all.
+static u64 sel_regions_rows()
+{
+    return 1ull << 23;
+}
+extern "C" ivx_status ivx_probe_overlap_select(ivx_ctx *ctx, const ivx_index *ix, int mem, const uint32_t *key,
+                                               const int32_t *start, const int32_t *end, uint64_t n, const void *val, uint32_t val_bytes,
+                                               int by, uint32_t *build_idx, int64_t *score)
+{
+    Frame f(ctx, mem);
+    IVX_TRY(check_probe_args(f, ix, IVX_KIND_OVERLAP, start, end, n));             // (orders the stream behind a build tail, too)
+    if (!build_idx) return ctx->fail(IVX_ERR_INVALID, "overlap_select: null build_idx");
+    if (by < 0 || by >= IVX_SEL_N) return ctx->fail(IVX_ERR_INVALID, "overlap_select: unknown criterion");
+    const bool by_val = by == IVX_SEL_MIN_VAL || by == IVX_SEL_MAX_VAL;
+    if (by_val && val_bytes != 4 && val_bytes != 8) return ctx->fail(IVX_ERR_INVALID, "overlap_select: val_bytes is 4 or 8");
+    if (by_val && ix->n && !val) return ctx->fail(IVX_ERR_INVALID, "overlap_select: null value column");
+    f.meter(false, n);
+    f.drop_join_plan();                                     // as any other call between a count call and its fill
+    if (n == 0) return IVX_OK;
+    // the override of ivx_probe_overlap_agg, a threshold of its own
+    bool regions = ix->jv_nreg > 0 && ix->jv_nreg <= IVX_MAXREG_WIDE && n >= sel_regions_rows();
+    if (const char *p = getenv("IVX_JOIN_PATH")) {
+        if (!strcmp(p, "direct")) regions = false;
+        else if (!strcmp(p, "regions")) regions = ix->jv_nreg > 0 && ix->jv_nreg <= IVX_MAXREG_WIDE;
+    }
+    const u32 *dk = f.in(key, n);
+    const i32 *ds = f.in(start, n), *de = f.in(end, n);
+    const void *dv = by_val ? f.in((const u8 *)val, (u64)ix->n * val_bytes) : nullptr;      // (the other criteria stage nothing of val)
+    SelOut o;
+    o.idx = f.out(build_idx, n); o.score = f.out(score, n);
+    IVX_TRY(f.st);
+    IVX_TRY(f.run([&]() -> ivx_status {
+        bool took = false;
+        if (regions) IVX_TRY(ivx_sel_probe_regions(ctx, ix->jv, ix->jv_nreg, dk, ds, de, n, dv, val_bytes, by, o, ix->jv_filter, ix->jv_pk24, ix->jv_lean.load(std::memory_order_relaxed) == 1, &took));
+        return took ? IVX_OK : ivx_sel_probe(ctx, ix->jv, dk, ds, de, n, dv, val_bytes, by, o);
+    }));
+    f.rows_out(n);                                          // (as ivx_probe_count: not on a refused call)
+    f.back_all();
+    return f.finish();
+}
+
 extern "C" ivx_status ivx_bits_mark(ivx_ctx *ctx, int mem, const uint32_t *idx, uint64_t n, uint32_t *bits, uint64_t n_bits)
 {
     Frame f(ctx, mem);

@@ -7,6 +7,7 @@
 #include <string>
 #include <vector>
 #include "../../include/ivx.h"
+#include "../../include/ivx_select.h"
 
 typedef uint8_t u8;
 typedef uint32_t u32;
@@ -391,6 +392,14 @@ ivx_status ivx_agg_probe(ivx_ctx *ctx, const JoinIndexView &jv, const u32 *key, 
                          const void *val, u32 val_bytes, const AggOut &out);
 ivx_status ivx_agg_probe_regions(ivx_ctx *ctx, const JoinIndexView &jv, u32 nreg, const u32 *key, const i32 *s, const i32 *e, u64 n,
                                  const void *val, u32 val_bytes, const AggOut &out, bool has_filter, bool pk24, bool fast, bool *took);
+// overlap select (ivx_select.hip; the lean region form in ivx_regions_probe.hip): per probe row the one build row of those the
+// join pairs it with that is best by `by` (an IVX_SEL_* criterion; val / val_bytes are read by the *_VAL ones only).  idx is
+// always wanted; score may be null: neither computed nor stored
+struct SelOut { u32 *idx; i64 *score; };
+ivx_status ivx_sel_probe(ivx_ctx *ctx, const JoinIndexView &jv, const u32 *key, const i32 *s, const i32 *e, u64 n,
+                         const void *val, u32 val_bytes, int by, const SelOut &out);
+ivx_status ivx_sel_probe_regions(ivx_ctx *ctx, const JoinIndexView &jv, u32 nreg, const u32 *key, const i32 *s, const i32 *e, u64 n,
+                                 const void *val, u32 val_bytes, int by, const SelOut &out, bool has_filter, bool pk24, bool fast, bool *took);
 ivx_status ivx_bits_mark_device(ivx_ctx *ctx, const u32 *idx, u64 n, u32 *bits, u64 n_bits);
 ivx_status ivx_bits_select_device(ivx_ctx *ctx, const u32 *bits, u64 n_bits, int want_set, u32 *out, u64 cap, u64 *n_out);
 

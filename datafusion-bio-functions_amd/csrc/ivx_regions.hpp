@@ -88,3 +88,5 @@ ivx_status ivx_unroute_values(ivx_ctx *ctx, const ivx_routed &R, u32 nreg, int k
 // the overlap aggregates' records back into input order (PAGED, rowval): rec.* are indexed like the page pool, one array per
 // wanted output of `out` (null: not wanted); rows that were never routed get the empty result (0, and the min / max identities)
 ivx_status ivx_unroute_records(ivx_ctx *ctx, const ivx_routed &R, u32 nreg, u64 n, const AggOut &rec, const AggOut &out);
+// the same for overlap select's records: rows that were never routed get (IVX_NULL_IDX, 0)
+ivx_status ivx_unroute_sel_records(ivx_ctx *ctx, const ivx_routed &R, u32 nreg, u64 n, const SelOut &rec, const SelOut &out);

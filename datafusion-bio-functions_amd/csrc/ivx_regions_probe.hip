@@ -16,13 +16,15 @@
 // Host side: region_knobs (the IVX_* environment settings, read once per call), probe_pairs (count / fill over any
 // ivx_routed), and the entry points ivx_join_probe_regions (COUNT / FILL; a COUNT call leaves its routed rows to the
 // FILL call that follows: ivx_join_plan), ivx_rowval_probe_regions (one value per probe row, in input order) and
-// ivx_mark_probe_regions (one bit per matched BUILD row, ORed into the caller's bitmap; lean form only) and
-// ivx_agg_probe_regions (per probe row, aggregates of a build-side value column; lean form only).
+// ivx_mark_probe_regions (one bit per matched BUILD row, ORed into the caller's bitmap; lean form only),
+// ivx_agg_probe_regions (per probe row, aggregates of a build-side value column; lean form only) and
+// ivx_sel_probe_regions (per probe row, the best matching build row by a criterion: k_sel_fast/_rest; lean form only).
 //
 // HBM traffic per probe row behind the routing: 12 B or 8 B (probe) + 8 B per pair, all streaming (measured:
 // profiles/r1_d_regions_pipeline_pmc.txt).
 #include "ivx_regions.hpp"
 #include "ivx_agg.hpp"
+#include "ivx_select.hpp"
 
 namespace {
 
@@ -1247,6 +1249,93 @@ __global__ __launch_bounds__(256) void k_agg_rest(JoinIndexView ix, const u64 *_
     }
 }
 
+// ------------------------------------------------------------------ lean overlap select
+// Per probe row, the one best build row among the row's matches (ivx_probe_overlap_select), over LeanRows and lean_cells as
+// k_agg_fast.  The result names a build row, so beside the slice the workgroup stages the slice's build ROW IDS at slice
+// load, s_row[j] = the row of slice entry j, and for the two *_VAL criteria the values as k_agg_fast does: the candidate loop
+// reads LDS only.  Declared LDS: 24 KB more than k_rv_fast without values, 48 or 72 KB more with them -- one 1024-thread
+// workgroup per CU either way.  A row's (winner, score) goes to a RECORD as the aggregates' do: rec.idx, and rec.score
+// when wanted, indexed like the page pool; ivx_unroute_sel_records brings them into input order and gives the rows the
+// routing pass dropped (IVX_NULL_IDX, 0).  Rows the packed form cannot carry are listed as in k_rv_fast; k_sel_rest walks
+// them with global reads and writes their records.
+template <int B, int BY, int VB, bool SCORE>
+__global__ __launch_bounds__(RP_T, IVX_RV_WPS) void k_sel_fast(JoinIndexView ix, const u64 *__restrict__ pool, const u32 *__restrict__ rcur, const u32 *__restrict__ cfirst,
+                                                   PageTab pt, u32 rowbits, u64 *__restrict__ rest_rows, u32 *rest_n, const void *__restrict__ val, SelOut rec)
+{
+    using VT = typename std::conditional<VB == 4, i32, i64>::type;
+    constexpr bool VAL = sel_by_val<BY>;
+    __shared__ unsigned short s_off[RP_CCAP];
+    __shared__ u64 s_ent[RP_ECAP];
+    __shared__ u32 s_cfirst[IVX_MAXREG_WIDE + 2];
+    __shared__ u32 s_row[RP_ECAP];
+    __shared__ VT s_val[VAL ? RP_ECAP : 1];
+    ProbeLds L{s_off, s_ent, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    const u32 ln = lane_id();
+    auto miss = []() {};                                                 // (a page never published: stay in bounds, silently)
+    LeanRows<B, const u64> rows;
+    if (!rows.init(ix, s_cfirst, cfirst, rcur, pt, pool, rowbits)) return;
+    Slice S;
+    slice_init(ix, S, L);
+    rows.start(miss);
+    u32 loaded_r = 0xFFFFFFFFu;
+    for (u32 i = 0; i < rows.nbatch; i++) {
+        const u32 r = rows.r;
+        if (r != loaded_r) {
+            slice_load(ix, S, L, r, true);                               // (its first barrier: nobody reads the old rows and values any more)
+            const u32 ne = ix.rdesc[r].ne;
+            if (S.inlds) for (u32 j = threadIdx.x; j < ne && j < RP_ECAP; j += RP_T) {
+                const u32 row = ix.ent[S.e0 + j].row;
+                s_row[j] = row;
+                if (VAL) s_val[j] = ((const VT *)val)[row];
+            }
+            __syncthreads();
+            loaded_r = r;
+        }
+        u32 rel[B], len[B], roww[B];                                     // (roww: not used, the un-permute reads the row ids)
+        const auto bt = rows.take(i, rel, len, roww, miss);
+        const u64 at = (u64)(bt.src - pool) + ln;                        // the lane's first row of the batch: its word's place in the pool
+        const i32 rbase = S.rbase;
+        u32 ca[B], cb[B], slow, okm;
+        lean_cells<B>(S, rel, len, rows.maxlen, bt.cnt, ln, ca, cb, slow, okm);
+#pragma unroll
+        for (int q = 0; q < B; q++) {
+            const i32 qs = (i32)((u32)rbase + rel[q]), qe = (i32)((u32)qs + len[q]);
+            SelAcc<BY, SCORE> a;
+            for (u32 j = ca[q]; j < cb[q]; j++) {
+                const u64 x = s_ent[j];
+                const i32 xs = (i32)(u32)x, xe = (i32)(u32)(x >> 32);
+                if (xs <= qe && xe >= qs) {
+                    const u32 row = s_row[j];
+                    a.add(sel_crit<BY>(VAL ? (i64)s_val[j] : 0, row, qs, qe, xs, xe), row);
+                }
+            }
+            if ((okm >> q) & 1u) a.store(rec, at + (u32)q * IVX_WAVE);
+        }
+        if (__builtin_expect(slow != 0, 0)) lean_list_slow<B>(slow, r, bt.first, ln, rest_rows, rest_n);
+    }
+}
+
+template <int BY, int VB, bool SCORE>
+__global__ __launch_bounds__(256) void k_sel_rest(JoinIndexView ix, const u64 *__restrict__ pool, PageTab pt, const u64 *__restrict__ rest_rows,
+                                                  const u32 *__restrict__ rest_n, const i32 *__restrict__ ps_in, const i32 *__restrict__ pe_in,
+                                                  u32 rowbits, const void *__restrict__ val, SelOut rec)
+{
+    const u32 nrow = rest_n[1];
+    const u32 sh0 = ix.hdr[HDR_SH0], nlev = ix.hdr[HDR_NLEV];
+    for (u32 i = blockIdx.x * blockDim.x + threadIdx.x; i < nrow; i += gridDim.x * blockDim.x) {
+        const u64 ent = rest_rows[i];
+        const u32 r = (u32)(ent >> 32);
+        const auto e = rest_row(ix, pt, pool, r, (u32)ent, rowbits, ps_in, pe_in, 0u, []() {});
+        const i32 qs = e.qs, qe = e.qe;
+        SelAcc<BY, SCORE> a;
+        walk_ent(ix, sh0, 0, nlev, ix.rkey[r], qs, qe, [&](const ivx_ent &x) {
+            const i64 v = sel_by_val<BY> ? agg_val<VB>(val, x.row) : 0;
+            a.add(sel_crit<BY>(v, x.row, qs, qe, x.s, x.e), x.row);
+        });
+        a.store(rec, (u64)(e.slot - pool));
+    }
+}
+
 // ------------------------------------------------------------------ match-dense fill: count, scan, write
 // With several pairs per probe row the staging ring holds only one 64-row batch per wavefront and the 16
 // wavefronts of a workgroup end up in lock step, round after round.  For such joins the pairs are written in two
@@ -1756,6 +1845,41 @@ ivx_status ivx_agg_probe_regions(ivx_ctx *ctx, const JoinIndexView &jv, u32 nreg
     }, val_bytes == 8, mm, wt);
     IVX_HIP(ctx, hipGetLastError());
     IVX_TRY(ivx_unroute_records(ctx, R, nreg, n, rec, out));
+    *took = true;
+    return IVX_OK;
+}
+
+// Per probe row the best matching build row by `by` (and the criterion's value there), through the region partition -- the
+// lean form only, with ivx_agg_probe_regions' eligibility: *took = false (nothing launched, no scratch taken) when the index
+// or the settings do not qualify, and the caller runs the direct kernel (ivx_sel_probe).  The outputs are device columns in
+// input order.
+ivx_status ivx_sel_probe_regions(ivx_ctx *ctx, const JoinIndexView &jv, u32 nreg, const u32 *key, const i32 *s, const i32 *e, u64 n,
+                                 const void *val, u32 val_bytes, int by, const SelOut &out, bool has_filter, bool pk24, bool fast, bool *took)
+{
+    *took = false;
+    const RegionKnobs K = region_knobs();
+    if (n == 0 || nreg == 0 || nreg > IVX_MAXREG || !pk24 || !fast || K.two_pass || K.pack_off || K.lean_off) return IVX_OK;
+    hipStream_t st = ctx->stream;
+    ivx_routed R;
+    IVX_TRY(ivx_route_paged(ctx, jv, nreg, key, s, e, n, ivx_paged_opts{has_filter && !K.filter_off, true, true, true, 0u}, &R));
+    if (!lean_rows_ok(R)) return IVX_OK;
+    // the records: a cell per word of the page pool (ivx_route_paged's own size of it), the 8-byte array first
+    const u64 cells = ((n >> R.pt.lgpg) + nreg + 1) << R.pt.lgpg;
+    u8 *buf;
+    IVX_TRY(ctx->get_scratch(WS_T4, (size_t)cells * (out.score ? 12u : 4u), (void **)&buf));
+    SelOut rec{};
+    if (out.score) { rec.score = reinterpret_cast<i64 *>(buf); buf += cells * sizeof(i64); }
+    rec.idx = reinterpret_cast<u32 *>(buf);
+    sel_dispatch(by, val_bytes, out.score != nullptr, [&](auto b, auto vb, auto sc) {
+        constexpr int BY = decltype(b)::value, VB = decltype(vb)::value;
+        constexpr bool SC = decltype(sc)::value;
+        hipLaunchKernelGGL((k_sel_fast<IVX_AGG_B, BY, VB, SC>), dim3(RP_GRID * (IVX_RV_WPS / 4)), dim3(RP_T), 0, st, jv, R.se, (const u32 *)R.ctl->rcur,
+                           (const u32 *)R.ctl->cfirst, R.pt, R.rowbits, R.rest_rows, R.ctl->rest_n, val, rec);
+        hipLaunchKernelGGL((k_sel_rest<BY, VB, SC>), dim3(256), dim3(256), 0, st, jv, R.se, R.pt, (const u64 *)R.rest_rows, (const u32 *)R.ctl->rest_n, s, e,
+                           R.rowbits, val, rec);
+    });
+    IVX_HIP(ctx, hipGetLastError());
+    IVX_TRY(ivx_unroute_sel_records(ctx, R, nreg, n, rec, out));
     *took = true;
     return IVX_OK;
 }

@@ -814,9 +814,31 @@ __global__ __launch_bounds__(512) void k_unpermute_paged(const u64 *__restrict__
 // the page pool, at the word's own index; the tile's words are walked as above, once per wanted output: the output's records
 // are dropped at row - tile start in LDS, over the empty result's value for the rows that were never routed, and written out
 // in input order.  The words' second and later reads hit the cache (64 KB a tile).
-template <int TILE>
+// RECS says what the outputs are: io.each(pass) calls pass(an output's records, the caller's column, the value of a row that
+// was never routed) once per output.
+struct AggRecs {
+    AggOut rec, out;
+    template <class P> __device__ __forceinline__ void each(P &&pass) const
+    {
+        pass(rec.count, out.count, 0ull);
+        pass(rec.sum, out.sum, 0ull);
+        pass(rec.vmin, out.vmin, (u64)INT64_MAX);
+        pass(rec.vmax, out.vmax, (u64)INT64_MIN);
+        pass(rec.bases, out.bases, 0ull);
+        pass(rec.wsum, out.wsum, 0ull);
+    }
+};
+struct SelRecs {
+    SelOut rec, out;
+    template <class P> __device__ __forceinline__ void each(P &&pass) const
+    {
+        pass(rec.idx, out.idx, (u64)IVX_NULL_IDX);
+        pass(rec.score, out.score, 0ull);
+    }
+};
+template <int TILE, class RECS>
 __global__ __launch_bounds__(512) void k_unpermute_records(const u64 *__restrict__ pool, const uint2 *__restrict__ vtab, PageTab pt, u32 nreg, u32 rowbits,
-                                                           u64 n, AggOut rec, AggOut out)
+                                                           u64 n, RECS io)
 {
     constexpr int T = 512, ND = 256;
     __shared__ u64 s_val[TILE];
@@ -857,12 +879,7 @@ __global__ __launch_bounds__(512) void k_unpermute_records(const u64 *__restrict
         for (u32 t = tid; t < len; t += T) dst[t0 + t] = (E)s_val[t];
         __syncthreads();
     };
-    pass(rec.count, out.count, 0ull);
-    pass(rec.sum, out.sum, 0ull);
-    pass(rec.vmin, out.vmin, (u64)INT64_MAX);
-    pass(rec.vmax, out.vmax, (u64)INT64_MIN);
-    pass(rec.bases, out.bases, 0ull);
-    pass(rec.wsum, out.wsum, 0ull);
+    io.each(pass);
 }
 
 // two values per row back into input order: the un-permute above for (u32, i64) pairs with one-tile chunks; rows that
@@ -1235,11 +1252,22 @@ ivx_status ivx_unroute_pair(ivx_ctx *ctx, const ivx_routed &r, u64 n, const u32 
     return IVX_OK;
 }
 
-ivx_status ivx_unroute_records(ivx_ctx *ctx, const ivx_routed &R, u32 nreg, u64 n, const AggOut &rec, const AggOut &out)
+template <class RECS>
+static ivx_status unroute_records(ivx_ctx *ctx, const ivx_routed &R, u32 nreg, u64 n, const RECS &io)
 {
     if (R.form != IVX_ROWS_PAGED || R.vtab == nullptr || nreg > IVX_MAXREG) return ctx->fail(IVX_ERR_INVALID, "internal error: records are un-permuted from region pages with a tile table");
     constexpr u32 TILE = 512u * 16u;                                    // the one-pass partition's tile for packed rows
-    hipLaunchKernelGGL((k_unpermute_records<(int)TILE>), dim3((u32)((n + TILE - 1) / TILE)), dim3(512), 0, ctx->stream, R.se, R.vtab, R.pt, nreg, R.rowbits, n, rec, out);
+    hipLaunchKernelGGL((k_unpermute_records<(int)TILE, RECS>), dim3((u32)((n + TILE - 1) / TILE)), dim3(512), 0, ctx->stream, R.se, R.vtab, R.pt, nreg, R.rowbits, n, io);
     IVX_HIP(ctx, hipGetLastError());
     return IVX_OK;
+}
+
+ivx_status ivx_unroute_records(ivx_ctx *ctx, const ivx_routed &R, u32 nreg, u64 n, const AggOut &rec, const AggOut &out)
+{
+    return unroute_records(ctx, R, nreg, n, AggRecs{rec, out});
+}
+
+ivx_status ivx_unroute_sel_records(ivx_ctx *ctx, const ivx_routed &R, u32 nreg, u64 n, const SelOut &rec, const SelOut &out)
+{
+    return unroute_records(ctx, R, nreg, n, SelRecs{rec, out});
 }

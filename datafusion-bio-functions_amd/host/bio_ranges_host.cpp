@@ -2,6 +2,7 @@
 // (see include/bio_ranges_host.h).  Plain C++17; the only dependency is libivx_hip.so.
 #include "../../include/bio_ranges_host.h"
 #include "../../include/ivx.h"
+#include "../../include/ivx_select.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -575,19 +576,20 @@ extern "C" int brh_interval_join(brh_session *s, brh_batch build, brh_columns bc
 namespace {
 
 // the build side's value column, widened to what the device takes: int32 (Int8, Int16, Int32, UInt8, UInt16) or int64
-// (UInt32, Int64).  Everything else is refused by name
-int load_agg_values(brh_session *s, brh_batch t, const char *name, std::vector<int32_t> *v32, std::vector<int64_t> *v64, uint32_t *val_bytes)
+// (UInt32, Int64).  Everything else is refused by name, for the operator `op`
+int load_agg_values(brh_session *s, brh_batch t, const char *name, std::vector<int32_t> *v32, std::vector<int64_t> *v64, uint32_t *val_bytes,
+                    const std::string &op = "overlap_aggregate")
 {
     const int c = find_col(t.schema, name);
-    if (c < 0) return fail(s, "overlap_aggregate: value column '" + std::string(name) + "' not found in batch with columns: " + column_list(t.schema));
+    if (c < 0) return fail(s, op + ": value column '" + std::string(name) + "' not found in batch with columns: " + column_list(t.schema));
     const char *f = t.schema->children[c]->format;
-    const std::string what = "overlap_aggregate: unsupported data type " + std::string(f) + " for value column '" + name + "'";
+    const std::string what = op + ": unsupported data type " + std::string(f) + " for value column '" + name + "'";
     if (!std::strcmp(f, "L")) return fail(s, what + ": UInt64 values do not fit the Int64 aggregates");
     if (!std::strcmp(f, "e") || !std::strcmp(f, "f") || !std::strcmp(f, "g"))
         return fail(s, what + ": float values are not supported (their sums would not be bit-reproducible)");
     if (std::strlen(f) != 1 || !std::strchr("csilCSI", f[0])) return fail(s, what + "; expected Int8, Int16, Int32, Int64, UInt8, UInt16 or UInt32");
     const ArrowArray *a = t.array->children[c];
-    if (null_count(a) > 0) return fail(s, "overlap_aggregate: value column '" + std::string(name) + "' contains null values");
+    if (null_count(a) > 0) return fail(s, op + ": value column '" + std::string(name) + "' contains null values");
     const int64_t n = a->length, o = a->offset;
     const void *d = a->n_buffers >= 2 ? a->buffers[1] : nullptr;
     const bool wide = f[0] == 'l' || f[0] == 'I';
@@ -607,7 +609,76 @@ int load_agg_values(brh_session *s, brh_batch t, const char *name, std::vector<i
     return 0;
 }
 
+// overlap select's value column: a selection needs only the values' ORDER, so beside what load_agg_values takes (*exact: the
+// int64 the device compares IS the value) it takes UInt64 and Float32 / Float64 through a monotone map into int64 order
+// (*exact = false: the caller gets no score, it takes the value with build_idx).  UInt64: the top bit flipped.  Floats:
+// widened to double, the bits as int64 i, i ^= INT64_MAX when i < 0 -- the order of the reals with -0.0 below +0.0; a NaN
+// has no place in that order and is refused
+int load_sel_values(brh_session *s, brh_batch t, const char *name, std::vector<int32_t> *v32, std::vector<int64_t> *v64, uint32_t *val_bytes, bool *exact)
+{
+    static const std::string op = "overlap_select";
+    const int c = find_col(t.schema, name);
+    const char *f = c < 0 ? "" : t.schema->children[c]->format;
+    *exact = true;
+    if (!std::strcmp(f, "e")) return fail(s, op + ": unsupported data type e for value column '" + name + "': Float16 is not supported, cast it to Float32");
+    if (std::strcmp(f, "L") && std::strcmp(f, "f") && std::strcmp(f, "g")) return load_agg_values(s, t, name, v32, v64, val_bytes, op);
+    const ArrowArray *a = t.array->children[c];
+    if (null_count(a) > 0) return fail(s, op + ": value column '" + std::string(name) + "' contains null values");
+    const int64_t n = a->length, o = a->offset;
+    const void *d = a->n_buffers >= 2 ? a->buffers[1] : nullptr;
+    *exact = false;
+    *val_bytes = 8u;
+    v64->resize((size_t)n);
+    for (int64_t i = 0; i < n; i++) {
+        if (f[0] == 'L') { (*v64)[i] = (int64_t)(((const uint64_t *)d)[o + i] ^ 0x8000000000000000ull); continue; }
+        const double x = f[0] == 'f' ? (double)((const float *)d)[o + i] : ((const double *)d)[o + i];
+        if (x != x) return fail(s, op + ": value column '" + std::string(name) + "' contains NaN values");
+        int64_t bits;
+        std::memcpy(&bits, &x, sizeof bits);
+        (*v64)[i] = bits < 0 ? bits ^ INT64_MAX : bits;
+    }
+    return 0;
+}
+
 }  // namespace
+
+// ---- overlap select: join on overlap, keep the one best build row per probe row (ivx_select.h ivx_probe_overlap_select)
+extern "C" int brh_overlap_select(brh_session *s, brh_batch build, brh_columns bcols, const char *value_column,
+                                  brh_batch probe, brh_columns pcols, int strict_predicate, int by,
+                                  ArrowArray *build_idx, ArrowSchema *build_idx_schema, ArrowArray *score, ArrowSchema *score_schema)
+{
+    if (!s) return 1;
+    if (!build_idx || !build_idx_schema || !score || !score_schema) return fail(s, "overlap_select: null outputs");
+    if (by < 0 || by >= BRH_SEL_N) return fail(s, "overlap_select: by is one of the BRH_SEL_* criteria, got " + std::to_string(by));
+    const bool by_val = by == BRH_SEL_MIN_VAL || by == BRH_SEL_MAX_VAL;
+    if (by_val && !value_column) return fail(s, "overlap_select: the criterion selects by value and no value column is named");
+    if (!by_val && value_column) return fail(s, "overlap_select: value column '" + std::string(value_column) + "' given with a criterion that reads no value");
+    KeyDict kd; Side32 B, P;
+    std::vector<int32_t> v32; std::vector<int64_t> v64; uint32_t vb = 4; bool exact = true;
+    if (by_val && load_sel_values(s, build, value_column, &v32, &v64, &vb, &exact)) return 1;
+    if (build_keys(s, {{build, bcols}, {probe, pcols}}, &kd, true) || load_side32(s, build, bcols, &B) || load_side32(s, probe, pcols, &P)) return 1;
+    if (strict_predicate) {                                       // as brh_interval_join: end - 1 on both sides, and the lengths follow
+        for (auto &v : B.e) v = (int32_t)((uint32_t)v - 1u);
+        for (auto &v : P.e) v = (int32_t)((uint32_t)v - 1u);
+    }
+    const uint32_t nk = (uint32_t)std::max<size_t>(kd.names.size(), 1);
+    IndexGuard g;
+    ivx_status st = ivx_index_build(s->ctx, IVX_KIND_OVERLAP, IVX_MEM_HOST, kd.ids[0].data(), B.s.data(), B.e.data(), B.s.size(), nk, &g.ix);
+    if (st != IVX_OK) return fail_ivx(s, st);
+    const uint64_t np = P.s.size(), na = np ? np : 1;
+    std::vector<uint32_t> bi(na);
+    std::vector<int64_t> sc(exact ? na : 0);
+    const void *val = !by_val ? nullptr : vb == 4 ? (const void *)v32.data() : (const void *)v64.data();     // (may be null for an empty build side: never read)
+    st = ivx_probe_overlap_select(s->ctx, g.ix, IVX_MEM_HOST, kd.ids[1].data(), P.s.data(), P.e.data(), np, val, vb, by,
+                                  bi.data(), exact ? sc.data() : nullptr);
+    if (st != IVX_OK) return fail_ivx(s, st);
+    std::vector<uint8_t> valid(na);
+    for (uint64_t i = 0; i < np; i++) { valid[i] = bi[i] != IVX_NULL_IDX; if (!valid[i]) bi[i] = 0; }     // (a NULL slot's value)
+    make_primitive<uint32_t>(build_idx, bi.data(), (int64_t)np, valid.data()); make_schema(build_idx_schema, "I", "build_idx", true);
+    std::memset(score, 0, sizeof *score); std::memset(score_schema, 0, sizeof *score_schema);
+    if (exact) { make_primitive<int64_t>(score, sc.data(), (int64_t)np, valid.data()); make_schema(score_schema, "l", "score", true); }
+    return 0;
+}
 
 extern "C" int brh_overlap_aggregate(brh_session *s, brh_batch build, brh_columns bcols, const char *value_column,
                                      brh_batch probe, brh_columns pcols, int strict_predicate, uint32_t ops,

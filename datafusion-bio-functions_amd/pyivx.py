@@ -37,6 +37,10 @@ SYMBOLS = [
     "ivx_depth_profile_quantize", "ivx_depth_profile_hist", "ivx_intersect",
 ]
 
+# every symbol the companion headers declare (include/ivx_select.h; checked by tests/test_select_abi.py): entries that are
+# not in include/ivx.h yet, bound beside SYMBOLS the way the test hooks are
+EXT_SYMBOLS = ["ivx_probe_overlap_select"]
+
 # outputs one workgroup of the expand kernel makes (csrc/ivx_depth_expand.hip DEPTH_EXPAND_TILE; tests/test_depth_per_base_tile.py)
 DEPTH_EXPAND_TILE = 4096
 # merged steps one workgroup of the merge kernel makes (csrc/ivx_depth_merge.hip DEPTH_MERGE_TILE; tests/test_depth_merge_cpu.py)
@@ -66,6 +70,9 @@ CIGAR_TILE = 4096
 
 # outputs of ivx_probe_overlap_agg, in the order of its pointers, and their element types
 AGG_OUTPUTS = ("count", "sum", "min", "max", "bases", "wsum")
+
+# criteria of ivx_probe_overlap_select, in the order of the IVX_SEL_* enum (include/ivx_select.h)
+SEL_BY = ("min_val", "max_val", "max_overlap", "min_overlap", "first_row", "last_row")
 
 # slots of ivx_index_layout (include/ivx.h IVX_LAYOUT_*), in order
 LAYOUT_SLOTS = ["kind", "sh0", "nlev", "levrows", "rcells", "rcs", "nreg", "pk24", "slow", "fg", "fbits", "nroute_nreg", "lbuild"]
@@ -149,6 +156,9 @@ def lib():
         L.ivx_probe_overlap_agg.restype = C.c_int
         L.ivx_probe_overlap_agg.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 3 + [C.c_uint64, C.c_void_p, C.c_uint32] + [C.c_void_p] * 6
         L.ivx_depth.restype = C.c_int
+        L.ivx_probe_overlap_select.restype = C.c_int
+        L.ivx_probe_overlap_select.argtypes = ([C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 3 + [C.c_uint64, C.c_void_p, C.c_uint32, C.c_int] +
+                                               [C.c_void_p] * 2)
         L.ivx_depth.argtypes = ([C.c_void_p, C.c_int] + [C.c_void_p] * 6 + [C.c_uint64] + [C.c_void_p] * 4 + [C.c_uint64] +
                                 [C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32] + [C.c_void_p] * 4 +
                                 [C.c_uint64, C.POINTER(C.c_uint64)])
@@ -719,6 +729,41 @@ class Ctx:
         self._chk(lib().ivx_probe_overlap_agg(self.h, ix.h, mem, _ptr(key), _ptr(s), _ptr(e), n, _ptr(val), vb,
                                               *[_ptr(out[name]) for name in AGG_OUTPUTS]))
         return {name: out[name][:n] for name in AGG_OUTPUTS if out[name] is not None}
+
+    # ---- a3'''': overlap select ----
+    def overlap_select(self, ix, key, start, end, by="max_overlap", val=None, score=True):
+        """per probe row, of the build rows the join pairs it with, the one that is best by `by` (SEL_BY; ties: the smallest
+        build row) -> (build_idx, score): build_idx uint32, NULL_IDX without a match; score int64, the criterion's value at
+        the winner (0 without a match), or None with score=False.  `val` (one int32 or int64 per build row of `ix`) is read
+        by "min_val" / "max_val" only.  numpy arrays, or device tensors (build_idx then as its int32 bits)."""
+        key, s, e, n, mem = _cols(key, start, end, np.int32)
+        if by not in SEL_BY:
+            raise ValueError(f"overlap_select: by is one of {SEL_BY}, got {by!r}")
+        if val is not None and _is_torch(val) != (mem == MEM_DEVICE):
+            raise ValueError("mix of host and device buffers in one call")
+        vb = 8
+        if val is not None:
+            if mem == MEM_DEVICE:
+                import torch
+                if val.dtype not in (torch.int32, torch.int64) or not val.is_contiguous():
+                    raise ValueError("overlap_select: val is a contiguous int32 or int64 tensor")
+                vb = 4 if val.dtype == torch.int32 else 8
+            else:
+                val = np.asarray(val)
+                if val.dtype not in (np.dtype(np.int32), np.dtype(np.int64)):
+                    raise ValueError("overlap_select: val is an int32 or int64 array")
+                val = np.ascontiguousarray(val)
+                vb = val.dtype.itemsize
+        if mem == MEM_DEVICE:
+            import torch
+            bi = torch.empty(max(n, 1), dtype=torch.int32, device=s.device)
+            sc = torch.empty(max(n, 1), dtype=torch.int64, device=s.device) if score else None
+        else:
+            bi = np.empty(max(n, 1), np.uint32)
+            sc = np.empty(max(n, 1), np.int64) if score else None
+        self._chk(lib().ivx_probe_overlap_select(self.h, ix.h, mem, _ptr(key), _ptr(s), _ptr(e), n, _ptr(val), vb, SEL_BY.index(by),
+                                                 _ptr(bi), _ptr(sc)))
+        return bi[:n], (sc[:n] if score else None)
 
     def bits_mark(self, idx, bits, n_bits):
         """OR bit idx[i] into `bits` (NULL_IDX skipped, anything else >= n_bits raises ERR_INVALID); -> bits"""

@@ -119,6 +119,27 @@ int brh_overlap_aggregate(brh_session *s, brh_batch build, brh_columns bcols, co
                           brh_batch probe, brh_columns pcols, int strict_predicate, uint32_t ops,
                           struct ArrowArray *out, struct ArrowSchema *out_schema);
 
+/* Overlap select: join `probe` to `build` on overlap and keep, per probe row, the ONE build row that is best by `by` -- "assign
+ * each read to the gene it overlaps most", the highest-scoring feature under each target, bedtools map -o first / last, SQL's
+ * ROW_NUMBER() OVER (PARTITION BY the probe row ORDER BY ...) = 1 -- in one ivx_probe_overlap_select call (ivx_select.h): no
+ * pair is ever made.  The reference has no counterpart.  Tables, keys and strict_predicate as in brh_overlap_aggregate (the
+ * overlap lengths are those of the adjusted coordinates).  Ties go to the smallest build row.
+ * by: a BRH_SEL_* criterion (numbered like IVX_SEL_*).  value_column is named for BRH_SEL_MIN_VAL / BRH_SEL_MAX_VAL and for
+ * them only: one that is missing, or given with another criterion, is refused with its own message.  It is Int8 .. Int64 or
+ * UInt8 .. UInt32 (as brh_overlap_aggregate), UInt64 (compared with the top bit flipped), or Float32 / Float64 (widened to
+ * double and compared in the order of the reals, -0.0 below +0.0; a NaN anywhere is refused by name); nulls are refused.
+ * Outputs, one row per probe row in probe order:
+ *   build_idx  UInt32, NULL where the probe row overlaps nothing: what a take of the build table wants for a left join to at
+ *              most one row
+ *   score      Int64, NULL where build_idx is: the criterion at the winner -- its value, the closed overlap length, or the
+ *              row.  For a UInt64 or float value column the slot stays released (zeroed): take the value with build_idx. */
+enum { BRH_SEL_MIN_VAL = 0, BRH_SEL_MAX_VAL = 1, BRH_SEL_MAX_OVERLAP = 2, BRH_SEL_MIN_OVERLAP = 3,
+       BRH_SEL_FIRST_ROW = 4, BRH_SEL_LAST_ROW = 5, BRH_SEL_N = 6 };
+int brh_overlap_select(brh_session *s, brh_batch build, brh_columns bcols, const char *value_column /* nullable */,
+                       brh_batch probe, brh_columns pcols, int strict_predicate, int by,
+                       struct ArrowArray *build_idx, struct ArrowSchema *build_idx_schema,
+                       struct ArrowArray *score, struct ArrowSchema *score_schema);
+
 /* merge('table'[,min_dist]...): MergeProvider/MergeStream (R/src/merge.rs:84-112, :263-350).
  * Outputs contig Utf8, start Int64, end Int64, n_intervals Int64. */
 int brh_merge(brh_session *s, brh_batch table, brh_columns cols, int64_t min_dist, int filter_op,
