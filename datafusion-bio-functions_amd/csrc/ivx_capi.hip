@@ -537,6 +537,18 @@ static bool rowval_routed_ok(u64 n)
     return n >= (1u << 21);
 }
 
+// Big batches of a per-row operator take the region path (nreg: one partition pass must do) from min_rows rows on;
+// IVX_JOIN_PATH overrides the size rule (tests: "direct" | "regions")
+static bool region_path_wanted(const ivx_index *ix, u64 n, u64 min_rows)
+{
+    const bool can = ix->jv_nreg > 0 && ix->jv_nreg <= IVX_MAXREG_WIDE;
+    if (const char *p = getenv("IVX_JOIN_PATH")) {
+        if (!strcmp(p, "direct")) return false;
+        if (!strcmp(p, "regions")) return can;
+    }
+    return can && n >= min_rows;
+}
+
 static ivx_status overlap_common(ivx_ctx *ctx, const ivx_index *ix, int mem, int mode,
                                  const u32 *key, const i32 *start, const i32 *end, u64 n,
                                  u32 *per_row, u8 *exists, u32 *bidx, u32 *pidx, u64 cap, u64 *total)
@@ -549,13 +561,10 @@ static ivx_status overlap_common(ivx_ctx *ctx, const ivx_index *ix, int mem, int
     // small batches and the per-row modes gather straight from the index
     bool regions = ix->jv_nreg > 0 && (mode == JP_COUNT || mode == JP_FILL) && n >= (1u << 21);   // measured crossover (tools/crossover.py)
     // the per-row modes (rle_right, semi / anti) of big batches: same partition, one value per row, un-permuted
-    bool rowval = ix->jv_nreg > 0 && ix->jv_nreg <= IVX_MAXREG_WIDE && (mode == JP_PER_ROW || mode == JP_EXISTS) && n >= (1u << 21);
+    const bool rowval = (mode == JP_PER_ROW || mode == JP_EXISTS) && region_path_wanted(ix, n, 1u << 21);
     if (const char *p = getenv("IVX_JOIN_PATH")) {
-        if (!strcmp(p, "direct")) regions = rowval = false;
-        else if (!strcmp(p, "regions")) {
-            regions = ix->jv_nreg > 0 && (mode == JP_COUNT || mode == JP_FILL);
-            rowval = ix->jv_nreg > 0 && ix->jv_nreg <= IVX_MAXREG_WIDE && (mode == JP_PER_ROW || mode == JP_EXISTS);
-        }
+        if (!strcmp(p, "direct")) regions = false;
+        else if (!strcmp(p, "regions")) regions = ix->jv_nreg > 0 && (mode == JP_COUNT || mode == JP_FILL);
     }
     // a fill call right after the count call that sized it: the routed probe rows are still in the context
     const void *in[3] = {key, start, end};
@@ -827,7 +836,7 @@ extern "C" ivx_status ivx_probe_exists(ivx_ctx *ctx, const ivx_index *ix, int me
 // ---------------------------------------------------------------- a3'': build-side match marks
 
 // Beside overlap_common: the same two ways through the index, the match recorded by BUILD row.  Big batches over a lean
-// index (the form ivx_rowval_probe_regions runs k_rv_fast on) take the region kernel; everything else the direct one.
+// index (the form ivx_rowval_probe_regions runs k_lean on) take the region kernels; everything else the direct one.
 extern "C" ivx_status ivx_probe_mark_build(ivx_ctx *ctx, const ivx_index *ix, int mem, const uint32_t *key,
                                            const int32_t *start, const int32_t *end, uint64_t n, uint32_t *marks)
 {
@@ -838,12 +847,7 @@ extern "C" ivx_status ivx_probe_mark_build(ivx_ctx *ctx, const ivx_index *ix, in
     f.drop_join_plan();                                     // as any other call between a count call and its fill
     const u64 nw = (ix->n + 31) / 32;
     if (n == 0 || nw == 0) return IVX_OK;
-    // thresholds and override of overlap_common's per-row branch
-    bool regions = ix->jv_nreg > 0 && ix->jv_nreg <= IVX_MAXREG_WIDE && n >= (1u << 21);
-    if (const char *p = getenv("IVX_JOIN_PATH")) {
-        if (!strcmp(p, "direct")) regions = false;
-        else if (!strcmp(p, "regions")) regions = ix->jv_nreg > 0 && ix->jv_nreg <= IVX_MAXREG_WIDE;
-    }
+    const bool regions = region_path_wanted(ix, n, 1u << 21);             // the threshold of overlap_common's per-row branch
     const u32 *dk = f.in(key, n);
     const i32 *ds = f.in(start, n), *de = f.in(end, n);
     u32 *dm = f.out_or(marks, nw);
@@ -879,13 +883,8 @@ extern "C" ivx_status ivx_probe_overlap_agg(ivx_ctx *ctx, const ivx_index *ix, i
     f.meter(false, n);
     f.drop_join_plan();                                     // as any other call between a count call and its fill
     if (n == 0) return IVX_OK;
-    // the override of ivx_probe_mark_build, thresholds of its own
     const int n64 = (sum != nullptr) + (vmin != nullptr) + (vmax != nullptr) + (bases != nullptr) + (wsum != nullptr);
-    bool regions = ix->jv_nreg > 0 && ix->jv_nreg <= IVX_MAXREG_WIDE && n >= agg_regions_rows(n64);
-    if (const char *p = getenv("IVX_JOIN_PATH")) {
-        if (!strcmp(p, "direct")) regions = false;
-        else if (!strcmp(p, "regions")) regions = ix->jv_nreg > 0 && ix->jv_nreg <= IVX_MAXREG_WIDE;
-    }
+    const bool regions = region_path_wanted(ix, n, agg_regions_rows(n64));
     const u32 *dk = f.in(key, n);
     const i32 *ds = f.in(start, n), *de = f.in(end, n);
     const void *dv = f.in((const u8 *)val, (u64)ix->n * val_bytes);
@@ -929,12 +928,7 @@ extern "C" ivx_status ivx_probe_overlap_select(ivx_ctx *ctx, const ivx_index *ix
     f.meter(false, n);
     f.drop_join_plan();                                     // as any other call between a count call and its fill
     if (n == 0) return IVX_OK;
-    // the override of ivx_probe_overlap_agg, a threshold of its own
-    bool regions = ix->jv_nreg > 0 && ix->jv_nreg <= IVX_MAXREG_WIDE && n >= sel_regions_rows();
-    if (const char *p = getenv("IVX_JOIN_PATH")) {
-        if (!strcmp(p, "direct")) regions = false;
-        else if (!strcmp(p, "regions")) regions = ix->jv_nreg > 0 && ix->jv_nreg <= IVX_MAXREG_WIDE;
-    }
+    const bool regions = region_path_wanted(ix, n, sel_regions_rows());
     const u32 *dk = f.in(key, n);
     const i32 *ds = f.in(start, n), *de = f.in(end, n);
     const void *dv = by_val ? f.in((const u8 *)val, (u64)ix->n * val_bytes) : nullptr;      // (the other criteria stage nothing of val)

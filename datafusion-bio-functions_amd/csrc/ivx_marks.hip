@@ -5,37 +5,17 @@
 // ever OR into it, with device-scope atomics behind a plain test of the word (mark_bit, ivx_join.hpp), so several
 // streams and contexts may mark into one buffer at once.
 //
-//   k_probe_mark   the direct path: k_probe_overlap's row loop and walk, the match sets the build row's bit.  Any index,
-//                  any batch size; what small batches take.  (Big batches over a lean index: k_mark_fast / k_mark_rest in
-//                  ivx_regions_probe.hip.)
+//   ivx_mark_probe the direct path: MarkOp on k_probe_rows (ivx_rowops.hpp), the match sets the build row's bit.  Any index,
+//                  any batch size; what small batches take.  (Big batches over a lean index: the same operator on k_lean /
+//                  k_lean_rest in ivx_regions_probe.hip.)
 //   k_bits_mark    OR bit idx[i] for a list of row numbers (Left / Full joins: the pairs exist anyway)
 //   k_bits_count / k_bits_write   ivx_bits_select: positions of the set (or clear) bits, ascending -- popcount per 256-word
 //                  block, exclusive scan of the block counts, then every lane expands its word at block base + prefix.
-#include "ivx_join.hpp"
+#include "ivx_rowops.hpp"
 
 namespace {
 
 constexpr int MT = 256;     // workgroup of every kernel here
-constexpr int MI = 4;       // probe rows per thread per tile of a big batch (as k_probe_overlap's PI)
-
-// MI_: probe rows per thread per tile; a DataFusion-sized batch takes ONE row per thread (see k_probe_overlap)
-template <int MI_>
-__global__ __launch_bounds__(MT) void k_probe_mark(JoinIndexView ix, const u32 *__restrict__ pkey, const i32 *__restrict__ ps,
-                                                   const i32 *__restrict__ pe, u64 n, u32 *marks)
-{
-    const u32 sh0 = ix.hdr[HDR_SH0], nlev = ix.hdr[HDR_NLEV];
-    constexpr int TILE_ = MT * MI_;
-    const u64 ntiles = (n + TILE_ - 1) / TILE_;
-    for (u64 tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-#pragma unroll
-        for (int it = 0; it < MI_; it++) {
-            const u64 i = tile * TILE_ + (u64)it * MT + threadIdx.x;
-            if (i >= n) continue;
-            const u32 k = pkey ? pkey[i] : 0u;                      // (a key id the build side does not have: walk_ent leaves at once)
-            walk(ix, sh0, 0, nlev, k, ps[i], pe[i], [&](u32 row) { mark_bit(marks, row); });
-        }
-    }
-}
 
 __global__ __launch_bounds__(MT) void k_bits_mark(const u32 *__restrict__ idx, u64 n, u32 *bits, u64 n_bits, u32 *bad)
 {
@@ -83,13 +63,7 @@ __global__ __launch_bounds__(MT) void k_bits_write(const u32 *__restrict__ bits,
 
 ivx_status ivx_mark_probe(ivx_ctx *ctx, const JoinIndexView &jv, const u32 *key, const i32 *s, const i32 *e, u64 n, u32 *marks)
 {
-    if (n == 0) return IVX_OK;
-    const bool small = n <= (1u << 18);                                // one row per thread, as ivx_join_probe
-    const u32 grid = small ? (u32)((n + MT - 1) / MT) : ivx_stream_grid(n, MT * MI, 256 * 8);
-    if (small) hipLaunchKernelGGL((k_probe_mark<1>), dim3(grid), dim3(MT), 0, ctx->stream, jv, key, s, e, n, marks);
-    else hipLaunchKernelGGL((k_probe_mark<MI>), dim3(grid), dim3(MT), 0, ctx->stream, jv, key, s, e, n, marks);
-    IVX_HIP(ctx, hipGetLastError());
-    return IVX_OK;
+    return ivx_direct_probe(ctx, jv, key, s, e, n, MarkOp{{}, marks});
 }
 
 ivx_status ivx_bits_mark_device(ivx_ctx *ctx, const u32 *idx, u64 n, u32 *bits, u64 n_bits)

@@ -5,7 +5,7 @@
 #include <type_traits>
 #include <cstdlib>
 #include <cstring>
-#include "ivx_join.hpp"
+#include "ivx_rowops.hpp"
 
 // PK (8-byte routed rows, hdr[HDR_PK24]): a routed row is ONE word,
 //     bits  0..23  start inside its region          bits 24..31  length (end - start), low 8 bits
@@ -40,7 +40,6 @@ __device__ __forceinline__ W *routed_word(const PageTab &pt, W *pool, u32 r, u32
     return pool + (((u64)(pg - 1u) << pt.lgpg) + (v & ((1u << pt.lgpg) - 1u)));
 }
 
-constexpr int RP_T = 1024;                 // probe kernels: one workgroup per CU (LDS-bound), 16 wavefronts
 constexpr int RP_W = RP_T / IVX_WAVE;
 // the lean probes deal their work in CHUNKS of 8192 routed rows that never straddle a pool page (k_chunk_bounds, k_fill_fast)
 constexpr u32 FP_CHUNK = (u32)RP_W * IVX_WAVE * 8u;
@@ -52,15 +51,6 @@ constexpr u32 FP_CHUNK = (u32)RP_W * IVX_WAVE * 8u;
 struct FpRest { u32 r, first, cnt, pad; };
 // the two lists live in one scratch buffer: batches first (at most one per wavefront batch), then single rows (at most n)
 __host__ __device__ __forceinline__ u64 fp_max_batches(u64 n, u32 nreg) { return ((n >> 13) + nreg + 1) * (u64)(RP_W * 8); }
-
-// run-time bools as template arguments: f(std::true_type / std::false_type ...), one per bool, in order
-template <class F> inline void with_bools(F &&f) { f(); }
-template <class F, class... B> inline void with_bools(F &&f, bool b, B... rest)
-{
-    if (b) with_bools([&](auto... t) { f(std::true_type{}, t...); }, rest...);
-    else with_bools([&](auto... t) { f(std::false_type{}, t...); }, rest...);
-}
-#define IVX_B(tag) (decltype(tag)::value)
 
 // ------------------------------------------------------------------ routing (ivx_regions_route.hip)
 // Each fills in *R (and R->slots); none waits for an index's `ready` event: all they read of the index is final before a

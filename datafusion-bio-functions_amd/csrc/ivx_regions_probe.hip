@@ -8,8 +8,9 @@
 //                     Rows longer than the slice halo, regions whose slice exceeds LDS and the long-interval levels
 //                     fall back to global reads inside the same kernel.
 //   k_fill_fast/_rest the lean fill for the case the headline always meets: packed rows in pages, every region one
-//   k_rv_fast/_rest   LDS-resident level; the same for per-row values
-//   k_mark_fast/_rest ... and for the build-side match marks: the matched slice entries in an LDS bitmap, flushed per region
+//                     LDS-resident level
+//   k_lean/_rest      the same for the per-row operators (ivx_rowops.hpp): per-row values, build-side match marks, overlap
+//                     aggregates, overlap select -- one kernel pair, instantiated per operator
 //   k_probe_dense     match-dense fill: count the 64-row pieces, scan, write
 //   k_pick_rows       rows per lane of the fill, decided on the device when the routed row count is known only there
 //
@@ -18,7 +19,7 @@
 // FILL call that follows: ivx_join_plan), ivx_rowval_probe_regions (one value per probe row, in input order) and
 // ivx_mark_probe_regions (one bit per matched BUILD row, ORed into the caller's bitmap; lean form only),
 // ivx_agg_probe_regions (per probe row, aggregates of a build-side value column; lean form only) and
-// ivx_sel_probe_regions (per probe row, the best matching build row by a criterion: k_sel_fast/_rest; lean form only).
+// ivx_sel_probe_regions (per probe row, the best matching build row by a criterion; lean form only).
 //
 // HBM traffic per probe row behind the routing: 12 B or 8 B (probe) + 8 B per pair, all streaming (measured:
 // profiles/r1_d_regions_pipeline_pmc.txt).
@@ -36,13 +37,9 @@ namespace {
 #ifndef IVX_RP_RING
 #define IVX_RP_RING 512
 #endif
-#ifndef IVX_RP_ECAP
-#define IVX_RP_ECAP 6144
-#endif
 constexpr int RP_B = IVX_RP_B;             // probe rows per lane per wavefront batch (fill: 8, 4, 2 or 1 by match density)
 constexpr u32 RP_HALO = IVX_RP_HALO;       // slice cells past the region's last cell
 constexpr u32 RP_CCAP = 8192 + RP_HALO + 2;
-constexpr u32 RP_ECAP = IVX_RP_ECAP;       // entries staged per slice
 constexpr u32 RP_RING = IVX_RP_RING;       // per-wavefront ring of staged pairs: two consecutive rounds must fit (power of two)
 constexpr u32 RP_NSLOT = 4;                // rounds whose reservation state is kept (see round_publish)
 constexpr u32 RP_NPG = 64;                 // page ids of one region segment kept in LDS (paged rows)
@@ -278,17 +275,7 @@ __device__ __forceinline__ void batch_write_direct(const Slice &S, const ProbeLd
     }
 }
 
-// Per-row-output operators on the same slices: the row's value instead of its pairs.
-//   RV_COUNT     count_overlaps: 0 if qe < qs (interval_tree.rs:42-44), else the number of build rows the
-//                literal predicate matches -- equal to #{starts <= qe} - #{ends < qs} (:45-48) whenever no
-//                build row has end < start, which is when the host takes this path
-//   RV_COVERAGE  get_coverage over the merged nodes: sum of max(1, min(qe+1, last) - max(qs-1, first)) in
-//                wrapping i32 arithmetic (:145-152)
-enum { RV_COUNT = 2, RV_COVERAGE = 3, RV_MATCHES = 4 };   // RV_MATCHES: the join's rle_right / exists (plain match count)
-
-__device__ __forceinline__ i32 rv_wadd(i32 a, i32 b) { return (i32)((u32)a + (u32)b); }
-__device__ __forceinline__ i32 rv_wsub(i32 a, i32 b) { return (i32)((u32)a - (u32)b); }
-
+// Per-row values (RV_*: ivx_rowops.hpp) on the same slices: the row's value instead of its pairs.
 template <int KIND, int B, bool PK = false>
 __device__ __forceinline__ void batch_rowval(const Slice &S, const i32 (&qs)[B], const i32 (&qe)[B], u32 okmask, u32 (&val)[B],
                                              const u32 (&rel)[B], const u32 (&len)[B], u32 relmask)
@@ -607,13 +594,14 @@ __global__ __launch_bounds__(RP_T) void k_probe_regions(JoinIndexView ix, const 
     if (FILL && round) round_copy_out(L, pend_mine, pend_start, round - 1, wv, ob, op, cap);
 }
 
-// ------------------------------------------------------------------ lean probes: what the three kernels share
-// k_fill_fast, k_rv_fast and k_mark_fast serve the case the headline always meets: packed 8-byte rows in region pages
-// (k_part_onepass) and an index whose every region is one LDS-resident level (hdr[HDR_FAST]).  They share how a workgroup
-// gets its rows (LeanRows), how a row finds its cell range in the staged slice (lean_cells) and what happens to a row the
-// packed form cannot carry (lean_list_slow, and rest_row in the *_rest kernels that walk the listed rows afterwards with
-// the generic walk over the index in global memory -- the lean kernels hold no generic code, and no scratch).  A kernel
-// itself is its LDS, what it does when the region changes and what it does with a row's candidates.
+// ------------------------------------------------------------------ lean probes: what the lean kernels share
+// k_fill_fast and k_lean serve the case the headline always meets: packed 8-byte rows in region pages (k_part_onepass) and
+// an index whose every region is one LDS-resident level (hdr[HDR_FAST]).  They share how a workgroup gets its rows
+// (LeanRows), how a row finds its cell range in the staged slice (lean_cells) and what happens to a row the packed form
+// cannot carry (lean_list_slow, and rest_row in the *_rest kernels that walk the listed rows afterwards with the generic
+// walk over the index in global memory -- the lean kernels hold no generic code, and no scratch).  The fill is a kernel of
+// its own (a ring, rounds); every per-row operator is k_lean with its LDS, what it does when the region changes and what it
+// does with a row's candidates filled in.
 
 // The rows of a workgroup, batch by batch.  Work is dealt in CHUNKS of 8192 routed rows that never straddle a pool page
 // (chunk k of region r = its virtual rows [8192 k, 8192 (k + 1)); wavefront w owns rows [512 w, 512 (w + 1)) of it), so the
@@ -1007,195 +995,35 @@ __global__ __launch_bounds__(256) void k_fill_rest(JoinIndexView ix, const u64 *
     }
 }
 
-// ------------------------------------------------------------------ lean per-row-value probe
-// count_overlaps / the join's rle_right and exists (RV_COUNT, RV_MATCHES) and coverage (RV_COVERAGE) over LeanRows and
-// lean_cells, without a ring, rounds or any synchronisation between wavefronts: nothing happens when the region changes but
-// the slice load, and a row's value replaces the low half of its packed word in place, as in k_probe_regions<RV_*>.  Rows the
-// packed form cannot carry are listed (region, virtual row) and valued by k_rv_rest.
+// ------------------------------------------------------------------ lean per-row operators
+// A per-row operator Op (ivx_rowops.hpp: RvOp, MarkOp, AggOp, SelOp) over LeanRows and lean_cells, without a ring, rounds or
+// any synchronisation between wavefronts: when the region changes, the slice load between Op's leave and enter; per row, the
+// candidate loop over the staged entries, Op::Row::hit for a match, Op::Row::done for the row.  Rows the packed form cannot
+// carry are listed (region, virtual row) and k_lean_rest walks them.
 #ifndef IVX_RV_WPS
 #define IVX_RV_WPS 4
 #endif
 #ifndef IVX_RV_B
 #define IVX_RV_B 8
 #endif
-template <int KIND, int B>
-__global__ __launch_bounds__(RP_T, IVX_RV_WPS) void k_rv_fast(JoinIndexView ix, u64 *__restrict__ pool, const u32 *__restrict__ rcur, const u32 *__restrict__ cfirst,
-                                                  PageTab pt, u32 rowbits, u64 *__restrict__ rest_rows, u32 *rest_n)
-{
-    __shared__ unsigned short s_off[RP_CCAP];
-    __shared__ u64 s_ent[RP_ECAP];
-    __shared__ u32 s_cfirst[IVX_MAXREG_WIDE + 2];
-    ProbeLds L{s_off, s_ent, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    const u32 ln = lane_id();
-    auto miss = []() {};                                                 // (a page never published: stay in bounds, silently)
-    LeanRows<B, u64> rows;
-    if (!rows.init(ix, s_cfirst, cfirst, rcur, pt, pool, rowbits)) return;
-    Slice S;
-    slice_init(ix, S, L);
-    rows.start(miss);
-    u32 loaded_r = 0xFFFFFFFFu;
-    for (u32 i = 0; i < rows.nbatch; i++) {
-        const u32 r = rows.r;
-        if (r != loaded_r) { slice_load(ix, S, L, r, true); loaded_r = r; }
-        u32 rel[B], len[B], roww[B];                                     // (roww: the un-permute masks the row id out of it)
-        const auto bt = rows.take(i, rel, len, roww, miss);
-        u64 *dst = bt.src;
-        const i32 rbase = S.rbase;
-        u32 ca[B], cb[B], slow, okm;
-        lean_cells<B>(S, rel, len, rows.maxlen, bt.cnt, ln, ca, cb, slow, okm);
-#pragma unroll
-        for (int q = 0; q < B; q++) {
-            const i32 qs = (i32)((u32)rbase + rel[q]), qe = (i32)((u32)qs + len[q]);
-            const i32 ca1 = rv_wadd(qe, 1), cb1 = rv_wsub(qs, 1);        // coverage: the closed query grown by one on either side
-            u32 v = 0;
-            for (u32 j = ca[q]; j < cb[q]; j++) {
-                const u64 x = s_ent[j];
-                const i32 xs = (i32)(u32)x, xe = (i32)(u32)(x >> 32);
-                if (xs <= qe && xe >= qs) {
-                    if (KIND == RV_COVERAGE) { const i32 d = rv_wsub(ca1 < xe ? ca1 : xe, cb1 > xs ? cb1 : xs); v = (u32)rv_wadd((i32)v, d > 1 ? d : 1); }
-                    else v++;
-                }
-            }
-            if ((okm >> q) & 1u) dst[q * IVX_WAVE + ln] = (u64)v | ((u64)roww[q] << 32);
-        }
-        if (__builtin_expect(slow != 0, 0)) lean_list_slow<B>(slow, r, bt.first, ln, rest_rows, rest_n);
-    }
-}
-
-template <int KIND>
-__global__ __launch_bounds__(256) void k_rv_rest(JoinIndexView ix, u64 *__restrict__ pool, PageTab pt, const u64 *__restrict__ rest_rows,
-                                                 const u32 *__restrict__ rest_n, const i32 *__restrict__ ps_in, const i32 *__restrict__ pe_in,
-                                                 u32 rowbits, u32 adj)
-{
-    const u32 nrow = rest_n[1];
-    const u32 sh0 = ix.hdr[HDR_SH0], nlev = ix.hdr[HDR_NLEV];
-    for (u32 i = blockIdx.x * blockDim.x + threadIdx.x; i < nrow; i += gridDim.x * blockDim.x) {
-        const u64 ent = rest_rows[i];
-        const u32 r = (u32)(ent >> 32);
-        const auto e = rest_row(ix, pt, pool, r, (u32)ent, rowbits, ps_in, pe_in, adj, []() {});
-        const i32 qs = e.qs, qe = e.qe;
-        u32 v = 0;
-        if (KIND == RV_COVERAGE) {
-            const i32 a = rv_wadd(qe, 1), b = rv_wsub(qs, 1);
-            walk_ent(ix, sh0, 0, nlev, ix.rkey[r], qs, qe, [&](const ivx_ent &n) {
-                const i32 d = rv_wsub(a < n.e ? a : n.e, b > n.s ? b : n.s);
-                v = (u32)rv_wadd((i32)v, d > 1 ? d : 1);
-            });
-        } else if (KIND != RV_COUNT || !(qe < qs)) {
-            walk_ent(ix, sh0, 0, nlev, ix.rkey[r], qs, qe, [&](const ivx_ent &) { v++; });
-        }
-        *e.slot = (u64)v | ((u64)e.hi << 32);
-    }
-}
-
-// ------------------------------------------------------------------ lean build-side marks
-// Which BUILD rows a big batch matched (ivx_probe_mark_build), over LeanRows and lean_cells -- but nothing is written back
-// per probe row.  Beside the slice the workgroup keeps one bit per slice entry in LDS (RP_ECAP bits); a match ORs bit j, its
-// slice entry, with one LDS atomic.  When the workgroup leaves a region, and at the end of its share, it sweeps the LDS
-// words: every set bit is a matched entry, whose build row (read from ix.ent, the slice stages no row ids) gets its bit in
-// the caller's bitmap by test-then-OR, and the LDS word is cleared.  Global atomics are then per distinct matched build row
-// and workgroup visit, not per match (the headline: ~37 matches per build row).  Rows the packed form cannot carry are
-// listed as in k_rv_fast; k_mark_rest marks for them.
-template <int B>
-__global__ __launch_bounds__(RP_T, IVX_RV_WPS) void k_mark_fast(JoinIndexView ix, const u64 *__restrict__ pool, const u32 *__restrict__ rcur, const u32 *__restrict__ cfirst,
-                                                    PageTab pt, u32 rowbits, u64 *__restrict__ rest_rows, u32 *rest_n, u32 *marks)
-{
-    constexpr u32 NBW = RP_ECAP / 32u;
-    static_assert(RP_ECAP % 32u == 0, "one LDS bit per slice entry, whole words");
-    __shared__ unsigned short s_off[RP_CCAP];
-    __shared__ u64 s_ent[RP_ECAP];
-    __shared__ u32 s_cfirst[IVX_MAXREG_WIDE + 2];
-    __shared__ u32 s_bits[NBW];
-    ProbeLds L{s_off, s_ent, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    const u32 ln = lane_id();
-    for (u32 t = threadIdx.x; t < NBW; t += RP_T) s_bits[t] = 0u;        // (the barrier behind it is init's)
-    auto miss = []() {};                                                 // (a page never published: stay in bounds, silently)
-    LeanRows<B, const u64> rows;
-    if (!rows.init(ix, s_cfirst, cfirst, rcur, pt, pool, rowbits)) return;
-    Slice S;
-    slice_init(ix, S, L);
-    rows.start(miss);
-    // the matched entries of the region just left: to the caller's bitmap, LDS words back to zero (all threads; the
-    // slice_load or the kernel's end that follows brings the barrier behind the sweep)
-    auto flush = [&]() {
-        __syncthreads();
-        for (u32 w = threadIdx.x; w < NBW; w += RP_T) {
-            u32 m = s_bits[w];
-            if (m == 0u) continue;
-            s_bits[w] = 0u;
-            do {
-                const u32 j = (w << 5) + (u32)__builtin_ctz(m);
-                m &= m - 1u;
-                mark_bit(marks, ix.ent[S.e0 + j].row);
-            } while (m);
-        }
-    };
-    u32 loaded_r = 0xFFFFFFFFu;
-    for (u32 i = 0; i < rows.nbatch; i++) {
-        const u32 r = rows.r;
-        if (r != loaded_r) {
-            if (loaded_r != 0xFFFFFFFFu) flush();
-            slice_load(ix, S, L, r, true);
-            loaded_r = r;
-        }
-        u32 rel[B], len[B], roww[B];                                     // (roww: not used, no probe row is named here)
-        const auto bt = rows.take(i, rel, len, roww, miss);
-        const i32 rbase = S.rbase;
-        u32 ca[B], cb[B], slow, okm;
-        lean_cells<B>(S, rel, len, rows.maxlen, bt.cnt, ln, ca, cb, slow, okm);
-#pragma unroll
-        for (int q = 0; q < B; q++) {
-            const i32 qs = (i32)((u32)rbase + rel[q]), qe = (i32)((u32)qs + len[q]);
-            for (u32 j = ca[q]; j < cb[q]; j++) {
-                const u64 x = s_ent[j];
-                if ((i32)(u32)x <= qe && (i32)(u32)(x >> 32) >= qs)
-                    __hip_atomic_fetch_or(&s_bits[j >> 5], 1u << (j & 31u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            }
-        }
-        if (__builtin_expect(slow != 0, 0)) lean_list_slow<B>(slow, r, bt.first, ln, rest_rows, rest_n);
-    }
-    flush();
-}
-
-__global__ __launch_bounds__(256) void k_mark_rest(JoinIndexView ix, const u64 *__restrict__ pool, PageTab pt, const u64 *__restrict__ rest_rows,
-                                                   const u32 *__restrict__ rest_n, const i32 *__restrict__ ps_in, const i32 *__restrict__ pe_in,
-                                                   u32 rowbits, u32 *marks)
-{
-    const u32 nrow = rest_n[1];
-    const u32 sh0 = ix.hdr[HDR_SH0], nlev = ix.hdr[HDR_NLEV];
-    for (u32 i = blockIdx.x * blockDim.x + threadIdx.x; i < nrow; i += gridDim.x * blockDim.x) {
-        const u64 ent = rest_rows[i];
-        const u32 r = (u32)(ent >> 32);
-        const auto e = rest_row(ix, pt, pool, r, (u32)ent, rowbits, ps_in, pe_in, 0u, []() {});
-        walk(ix, sh0, 0, nlev, ix.rkey[r], e.qs, e.qe, [&](u32 brow) { mark_bit(marks, brow); });
-    }
-}
-
-// ------------------------------------------------------------------ lean overlap aggregates
-// Per probe row, aggregates of a build-side value over the row's matches (ivx_probe_overlap_agg), over LeanRows and lean_cells
-// as k_rv_fast.  Beside the slice the workgroup stages the slice's VALUES in LDS at slice load, s_val[j] = val[row of slice
-// entry j] (the slice stages no row ids: ix.ent again, as k_mark_fast's sweep), so the candidate loop reads LDS only.  A
-// row's result is up to 44 bytes and no longer fits the low half of its packed word: it goes to a RECORD, one array per
-// wanted output (`rec`, scratch) indexed like the page pool -- the row's word is pool[i], its record rec.*[i] -- so a
-// wavefront's stores are as contiguous as its row loads.  ivx_unroute_records brings the records into input order and gives
-// the rows the routing pass dropped the empty result.  Rows the packed form cannot carry are listed as in k_rv_fast;
-// k_agg_rest walks them with global value reads and writes their records.
 #ifndef IVX_AGG_B
 #define IVX_AGG_B 4
 #endif
-template <int B, int VB, bool MM, bool WT>
-__global__ __launch_bounds__(RP_T, IVX_RV_WPS) void k_agg_fast(JoinIndexView ix, const u64 *__restrict__ pool, const u32 *__restrict__ rcur, const u32 *__restrict__ cfirst,
-                                                   PageTab pt, u32 rowbits, u64 *__restrict__ rest_rows, u32 *rest_n, const void *__restrict__ val, AggOut rec)
+template <int B, class Op>
+__global__ __launch_bounds__(RP_T, IVX_RV_WPS) void k_lean(JoinIndexView ix, typename Op::W *__restrict__ pool, const u32 *__restrict__ rcur, const u32 *__restrict__ cfirst,
+                                               PageTab pt, u32 rowbits, u64 *__restrict__ rest_rows, u32 *rest_n, Op op)
 {
-    using VT = typename std::conditional<VB == 4, i32, i64>::type;
     __shared__ unsigned short s_off[RP_CCAP];
     __shared__ u64 s_ent[RP_ECAP];
     __shared__ u32 s_cfirst[IVX_MAXREG_WIDE + 2];
-    __shared__ VT s_val[RP_ECAP];
+    // (the compiler lays a kernel's LDS out by the variables' names: s_own sits behind s_ent and s_off, which keep the low
+    //  offsets that a DS instruction's 16-bit immediate reaches)
+    __shared__ typename Op::Lds s_own;
     ProbeLds L{s_off, s_ent, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     const u32 ln = lane_id();
+    op.begin(s_own);                                                      // (the barrier behind it is init's)
     auto miss = []() {};                                                 // (a page never published: stay in bounds, silently)
-    LeanRows<B, const u64> rows;
+    LeanRows<B, typename Op::W> rows;
     if (!rows.init(ix, s_cfirst, cfirst, rcur, pt, pool, rowbits)) return;
     Slice S;
     slice_init(ix, S, L);
@@ -1204,13 +1032,12 @@ __global__ __launch_bounds__(RP_T, IVX_RV_WPS) void k_agg_fast(JoinIndexView ix,
     for (u32 i = 0; i < rows.nbatch; i++) {
         const u32 r = rows.r;
         if (r != loaded_r) {
-            slice_load(ix, S, L, r, true);                               // (its first barrier: nobody reads the old values any more)
-            const u32 ne = ix.rdesc[r].ne;
-            if (S.inlds) for (u32 j = threadIdx.x; j < ne; j += RP_T) s_val[j] = ((const VT *)val)[ix.ent[S.e0 + j].row];
-            __syncthreads();
+            if (loaded_r != 0xFFFFFFFFu) op.leave(ix, S, s_own);
+            slice_load(ix, S, L, r, true);
+            op.enter(ix, S, r, s_own);
             loaded_r = r;
         }
-        u32 rel[B], len[B], roww[B];                                     // (roww: not used, the un-permute reads the row ids)
+        u32 rel[B], len[B], roww[B];                                     // (roww: the word's upper half, for operators that write the word)
         const auto bt = rows.take(i, rel, len, roww, miss);
         const u64 at = (u64)(bt.src - pool) + ln;                        // the lane's first row of the batch: its word's place in the pool
         const i32 rbase = S.rbase;
@@ -1219,120 +1046,34 @@ __global__ __launch_bounds__(RP_T, IVX_RV_WPS) void k_agg_fast(JoinIndexView ix,
 #pragma unroll
         for (int q = 0; q < B; q++) {
             const i32 qs = (i32)((u32)rbase + rel[q]), qe = (i32)((u32)qs + len[q]);
-            AggAcc<MM, WT> a;
+            typename Op::Row a;
             for (u32 j = ca[q]; j < cb[q]; j++) {
                 const u64 x = s_ent[j];
                 const i32 xs = (i32)(u32)x, xe = (i32)(u32)(x >> 32);
-                if (xs <= qe && xe >= qs) a.add((i64)s_val[j], qs, qe, xs, xe);
+                if (xs <= qe && xe >= qs) a.hit(op, s_own, j, qs, qe, xs, xe);
             }
-            if ((okm >> q) & 1u) a.store(rec, at + (u32)q * IVX_WAVE);
+            if ((okm >> q) & 1u) a.done(op, bt.src + q * IVX_WAVE + ln, at + (u32)q * IVX_WAVE, roww[q]);
         }
         if (__builtin_expect(slow != 0, 0)) lean_list_slow<B>(slow, r, bt.first, ln, rest_rows, rest_n);
     }
+    op.leave(ix, S, s_own);
 }
 
-template <int VB, bool MM, bool WT>
-__global__ __launch_bounds__(256) void k_agg_rest(JoinIndexView ix, const u64 *__restrict__ pool, PageTab pt, const u64 *__restrict__ rest_rows,
-                                                  const u32 *__restrict__ rest_n, const i32 *__restrict__ ps_in, const i32 *__restrict__ pe_in,
-                                                  u32 rowbits, const void *__restrict__ val, AggOut rec)
+template <class Op>
+__global__ __launch_bounds__(256) void k_lean_rest(JoinIndexView ix, typename Op::W *__restrict__ pool, PageTab pt, const u64 *__restrict__ rest_rows,
+                                                   const u32 *__restrict__ rest_n, const i32 *__restrict__ ps_in, const i32 *__restrict__ pe_in,
+                                                   u32 rowbits, Op op)
 {
     const u32 nrow = rest_n[1];
     const u32 sh0 = ix.hdr[HDR_SH0], nlev = ix.hdr[HDR_NLEV];
     for (u32 i = blockIdx.x * blockDim.x + threadIdx.x; i < nrow; i += gridDim.x * blockDim.x) {
         const u64 ent = rest_rows[i];
         const u32 r = (u32)(ent >> 32);
-        const auto e = rest_row(ix, pt, pool, r, (u32)ent, rowbits, ps_in, pe_in, 0u, []() {});
+        const auto e = rest_row(ix, pt, pool, r, (u32)ent, rowbits, ps_in, pe_in, op.adj, []() {});
         const i32 qs = e.qs, qe = e.qe;
-        AggAcc<MM, WT> a;
-        walk_ent(ix, sh0, 0, nlev, ix.rkey[r], qs, qe, [&](const ivx_ent &x) { a.add(agg_val<VB>(val, x.row), qs, qe, x.s, x.e); });
-        a.store(rec, (u64)(e.slot - pool));
-    }
-}
-
-// ------------------------------------------------------------------ lean overlap select
-// Per probe row, the one best build row among the row's matches (ivx_probe_overlap_select), over LeanRows and lean_cells as
-// k_agg_fast.  The result names a build row, so beside the slice the workgroup stages the slice's build ROW IDS at slice
-// load, s_row[j] = the row of slice entry j, and for the two *_VAL criteria the values as k_agg_fast does: the candidate loop
-// reads LDS only.  Declared LDS: 24 KB more than k_rv_fast without values, 48 or 72 KB more with them -- one 1024-thread
-// workgroup per CU either way.  A row's (winner, score) goes to a RECORD as the aggregates' do: rec.idx, and rec.score
-// when wanted, indexed like the page pool; ivx_unroute_sel_records brings them into input order and gives the rows the
-// routing pass dropped (IVX_NULL_IDX, 0).  Rows the packed form cannot carry are listed as in k_rv_fast; k_sel_rest walks
-// them with global reads and writes their records.
-template <int B, int BY, int VB, bool SCORE>
-__global__ __launch_bounds__(RP_T, IVX_RV_WPS) void k_sel_fast(JoinIndexView ix, const u64 *__restrict__ pool, const u32 *__restrict__ rcur, const u32 *__restrict__ cfirst,
-                                                   PageTab pt, u32 rowbits, u64 *__restrict__ rest_rows, u32 *rest_n, const void *__restrict__ val, SelOut rec)
-{
-    using VT = typename std::conditional<VB == 4, i32, i64>::type;
-    constexpr bool VAL = sel_by_val<BY>;
-    __shared__ unsigned short s_off[RP_CCAP];
-    __shared__ u64 s_ent[RP_ECAP];
-    __shared__ u32 s_cfirst[IVX_MAXREG_WIDE + 2];
-    __shared__ u32 s_row[RP_ECAP];
-    __shared__ VT s_val[VAL ? RP_ECAP : 1];
-    ProbeLds L{s_off, s_ent, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    const u32 ln = lane_id();
-    auto miss = []() {};                                                 // (a page never published: stay in bounds, silently)
-    LeanRows<B, const u64> rows;
-    if (!rows.init(ix, s_cfirst, cfirst, rcur, pt, pool, rowbits)) return;
-    Slice S;
-    slice_init(ix, S, L);
-    rows.start(miss);
-    u32 loaded_r = 0xFFFFFFFFu;
-    for (u32 i = 0; i < rows.nbatch; i++) {
-        const u32 r = rows.r;
-        if (r != loaded_r) {
-            slice_load(ix, S, L, r, true);                               // (its first barrier: nobody reads the old rows and values any more)
-            const u32 ne = ix.rdesc[r].ne;
-            if (S.inlds) for (u32 j = threadIdx.x; j < ne && j < RP_ECAP; j += RP_T) {
-                const u32 row = ix.ent[S.e0 + j].row;
-                s_row[j] = row;
-                if (VAL) s_val[j] = ((const VT *)val)[row];
-            }
-            __syncthreads();
-            loaded_r = r;
-        }
-        u32 rel[B], len[B], roww[B];                                     // (roww: not used, the un-permute reads the row ids)
-        const auto bt = rows.take(i, rel, len, roww, miss);
-        const u64 at = (u64)(bt.src - pool) + ln;                        // the lane's first row of the batch: its word's place in the pool
-        const i32 rbase = S.rbase;
-        u32 ca[B], cb[B], slow, okm;
-        lean_cells<B>(S, rel, len, rows.maxlen, bt.cnt, ln, ca, cb, slow, okm);
-#pragma unroll
-        for (int q = 0; q < B; q++) {
-            const i32 qs = (i32)((u32)rbase + rel[q]), qe = (i32)((u32)qs + len[q]);
-            SelAcc<BY, SCORE> a;
-            for (u32 j = ca[q]; j < cb[q]; j++) {
-                const u64 x = s_ent[j];
-                const i32 xs = (i32)(u32)x, xe = (i32)(u32)(x >> 32);
-                if (xs <= qe && xe >= qs) {
-                    const u32 row = s_row[j];
-                    a.add(sel_crit<BY>(VAL ? (i64)s_val[j] : 0, row, qs, qe, xs, xe), row);
-                }
-            }
-            if ((okm >> q) & 1u) a.store(rec, at + (u32)q * IVX_WAVE);
-        }
-        if (__builtin_expect(slow != 0, 0)) lean_list_slow<B>(slow, r, bt.first, ln, rest_rows, rest_n);
-    }
-}
-
-template <int BY, int VB, bool SCORE>
-__global__ __launch_bounds__(256) void k_sel_rest(JoinIndexView ix, const u64 *__restrict__ pool, PageTab pt, const u64 *__restrict__ rest_rows,
-                                                  const u32 *__restrict__ rest_n, const i32 *__restrict__ ps_in, const i32 *__restrict__ pe_in,
-                                                  u32 rowbits, const void *__restrict__ val, SelOut rec)
-{
-    const u32 nrow = rest_n[1];
-    const u32 sh0 = ix.hdr[HDR_SH0], nlev = ix.hdr[HDR_NLEV];
-    for (u32 i = blockIdx.x * blockDim.x + threadIdx.x; i < nrow; i += gridDim.x * blockDim.x) {
-        const u64 ent = rest_rows[i];
-        const u32 r = (u32)(ent >> 32);
-        const auto e = rest_row(ix, pt, pool, r, (u32)ent, rowbits, ps_in, pe_in, 0u, []() {});
-        const i32 qs = e.qs, qe = e.qe;
-        SelAcc<BY, SCORE> a;
-        walk_ent(ix, sh0, 0, nlev, ix.rkey[r], qs, qe, [&](const ivx_ent &x) {
-            const i64 v = sel_by_val<BY> ? agg_val<VB>(val, x.row) : 0;
-            a.add(sel_crit<BY>(v, x.row, qs, qe, x.s, x.e), x.row);
-        });
-        a.store(rec, (u64)(e.slot - pool));
+        typename Op::Row a;
+        if (!Op::skip_empty || !(qe < qs)) walk_ent(ix, sh0, 0, nlev, ix.rkey[r], qs, qe, [&](const ivx_ent &x) { a.hit(op, x, qs, qe); });
+        a.done(op, e.slot, (u64)(e.slot - pool), e.hi);
     }
 }
 
@@ -1570,7 +1311,7 @@ bool dense_fill_wanted(const RegionKnobs &K, u64 cap, u64 n)
     return (double)cap / (double)n > 3.5;                                  // measured crossover (tools/probe_only.py IVX_DENSE=0/1): the ring wins below
 }
 
-// may the lean kernels (k_fill_fast, k_rv_fast, k_mark_fast) run on these routed rows: packed words in region pages that
+// may the lean kernels (k_fill_fast, k_lean) run on these routed rows: packed words in region pages that
 // hold at least a chunk, and a rest list for the rows the packed form cannot carry (the routing pass made one: its `lean`
 // option).  Whether the INDEX qualifies (`fast`) and IVX_FILL=old are each launcher's own to test.
 bool lean_rows_ok(const ivx_routed &R)
@@ -1580,6 +1321,47 @@ bool lean_rows_ok(const ivx_routed &R)
 
 // ... and the lean fill pair (k_fill_fast + k_fill_rest), which also wants the batch list
 bool lean_fill_ok(const ivx_routed &R, const RegionKnobs &K) { return lean_rows_ok(R) && !K.lean_off && R.rest != nullptr; }
+
+// The shared opening of the launchers that have the lean form only (marks, aggregates, select): may the lean kernels run on
+// this index under these settings -- the form ivx_rowval_probe_regions runs k_lean on -- and if so, route the rows.  *ok =
+// false: the index, the settings or the routed rows do not qualify, and nothing else was taken or launched.
+ivx_status lean_route(ivx_ctx *ctx, const JoinIndexView &jv, u32 nreg, const u32 *key, const i32 *s, const i32 *e, u64 n,
+                      bool has_filter, bool pk24, bool fast, bool no_vtab, ivx_routed *R, bool *ok)
+{
+    *ok = false;
+    const RegionKnobs K = region_knobs();
+    if (n == 0 || nreg == 0 || nreg > IVX_MAXREG || !pk24 || !fast || K.two_pass || K.pack_off || K.lean_off) return IVX_OK;
+    IVX_TRY(ivx_route_paged(ctx, jv, nreg, key, s, e, n, ivx_paged_opts{has_filter && !K.filter_off, true, true, true, 0u, nullptr, false, no_vtab}, R));
+    *ok = lean_rows_ok(*R);
+    return IVX_OK;
+}
+
+// k_lean values the routed rows, k_lean_rest the few the packed form cannot carry (s, e: the input columns, for the escapes)
+template <int B, class Op>
+void lean_launch(hipStream_t st, const JoinIndexView &jv, const ivx_routed &R, const i32 *s, const i32 *e, const Op &op)
+{
+    typename Op::W *pool = const_cast<u64 *>(R.se);
+    hipLaunchKernelGGL((k_lean<B, Op>), dim3(RP_GRID * (IVX_RV_WPS / 4)), dim3(RP_T), 0, st, jv, pool, (const u32 *)R.ctl->rcur, (const u32 *)R.ctl->cfirst, R.pt, R.rowbits,
+                       R.rest_rows, R.ctl->rest_n, op);
+    hipLaunchKernelGGL((k_lean_rest<Op>), dim3(256), dim3(256), 0, st, jv, pool, R.pt, (const u64 *)R.rest_rows, (const u32 *)R.ctl->rest_n, s, e, R.rowbits, op);
+}
+
+// The operators' records: arrays with a cell per word of the page pool (ivx_route_paged's own size of it), cell_bytes in all,
+// out of one scratch buffer.  take(p, wanted) gives p the next array if the output is wanted; 8-byte arrays first.
+struct RecCarve {
+    u8 *buf = nullptr; u64 cells = 0;
+    ivx_status reserve(ivx_ctx *ctx, const ivx_routed &R, u32 nreg, u64 n, size_t cell_bytes)
+    {
+        cells = ((n >> R.pt.lgpg) + nreg + 1) << R.pt.lgpg;
+        return ctx->get_scratch(WS_T4, (size_t)cells * cell_bytes, (void **)&buf);
+    }
+    template <class T> void take(T *&p, const void *wanted)
+    {
+        if (!wanted) return;
+        p = reinterpret_cast<T *>(buf);
+        buf += cells * sizeof(T);
+    }
+};
 
 template <int V> using int_tag = std::integral_constant<int, V>;
 // rows per lane in {1, 2, 4, 8} as a template argument: f(int_tag<B>)
@@ -1775,12 +1557,9 @@ ivx_status ivx_rowval_probe_regions(ivx_ctx *ctx, const JoinIndexView &jv, u32 n
     u64 *pool = const_cast<u64 *>(R.se);
     auto probe = [&](auto kind_tag) {
         constexpr int M = decltype(kind_tag)::value;
-        // every region one LDS-resident level: the lean kernel values the rows, k_rv_rest the few the packed form cannot carry
-        // (IVX_FILL=old: the general kernel)
-        if (lean_rows_ok(R)) {
-            hipLaunchKernelGGL((k_rv_fast<M, IVX_RV_B>), dim3(RP_GRID * (IVX_RV_WPS / 4)), dim3(RP_T), 0, st, jv, pool, (const u32 *)R.ctl->rcur, (const u32 *)R.ctl->cfirst, R.pt, R.rowbits, R.rest_rows, R.ctl->rest_n);
-            hipLaunchKernelGGL((k_rv_rest<M>), dim3(256), dim3(256), 0, st, jv, pool, R.pt, (const u64 *)R.rest_rows, (const u32 *)R.ctl->rest_n, s, e, R.rowbits, adj);
-        } else launch_probe_regions<M, RP_B>(st, jv, R, RP_VGRID, paged ? (u32 *)pool : val, nullptr, 0, nullptr);
+        // every region one LDS-resident level: the lean pair (IVX_FILL=old: the general kernel)
+        if (lean_rows_ok(R)) lean_launch<IVX_RV_B>(st, jv, R, s, e, RvOp<M>{{}, adj});
+        else launch_probe_regions<M, RP_B>(st, jv, R, RP_VGRID, paged ? (u32 *)pool : val, nullptr, 0, nullptr);
     };
     if (kind == IVX_RV_COVERAGE) probe(int_tag<RV_COVERAGE>{}); else if (kind == IVX_RV_COUNT) probe(int_tag<RV_COUNT>{}); else probe(int_tag<RV_MATCHES>{});
     IVX_HIP(ctx, hipGetLastError());
@@ -1788,98 +1567,59 @@ ivx_status ivx_rowval_probe_regions(ivx_ctx *ctx, const JoinIndexView &jv, u32 n
 }
 
 // The build rows a big batch matched, ORed into `marks` (one bit per build row), through the region partition -- the lean
-// form only: packed rows in region pages over an index whose every region is one LDS-resident level, i.e. when
-// ivx_rowval_probe_regions would launch k_rv_fast.  *took = false (nothing launched) when the index or the settings do not
-// qualify: the caller then runs the direct kernel (ivx_mark_probe) on its columns.
+// form only: packed rows in region pages over an index whose every region is one LDS-resident level (lean_route).  *took =
+// false (nothing launched) when the index or the settings do not qualify: the caller then runs the direct kernel
+// (ivx_mark_probe) on its columns.  (*took means something on IVX_OK only.)
 ivx_status ivx_mark_probe_regions(ivx_ctx *ctx, const JoinIndexView &jv, u32 nreg, const u32 *key, const i32 *s, const i32 *e, u64 n,
                                   u32 *marks, bool has_filter, bool pk24, bool fast, bool *took)
 {
-    *took = false;
-    const RegionKnobs K = region_knobs();
-    if (n == 0 || nreg == 0 || nreg > IVX_MAXREG || !pk24 || !fast || K.two_pass || K.pack_off || K.lean_off) return IVX_OK;
-    hipStream_t st = ctx->stream;
     ivx_routed R;
-    IVX_TRY(ivx_route_paged(ctx, jv, nreg, key, s, e, n, ivx_paged_opts{has_filter && !K.filter_off, true, true, true, 0u, nullptr, false, true}, &R));
-    if (!lean_rows_ok(R)) return IVX_OK;
-    hipLaunchKernelGGL((k_mark_fast<IVX_RV_B>), dim3(RP_GRID * (IVX_RV_WPS / 4)), dim3(RP_T), 0, st, jv, R.se, (const u32 *)R.ctl->rcur, (const u32 *)R.ctl->cfirst, R.pt, R.rowbits,
-                       R.rest_rows, R.ctl->rest_n, marks);
-    hipLaunchKernelGGL(k_mark_rest, dim3(256), dim3(256), 0, st, jv, R.se, R.pt, (const u64 *)R.rest_rows, (const u32 *)R.ctl->rest_n, s, e, R.rowbits, marks);
+    IVX_TRY(lean_route(ctx, jv, nreg, key, s, e, n, has_filter, pk24, fast, true, &R, took));       // (no un-permute: no vtab)
+    if (!*took) return IVX_OK;
+    lean_launch<IVX_RV_B>(ctx->stream, jv, R, s, e, MarkOp{{}, marks});
     IVX_HIP(ctx, hipGetLastError());
-    *took = true;
     return IVX_OK;
 }
 
 // Per-row aggregates of `val` over each probe row's matches, through the region partition -- the lean form only, as
 // ivx_mark_probe_regions: *took = false (nothing launched, no scratch taken) when the index or the settings do not qualify,
-// and the caller runs the direct kernel (ivx_agg_probe).  The outputs are device columns in input order.
+// and the caller runs the direct kernel (ivx_agg_probe).  The outputs are device columns in input order:
+// ivx_unroute_records brings the records there and gives the rows the routing pass dropped the empty result.
 ivx_status ivx_agg_probe_regions(ivx_ctx *ctx, const JoinIndexView &jv, u32 nreg, const u32 *key, const i32 *s, const i32 *e, u64 n,
                                  const void *val, u32 val_bytes, const AggOut &out, bool has_filter, bool pk24, bool fast, bool *took)
 {
-    *took = false;
-    const RegionKnobs K = region_knobs();
-    if (n == 0 || nreg == 0 || nreg > IVX_MAXREG || !pk24 || !fast || K.two_pass || K.pack_off || K.lean_off) return IVX_OK;
-    hipStream_t st = ctx->stream;
     ivx_routed R;
-    IVX_TRY(ivx_route_paged(ctx, jv, nreg, key, s, e, n, ivx_paged_opts{has_filter && !K.filter_off, true, true, true, 0u}, &R));
-    if (!lean_rows_ok(R)) return IVX_OK;
-    // the records: one array per wanted output, a cell per word of the page pool (ivx_route_paged's own size of it)
-    const u64 cells = ((n >> R.pt.lgpg) + nreg + 1) << R.pt.lgpg;
+    IVX_TRY(lean_route(ctx, jv, nreg, key, s, e, n, has_filter, pk24, fast, false, &R, took));
+    if (!*took) return IVX_OK;
     const int n64 = (out.sum != nullptr) + (out.vmin != nullptr) + (out.vmax != nullptr) + (out.bases != nullptr) + (out.wsum != nullptr);
-    u8 *buf;
-    IVX_TRY(ctx->get_scratch(WS_T4, (size_t)cells * (8u * (size_t)n64 + (out.count ? 4u : 0u)), (void **)&buf));
+    RecCarve c;
+    IVX_TRY(c.reserve(ctx, R, nreg, n, 8u * (size_t)n64 + (out.count ? 4u : 0u)));
     AggOut rec{};
-    auto carve = [&](auto *&p, const void *wanted) {
-        if (!wanted) return;
-        p = reinterpret_cast<std::remove_reference_t<decltype(p)>>(buf);
-        buf += cells * sizeof(*p);
-    };
-    carve(rec.sum, out.sum); carve(rec.vmin, out.vmin); carve(rec.vmax, out.vmax); carve(rec.bases, out.bases); carve(rec.wsum, out.wsum);
-    carve(rec.count, out.count);                                        // (the 4-byte array last: the others stay 8-byte aligned)
-    const bool mm = out.vmin || out.vmax, wt = out.bases || out.wsum;
-    with_bools([&](auto wide, auto m, auto w) {
-        constexpr int VB = IVX_B(wide) ? 8 : 4;
-        hipLaunchKernelGGL((k_agg_fast<IVX_AGG_B, VB, IVX_B(m), IVX_B(w)>), dim3(RP_GRID * (IVX_RV_WPS / 4)), dim3(RP_T), 0, st, jv, R.se, (const u32 *)R.ctl->rcur,
-                           (const u32 *)R.ctl->cfirst, R.pt, R.rowbits, R.rest_rows, R.ctl->rest_n, val, rec);
-        hipLaunchKernelGGL((k_agg_rest<VB, IVX_B(m), IVX_B(w)>), dim3(256), dim3(256), 0, st, jv, R.se, R.pt, (const u64 *)R.rest_rows, (const u32 *)R.ctl->rest_n, s, e,
-                           R.rowbits, val, rec);
-    }, val_bytes == 8, mm, wt);
+    c.take(rec.sum, out.sum); c.take(rec.vmin, out.vmin); c.take(rec.vmax, out.vmax); c.take(rec.bases, out.bases); c.take(rec.wsum, out.wsum);
+    c.take(rec.count, out.count);
+    with_bools([&](auto wide, auto mm, auto wt) {
+        lean_launch<IVX_AGG_B>(ctx->stream, jv, R, s, e, AggOp<IVX_B(wide) ? 8 : 4, IVX_B(mm), IVX_B(wt)>{{}, val, rec});
+    }, val_bytes == 8, out.vmin || out.vmax, out.bases || out.wsum);
     IVX_HIP(ctx, hipGetLastError());
-    IVX_TRY(ivx_unroute_records(ctx, R, nreg, n, rec, out));
-    *took = true;
-    return IVX_OK;
+    return ivx_unroute_records(ctx, R, nreg, n, rec, out);
 }
 
 // Per probe row the best matching build row by `by` (and the criterion's value there), through the region partition -- the
-// lean form only, with ivx_agg_probe_regions' eligibility: *took = false (nothing launched, no scratch taken) when the index
-// or the settings do not qualify, and the caller runs the direct kernel (ivx_sel_probe).  The outputs are device columns in
-// input order.
+// lean form only, with ivx_agg_probe_regions' eligibility and *took.  The outputs are device columns in input order:
+// ivx_unroute_sel_records brings the records there and gives the rows the routing pass dropped (IVX_NULL_IDX, 0).
 ivx_status ivx_sel_probe_regions(ivx_ctx *ctx, const JoinIndexView &jv, u32 nreg, const u32 *key, const i32 *s, const i32 *e, u64 n,
                                  const void *val, u32 val_bytes, int by, const SelOut &out, bool has_filter, bool pk24, bool fast, bool *took)
 {
-    *took = false;
-    const RegionKnobs K = region_knobs();
-    if (n == 0 || nreg == 0 || nreg > IVX_MAXREG || !pk24 || !fast || K.two_pass || K.pack_off || K.lean_off) return IVX_OK;
-    hipStream_t st = ctx->stream;
     ivx_routed R;
-    IVX_TRY(ivx_route_paged(ctx, jv, nreg, key, s, e, n, ivx_paged_opts{has_filter && !K.filter_off, true, true, true, 0u}, &R));
-    if (!lean_rows_ok(R)) return IVX_OK;
-    // the records: a cell per word of the page pool (ivx_route_paged's own size of it), the 8-byte array first
-    const u64 cells = ((n >> R.pt.lgpg) + nreg + 1) << R.pt.lgpg;
-    u8 *buf;
-    IVX_TRY(ctx->get_scratch(WS_T4, (size_t)cells * (out.score ? 12u : 4u), (void **)&buf));
+    IVX_TRY(lean_route(ctx, jv, nreg, key, s, e, n, has_filter, pk24, fast, false, &R, took));
+    if (!*took) return IVX_OK;
+    RecCarve c;
+    IVX_TRY(c.reserve(ctx, R, nreg, n, out.score ? 12u : 4u));
     SelOut rec{};
-    if (out.score) { rec.score = reinterpret_cast<i64 *>(buf); buf += cells * sizeof(i64); }
-    rec.idx = reinterpret_cast<u32 *>(buf);
+    c.take(rec.score, out.score); c.take(rec.idx, out.idx);
     sel_dispatch(by, val_bytes, out.score != nullptr, [&](auto b, auto vb, auto sc) {
-        constexpr int BY = decltype(b)::value, VB = decltype(vb)::value;
-        constexpr bool SC = decltype(sc)::value;
-        hipLaunchKernelGGL((k_sel_fast<IVX_AGG_B, BY, VB, SC>), dim3(RP_GRID * (IVX_RV_WPS / 4)), dim3(RP_T), 0, st, jv, R.se, (const u32 *)R.ctl->rcur,
-                           (const u32 *)R.ctl->cfirst, R.pt, R.rowbits, R.rest_rows, R.ctl->rest_n, val, rec);
-        hipLaunchKernelGGL((k_sel_rest<BY, VB, SC>), dim3(256), dim3(256), 0, st, jv, R.se, R.pt, (const u64 *)R.rest_rows, (const u32 *)R.ctl->rest_n, s, e,
-                           R.rowbits, val, rec);
+        lean_launch<IVX_AGG_B>(ctx->stream, jv, R, s, e, SelOp<decltype(b)::value, decltype(vb)::value, decltype(sc)::value>{{}, val, rec});
     });
     IVX_HIP(ctx, hipGetLastError());
-    IVX_TRY(ivx_unroute_sel_records(ctx, R, nreg, n, rec, out));
-    *took = true;
-    return IVX_OK;
+    return ivx_unroute_sel_records(ctx, R, nreg, n, rec, out);
 }

@@ -1,9 +1,8 @@
-// ivx_select.hpp -- device pieces shared by the overlap-select kernels (ivx_select.hip: the direct walk;
-// ivx_regions_probe.hip: k_sel_fast / k_sel_rest): the criterion value of one match, the best match one probe row has seen
-// so far, and its store into the output columns (SelOut, ivx_internal.hpp: the caller's columns by row, or the region
-// path's records by pool index).
+// ivx_select.hpp -- overlap select as a per-row operator (ivx_rowops.hpp; ivx_select.hip runs it on the direct walk,
+// ivx_regions_probe.hip on the lean kernels): the criterion value of one match, the best match one probe row has seen so far,
+// and its store into the output columns (SelOut, ivx_internal.hpp: the caller's columns by row, or the region path's records
+// by pool index).
 #pragma once
-#include <type_traits>
 #include "ivx_agg.hpp"
 
 // BY: an IVX_SEL_* criterion (include/ivx_select.h)
@@ -56,4 +55,37 @@ struct SelAcc {
         o.idx[i] = row;
         if (SCORE) o.score[i] = c;
     }
+};
+
+// The result names a build row, so k_lean stages the slice's build ROW IDS when a region is entered, row[j] = the row of slice
+// entry j, and for the two *_VAL criteria the values as AggOp does (24 KB of LDS more than the slice alone, 48 or 72 KB with
+// values: one 1024-thread workgroup per CU either way).  (winner, score) go to out.idx[at], and out.score[at] when wanted: on
+// the region path a record, as the aggregates'.
+template <int BY, int VB, bool SCORE>
+struct SelOp : RowOpBase {
+    using VT = typename std::conditional<VB == 4, i32, i64>::type;
+    static constexpr bool VAL = sel_by_val<BY>;
+    const void *val; SelOut out;
+    struct RowsVals { u32 row[RP_ECAP]; VT val[RP_ECAP]; };
+    struct Rows { u32 row[RP_ECAP]; };
+    using Lds = typename std::conditional<VAL, RowsVals, Rows>::type;
+    // (the slice load's first barrier: nobody reads the old rows and values any more)
+    template <class S> __device__ __forceinline__ void enter(const JoinIndexView &ix, const S &sl, u32 r, Lds &l) const
+    {
+        slice_rows(ix, sl, r, [&](u32 j, u32 row) { l.row[j] = row; if constexpr (VAL) l.val[j] = ((const VT *)val)[row]; });
+    }
+    struct Row : SelAcc<BY, SCORE> {
+        __device__ __forceinline__ void hit(const SelOp &, const Lds &l, u32 j, i32 qs, i32 qe, i32 xs, i32 xe)
+        {
+            const u32 row = l.row[j];
+            i64 v = 0;
+            if constexpr (VAL) v = (i64)l.val[j];
+            this->add(sel_crit<BY>(v, row, qs, qe, xs, xe), row);
+        }
+        __device__ __forceinline__ void hit(const SelOp &op, const ivx_ent &x, i32 qs, i32 qe)
+        {
+            this->add(sel_crit<BY>(VAL ? agg_val<VB>(op.val, x.row) : 0, x.row, qs, qe, x.s, x.e), x.row);
+        }
+        __device__ __forceinline__ void done(const SelOp &op, const u64 *, u64 at, u32) const { this->store(op.out, at); }
+    };
 };

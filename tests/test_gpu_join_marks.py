@@ -329,7 +329,7 @@ def test_mark_regions_slow_index_falls_back(ctx):
 
 def test_mark_regions_rest_rows(ctx):
     """(d) rows the packed form cannot carry: a span past the region's halo, qe < qs, a length at and past the packed
-    maximum, rows that start before the key's first or behind its last build row -- k_mark_rest marks for them"""
+    maximum, rows that start before the key's first or behind its last build row -- k_lean_rest<MarkOp> marks for them"""
     b = rf.sparse_build()
     ix = ctx.build(pyivx.KIND_OVERLAP, *b, n_keys=1)
     lay, geo = rf.layout_of(ix, *b, 1)

@@ -306,7 +306,7 @@ def test_agg_regions_slow_index_falls_back(ctx):
 
 def test_agg_regions_rest_rows(ctx):
     """rows the packed form cannot carry: a span past the region's halo, qe < qs, a length at and past the packed maximum,
-    rows that start before the key's first or behind its last build row -- k_agg_rest values them"""
+    rows that start before the key's first or behind its last build row -- k_lean_rest<AggOp> values them"""
     b = rf.sparse_build()
     ix = ctx.build(pyivx.KIND_OVERLAP, *b, n_keys=1)
     lay, geo = rf.layout_of(ix, *b, 1)

@@ -301,7 +301,7 @@ def test_select_regions_slice_capacity(ctx, side):
 
 def test_select_regions_rest_rows(ctx):
     """rows the packed form cannot carry: a span past the region's halo, qe < qs, a length at and past the packed maximum,
-    rows that start before the key's first or behind its last build row -- k_sel_rest answers them, alone and beside the
+    rows that start before the key's first or behind its last build row -- k_lean_rest<SelOp> answers them, alone and beside the
     lean walk"""
     b = rf.sparse_build()
     ix = ctx.build(pyivx.KIND_OVERLAP, *b, n_keys=1)

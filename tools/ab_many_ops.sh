@@ -7,7 +7,7 @@ for round in 1 2; do
   for v in $LIBS; do
     cp $L/$v $L/libivx_hip.so
     echo "== $v (round $round)"
-    $R/tools/prof_ops.sh ab_$(basename $v .so)_$round "$@" 2>&1 | grep -E "k_rv_fast|k_probe_regions|k_unpermute"
+    $R/tools/prof_ops.sh ab_$(basename $v .so)_$round "$@" 2>&1 | grep -E "k_lean|k_probe_regions|k_unpermute"
   done
 done
 cp $L/.orig.so $L/libivx_hip.so

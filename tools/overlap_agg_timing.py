@@ -13,7 +13,7 @@ value per build row.
 Warm-up + REPS repeats, median [min-max] of torch events around the calls on the context's stream (kernels, the gaps
 between them and, for the old way, the host round trip of its count).
 
-  N=100000000  REPS=5
+  N=100000000  REPS=5   ONLY=paths: the paths part alone; ROWS=8388608,100000000: its batch sizes
 """
 import json
 import os
@@ -71,8 +71,33 @@ def main():
     ix = ctx.build(pyivx.KIND_OVERLAP, bk, bs, be, n_keys=24)
     res = dict(probe_rows=n, build_rows=1_000_000, reps=reps, layout=ix.layout())
     os.environ.pop("IVX_JOIN_PATH", None)
+    if os.environ.get("ONLY") != "paths":
+        fused_floor_old(ctx, ix, pk, ps, pe, val, n, reps, res)
+    sizes = {int(float(x)) for x in os.environ["ROWS"].split(",")} if os.environ.get("ROWS") else {1 << 20, 1 << 21, 1 << 22, 1 << 23, 1 << 24, 1 << 25, n}
 
-    # ---- the fused call, the floor and the old way, alternating
+    # ---- direct against regions by batch size
+    res["paths"] = []
+    print("  rows        outputs            direct                              regions")
+    for m in sorted(sizes):
+        if m > n:
+            continue
+        qk, qs, qe = pk[:m], ps[:m], pe[:m]
+        for name in SETS:
+            row = dict(rows=m, outputs=name)
+            for path in ("direct", "regions"):
+                os.environ["IVX_JOIN_PATH"] = path
+                _, row[path] = repeat(lambda: ctx.overlap_agg(ix, qk, qs, qe, val, outputs=SETS[name]), reps)
+                torch.cuda.empty_cache()
+            os.environ.pop("IVX_JOIN_PATH", None)
+            res["paths"].append(row)
+            print(f"  {m:<11d} {name:<18} {fmt(row['direct'])}   {fmt(row['regions'])}")
+    print(json.dumps(res), flush=True)
+    ix.free()
+    ctx.close()
+
+
+def fused_floor_old(ctx, ix, pk, ps, pe, val, n, reps, res):
+    """the fused call, the floor and the old way, alternating"""
     def old_way():
         total = ctx.overlap_count(ix, pk, ps, pe)
         ob, op = ctx.overlap_fill(ix, pk, ps, pe, cap=total)
@@ -115,26 +140,6 @@ def main():
         print(f"  agg {name:<18} {fmt(res['agg_ms'][name])}")
     print(f"  floor: count(per_row)  {fmt(res['floor_count_per_row_ms'])}")
     print(f"  old way (4 outputs)    {fmt(res['old_way_ms'])}   equal to agg: {same}")
-
-    # ---- direct against regions by batch size
-    res["paths"] = []
-    print("  rows        outputs            direct                              regions")
-    for m in sorted({1 << 20, 1 << 21, 1 << 22, 1 << 23, 1 << 24, 1 << 25, n}):
-        if m > n:
-            continue
-        qk, qs, qe = pk[:m], ps[:m], pe[:m]
-        for name in SETS:
-            row = dict(rows=m, outputs=name)
-            for path in ("direct", "regions"):
-                os.environ["IVX_JOIN_PATH"] = path
-                _, row[path] = repeat(lambda: ctx.overlap_agg(ix, qk, qs, qe, val, outputs=SETS[name]), reps)
-                torch.cuda.empty_cache()
-            os.environ.pop("IVX_JOIN_PATH", None)
-            res["paths"].append(row)
-            print(f"  {m:<11d} {name:<18} {fmt(row['direct'])}   {fmt(row['regions'])}")
-    print(json.dumps(res), flush=True)
-    ix.free()
-    ctx.close()
 
 
 if __name__ == "__main__":

@@ -14,7 +14,7 @@ synth.py; one int32 value per build row.
 All variants of one batch size alternate in ONE loop (a warm-up round + REPS rounds), so that drift hits them alike; median
 [min-max] of torch events around the calls on the context's stream.
 
-  N=100000000  REPS=5  CHECK=2000000
+  N=100000000  REPS=5  CHECK=2000000   ONLY=paths: no check and no old way; ROWS=8388608,100000000: the batch sizes
 """
 import json
 import os
@@ -88,7 +88,18 @@ def main():
         idx[win >> 31] = win & 0xFFFFF
         return idx, total
 
-    # ---- results equal first
+    only_paths = os.environ.get("ONLY") == "paths"
+    sizes = {int(float(x)) for x in os.environ["ROWS"].split(",")} if os.environ.get("ROWS") else {1 << 20, 1 << 21, 1 << 22, 1 << 23, 1 << 24, 1 << 25, 1 << 26, n}
+    if not only_paths:
+        results_equal(ctx, ix, pk, ps, pe, check, n, reps, select, old_way, res)
+    by_size(ctx, ix, pk, ps, pe, n, reps, sizes, only_paths, select, old_way, res)
+    print(json.dumps(res), flush=True)
+    ix.free()
+    ctx.close()
+
+
+def results_equal(ctx, ix, pk, ps, pe, check, n, reps, select, old_way, res):
+    """both paths equal each other for every variant, and the old way's winner equals the fused call's"""
     q = (pk[:check], ps[:check], pe[:check])
     same = True
     for by, score in VARIANTS:
@@ -104,10 +115,12 @@ def main():
     del idx, fused, d, r
     torch.cuda.empty_cache()
 
-    # ---- by batch size, every variant of a size alternating in one loop
+
+def by_size(ctx, ix, pk, ps, pe, n, reps, sizes, only_paths, select, old_way, res):
+    """by batch size, every variant of a size alternating in one loop"""
     res["sizes"] = []
     print("  ms, median [min-max]")
-    for m in sorted({1 << 20, 1 << 21, 1 << 22, 1 << 23, 1 << 24, 1 << 25, 1 << 26, n}):
+    for m in sorted(sizes):
         if m > n:
             continue
         q = (pk[:m], ps[:m], pe[:m])
@@ -115,7 +128,7 @@ def main():
         for by, score in VARIANTS:
             for path in ("direct", "regions"):
                 runs[(by, score, path)] = (lambda by=by, score=score, path=path: select(q, by, score, path))
-        if m in OLD or m == n:
+        if not only_paths and (m in OLD or m == n):
             runs[("old",)] = lambda: old_way(q)
         ms = {k: [] for k in runs}
         pairs = None
@@ -141,9 +154,6 @@ def main():
             best = min(row["max_val+score"]["direct"]["median"], row["max_val+score"]["regions"]["median"])
             print(f"    old way (max_val)  {fmt(row['old_way'])}   pairs {pairs}   old / select: {row['old_way']['median'] / best:.1f}x")
         res["sizes"].append(row)
-    print(json.dumps(res), flush=True)
-    ix.free()
-    ctx.close()
 
 
 if __name__ == "__main__":
