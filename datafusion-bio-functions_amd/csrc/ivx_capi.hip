@@ -1164,7 +1164,7 @@ extern "C" ivx_status ivx_intersect(ivx_ctx *ctx, int mem,
 }
 
 // Test hook (not in include/ivx.h; tests/test_gpu_intersect_edges.py): an intersect SIZING call for these inputs that also says
-// what its count pass did.  wg: ISECT_DBG_WORDS words per workgroup (k_isect_count, ivx_sweep.hip; ivx_debug_intersect_geometry
+// what its count pass did.  wg: frag_dbg_words<IsectOp> words per workgroup (k_frag_count, ivx_sweep.hip; ivx_debug_intersect_geometry
 // gives the constants), row_esc: one byte per left row at its original index; both HOST buffers in either mode, capacities in
 // workgroups / rows.  *n_wg and *n_rows are set before the capacities are checked (IVX_ERR_CAPACITY); both are 0, and nothing is
 // written, when a side is empty.

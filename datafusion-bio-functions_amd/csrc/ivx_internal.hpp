@@ -476,7 +476,7 @@ ivx_status ivx_subtract_device(ivx_ctx *ctx, const u32 *lkey, const i64 *ls, con
                                u32 *ok, i64 *os, i64 *oe, u32 *orow, u64 cap, u64 *n_out);
 ivx_status ivx_subtract_fill_planned(ivx_ctx *ctx, u32 *ok, i64 *os, i64 *oe, u32 *orow, u64 cap, u64 *n_out);
 // intersect; dbg (nullable; the test hook ivx_debug_intersect_paths): HOST buffers for what the count pass did -- `wg`: words
-// per workgroup (k_isect_count), `row_esc`: one byte per left row at its original index -- capacities in workgroups / rows,
+// per workgroup (k_frag_count), `row_esc`: one byte per left row at its original index -- capacities in workgroups / rows,
 // and where the numbers of both go
 struct ivx_isect_debug { u32 *wg; u64 wg_cap; u8 *row_esc; u64 row_cap; u64 *n_wg, *n_rows; };
 ivx_status ivx_intersect_device(ivx_ctx *ctx, const u32 *lkey, const i64 *ls, const i64 *le, u64 nl,

@@ -631,40 +631,48 @@ __device__ __forceinline__ u32 rank_near_down(u32 start, u32 n, Before before)
     return bisect(lo, hi, before);
 }
 
+// ---- how a row plan reads the right side's arrays: through an index map in front of every array.  Whole: the arrays as they
+// are, in global memory.  Window: a workgroup's LDS copy of elements [w0, w0 + wn); an index outside raises `esc` and reads slot
+// 0 -- the caller then plans that row again from global memory.  (Two types, and every read of a plan over Windows an LDS
+// read: an accessor that falls back to global memory per access compiles to flat loads with full waits, 36 -> 46 ms.)
+struct Whole {
+    __device__ __forceinline__ u32 operator()(u32 i) const { return i; }
+    __device__ __forceinline__ u32 end(u32 n) const { return n; }
+    __device__ __forceinline__ void reached(u32, u32) const {}
+};
+struct Window {
+    u32 w0, wn;
+    bool &esc;
+    __device__ __forceinline__ u32 operator()(u32 i) const { const u32 x = i - w0; if (x >= wn) { esc = true; return 0u; } return x; }
+    // a gallop stops at the window's end: an answer AT that end, short of all n elements, may lie beyond it
+    __device__ __forceinline__ u32 end(u32 n) const { const u32 we = w0 + wn; return we < n ? we : n; }
+    __device__ __forceinline__ void reached(u32 b, u32 n) const { if (b == w0 + wn && b < n) esc = true; }
+};
+
 struct SubPlan { u32 h_lo, h_hi; i64 tail_from; u32 has_tail; };
+
+// the arrays plan_row searches: heads through H, rights through R; the running max of the right ends as the scan left it
+// (global memory) or as plain ends (the LDS copy)
+__device__ __forceinline__ i64 end_of(const SegMax64 &x) { return x.v; }
+__device__ __forceinline__ i64 end_of(i64 x) { return x; }
+template <class Ix, class PM>
+struct SubView {
+    const u32 *hk; const i64 *hrs; const u32 *hj; const u32 *rk; const i64 *rs; const PM *pm;
+    Ix H, R;
+    __device__ __forceinline__ u32 Hk(u32 i) const { return hk[H(i)]; }
+    __device__ __forceinline__ i64 Hrs(u32 i) const { return hrs[H(i)]; }
+    __device__ __forceinline__ u32 Hj(u32 i) const { return hj[H(i)]; }
+    __device__ __forceinline__ u32 Rk(u32 i) const { return rk[R(i)]; }
+    __device__ __forceinline__ i64 Rs(u32 i) const { return rs[R(i)]; }
+    __device__ __forceinline__ i64 Pm(u32 i) const { return end_of(pm[R(i)]); }
+};
 
 // One left row [ls,le) of key k against the rights of that key (sorted by start; sm = running max of their
 // ends; heads = rights that start a new gap).  Two of the five partition points are real searches; the
 // other three sit next to them (the row's end is a few rights after its start), so they gallop from there.
 // [ha, hb]: bounds of the first search (the heads at or below the row's start): the caller's workgroup holds consecutive
 // rows of the sorted left side, so the answers of its first and last row bracket everybody's (0 .. nh if unknown)
-// the arrays plan_row searches, read from global memory ...
-struct SubGlobal {
-    const u32 *hk; const i64 *hrs; const u32 *hj; const u32 *rk; const i64 *rs; const SegMax64 *sm;
-    __device__ __forceinline__ u32 Hk(u32 i) const { return hk[i]; }
-    __device__ __forceinline__ i64 Hrs(u32 i) const { return hrs[i]; }
-    __device__ __forceinline__ u32 Hj(u32 i) const { return hj[i]; }
-    __device__ __forceinline__ u32 Rk(u32 i) const { return rk[i]; }
-    __device__ __forceinline__ i64 Rs(u32 i) const { return rs[i]; }
-    __device__ __forceinline__ i64 Pm(u32 i) const { return sm[i].v; }
-};
-// ... or from the workgroup's LDS copy of the stretch its rows need: heads [h0, h1), rights [r0, r1).  An index outside
-// raises `esc` and reads as 0 -- the caller then plans that row again from global memory.  (Every read here is an LDS
-// read; an accessor that falls back to global memory per access compiles to flat loads with full waits, 36 -> 46 ms.)
-struct SubLds {
-    const u32 *hk; const i64 *hrs; const u32 *hj; const u32 *rk; const i64 *rs; const i64 *pm;
-    u32 h0, hn, r0, rn;
-    mutable bool esc;
-    __device__ __forceinline__ u32 hi_(u32 i) const { const u32 x = i - h0; if (x >= hn) { esc = true; return 0u; } return x; }
-    __device__ __forceinline__ u32 ri_(u32 i) const { const u32 x = i - r0; if (x >= rn) { esc = true; return 0u; } return x; }
-    __device__ __forceinline__ u32 Hk(u32 i) const { return hk[hi_(i)]; }
-    __device__ __forceinline__ i64 Hrs(u32 i) const { return hrs[hi_(i)]; }
-    __device__ __forceinline__ u32 Hj(u32 i) const { return hj[hi_(i)]; }
-    __device__ __forceinline__ u32 Rk(u32 i) const { return rk[ri_(i)]; }
-    __device__ __forceinline__ i64 Rs(u32 i) const { return rs[ri_(i)]; }
-    __device__ __forceinline__ i64 Pm(u32 i) const { return pm[ri_(i)]; }
-};
-
+//
 // WF: every right row has start <= end (k_range64 says so).  Then the gap heads are the merged runs of the rights, the right_cursor
 // can never be behind the first head above ls (that head's own row ends beyond ls), and the walk's last right with rs <= le lies in
 // the run of the last head with rs <= le, whose final end is either the cursor or beyond le: TWO searches and one lookup instead of
@@ -714,111 +722,100 @@ __device__ __forceinline__ SubPlan plan_row(u32 k, i64 ls, i64 le, int strict, c
     return p;
 }
 
-// The workgroup's rows are consecutive rows of the sorted left side: the heads at or below its first and last row's start
-// bracket everybody's first search, and the heads / rights all its searches touch are a short stretch around that bracket
-// -- staged in LDS (SUB_HW heads, SUB_RW rights), so that the ~70 dependent reads of a row's five partition points are LDS
-// reads (11.7 -> ... ms for 200 M rows); a row whose searches leave the stretch (a long row, rights with end < start) is
-// planned again from global memory, and a workgroup whose stretch does not fit plans all its rows there.
-constexpr u32 SUB_HW = 256, SUB_RW = 640, SUB_MARGIN = 48;      // (17 KB of LDS: eight workgroups per CU)
-// brk[b] = heads at or below the start of the first left row of workgroup b (brk[#workgroups]: of the last row): one thread
-// per boundary, all searches in flight together.  (Done by two threads at the head of every k_sub_count workgroup, the two
-// full-length searches -- ~24 dependent reads -- held the other 254 threads up: 9 of the kernel's 11.7 ms.)
-__global__ __launch_bounds__(ST) void k_sub_brackets(const u32 *__restrict__ lk, const i64 *__restrict__ lsv, u64 nl, const u32 *hk, const i64 *hrs, u32 nh,
-                                                     u32 nblk, u32 *__restrict__ brk)
+// ---------------------------------------------------------------- fragments: one count pass, one fill pass, two operators
+//
+// subtract and intersect cut every left row into fragments with the same two passes over the SORTED left side; what differs
+// is what a row is searched in and what a fragment is, and that is an operator: SubOp, IsectOp (below).  An operator carries
+// its right side -- the arrays and their lengths -- and the arrays its rows' plan words go to, and defines
+//   bracket(...)           brk[b]: the first search's answer for the first left row of workgroup b, with the operator's rule for
+//                          a boundary at or behind the last row
+//   WIN, window(b0, b1, win)   the stretch of the right side that the searches of a workgroup with the bracket [b0, b1] touch
+//   fits(win)              ... is staged in LDS (Stage, stage(): all threads); else the whole workgroup plans from global memory
+//   whole(), staged(Stage, win, esc)   the right side as the row plan reads it: in global memory, in the staged window
+//   plan(view, row, b0, b1)   -> Plan: what the searches for one row find
+//   keep(i, Plan)          stores the row's plan words; -> its fragments
+//   Fill                   the fill pass's half: the arrays it reads, Kept = a workgroup's plan words in LDS, keep(Kept&, t, i),
+//                          and fragment(Kept, r, j, n, ls, le, fs, fe): fragment j of the n of row r = [fs, fe)
+//
+// k_frag_brackets.  The workgroup's rows are consecutive rows of the sorted left side: the first search's answers for its first
+// row and for the next workgroup's first row bracket everybody's, and what all its searches touch is a short stretch around
+// that bracket.  brk[b], one thread per workgroup boundary, all searches in flight together.  (Done by two threads at the head
+// of every count workgroup, the two full-length searches -- ~24 dependent reads -- held the other 254 threads up: 9 of
+// subtract's 11.7 ms.)
+template <class Op>
+__global__ __launch_bounds__(ST) void k_frag_brackets(const u32 *__restrict__ lk, const i64 *__restrict__ lsv, u64 nl, Op op, u32 nblk, u32 *__restrict__ brk)
 {
     const u32 b = blockIdx.x * ST + threadIdx.x;
     if (b > nblk) return;
-    const u64 r = b < nblk ? (u64)b * ST : nl - 1;
-    brk[b] = r < nl ? lex_rank(hk, hrs, nh, lk[r], lsv[r], true) : nh;
+    brk[b] = op.bracket(lk, lsv, nl, b, nblk);
 }
 
-// DEBUG (ivx_debug_subtract_paths, tests only): the same pass also says what it did -- per workgroup SUB_DBG_WORDS words
-// (brk[b], brk[b+1], h0, hn, r0, rn, lds, rows planned again after `esc`; all 0 for the workgroup that owns only cnt[nl]),
-// zeroed by the caller, and per left row, at its original index, whether its LDS plan raised `esc`.
-constexpr u32 SUB_DBG_WORDS = 8;
-template <bool DEBUG>
-__global__ __launch_bounds__(ST) void k_sub_count(const u32 *__restrict__ lk, const i64 *__restrict__ lsv, const i64 *__restrict__ lev, u64 nl,
-                                                  int strict, const u32 *hk, const i64 *hrs, const u32 *hj, u32 nh,
-                                                  const u32 *rk, const i64 *rs, const SegMax64 *sm, u32 nr, u64 *cnt,
-                                                  u32 *__restrict__ plan_hlo, i64 *__restrict__ plan_tail, const u32 *__restrict__ brk, int wf,
-                                                  u32 *dbg_wg, u8 *dbg_esc, const u32 *dbg_lrow)
+// k_frag_count, one thread per sorted left row: cnt[i] = its fragments, and its plan words stay for the fill pass, which does
+// not search again.  The window is staged in LDS, so that the dependent reads of a row's searches (~70 for subtract's five
+// partition points) are LDS reads (subtract: 11.7 -> 3.7 ms for 200 M rows); a row whose searches leave the window (a long row,
+// rights with end < start) is planned again from global memory, and a workgroup whose window does not fit plans all its rows
+// there.
+// DEBUG (the test hooks ivx_debug_subtract_paths / ivx_debug_intersect_paths): the same pass also says what it did -- per
+// workgroup frag_dbg_words<Op> words (brk[b], brk[b+1], the window, lds, rows planned again after `esc`; all 0 for the workgroup
+// that owns only cnt[nl]), zeroed by the caller, and per left row, at its original index, whether its LDS plan raised `esc`.
+template <class Op> constexpr u32 frag_dbg_words = Op::WIN + 4;
+template <class Op, bool DEBUG>
+__global__ __launch_bounds__(ST) void k_frag_count(const u32 *__restrict__ lk, const i64 *__restrict__ lsv, const i64 *__restrict__ lev, u64 nl,
+                                                   Op op, u64 *cnt, const u32 *__restrict__ brk, u32 *dbg_wg, u8 *dbg_esc, const u32 *dbg_lrow)
 {
-    __shared__ u32 s_h[2], s_win[4];
-    __shared__ u32 l_hk[SUB_HW], l_hj[SUB_HW], l_rk[SUB_RW];
-    __shared__ i64 l_hrs[SUB_HW], l_rs[SUB_RW], l_pm[SUB_RW];
+    __shared__ u32 s_h[2], s_win[Op::WIN];
+    __shared__ typename Op::Stage s_st;
     const u64 i0 = (u64)blockIdx.x * ST;
-    // the answers of the workgroup's first row and of the next workgroup's first row (the last row's, for the last
-    // workgroup) bracket everybody's first search: the left side is sorted
     if (threadIdx.x < 2 && i0 < nl) s_h[threadIdx.x] = brk[blockIdx.x + threadIdx.x];
     __syncthreads();
-    if (threadIdx.x == 0 && i0 < nl) {
-        const u32 h0 = s_h[0] > SUB_MARGIN + 1 ? s_h[0] - SUB_MARGIN - 1 : 0u;
-        const u32 h1 = nh - s_h[1] > SUB_MARGIN ? s_h[1] + SUB_MARGIN : nh;
-        const u32 r0 = h0 < nh ? hj[h0] : nr;
-        u32 r1 = h1 < nh ? hj[h1] : nr;
-        r1 = nr - r1 > SUB_MARGIN ? r1 + SUB_MARGIN : nr;
-        s_win[0] = h0; s_win[1] = h1 - h0; s_win[2] = r0 < r1 ? r0 : r1; s_win[3] = r1 > r0 ? r1 - r0 : 0u;
-    }
+    if (threadIdx.x == 0 && i0 < nl) op.window(s_h[0], s_h[1], s_win);
     __syncthreads();
-    const bool lds = i0 < nl && s_win[1] <= SUB_HW && s_win[3] <= SUB_RW;          // (the same for the whole workgroup)
+    const bool lds = i0 < nl && op.fits(s_win);                         // (the same for the whole workgroup)
     if constexpr (DEBUG) {
         if (threadIdx.x == 0 && i0 < nl) {
-            u32 *w = dbg_wg + (size_t)blockIdx.x * SUB_DBG_WORDS;
-            w[0] = s_h[0]; w[1] = s_h[1]; w[2] = s_win[0]; w[3] = s_win[1]; w[4] = s_win[2]; w[5] = s_win[3]; w[6] = lds ? 1u : 0u;
+            u32 *w = dbg_wg + (size_t)blockIdx.x * frag_dbg_words<Op>;
+            w[0] = s_h[0]; w[1] = s_h[1];
+            for (u32 q = 0; q < Op::WIN; q++) w[2 + q] = s_win[q];
+            w[2 + Op::WIN] = lds ? 1u : 0u;
         }
     }
-    if (lds) {
-        const u32 h0 = s_win[0], hn = s_win[1], r0 = s_win[2], rn = s_win[3];
-        for (u32 x = threadIdx.x; x < hn; x += ST) { l_hk[x] = hk[h0 + x]; l_hrs[x] = hrs[h0 + x]; l_hj[x] = hj[h0 + x]; }
-        for (u32 x = threadIdx.x; x < rn; x += ST) { l_rk[x] = rk[r0 + x]; l_rs[x] = rs[r0 + x]; l_pm[x] = sm[r0 + x].v; }
-        __syncthreads();
-    }
+    if (lds) { op.stage(s_st, s_win); __syncthreads(); }
     const u64 i = i0 + threadIdx.x;
     if (i > nl) return;
     if (i == nl) { cnt[i] = 0; return; }
     const u32 k = lk[i]; const i64 ls = lsv[i], le = lev[i];
-    const SubGlobal g{hk, hrs, hj, rk, rs, sm};
-    SubPlan p;
-    bool redo = !lds;
-    if (lds) {
-        SubLds a{l_hk, l_hrs, l_hj, l_rk, l_rs, l_pm, s_win[0], s_win[1], s_win[2], s_win[3], false};
-        p = wf ? plan_row<SubLds, true>(k, ls, le, strict, a, nh, nr, s_h[0], s_h[1]) : plan_row<SubLds, false>(k, ls, le, strict, a, nh, nr, s_h[0], s_h[1]);
-        redo = a.esc;
-    }
+    typename Op::Plan p;
+    bool esc = false;
+    if (lds) p = op.plan(op.staged(s_st, s_win, esc), k, ls, le, s_h[0], s_h[1]);
     if constexpr (DEBUG) {
-        const bool esc = lds && redo;
         dbg_esc[dbg_lrow[i]] = esc ? 1 : 0;
-        if (esc) atomicAdd(dbg_wg + (size_t)blockIdx.x * SUB_DBG_WORDS + 7, 1u);
+        if (esc) atomicAdd(dbg_wg + (size_t)blockIdx.x * frag_dbg_words<Op> + 3 + Op::WIN, 1u);
     }
-    if (redo) p = wf ? plan_row<SubGlobal, true>(k, ls, le, strict, g, nh, nr, s_h[0], s_h[1]) : plan_row<SubGlobal, false>(k, ls, le, strict, g, nh, nr, s_h[0], s_h[1]);
-    cnt[i] = (u64)(p.h_hi - p.h_lo) + p.has_tail;
-    // the row's plan stays for the fill pass (12 bytes per row instead of the five searches again): its first head and
-    // where its tail fragment starts; the number of heads follows from the scanned counts, has_tail from tail < end
-    plan_hlo[i] = p.h_lo; plan_tail[i] = p.tail_from;
+    if (!lds || esc) p = op.plan(op.whole(), k, ls, le, s_h[0], s_h[1]);
+    cnt[i] = op.keep(i, p);
 }
 
-// Fragments of ST consecutive left rows, one thread per OUTPUT row: the rows' plans (k_sub_count) and scanned counts
-// are staged in LDS, a thread finds the left row of its fragment there by bisection and writes the fragment -- the
+// k_frag_fill.  Fragments of ST consecutive left rows, one thread per OUTPUT row: the rows, their plan words and their scanned
+// counts are staged in LDS, a thread finds the left row of its fragment there by bisection and writes the fragment -- the
 // stores of a wavefront are consecutive whatever the rows' fragment counts are (a thread per left row looping over its
-// fragments wrote strided, divergent runs: 9.1 ms for 564 M fragments).
-__global__ __launch_bounds__(ST) void k_sub_fill(const u32 *__restrict__ lk, const i64 *__restrict__ lsv, const i64 *__restrict__ lev,
-                                                 const u32 *__restrict__ lrow, u64 nl, int strict,
-                                                 const u32 *hk, const i64 *hrs, const i64 *hpm, const u32 *hj, u32 nh,
-                                                 const u32 *rk, const i64 *rs, const SegMax64 *sm, u32 nr,
-                                                 const u64 *__restrict__ offs, u64 cap,
-                                                 u32 *ok, i64 *os, i64 *oe, u32 *orow,
-                                                 const u32 *__restrict__ plan_hlo, const i64 *__restrict__ plan_tail)
+// fragments wrote strided, divergent runs: 9.1 ms for subtract's 564 M fragments).  The host has refused a total beyond the
+// output columns' capacity.
+template <class F>
+__global__ __launch_bounds__(ST) void k_frag_fill(const u32 *__restrict__ lk, const i64 *__restrict__ lsv, const i64 *__restrict__ lev,
+                                                  const u32 *__restrict__ lrow, u64 nl, F f, const u64 *__restrict__ offs,
+                                                  u32 *ok, i64 *os, i64 *oe, u32 *orow)
 {
     __shared__ u64 s_off[ST + 1];
-    __shared__ i64 s_ls[ST], s_le[ST], s_tail[ST];
-    __shared__ u32 s_k[ST], s_row[ST], s_hlo[ST];
+    __shared__ i64 s_ls[ST], s_le[ST];
+    __shared__ u32 s_k[ST], s_row[ST];
+    __shared__ typename F::Kept s_kept;
     const u64 i0 = (u64)blockIdx.x * ST;
     const u32 nrows = (u32)(nl - i0 < (u64)ST ? nl - i0 : (u64)ST);
     const u32 t = threadIdx.x;
     if (t < nrows) {
         const u64 i = i0 + t;
-        s_off[t] = offs[i]; s_k[t] = lk[i]; s_ls[t] = lsv[i]; s_le[t] = lev[i]; s_row[t] = lrow ? lrow[i] : 0u;
-        s_hlo[t] = plan_hlo[i]; s_tail[t] = plan_tail[i];
+        s_off[t] = offs[i]; s_k[t] = lk[i]; s_ls[t] = lsv[i]; s_le[t] = lev[i]; s_row[t] = lrow[i];
+        f.keep(s_kept, t, i);
     }
     if (t == 0) s_off[nrows] = offs[i0 + nrows];
     __syncthreads();
@@ -826,26 +823,82 @@ __global__ __launch_bounds__(ST) void k_sub_fill(const u32 *__restrict__ lk, con
     const u64 total = s_off[nrows] - base;
     for (u64 o = t; o < total; o += ST) {
         const u64 at = base + o;
-        if (at >= cap) return;
         u32 lo = 0, hi = nrows - 1;                                     // last row r with s_off[r] <= at
         while (lo < hi) { const u32 mid = (lo + hi + 1) >> 1; if (s_off[mid] <= at) lo = mid; else hi = mid - 1; }
         const u32 r = lo;
-        const u32 j = (u32)(at - s_off[r]);
-        const i64 ls = s_ls[r], le = s_le[r];
-        const u32 has_tail = s_tail[r] < le ? 1u : 0u;
-        const u32 nheads = (u32)(s_off[r + 1] - s_off[r]) - has_tail;
         i64 fs, fe;
-        if (j < nheads) {                                               // [cursor, rs)  subtract.rs:423-428
-            const u32 h = s_hlo[r] + j;
-            const i64 pm = hpm[h];
-            fs = pm > ls ? pm : ls; fe = hrs[h];
-        } else { fs = s_tail[r]; fe = le; }                             // [cursor, le)  :435-440
+        f.fragment(s_kept, r, (u32)(at - s_off[r]), (u32)(s_off[r + 1] - s_off[r]), s_ls[r], s_le[r], fs, fe);
         if (ok) ok[at] = s_k[r];
         if (os) os[at] = fs;
         if (oe) oe[at] = fe;
         if (orow) orow[at] = s_row[r];
     }
 }
+
+// ---- subtract's operator.  The window: SUB_MARGIN heads around the bracket and the rights under them (SUB_HW heads, SUB_RW
+// rights: 17 KB of LDS, eight workgroups per CU).  A boundary of the grid whose row is past the last one takes nh.  The plan
+// words (12 bytes per row instead of the five searches again): the row's first head and where its tail fragment starts; the
+// number of heads follows from the scanned counts, has_tail from tail < end.
+constexpr u32 SUB_HW = 256, SUB_RW = 640, SUB_MARGIN = 48;
+struct SubOp {
+    const u32 *hk; const i64 *hrs; const u32 *hj; u32 nh;               // gap heads: key, start, right row
+    const u32 *rk; const i64 *rs; const SegMax64 *sm; u32 nr;           // rights: key, start, running max of the ends
+    int strict, wf;
+    u32 *plan_hlo; i64 *plan_tail;
+    static constexpr u32 WIN = 4;
+    struct Stage { i64 hrs[SUB_HW], rs[SUB_RW], pm[SUB_RW]; u32 hk[SUB_HW], hj[SUB_HW], rk[SUB_RW]; };
+    using Plan = SubPlan;
+    __device__ __forceinline__ u32 bracket(const u32 *lk, const i64 *lsv, u64 nl, u32 b, u32 nblk) const
+    {
+        const u64 r = b < nblk ? (u64)b * ST : nl - 1;
+        return r < nl ? lex_rank(hk, hrs, nh, lk[r], lsv[r], true) : nh;   // heads at or below the row's start
+    }
+    __device__ __forceinline__ void window(u32 b0, u32 b1, u32 *win) const
+    {
+        const u32 h0 = b0 > SUB_MARGIN + 1 ? b0 - SUB_MARGIN - 1 : 0u;
+        const u32 h1 = nh - b1 > SUB_MARGIN ? b1 + SUB_MARGIN : nh;
+        const u32 r0 = h0 < nh ? hj[h0] : nr;
+        u32 r1 = h1 < nh ? hj[h1] : nr;
+        r1 = nr - r1 > SUB_MARGIN ? r1 + SUB_MARGIN : nr;
+        win[0] = h0; win[1] = h1 - h0; win[2] = r0 < r1 ? r0 : r1; win[3] = r1 > r0 ? r1 - r0 : 0u;
+    }
+    __device__ __forceinline__ bool fits(const u32 *win) const { return win[1] <= SUB_HW && win[3] <= SUB_RW; }
+    __device__ __forceinline__ void stage(Stage &s, const u32 *win) const
+    {
+        const u32 h0 = win[0], hn = win[1], r0 = win[2], rn = win[3];
+        for (u32 x = threadIdx.x; x < hn; x += ST) { s.hk[x] = hk[h0 + x]; s.hrs[x] = hrs[h0 + x]; s.hj[x] = hj[h0 + x]; }
+        for (u32 x = threadIdx.x; x < rn; x += ST) { s.rk[x] = rk[r0 + x]; s.rs[x] = rs[r0 + x]; s.pm[x] = sm[r0 + x].v; }
+    }
+    __device__ __forceinline__ auto whole() const { return SubView<Whole, SegMax64>{hk, hrs, hj, rk, rs, sm, {}, {}}; }
+    __device__ __forceinline__ auto staged(const Stage &s, const u32 *win, bool &esc) const
+    {
+        return SubView<Window, i64>{s.hk, s.hrs, s.hj, s.rk, s.rs, s.pm, {win[0], win[1], esc}, {win[2], win[3], esc}};
+    }
+    template <class V> __device__ __forceinline__ SubPlan plan(const V &v, u32 k, i64 ls, i64 le, u32 b0, u32 b1) const
+    {
+        return wf ? plan_row<V, true>(k, ls, le, strict, v, nh, nr, b0, b1) : plan_row<V, false>(k, ls, le, strict, v, nh, nr, b0, b1);
+    }
+    __device__ __forceinline__ u64 keep(u64 i, const SubPlan &p) const
+    {
+        plan_hlo[i] = p.h_lo; plan_tail[i] = p.tail_from;
+        return (u64)(p.h_hi - p.h_lo) + p.has_tail;
+    }
+    struct Fill {
+        const i64 *hrs, *hpm;                                           // gap heads: start, running max of the right ends before it
+        const u32 *plan_hlo; const i64 *plan_tail;
+        struct Kept { i64 tail[ST]; u32 hlo[ST]; };
+        __device__ __forceinline__ void keep(Kept &s, u32 t, u64 i) const { s.hlo[t] = plan_hlo[i]; s.tail[t] = plan_tail[i]; }
+        __device__ __forceinline__ void fragment(const Kept &s, u32 r, u32 j, u32 n, i64 ls, i64 le, i64 &fs, i64 &fe) const
+        {
+            const u32 nheads = n - (s.tail[r] < le ? 1u : 0u);
+            if (j < nheads) {                                           // [cursor, rs)  subtract.rs:423-428
+                const u32 h = s.hlo[r] + j;
+                const i64 pm = hpm[h];
+                fs = pm > ls ? pm : ls; fe = hrs[h];
+            } else { fs = s.tail[r]; fe = le; }                         // [cursor, le)  :435-440
+        }
+    };
+};
 
 // ---------------------------------------------------------------- intersect
 //
@@ -857,32 +910,19 @@ __global__ __launch_bounds__(ST) void k_sub_fill(const u32 *__restrict__ lk, con
 // -- two partition points, the second a few runs after the first -- and piece j of the row is run a + j clipped to it.
 // (b < a only for ls == le in strict mode on an empty run at that very point: such a row overlaps nothing.)
 
-// the runs as plan_isect reads them: from global memory ...
-struct IsectGlobal {
+// the runs as plan_isect reads them, through a Whole or a Window (as SubView)
+template <class Ix>
+struct IsectView {
     const u32 *mk; const i64 *ms, *me;
-    __device__ __forceinline__ u32 K(u32 i) const { return mk[i]; }
-    __device__ __forceinline__ i64 S(u32 i) const { return ms[i]; }
-    __device__ __forceinline__ i64 E(u32 i) const { return me[i]; }
-    __device__ __forceinline__ u32 end(u32 m) const { return m; }
-    __device__ __forceinline__ void reached(u32, u32) const {}
-};
-// ... or from the workgroup's LDS copy of runs [w0, w0 + wn).  An index outside raises `esc` and reads slot 0: the caller
-// plans that row again from global memory.  (Two types, as SubGlobal / SubLds and for their reason: every read here is an
-// LDS read.)
-struct IsectLds {
-    const u32 *mk; const i64 *ms, *me;
-    u32 w0, wn;
-    mutable bool esc;
-    __device__ __forceinline__ u32 at(u32 i) const { const u32 x = i - w0; if (x >= wn) { esc = true; return 0u; } return x; }
+    Ix at;
     __device__ __forceinline__ u32 K(u32 i) const { return mk[at(i)]; }
     __device__ __forceinline__ i64 S(u32 i) const { return ms[at(i)]; }
     __device__ __forceinline__ i64 E(u32 i) const { return me[at(i)]; }
-    // the gallop stops at the stretch's end: an answer AT that end, short of all runs, may lie beyond it
-    __device__ __forceinline__ u32 end(u32 m) const { const u32 we = w0 + wn; return we < m ? we : m; }
-    __device__ __forceinline__ void reached(u32 b, u32 m) const { if (b == w0 + wn && b < m) esc = true; }
+    __device__ __forceinline__ u32 end(u32 m) const { return at.end(m); }
+    __device__ __forceinline__ void reached(u32 b, u32 m) const { at.reached(b, m); }
 };
 
-// [ha, hb]: bounds of the first search (the caller's workgroup holds consecutive rows of the sorted left side, see k_sub_count)
+// [ha, hb]: bounds of the first search (the caller's workgroup holds consecutive rows of the sorted left side, see k_frag_brackets)
 template <class A>
 __device__ __forceinline__ void plan_isect(u32 k, i64 ls, i64 le, int strict, const A &r, u32 m, u32 ha, u32 hb, u32 &a, u32 &b)
 {
@@ -894,19 +934,59 @@ __device__ __forceinline__ void plan_isect(u32 k, i64 ls, i64 le, int strict, co
     if (b < a) b = a;
 }
 
-// The runs a workgroup's searches touch are the stretch from its bracket's low end (one below: the gallop looks at its start's
-// predecessor) to ISECT_MARGIN past its high end, staged in LDS as (key, ms, me) when that is at most ISECT_RW runs
-constexpr u32 ISECT_RW = 832, ISECT_MARGIN = 48;                // (16.6 KB of LDS: eight workgroups per CU)
-// brk[b] = the `a` of the first left row of workgroup b, one thread per boundary as k_sub_brackets; a boundary at or behind
-// the last row takes that row's (nl a multiple of ST: the last rows' workgroup is followed by one that owns only cnt[nl])
-__global__ __launch_bounds__(ST) void k_isect_brackets(const u32 *__restrict__ lk, const i64 *__restrict__ lsv, u64 nl, const u32 *mk, const i64 *me, u32 m,
-                                                       int strict, u32 nblk, u32 *__restrict__ brk)
-{
-    const u32 b = blockIdx.x * ST + threadIdx.x;
-    if (b > nblk) return;
-    const u64 r = (u64)b * ST < nl ? (u64)b * ST : nl - 1;              // (nl > 0)
-    brk[b] = lex_rank(mk, me, m, lk[r], lsv[r], strict != 0);
-}
+// ---- intersect's operator.  The window: the runs from the bracket's low end (one below: the gallop looks at its start's
+// predecessor) to ISECT_MARGIN past its high end, staged as (key, ms, me) when that is at most ISECT_RW runs (16.6 KB of LDS:
+// eight workgroups per CU).  brk[b] is the `a` of the workgroup's first row; a boundary at or behind the last row takes that
+// row's (nl a multiple of ST: the last rows' workgroup is followed by one that owns only cnt[nl]).  The plan word: the row's
+// first run.
+constexpr u32 ISECT_RW = 832, ISECT_MARGIN = 48;
+struct IsectOp {
+    const u32 *mk; const i64 *ms, *me; u32 m;                           // the right side's merged runs
+    int strict;
+    u32 *plan_a;
+    static constexpr u32 WIN = 2;
+    struct Stage { i64 s[ISECT_RW], e[ISECT_RW]; u32 k[ISECT_RW]; };
+    struct Plan { u32 a, b; };
+    __device__ __forceinline__ u32 bracket(const u32 *lk, const i64 *lsv, u64 nl, u32 b, u32) const
+    {
+        const u64 r = (u64)b * ST < nl ? (u64)b * ST : nl - 1;          // (nl > 0)
+        return lex_rank(mk, me, m, lk[r], lsv[r], strict != 0);
+    }
+    __device__ __forceinline__ void window(u32 b0, u32 b1, u32 *win) const
+    {
+        const u32 w0 = b0 > 0 ? b0 - 1 : 0u;
+        const u32 w1 = m - b1 > ISECT_MARGIN ? b1 + ISECT_MARGIN : m;
+        win[0] = w0; win[1] = w1 - w0;
+    }
+    __device__ __forceinline__ bool fits(const u32 *win) const { return win[1] <= ISECT_RW; }
+    __device__ __forceinline__ void stage(Stage &s, const u32 *win) const
+    {
+        const u32 w0 = win[0], wn = win[1];
+        for (u32 x = threadIdx.x; x < wn; x += ST) { s.k[x] = mk[w0 + x]; s.s[x] = ms[w0 + x]; s.e[x] = me[w0 + x]; }
+    }
+    __device__ __forceinline__ auto whole() const { return IsectView<Whole>{mk, ms, me, {}}; }
+    __device__ __forceinline__ auto staged(const Stage &s, const u32 *win, bool &esc) const { return IsectView<Window>{s.k, s.s, s.e, {win[0], win[1], esc}}; }
+    template <class V> __device__ __forceinline__ Plan plan(const V &v, u32 k, i64 ls, i64 le, u32 b0, u32 b1) const
+    {
+        Plan p;
+        plan_isect(k, ls, le, strict, v, m, b0, b1, p.a, p.b);
+        return p;
+    }
+    __device__ __forceinline__ u64 keep(u64 i, const Plan &p) const { plan_a[i] = p.a; return (u64)(p.b - p.a); }
+    struct Fill {
+        const i64 *ms, *me;
+        const u32 *plan_a;
+        struct Kept { u32 a[ST]; };
+        __device__ __forceinline__ void keep(Kept &s, u32 t, u64 i) const { s.a[t] = plan_a[i]; }
+        // piece j: run a + j clipped to the row
+        __device__ __forceinline__ void fragment(const Kept &s, u32 r, u32 j, u32, i64 ls, i64 le, i64 &fs, i64 &fe) const
+        {
+            const u32 run = s.a[r] + j;
+            const i64 rs = ms[run], re = me[run];
+            fs = rs > ls ? rs : ls; fe = re < le ? re : le;
+        }
+    };
+};
 
 // the checks of the sorts' range pass alone, for the side that faces an empty one (nothing is sorted then): flags[0] a key id
 // >= nkeys, flags[1] a row with end < start
@@ -916,99 +996,6 @@ __global__ __launch_bounds__(ST) void k_isect_check(const u32 *__restrict__ key,
     if (i >= n) return;
     if (key && key[i] >= nkeys) flags[0] = 1;
     if (e[i] < s[i]) flags[1] = 1;
-}
-
-// One thread per sorted left row: cnt[i] = its pieces, plan_a[i] = its first run (the fill pass does not search again).
-// DEBUG (ivx_debug_intersect_paths, tests only): per workgroup ISECT_DBG_WORDS words (brk[b], brk[b+1], w0, wn, lds, rows
-// planned again after `esc`; all 0 for the workgroup that owns only cnt[nl]), zeroed by the caller, and per left row, at
-// its original index, whether its LDS plan raised `esc`.
-constexpr u32 ISECT_DBG_WORDS = 6;
-template <bool DEBUG>
-__global__ __launch_bounds__(ST) void k_isect_count(const u32 *__restrict__ lk, const i64 *__restrict__ lsv, const i64 *__restrict__ lev, u64 nl,
-                                                    int strict, const u32 *mk, const i64 *ms, const i64 *me, u32 m, u64 *cnt,
-                                                    u32 *__restrict__ plan_a, const u32 *__restrict__ brk,
-                                                    u32 *dbg_wg, u8 *dbg_esc, const u32 *dbg_lrow)
-{
-    __shared__ u32 s_h[2], s_win[2];
-    __shared__ u32 l_k[ISECT_RW];
-    __shared__ i64 l_s[ISECT_RW], l_e[ISECT_RW];
-    const u64 i0 = (u64)blockIdx.x * ST;
-    if (threadIdx.x < 2 && i0 < nl) s_h[threadIdx.x] = brk[blockIdx.x + threadIdx.x];
-    __syncthreads();
-    if (threadIdx.x == 0 && i0 < nl) {
-        const u32 w0 = s_h[0] > 0 ? s_h[0] - 1 : 0u;
-        const u32 w1 = m - s_h[1] > ISECT_MARGIN ? s_h[1] + ISECT_MARGIN : m;
-        s_win[0] = w0; s_win[1] = w1 - w0;
-    }
-    __syncthreads();
-    const bool lds = i0 < nl && s_win[1] <= ISECT_RW;                   // (the same for the whole workgroup)
-    if constexpr (DEBUG) {
-        if (threadIdx.x == 0 && i0 < nl) {
-            u32 *w = dbg_wg + (size_t)blockIdx.x * ISECT_DBG_WORDS;
-            w[0] = s_h[0]; w[1] = s_h[1]; w[2] = s_win[0]; w[3] = s_win[1]; w[4] = lds ? 1u : 0u;
-        }
-    }
-    if (lds) {
-        const u32 w0 = s_win[0], wn = s_win[1];
-        for (u32 x = threadIdx.x; x < wn; x += ST) { l_k[x] = mk[w0 + x]; l_s[x] = ms[w0 + x]; l_e[x] = me[w0 + x]; }
-        __syncthreads();
-    }
-    const u64 i = i0 + threadIdx.x;
-    if (i > nl) return;
-    if (i == nl) { cnt[i] = 0; return; }
-    const u32 k = lk[i]; const i64 ls = lsv[i], le = lev[i];
-    u32 a = 0, b = 0;
-    bool redo = !lds;
-    if (lds) {
-        const IsectLds r{l_k, l_s, l_e, s_win[0], s_win[1], false};
-        plan_isect(k, ls, le, strict, r, m, s_h[0], s_h[1], a, b);
-        redo = r.esc;
-    }
-    if constexpr (DEBUG) {
-        const bool esc = lds && redo;
-        dbg_esc[dbg_lrow[i]] = esc ? 1 : 0;
-        if (esc) atomicAdd(dbg_wg + (size_t)blockIdx.x * ISECT_DBG_WORDS + 5, 1u);
-    }
-    if (redo) { const IsectGlobal g{mk, ms, me}; plan_isect(k, ls, le, strict, g, m, s_h[0], s_h[1], a, b); }
-    cnt[i] = (u64)(b - a);
-    plan_a[i] = a;
-}
-
-// Pieces of ST consecutive left rows, one thread per OUTPUT row (as k_sub_fill): the rows, their first runs and their scanned
-// counts are staged in LDS, a thread finds the left row of its piece there by bisection, reads run a + j and writes the run
-// clipped to the row -- a wavefront's stores are consecutive whatever the rows' piece counts are
-__global__ __launch_bounds__(ST) void k_isect_fill(const u32 *__restrict__ lk, const i64 *__restrict__ lsv, const i64 *__restrict__ lev,
-                                                   const u32 *__restrict__ lrow, u64 nl, const i64 *__restrict__ ms, const i64 *__restrict__ me,
-                                                   const u64 *__restrict__ offs, const u32 *__restrict__ plan_a, u64 cap,
-                                                   u32 *ok, i64 *os, i64 *oe, u32 *orow)
-{
-    __shared__ u64 s_off[ST + 1];
-    __shared__ i64 s_ls[ST], s_le[ST];
-    __shared__ u32 s_k[ST], s_row[ST], s_a[ST];
-    const u64 i0 = (u64)blockIdx.x * ST;
-    const u32 nrows = (u32)(nl - i0 < (u64)ST ? nl - i0 : (u64)ST);
-    const u32 t = threadIdx.x;
-    if (t < nrows) {
-        const u64 i = i0 + t;
-        s_off[t] = offs[i]; s_k[t] = lk[i]; s_ls[t] = lsv[i]; s_le[t] = lev[i]; s_row[t] = lrow[i]; s_a[t] = plan_a[i];
-    }
-    if (t == 0) s_off[nrows] = offs[i0 + nrows];
-    __syncthreads();
-    const u64 base = s_off[0];
-    const u64 total = s_off[nrows] - base;
-    for (u64 o = t; o < total; o += ST) {
-        const u64 at = base + o;
-        if (at >= cap) return;
-        u32 lo = 0, hi = nrows - 1;                                     // last row r with s_off[r] <= at
-        while (lo < hi) { const u32 mid = (lo + hi + 1) >> 1; if (s_off[mid] <= at) lo = mid; else hi = mid - 1; }
-        const u32 r = lo;
-        const u32 run = s_a[r] + (u32)(at - s_off[r]);
-        const i64 ls = s_ls[r], le = s_le[r], rs = ms[run], re = me[run];
-        if (ok) ok[at] = s_k[r];
-        if (os) os[at] = rs > ls ? rs : ls;
-        if (oe) oe[at] = re < le ? re : le;
-        if (orow) orow[at] = s_row[r];
-    }
 }
 
 ivx_status keyflag(ivx_ctx *ctx, const char *what) { return ctx->check_flag(SC_SWEEP_FLAG, ctx->stream, what); }
@@ -1170,6 +1157,73 @@ __global__ __launch_bounds__(ST) void k_comp_fill_serial(const u32 *__restrict__
     else view_walk_serial(R, k, ws[i], we[i], put);
 }
 
+// ---------------------------------------------------------------- host pieces the entry points share
+
+// Sort the rows by (key, start, end) and merge them into runs (min_dist, strict): the runs' columns to ro, their number to *m.
+// The sweep runs over the packed sort words where that applies, else over the sorted rows (ivx_runs.hpp).  The form words and
+// the pinned Range64 are sort64's.  inverted (nullable): the refusal of a row with end < start, ahead of the sweep.
+ivx_status sorted_runs(ivx_ctx *ctx, const u32 *key, const i64 *s, const i64 *e, u64 n, u32 nkeys, i64 min_dist, int strict,
+                       const ivx_runs_out &ro, u64 *m, const char *inverted = nullptr)
+{
+    u32 *ks; i64 *ss, *es;
+    IVX_TRY(ctx->get_scratch(WS_T0, n * sizeof(u32), (void **)&ks));
+    IVX_TRY(ctx->get_scratch(WS_T1, n * sizeof(i64), (void **)&ss));
+    IVX_TRY(ctx->get_scratch(WS_T2, n * sizeof(i64), (void **)&es));
+    SortedRows rows;
+    PackedWant pk{min_dist, strict, false, nullptr, Pack64{}};
+    IVX_TRY(sort64(ctx, WS_SA0, WS_SB0, key, s, e, n, nkeys, ks, ss, es, nullptr, &rows, &pk));
+    if (inverted && (ctx->hword<Range64>(SC_RANGE)->odd & 1ull)) return ctx->fail(IVX_ERR_INVALID, inverted);
+    if (pk.ok) return ivx_merge_runs_packed(ctx, pk.w, n, pk.p, min_dist, strict, ro, m);
+    return ivx_merge_runs_rows(ctx, rows, n, min_dist, strict, ro, m);
+}
+
+// the left side of a fragment operator: its rows sorted by (key, start, end, row), with their input indices
+struct FragLeft { const u32 *k; const i64 *s, *e; const u32 *row; u64 n; };
+
+// The count pass on the context's stream: brackets, count, scan; *total = the fragments of all rows, cnt = their offsets.
+// rep (nullable; the test hooks): host buffers for what the pass did (k_frag_count's DEBUG) and the scratch slots of their
+// device copies; the copies are complete when this returns.
+struct FragReport { u32 *wg; u8 *row_esc; int wg_slot, esc_slot; };
+template <class Op>
+ivx_status frag_count(ivx_ctx *ctx, const FragLeft &L, const Op &op, u64 *cnt, const FragReport *rep, u64 *total)
+{
+    hipStream_t st = ctx->stream;
+    const u32 nblk = grid1(L.n + 1);
+    u32 *brk;
+    IVX_TRY(ctx->get_scratch(WS_GRID0, ((size_t)nblk + 2) * sizeof(u32), (void **)&brk));
+    hipLaunchKernelGGL(k_frag_brackets<Op>, dim3(grid1((u64)nblk + 1)), dim3(ST), 0, st, L.k, L.s, L.n, op, nblk, brk);
+    if (!rep)
+        hipLaunchKernelGGL((k_frag_count<Op, false>), dim3(nblk), dim3(ST), 0, st, L.k, L.s, L.e, L.n, op, cnt, (const u32 *)brk,
+                           (u32 *)nullptr, (u8 *)nullptr, (const u32 *)nullptr);
+    else {
+        u32 *d_wg; u8 *d_esc;
+        const size_t wg_bytes = (size_t)nblk * frag_dbg_words<Op> * sizeof(u32);
+        IVX_TRY(ctx->get_scratch(rep->wg_slot, wg_bytes, (void **)&d_wg));
+        IVX_TRY(ctx->get_scratch(rep->esc_slot, L.n, (void **)&d_esc));
+        IVX_HIP(ctx, hipMemsetAsync(d_wg, 0, wg_bytes, st));
+        hipLaunchKernelGGL((k_frag_count<Op, true>), dim3(nblk), dim3(ST), 0, st, L.k, L.s, L.e, L.n, op, cnt, (const u32 *)brk, d_wg, d_esc, L.row);
+        IVX_HIP(ctx, hipMemcpyAsync(rep->wg, d_wg, wg_bytes, hipMemcpyDeviceToHost, st));
+        IVX_HIP(ctx, hipMemcpyAsync(rep->row_esc, d_esc, L.n, hipMemcpyDeviceToHost, st));
+    }
+    IVX_HIP(ctx, hipGetLastError());
+    IVX_TRY(ivx_scan_exclusive_u64(ctx, cnt, L.n + 1));
+    return ctx->fetch_wait((const u64 *)cnt + L.n, st, total);          // (lands in the scalar table's SC_LANDING; synchronises)
+}
+
+// What a call does once its total is known: without capacity and output columns it only sizes, with buffers too small it is
+// refused (`small`), else the fill pass runs
+template <class F>
+ivx_status frag_fill(ivx_ctx *ctx, const FragLeft &L, const F &f, const u64 *offs, u64 total, u64 cap, const char *small,
+                     u32 *ok, i64 *os, i64 *oe, u32 *orow)
+{
+    if (cap == 0 && !ok && !os && !oe && !orow) return IVX_OK;
+    if (total > cap) return ctx->fail(IVX_ERR_CAPACITY, small);
+    if (total == 0) return IVX_OK;
+    hipLaunchKernelGGL(k_frag_fill<F>, dim3(grid1(L.n)), dim3(ST), 0, ctx->stream, L.k, L.s, L.e, L.row, L.n, f, offs, ok, os, oe, orow);
+    IVX_HIP(ctx, hipGetLastError());
+    return IVX_OK;
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------------------------ device entry points
@@ -1181,16 +1235,7 @@ ivx_status ivx_merge_device(ivx_ctx *ctx, const u32 *key, const i64 *s, const i6
     for (u32 &f : ctx->sweep_form) f = 0;
     if (n == 0) return IVX_OK;
     IVX_HIP(ctx, hipMemsetAsync(ctx->dword(SC_SWEEP_FLAG), 0, sizeof(u64), ctx->stream));
-    u32 *ks; i64 *ss, *es;
-    IVX_TRY(ctx->get_scratch(WS_T0, n * sizeof(u32), (void **)&ks));
-    IVX_TRY(ctx->get_scratch(WS_T1, n * sizeof(i64), (void **)&ss));
-    IVX_TRY(ctx->get_scratch(WS_T2, n * sizeof(i64), (void **)&es));
-    SortedRows rows;
-    PackedWant pk{min_dist, strict, false, nullptr, Pack64{}};
-    IVX_TRY(sort64(ctx, WS_SA0, WS_SB0, key, s, e, n, nkeys, ks, ss, es, nullptr, &rows, &pk));
-    ivx_runs_out ro{ok, os, oe, on};
-    if (pk.ok) IVX_TRY(ivx_merge_runs_packed(ctx, pk.w, n, pk.p, min_dist, strict, ro, m));
-    else IVX_TRY(ivx_merge_runs_rows(ctx, rows, n, min_dist, strict, ro, m));
+    IVX_TRY(sorted_runs(ctx, key, s, e, n, nkeys, min_dist, strict, ivx_runs_out{ok, os, oe, on}, m));
     return keyflag(ctx, "merge: key id >= n_keys");
 }
 
@@ -1208,6 +1253,7 @@ ivx_status ivx_subtract_device(ivx_ctx *ctx, const u32 *lkey, const i64 *ls, con
     IVX_TRY(ctx->get_scratch(WS_T2, nl * sizeof(i64), (void **)&lev));
     IVX_TRY(ctx->get_scratch(WS_T3, nl * sizeof(u32), (void **)&lrow));
     IVX_TRY(sort64(ctx, WS_SA0, WS_SB0, lkey, ls, le, nl, nkeys, lk, lsv, lev, lrow));
+    const FragLeft L{lk, lsv, lev, lrow, nl};
     const u64 nra = nr ? nr : 1;
     IVX_TRY(ctx->get_scratch(WS_T4, nra * sizeof(u32), (void **)&rk));
     IVX_TRY(ctx->get_scratch(WS_T5, nra * sizeof(i64), (void **)&rsv));
@@ -1243,78 +1289,57 @@ ivx_status ivx_subtract_device(ivx_ctx *ctx, const u32 *lkey, const i64 *ls, con
     IVX_TRY(ctx->get_scratch(WS_RA2, (nl + 1) * sizeof(u64), (void **)&cnt));
     IVX_TRY(ctx->get_scratch(WS_RB1, nl * sizeof(u32), (void **)&plan_hlo));
     IVX_TRY(ctx->get_scratch(WS_RB2, nl * sizeof(i64), (void **)&plan_tail));
-    const u32 nblk_c = grid1(nl + 1);
-    u32 *brk;
-    IVX_TRY(ctx->get_scratch(WS_GRID0, ((size_t)nblk_c + 2) * sizeof(u32), (void **)&brk));
-    hipLaunchKernelGGL(k_sub_brackets, dim3(grid1((u64)nblk_c + 1)), dim3(ST), 0, st, (const u32 *)lk, (const i64 *)lsv, nl, (const u32 *)hk, (const i64 *)hrs, (u32)nh, nblk_c, brk);
-    hipLaunchKernelGGL(k_sub_count<false>, dim3(nblk_c), dim3(ST), 0, st, (const u32 *)lk, (const i64 *)lsv, (const i64 *)lev, nl, strict,
-                       (const u32 *)hk, (const i64 *)hrs, (const u32 *)hj, (u32)nh, (const u32 *)rk, (const i64 *)rsv, (const SegMax64 *)sm, (u32)nr, cnt,
-                       plan_hlo, plan_tail, (const u32 *)brk, wf, (u32 *)nullptr, (u8 *)nullptr, (const u32 *)nullptr);
-    IVX_TRY(ivx_scan_exclusive_u64(ctx, cnt, nl + 1));
     u64 total;
-    IVX_TRY(ctx->fetch_wait((const u64 *)cnt + nl, st, &total));
+    IVX_TRY(frag_count(ctx, L, SubOp{hk, hrs, hj, (u32)nh, rk, rsv, sm, (u32)nr, strict, wf, plan_hlo, plan_tail}, cnt, nullptr, &total));
     *n_out = total;
     ivx_sub_plan &pl = ctx->sub_plan;
     pl.nl = nl; pl.nr = nr; pl.nh = nh; pl.total = total; pl.nkeys = nkeys; pl.strict = strict; pl.stream = st;
-    pl.lk = lk; pl.lsv = lsv; pl.lev = lev; pl.lrow = lrow; pl.rk = rk; pl.rsv = rsv; pl.sm = sm;
+    pl.lk = L.k; pl.lsv = L.s; pl.lev = L.e; pl.lrow = L.row; pl.rk = rk; pl.rsv = rsv; pl.sm = sm;
     pl.hk = hk; pl.hrs = hrs; pl.hpm = hpm; pl.hj = hj; pl.offs = cnt; pl.plan_hlo = plan_hlo; pl.plan_tail = plan_tail; pl.wf = wf;
-    if (cap == 0 && !ok && !os && !oe && !orow) {                       // count only: the fill call that follows reuses all of it
+    if (cap == 0 && !ok && !os && !oe && !orow) {                       // a sizing call: the fill call that follows reuses all of it
         pl.slots = 0;
         for (int slot : {WS_T0, WS_T1, WS_T2, WS_T3, WS_T4, WS_T5, WS_T7, WS_T9, WS_RA0, WS_RA1, WS_RA2, WS_RB0, WS_RB1, WS_RB2}) pl.slots |= 1ull << slot;
         pl.valid = true;
-        return IVX_OK;
     }
     return ivx_subtract_fill_planned(ctx, ok, os, oe, orow, cap, n_out);
 }
 
-// the output pass alone, from the plan a sizing call (or the lines above) left in the context
+// the output pass alone, from the plan a sizing call (or the lines above) left in the context; for a sizing call, nothing
 ivx_status ivx_subtract_fill_planned(ivx_ctx *ctx, u32 *ok, i64 *os, i64 *oe, u32 *orow, u64 cap, u64 *n_out)
 {
     const ivx_sub_plan &pl = ctx->sub_plan;
     *n_out = pl.total;
-    if (pl.total > cap) return ctx->fail(IVX_ERR_CAPACITY, "subtract: output buffers too small");
-    hipLaunchKernelGGL(k_sub_fill, dim3(grid1(pl.nl)), dim3(ST), 0, ctx->stream, pl.lk, pl.lsv, pl.lev, pl.lrow, pl.nl, pl.strict,
-                       pl.hk, pl.hrs, pl.hpm, pl.hj, (u32)pl.nh, pl.rk, pl.rsv, (const SegMax64 *)pl.sm, (u32)pl.nr,
-                       pl.offs, cap, ok, os, oe, orow, pl.plan_hlo, pl.plan_tail);
-    IVX_HIP(ctx, hipGetLastError());
-    return IVX_OK;
+    return frag_fill(ctx, FragLeft{pl.lk, pl.lsv, pl.lev, pl.lrow, pl.nl}, SubOp::Fill{pl.hrs, pl.hpm, pl.plan_hlo, pl.plan_tail}, pl.offs,
+                     pl.total, cap, "subtract: output buffers too small", ok, os, oe, orow);
 }
 
 // Test hook (not in include/ivx.h): what the count pass of the last subtract SIZING call did, read off a second run of that
-// pass (k_sub_count<true>) over the plan the call left in the context.  wg: SUB_DBG_WORDS words per workgroup (k_sub_count),
-// row_esc: one byte per left row at its original index; both host buffers, capacities in workgroups / rows.  The run writes
-// its counts and row plans into scratch of its own, in slots that are none of the plan's: the fill call that follows is
-// still served by the plan.
+// pass (k_frag_count<SubOp, true>) over the plan the call left in the context, on the stream of that call.  wg:
+// frag_dbg_words<SubOp> words per workgroup, row_esc: one byte per left row at its original index; both host buffers,
+// capacities in workgroups / rows.  The run writes its counts and row plans into scratch of its own, in slots that are none
+// of the plan's: the fill call that follows is still served by the plan.
 extern "C" ivx_status ivx_debug_subtract_paths(ivx_ctx *ctx, u32 *wg, u64 wg_cap, u8 *row_esc, u64 row_cap, u64 *n_wg, u64 *n_rows)
 {
     if (!ctx) return IVX_ERR_INVALID;
     const ivx_sub_plan &pl = ctx->sub_plan;
-    if (!pl.valid || !pl.lrow || !n_wg || !n_rows) return ctx->fail(IVX_ERR_INVALID, "debug_subtract_paths: no subtract plan (call it after a sizing call)");
+    if (!pl.valid || !pl.lrow || pl.stream != ctx->stream || !n_wg || !n_rows)
+        return ctx->fail(IVX_ERR_INVALID, "debug_subtract_paths: no subtract plan (call it after a sizing call)");
     const u64 nl = pl.nl;
     const u32 nblk_c = grid1(nl + 1);
     *n_wg = nblk_c; *n_rows = nl;
     if (wg_cap < nblk_c || row_cap < nl || !wg || !row_esc) return ctx->fail(IVX_ERR_CAPACITY, "debug_subtract_paths: buffers too small");
     IVX_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = pl.stream;
-    u64 *cnt; u32 *plan_hlo, *brk, *d_wg; i64 *plan_tail; u8 *d_esc;
+    u64 *cnt; u32 *plan_hlo; i64 *plan_tail;
     constexpr int mine[] = {WS_T6, WS_T8, WS_SA0, WS_GRID0, WS_SA1, WS_SA2};
     for (int slot : mine)
         if ((pl.slots >> slot) & 1) return ctx->fail(IVX_ERR_INVALID, "debug_subtract_paths: scratch slot belongs to the plan");
     IVX_TRY(ctx->get_scratch(WS_T6, (nl + 1) * sizeof(u64), (void **)&cnt));
     IVX_TRY(ctx->get_scratch(WS_T8, nl * sizeof(u32), (void **)&plan_hlo));
     IVX_TRY(ctx->get_scratch(WS_SA0, nl * sizeof(i64), (void **)&plan_tail));
-    IVX_TRY(ctx->get_scratch(WS_GRID0, ((size_t)nblk_c + 2) * sizeof(u32), (void **)&brk));
-    IVX_TRY(ctx->get_scratch(WS_SA1, (size_t)nblk_c * SUB_DBG_WORDS * sizeof(u32), (void **)&d_wg));
-    IVX_TRY(ctx->get_scratch(WS_SA2, nl, (void **)&d_esc));
-    IVX_HIP(ctx, hipMemsetAsync(d_wg, 0, (size_t)nblk_c * SUB_DBG_WORDS * sizeof(u32), st));
-    hipLaunchKernelGGL(k_sub_brackets, dim3(grid1((u64)nblk_c + 1)), dim3(ST), 0, st, pl.lk, pl.lsv, nl, pl.hk, pl.hrs, (u32)pl.nh, nblk_c, brk);
-    hipLaunchKernelGGL(k_sub_count<true>, dim3(nblk_c), dim3(ST), 0, st, pl.lk, pl.lsv, pl.lev, nl, pl.strict,
-                       pl.hk, pl.hrs, pl.hj, (u32)pl.nh, pl.rk, pl.rsv, (const SegMax64 *)pl.sm, (u32)pl.nr, cnt,
-                       plan_hlo, plan_tail, (const u32 *)brk, pl.wf, d_wg, d_esc, pl.lrow);
-    IVX_HIP(ctx, hipGetLastError());
-    IVX_HIP(ctx, hipMemcpyAsync(wg, d_wg, (size_t)nblk_c * SUB_DBG_WORDS * sizeof(u32), hipMemcpyDeviceToHost, st));
-    IVX_HIP(ctx, hipMemcpyAsync(row_esc, d_esc, nl, hipMemcpyDeviceToHost, st));
-    IVX_HIP(ctx, hipStreamSynchronize(st));
+    const SubOp op{pl.hk, pl.hrs, pl.hj, (u32)pl.nh, pl.rk, pl.rsv, (const SegMax64 *)pl.sm, (u32)pl.nr, pl.strict, pl.wf, plan_hlo, plan_tail};
+    const FragReport rep{wg, row_esc, WS_SA1, WS_SA2};
+    u64 total;
+    IVX_TRY(frag_count(ctx, FragLeft{pl.lk, pl.lsv, pl.lev, pl.lrow, nl}, op, cnt, &rep, &total));
     if (!pl.valid) return ctx->fail(IVX_ERR_INVALID, "debug_subtract_paths: the plan was dropped");
     return IVX_OK;
 }
@@ -1384,18 +1409,7 @@ ivx_status ivx_complement_device(ivx_ctx *ctx, const u32 *key, const i64 *s, con
     IVX_TRY(ctx->get_scratch(WS_T3, na * sizeof(u32), (void **)&mk));
     IVX_TRY(ctx->get_scratch(WS_T4, na * sizeof(i64), (void **)&ms));
     IVX_TRY(ctx->get_scratch(WS_T7, na * sizeof(i64), (void **)&me));
-    if (n) {
-        u32 *ks; i64 *ss, *es;
-        IVX_TRY(ctx->get_scratch(WS_T0, n * sizeof(u32), (void **)&ks));
-        IVX_TRY(ctx->get_scratch(WS_T1, n * sizeof(i64), (void **)&ss));
-        IVX_TRY(ctx->get_scratch(WS_T2, n * sizeof(i64), (void **)&es));
-        SortedRows rows;
-        PackedWant pk{0, strict, false, nullptr, Pack64{}};
-        IVX_TRY(sort64(ctx, WS_SA0, WS_SB0, key, s, e, n, nkeys, ks, ss, es, nullptr, &rows, &pk));
-        const ivx_runs_out ro{mk, ms, me, nullptr};
-        if (pk.ok) IVX_TRY(ivx_merge_runs_packed(ctx, pk.w, n, pk.p, 0, strict, ro, &m));
-        else IVX_TRY(ivx_merge_runs_rows(ctx, rows, n, 0, strict, ro, &m));
-    }
+    if (n) IVX_TRY(sorted_runs(ctx, key, s, e, n, nkeys, 0, strict, ivx_runs_out{mk, ms, me, nullptr}, &m));
     u32 *G, *cg;
     IVX_TRY(ctx->get_scratch(WS_T5, (m + 1) * sizeof(u32), (void **)&G));       // the sweep's scratch is free again
     IVX_TRY(ctx->get_scratch(WS_T6, (m + 1) * sizeof(u32), (void **)&cg));
@@ -1448,7 +1462,7 @@ ivx_status ivx_complement_device(ivx_ctx *ctx, const u32 *key, const i64 *s, con
 }
 
 // intersect: sort the right side and merge it into runs exactly as complement does its input, sort the left side with its row
-// ids, count (k_isect_brackets, k_isect_count), scan, fill (k_isect_fill).  No plan is kept: a sizing call returns after the
+// ids, count, scan, fill (the fragment passes over IsectOp).  No plan is kept: a sizing call returns after the
 // scan, and the fill call does all of it again.  With one side empty nothing is sorted, but the other side's rows are checked
 // as the sorts would check them.  The form words (ivx_debug_sweep_form) are the right side's, and two of the left side's
 // sort (IVX_SWEEP_LEFT_*).  dbg (tests only): the count pass also reports what it did.
@@ -1485,19 +1499,7 @@ ivx_status ivx_intersect_device(ivx_ctx *ctx, const u32 *lkey, const i64 *ls, co
     IVX_TRY(ctx->get_scratch(WS_T3, nr * sizeof(u32), (void **)&mk));
     IVX_TRY(ctx->get_scratch(WS_T4, nr * sizeof(i64), (void **)&ms));
     IVX_TRY(ctx->get_scratch(WS_T7, nr * sizeof(i64), (void **)&me));
-    {
-        u32 *ks; i64 *ss, *es;
-        IVX_TRY(ctx->get_scratch(WS_T0, nr * sizeof(u32), (void **)&ks));
-        IVX_TRY(ctx->get_scratch(WS_T1, nr * sizeof(i64), (void **)&ss));
-        IVX_TRY(ctx->get_scratch(WS_T2, nr * sizeof(i64), (void **)&es));
-        SortedRows rows;
-        PackedWant pk{0, strict, false, nullptr, Pack64{}};
-        IVX_TRY(sort64(ctx, WS_SA0, WS_SB0, rkey, rs, re, nr, nkeys, ks, ss, es, nullptr, &rows, &pk));
-        if (ctx->hword<Range64>(SC_RANGE)->odd & 1ull) return ctx->fail(IVX_ERR_INVALID, malformed);
-        const ivx_runs_out ro{mk, ms, me, nullptr};
-        if (pk.ok) IVX_TRY(ivx_merge_runs_packed(ctx, pk.w, nr, pk.p, 0, strict, ro, &m));
-        else IVX_TRY(ivx_merge_runs_rows(ctx, rows, nr, 0, strict, ro, &m));
-    }
+    IVX_TRY(sorted_runs(ctx, rkey, rs, re, nr, nkeys, 0, strict, ivx_runs_out{mk, ms, me, nullptr}, &m, malformed));
 
     // the left side in (key, start, end, row) order; the sorted right rows and the sweep's scratch are dead by now
     u32 *lk, *lrow; i64 *lsv, *lev;
@@ -1517,41 +1519,19 @@ ivx_status ivx_intersect_device(ivx_ctx *ctx, const u32 *lkey, const i64 *ls, co
     if (ctx->hword<Range64>(SC_RANGE)->odd & 1ull) return ctx->fail(IVX_ERR_INVALID, malformed);
     IVX_TRY(keyflag(ctx, "intersect: key id >= n_keys"));
 
-    u64 *cnt; u32 *plan_a, *brk;
+    u64 *cnt; u32 *plan_a;
     IVX_TRY(ctx->get_scratch(WS_T5, (nl + 1) * sizeof(u64), (void **)&cnt));
     IVX_TRY(ctx->get_scratch(WS_T8, nl * sizeof(u32), (void **)&plan_a));
-    IVX_TRY(ctx->get_scratch(WS_GRID0, ((size_t)nblk_c + 2) * sizeof(u32), (void **)&brk));
-    hipLaunchKernelGGL(k_isect_brackets, dim3(grid1((u64)nblk_c + 1)), dim3(ST), 0, st, (const u32 *)lk, (const i64 *)lsv, nl, (const u32 *)mk, (const i64 *)me, (u32)m,
-                       strict, nblk_c, brk);
-    if (!dbg)
-        hipLaunchKernelGGL(k_isect_count<false>, dim3(nblk_c), dim3(ST), 0, st, (const u32 *)lk, (const i64 *)lsv, (const i64 *)lev, nl, strict,
-                           (const u32 *)mk, (const i64 *)ms, (const i64 *)me, (u32)m, cnt, plan_a, (const u32 *)brk, (u32 *)nullptr, (u8 *)nullptr, (const u32 *)nullptr);
-    else {
-        u32 *d_wg; u8 *d_esc;                                               // (the sorts' record slots are free again)
-        const size_t wg_bytes = (size_t)nblk_c * ISECT_DBG_WORDS * sizeof(u32);
-        IVX_TRY(ctx->get_scratch(WS_SA0, wg_bytes, (void **)&d_wg));
-        IVX_TRY(ctx->get_scratch(WS_SA1, nl, (void **)&d_esc));
-        IVX_HIP(ctx, hipMemsetAsync(d_wg, 0, wg_bytes, st));
-        hipLaunchKernelGGL(k_isect_count<true>, dim3(nblk_c), dim3(ST), 0, st, (const u32 *)lk, (const i64 *)lsv, (const i64 *)lev, nl, strict,
-                           (const u32 *)mk, (const i64 *)ms, (const i64 *)me, (u32)m, cnt, plan_a, (const u32 *)brk, d_wg, d_esc, (const u32 *)lrow);
-        IVX_HIP(ctx, hipMemcpyAsync(dbg->wg, d_wg, wg_bytes, hipMemcpyDeviceToHost, st));
-        IVX_HIP(ctx, hipMemcpyAsync(dbg->row_esc, d_esc, nl, hipMemcpyDeviceToHost, st));
-    }
-    IVX_TRY(ivx_scan_exclusive_u64(ctx, cnt, nl + 1));
+    const FragLeft L{lk, lsv, lev, lrow, nl};
+    const FragReport rep{dbg ? dbg->wg : nullptr, dbg ? dbg->row_esc : nullptr, WS_SA0, WS_SA1};   // (the sorts' record slots are free again)
     u64 total;
-    IVX_TRY(ctx->fetch_wait((const u64 *)cnt + nl, st, &total));            // (lands in the scalar table's SC_LANDING; synchronises)
+    IVX_TRY(frag_count(ctx, L, IsectOp{mk, ms, me, (u32)m, strict, plan_a}, cnt, dbg ? &rep : nullptr, &total));
     *n_out = total;
-    if (cap == 0 && !ok && !os && !oe && !orow) return IVX_OK;              // count only
-    if (total > cap) return ctx->fail(IVX_ERR_CAPACITY, "intersect: output buffers too small");
-    if (total == 0) return IVX_OK;
-    hipLaunchKernelGGL(k_isect_fill, dim3(grid1(nl)), dim3(ST), 0, st, (const u32 *)lk, (const i64 *)lsv, (const i64 *)lev, (const u32 *)lrow, nl,
-                       (const i64 *)ms, (const i64 *)me, (const u64 *)cnt, (const u32 *)plan_a, cap, ok, os, oe, orow);
-    IVX_HIP(ctx, hipGetLastError());
-    return IVX_OK;
+    return frag_fill(ctx, L, IsectOp::Fill{ms, me, plan_a}, cnt, total, cap, "intersect: output buffers too small", ok, os, oe, orow);
 }
 
-// The constants a test needs to build a shape for one path of k_isect_count (ivx_debug_intersect_paths, ivx_capi.hip)
+// The constants a test needs to build a shape for one path of intersect's count pass (ivx_debug_intersect_paths, ivx_capi.hip)
 extern "C" void ivx_debug_intersect_geometry(u32 *rows_per_wg, u32 *staged_runs, u32 *margin, u32 *dbg_words)
 {
-    *rows_per_wg = ST; *staged_runs = ISECT_RW; *margin = ISECT_MARGIN; *dbg_words = ISECT_DBG_WORDS;
+    *rows_per_wg = ST; *staged_runs = ISECT_RW; *margin = ISECT_MARGIN; *dbg_words = frag_dbg_words<IsectOp>;
 }

@@ -90,7 +90,7 @@ SWEEP_ROWS, SWEEP_PACKED, SWEEP_PACKED_BESIDE_ROWS = 0, 1, 2            # packed
 # ... and the two words behind them that only an intersect sets (IVX_SWEEP_LEFT_*): nw and sort_words of its LEFT side's sort
 SWEEP_LEFT_SLOTS = ["left_nw", "left_sort_words"]
 
-# words per workgroup of the test hook ivx_debug_intersect_paths (csrc/ivx_sweep.hip k_isect_count), in order: the bracket of the
+# words per workgroup of the test hook ivx_debug_intersect_paths (csrc/ivx_sweep.hip k_frag_count<IsectOp>), in order: the bracket of the
 # workgroup's first searches, the staged window (first run, runs), whether LDS was used, rows planned again from global memory
 ISECT_DBG_SLOTS = ["brk_lo", "brk_hi", "win_first", "win_runs", "lds", "escaped"]
 

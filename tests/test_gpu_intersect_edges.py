@@ -1,6 +1,6 @@
 """-m gpu: intersect at the edges of its count pass's LDS window, of its workgroups and of its fill pass.
 
-k_isect_count (csrc/ivx_sweep.hip) stages for every workgroup of 256 sorted left rows the stretch of merged runs its rows'
+k_frag_count<IsectOp> (csrc/ivx_sweep.hip) stages for every workgroup of 256 sorted left rows the stretch of merged runs its rows'
 searches touch -- from one below brk[b] to `margin` past brk[b+1] -- when it is at most `staged_runs` runs; a row whose
 searches leave the stretch raises `esc` and is planned again from global memory, and a workgroup whose stretch does not fit
 plans all its rows there.  Every window case here reads what the pass did (Ctx.intersect_paths, the test hook
@@ -82,7 +82,7 @@ def is_sorted(side):
 
 
 def model(left, right, strict, geo):
-    """words 0..4 of every workgroup for SORTED lefts, from the window rule of k_isect_count"""
+    """words 0..4 of every workgroup for SORTED lefts, from the window rule of IsectOp (csrc/ivx_sweep.hip)"""
     runs = io.merged_runs(right, strict)
     keys = [(k, me) for k in sorted(runs) for _, me in runs[k]]
     m = len(keys)

@@ -1,6 +1,6 @@
 """-m gpu: subtract at the edges of its count pass's LDS window, of its workgroups and of its fill pass.
 
-k_sub_count (csrc/ivx_sweep.hip) stages for every workgroup of ST sorted left rows the stretch of the right side its rows'
+k_frag_count<SubOp> (csrc/ivx_sweep.hip) stages for every workgroup of ST sorted left rows the stretch of the right side its rows'
 searches touch -- heads [h0, h1), rights [r0, r1), sized from the two brackets brk[b], brk[b+1] plus SUB_MARGIN -- when it
 fits SUB_HW heads and SUB_RW rights; a row whose searches leave the stretch raises `esc` and is planned again from global
 memory.  Every window case here reads what the pass did (ivx_debug_subtract_paths, between the sizing and the fill call)
@@ -13,8 +13,8 @@ sorted position is its index; every case runs once more with its lefts shuffled 
 and the well-formed window cases once more with 2^40 added to every coordinate.  All four output columns are compared
 bit-exactly with the CPU oracle; where the lattice makes the fragment count obvious it is asserted too.
 
-The `at >= cap` guard of k_sub_fill cannot fire through the C ABI (a fill with total > cap is refused on the host before
-the launch); the capacity cases check that refusal, the canaries behind the rows and the call that follows."""
+k_frag_fill has no capacity guard of its own: a fill with total > cap is refused on the host before the launch; the
+capacity cases check that refusal, the canaries behind the rows and the call that follows."""
 import bisect
 import contextlib
 import ctypes as C
@@ -34,7 +34,7 @@ pytestmark = pytest.mark.gpu
 
 # csrc/ivx_sweep.hip: ST (rows of a workgroup), SUB_HW / SUB_RW (heads / rights the LDS stretch holds), SUB_MARGIN
 ST, SUB_HW, SUB_RW, SUB_MARGIN = 256, 256, 640, 48
-# words of a workgroup in the readout (SUB_DBG_WORDS)
+# words of a workgroup in the readout (frag_dbg_words<SubOp>)
 W_B0, W_B1, W_H0, W_HN, W_R0, W_RN, W_LDS, W_ESC = range(8)
 KEY = 1                     # the key of the lattice and of the lefts; keys 0 and 2 hold what a mode adds
 MODES = ["wf", "env", "inv"]  # two-search plan; five-point plan by IVX_SUB_GENERAL; five-point plan by an inverted right in another key
@@ -119,7 +119,7 @@ def heads_of(right):
 
 
 def model(left, right):
-    """words 0..6 of every workgroup for SORTED lefts, from the window rule of k_sub_count"""
+    """words 0..6 of every workgroup for SORTED lefts, from the window rule of SubOp (csrc/ivx_sweep.hip)"""
     lk, ls, _ = left
     nl = len(lk)
     (rk, _, _), hk, hrs, hj = heads_of(right)
@@ -506,7 +506,7 @@ def test_workgroup_that_emits_nothing_between_two_that_do(ctx):
 @pytest.mark.parametrize("frags", [255, 256, 257, 512, 513])
 @pytest.mark.parametrize("tail", [False, True])
 def test_one_row_with_many_fragments(ctx, frags, tail):
-    """k_sub_fill's o += ST loop: a row's fragments spread over one, two and three trips; alone and between other rows"""
+    """k_frag_fill's o += ST loop: a row's fragments spread over one, two and three trips; alone and between other rows"""
     right = lattice(600)
     long_row = (5, 100 * (frags - 2) + 80) if tail else (5, 100 * (frags - 1) + 30)    # frags-1 heads and a tail / frags heads
     alone = cols(KEY, [long_row[0]], [long_row[1]])
