@@ -33,6 +33,11 @@ JOIN_LEFT_SEMI, JOIN_LEFT_ANTI, JOIN_LEFT, JOIN_RIGHT, JOIN_FULL = 4, 5, 6, 7, 8
 AGG_OPS = ("count", "sum", "min", "max", "bases", "wsum")
 # the criteria of overlap_select, in the order of the BRH_SEL_* enum (include/bio_ranges_host.h)
 SEL_BY = pyivx.SEL_BY
+# an overlap threshold (`where=` of interval_join, overlap_aggregate and overlap_select): a pyivx.OverlapWhere or a dict of its
+# keywords -- min_bases, probe / build (minimum fractions of the probe / build row that the overlap covers: a (num, den) pair, a
+# Fraction, or a float, which is taken as Fraction(f).limit_denominator(10**9)) and either.  brh_overlap_where has the layout of
+# ivx_overlap_where.
+OverlapWhere = pyivx.OverlapWhere
 
 
 class _ArrowSchema(C.Structure):
@@ -192,34 +197,46 @@ class Session:
 
     # ---- IntervalJoinExec (the SQL range join), `build` = the SQL join's left table
     def interval_join(self, build, probe, cols_build=DEFAULT_COLS, cols_probe=DEFAULT_COLS, join_type=JOIN_INNER,
-                      strict_predicate=False, nearest_algorithm=False):
+                      strict_predicate=False, nearest_algorithm=False, where=None):
         """-> (build_idx, probe_idx) UInt32 arrays.  JOIN_RIGHT_SEMI / _ANTI: probe_idx only; JOIN_LEFT_SEMI / _ANTI: build_idx
-        only, ascending; JOIN_LEFT / _RIGHT / _FULL: the Inner pairs, then the unmatched rows with a NULL on the other side."""
+        only, ascending; JOIN_LEFT / _RIGHT / _FULL: the Inner pairs, then the unmatched rows with a NULL on the other side.
+        where (OverlapWhere): only overlaps that pass the threshold are matches, for every join type alike."""
+        wp, _keep = pyivx.as_where(where)
         B, P = _Exported(build), _Exported(probe)
         (ba, bs), (pa_, ps) = _out(), _out()
         try:
-            self._chk(lib().brh_interval_join(self.h, B.c, _cols(cols_build), P.c, _cols(cols_probe), C.c_int(join_type),
-                                              C.c_int(int(strict_predicate)), C.c_int(int(nearest_algorithm)),
-                                              C.byref(ba), C.byref(bs), C.byref(pa_), C.byref(ps)))
+            if where is not None:
+                self._chk(lib().brh_interval_join_where(self.h, B.c, _cols(cols_build), P.c, _cols(cols_probe), C.c_int(join_type),
+                                                        C.c_int(int(strict_predicate)), C.c_int(int(nearest_algorithm)), wp,
+                                                        C.byref(ba), C.byref(bs), C.byref(pa_), C.byref(ps)))
+            else:
+                self._chk(lib().brh_interval_join(self.h, B.c, _cols(cols_build), P.c, _cols(cols_probe), C.c_int(join_type),
+                                                  C.c_int(int(strict_predicate)), C.c_int(int(nearest_algorithm)),
+                                                  C.byref(ba), C.byref(bs), C.byref(pa_), C.byref(ps)))
         finally:
             B.close(); P.close()
         return _import(ba, bs), _import(pa_, ps)
 
     # ---- overlap aggregates: the join grouped by probe row, a build-side value aggregated (no pairs are made)
     def overlap_aggregate(self, build, probe, value, ops=AGG_OPS, cols_build=DEFAULT_COLS, cols_probe=DEFAULT_COLS,
-                          strict_predicate=False):
-        """per row of `probe`, over the rows of `build` it overlaps: aggregates of build's column `value` (Int8 .. Int64 or
+                          strict_predicate=False, where=None):
+        """per row of `probe`, over the rows of `build` it overlaps (where: with an overlap that passes the threshold): aggregates of build's column `value` (Int8 .. Int64 or
         UInt8 .. UInt32) -> a table of Int64 columns named after `ops` (AGG_OPS), one row per probe row in probe order.
         count and bases are non-null; sum, min, max and wsum are NULL where count is 0."""
         unknown = [o for o in ops if o not in AGG_OPS]
         if unknown or not ops:
             raise BioRangesError(f"overlap_aggregate: ops is a non-empty subset of {AGG_OPS}, got {tuple(ops)}")
         mask = sum(1 << AGG_OPS.index(o) for o in set(ops))
+        wp, _keep = pyivx.as_where(where)
         B, P = _Exported(build), _Exported(probe)
         arrs, schs = (_ArrowArray * len(AGG_OPS))(), (_ArrowSchema * len(AGG_OPS))()
         try:
-            self._chk(lib().brh_overlap_aggregate(self.h, B.c, _cols(cols_build), value.encode(), P.c, _cols(cols_probe),
-                                                  C.c_int(int(strict_predicate)), C.c_uint32(mask), arrs, schs))
+            if where is not None:
+                self._chk(lib().brh_overlap_aggregate_where(self.h, B.c, _cols(cols_build), value.encode(), P.c, _cols(cols_probe),
+                                                            C.c_int(int(strict_predicate)), C.c_uint32(mask), wp, arrs, schs))
+            else:
+                self._chk(lib().brh_overlap_aggregate(self.h, B.c, _cols(cols_build), value.encode(), P.c, _cols(cols_probe),
+                                                      C.c_int(int(strict_predicate)), C.c_uint32(mask), arrs, schs))
         finally:
             B.close(); P.close()
         got = {o: _import(arrs[i], schs[i]) for i, o in enumerate(AGG_OPS) if mask & (1 << i)}
@@ -227,8 +244,8 @@ class Session:
 
     # ---- overlap select: the join reduced to the one best build row per probe row (no pairs are made)
     def overlap_select(self, build, probe, by, value=None, cols_build=DEFAULT_COLS, cols_probe=DEFAULT_COLS,
-                       strict_predicate=False):
-        """per row of `probe`, of the rows of `build` it overlaps, the one that is best by `by` (SEL_BY; ties: the smallest
+                       strict_predicate=False, where=None):
+        """per row of `probe`, of the rows of `build` it overlaps (where: with an overlap that passes the threshold), the one that is best by `by` (SEL_BY; ties: the smallest
         build row) -> (build_idx, score), one row per probe row in probe order.  build_idx: UInt32, NULL without a match --
         take_table(build, build_idx) gives the left join to at most one row.  score: Int64, NULL where build_idx is: the
         winner's value, closed overlap length or row.  `value` names build's value column for "min_val" / "max_val" (and for
@@ -236,12 +253,18 @@ class Session:
         score is None (take the value with build_idx)."""
         if by not in SEL_BY:
             raise BioRangesError(f"overlap_select: by is one of {SEL_BY}, got {by!r}")
+        wp, _keep = pyivx.as_where(where)
         B, P = _Exported(build), _Exported(probe)
         (ia, is_), (sa, ss) = _out(), _out()
         try:
-            self._chk(lib().brh_overlap_select(self.h, B.c, _cols(cols_build), None if value is None else value.encode(), P.c,
-                                               _cols(cols_probe), C.c_int(int(strict_predicate)), C.c_int(SEL_BY.index(by)),
-                                               C.byref(ia), C.byref(is_), C.byref(sa), C.byref(ss)))
+            if where is not None:
+                self._chk(lib().brh_overlap_select_where(self.h, B.c, _cols(cols_build), None if value is None else value.encode(), P.c,
+                                                         _cols(cols_probe), C.c_int(int(strict_predicate)), C.c_int(SEL_BY.index(by)), wp,
+                                                         C.byref(ia), C.byref(is_), C.byref(sa), C.byref(ss)))
+            else:
+                self._chk(lib().brh_overlap_select(self.h, B.c, _cols(cols_build), None if value is None else value.encode(), P.c,
+                                                   _cols(cols_probe), C.c_int(int(strict_predicate)), C.c_int(SEL_BY.index(by)),
+                                                   C.byref(ia), C.byref(is_), C.byref(sa), C.byref(ss)))
         finally:
             B.close(); P.close()
         return _import(ia, is_), (_import(sa, ss) if sa.release else None)

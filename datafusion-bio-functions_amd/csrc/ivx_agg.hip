@@ -7,14 +7,14 @@
 // lean index: the same operator on k_lean / k_lean_rest in ivx_regions_probe.hip.)
 //
 // A row without a match stores count 0, sum 0, bases 0, wsum 0 and the identities INT64_MAX / INT64_MIN for min / max.
-#include "ivx_agg.hpp"
+#include "ivx_where.hpp"
 
 ivx_status ivx_agg_probe(ivx_ctx *ctx, const JoinIndexView &jv, const u32 *key, const i32 *s, const i32 *e, u64 n,
-                         const void *val, u32 val_bytes, const AggOut &out)
+                         const void *val, u32 val_bytes, const AggOut &out, const WherePred *w)
 {
     ivx_status st = IVX_OK;
     with_bools([&](auto wide, auto mm, auto wt) {
-        st = ivx_direct_probe(ctx, jv, key, s, e, n, AggOp<IVX_B(wide) ? 8 : 4, IVX_B(mm), IVX_B(wt)>{{}, val, out});
+        with_where(w, AggOp<IVX_B(wide) ? 8 : 4, IVX_B(mm), IVX_B(wt)>{{}, val, out}, [&](const auto &op) { st = ivx_direct_probe(ctx, jv, key, s, e, n, op); });
     }, val_bytes == 8, out.vmin || out.vmax, out.bases || out.wsum);
     return st;
 }

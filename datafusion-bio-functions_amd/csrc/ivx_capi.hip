@@ -3,6 +3,7 @@
 // scratch management.  All arithmetic happens in the HIP kernels.
 #include "ivx_internal.hpp"
 #include "ivx_call.hpp"
+#include "ivx_where.hpp"
 #include <cstdlib>
 #include <atomic>
 #include <cstring>
@@ -149,6 +150,16 @@ ivx_status check_probe_args(Frame &f, const ivx_index *ix, int kind, const void 
     // an index whose build tail ran beside other work is complete behind its `ready` event: this context's stream is
     // ordered behind it here, unless the caller takes care of that itself (the region path: after its routing pass)
     if (ix->ready != nullptr && !defer_ready) IVX_HIP(ctx, hipStreamWaitEvent(ctx->stream, ix->ready, 0));
+    return IVX_OK;
+}
+
+// the threshold of a *_where entry (include/ivx_where.h), behind the entry's own head: refused by its rule's text, else *asked
+// says whether it filters at all (a call that asks nothing is the plain call) and *p is what the kernels take
+ivx_status check_where(ivx_ctx *ctx, const ivx_overlap_where *w, WherePred *p, bool *asked)
+{
+    if (const char *bad = where_invalid(w)) return ctx->fail(IVX_ERR_INVALID, bad);
+    *p = where_pred(w);
+    *asked = where_asks(w);
     return IVX_OK;
 }
 
@@ -837,11 +848,14 @@ extern "C" ivx_status ivx_probe_exists(ivx_ctx *ctx, const ivx_index *ix, int me
 
 // Beside overlap_common: the same two ways through the index, the match recorded by BUILD row.  Big batches over a lean
 // index (the form ivx_rowval_probe_regions runs k_lean on) take the region kernels; everything else the direct one.
-extern "C" ivx_status ivx_probe_mark_build(ivx_ctx *ctx, const ivx_index *ix, int mem, const uint32_t *key,
-                                           const int32_t *start, const int32_t *end, uint64_t n, uint32_t *marks)
+static ivx_status mark_build_impl(ivx_ctx *ctx, const ivx_index *ix, int mem, const uint32_t *key,
+                                  const int32_t *start, const int32_t *end, uint64_t n, const ivx_overlap_where *where, uint32_t *marks)
 {
     Frame f(ctx, mem);
     IVX_TRY(check_probe_args(f, ix, IVX_KIND_OVERLAP, start, end, n));             // (orders the stream behind a build tail, too)
+    WherePred wp; bool filtered;
+    IVX_TRY(check_where(ctx, where, &wp, &filtered));
+    const WherePred *w = filtered ? &wp : nullptr;
     if (n && ix->n && !marks) return ctx->fail(IVX_ERR_INVALID, "null mark bitmap");
     f.meter(false, n);
     f.drop_join_plan();                                     // as any other call between a count call and its fill
@@ -853,11 +867,21 @@ extern "C" ivx_status ivx_probe_mark_build(ivx_ctx *ctx, const ivx_index *ix, in
     u32 *dm = f.out_or(marks, nw);
     IVX_TRY(f.run([&]() -> ivx_status {
         bool took = false;
-        if (regions) IVX_TRY(ivx_mark_probe_regions(ctx, ix->jv, ix->jv_nreg, dk, ds, de, n, dm, ix->jv_filter, ix->jv_pk24, ix->jv_lean.load(std::memory_order_relaxed) == 1, &took));
-        return took ? IVX_OK : ivx_mark_probe(ctx, ix->jv, dk, ds, de, n, dm);
+        if (regions) IVX_TRY(ivx_mark_probe_regions(ctx, ix->jv, ix->jv_nreg, dk, ds, de, n, dm, ix->jv_filter, ix->jv_pk24, ix->jv_lean.load(std::memory_order_relaxed) == 1, &took, w));
+        return took ? IVX_OK : ivx_mark_probe(ctx, ix->jv, dk, ds, de, n, dm, w);
     }));
     f.or_back(marks);                                       // (synchronises: nothing is left for finish())
     return f.st;
+}
+extern "C" ivx_status ivx_probe_mark_build(ivx_ctx *ctx, const ivx_index *ix, int mem, const uint32_t *key,
+                                           const int32_t *start, const int32_t *end, uint64_t n, uint32_t *marks)
+{
+    return mark_build_impl(ctx, ix, mem, key, start, end, n, nullptr, marks);
+}
+extern "C" ivx_status ivx_probe_mark_build_where(ivx_ctx *ctx, const ivx_index *ix, int mem, const uint32_t *key,
+                                                 const int32_t *start, const int32_t *end, uint64_t n, const ivx_overlap_where *w, uint32_t *marks)
+{
+    return mark_build_impl(ctx, ix, mem, key, start, end, n, w, marks);
 }
 
 // ---------------------------------------------------------------- a3''': overlap aggregates
@@ -871,12 +895,16 @@ static u64 agg_regions_rows(int n64)
 {
     return n64 <= 1 ? 1ull << 23 : n64 <= 3 ? 1ull << 24 : ~0ull;
 }
-extern "C" ivx_status ivx_probe_overlap_agg(ivx_ctx *ctx, const ivx_index *ix, int mem, const uint32_t *key,
-                                            const int32_t *start, const int32_t *end, uint64_t n, const void *val, uint32_t val_bytes,
-                                            uint32_t *count, int64_t *sum, int64_t *vmin, int64_t *vmax, int64_t *bases, int64_t *wsum)
+static ivx_status overlap_agg_impl(ivx_ctx *ctx, const ivx_index *ix, int mem, const uint32_t *key,
+                                   const int32_t *start, const int32_t *end, uint64_t n, const void *val, uint32_t val_bytes,
+                                   const ivx_overlap_where *where,
+                                   uint32_t *count, int64_t *sum, int64_t *vmin, int64_t *vmax, int64_t *bases, int64_t *wsum)
 {
     Frame f(ctx, mem);
     IVX_TRY(check_probe_args(f, ix, IVX_KIND_OVERLAP, start, end, n));             // (orders the stream behind a build tail, too)
+    WherePred wp; bool filtered;
+    IVX_TRY(check_where(ctx, where, &wp, &filtered));
+    const WherePred *w = filtered ? &wp : nullptr;
     if (!count && !sum && !vmin && !vmax && !bases && !wsum) return ctx->fail(IVX_ERR_INVALID, "overlap_agg: no output wanted");
     if (val_bytes != 4 && val_bytes != 8) return ctx->fail(IVX_ERR_INVALID, "overlap_agg: val_bytes is 4 or 8");
     if (ix->n && !val) return ctx->fail(IVX_ERR_INVALID, "overlap_agg: null value column");
@@ -894,12 +922,25 @@ extern "C" ivx_status ivx_probe_overlap_agg(ivx_ctx *ctx, const ivx_index *ix, i
     IVX_TRY(f.st);
     IVX_TRY(f.run([&]() -> ivx_status {
         bool took = false;
-        if (regions) IVX_TRY(ivx_agg_probe_regions(ctx, ix->jv, ix->jv_nreg, dk, ds, de, n, dv, val_bytes, o, ix->jv_filter, ix->jv_pk24, ix->jv_lean.load(std::memory_order_relaxed) == 1, &took));
-        return took ? IVX_OK : ivx_agg_probe(ctx, ix->jv, dk, ds, de, n, dv, val_bytes, o);
+        if (regions) IVX_TRY(ivx_agg_probe_regions(ctx, ix->jv, ix->jv_nreg, dk, ds, de, n, dv, val_bytes, o, ix->jv_filter, ix->jv_pk24, ix->jv_lean.load(std::memory_order_relaxed) == 1, &took, w));
+        return took ? IVX_OK : ivx_agg_probe(ctx, ix->jv, dk, ds, de, n, dv, val_bytes, o, w);
     }));
     f.rows_out(n);                                          // (as ivx_probe_count: not on a refused call)
     f.back_all();
     return f.finish();
+}
+extern "C" ivx_status ivx_probe_overlap_agg(ivx_ctx *ctx, const ivx_index *ix, int mem, const uint32_t *key,
+                                            const int32_t *start, const int32_t *end, uint64_t n, const void *val, uint32_t val_bytes,
+                                            uint32_t *count, int64_t *sum, int64_t *vmin, int64_t *vmax, int64_t *bases, int64_t *wsum)
+{
+    return overlap_agg_impl(ctx, ix, mem, key, start, end, n, val, val_bytes, nullptr, count, sum, vmin, vmax, bases, wsum);
+}
+extern "C" ivx_status ivx_probe_overlap_agg_where(ivx_ctx *ctx, const ivx_index *ix, int mem, const uint32_t *key,
+                                                  const int32_t *start, const int32_t *end, uint64_t n, const void *val, uint32_t val_bytes,
+                                                  const ivx_overlap_where *w,
+                                                  uint32_t *count, int64_t *sum, int64_t *vmin, int64_t *vmax, int64_t *bases, int64_t *wsum)
+{
+    return overlap_agg_impl(ctx, ix, mem, key, start, end, n, val, val_bytes, w, count, sum, vmin, vmax, bases, wsum);
 }
 
 // ---------------------------------------------------------------- a3'''': overlap select (include/ivx_select.h)
@@ -914,12 +955,15 @@ static u64 sel_regions_rows()
 {
     return 1ull << 23;
 }
-extern "C" ivx_status ivx_probe_overlap_select(ivx_ctx *ctx, const ivx_index *ix, int mem, const uint32_t *key,
-                                               const int32_t *start, const int32_t *end, uint64_t n, const void *val, uint32_t val_bytes,
-                                               int by, uint32_t *build_idx, int64_t *score)
+static ivx_status overlap_select_impl(ivx_ctx *ctx, const ivx_index *ix, int mem, const uint32_t *key,
+                                      const int32_t *start, const int32_t *end, uint64_t n, const void *val, uint32_t val_bytes,
+                                      int by, const ivx_overlap_where *where, uint32_t *build_idx, int64_t *score)
 {
     Frame f(ctx, mem);
     IVX_TRY(check_probe_args(f, ix, IVX_KIND_OVERLAP, start, end, n));             // (orders the stream behind a build tail, too)
+    WherePred wp; bool filtered;
+    IVX_TRY(check_where(ctx, where, &wp, &filtered));
+    const WherePred *w = filtered ? &wp : nullptr;
     if (!build_idx) return ctx->fail(IVX_ERR_INVALID, "overlap_select: null build_idx");
     if (by < 0 || by >= IVX_SEL_N) return ctx->fail(IVX_ERR_INVALID, "overlap_select: unknown criterion");
     const bool by_val = by == IVX_SEL_MIN_VAL || by == IVX_SEL_MAX_VAL;
@@ -937,11 +981,113 @@ extern "C" ivx_status ivx_probe_overlap_select(ivx_ctx *ctx, const ivx_index *ix
     IVX_TRY(f.st);
     IVX_TRY(f.run([&]() -> ivx_status {
         bool took = false;
-        if (regions) IVX_TRY(ivx_sel_probe_regions(ctx, ix->jv, ix->jv_nreg, dk, ds, de, n, dv, val_bytes, by, o, ix->jv_filter, ix->jv_pk24, ix->jv_lean.load(std::memory_order_relaxed) == 1, &took));
-        return took ? IVX_OK : ivx_sel_probe(ctx, ix->jv, dk, ds, de, n, dv, val_bytes, by, o);
+        if (regions) IVX_TRY(ivx_sel_probe_regions(ctx, ix->jv, ix->jv_nreg, dk, ds, de, n, dv, val_bytes, by, o, ix->jv_filter, ix->jv_pk24, ix->jv_lean.load(std::memory_order_relaxed) == 1, &took, w));
+        return took ? IVX_OK : ivx_sel_probe(ctx, ix->jv, dk, ds, de, n, dv, val_bytes, by, o, w);
     }));
     f.rows_out(n);                                          // (as ivx_probe_count: not on a refused call)
     f.back_all();
+    return f.finish();
+}
+extern "C" ivx_status ivx_probe_overlap_select(ivx_ctx *ctx, const ivx_index *ix, int mem, const uint32_t *key,
+                                               const int32_t *start, const int32_t *end, uint64_t n, const void *val, uint32_t val_bytes,
+                                               int by, uint32_t *build_idx, int64_t *score)
+{
+    return overlap_select_impl(ctx, ix, mem, key, start, end, n, val, val_bytes, by, nullptr, build_idx, score);
+}
+extern "C" ivx_status ivx_probe_overlap_select_where(ivx_ctx *ctx, const ivx_index *ix, int mem, const uint32_t *key,
+                                                     const int32_t *start, const int32_t *end, uint64_t n, const void *val, uint32_t val_bytes,
+                                                     int by, const ivx_overlap_where *w, uint32_t *build_idx, int64_t *score)
+{
+    return overlap_select_impl(ctx, ix, mem, key, start, end, n, val, val_bytes, by, w, build_idx, score);
+}
+
+// ---------------------------------------------------------------- a3''''': overlap thresholds (include/ivx_where.h)
+
+// The per-row match count under a threshold: per_row, exists and the total, each wanted or not.  Beside ivx_probe_mark_build,
+// with its path choice (region_path_wanted from 2^21 rows: the threshold of overlap_common's per-row branch); where the plain
+// per-row modes take the routed per-row path (an index of too many regions) this one takes the direct kernel.  One walk:
+// the counts go to per_row -- the caller's, or scratch when only the total is wanted.  The total is a device reduction of them:
+// the region path's un-permute adds them up on its way (as for the plain per-row mode), the direct path runs k_match_totals,
+// which also derives the exists bytes where the region path wrote per_row alone; exists alone is written by the walk itself.
+extern "C" ivx_status ivx_probe_overlap_count_where(ivx_ctx *ctx, const ivx_index *ix, int mem, const uint32_t *key,
+                                                    const int32_t *start, const int32_t *end, uint64_t n, const ivx_overlap_where *where,
+                                                    uint32_t *per_row, uint8_t *exists, uint64_t *total)
+{
+    Frame f(ctx, mem);
+    IVX_TRY(check_probe_args(f, ix, IVX_KIND_OVERLAP, start, end, n));             // (orders the stream behind a build tail, too)
+    WherePred wp; bool filtered;
+    IVX_TRY(check_where(ctx, where, &wp, &filtered));
+    if (!per_row && !exists && !total) return ctx->fail(IVX_ERR_INVALID, "overlap_count_where: no output wanted");
+    if (total) *total = 0;
+    f.meter(false, n);
+    f.drop_join_plan();                                     // as any other call between a count call and its fill
+    if (n == 0) return IVX_OK;
+    const bool regions = region_path_wanted(ix, n, 1u << 21);
+    const u32 *dk = f.in(key, n);
+    const i32 *ds = f.in(start, n), *de = f.in(end, n);
+    u32 *d_row = f.out(per_row, n);
+    u8 *d_ex = f.out(exists, n);
+    if (!d_row && total) IVX_TRY(f.scratch_at(WS_T6, (size_t)n * sizeof(u32), (void **)&d_row));   // (the reduction's input)
+    IVX_TRY(f.st);
+    u64 *d_total = ctx->dword(SC_PAIRS);                    // this call is an overlap probe: the pair's first word is its total
+    if (total) IVX_HIP(ctx, hipMemsetAsync(d_total, 0, 2 * sizeof(u64), ctx->stream));
+    IVX_TRY(f.run([&]() -> ivx_status {
+        bool took = false;
+        if (regions) IVX_TRY(ivx_match_probe_regions_where(ctx, ix->jv, ix->jv_nreg, dk, ds, de, n, d_row, d_ex, total ? d_total : nullptr, ix->jv_filter, ix->jv_pk24,
+                                                           ix->jv_lean.load(std::memory_order_relaxed) == 1, &took, wp));
+        // the region form has summed the counts in its un-permute and wrote per_row alone when both columns were wanted: the
+        // exists bytes are still to derive; the direct walk wrote both columns and has no total yet
+        if (took) return d_row && d_ex ? ivx_match_totals(ctx, d_row, n, d_ex, nullptr) : IVX_OK;
+        IVX_TRY(ivx_match_probe_where(ctx, ix->jv, dk, ds, de, n, d_row, d_ex, wp));
+        return total ? ivx_match_totals(ctx, d_row, n, nullptr, d_total) : IVX_OK;
+    }));
+    if (total) IVX_TRY(ctx->fetch_wait(SC_PAIRS, ctx->stream, total));
+    f.rows_out(n);
+    f.back_all();
+    return f.finish();
+}
+
+// The stable pair filter.  Its columns are the join's own: the pairs a fill call wrote, the coordinate columns it was given.
+extern "C" ivx_status ivx_pairs_where(ivx_ctx *ctx, int mem, const uint32_t *build_idx, const uint32_t *probe_idx, uint64_t n_pairs,
+                                      const int32_t *bstart, const int32_t *bend, uint64_t nb,
+                                      const int32_t *pstart, const int32_t *pend, uint64_t np, const ivx_overlap_where *where,
+                                      uint32_t *out_build, uint32_t *out_probe, uint64_t cap, uint64_t *n_out)
+{
+    Frame f(ctx, mem);
+    IVX_TRY(f.enter(n_out, "pairs_where: null n_out"));
+    WherePred wp; bool filtered;
+    IVX_TRY(check_where(ctx, where, &wp, &filtered));
+    if (n_pairs && (!build_idx || !probe_idx)) return ctx->fail(IVX_ERR_INVALID, "pairs_where: null pair columns");
+    if ((nb && (!bstart || !bend)) || (np && (!pstart || !pend))) return ctx->fail(IVX_ERR_INVALID, "pairs_where: null coordinate column");
+    if (nb > 0xFFFFFFFFull || np > 0xFFFFFFFFull) return ctx->fail(IVX_ERR_INVALID, "pairs_where: row count exceeds UInt32 index capacity");
+    if (cap && (!out_build || !out_probe)) return ctx->fail(IVX_ERR_INVALID, "pairs_where: null output columns");
+    if (!cap && (out_build || out_probe)) return ctx->fail(IVX_ERR_INVALID, "pairs_where: output columns without capacity");
+    // an output is written while other workgroups still read the inputs: no overlap with any of them, nor with the other output
+    {
+        struct Span { const void *p; u64 bytes; };
+        const Span ins[] = {{build_idx, n_pairs * 4}, {probe_idx, n_pairs * 4}, {bstart, nb * 4}, {bend, nb * 4}, {pstart, np * 4}, {pend, np * 4},
+                            {out_probe, cap * 4}};
+        const Span outs[] = {{out_build, cap * 4}, {out_probe, cap * 4}};
+        for (int o = 0; o < 2; o++)
+            for (int i = 0; i < 7 - o; i++) {
+                const uintptr_t a = (uintptr_t)outs[o].p, b = (uintptr_t)ins[i].p;
+                if (outs[o].bytes && ins[i].bytes && a < b + ins[i].bytes && b < a + outs[o].bytes)
+                    return ctx->fail(IVX_ERR_INVALID, "pairs_where: an output overlaps an input or the other output");
+            }
+    }
+    f.meter(false, n_pairs);
+    f.drop_join_plan();
+    if (n_pairs == 0) return IVX_OK;
+    const u32 *db = f.in(build_idx, n_pairs), *dp = f.in(probe_idx, n_pairs);
+    const i32 *dbs = f.in(bstart, nb), *dbe = f.in(bend, nb), *dps = f.in(pstart, np), *dpe = f.in(pend, np);
+    u32 *dob = f.out(out_build, cap), *dop = f.out(out_probe, cap);
+    IVX_TRY(f.st);
+    u64 m = 0;
+    const ivx_status st = f.run([&] { return ivx_pairs_where_device(ctx, db, dp, n_pairs, dbs, dbe, nb, dps, dpe, np, wp, dob, dop, cap, &m); });
+    *n_out = m;
+    if (st != IVX_OK) return st;
+    f.rows_out(m);
+    f.back(out_build, m); f.back(out_probe, m);
     return f.finish();
 }
 

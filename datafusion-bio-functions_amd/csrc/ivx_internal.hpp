@@ -380,26 +380,45 @@ ivx_status ivx_rowval_probe_regions(ivx_ctx *ctx, const JoinIndexView &jv, u32 n
                                     const u32 *key, const i32 *s, const i32 *e, u64 n, int strict, void *out, u64 *d_total,
                                     bool has_filter = false, bool pk24 = false, bool fast = false);
 
+// An overlap threshold as the kernels carry it (ivx_where.hpp).  The per-row probes below take one as `w`: null is the plain
+// call; else only the pairs that pass reach the operator (WhereOp), on the same launchers and un-permute passes.
+struct WherePred;
 // build-side match marks (ivx_marks.hip; the lean region form in ivx_regions_probe.hip): one bit per build row, ORed
-ivx_status ivx_mark_probe(ivx_ctx *ctx, const JoinIndexView &jv, const u32 *key, const i32 *s, const i32 *e, u64 n, u32 *marks);
+ivx_status ivx_mark_probe(ivx_ctx *ctx, const JoinIndexView &jv, const u32 *key, const i32 *s, const i32 *e, u64 n, u32 *marks,
+                          const WherePred *w = nullptr);
 ivx_status ivx_mark_probe_regions(ivx_ctx *ctx, const JoinIndexView &jv, u32 nreg, const u32 *key, const i32 *s, const i32 *e, u64 n,
-                                  u32 *marks, bool has_filter, bool pk24, bool fast, bool *took);
+                                  u32 *marks, bool has_filter, bool pk24, bool fast, bool *took, const WherePred *w = nullptr);
 // overlap aggregates (ivx_agg.hip; the lean region form in ivx_regions_probe.hip): per probe row, over the build rows the
 // join pairs it with, aggregates of a build-side value column (val_bytes: 4 or 8, signed).  The call's output columns, one
 // element per probe row in input order; null: not wanted, neither computed nor stored
 struct AggOut { u32 *count; i64 *sum, *vmin, *vmax, *bases, *wsum; };
 ivx_status ivx_agg_probe(ivx_ctx *ctx, const JoinIndexView &jv, const u32 *key, const i32 *s, const i32 *e, u64 n,
-                         const void *val, u32 val_bytes, const AggOut &out);
+                         const void *val, u32 val_bytes, const AggOut &out, const WherePred *w = nullptr);
 ivx_status ivx_agg_probe_regions(ivx_ctx *ctx, const JoinIndexView &jv, u32 nreg, const u32 *key, const i32 *s, const i32 *e, u64 n,
-                                 const void *val, u32 val_bytes, const AggOut &out, bool has_filter, bool pk24, bool fast, bool *took);
+                                 const void *val, u32 val_bytes, const AggOut &out, bool has_filter, bool pk24, bool fast, bool *took,
+                                 const WherePred *w = nullptr);
 // overlap select (ivx_select.hip; the lean region form in ivx_regions_probe.hip): per probe row the one build row of those the
 // join pairs it with that is best by `by` (an IVX_SEL_* criterion; val / val_bytes are read by the *_VAL ones only).  idx is
 // always wanted; score may be null: neither computed nor stored
 struct SelOut { u32 *idx; i64 *score; };
 ivx_status ivx_sel_probe(ivx_ctx *ctx, const JoinIndexView &jv, const u32 *key, const i32 *s, const i32 *e, u64 n,
-                         const void *val, u32 val_bytes, int by, const SelOut &out);
+                         const void *val, u32 val_bytes, int by, const SelOut &out, const WherePred *w = nullptr);
 ivx_status ivx_sel_probe_regions(ivx_ctx *ctx, const JoinIndexView &jv, u32 nreg, const u32 *key, const i32 *s, const i32 *e, u64 n,
-                                 const void *val, u32 val_bytes, int by, const SelOut &out, bool has_filter, bool pk24, bool fast, bool *took);
+                                 const void *val, u32 val_bytes, int by, const SelOut &out, bool has_filter, bool pk24, bool fast, bool *took,
+                                 const WherePred *w = nullptr);
+// overlap thresholds (ivx_where.hip; the lean region form in ivx_regions_probe.hip).  The match count per probe row under a
+// threshold: per_row / exists (either may be null), one element per probe row in input order.  The region form has the
+// marks' eligibility and *took, writes ONE of the two columns (per_row if given) and, with per_row, adds the counts to *d_total
+// (nullable) in its un-permute.
+ivx_status ivx_match_probe_where(ivx_ctx *ctx, const JoinIndexView &jv, const u32 *key, const i32 *s, const i32 *e, u64 n,
+                                 u32 *per_row, u8 *exists, const WherePred &w);
+ivx_status ivx_match_probe_regions_where(ivx_ctx *ctx, const JoinIndexView &jv, u32 nreg, const u32 *key, const i32 *s, const i32 *e, u64 n,
+                                         u32 *per_row, u8 *exists, u64 *d_total, bool has_filter, bool pk24, bool fast, bool *took, const WherePred &w);
+// *d_total += the sum of per_row[0 .. n) (null: not wanted), and exists[i] = per_row[i] != 0 when exists is given
+ivx_status ivx_match_totals(ivx_ctx *ctx, const u32 *per_row, u64 n, u8 *exists, u64 *d_total);
+// the stable pair filter (ivx_pairs_where of include/ivx_where.h, device pointers); scratch: WS_T5, WS_T6 and the scan's
+ivx_status ivx_pairs_where_device(ivx_ctx *ctx, const u32 *bidx, const u32 *pidx, u64 n_pairs, const i32 *bs, const i32 *be, u64 nb,
+                                  const i32 *ps, const i32 *pe, u64 np, const WherePred &w, u32 *ob, u32 *op, u64 cap, u64 *n_out);
 ivx_status ivx_bits_mark_device(ivx_ctx *ctx, const u32 *idx, u64 n, u32 *bits, u64 n_bits);
 ivx_status ivx_bits_select_device(ivx_ctx *ctx, const u32 *bits, u64 n_bits, int want_set, u32 *out, u64 cap, u64 *n_out);
 

@@ -11,7 +11,7 @@
 //   k_bits_mark    OR bit idx[i] for a list of row numbers (Left / Full joins: the pairs exist anyway)
 //   k_bits_count / k_bits_write   ivx_bits_select: positions of the set (or clear) bits, ascending -- popcount per 256-word
 //                  block, exclusive scan of the block counts, then every lane expands its word at block base + prefix.
-#include "ivx_rowops.hpp"
+#include "ivx_where.hpp"
 
 namespace {
 
@@ -61,9 +61,12 @@ __global__ __launch_bounds__(MT) void k_bits_write(const u32 *__restrict__ bits,
 
 }  // namespace
 
-ivx_status ivx_mark_probe(ivx_ctx *ctx, const JoinIndexView &jv, const u32 *key, const i32 *s, const i32 *e, u64 n, u32 *marks)
+ivx_status ivx_mark_probe(ivx_ctx *ctx, const JoinIndexView &jv, const u32 *key, const i32 *s, const i32 *e, u64 n, u32 *marks,
+                          const WherePred *w)
 {
-    return ivx_direct_probe(ctx, jv, key, s, e, n, MarkOp{{}, marks});
+    ivx_status st = IVX_OK;
+    with_where(w, MarkOp{{}, marks}, [&](const auto &op) { st = ivx_direct_probe(ctx, jv, key, s, e, n, op); });
+    return st;
 }
 
 ivx_status ivx_bits_mark_device(ivx_ctx *ctx, const u32 *idx, u64 n, u32 *bits, u64 n_bits)

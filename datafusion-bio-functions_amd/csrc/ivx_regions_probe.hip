@@ -26,6 +26,7 @@
 #include "ivx_regions.hpp"
 #include "ivx_agg.hpp"
 #include "ivx_select.hpp"
+#include "ivx_where.hpp"
 
 namespace {
 
@@ -1571,12 +1572,12 @@ ivx_status ivx_rowval_probe_regions(ivx_ctx *ctx, const JoinIndexView &jv, u32 n
 // false (nothing launched) when the index or the settings do not qualify: the caller then runs the direct kernel
 // (ivx_mark_probe) on its columns.  (*took means something on IVX_OK only.)
 ivx_status ivx_mark_probe_regions(ivx_ctx *ctx, const JoinIndexView &jv, u32 nreg, const u32 *key, const i32 *s, const i32 *e, u64 n,
-                                  u32 *marks, bool has_filter, bool pk24, bool fast, bool *took)
+                                  u32 *marks, bool has_filter, bool pk24, bool fast, bool *took, const WherePred *w)
 {
     ivx_routed R;
     IVX_TRY(lean_route(ctx, jv, nreg, key, s, e, n, has_filter, pk24, fast, true, &R, took));       // (no un-permute: no vtab)
     if (!*took) return IVX_OK;
-    lean_launch<IVX_RV_B>(ctx->stream, jv, R, s, e, MarkOp{{}, marks});
+    with_where(w, MarkOp{{}, marks}, [&](const auto &op) { lean_launch<IVX_RV_B>(ctx->stream, jv, R, s, e, op); });
     IVX_HIP(ctx, hipGetLastError());
     return IVX_OK;
 }
@@ -1586,7 +1587,8 @@ ivx_status ivx_mark_probe_regions(ivx_ctx *ctx, const JoinIndexView &jv, u32 nre
 // and the caller runs the direct kernel (ivx_agg_probe).  The outputs are device columns in input order:
 // ivx_unroute_records brings the records there and gives the rows the routing pass dropped the empty result.
 ivx_status ivx_agg_probe_regions(ivx_ctx *ctx, const JoinIndexView &jv, u32 nreg, const u32 *key, const i32 *s, const i32 *e, u64 n,
-                                 const void *val, u32 val_bytes, const AggOut &out, bool has_filter, bool pk24, bool fast, bool *took)
+                                 const void *val, u32 val_bytes, const AggOut &out, bool has_filter, bool pk24, bool fast, bool *took,
+                                 const WherePred *w)
 {
     ivx_routed R;
     IVX_TRY(lean_route(ctx, jv, nreg, key, s, e, n, has_filter, pk24, fast, false, &R, took));
@@ -1598,7 +1600,7 @@ ivx_status ivx_agg_probe_regions(ivx_ctx *ctx, const JoinIndexView &jv, u32 nreg
     c.take(rec.sum, out.sum); c.take(rec.vmin, out.vmin); c.take(rec.vmax, out.vmax); c.take(rec.bases, out.bases); c.take(rec.wsum, out.wsum);
     c.take(rec.count, out.count);
     with_bools([&](auto wide, auto mm, auto wt) {
-        lean_launch<IVX_AGG_B>(ctx->stream, jv, R, s, e, AggOp<IVX_B(wide) ? 8 : 4, IVX_B(mm), IVX_B(wt)>{{}, val, rec});
+        with_where(w, AggOp<IVX_B(wide) ? 8 : 4, IVX_B(mm), IVX_B(wt)>{{}, val, rec}, [&](const auto &op) { lean_launch<IVX_AGG_B>(ctx->stream, jv, R, s, e, op); });
     }, val_bytes == 8, out.vmin || out.vmax, out.bases || out.wsum);
     IVX_HIP(ctx, hipGetLastError());
     return ivx_unroute_records(ctx, R, nreg, n, rec, out);
@@ -1608,7 +1610,8 @@ ivx_status ivx_agg_probe_regions(ivx_ctx *ctx, const JoinIndexView &jv, u32 nreg
 // lean form only, with ivx_agg_probe_regions' eligibility and *took.  The outputs are device columns in input order:
 // ivx_unroute_sel_records brings the records there and gives the rows the routing pass dropped (IVX_NULL_IDX, 0).
 ivx_status ivx_sel_probe_regions(ivx_ctx *ctx, const JoinIndexView &jv, u32 nreg, const u32 *key, const i32 *s, const i32 *e, u64 n,
-                                 const void *val, u32 val_bytes, int by, const SelOut &out, bool has_filter, bool pk24, bool fast, bool *took)
+                                 const void *val, u32 val_bytes, int by, const SelOut &out, bool has_filter, bool pk24, bool fast, bool *took,
+                                 const WherePred *w)
 {
     ivx_routed R;
     IVX_TRY(lean_route(ctx, jv, nreg, key, s, e, n, has_filter, pk24, fast, false, &R, took));
@@ -1618,8 +1621,23 @@ ivx_status ivx_sel_probe_regions(ivx_ctx *ctx, const JoinIndexView &jv, u32 nreg
     SelOut rec{};
     c.take(rec.score, out.score); c.take(rec.idx, out.idx);
     sel_dispatch(by, val_bytes, out.score != nullptr, [&](auto b, auto vb, auto sc) {
-        lean_launch<IVX_AGG_B>(ctx->stream, jv, R, s, e, SelOp<decltype(b)::value, decltype(vb)::value, decltype(sc)::value>{{}, val, rec});
+        with_where(w, SelOp<decltype(b)::value, decltype(vb)::value, decltype(sc)::value>{{}, val, rec}, [&](const auto &op) { lean_launch<IVX_AGG_B>(ctx->stream, jv, R, s, e, op); });
     });
     IVX_HIP(ctx, hipGetLastError());
     return ivx_unroute_sel_records(ctx, R, nreg, n, rec, out);
+}
+
+// The match count per probe row under a threshold, through the region partition -- the lean form only, with
+// ivx_mark_probe_regions' eligibility and *took.  RvOp<RV_MATCHES> behind the threshold leaves each count in the row's own
+// word; the un-permute brings it to per_row -- adding the counts to *d_total on its way, if that is given -- or, per_row null,
+// as "count != 0" to exists.
+ivx_status ivx_match_probe_regions_where(ivx_ctx *ctx, const JoinIndexView &jv, u32 nreg, const u32 *key, const i32 *s, const i32 *e, u64 n,
+                                         u32 *per_row, u8 *exists, u64 *d_total, bool has_filter, bool pk24, bool fast, bool *took, const WherePred &w)
+{
+    ivx_routed R;
+    IVX_TRY(lean_route(ctx, jv, nreg, key, s, e, n, has_filter, pk24, fast, false, &R, took));
+    if (!*took) return IVX_OK;
+    lean_launch<IVX_RV_B>(ctx->stream, jv, R, s, e, WhereOp<RvOp<RV_MATCHES>>{RvOp<RV_MATCHES>{{}, 0u}, w});
+    IVX_HIP(ctx, hipGetLastError());
+    return ivx_unroute_values(ctx, R, nreg, per_row ? IVX_RV_PER_ROW : IVX_RV_EXISTS, nullptr, n, per_row ? (void *)per_row : (void *)exists, per_row ? d_total : nullptr);
 }

@@ -8,14 +8,14 @@
 // on k_lean / k_lean_rest in ivx_regions_probe.hip.)
 //
 // A row without a match stores IVX_NULL_IDX and score 0.
-#include "ivx_select.hpp"
+#include "ivx_where.hpp"
 
 ivx_status ivx_sel_probe(ivx_ctx *ctx, const JoinIndexView &jv, const u32 *key, const i32 *s, const i32 *e, u64 n,
-                         const void *val, u32 val_bytes, int by, const SelOut &out)
+                         const void *val, u32 val_bytes, int by, const SelOut &out, const WherePred *w)
 {
     ivx_status st = IVX_OK;
     sel_dispatch(by, val_bytes, out.score != nullptr, [&](auto b, auto vb, auto sc) {
-        st = ivx_direct_probe(ctx, jv, key, s, e, n, SelOp<decltype(b)::value, decltype(vb)::value, decltype(sc)::value>{{}, val, out});
+        with_where(w, SelOp<decltype(b)::value, decltype(vb)::value, decltype(sc)::value>{{}, val, out}, [&](const auto &op) { st = ivx_direct_probe(ctx, jv, key, s, e, n, op); });
     });
     return st;
 }

@@ -3,6 +3,7 @@
 #include "../../include/bio_ranges_host.h"
 #include "../../include/ivx.h"
 #include "../../include/ivx_select.h"
+#include "../../include/ivx_where.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -347,9 +348,33 @@ int select_build_rows(brh_session *s, const std::vector<uint32_t> &marks, uint64
     return 0;
 }
 
-// the Inner pairs of one batch (count, then fill), and behind them the probe rows without a match, build_idx NULL (Right / Full)
+// an overlap threshold of the table layer as the entries of ivx_where.h take it (null stays null: the plain call)
+struct WhereArg {
+    ivx_overlap_where w{};
+    const ivx_overlap_where *p = nullptr;
+    explicit WhereArg(const brh_overlap_where *b)
+    {
+        if (!b) return;
+        w.min_bases = b->min_bases; w.probe_num = b->probe_num; w.probe_den = b->probe_den;
+        w.build_num = b->build_num; w.build_den = b->build_den; w.either = b->either;
+        p = &w;
+    }
+    bool asks() const { return p && (w.min_bases > 0 || w.probe_num || w.build_num); }
+};
+
+// probe rows with a match: ivx_probe_exists, or under a threshold the exists bytes of ivx_probe_overlap_count_where
+ivx_status probe_exists(brh_session *s, const ivx_index *ix, const uint32_t *pk, const int32_t *ps, const int32_t *pe, uint64_t np,
+                        const ivx_overlap_where *w, uint8_t *ex)
+{
+    if (!w) return ivx_probe_exists(s->ctx, ix, IVX_MEM_HOST, pk, ps, pe, np, ex);
+    return ivx_probe_overlap_count_where(s->ctx, ix, IVX_MEM_HOST, pk, ps, pe, np, w, nullptr, ex, nullptr);
+}
+
+// the Inner pairs of one batch (count, then fill; under a threshold then ivx_pairs_where over the build side's columns bs / be),
+// and behind them the probe rows without a match, build_idx NULL (Right / Full)
 int join_pairs(brh_session *s, const ivx_index *ix, const uint32_t *pk, const int32_t *ps, const int32_t *pe, uint64_t np, bool null_build,
-               std::vector<uint32_t> *bi, std::vector<uint32_t> *pi, std::vector<uint8_t> *bvalid, uint64_t *n_pairs)
+               std::vector<uint32_t> *bi, std::vector<uint32_t> *pi, std::vector<uint8_t> *bvalid, uint64_t *n_pairs,
+               const ivx_overlap_where *w = nullptr, const int32_t *bs = nullptr, const int32_t *be = nullptr, uint64_t nb = 0)
 {
     uint64_t total = 0, written = 0;
     ivx_status st = ivx_probe_overlap_count(s->ctx, ix, IVX_MEM_HOST, pk, ps, pe, np, nullptr, &total);
@@ -357,11 +382,20 @@ int join_pairs(brh_session *s, const ivx_index *ix, const uint32_t *pk, const in
     bi->assign(total ? total : 1, 0u); pi->assign(total ? total : 1, 0u);
     st = ivx_probe_overlap_fill(s->ctx, ix, IVX_MEM_HOST, pk, ps, pe, np, bi->data(), pi->data(), total, &written);
     if (st != IVX_OK) return fail_ivx(s, st);
+    if (w) {
+        std::vector<uint32_t> fb(written ? written : 1), fp(written ? written : 1);
+        uint64_t kept = 0;
+        st = ivx_pairs_where(s->ctx, IVX_MEM_HOST, bi->data(), pi->data(), written, bs, be, nb, ps, pe, np, w,
+                             written ? fb.data() : nullptr, written ? fp.data() : nullptr, written, &kept);
+        if (st != IVX_OK) return fail_ivx(s, st);
+        bi->swap(fb); pi->swap(fp);
+        written = kept;
+    }
     bi->resize(written); pi->resize(written);
     *n_pairs = written;
     if (null_build) {
         std::vector<uint8_t> ex(np ? np : 1);
-        st = ivx_probe_exists(s->ctx, ix, IVX_MEM_HOST, pk, ps, pe, np, ex.data());
+        st = probe_exists(s, ix, pk, ps, pe, np, w, ex.data());
         if (st != IVX_OK) return fail_ivx(s, st);
         bvalid->assign(written, 1);
         for (uint64_t i = 0; i < np; i++) if (!ex[i]) { bi->push_back(0u); pi->push_back((uint32_t)i); bvalid->push_back(0); }
@@ -492,12 +526,19 @@ extern "C" int brh_nearest(brh_session *s, brh_batch left, brh_columns lcols, br
     return 0;
 }
 
-extern "C" int brh_interval_join(brh_session *s, brh_batch build, brh_columns bcols, brh_batch probe, brh_columns pcols,
-                                 int join_type, int strict_predicate, int nearest_algorithm,
-                                 ArrowArray *build_idx, ArrowSchema *build_idx_schema, ArrowArray *probe_idx, ArrowSchema *probe_idx_schema)
+namespace {
+// brh_interval_join and brh_interval_join_where: where = null is the plain join.  Under a threshold every join type is taken
+// from the same filtered matches: Inner = the fill, then ivx_pairs_where; RightSemi / RightAnti from the filtered exists;
+// LeftSemi / LeftAnti from the filtered marks; Left / Right / Full = the filtered pairs, then the rows without one.
+int interval_join_impl(brh_session *s, brh_batch build, brh_columns bcols, brh_batch probe, brh_columns pcols,
+                       int join_type, int strict_predicate, int nearest_algorithm, const brh_overlap_where *where,
+                       ArrowArray *build_idx, ArrowSchema *build_idx_schema, ArrowArray *probe_idx, ArrowSchema *probe_idx_schema)
 {
     if (!s) return 1;
     if (nearest_algorithm && join_marks_build(join_type)) return fail(s, "interval join: Algorithm::CoitreesNearest is an Inner join");
+    const WhereArg wa(where);
+    const ivx_overlap_where *w = wa.p;
+    if (nearest_algorithm && wa.asks()) return fail(s, "interval join: an overlap threshold (where) does not apply to Algorithm::CoitreesNearest");
     KeyDict kd; Side32 B, P;
     if (build_keys(s, {{build, bcols}, {probe, pcols}}, &kd, true) || load_side32(s, build, bcols, &B) || load_side32(s, probe, pcols, &P)) return 1;
     if (strict_predicate) {                                       // `a.start < b.end AND a.end > b.start`: end - 1 on both sides
@@ -523,7 +564,7 @@ extern "C" int brh_interval_join(brh_session *s, brh_batch build, brh_columns bc
     }
     if (join_type == BRH_JOIN_RIGHT_SEMI || join_type == BRH_JOIN_RIGHT_ANTI) {      // :1014-1024, :1433-1447
         std::vector<uint8_t> ex(np ? np : 1);
-        st = ivx_probe_exists(s->ctx, g.ix, IVX_MEM_HOST, kd.ids[1].data(), P.s.data(), P.e.data(), np, ex.data());
+        st = probe_exists(s, g.ix, kd.ids[1].data(), P.s.data(), P.e.data(), np, w, ex.data());
         if (st != IVX_OK) return fail_ivx(s, st);
         std::vector<uint32_t> pi;
         const bool want = join_type == BRH_JOIN_RIGHT_SEMI;
@@ -535,7 +576,7 @@ extern "C" int brh_interval_join(brh_session *s, brh_batch build, brh_columns bc
     const uint64_t nb = B.s.size();
     if (join_type == BRH_JOIN_LEFT_SEMI || join_type == BRH_JOIN_LEFT_ANTI) {        // the build rows with / without a match: no pairs are made
         std::vector<uint32_t> marks((nb + 31) / 32 + 1, 0u), rows;
-        st = ivx_probe_mark_build(s->ctx, g.ix, IVX_MEM_HOST, kd.ids[1].data(), P.s.data(), P.e.data(), np, marks.data());
+        st = ivx_probe_mark_build_where(s->ctx, g.ix, IVX_MEM_HOST, kd.ids[1].data(), P.s.data(), P.e.data(), np, w, marks.data());
         if (st != IVX_OK) return fail_ivx(s, st);
         if (select_build_rows(s, marks, nb, join_type == BRH_JOIN_LEFT_SEMI, &rows)) return 1;
         make_primitive<uint32_t>(build_idx, rows.data(), (int64_t)rows.size(), nullptr); make_schema(build_idx_schema, "I", "build_idx", false);
@@ -546,7 +587,7 @@ extern "C" int brh_interval_join(brh_session *s, brh_batch build, brh_columns bc
         const bool nullb = join_null_build(join_type), nullp = join_null_probe(join_type);
         std::vector<uint32_t> bi, pi; std::vector<uint8_t> bvalid, pvalid;
         uint64_t n_pairs = 0;
-        if (join_pairs(s, g.ix, kd.ids[1].data(), P.s.data(), P.e.data(), np, nullb, &bi, &pi, &bvalid, &n_pairs)) return 1;
+        if (join_pairs(s, g.ix, kd.ids[1].data(), P.s.data(), P.e.data(), np, nullb, &bi, &pi, &bvalid, &n_pairs, w, B.s.data(), B.e.data(), nb)) return 1;
         if (nullp) {
             std::vector<uint32_t> marks((nb + 31) / 32 + 1, 0u), rows;
             st = ivx_bits_mark(s->ctx, IVX_MEM_HOST, bi.data(), n_pairs, marks.data(), nb);
@@ -560,6 +601,14 @@ extern "C" int brh_interval_join(brh_session *s, brh_batch build, brh_columns bc
         make_primitive<uint32_t>(probe_idx, pi.data(), (int64_t)pi.size(), nullp ? pvalid.data() : nullptr); make_schema(probe_idx_schema, "I", "probe_idx", nullp);
         return 0;
     }
+    if (w) {                                                                         // Inner under a threshold: the fill, then the pair filter
+        std::vector<uint32_t> bi, pi; std::vector<uint8_t> unused;
+        uint64_t n_pairs = 0;
+        if (join_pairs(s, g.ix, kd.ids[1].data(), P.s.data(), P.e.data(), np, false, &bi, &pi, &unused, &n_pairs, w, B.s.data(), B.e.data(), nb)) return 1;
+        make_primitive<uint32_t>(build_idx, bi.data(), (int64_t)n_pairs, nullptr); make_schema(build_idx_schema, "I", "build_idx", false);
+        make_primitive<uint32_t>(probe_idx, pi.data(), (int64_t)n_pairs, nullptr); make_schema(probe_idx_schema, "I", "probe_idx", false);
+        return 0;
+    }
     uint64_t total = 0;
     st = ivx_probe_overlap_count(s->ctx, g.ix, IVX_MEM_HOST, kd.ids[1].data(), P.s.data(), P.e.data(), np, nullptr, &total);
     if (st != IVX_OK) return fail_ivx(s, st);
@@ -570,6 +619,22 @@ extern "C" int brh_interval_join(brh_session *s, brh_batch build, brh_columns bc
     make_primitive<uint32_t>(build_idx, bi.data(), (int64_t)written, nullptr); make_schema(build_idx_schema, "I", "build_idx", false);
     make_primitive<uint32_t>(probe_idx, pi.data(), (int64_t)written, nullptr); make_schema(probe_idx_schema, "I", "probe_idx", false);
     return 0;
+}
+}  // namespace
+
+extern "C" int brh_interval_join(brh_session *s, brh_batch build, brh_columns bcols, brh_batch probe, brh_columns pcols,
+                                 int join_type, int strict_predicate, int nearest_algorithm,
+                                 ArrowArray *build_idx, ArrowSchema *build_idx_schema, ArrowArray *probe_idx, ArrowSchema *probe_idx_schema)
+{
+    return interval_join_impl(s, build, bcols, probe, pcols, join_type, strict_predicate, nearest_algorithm, nullptr,
+                              build_idx, build_idx_schema, probe_idx, probe_idx_schema);
+}
+extern "C" int brh_interval_join_where(brh_session *s, brh_batch build, brh_columns bcols, brh_batch probe, brh_columns pcols,
+                                       int join_type, int strict_predicate, int nearest_algorithm, const brh_overlap_where *where,
+                                       ArrowArray *build_idx, ArrowSchema *build_idx_schema, ArrowArray *probe_idx, ArrowSchema *probe_idx_schema)
+{
+    return interval_join_impl(s, build, bcols, probe, pcols, join_type, strict_predicate, nearest_algorithm, where,
+                              build_idx, build_idx_schema, probe_idx, probe_idx_schema);
 }
 
 // ---- overlap aggregates: join on overlap, group by probe row, aggregate a build-side value (ivx.h ivx_probe_overlap_agg)
@@ -643,11 +708,12 @@ int load_sel_values(brh_session *s, brh_batch t, const char *name, std::vector<i
 }  // namespace
 
 // ---- overlap select: join on overlap, keep the one best build row per probe row (ivx_select.h ivx_probe_overlap_select)
-extern "C" int brh_overlap_select(brh_session *s, brh_batch build, brh_columns bcols, const char *value_column,
-                                  brh_batch probe, brh_columns pcols, int strict_predicate, int by,
-                                  ArrowArray *build_idx, ArrowSchema *build_idx_schema, ArrowArray *score, ArrowSchema *score_schema)
+static int overlap_select_impl(brh_session *s, brh_batch build, brh_columns bcols, const char *value_column,
+                               brh_batch probe, brh_columns pcols, int strict_predicate, int by, const brh_overlap_where *where,
+                               ArrowArray *build_idx, ArrowSchema *build_idx_schema, ArrowArray *score, ArrowSchema *score_schema)
 {
     if (!s) return 1;
+    const WhereArg wa(where);
     if (!build_idx || !build_idx_schema || !score || !score_schema) return fail(s, "overlap_select: null outputs");
     if (by < 0 || by >= BRH_SEL_N) return fail(s, "overlap_select: by is one of the BRH_SEL_* criteria, got " + std::to_string(by));
     const bool by_val = by == BRH_SEL_MIN_VAL || by == BRH_SEL_MAX_VAL;
@@ -669,8 +735,8 @@ extern "C" int brh_overlap_select(brh_session *s, brh_batch build, brh_columns b
     std::vector<uint32_t> bi(na);
     std::vector<int64_t> sc(exact ? na : 0);
     const void *val = !by_val ? nullptr : vb == 4 ? (const void *)v32.data() : (const void *)v64.data();     // (may be null for an empty build side: never read)
-    st = ivx_probe_overlap_select(s->ctx, g.ix, IVX_MEM_HOST, kd.ids[1].data(), P.s.data(), P.e.data(), np, val, vb, by,
-                                  bi.data(), exact ? sc.data() : nullptr);
+    st = ivx_probe_overlap_select_where(s->ctx, g.ix, IVX_MEM_HOST, kd.ids[1].data(), P.s.data(), P.e.data(), np, val, vb, by, wa.p,
+                                        bi.data(), exact ? sc.data() : nullptr);
     if (st != IVX_OK) return fail_ivx(s, st);
     std::vector<uint8_t> valid(na);
     for (uint64_t i = 0; i < np; i++) { valid[i] = bi[i] != IVX_NULL_IDX; if (!valid[i]) bi[i] = 0; }     // (a NULL slot's value)
@@ -679,12 +745,25 @@ extern "C" int brh_overlap_select(brh_session *s, brh_batch build, brh_columns b
     if (exact) { make_primitive<int64_t>(score, sc.data(), (int64_t)np, valid.data()); make_schema(score_schema, "l", "score", true); }
     return 0;
 }
+extern "C" int brh_overlap_select(brh_session *s, brh_batch build, brh_columns bcols, const char *value_column,
+                                  brh_batch probe, brh_columns pcols, int strict_predicate, int by,
+                                  ArrowArray *build_idx, ArrowSchema *build_idx_schema, ArrowArray *score, ArrowSchema *score_schema)
+{
+    return overlap_select_impl(s, build, bcols, value_column, probe, pcols, strict_predicate, by, nullptr, build_idx, build_idx_schema, score, score_schema);
+}
+extern "C" int brh_overlap_select_where(brh_session *s, brh_batch build, brh_columns bcols, const char *value_column,
+                                        brh_batch probe, brh_columns pcols, int strict_predicate, int by, const brh_overlap_where *where,
+                                        ArrowArray *build_idx, ArrowSchema *build_idx_schema, ArrowArray *score, ArrowSchema *score_schema)
+{
+    return overlap_select_impl(s, build, bcols, value_column, probe, pcols, strict_predicate, by, where, build_idx, build_idx_schema, score, score_schema);
+}
 
-extern "C" int brh_overlap_aggregate(brh_session *s, brh_batch build, brh_columns bcols, const char *value_column,
-                                     brh_batch probe, brh_columns pcols, int strict_predicate, uint32_t ops,
-                                     ArrowArray *out, ArrowSchema *out_schema)
+static int overlap_aggregate_impl(brh_session *s, brh_batch build, brh_columns bcols, const char *value_column,
+                                  brh_batch probe, brh_columns pcols, int strict_predicate, uint32_t ops, const brh_overlap_where *where,
+                                  ArrowArray *out, ArrowSchema *out_schema)
 {
     if (!s) return 1;
+    const WhereArg wa(where);
     if (!value_column) return fail(s, "overlap_aggregate: null value column name");
     if (!out || !out_schema) return fail(s, "overlap_aggregate: null outputs");
     if (ops == 0 || (ops & ~(uint32_t)BRH_AGG_ALL)) return fail(s, "overlap_aggregate: ops is a non-empty set of BRH_AGG_* bits");
@@ -708,8 +787,8 @@ extern "C" int brh_overlap_aggregate(brh_session *s, brh_batch build, brh_column
     for (int k = 1; k < BRH_AGG_N; k++) if (ops & (1u << k)) col[k].resize(na);
     auto ptr = [&](int k) { return col[k].empty() ? nullptr : col[k].data(); };
     const void *val = vb == 4 ? (const void *)v32.data() : (const void *)v64.data();     // (may be null for an empty build side: never read)
-    st = ivx_probe_overlap_agg(s->ctx, g.ix, IVX_MEM_HOST, kd.ids[1].data(), P.s.data(), P.e.data(), np, val, vb,
-                               cnt.empty() ? nullptr : cnt.data(), ptr(1), ptr(2), ptr(3), ptr(4), ptr(5));
+    st = ivx_probe_overlap_agg_where(s->ctx, g.ix, IVX_MEM_HOST, kd.ids[1].data(), P.s.data(), P.e.data(), np, val, vb, wa.p,
+                                     cnt.empty() ? nullptr : cnt.data(), ptr(1), ptr(2), ptr(3), ptr(4), ptr(5));
     if (st != IVX_OK) return fail_ivx(s, st);
     std::vector<uint8_t> valid(nullable ? na : 0);
     for (uint64_t i = 0; nullable && i < np; i++) valid[i] = cnt[i] != 0;
@@ -724,6 +803,18 @@ extern "C" int brh_overlap_aggregate(brh_session *s, brh_batch build, brh_column
         make_schema(&out_schema[k], "l", names[k], nulls);
     }
     return 0;
+}
+extern "C" int brh_overlap_aggregate(brh_session *s, brh_batch build, brh_columns bcols, const char *value_column,
+                                     brh_batch probe, brh_columns pcols, int strict_predicate, uint32_t ops,
+                                     ArrowArray *out, ArrowSchema *out_schema)
+{
+    return overlap_aggregate_impl(s, build, bcols, value_column, probe, pcols, strict_predicate, ops, nullptr, out, out_schema);
+}
+extern "C" int brh_overlap_aggregate_where(brh_session *s, brh_batch build, brh_columns bcols, const char *value_column,
+                                           brh_batch probe, brh_columns pcols, int strict_predicate, uint32_t ops, const brh_overlap_where *where,
+                                           ArrowArray *out, ArrowSchema *out_schema)
+{
+    return overlap_aggregate_impl(s, build, bcols, value_column, probe, pcols, strict_predicate, ops, where, out, out_schema);
 }
 
 extern "C" int brh_merge(brh_session *s, brh_batch table, brh_columns cols, int64_t min_dist, int filter_op,

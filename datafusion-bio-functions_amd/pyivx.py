@@ -41,6 +41,13 @@ SYMBOLS = [
 # not in include/ivx.h yet, bound beside SYMBOLS the way the test hooks are
 EXT_SYMBOLS = ["ivx_probe_overlap_select"]
 
+# every symbol include/ivx_where.h declares (checked by tests/test_where_abi.py): the overlap thresholds' entries, a list of
+# their own
+WHERE_SYMBOLS = ["ivx_probe_overlap_count_where", "ivx_probe_mark_build_where", "ivx_probe_overlap_agg_where",
+                 "ivx_probe_overlap_select_where", "ivx_pairs_where"]
+# pairs per tile of ivx_pairs_where's two passes (csrc/ivx_where.hpp PW_TILE = PW_T * PW_PI; tests/test_gpu_overlap_where.py)
+PAIRS_WHERE_TILE = 1024
+
 # outputs one workgroup of the expand kernel makes (csrc/ivx_depth_expand.hip DEPTH_EXPAND_TILE; tests/test_depth_per_base_tile.py)
 DEPTH_EXPAND_TILE = 4096
 # merged steps one workgroup of the merge kernel makes (csrc/ivx_depth_merge.hip DEPTH_MERGE_TILE; tests/test_depth_merge_cpu.py)
@@ -116,6 +123,70 @@ class Metrics(C.Structure):
                 ("input_rows", C.c_uint64), ("output_batches", C.c_uint64), ("output_rows", C.c_uint64)]
 
 
+class OverlapWhereC(C.Structure):
+    """ivx_overlap_where of include/ivx_where.h"""
+    _fields_ = [("min_bases", C.c_int64), ("probe_num", C.c_uint32), ("probe_den", C.c_uint32),
+                ("build_num", C.c_uint32), ("build_den", C.c_uint32), ("either", C.c_uint32)]
+
+
+def _fraction(f, what):
+    """(num, den) of a threshold fraction: None -> not asked; a (num, den) pair is taken as it is (the library checks it); a
+    Fraction exactly; a float as Fraction(f).limit_denominator(10**9) -- the nearest fraction with a denominator up to 10^9, so
+    0.5 is 1/2 and 0.1 is 1/10, but a pair that sits exactly on a boundary may fall on the other side of it than it does for a
+    tool that compares in floating point."""
+    from fractions import Fraction
+    if f is None:
+        return 0, 0
+    if isinstance(f, (tuple, list)):
+        if len(f) != 2:
+            raise ValueError(f"overlap where: {what} is a (num, den) pair")
+        return int(f[0]), int(f[1])
+    if isinstance(f, float):
+        if f != f or f < 0:
+            raise ValueError(f"overlap where: {what} is a fraction in [0, 1]")
+        f = Fraction(f).limit_denominator(10 ** 9)
+    if isinstance(f, (Fraction, int)) and not isinstance(f, bool):
+        f = Fraction(f)
+        if f < 0:
+            raise ValueError(f"overlap where: {what} is a fraction in [0, 1]")
+        return f.numerator, f.denominator
+    raise TypeError(f"overlap where: {what} is a (num, den) pair, a Fraction or a float")
+
+
+class OverlapWhere:
+    """An overlap threshold (include/ivx_where.h): min_bases shared bases, and / or minimum fractions of the probe row and of
+    the build row that the overlap must cover; either=True: one of two fractions suffices.  Fractions: see _fraction."""
+
+    def __init__(self, min_bases=0, probe=None, build=None, either=False):
+        self.min_bases, self.probe, self.build, self.either = min_bases, probe, build, either
+
+    def __repr__(self):
+        return f"OverlapWhere(min_bases={self.min_bases!r}, probe={self.probe!r}, build={self.build!r}, either={self.either!r})"
+
+    def c_struct(self):
+        pn, pd = _fraction(self.probe, "probe")
+        bn, bd = _fraction(self.build, "build")
+        for v in (pn, pd, bn, bd):
+            if not 0 <= v <= 0xFFFFFFFF:
+                raise ValueError("overlap where: a fraction's terms are unsigned 32-bit numbers")
+        return OverlapWhereC(int(self.min_bases), pn, pd, bn, bd, int(self.either))
+
+
+def as_where(w):
+    """None, an OverlapWhere, or a dict of its keywords -> a byref() argument (None: the NULL pointer) and the struct it
+    points to (to be kept alive across the call)"""
+    if w is None:
+        return None, None
+    if isinstance(w, dict):
+        w = OverlapWhere(**w)
+    if isinstance(w, OverlapWhereC):
+        return C.byref(w), w
+    if not isinstance(w, OverlapWhere):
+        raise TypeError("where is None, an OverlapWhere or a dict of its keywords")
+    s = w.c_struct()
+    return C.byref(s), s
+
+
 class IvxError(RuntimeError):
     def __init__(self, status, msg):
         super().__init__(f"ivx status {status}: {msg}")
@@ -159,6 +230,16 @@ def lib():
         L.ivx_probe_overlap_select.restype = C.c_int
         L.ivx_probe_overlap_select.argtypes = ([C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 3 + [C.c_uint64, C.c_void_p, C.c_uint32, C.c_int] +
                                                [C.c_void_p] * 2)
+        head = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 3 + [C.c_uint64]        # ctx, ix, mem, key, start, end, n
+        W = C.POINTER(OverlapWhereC)
+        for name in WHERE_SYMBOLS:
+            getattr(L, name).restype = C.c_int
+        L.ivx_probe_overlap_count_where.argtypes = head + [W, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
+        L.ivx_probe_mark_build_where.argtypes = head + [W, C.c_void_p]
+        L.ivx_probe_overlap_agg_where.argtypes = head + [C.c_void_p, C.c_uint32, W] + [C.c_void_p] * 6
+        L.ivx_probe_overlap_select_where.argtypes = head + [C.c_void_p, C.c_uint32, C.c_int, W] + [C.c_void_p] * 2
+        L.ivx_pairs_where.argtypes = ([C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64,
+                                       C.c_void_p, C.c_void_p, C.c_uint64, W, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)])
         L.ivx_depth.argtypes = ([C.c_void_p, C.c_int] + [C.c_void_p] * 6 + [C.c_uint64] + [C.c_void_p] * 4 + [C.c_uint64] +
                                 [C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32] + [C.c_void_p] * 4 +
                                 [C.c_uint64, C.POINTER(C.c_uint64)])
@@ -685,19 +766,25 @@ class Ctx:
         import torch
         return torch.zeros(max(nw, 1), dtype=torch.int32, device=device)
 
-    def mark_build(self, ix, key, start, end, marks):
-        """OR the bit of every build row of `ix` that a row of this batch overlaps into `marks` (ix.rows bits); -> marks"""
+    def mark_build(self, ix, key, start, end, marks, where=None):
+        """OR the bit of every build row of `ix` that a row of this batch overlaps into `marks` (ix.rows bits); -> marks.
+        where (as_where): only overlaps that pass the threshold count"""
         key, s, e, n, mem = _cols(key, start, end, np.int32)
         if _is_torch(marks) != (mem == MEM_DEVICE):
             raise ValueError("mix of host and device buffers in one call")
+        if where is not None:
+            wp, _keep = as_where(where)
+            self._chk(lib().ivx_probe_mark_build_where(self.h, ix.h, mem, _ptr(key), _ptr(s), _ptr(e), n, wp, _ptr(marks)))
+            return marks
         self._chk(lib().ivx_probe_mark_build(self.h, ix.h, C.c_int(mem), _ptr(key), _ptr(s), _ptr(e), C.c_uint64(n), _ptr(marks)))
         return marks
 
     # ---- a3''': overlap aggregates ----
-    def overlap_agg(self, ix, key, start, end, val, outputs=AGG_OUTPUTS):
+    def overlap_agg(self, ix, key, start, end, val, outputs=AGG_OUTPUTS, where=None):
         """per probe row, over the build rows the join pairs it with: aggregates of `val` (one int32 or int64 per build row
         of `ix`) -> {name: column} for the names in `outputs` (AGG_OUTPUTS): "count" uint32, the others int64 (min / max of
-        a row without a match: INT64_MAX / INT64_MIN).  numpy arrays, or device tensors ("count" then as its int32 bits)."""
+        a row without a match: INT64_MAX / INT64_MIN).  numpy arrays, or device tensors ("count" then as its int32 bits).
+        where (as_where): over the build rows whose overlap passes the threshold."""
         key, s, e, n, mem = _cols(key, start, end, np.int32)
         unknown = [o for o in outputs if o not in AGG_OUTPUTS]
         if unknown:
@@ -726,16 +813,22 @@ class Ctx:
                 out[name] = torch.empty(max(n, 1), dtype=torch.int32 if name == "count" else torch.int64, device=s.device)
             else:
                 out[name] = np.empty(max(n, 1), np.uint32 if name == "count" else np.int64)
-        self._chk(lib().ivx_probe_overlap_agg(self.h, ix.h, mem, _ptr(key), _ptr(s), _ptr(e), n, _ptr(val), vb,
-                                              *[_ptr(out[name]) for name in AGG_OUTPUTS]))
+        if where is not None:
+            wp, _keep = as_where(where)
+            self._chk(lib().ivx_probe_overlap_agg_where(self.h, ix.h, mem, _ptr(key), _ptr(s), _ptr(e), n, _ptr(val), vb, wp,
+                                                        *[_ptr(out[name]) for name in AGG_OUTPUTS]))
+        else:
+            self._chk(lib().ivx_probe_overlap_agg(self.h, ix.h, mem, _ptr(key), _ptr(s), _ptr(e), n, _ptr(val), vb,
+                                                  *[_ptr(out[name]) for name in AGG_OUTPUTS]))
         return {name: out[name][:n] for name in AGG_OUTPUTS if out[name] is not None}
 
     # ---- a3'''': overlap select ----
-    def overlap_select(self, ix, key, start, end, by="max_overlap", val=None, score=True):
+    def overlap_select(self, ix, key, start, end, by="max_overlap", val=None, score=True, where=None):
         """per probe row, of the build rows the join pairs it with, the one that is best by `by` (SEL_BY; ties: the smallest
         build row) -> (build_idx, score): build_idx uint32, NULL_IDX without a match; score int64, the criterion's value at
         the winner (0 without a match), or None with score=False.  `val` (one int32 or int64 per build row of `ix`) is read
-        by "min_val" / "max_val" only.  numpy arrays, or device tensors (build_idx then as its int32 bits)."""
+        by "min_val" / "max_val" only.  numpy arrays, or device tensors (build_idx then as its int32 bits).
+        where (as_where): of the build rows whose overlap passes the threshold."""
         key, s, e, n, mem = _cols(key, start, end, np.int32)
         if by not in SEL_BY:
             raise ValueError(f"overlap_select: by is one of {SEL_BY}, got {by!r}")
@@ -761,9 +854,93 @@ class Ctx:
         else:
             bi = np.empty(max(n, 1), np.uint32)
             sc = np.empty(max(n, 1), np.int64) if score else None
-        self._chk(lib().ivx_probe_overlap_select(self.h, ix.h, mem, _ptr(key), _ptr(s), _ptr(e), n, _ptr(val), vb, SEL_BY.index(by),
-                                                 _ptr(bi), _ptr(sc)))
+        if where is not None:
+            wp, _keep = as_where(where)
+            self._chk(lib().ivx_probe_overlap_select_where(self.h, ix.h, mem, _ptr(key), _ptr(s), _ptr(e), n, _ptr(val), vb, SEL_BY.index(by),
+                                                           wp, _ptr(bi), _ptr(sc)))
+        else:
+            self._chk(lib().ivx_probe_overlap_select(self.h, ix.h, mem, _ptr(key), _ptr(s), _ptr(e), n, _ptr(val), vb, SEL_BY.index(by),
+                                                     _ptr(bi), _ptr(sc)))
         return bi[:n], (sc[:n] if score else None)
+
+    # ---- a3''''': overlap thresholds (include/ivx_where.h) ----
+    def overlap_count_where(self, ix, key, start, end, where=None, per_row=True, exists=True, total=True):
+        """the matches of every probe row that pass `where` (as_where; None: all of them) -> {"per_row": uint32 column,
+        "exists": uint8 column, "total": int}, each only if wanted.  numpy arrays, or device tensors (per_row as int32 bits)."""
+        key, s, e, n, mem = _cols(key, start, end, np.int32)
+        wp, _keep = as_where(where)
+        pr = ex = None
+        if mem == MEM_DEVICE:
+            import torch
+            if per_row:
+                pr = torch.empty(max(n, 1), dtype=torch.int32, device=s.device)
+            if exists:
+                ex = torch.empty(max(n, 1), dtype=torch.uint8, device=s.device)
+        else:
+            if per_row:
+                pr = np.empty(max(n, 1), np.uint32)
+            if exists:
+                ex = np.empty(max(n, 1), np.uint8)
+        tot = C.c_uint64(0)
+        self._chk(lib().ivx_probe_overlap_count_where(self.h, ix.h, mem, _ptr(key), _ptr(s), _ptr(e), n, wp, _ptr(pr), _ptr(ex),
+                                                      C.byref(tot) if total else None))
+        out = {}
+        if per_row:
+            out["per_row"] = pr[:n]
+        if exists:
+            out["exists"] = ex[:n]
+        if total:
+            out["total"] = tot.value
+        return out
+
+    def pairs_where(self, build_idx, probe_idx, bstart, bend, pstart, pend, where=None, cap=None, count_only=False, out=None):
+        """the pairs (build_idx[j], probe_idx[j]) whose overlap passes `where` (as_where), in input order, from the two sides'
+        int32 coordinate columns -> (out_build, out_probe).  cap=None: a counting call sizes the outputs; count_only: -> the
+        count; out: the caller's own (out_build, out_probe).  A cap that is too small raises IvxError(ERR_CAPACITY) whose
+        .needed is the size."""
+        cols = (build_idx, probe_idx, bstart, bend, pstart, pend)
+        dev = _is_torch(build_idx)
+        if any(_is_torch(c) != dev for c in cols) or (out is not None and any(_is_torch(o) != dev for o in out)):
+            raise ValueError("mix of host and device buffers in one call")
+        if dev:
+            assert all(c.is_contiguous() for c in cols)
+            n, nb, npr = int(build_idx.numel()), int(bstart.numel()), int(pstart.numel())
+            assert int(probe_idx.numel()) == n and int(bend.numel()) == nb and int(pend.numel()) == npr
+        else:
+            build_idx, probe_idx = _np(build_idx, np.uint32), _np(probe_idx, np.uint32)
+            bstart, bend, pstart, pend = (_np(c, np.int32) for c in (bstart, bend, pstart, pend))
+            n, nb, npr = len(build_idx), len(bstart), len(pstart)
+            assert len(probe_idx) == n and len(bend) == nb and len(pend) == npr
+        wp, _keep = as_where(where)
+        mem = MEM_DEVICE if dev else MEM_HOST
+        m = C.c_uint64(0)
+
+        def call(ob, op, cap):
+            return lib().ivx_pairs_where(self.h, mem, _ptr(build_idx), _ptr(probe_idx), n, _ptr(bstart), _ptr(bend), nb,
+                                         _ptr(pstart), _ptr(pend), npr, wp, _ptr(ob), _ptr(op), cap, C.byref(m))
+
+        if out is not None:
+            ob, op = out
+            cap = int(ob.numel()) if dev else len(ob)
+        else:
+            if count_only or cap is None:
+                self._chk(call(None, None, 0))
+                if count_only:
+                    return m.value
+                cap = m.value
+            if dev:
+                import torch
+                ob = torch.empty(max(cap, 1), dtype=torch.int32, device=build_idx.device)
+                op = torch.empty(max(cap, 1), dtype=torch.int32, device=build_idx.device)
+            else:
+                ob = np.empty(max(cap, 1), np.uint32); op = np.empty(max(cap, 1), np.uint32)
+        st = call(ob, op, cap) if cap else call(None, None, 0)
+        if st == ERR_CAPACITY:
+            err = IvxError(st, f"need {m.value} pairs, cap {cap}")
+            err.needed = m.value
+            raise err
+        self._chk(st)
+        return ob[: m.value], op[: m.value]
 
     def bits_mark(self, idx, bits, n_bits):
         """OR bit idx[i] into `bits` (NULL_IDX skipped, anything else >= n_bits raises ERR_INVALID); -> bits"""

@@ -140,6 +140,36 @@ int brh_overlap_select(brh_session *s, brh_batch build, brh_columns bcols, const
                        struct ArrowArray *build_idx, struct ArrowSchema *build_idx_schema,
                        struct ArrowArray *score, struct ArrowSchema *score_schema);
 
+/* Overlap thresholds (ivx_where.h): the integer fields of ivx_overlap_where, with its pass rule and its refusals (a negative
+ * min_bases, a fraction above 1, a zero or too large denominator, either not 0 or 1).  On the adjusted coordinates of the two
+ * tables (strict_predicate: end - 1 on both sides): len = the closed overlap length, plen / blen = the probe / build row's.
+ * A pair passes iff len >= max(1, min_bases), len * probe_den >= plen * probe_num and len * build_den >= blen * build_num
+ * (a fraction with num = 0 is not asked; either = 1: one of two asked fractions suffices).  where = NULL, or one that asks
+ * nothing, is the function without _where.
+ *   brh_interval_join_where      every join type over the same filtered matches: Inner = the pairs that pass (ivx_pairs_where
+ *                                behind the fill); RightSemi / RightAnti = the probe rows with / without a passing pair;
+ *                                LeftSemi / LeftAnti = the build rows with / without one; Left / Right / Full = the passing
+ *                                pairs, then the rows without one.  nearest_algorithm != 0 with a threshold is refused.
+ *   brh_overlap_aggregate_where  the aggregates over the passing build rows of each probe row
+ *   brh_overlap_select_where     the best of the passing build rows of each probe row */
+typedef struct brh_overlap_where {
+    int64_t  min_bases;
+    uint32_t probe_num, probe_den;
+    uint32_t build_num, build_den;
+    uint32_t either;
+} brh_overlap_where;
+int brh_interval_join_where(brh_session *s, brh_batch build, brh_columns bcols, brh_batch probe, brh_columns pcols,
+                            int join_type, int strict_predicate, int nearest_algorithm, const brh_overlap_where *where,
+                            struct ArrowArray *build_idx, struct ArrowSchema *build_idx_schema,
+                            struct ArrowArray *probe_idx, struct ArrowSchema *probe_idx_schema);
+int brh_overlap_aggregate_where(brh_session *s, brh_batch build, brh_columns bcols, const char *value_column,
+                                brh_batch probe, brh_columns pcols, int strict_predicate, uint32_t ops, const brh_overlap_where *where,
+                                struct ArrowArray *out, struct ArrowSchema *out_schema);
+int brh_overlap_select_where(brh_session *s, brh_batch build, brh_columns bcols, const char *value_column /* nullable */,
+                             brh_batch probe, brh_columns pcols, int strict_predicate, int by, const brh_overlap_where *where,
+                             struct ArrowArray *build_idx, struct ArrowSchema *build_idx_schema,
+                             struct ArrowArray *score, struct ArrowSchema *score_schema);
+
 /* merge('table'[,min_dist]...): MergeProvider/MergeStream (R/src/merge.rs:84-112, :263-350).
  * Outputs contig Utf8, start Int64, end Int64, n_intervals Int64. */
 int brh_merge(brh_session *s, brh_batch table, brh_columns cols, int64_t min_dist, int filter_op,
