@@ -1709,23 +1709,15 @@ extern "C" ivx_status ivx_depth_profile_blocks(ivx_ctx *ctx, const ivx_index *p,
 // domain [pos_lo, key_hi[key]], or n windows of `width` positions of one key from first_pos on, cut at last_pos
 namespace {
 
-struct RegionSrc {
-    bool windows;
-    const u32 *qkey, *qstart, *qend; u32 pos_lo; const u32 *key_hi;         // the table
-    u32 key, first_pos, last_pos, width;                                    // the windows
-    u64 n; int skip_pos0;
-};
+using RegionSrc = DepthRegionSrc;         // (the table's columns as the caller gave them, until regions_stage)
 RegionSrc region_table(const u32 *qkey, const u32 *qstart, const u32 *qend, u64 n, u32 pos_lo, const u32 *key_hi, int skip_pos0)
 {
-    return RegionSrc{false, qkey, qstart, qend, pos_lo, key_hi, 0, 0, 0, 0, n, skip_pos0};
+    return RegionSrc{false, qkey, qstart, qend, pos_lo, key_hi, 0, 0, 0, 0, n, skip_pos0 != 0};
 }
 RegionSrc region_windows(u32 key, u32 first_pos, u32 last_pos, u32 width, u64 n, int skip_pos0)
 {
-    return RegionSrc{true, nullptr, nullptr, nullptr, 0, nullptr, key, first_pos, last_pos, width, n, skip_pos0};
+    return RegionSrc{true, nullptr, nullptr, nullptr, 0, nullptr, key, first_pos, last_pos, width, n, skip_pos0 != 0};
 }
-
-// the table's columns on the device (windows: none)
-struct RegionCols { const u32 *key = nullptr, *start = nullptr, *end = nullptr, *hi = nullptr; };
 
 // the checks of the source, after the statistic's own; then the call counts as made (the caller returns if it has no region)
 ivx_status regions_begin(Frame &f, const ivx_index *p, const RegionSrc &r)
@@ -1746,13 +1738,13 @@ ivx_status regions_begin(Frame &f, const ivx_index *p, const RegionSrc &r)
     return IVX_OK;
 }
 
-RegionCols regions_stage(Frame &f, const ivx_index *p, const RegionSrc &r)
+// the source as the device entries take it: the table's columns on the device
+RegionSrc regions_stage(Frame &f, const ivx_index *p, RegionSrc r)
 {
-    RegionCols c;
-    if (r.windows) return c;
-    c.key = f.in(r.qkey, r.n); c.start = f.in(r.qstart, r.n); c.end = f.in(r.qend, r.n);
-    c.hi = f.in_at(WS_IN_KEYLEN, r.key_hi, p->nkeys);
-    return c;
+    if (r.windows) return r;
+    r.qkey = f.in(r.qkey, r.n); r.qstart = f.in(r.qstart, r.n); r.qend = f.in(r.qend, r.n);
+    r.key_hi = f.in_at(WS_IN_KEYLEN, r.key_hi, p->nkeys);
+    return r;
 }
 
 // bases, coverage sum and bases at or above each threshold, per region
@@ -1768,12 +1760,9 @@ ivx_status depth_summary(ivx_ctx *ctx, const ivx_index *p, int mem, const Region
         return ctx->fail(IVX_ERR_INVALID, "depth profile: output pointer not aligned to its element size");
     IVX_TRY(regions_begin(f, p, r));
     if (r.n == 0) return IVX_OK;
-    const RegionCols c = regions_stage(f, p, r);
+    const RegionSrc d = regions_stage(f, p, r);
     i64 *ol = f.out(out_len, r.n), *os = f.out(out_sum, r.n), *og = f.out(out_ge, (u64)n_thr * r.n);
-    IVX_TRY(f.run([&] {
-        return r.windows ? ivx_depth_windows_device(ctx, p->dp, r.key, r.first_pos, r.last_pos, r.width, r.n, r.skip_pos0 != 0, thresholds, n_thr, ol, os, og)
-                         : ivx_depth_regions_device(ctx, p->dp, p->nkeys, c.key, c.start, c.end, r.n, r.pos_lo, c.hi, r.skip_pos0 != 0, thresholds, n_thr, ol, os, og);
-    }));
+    IVX_TRY(f.run([&] { return ivx_depth_region_sums_device(ctx, p->dp, p->nkeys, d, thresholds, n_thr, ol, os, og); }));
     f.rows_out(r.n);
     f.back_all();
     return f.finish();
@@ -1795,13 +1784,10 @@ ivx_status depth_ranks(ivx_ctx *ctx, const ivx_index *p, int mem, const RegionSr
         return ctx->fail(IVX_ERR_INVALID, "depth profile: output pointer not aligned to its element size");
     IVX_TRY(regions_begin(f, p, r));
     if (r.n == 0) return IVX_OK;
-    const RegionCols c = regions_stage(f, p, r);
+    const RegionSrc d = regions_stage(f, p, r);
     i64 *ol = f.out(out_len, r.n);
     i32 *omn = f.out(out_min, r.n), *omx = f.out(out_max, r.n), *oq = f.out(out_q, (u64)n_q * r.n);
-    IVX_TRY(f.run([&] {
-        return r.windows ? ivx_depth_window_ranks_device(ctx, p->dp, r.key, r.first_pos, r.last_pos, r.width, r.n, r.skip_pos0 != 0, q_num, n_q, q_den, ol, omn, omx, oq)
-                         : ivx_depth_region_ranks_device(ctx, p->dp, p->nkeys, c.key, c.start, c.end, r.n, r.pos_lo, c.hi, r.skip_pos0 != 0, q_num, n_q, q_den, ol, omn, omx, oq);
-    }));
+    IVX_TRY(f.run([&] { return ivx_depth_region_ranks_device(ctx, p->dp, p->nkeys, d, q_num, n_q, q_den, ol, omn, omx, oq); }));
     f.rows_out(r.n);
     f.back_all();
     return f.finish();

@@ -5,8 +5,9 @@
 //   profile   from the front half of depth() (ivx_depth.hip: the sorted events and, per (key, position) group, the key's
 //             running sum c and the group's sum g): a group with g != 0 is a step (key, position, c).  One counting scan
 //             sizes the three columns, the same scan again writes them; a search per key gives the key's first step.
-//   expand    one workgroup makes one tile of DEPTH_EXPAND_TILE consecutive outputs.  A wavefront-wide 64-ary search inside
-//             the key's slice finds the tile's first step (4 dependent loads for 16 M steps, not 24); the step before it,
+//   expand    one workgroup makes one tile of DEPTH_EXPAND_TILE consecutive outputs.  The wavefront-wide 64-ary search inside
+//             the key's slice (ivx_depth_regions.hpp, which the region statistics share, with the key's c0) finds the
+//             tile's first step (4 dependent loads for 16 M steps, not 24); the step before it,
 //             if the key has one, is the carry-in.  A tile without a step -- most of a genome -- is a constant fill and
 //             touches no LDS.  Otherwise the tile's steps (at most one per slot: positions are distinct) are scattered to an
 //             LDS image with a bit per set slot, every thread takes the last set slot of its 8 slots, a scan over the
@@ -16,7 +17,7 @@
 //             coverage column (and, independently, b * TILE/4 ... of the position column: positions are arithmetic and
 //             need no step).  Every thread then owns whole aligned lines and stores each with one 16-byte store; only the
 //             window's first and last line, when the caller's pointer or length cuts them, leave as scalar stores.
-#include "ivx_device.hpp"
+#include "ivx_depth_regions.hpp"
 #include "ivx_scan.hpp"
 
 namespace {
@@ -101,22 +102,9 @@ __global__ __launch_bounds__(XT) void k_depth_expand(DepthProfileView dp, u32 ke
     const u64 lo_pos = P0 < 0 ? 0ull : (u64)P0;
     const u64 hi_pos = (u64)(P0 + T);                       // (> first_pos: the tile holds an element of the window)
 
-    // the first step of the key at or after lo_pos: answer in [lo, lo + len], 64 probes a round.  (32-bit throughout: a
-    // profile holds fewer than 2^32 - 256 steps.)
-    u32 lo = klo, len = khi - klo;
-    while (len) {
-        const u32 stride = (len + 63u) >> 6;
-        const u32 off = (l + 1u) * stride - 1u;
-        const bool less = off < len && (u64)dp.pos[lo + off] < lo_pos;
-        const u32 cnt = (u32)__popcll(__ballot(less));      // the probes before the answer: a prefix of the lanes
-        const u32 skip = min(cnt * stride, len);            // steps known to lie before the answer
-        lo += skip;
-        len = min(len - skip, stride - 1u);                 // the first probe that is not before it bounds the answer
-    }
-    const u32 a = lo;
+    const u32 a = wave_first_at_or_after(dp.pos, klo, khi - klo, lo_pos, l);    // the first step of the key at or after lo_pos
     const u32 cin = a > klo ? (u32)dp.cov[a - 1] : 0u;      // the step before it belongs to the same key, or there is no carry
-    u32 c0 = 0u;
-    if (skip_pos0 && klo < khi && dp.pos[klo] == 0u) c0 = (u32)dp.cov[klo];
+    const u32 c0 = klo < khi ? key_c0(dp, klo, skip_pos0) : 0u;     // (a key without steps has no first step to read)
     const bool busy = a < khi && (u64)dp.pos[a] < hi_pos;
 
     u32 o[8];

@@ -3,15 +3,15 @@
 // MIN_ / MEDIAN_TARGET_COVERAGE, mosdepth --use-median; include/ivx.h ivx_depth_profile_quantiles / _window_quantiles).
 //
 //   profile   a sorted step list.  A region's per-base values are a list of SEGMENTS (value, length): the zero stretch before
-//             the key's first step if it has length, then the steps s..b that the two wavefront searches of the sums find
-//             (ivx_depth_regions.hpp), the first and the last one clipped to the region.  Every segment has length >= 1.
-//   tiles     one workgroup per tile of DEPTH_RANK_TILE consecutive steps reduces (min, max) of v over its steps that have a
-//             successor with the same key (the rule and the c0 of the sums' tile pass); a tile without one gets the neutral
-//             pair.  Over the tiles a sparse table: level l, entry t = the pair of tiles t .. t + 2^l - 1, levels up to
-//             log2(tiles - 2), several levels a launch.  8 bytes a tile and level.
-//   query     one wavefront per region: the searches, then (min, max) over s's tile tail, b's tile head and two table
-//             look-ups for the tiles strictly between (every step there has a same-key successor, b at the latest), the zero
-//             stretch's 0, a wavefront reduction.  Two searches and at most two tiles of steps, whatever the region's length.
+//             the key's first step if it has length, then the steps s..b of the region's span, the first and the last one
+//             clipped to the region (ivx_depth_regions.hpp: the segment rule).  Every segment has length >= 1.
+//   tiles     one workgroup per tile of DEPTH_RANK_TILE consecutive steps reduces (min, max) of v over the steps the shared
+//             tile walk passes (ivx_depth_regions.hpp tile_steps); a tile without one gets the neutral pair.  Over the tiles
+//             a sparse table: level l, entry t = the pair of tiles t .. t + 2^l - 1, levels up to log2(tiles - 2), several
+//             levels a launch.  8 bytes a tile and level.
+//   query     one wavefront per region: the span front (ivx_depth_regions.hpp describes it), then (min, max) over s's tile tail,
+//             b's tile head and two table look-ups for the tiles strictly between, the zero stretch's 0, a wavefront
+//             reduction.  Two searches and at most two tiles of steps, whatever the region's length.
 //             Quantiles of at most DEPTH_RANK_SEGS = 64 segments: one segment per lane; in as many broadcast rounds as there
 //             are segments every lane adds up `below`, the bases of the segments with a smaller value, and `atmost`, the
 //             same for <=; the value of rank r sits in any lane with below <= r < atmost.  Registers only.
@@ -22,7 +22,6 @@
 //             adds the clipped lengths to 256 64-bit LDS bins (a bin can reach 2^32) per DISTINCT prefix the quantiles have
 //             reached so far, a workgroup scan finds each quantile's bin.  A coverage span below 256 (the usual case) is one
 //             walk for all quantiles.  Cost: linear in the region's steps, times the passes.
-//             The region index is made wave-uniform for the compiler as in the sums' query.
 #include "ivx_depth_regions.hpp"
 
 namespace {
@@ -30,15 +29,11 @@ namespace {
 constexpr int DEPTH_RANK_TILE = 1024;           // steps per (min, max) tile: the sums' DEPTH_REGION_TILE
 constexpr int DEPTH_RANK_SEGS = 64;             // segments the query wavefront ranks in registers: one per lane
 constexpr int DEPTH_RANK_SELECT_GRID = 512;     // workgroups of the select kernel: two per compute unit
-constexpr int RT = 256;                         // threads of every kernel
-constexpr int RW = RT / IVX_WAVE;               // regions per workgroup of the query: one per wavefront
-constexpr int RS = DEPTH_RANK_TILE / RT;        // steps per thread of the tile pass
 constexpr int MAXQ = 8;                         // IVX_DEPTH_MAX_QUANTILES
 constexpr u32 TABLE_LEVELS = 4;                 // table levels one launch makes: up to 16 reads an entry
-static_assert(DEPTH_RANK_TILE % RT == 0 && RT % IVX_WAVE == 0 && DEPTH_RANK_SEGS == IVX_WAVE && RT == 256, "whole steps per thread; a lane per segment; a thread per bin");
+static_assert(DEPTH_RANK_SEGS == IVX_WAVE && RT == 256, "a lane per segment; a thread per bin");
 static_assert(MAXQ == IVX_DEPTH_MAX_QUANTILES, "the header's limit");
 
-constexpr u64 QUERY_CHUNK = (u64)RW << 23;      // regions per launch: the grid times the workgroup stays below 2^32 threads
 constexpr i32 I32_LO = (i32)0x80000000, I32_HI = 0x7FFFFFFF;
 
 struct Qn { u32 num[MAXQ]; u32 n, den; };
@@ -64,28 +59,17 @@ __device__ __forceinline__ u64 lane_u64(u64 v, u32 lane)       // lane: wave-uni
 }
 
 // ------------------------------------------------------------------------------------------------ tiles and their table
-// tab[tile] = (min, max) of v over the tile's steps whose successor has the same key.  only_key != IVX_NULL_IDX (the windows
-// call): a tile without a step of the key is never part of a region, it gets the neutral pair and loads nothing.
+// tab[tile] = (min, max) of v over the steps tile_steps passes; the neutral pair for a skipped tile
 __global__ __launch_bounds__(RT) void k_rank_tiles(DepthProfileView dp, int skip_pos0, u32 only_key, int2 *__restrict__ tab)
 {
     __shared__ int2 part[RW];
     const u32 t = threadIdx.x;
-    const u64 base = (u64)blockIdx.x * DEPTH_RANK_TILE;
-    if (only_key != IVX_NULL_IDX && (base >= dp.koff[only_key + 1] || base + DEPTH_RANK_TILE <= dp.koff[only_key])) {
-        if (t == 0) tab[blockIdx.x] = make_int2(I32_HI, I32_LO);   // (the same for the whole workgroup)
+    if (tile_skipped<DEPTH_RANK_TILE>(dp, only_key)) {
+        if (t == 0) tab[blockIdx.x] = make_int2(I32_HI, I32_LO);
         return;
     }
     i32 mn = I32_HI, mx = I32_LO;
-#pragma unroll
-    for (int j = 0; j < RS; j++) {
-        const u64 i = base + t + (u64)RT * j;
-        if (i + 1 >= dp.steps) continue;
-        const u32 k = dp.key[i];
-        if (dp.key[i + 1] != k) continue;
-        const u32 c0 = skip_pos0 ? key_c0(dp, dp.koff[k], 1) : 0u;
-        const i32 v = (i32)((u32)dp.cov[i] - c0);
-        mn = min(mn, v); mx = max(mx, v);
-    }
+    tile_steps<DEPTH_RANK_TILE>(dp, skip_pos0, [&](i32 v, u64) { mn = min(mn, v); mx = max(mx, v); });
     mn = wave_min(mn); mx = wave_max(mx);
     if (lane_id() == 0) part[t / IVX_WAVE] = make_int2(mn, mx);
     __syncthreads();
@@ -129,7 +113,7 @@ __global__ __launch_bounds__(RT) void k_rank_query(DepthProfileView dp, In in, u
 {
     constexpr u32 T = DEPTH_RANK_TILE;
     const u32 l = lane_id();
-    const u64 i = i0 + (u64)blockIdx.x * RW + (u32)__builtin_amdgcn_readfirstlane((int)(threadIdx.x / IVX_WAVE));
+    const u64 i = query_region(i0);
     if (i >= n) return;
     u64 len = 0;
     i32 mn = 0, mx = 0, qv[MAXQ];
@@ -170,12 +154,8 @@ __global__ __launch_bounds__(RT) void k_rank_query(DepthProfileView dp, In in, u
                     i32 v = 0;
                     u64 ln = 0;                             // (a lane without a segment: no bases, and it never answers)
                     if (l < ns && !(zs && l == 0)) {
-                        const u32 j = s + l - zs;
-                        const u32 p = dp.pos[j];
-                        const u64 start = p > lo ? p : lo;
-                        const u64 end = j < b ? (u64)dp.pos[j + 1] : (u64)hi + 1u;
-                        ln = end - start;
-                        v = (i32)((u32)dp.cov[j] - c0);
+                        const StepSegment g = span_segment(dp, SpanClip{b, c0, lo, hi}, s + l - zs);
+                        v = g.v; ln = g.len;
                     } else if (l == 0 && zs) ln = zero;
                     u64 below = 0, atmost = 0;
                     for (u32 r = 0; r < ns; r++) {
@@ -230,6 +210,7 @@ __global__ __launch_bounds__(RT) void k_rank_select(DepthProfileView dp, In in, 
         const u32 p0 = dp.pos[klo];
         const u64 zero = (R.s == klo && lo < p0) ? (u64)(p0 - lo) : 0ull;
         const u64 len = (u64)hi - lo + 1u;
+        const SpanClip sp{R.b, c0, lo, hi};
         const u32 span = (u32)R.mx - (u32)R.mn;
         const int ndig = span < 256u ? 1 : span < 65536u ? 2 : span < (1u << 24) ? 3 : 4;
         if (t < q.n) { prefix[t] = 0u; rem[t] = (len - 1u) * q.num[t] / q.den; }
@@ -248,10 +229,8 @@ __global__ __launch_bounds__(RT) void k_rank_select(DepthProfileView dp, In in, 
             };
             if (t == 0 && zero) add(0u - (u32)R.mn, zero);
             for (u64 j = (u64)R.s + t; j <= R.b; j += RT) {
-                const u32 p = dp.pos[j];
-                const u64 start = p > lo ? p : lo;
-                const u64 end = j < R.b ? (u64)dp.pos[j + 1] : (u64)hi + 1u;
-                add((u32)dp.cov[j] - c0 - (u32)R.mn, end - start);
+                const StepSegment g = span_segment(dp, sp, j);
+                add((u32)g.v - (u32)R.mn, g.len);
             }
             __syncthreads();
             for (u32 e = 0; e < q.n; e++) {
@@ -291,59 +270,37 @@ ivx_status rank_table(ivx_ctx *ctx, const DepthProfileView &dp, int skip_pos0, u
     return IVX_OK;
 }
 
-// Scratch: rank_table's, and WS_T1 (the long-region list: 24 bytes a region) when quantiles are asked for.
-template <typename In>
-ivx_status rank_query(ivx_ctx *ctx, const DepthProfileView &dp, const In &in, u32 only_key, u64 n, int skip_pos0, const Qn &q,
-                      i64 *out_len, i32 *out_min, i32 *out_max, i32 *out_q)
-{
-    const int2 *tab; u32 ntiles;
-    IVX_TRY(rank_table(ctx, dp, skip_pos0, only_key, &tab, &ntiles));
-    const bool ranks = q.n && out_q;
-    LongRegion *list = nullptr;
-    u64 *counter = ctx->dword(SC_RANK_LONG);
-    if (ranks) {
-        IVX_TRY(ctx->get_scratch(WS_T1, (size_t)n * sizeof(LongRegion), (void **)&list));
-        IVX_HIP(ctx, hipMemsetAsync(counter, 0, sizeof(u64), ctx->stream));
-    }
-    for (u64 i0 = 0; i0 < n; i0 += QUERY_CHUNK) {
-        const u64 m = n - i0 < QUERY_CHUNK ? n - i0 : QUERY_CHUNK;
-        hipLaunchKernelGGL((k_rank_query<In>), dim3((u32)((m + RW - 1) / RW)), dim3(RT), 0, ctx->stream, dp, in, i0, n, skip_pos0, q,
-                           tab, ntiles, out_len, out_min, out_max, out_q, list, counter);
-    }
-    if (ranks)
-        hipLaunchKernelGGL((k_rank_select<In>), dim3(DEPTH_RANK_SELECT_GRID), dim3(RT), 0, ctx->stream, dp, in, n, skip_pos0, q, list, counter, out_q);
-    IVX_HIP(ctx, hipGetLastError());
-    return IVX_OK;
-}
+}  // namespace
 
-Qn make_qn(const u32 *q_num, u32 n_q, u32 q_den)
+// Scratch: rank_table's, and WS_T1 (the long-region list: 24 bytes a region) when quantiles are asked for.
+ivx_status ivx_depth_region_ranks_device(ivx_ctx *ctx, const DepthProfileView &dp, u32 nkeys, const DepthRegionSrc &src,
+                                         const u32 *q_num, u32 n_q, u32 q_den, i64 *out_len, i32 *out_min, i32 *out_max, i32 *out_q)
 {
+    const u64 n = src.n;
+    if (n == 0) return IVX_OK;
+    if (!src.windows) IVX_TRY(ivx_depth_regions_check_keys(ctx, src.qkey, n, nkeys));
+    if (!out_len && !out_min && !out_max && !(out_q && n_q)) return IVX_OK;
     Qn q{};
     q.n = n_q; q.den = q_den;
     for (u32 e = 0; e < n_q; e++) q.num[e] = q_num[e];
-    return q;
-}
-
-}  // namespace
-
-// q_num: host memory, n_q <= 8, every q_num <= q_den <= 65536; every other pointer on the device.  The key check of the sums.
-ivx_status ivx_depth_region_ranks_device(ivx_ctx *ctx, const DepthProfileView &dp, u32 nkeys, const u32 *qkey, const u32 *qs, const u32 *qe, u64 n,
-                                         u32 pos_lo, const u32 *key_hi, int skip_pos0, const u32 *q_num, u32 n_q, u32 q_den,
-                                         i64 *out_len, i32 *out_min, i32 *out_max, i32 *out_q)
-{
-    if (n == 0) return IVX_OK;
-    IVX_TRY(ivx_depth_regions_check_keys(ctx, qkey, n, nkeys));
-    if (!out_len && !out_min && !out_max && !(out_q && n_q)) return IVX_OK;
-    return rank_query(ctx, dp, RegionsIn{qkey, qs, qe, key_hi, pos_lo}, qkey ? IVX_NULL_IDX : 0u, n, skip_pos0, make_qn(q_num, n_q, q_den),
-                      out_len, out_min, out_max, out_q);
-}
-
-// window i = [first_pos + i * width, + width - 1], cut at last_pos; key < nkeys and first_pos + (n - 1) * width < 2^32: the caller's checks
-ivx_status ivx_depth_window_ranks_device(ivx_ctx *ctx, const DepthProfileView &dp, u32 key, u32 first_pos, u32 last_pos, u32 width, u64 n,
-                                         int skip_pos0, const u32 *q_num, u32 n_q, u32 q_den,
-                                         i64 *out_len, i32 *out_min, i32 *out_max, i32 *out_q)
-{
-    if (n == 0 || (!out_len && !out_min && !out_max && !(out_q && n_q))) return IVX_OK;
-    return rank_query(ctx, dp, WindowsIn{key, first_pos, last_pos, width}, key, n, skip_pos0, make_qn(q_num, n_q, q_den),
-                      out_len, out_min, out_max, out_q);
+    return with_region_in(src, [&](const auto &in, u32 only_key) -> ivx_status {
+        using In = std::decay_t<decltype(in)>;
+        const int2 *tab; u32 ntiles;
+        IVX_TRY(rank_table(ctx, dp, src.skip_pos0, only_key, &tab, &ntiles));
+        const bool ranks = q.n && out_q;
+        LongRegion *list = nullptr;
+        u64 *counter = ctx->dword(SC_RANK_LONG);
+        if (ranks) {
+            IVX_TRY(ctx->get_scratch(WS_T1, (size_t)n * sizeof(LongRegion), (void **)&list));
+            IVX_HIP(ctx, hipMemsetAsync(counter, 0, sizeof(u64), ctx->stream));
+        }
+        query_chunks(n, [&](u64 i0, dim3 grid) {
+            hipLaunchKernelGGL((k_rank_query<In>), grid, dim3(RT), 0, ctx->stream, dp, in, i0, n, src.skip_pos0, q,
+                               tab, ntiles, out_len, out_min, out_max, out_q, list, counter);
+        });
+        if (ranks)
+            hipLaunchKernelGGL((k_rank_select<In>), dim3(DEPTH_RANK_SELECT_GRID), dim3(RT), 0, ctx->stream, dp, in, n, src.skip_pos0, q, list, counter, out_q);
+        IVX_HIP(ctx, hipGetLastError());
+        return IVX_OK;
+    });
 }

@@ -454,22 +454,22 @@ ivx_status ivx_depth_expand_device(ivx_ctx *ctx, const DepthProfileView &dp, u32
 // ivx_depth_merge.hip: ix (from ivx_depth_profile_begin, nkeys = the larger of the two) = a + b; the coverage blocks of a profile
 ivx_status ivx_depth_profile_merge_device(ivx_ctx *ctx, const DepthProfileView &a, u32 nka, const DepthProfileView &b, u32 nkb, ivx_index *ix);
 ivx_status ivx_depth_profile_blocks_device(ivx_ctx *ctx, const DepthProfileView &dp, u32 *ok, u32 *os, u32 *oe, i32 *oc, u64 cap, u64 *n_out);
-// ivx_depth_regions.hip: bases, coverage sum and bases at or above each threshold per region / per fixed-width window of a
-// profile (thresholds: host memory; out_ge threshold-major [n_thr * n]; any output may be null)
-ivx_status ivx_depth_regions_device(ivx_ctx *ctx, const DepthProfileView &dp, u32 nkeys, const u32 *qkey, const u32 *qs, const u32 *qe, u64 n,
-                                    u32 pos_lo, const u32 *key_hi, int skip_pos0, const i32 *thresholds, u32 n_thr,
-                                    i64 *out_len, i64 *out_sum, i64 *out_ge);
-ivx_status ivx_depth_windows_device(ivx_ctx *ctx, const DepthProfileView &dp, u32 key, u32 first_pos, u32 last_pos, u32 width, u64 n,
-                                    int skip_pos0, const i32 *thresholds, u32 n_thr, i64 *out_len, i64 *out_sum, i64 *out_ge);
-ivx_status ivx_depth_regions_check_keys(ivx_ctx *ctx, const u32 *qkey, u64 n, u32 nkeys);    // a key id >= nkeys other than the skip mark: IVX_ERR_INVALID (reads one word back)
-// ivx_depth_rank.hip: bases, min, max and up to 8 lower quantiles of the per-base coverage per region / per window (q_num:
-// host memory, rank = floor((bases - 1) * q_num / q_den); out_q quantile-major [n_q * n]; any output may be null)
-ivx_status ivx_depth_region_ranks_device(ivx_ctx *ctx, const DepthProfileView &dp, u32 nkeys, const u32 *qkey, const u32 *qs, const u32 *qe, u64 n,
-                                         u32 pos_lo, const u32 *key_hi, int skip_pos0, const u32 *q_num, u32 n_q, u32 q_den,
-                                         i64 *out_len, i32 *out_min, i32 *out_max, i32 *out_q);
-ivx_status ivx_depth_window_ranks_device(ivx_ctx *ctx, const DepthProfileView &dp, u32 key, u32 first_pos, u32 last_pos, u32 width, u64 n,
-                                         int skip_pos0, const u32 *q_num, u32 n_q, u32 q_den,
-                                         i64 *out_len, i32 *out_min, i32 *out_max, i32 *out_q);
+// The n regions of a region statistic: rows (key, start, end) of a table (device columns; qkey null: key 0; IVX_NULL_IDX: the skip
+// mark), clipped to [pos_lo, key_hi[key]] (key_hi nullable), or windows of `width` positions of one key from first_pos on, cut
+// at last_pos (key < nkeys, first_pos + (n - 1) * width < 2^32: the caller's checks).  with_region_in makes the kernel's form of it.
+struct DepthRegionSrc {
+    bool windows; const u32 *qkey, *qstart, *qend; u32 pos_lo; const u32 *key_hi;       // the table
+    u32 key, first_pos, last_pos, width; u64 n; int skip_pos0;                          // the windows; both
+};
+// ivx_depth_regions.hip: bases, coverage sum and bases >= each threshold per region (thresholds: host memory; out_ge threshold-
+// major [n_thr * n]; any output may be null).  A table's key id >= nkeys other than the skip mark: IVX_ERR_INVALID (one word
+// read back), before anything is indexed with it and even when no output is wanted; nothing is written then.
+ivx_status ivx_depth_region_sums_device(ivx_ctx *ctx, const DepthProfileView &dp, u32 nkeys, const DepthRegionSrc &src,
+                                        const i32 *thresholds, u32 n_thr, i64 *out_len, i64 *out_sum, i64 *out_ge);
+// ivx_depth_rank.hip: bases, min, max and up to 8 lower quantiles of the per-base coverage per region (q_num: host memory,
+// rank = floor((bases - 1) * q_num / q_den); out_q quantile-major [n_q * n]; any output may be null).  The key check of the sums.
+ivx_status ivx_depth_region_ranks_device(ivx_ctx *ctx, const DepthProfileView &dp, u32 nkeys, const DepthRegionSrc &src,
+                                         const u32 *q_num, u32 n_q, u32 q_den, i64 *out_len, i32 *out_min, i32 *out_max, i32 *out_q);
 // ivx_depth_classes.hip: the maximal runs of one coverage class per key (cuts: host memory, checked by the caller; any output
 // may be null; synchronises for the count), and the per-key histogram of the per-base coverage (out: [nkeys * n_bins])
 ivx_status ivx_depth_quantize_device(ivx_ctx *ctx, const DepthProfileView &dp, u32 nkeys, u32 pos_lo, const u32 *key_hi, int skip_pos0, int seen_only,

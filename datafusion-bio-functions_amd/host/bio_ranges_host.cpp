@@ -10,7 +10,6 @@
 #include <cstdlib>
 #include <cstring>
 #include <deque>
-#include <functional>
 #include <memory>
 #include <string>
 #include <string_view>
@@ -1033,26 +1032,56 @@ struct DepthInputs {
     bool text = false; int large = 0;
     const void *toff = nullptr; const uint8_t *ctext = nullptr;
     int load(brh_session *s, brh_batch reads, brh_batch prior, brh_batch lengths);
-    // ivx_depth / ivx_depth_text and ivx_depth_profile_build / ..._text on the read columns, whichever form the cigar column has
-    ivx_status depth(ivx_ctx *ctx, const uint32_t *skey_, const uint32_t *ss_, const uint32_t *se_, const int32_t *sw_, uint64_t n_seg_,
-                     uint32_t nk_, const uint32_t *key_len_, uint32_t filter_flag, uint32_t min_mapq,
-                     uint32_t *ok, uint32_t *os, uint32_t *oe, int32_t *oc, uint64_t cap, uint64_t *m) const
+    // what goes with the read columns: the prior segments and the keys.  own(): this call's; of_stream(): a push stream's keys and
+    // length table, no prior segments (its batches carry the stream's ids)
+    struct Rest { const uint32_t *skey, *ss, *se; const int32_t *sw; uint64_t n_seg; uint32_t nk; const uint32_t *key_len; };
+    Rest own() const
     {
-        if (text)
-            return ivx_depth_text(ctx, IVX_MEM_HOST, rkey.data(), rpos, rflags, rmapq, large, toff, ctext, n_reads, skey_, ss_, se_, sw_, n_seg_,
-                                  nk_, key_len_, filter_flag, min_mapq, ok, os, oe, oc, cap, m);
-        return ivx_depth(ctx, IVX_MEM_HOST, rkey.data(), rpos, rflags, rmapq, coff, cops, n_reads, skey_, ss_, se_, sw_, n_seg_,
-                         nk_, key_len_, filter_flag, min_mapq, ok, os, oe, oc, cap, m);
+        return Rest{has_prior ? skey.data() : nullptr, ss.data(), se.data(), has_prior ? sw.data() : nullptr, n_seg, nk, has_len ? key_len.data() : nullptr};
     }
-    ivx_status profile(ivx_ctx *ctx, const uint32_t *skey_, const uint32_t *ss_, const uint32_t *se_, const int32_t *sw_, uint64_t n_seg_,
-                       uint32_t nk_, const uint32_t *key_len_, uint32_t filter_flag, uint32_t min_mapq, ivx_index **out) const
+    static Rest of_stream(uint32_t nk, const uint32_t *key_len) { return Rest{nullptr, nullptr, nullptr, nullptr, 0, nk, key_len}; }
+    // ivx_depth / ivx_depth_text and ivx_depth_profile_build / ..._text on the read columns, whichever form the cigar column has
+    ivx_status depth(ivx_ctx *ctx, uint32_t filter_flag, uint32_t min_mapq, uint32_t *ok, uint32_t *os, uint32_t *oe, int32_t *oc, uint64_t cap, uint64_t *m) const
+    {
+        const Rest r = own();
+        if (text)
+            return ivx_depth_text(ctx, IVX_MEM_HOST, rkey.data(), rpos, rflags, rmapq, large, toff, ctext, n_reads, r.skey, r.ss, r.se, r.sw, r.n_seg,
+                                  r.nk, r.key_len, filter_flag, min_mapq, ok, os, oe, oc, cap, m);
+        return ivx_depth(ctx, IVX_MEM_HOST, rkey.data(), rpos, rflags, rmapq, coff, cops, n_reads, r.skey, r.ss, r.se, r.sw, r.n_seg,
+                         r.nk, r.key_len, filter_flag, min_mapq, ok, os, oe, oc, cap, m);
+    }
+    ivx_status profile(ivx_ctx *ctx, uint32_t filter_flag, uint32_t min_mapq, ivx_index **out) const { return profile(ctx, own(), filter_flag, min_mapq, out); }
+    ivx_status profile(ivx_ctx *ctx, const Rest &r, uint32_t filter_flag, uint32_t min_mapq, ivx_index **out) const
     {
         if (text)
             return ivx_depth_profile_build_text(ctx, IVX_MEM_HOST, rkey.data(), rpos, rflags, rmapq, large, toff, ctext, n_reads,
-                                                skey_, ss_, se_, sw_, n_seg_, nk_, key_len_, filter_flag, min_mapq, out);
+                                                r.skey, r.ss, r.se, r.sw, r.n_seg, r.nk, r.key_len, filter_flag, min_mapq, out);
         return ivx_depth_profile_build(ctx, IVX_MEM_HOST, rkey.data(), rpos, rflags, rmapq, coff, cops, n_reads,
-                                       skey_, ss_, se_, sw_, n_seg_, nk_, key_len_, filter_flag, min_mapq, out);
+                                       r.skey, r.ss, r.se, r.sw, r.n_seg, r.nk, r.key_len, filter_flag, min_mapq, out);
     }
+};
+
+// Which profile a statistic reads, and what it needs to know about its keys: the same for a one-shot call (the profile of its
+// inputs, owned here) and for a push stream (everything pushed so far, merged; the stream keeps it).
+struct ProfileSource {
+    const ivx_index *profile = nullptr;
+    uint32_t nk = 1, known = 0;                         // keys of the profile; ids below `known` name a contig (an empty dictionary: none)
+    const std::vector<std::string> *names = nullptr;    // key id -> contig
+    const std::vector<uint32_t> *key_len = nullptr;     // null: no length table
+    bool by_name = false;                               // rows go out in byte order of the names, not in id order
+    DepthInputs in; IndexGuard g;                       // one-shot
+    const brh_depth_push *dp = nullptr;                 // push
+    int open(brh_session *s, brh_batch reads, brh_batch prior, brh_batch lengths, uint32_t filter_flag, uint32_t min_mapq)
+    {
+        if (in.load(s, reads, prior, lengths)) return 1;
+        const ivx_status st = in.profile(s->ctx, filter_flag, min_mapq, &g.ix);
+        if (st != IVX_OK) return fail_ivx(s, st);
+        profile = g.ix; nk = in.nk; known = (uint32_t)in.dict.names.size();
+        names = &in.dict.names; key_len = in.has_len ? &in.key_len : nullptr;
+        return 0;
+    }
+    int open(brh_depth_push *dp);                       // depth_push_check + depth_push_merge_all: the merged profile stays the stack's only entry
+    uint32_t id_of(std::string_view name) const;        // IVX_NULL_IDX: a contig the source does not know
 };
 
 int DepthInputs::load(brh_session *s, brh_batch reads, brh_batch prior, brh_batch lengths)
@@ -1141,29 +1170,19 @@ extern "C" int brh_depth(brh_session *s, brh_batch reads, brh_batch prior, brh_b
     if (!s) return 1;
     DepthInputs in;
     if (in.load(s, reads, prior, lengths)) return 1;
-    const bool has_prior = in.has_prior, has_len = in.has_len;
-    const uint64_t n_seg = in.n_seg;
-    const uint32_t nk = in.nk;
-    const NameDict &dict = in.dict;
-    const std::vector<uint32_t> &skey = in.skey, &ss = in.ss, &se = in.se, &key_len = in.key_len;
-    const std::vector<int32_t> &sw = in.sw;
     // ---- sizing call, then the fill call
-    auto call = [&](uint32_t *ok, uint32_t *os, uint32_t *oe, int32_t *oc, uint64_t cap, uint64_t *m) {
-        return in.depth(s->ctx, has_prior ? skey.data() : nullptr, ss.data(), se.data(), has_prior ? sw.data() : nullptr, n_seg,
-                        nk, has_len ? key_len.data() : nullptr, filter_flag, min_mapq, ok, os, oe, oc, cap, m);
-    };
     uint64_t m = 0, m2 = 0;
-    ivx_status st = call(nullptr, nullptr, nullptr, nullptr, 0, &m);
+    ivx_status st = in.depth(s->ctx, filter_flag, min_mapq, nullptr, nullptr, nullptr, nullptr, 0, &m);
     if (st != IVX_OK) return fail_ivx(s, st);
     std::vector<uint32_t> ok(m ? m : 1), os(m ? m : 1), oe(m ? m : 1); std::vector<int32_t> oc(m ? m : 1);
     if (m) {
-        st = call(ok.data(), os.data(), oe.data(), oc.data(), m, &m2);
+        st = in.depth(s->ctx, filter_flag, min_mapq, ok.data(), os.data(), oe.data(), oc.data(), m, &m2);
         if (st != IVX_OK) return fail_ivx(s, st);
     }
     // ---- schema.rs:28-41: contig Utf8, pos_start / pos_end Int32 (`as i32`), coverage Int16 (`as i16`)
     std::vector<int32_t> o32s(m2 ? m2 : 1), o32e(m2 ? m2 : 1); std::vector<int16_t> o16(m2 ? m2 : 1);
     for (uint64_t i = 0; i < m2; i++) { o32s[i] = (int32_t)os[i]; o32e[i] = (int32_t)oe[i]; o16[i] = (int16_t)oc[i]; }
-    make_utf8(contig, dict.names, ok.data(), (int64_t)m2); make_schema(contig_schema, "u", "contig", true);
+    make_utf8(contig, in.dict.names, ok.data(), (int64_t)m2); make_schema(contig_schema, "u", "contig", true);
     make_primitive<int32_t>(pos_start, o32s.data(), (int64_t)m2, nullptr); make_schema(pos_start_schema, "i", "pos_start", false);
     make_primitive<int32_t>(pos_end, o32e.data(), (int64_t)m2, nullptr); make_schema(pos_end_schema, "i", "pos_end", false);
     make_primitive<int16_t>(coverage, o16.data(), (int64_t)m2, nullptr); make_schema(coverage_schema, "s", "coverage", false);
@@ -1191,19 +1210,17 @@ extern "C" int brh_depth_per_base_open(brh_session *s, brh_batch reads, brh_batc
     if (!lengths.array)                     // physical_exec.rs:299-303
         return fail(s, "per_base mode requires dense accumulation (BAM header with contig lengths). "
                        "Sparse fallback (e.g. MemTable) is not supported for per_base output.");
-    DepthInputs in;
-    if (in.load(s, reads, prior, lengths)) return 1;
+    ProfileSource src;
+    if (src.open(s, reads, prior, lengths, filter_flag, min_mapq)) return 1;
     std::unique_ptr<brh_depth_stream> ds(new brh_depth_stream());
     ds->s = s; ds->zero_based = zero_based != 0;
-    ivx_status st = in.profile(s->ctx, in.has_prior ? in.skey.data() : nullptr, in.ss.data(), in.se.data(), in.has_prior ? in.sw.data() : nullptr,
-                               in.n_seg, in.nk, in.key_len.data(), filter_flag, min_mapq, &ds->profile);
-    if (st != IVX_OK) return fail_ivx(s, st);
-    ds->names = in.dict.names; ds->key_len = in.key_len;
-    ds->seen.assign(in.nk, 0);
+    ds->names = *src.names; ds->key_len = *src.key_len;
+    ds->seen.assign(src.nk, 0);
     uint64_t steps = 0;
-    st = ivx_depth_profile_read(s->ctx, ds->profile, IVX_MEM_HOST, nullptr, nullptr, nullptr, ds->seen.data(), 0, &steps);
-    if (st != IVX_OK) { ivx_depth_profile_free(ds->profile); return fail_ivx(s, st); }
+    const ivx_status st = ivx_depth_profile_read(s->ctx, src.profile, IVX_MEM_HOST, nullptr, nullptr, nullptr, ds->seen.data(), 0, &steps);
+    if (st != IVX_OK) return fail_ivx(s, st);
     if (ds->names.empty()) ds->seen.assign(ds->seen.size(), 0);     // (an empty length table: key 0 stands for no contig)
+    ds->profile = src.g.ix; src.g.ix = nullptr;                     // the profile moves into the pull stream
     *out = ds.release();
     return 0;
 }
@@ -1294,6 +1311,21 @@ int depth_push_merge_all(brh_depth_push *dp)
     return 0;
 }
 
+int ProfileSource::open(brh_depth_push *p)
+{
+    if (depth_push_check(p) || depth_push_merge_all(p)) return 1;
+    dp = p; profile = p->stack[0]; nk = p->built_nk; known = std::min<uint32_t>((uint32_t)p->names.size(), p->built_nk);
+    names = &p->names; key_len = p->dense ? &p->key_len : nullptr; by_name = !p->dense;
+    return 0;
+}
+
+uint32_t ProfileSource::id_of(std::string_view name) const
+{
+    if (!dp) return in.dict.id_of(name);
+    auto it = dp->ids.find(std::string(name));
+    return it == dp->ids.end() ? IVX_NULL_IDX : it->second;
+}
+
 }  // namespace
 
 // the rows [lo[k], lo[k + 1]) of every key k, the keys taken in byte order of their names: for each output row the input row it
@@ -1351,8 +1383,7 @@ extern "C" int brh_depth_push_batch(brh_depth_push *dp, brh_batch reads)
     }
     for (uint32_t &k : in.rkey) if (k != IVX_NULL_IDX) k = to_stream[k];
     ivx_index *p = nullptr;
-    const ivx_status st = in.profile(s->ctx, nullptr, nullptr, nullptr, nullptr, 0, dp->nk(), dp->dense ? dp->key_len.data() : nullptr,
-                                     dp->filter_flag, dp->min_mapq, &p);
+    const ivx_status st = in.profile(s->ctx, DepthInputs::of_stream(dp->nk(), dp->dense ? dp->key_len.data() : nullptr), dp->filter_flag, dp->min_mapq, &p);
     if (st != IVX_OK) return fail_ivx(s, st);
     dp->stack.push_back(p);
     dp->built_nk = std::max(dp->built_nk, dp->nk());
@@ -1453,8 +1484,8 @@ int region_coords(brh_session *s, const PosCol &p, std::vector<int64_t> *out)
     return 0;
 }
 
-// The rows of a regions table as the closed u32 regions the profile calls take.  The keys are the ids `id_of` gives
-// (IVX_NULL_IDX, or an id of n_keys or more: a contig the profile does not know, coverage 0 everywhere: `unknown`, answered by
+// The rows of a regions table as the closed u32 regions the profile calls take.  The keys are the ids the profile source gives
+// (IVX_NULL_IDX, or an id of src.known or more: a contig the profile does not know, coverage 0 everywhere: `unknown`, answered by
 // the caller).  A region that is empty whatever the coverage gets the skip mark.  key_len (null: no length table) gives the
 // domain the per-base rows have: [0, len - 1] when zero_based, else [1, len] without the step at position 0.
 struct RegionRows {
@@ -1464,9 +1495,10 @@ struct RegionRows {
     uint32_t pos_lo = 0;
     bool has_len = false, skip_pos0 = false;
 
-    int load(brh_session *s, const char *what, uint32_t n_keys, const std::function<uint32_t(std::string_view)> &id_of,
-             const std::vector<uint32_t> *key_len, int zero_based, brh_batch regions, brh_columns cols, int end_exclusive)
+    int load(brh_session *s, const char *what, const ProfileSource &src, int zero_based, brh_batch regions, brh_columns cols, int end_exclusive)
     {
+        const uint32_t n_keys = src.known;
+        const std::vector<uint32_t> *key_len = src.key_len;
         if (!regions.array || !regions.schema) return fail(s, std::string(what) + ": null regions batch");
         if (cols.n_keys != 1 || !cols.keys || !cols.start || !cols.end)
             return fail(s, std::string(what) + ": the regions take one contig, one start and one end column");
@@ -1495,7 +1527,7 @@ struct RegionRows {
             uint32_t k = IVX_NULL_IDX;
             if (!contig.null_at((int64_t)i)) {
                 const std::string_view name = contig.at((int64_t)i);
-                if (!have || name != last) { last_id = id_of(name); last = name; have = true; }
+                if (!have || name != last) { last_id = src.id_of(name); last = name; have = true; }
                 k = last_id;
             }
             if (k >= n_keys) { unknown[i] = !empty && b >= a; k = IVX_NULL_IDX; }
@@ -1508,8 +1540,7 @@ struct RegionRows {
 };
 
 // The regions of `regions` summarised over `profile` (RegionRows for the keys, the domain and the unknown contigs)
-int summarize_regions(brh_session *s, const ivx_index *profile, uint32_t n_keys, const std::function<uint32_t(std::string_view)> &id_of,
-                      const std::vector<uint32_t> *key_len, int zero_based, brh_batch regions, brh_columns cols, int end_exclusive,
+int summarize_regions(brh_session *s, const ProfileSource &src, int zero_based, brh_batch regions, brh_columns cols, int end_exclusive,
                       const int32_t *thresholds, uint32_t n_thr,
                       ArrowArray *bases, ArrowSchema *bases_schema, ArrowArray *sum, ArrowSchema *sum_schema, ArrowArray *ge, ArrowSchema *ge_schemas)
 {
@@ -1518,10 +1549,10 @@ int summarize_regions(brh_session *s, const ivx_index *profile, uint32_t n_keys,
     if (n_thr > IVX_DEPTH_MAX_THRESHOLDS) return fail(s, "depth_regions: more than 8 thresholds");
     if (n_thr && (!thresholds || !ge || !ge_schemas)) return fail(s, "depth_regions: null thresholds or threshold outputs");
     RegionRows r;
-    if (r.load(s, "depth_regions", n_keys, id_of, key_len, zero_based, regions, cols, end_exclusive)) return 1;
+    if (r.load(s, "depth_regions", src, zero_based, regions, cols, end_exclusive)) return 1;
     const uint64_t n = r.n;
     std::vector<int64_t> ol(n ? n : 1, 0), os(n ? n : 1, 0), og((size_t)n_thr * n + 1, 0);
-    const ivx_status st = ivx_depth_profile_summarize(s->ctx, profile, IVX_MEM_HOST, r.qk.data(), r.qs.data(), r.qe.data(), n, r.pos_lo,
+    const ivx_status st = ivx_depth_profile_summarize(s->ctx, src.profile, IVX_MEM_HOST, r.qk.data(), r.qs.data(), r.qe.data(), n, r.pos_lo,
                                                       r.hi(), r.skip_pos0, thresholds, n_thr,
                                                       ol.data(), os.data(), n_thr ? og.data() : nullptr);
     if (st != IVX_OK) return fail_ivx(s, st);
@@ -1540,8 +1571,7 @@ int summarize_regions(brh_session *s, const ivx_index *profile, uint32_t n_keys,
 }
 
 // The same rows ranked over `profile` (ivx_depth_profile_quantiles): bases, and min / max / the quantiles, NULL where bases = 0
-int rank_regions(brh_session *s, const ivx_index *profile, uint32_t n_keys, const std::function<uint32_t(std::string_view)> &id_of,
-                 const std::vector<uint32_t> *key_len, int zero_based, brh_batch regions, brh_columns cols, int end_exclusive,
+int rank_regions(brh_session *s, const ProfileSource &src, int zero_based, brh_batch regions, brh_columns cols, int end_exclusive,
                  const uint32_t *q_num, uint32_t n_q, uint32_t q_den,
                  ArrowArray *bases, ArrowSchema *bases_schema, ArrowArray *mn, ArrowSchema *mn_schema, ArrowArray *mx, ArrowSchema *mx_schema,
                  ArrowArray *q, ArrowSchema *q_schemas)
@@ -1549,11 +1579,11 @@ int rank_regions(brh_session *s, const ivx_index *profile, uint32_t n_keys, cons
     if (n_q > IVX_DEPTH_MAX_QUANTILES) return fail(s, "depth_region_quantiles: more than 8 quantiles");
     if (n_q && (!q_num || !q || !q_schemas)) return fail(s, "depth_region_quantiles: null q_num or quantile outputs");
     RegionRows r;
-    if (r.load(s, "depth_region_quantiles", n_keys, id_of, key_len, zero_based, regions, cols, end_exclusive)) return 1;
+    if (r.load(s, "depth_region_quantiles", src, zero_based, regions, cols, end_exclusive)) return 1;
     const uint64_t n = r.n;
     std::vector<int64_t> ol(n ? n : 1, 0);
     std::vector<int32_t> omn(n ? n : 1, 0), omx(n ? n : 1, 0), oq((size_t)n_q * n + 1, 0);
-    const ivx_status st = ivx_depth_profile_quantiles(s->ctx, profile, IVX_MEM_HOST, r.qk.data(), r.qs.data(), r.qe.data(), n, r.pos_lo,
+    const ivx_status st = ivx_depth_profile_quantiles(s->ctx, src.profile, IVX_MEM_HOST, r.qk.data(), r.qs.data(), r.qe.data(), n, r.pos_lo,
                                                       r.hi(), r.skip_pos0, q_num, n_q, q_den,
                                                       ol.data(), omn.data(), omx.data(), n_q ? oq.data() : nullptr);
     if (st != IVX_OK) return fail_ivx(s, st);
@@ -1581,15 +1611,9 @@ extern "C" int brh_depth_regions(brh_session *s, brh_batch reads, brh_batch prio
                                  ArrowArray *ge, ArrowSchema *ge_schemas)
 {
     if (!s) return 1;
-    DepthInputs in;
-    if (in.load(s, reads, prior, lengths)) return 1;
-    IndexGuard g;
-    const ivx_status st = in.profile(s->ctx, in.has_prior ? in.skey.data() : nullptr, in.ss.data(), in.se.data(), in.has_prior ? in.sw.data() : nullptr,
-                                     in.n_seg, in.nk, in.has_len ? in.key_len.data() : nullptr, filter_flag, min_mapq, &g.ix);
-    if (st != IVX_OK) return fail_ivx(s, st);
-    const uint32_t known = (uint32_t)in.dict.names.size();           // (an empty dictionary: key 0 stands for no contig)
-    return summarize_regions(s, g.ix, known, [&](std::string_view k) { return in.dict.id_of(k); }, in.has_len ? &in.key_len : nullptr, zero_based,
-                             regions, region_cols, end_exclusive, thresholds, n_thr, bases, bases_schema, sum, sum_schema, ge, ge_schemas);
+    ProfileSource src;
+    if (src.open(s, reads, prior, lengths, filter_flag, min_mapq)) return 1;
+    return summarize_regions(s, src, zero_based, regions, region_cols, end_exclusive, thresholds, n_thr, bases, bases_schema, sum, sum_schema, ge, ge_schemas);
 }
 
 extern "C" int brh_depth_push_regions(brh_depth_push *dp, brh_batch regions, brh_columns region_cols, int zero_based, int end_exclusive,
@@ -1598,13 +1622,9 @@ extern "C" int brh_depth_push_regions(brh_depth_push *dp, brh_batch regions, brh
                                       ArrowArray *ge, ArrowSchema *ge_schemas)
 {
     if (!dp) return 1;
-    brh_session *s = dp->s;
-    if (depth_push_check(dp) || depth_push_merge_all(dp)) return 1;            // the merged profile stays the stack's only entry
-    const uint32_t known = std::min<uint32_t>((uint32_t)dp->names.size(), dp->built_nk);
-    return summarize_regions(s, dp->stack[0], known,
-                             [&](std::string_view k) { auto it = dp->ids.find(std::string(k)); return it == dp->ids.end() ? IVX_NULL_IDX : it->second; },
-                             dp->dense ? &dp->key_len : nullptr, zero_based, regions, region_cols, end_exclusive, thresholds, n_thr,
-                             bases, bases_schema, sum, sum_schema, ge, ge_schemas);
+    ProfileSource src;
+    if (src.open(dp)) return 1;
+    return summarize_regions(dp->s, src, zero_based, regions, region_cols, end_exclusive, thresholds, n_thr, bases, bases_schema, sum, sum_schema, ge, ge_schemas);
 }
 
 extern "C" int brh_depth_region_quantiles(brh_session *s, brh_batch reads, brh_batch prior, brh_batch lengths, brh_batch regions, brh_columns region_cols,
@@ -1614,15 +1634,9 @@ extern "C" int brh_depth_region_quantiles(brh_session *s, brh_batch reads, brh_b
                                           ArrowArray *mx, ArrowSchema *mx_schema, ArrowArray *q, ArrowSchema *q_schemas)
 {
     if (!s) return 1;
-    DepthInputs in;
-    if (in.load(s, reads, prior, lengths)) return 1;
-    IndexGuard g;
-    const ivx_status st = in.profile(s->ctx, in.has_prior ? in.skey.data() : nullptr, in.ss.data(), in.se.data(), in.has_prior ? in.sw.data() : nullptr,
-                                     in.n_seg, in.nk, in.has_len ? in.key_len.data() : nullptr, filter_flag, min_mapq, &g.ix);
-    if (st != IVX_OK) return fail_ivx(s, st);
-    const uint32_t known = (uint32_t)in.dict.names.size();           // (an empty dictionary: key 0 stands for no contig)
-    return rank_regions(s, g.ix, known, [&](std::string_view k) { return in.dict.id_of(k); }, in.has_len ? &in.key_len : nullptr, zero_based,
-                        regions, region_cols, end_exclusive, q_num, n_q, q_den, bases, bases_schema, mn, mn_schema, mx, mx_schema, q, q_schemas);
+    ProfileSource src;
+    if (src.open(s, reads, prior, lengths, filter_flag, min_mapq)) return 1;
+    return rank_regions(s, src, zero_based, regions, region_cols, end_exclusive, q_num, n_q, q_den, bases, bases_schema, mn, mn_schema, mx, mx_schema, q, q_schemas);
 }
 
 extern "C" int brh_depth_push_region_quantiles(brh_depth_push *dp, brh_batch regions, brh_columns region_cols, int zero_based, int end_exclusive,
@@ -1631,13 +1645,9 @@ extern "C" int brh_depth_push_region_quantiles(brh_depth_push *dp, brh_batch reg
                                                ArrowArray *mx, ArrowSchema *mx_schema, ArrowArray *q, ArrowSchema *q_schemas)
 {
     if (!dp) return 1;
-    brh_session *s = dp->s;
-    if (depth_push_check(dp) || depth_push_merge_all(dp)) return 1;            // the merged profile stays the stack's only entry
-    const uint32_t known = std::min<uint32_t>((uint32_t)dp->names.size(), dp->built_nk);
-    return rank_regions(s, dp->stack[0], known,
-                        [&](std::string_view k) { auto it = dp->ids.find(std::string(k)); return it == dp->ids.end() ? IVX_NULL_IDX : it->second; },
-                        dp->dense ? &dp->key_len : nullptr, zero_based, regions, region_cols, end_exclusive, q_num, n_q, q_den,
-                        bases, bases_schema, mn, mn_schema, mx, mx_schema, q, q_schemas);
+    ProfileSource src;
+    if (src.open(dp)) return 1;
+    return rank_regions(dp->s, src, zero_based, regions, region_cols, end_exclusive, q_num, n_q, q_den, bases, bases_schema, mn, mn_schema, mx, mx_schema, q, q_schemas);
 }
 
 // ---- depth coverage classes (ivx_depth_profile_quantize / ivx_depth_profile_hist): the maximal intervals of one coverage bin,
@@ -1652,8 +1662,10 @@ struct ClassDomain {
     std::vector<uint8_t> drop;
     uint32_t pos_lo = 0;
     bool has_len = false, skip_pos0 = false;
-    ClassDomain(uint32_t nk, uint32_t known, const std::vector<uint32_t> *key_len, int zero_based)
+    ClassDomain(const ProfileSource &src, int zero_based)
     {
+        const uint32_t nk = src.nk, known = src.known;
+        const std::vector<uint32_t> *key_len = src.key_len;
         has_len = key_len != nullptr;
         pos_lo = (key_len && !zero_based) ? 1u : 0u;
         skip_pos0 = key_len && !zero_based;
@@ -1671,23 +1683,23 @@ struct ClassDomain {
 };
 
 // the keys < known in the order their rows go out: ascending ids, or (by_name) the byte order of their names
-std::vector<uint32_t> class_key_order(const std::vector<std::string> &names, uint32_t known, bool by_name)
+std::vector<uint32_t> class_key_order(const ProfileSource &src)
 {
-    std::vector<uint32_t> order(known);
-    for (uint32_t k = 0; k < known; k++) order[k] = k;
-    if (by_name) std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return names[a] < names[b]; });
+    std::vector<uint32_t> order(src.known);
+    for (uint32_t k = 0; k < src.known; k++) order[k] = k;
+    if (src.by_name) std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return (*src.names)[a] < (*src.names)[b]; });
     return order;
 }
 
-int quantize_profile(brh_session *s, const ivx_index *profile, uint32_t nk, uint32_t known, const std::vector<std::string> &names,
-                     const std::vector<uint32_t> *key_len, bool by_name, int zero_based, int end_exclusive, int touched_only,
+int quantize_profile(brh_session *s, const ProfileSource &src, int zero_based, int end_exclusive, int touched_only,
                      const int32_t *cuts, uint32_t n_cuts, uint32_t emit_mask,
                      ArrowArray *contig, ArrowSchema *contig_schema, ArrowArray *start, ArrowSchema *start_schema,
                      ArrowArray *end, ArrowSchema *end_schema, ArrowArray *bin, ArrowSchema *bin_schema)
 {
-    const ClassDomain d(nk, known, key_len, zero_based);
+    const ClassDomain d(src, zero_based);
+    const uint32_t nk = src.nk;
     auto call = [&](uint32_t *ok, uint32_t *os, uint32_t *oe, uint32_t *oc, uint64_t cap, uint64_t *m) {
-        return ivx_depth_profile_quantize(s->ctx, profile, IVX_MEM_HOST, d.pos_lo, d.hi(), d.skip_pos0, touched_only != 0, cuts, n_cuts, emit_mask,
+        return ivx_depth_profile_quantize(s->ctx, src.profile, IVX_MEM_HOST, d.pos_lo, d.hi(), d.skip_pos0, touched_only != 0, cuts, n_cuts, emit_mask,
                                           ok, os, oe, oc, cap, m);
     };
     uint64_t m = 0, m2 = 0;
@@ -1703,7 +1715,7 @@ int quantize_profile(brh_session *s, const ivx_index *profile, uint32_t nk, uint
     for (uint64_t i = m2; i-- > 0;) if (ok[i] < nk) lo[ok[i]] = i;
     for (size_t k = nk; k-- > 0;) if (lo[k] > lo[k + 1]) lo[k] = lo[k + 1];
     std::vector<uint32_t> oid; std::vector<int64_t> o64s, o64e; std::vector<int32_t> obin;
-    for (uint32_t k : class_key_order(names, known, by_name)) {
+    for (uint32_t k : class_key_order(src)) {
         if (d.drop[k]) continue;
         for (uint64_t i = lo[k]; i < lo[k + 1]; i++) {
             oid.push_back(k); o64s.push_back((int64_t)os[i]); o64e.push_back((int64_t)oe[i] + (end_exclusive ? 1 : 0)); obin.push_back((int32_t)oc[i]);
@@ -1711,25 +1723,24 @@ int quantize_profile(brh_session *s, const ivx_index *profile, uint32_t nk, uint
     }
     const int64_t n = (int64_t)oid.size();
     if (!n) { oid.push_back(0); o64s.push_back(0); o64e.push_back(0); obin.push_back(0); }
-    make_utf8(contig, names, oid.data(), n); make_schema(contig_schema, "u", "contig", true);
+    make_utf8(contig, *src.names, oid.data(), n); make_schema(contig_schema, "u", "contig", true);
     make_primitive<int64_t>(start, o64s.data(), n, nullptr); make_schema(start_schema, "l", "start", false);
     make_primitive<int64_t>(end, o64e.data(), n, nullptr); make_schema(end_schema, "l", "end", false);
     make_primitive<int32_t>(bin, obin.data(), n, nullptr); make_schema(bin_schema, "i", "bin", false);
     return 0;
 }
 
-int dist_profile(brh_session *s, const ivx_index *profile, uint32_t nk, uint32_t known, const std::vector<std::string> &names,
-                 const std::vector<uint32_t> *key_len, bool by_name, int zero_based, int touched_only, int32_t v_lo, uint32_t n_bins,
+int dist_profile(brh_session *s, const ProfileSource &src, int zero_based, int touched_only, int32_t v_lo, uint32_t n_bins,
                  ArrowArray *contig, ArrowSchema *contig_schema, ArrowArray *coverage, ArrowSchema *coverage_schema,
                  ArrowArray *bases, ArrowSchema *bases_schema)
 {
     if (n_bins == 0 || n_bins > IVX_DEPTH_MAX_BINS) return fail(s, "depth_dist: n_bins outside 1 .. 65536");
-    const ClassDomain d(nk, known, key_len, zero_based);
-    std::vector<int64_t> h((size_t)nk * n_bins, 0);
-    const ivx_status st = ivx_depth_profile_hist(s->ctx, profile, IVX_MEM_HOST, d.pos_lo, d.hi(), d.skip_pos0, touched_only != 0, v_lo, n_bins, h.data());
+    const ClassDomain d(src, zero_based);
+    std::vector<int64_t> h((size_t)src.nk * n_bins, 0);
+    const ivx_status st = ivx_depth_profile_hist(s->ctx, src.profile, IVX_MEM_HOST, d.pos_lo, d.hi(), d.skip_pos0, touched_only != 0, v_lo, n_bins, h.data());
     if (st != IVX_OK) return fail_ivx(s, st);
     std::vector<uint32_t> oid; std::vector<int32_t> ocov; std::vector<int64_t> obases;
-    for (uint32_t k : class_key_order(names, known, by_name)) {
+    for (uint32_t k : class_key_order(src)) {
         if (d.drop[k]) continue;
         for (uint32_t b = 0; b < n_bins; b++) {
             const int64_t c = h[(size_t)k * n_bins + b];
@@ -1739,20 +1750,10 @@ int dist_profile(brh_session *s, const ivx_index *profile, uint32_t nk, uint32_t
     }
     const int64_t n = (int64_t)oid.size();
     if (!n) { oid.push_back(0); ocov.push_back(0); obases.push_back(0); }
-    make_utf8(contig, names, oid.data(), n); make_schema(contig_schema, "u", "contig", true);
+    make_utf8(contig, *src.names, oid.data(), n); make_schema(contig_schema, "u", "contig", true);
     make_primitive<int32_t>(coverage, ocov.data(), n, nullptr); make_schema(coverage_schema, "i", "coverage", false);
     make_primitive<int64_t>(bases, obases.data(), n, nullptr); make_schema(bases_schema, "l", "bases", false);
     return 0;
-}
-
-// ONE profile of the inputs of a depth() call
-int depth_one_profile(brh_session *s, DepthInputs *in, brh_batch reads, brh_batch prior, brh_batch lengths, uint32_t filter_flag, uint32_t min_mapq,
-                      IndexGuard *g)
-{
-    if (in->load(s, reads, prior, lengths)) return 1;
-    const ivx_status st = in->profile(s->ctx, in->has_prior ? in->skey.data() : nullptr, in->ss.data(), in->se.data(), in->has_prior ? in->sw.data() : nullptr,
-                                      in->n_seg, in->nk, in->has_len ? in->key_len.data() : nullptr, filter_flag, min_mapq, &g->ix);
-    return st != IVX_OK ? fail_ivx(s, st) : 0;
 }
 
 }  // namespace
@@ -1764,10 +1765,9 @@ extern "C" int brh_depth_quantize(brh_session *s, brh_batch reads, brh_batch pri
                                   ArrowArray *end, ArrowSchema *end_schema, ArrowArray *bin, ArrowSchema *bin_schema)
 {
     if (!s) return 1;
-    DepthInputs in; IndexGuard g;
-    if (depth_one_profile(s, &in, reads, prior, lengths, filter_flag, min_mapq, &g)) return 1;
-    return quantize_profile(s, g.ix, in.nk, (uint32_t)in.dict.names.size(), in.dict.names, in.has_len ? &in.key_len : nullptr, false,
-                            zero_based, end_exclusive, touched_only, cuts, n_cuts, emit_mask,
+    ProfileSource src;
+    if (src.open(s, reads, prior, lengths, filter_flag, min_mapq)) return 1;
+    return quantize_profile(s, src, zero_based, end_exclusive, touched_only, cuts, n_cuts, emit_mask,
                             contig, contig_schema, start, start_schema, end, end_schema, bin, bin_schema);
 }
 
@@ -1777,10 +1777,9 @@ extern "C" int brh_depth_push_quantize(brh_depth_push *dp, int zero_based, int e
                                        ArrowArray *end, ArrowSchema *end_schema, ArrowArray *bin, ArrowSchema *bin_schema)
 {
     if (!dp) return 1;
-    if (depth_push_check(dp) || depth_push_merge_all(dp)) return 1;            // the merged profile stays the stack's only entry
-    const uint32_t known = std::min<uint32_t>((uint32_t)dp->names.size(), dp->built_nk);
-    return quantize_profile(dp->s, dp->stack[0], dp->built_nk, known, dp->names, dp->dense ? &dp->key_len : nullptr, !dp->dense,
-                            zero_based, end_exclusive, touched_only, cuts, n_cuts, emit_mask,
+    ProfileSource src;
+    if (src.open(dp)) return 1;
+    return quantize_profile(dp->s, src, zero_based, end_exclusive, touched_only, cuts, n_cuts, emit_mask,
                             contig, contig_schema, start, start_schema, end, end_schema, bin, bin_schema);
 }
 
@@ -1790,10 +1789,9 @@ extern "C" int brh_depth_dist(brh_session *s, brh_batch reads, brh_batch prior, 
                               ArrowArray *bases, ArrowSchema *bases_schema)
 {
     if (!s) return 1;
-    DepthInputs in; IndexGuard g;
-    if (depth_one_profile(s, &in, reads, prior, lengths, filter_flag, min_mapq, &g)) return 1;
-    return dist_profile(s, g.ix, in.nk, (uint32_t)in.dict.names.size(), in.dict.names, in.has_len ? &in.key_len : nullptr, false,
-                        zero_based, touched_only, v_lo, n_bins, contig, contig_schema, coverage, coverage_schema, bases, bases_schema);
+    ProfileSource src;
+    if (src.open(s, reads, prior, lengths, filter_flag, min_mapq)) return 1;
+    return dist_profile(s, src, zero_based, touched_only, v_lo, n_bins, contig, contig_schema, coverage, coverage_schema, bases, bases_schema);
 }
 
 extern "C" int brh_depth_push_dist(brh_depth_push *dp, int zero_based, int touched_only, int32_t v_lo, uint32_t n_bins,
@@ -1801,10 +1799,9 @@ extern "C" int brh_depth_push_dist(brh_depth_push *dp, int zero_based, int touch
                                    ArrowArray *bases, ArrowSchema *bases_schema)
 {
     if (!dp) return 1;
-    if (depth_push_check(dp) || depth_push_merge_all(dp)) return 1;            // the merged profile stays the stack's only entry
-    const uint32_t known = std::min<uint32_t>((uint32_t)dp->names.size(), dp->built_nk);
-    return dist_profile(dp->s, dp->stack[0], dp->built_nk, known, dp->names, dp->dense ? &dp->key_len : nullptr, !dp->dense,
-                        zero_based, touched_only, v_lo, n_bins, contig, contig_schema, coverage, coverage_schema, bases, bases_schema);
+    ProfileSource src;
+    if (src.open(dp)) return 1;
+    return dist_profile(dp->s, src, zero_based, touched_only, v_lo, n_bins, contig, contig_schema, coverage, coverage_schema, bases, bases_schema);
 }
 
 // ---- f3: payload gather
