@@ -176,13 +176,26 @@ class Session:
 
     # ---- nearest: NearestTableFunction (table_function.rs:286-367)
     def nearest(self, left, right, k=1, overlap=True, compute_distance=True, cols_left=DEFAULT_COLS, cols_right=DEFAULT_COLS,
-                strict=False):
+                strict=False, direction="any", max_distance=None):
+        """direction: "any" | "before" ("upstream": only left rows that end before the right row) | "after" ("downstream": only
+        left rows that start after it); max_distance: no left row farther than that is an answer (None: no cap).  Direction
+        does not touch overlapping rows: `overlap` alone decides them.  The defaults are the reference's nearest()."""
+        d = pyivx.NEAR_ALIASES.get(direction, direction)
+        if d not in pyivx.NEAR_DIRECTIONS:
+            raise ValueError(f"direction must be one of {pyivx.NEAR_DIRECTIONS + tuple(pyivx.NEAR_ALIASES)}, got {direction!r}")
+        if max_distance is not None and int(max_distance) < 0:
+            raise ValueError(f"max_distance must be >= 0 or None, got {max_distance!r}")
         L, R = _Exported(left), _Exported(right)
         (la, ls), (ra, rs), (da, ds) = _out(), _out(), _out()
         try:
-            self._chk(lib().brh_nearest(self.h, L.c, _cols(cols_left), R.c, _cols(cols_right), C.c_int(STRICT if strict else WEAK),
-                                        C.c_uint32(int(k)), C.c_int(int(overlap)), C.c_int(int(compute_distance)),
-                                        C.byref(la), C.byref(ls), C.byref(ra), C.byref(rs), C.byref(da), C.byref(ds)))
+            head = (self.h, L.c, _cols(cols_left), R.c, _cols(cols_right), C.c_int(STRICT if strict else WEAK),
+                    C.c_uint32(int(k)), C.c_int(int(overlap)), C.c_int(int(compute_distance)))
+            outs = (C.byref(la), C.byref(ls), C.byref(ra), C.byref(rs), C.byref(da), C.byref(ds))
+            if d == "any" and max_distance is None:
+                self._chk(lib().brh_nearest(*head, *outs))
+            else:
+                self._chk(lib().brh_nearest_dir(*head, C.c_int(pyivx.NEAR_DIRECTIONS.index(d)), C.c_int64(int(max_distance if max_distance is not None else -1)),
+                                                *outs))
         finally:
             L.close(); R.close()
         li, ri = _import(la, ls), _import(ra, rs)

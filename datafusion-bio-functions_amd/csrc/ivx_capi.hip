@@ -1198,6 +1198,36 @@ extern "C" ivx_status ivx_probe_nearest(ivx_ctx *ctx, const ivx_index *ix, int m
     return f.finish();
 }
 
+// a6' (include/ivx_nearest.h): one side only and / or within a distance cap.  Without either it IS ivx_probe_nearest
+extern "C" ivx_status ivx_probe_nearest_dir(ivx_ctx *ctx, const ivx_index *ix, int mem, const uint32_t *key, const int32_t *start,
+                                            const int32_t *end, uint64_t n, int strict, uint32_t k, int include_overlaps,
+                                            int direction, int64_t max_distance,
+                                            uint32_t *build_idx, uint32_t *probe_idx, int64_t *distance, uint64_t cap, uint64_t *rows)
+{
+    if (direction == IVX_NEAR_ANY && max_distance < 0)
+        return ivx_probe_nearest(ctx, ix, mem, key, start, end, n, strict, k, include_overlaps, build_idx, probe_idx, distance, cap, rows);
+    Frame f(ctx, mem);
+    IVX_TRY(check_probe_args(f, ix, IVX_KIND_NEAREST, start, end, n));
+    if (!rows) return ctx->fail(IVX_ERR_INVALID, "null rows");
+    *rows = 0;
+    if (direction < 0 || direction >= IVX_NEAR_N) return ctx->fail(IVX_ERR_INVALID, "nearest: direction must be IVX_NEAR_ANY, IVX_NEAR_BEFORE or IVX_NEAR_AFTER");
+    if (n && (!build_idx || !probe_idx)) return ctx->fail(IVX_ERR_INVALID, "null output column");
+    if ((u64)k * n > 0xFFFFFFFFFFull) return ctx->fail(IVX_ERR_INVALID, "nearest: k * rows too large");
+    f.meter(false, n);
+    const u32 *dk = f.in(key, n);
+    const i32 *ds = f.in(start, n), *de = f.in(end, n);
+    u32 *db = f.out(build_idx, cap), *dp = f.out(probe_idx, cap);
+    i64 *dd = f.out(distance, cap);
+    IVX_TRY(f.st);
+    u64 r = 0;
+    const ivx_status st = f.run([&] { return ivx_nearest_probe_dir(ctx, ix, dk, ds, de, n, strict, k, include_overlaps, direction, max_distance, db, dp, dd, cap, &r); });
+    *rows = r;
+    if (st != IVX_OK) return st;
+    f.rows_out(r);
+    f.back_all(r);
+    return f.finish();
+}
+
 // ---------------------------------------------------------------- a7..a9
 
 extern "C" ivx_status ivx_merge(ivx_ctx *ctx, int mem, const uint32_t *key, const int64_t *start, const int64_t *end, uint64_t n,

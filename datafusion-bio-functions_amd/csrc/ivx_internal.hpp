@@ -8,6 +8,7 @@
 #include <vector>
 #include "../../include/ivx.h"
 #include "../../include/ivx_select.h"
+#include "../../include/ivx_nearest.h"
 
 typedef uint8_t u8;
 typedef uint32_t u32;
@@ -485,6 +486,11 @@ ivx_status ivx_count_probe(ivx_ctx *ctx, const ivx_index *ix, const u32 *key, co
 ivx_status ivx_coverage_probe(ivx_ctx *ctx, const ivx_index *ix, const u32 *key, const i32 *s, const i32 *e, u64 n, int strict, i64 *out);
 ivx_status ivx_nearest_probe(ivx_ctx *ctx, const ivx_index *ix, const u32 *key, const i32 *s, const i32 *e, u64 n,
                              int strict, u32 k, int include_overlaps, u32 *ob, u32 *op, i64 *od, u64 cap, u64 *rows);
+// the same on one side only and / or within a distance cap (include/ivx_nearest.h): direction = IVX_NEAR_*, max_distance < 0 = no
+// cap; IVX_NEAR_ANY without a cap IS ivx_nearest_probe.  Scratch as ivx_nearest_probe
+ivx_status ivx_nearest_probe_dir(ivx_ctx *ctx, const ivx_index *ix, const u32 *key, const i32 *s, const i32 *e, u64 n,
+                                 int strict, u32 k, int include_overlaps, int direction, i64 max_distance,
+                                 u32 *ob, u32 *op, i64 *od, u64 cap, u64 *rows);
 
 // ivx_sweep.hip: merge / subtract / cluster / complement over int64 coordinates (device pointers); the fill half of a
 // subtract whose sizing call left its plan in the context

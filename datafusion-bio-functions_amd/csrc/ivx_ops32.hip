@@ -963,3 +963,226 @@ ivx_status ivx_nearest_probe(ivx_ctx *ctx, const ivx_index *ix, const u32 *key, 
     IVX_HIP(ctx, hipGetLastError());
     return IVX_OK;
 }
+
+// ======================================================================= a6': nearest on one side only, within a distance cap
+// (include/ivx_nearest.h).  The candidate stream of a probe row is nearest_k's -- overlaps, then the two cursors merged -- with
+// the right cursor (IVX_NEAR_BEFORE) or the left one (IVX_NEAR_AFTER) empty from the start, and with a cursor counting as
+// exhausted once its head's reported distance (raw probe coordinates) exceeds the cap D.  DIR and CAP are compile-time: a
+// one-sided row issues only its own side's rank lookup and record load (these kernels wait on scattered index sectors, see
+// first_overlap), and the plain kernels above keep their code.  IVX_NEAR_ANY without a cap is never instantiated: it is
+// ivx_nearest_probe.
+
+namespace {
+
+template <bool CAP>
+__device__ __forceinline__ bool head_within(i32 rs, i32 re, const Cand &c, i64 D)
+{
+    return !CAP || cand_dist(rs, re, c.s, c.e) <= D;
+}
+
+// nearest_one for the (already strict-adjusted) query [qs,qe] of the probe row [rs,re]: the first overlap if asked for and
+// present (the one-lookup form, first_overlap_pmax), else the head of the cursor(s)
+template <int DIR, bool CAP>
+__device__ __forceinline__ bool nearest_one_dir(const NearestCtx &x, u32 k, i32 qs, i32 qe, i32 rs, i32 re, int include_overlaps, i64 D, Cand *best)
+{
+    const NearestView &nv = x.nv;
+    if (k >= nv.by_start.nkeys || nv.by_start.kcnt[k] == 0) return false;
+    const u32 off = nv.by_start.koff[k], cnt = nv.by_start.kcnt[k];
+    if (include_overlaps && first_overlap_pmax(x, k, off, cnt, qs, qe, best)) return true;
+    Cand l{}, r{};
+    bool hl = false, hr = false;
+    if (DIR != IVX_NEAR_AFTER) {
+        const u32 li = grid_rank_lt<4>(nv.by_end, x.sh_e, k, qs);        // by_end.partition_point(last < start)
+        if (li > off) { l = x.by_end(li - 1); hl = head_within<CAP>(rs, re, l, D); }
+    }
+    if (DIR != IVX_NEAR_BEFORE) {
+        const u32 ri = grid_rank_le<4>(nv.by_start, x.sh_s, k, qe);      // by_start.partition_point(first <= end)
+        if (ri < off + cnt) { r = x.by_start(ri); hr = head_within<CAP>(rs, re, r, D); }
+    }
+    if (hl && hr) *best = cmp_cand(qs, qe, l, r) <= 0 ? l : r;
+    else if (hl) *best = l;
+    else if (hr) *best = r;
+    return hl || hr;
+}
+
+// k_probe_nearest1 with a direction and / or a cap
+template <int DIR, bool CAP>
+__global__ __launch_bounds__(OT) void k_probe_nearest1_dir(NearestView nv, const u32 *__restrict__ pkey, const i32 *__restrict__ ps,
+                                                           const i32 *__restrict__ pe, u64 n, int strict, int include_overlaps, i64 D,
+                                                           u32 *__restrict__ ob, u32 *__restrict__ op, i64 *__restrict__ od, const u32 *gate)
+{
+    if (gate && *gate != 0) return;
+    NearestCtx x; x.nv = nv; x.sh_s = nv.by_start.hdr[0]; x.sh_e = nv.by_end.hdr[0]; x.sh_p = nv.pmax.hdr[0];
+    for (u64 i = (u64)blockIdx.x * OT + threadIdx.x; i < n; i += (u64)gridDim.x * OT) {
+        const u32 k = pkey ? pkey[i] : 0u;
+        const i32 rs = ps[i], re = pe[i];
+        i32 qs = rs, qe = re;
+        if (strict) { qs = wadd(qs, 1); qe = wsub(qe, 1); }
+        Cand best{};
+        bool found;
+        const u32 k0 = (u32)__builtin_amdgcn_readfirstlane((int)k);       // one key per wavefront: its per-key tables go through the scalar unit (k_probe_nearest1)
+        if (__ballot(k != k0) == 0) found = nearest_one_dir<DIR, CAP>(x, k0, qs, qe, rs, re, include_overlaps, D, &best);
+        else found = nearest_one_dir<DIR, CAP>(x, k, qs, qe, rs, re, include_overlaps, D, &best);
+        ob[i] = found ? best.row : IVX_NULL_IDX;
+        op[i] = (u32)i;
+        if (od) od[i] = found ? cand_dist(rs, re, best.s, best.e) : -1;
+    }
+}
+
+// k_nearest_routed with a direction and / or a cap: the same sweep over the same routed rows
+template <int DIR, bool CAP>
+__global__ __launch_bounds__(NR_T) void k_nearest_routed_dir(NearestView nv, const u32 *__restrict__ rkey, u32 nreg, const u64 *__restrict__ pse,
+                                                             const u32 *__restrict__ offs, u32 nblk, u32 adj, int include_overlaps, i64 D,
+                                                             u32 *__restrict__ vb, i64 *__restrict__ vd, const u32 *unsorted)
+{
+    __shared__ u32 s_rfirst[IVX_MAXREG_WIDE + 2];
+    if (*unsorted == 0) return;
+    for (u32 t = threadIdx.x; t <= nreg; t += NR_T) s_rfirst[t] = offs[(u64)t * nblk];
+    __syncthreads();
+    const u64 total = s_rfirst[nreg];
+    NearestCtx x; x.nv = nv; x.sh_s = nv.by_start.hdr[0]; x.sh_e = nv.by_end.hdr[0]; x.sh_p = nv.pmax.hdr[0];
+    const u32 xcd = blockIdx.x & 7u, nb = gridDim.x >> 3, bi = blockIdx.x >> 3;      // XCD x sweeps the x-th eighth (k_nearest_routed)
+    const u64 seg_lo = total * xcd / 8, seg_hi = total * (xcd + 1) / 8;
+    for (u64 i = seg_lo + (u64)bi * NR_T + threadIdx.x; i < seg_hi; i += (u64)nb * NR_T) {
+        u32 a = 0, b = nreg;
+        while (a < b) { const u32 m = (a + b + 1) >> 1; if (s_rfirst[m] <= i) a = m; else b = m - 1; }
+        const u32 k = rkey[a];
+        const u64 w = pse[i];
+        const i32 qs = (i32)(u32)w, qe = (i32)(u32)(w >> 32);
+        const i32 rs = wsub(qs, (i32)adj), re = wadd(qe, (i32)adj);     // the raw coordinates: what the distance and the cap are on
+        Cand best{};
+        const bool found = nearest_one_dir<DIR, CAP>(x, k, qs, qe, rs, re, include_overlaps, D, &best);
+        vb[i] = found ? best.row : IVX_NULL_IDX;
+        if (vd) vd[i] = found ? cand_dist(rs, re, best.s, best.e) : -1;
+    }
+}
+
+// k_probe_nearestk with a direction and / or a cap: one cursor or two into tmp[i*k ..]; with a cap a cursor ends on its
+// first candidate past D
+template <int DIR, bool CAP>
+__global__ __launch_bounds__(OT) void k_probe_nearestk_dir(NearestView nv, const u32 *__restrict__ pkey, const i32 *__restrict__ ps,
+                                                           const i32 *__restrict__ pe, u64 n, int strict, int include_overlaps, u32 kk, i64 D,
+                                                           u32 *__restrict__ tmp, i64 *__restrict__ tmpd, u32 *__restrict__ cnt)
+{
+    NearestCtx x; x.nv = nv; x.sh_s = nv.by_start.hdr[0]; x.sh_e = nv.by_end.hdr[0]; x.sh_p = nv.pmax.hdr[0];
+    for (u64 i = (u64)blockIdx.x * OT + threadIdx.x; i < n; i += (u64)gridDim.x * OT) {
+        const u32 k = pkey ? pkey[i] : 0u;
+        const i32 rs = ps[i], re = pe[i];
+        i32 qs = rs, qe = re;
+        if (strict) { qs = wadd(qs, 1); qe = wsub(qe, 1); }
+        u32 *mine = tmp + i * (u64)kk;
+        i64 *mined = tmpd ? tmpd + i * (u64)kk : nullptr;
+        auto take = [&](u32 at, const Cand &c) { mine[at] = c.row; if (mined) mined[at] = cand_dist(rs, re, c.s, c.e); };
+        u32 found = 0;
+        if (k < nv.by_start.nkeys && nv.by_start.kcnt[k] != 0) {
+            const u32 off = nv.by_start.koff[k], end_k = off + nv.by_start.kcnt[k];
+            // one cursor never meets a row twice, nor a row of the overlap stage (those end at or behind qs and start at or
+            // before qe); the two cursors of a query with qe < qs can
+            auto seen = [&](u32 row) { if (DIR != IVX_NEAR_ANY) return false; for (u32 q = 0; q < found; q++) if (mine[q] == row) return true; return false; };
+            u32 pend = end_k;
+            if (DIR != IVX_NEAR_BEFORE) pend = grid_rank_le<4>(nv.by_start, x.sh_s, k, qe);
+            if (include_overlaps) {
+                // all overlaps in (start,end,row) order = by_start order from the first running max that reaches qs, while
+                // start <= qe, filtered by end >= qs.  BEFORE has no use for the by_start rank: it stops on the first start past qe
+                if (DIR == IVX_NEAR_BEFORE) {
+                    for (u32 j = grid_rank_lt<4>(nv.pmax, x.sh_p, k, qs); j < end_k && found < kk; j++) {
+                        const ivx_nrec r = nv.rs[j];
+                        if (r.a > qe) break;
+                        if (r.b >= qs) { Cand c; c.s = r.a; c.e = r.b; c.row = r.row; take(found++, c); }
+                    }
+                } else if (pend > off && nv.rs[pend - 1].pmax >= qs) {
+                    for (u32 j = grid_rank_lt<4>(nv.pmax, x.sh_p, k, qs); j < pend && found < kk; j++) {
+                        const ivx_nrec r = nv.rs[j];
+                        if (r.b >= qs) { Cand c; c.s = r.a; c.e = r.b; c.row = r.row; take(found++, c); }
+                    }
+                }
+            }
+            if (found < kk) {
+                u32 li = off, ri = end_k;                                   // a cursor the direction leaves out starts exhausted
+                if (DIR != IVX_NEAR_AFTER) li = grid_rank_lt<4>(nv.by_end, x.sh_e, k, qs);
+                if (DIR != IVX_NEAR_BEFORE) ri = pend;
+                while (found < kk) {
+                    bool hl = DIR != IVX_NEAR_AFTER && li > off, hr = DIR != IVX_NEAR_BEFORE && ri < end_k;
+                    Cand l{}, r{};
+                    if (hl) { l = x.by_end(li - 1); hl = head_within<CAP>(rs, re, l, D); }
+                    if (hr) { r = x.by_start(ri); hr = head_within<CAP>(rs, re, r, D); }
+                    if (!hl && !hr) break;
+                    const bool take_left = hl && (!hr || cmp_cand(qs, qe, l, r) <= 0);
+                    const Cand c = take_left ? l : r;
+                    if (take_left) li--; else ri++;
+                    if (!include_overlaps && cand_dist(qs, qe, c.s, c.e) == 0) continue;
+                    if (!seen(c.row)) take(found++, c);
+                }
+            }
+        }
+        cnt[i] = found;
+    }
+}
+
+template <int DIR, bool CAP>
+ivx_status nearest_probe_dir_t(ivx_ctx *ctx, const ivx_index *ix, const u32 *key, const i32 *s, const i32 *e, u64 n, int strict, u32 k,
+                               int include_overlaps, i64 D, u32 *ob, u32 *op, i64 *od, u64 cap, u64 *rows)
+{
+    hipStream_t st = ctx->stream;
+    if (k == 1) {
+        if (cap < n) { *rows = n; return ctx->fail(IVX_ERR_CAPACITY, "nearest: output buffers too small"); }
+        // the switch point and its override are ivx_nearest_probe's
+        bool routed = ix->nroute_nreg > 0 && n >= (1u << 21);
+        if (const char *f = getenv("IVX_NEAREST_PATH")) routed = !strcmp(f, "routed") ? ix->nroute_nreg > 0 : (!strcmp(f, "direct") ? false : routed);
+        if (routed) {
+            ivx_routed R;
+            IVX_TRY(ivx_route_rows(ctx, ix->nroute, key, s, e, n, strict ? 1u : 0u, &R));
+            u32 *vb; i64 *vd = nullptr;
+            IVX_TRY(ctx->get_scratch(WS_T2, n * sizeof(u32), (void **)&vb));
+            if (od) IVX_TRY(ctx->get_scratch(WS_T3, n * sizeof(i64), (void **)&vd));
+            hipLaunchKernelGGL((k_nearest_routed_dir<DIR, CAP>), dim3((ivx_stream_grid(n, NR_T * 4, 1280u) + 7u) & ~7u), dim3(NR_T), 0, st, ix->nv, ix->nroute.rkey,
+                               ix->nroute_nreg, R.se, R.rfirst, R.nblk, strict ? 1u : 0u, include_overlaps, D, vb, vd, R.unsorted);
+            IVX_TRY(ivx_unroute_pair(ctx, R, n, vb, vd, ob, op, od, -1));
+            // rows that came in region order were not moved: the direct kernel answers them in place
+            hipLaunchKernelGGL((k_probe_nearest1_dir<DIR, CAP>), dim3(ivx_stream_grid(n, OT * 4)), dim3(OT), 0, st, ix->nv, key, s, e, n, strict, include_overlaps, D,
+                               ob, op, od, R.unsorted);
+        } else {
+            hipLaunchKernelGGL((k_probe_nearest1_dir<DIR, CAP>), dim3(ivx_stream_grid(n, OT)), dim3(OT), 0, st, ix->nv, key, s, e, n, strict, include_overlaps, D,
+                               ob, op, od, (const u32 *)nullptr);
+        }
+        IVX_HIP(ctx, hipGetLastError());
+        *rows = n;
+        return IVX_OK;
+    }
+    u32 *tmp, *cnt; u64 *offs; i64 *tmpd = nullptr;
+    IVX_TRY(ctx->get_scratch(WS_T2, n * (u64)k * sizeof(u32), (void **)&tmp));
+    if (od) IVX_TRY(ctx->get_scratch(WS_T5, n * (u64)k * sizeof(i64), (void **)&tmpd));
+    IVX_TRY(ctx->get_scratch(WS_T3, n * sizeof(u32), (void **)&cnt));
+    IVX_TRY(ctx->get_scratch(WS_T4, (n + 1) * sizeof(u64), (void **)&offs));
+    hipLaunchKernelGGL((k_probe_nearestk_dir<DIR, CAP>), dim3(ivx_stream_grid(n, OT * 2)), dim3(OT), 0, st, ix->nv, key, s, e, n, strict, include_overlaps, k, D, tmp, tmpd, cnt);
+    hipLaunchKernelGGL(k_rows_of, dim3(grid1(n + 1)), dim3(OT), 0, st, (const u32 *)cnt, n, offs);
+    IVX_TRY(ivx_scan_exclusive_u64(ctx, offs, n + 1));
+    u64 total;
+    IVX_TRY(ctx->fetch_wait((const u64 *)offs + n, st, &total));
+    *rows = total;
+    if (total > cap) return ctx->fail(IVX_ERR_CAPACITY, "nearest: output buffers too small");
+    hipLaunchKernelGGL(k_nearest_emit, dim3(ivx_stream_grid(n, OT * 2)), dim3(OT), 0, st, n, k, (const u32 *)tmp, (const i64 *)tmpd, (const u32 *)cnt, (const u64 *)offs, cap, ob, op, od);
+    IVX_HIP(ctx, hipGetLastError());
+    return IVX_OK;
+}
+
+}  // namespace
+
+ivx_status ivx_nearest_probe_dir(ivx_ctx *ctx, const ivx_index *ix, const u32 *key, const i32 *s, const i32 *e, u64 n,
+                                 int strict, u32 k, int include_overlaps, int direction, i64 max_distance,
+                                 u32 *ob, u32 *op, i64 *od, u64 cap, u64 *rows)
+{
+    // no candidate stream to restrict (k == 0: one NULL row per probe row), or nothing that restricts it
+    if (k == 0 || (direction == IVX_NEAR_ANY && max_distance < 0)) return ivx_nearest_probe(ctx, ix, key, s, e, n, strict, k, include_overlaps, ob, op, od, cap, rows);
+    *rows = 0;
+    if (n == 0) return IVX_OK;
+    const bool capped = max_distance >= 0;
+#define IVX_NEAR_RUN(DIR, CAP) nearest_probe_dir_t<DIR, CAP>(ctx, ix, key, s, e, n, strict, k, include_overlaps, max_distance, ob, op, od, cap, rows)
+    switch (direction) {
+        case IVX_NEAR_ANY: return IVX_NEAR_RUN(IVX_NEAR_ANY, true);
+        case IVX_NEAR_BEFORE: return capped ? IVX_NEAR_RUN(IVX_NEAR_BEFORE, true) : IVX_NEAR_RUN(IVX_NEAR_BEFORE, false);
+        case IVX_NEAR_AFTER: return capped ? IVX_NEAR_RUN(IVX_NEAR_AFTER, true) : IVX_NEAR_RUN(IVX_NEAR_AFTER, false);
+        default: return ctx->fail(IVX_ERR_INVALID, "nearest: direction must be IVX_NEAR_ANY, IVX_NEAR_BEFORE or IVX_NEAR_AFTER");
+    }
+#undef IVX_NEAR_RUN
+}

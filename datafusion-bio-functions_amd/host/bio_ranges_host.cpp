@@ -4,6 +4,7 @@
 #include "../../include/ivx.h"
 #include "../../include/ivx_select.h"
 #include "../../include/ivx_where.h"
+#include "../../include/ivx_nearest.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -493,10 +494,20 @@ extern "C" int brh_count_overlaps(brh_session *s, brh_batch left, brh_columns lc
     return 0;
 }
 
+// brh_nearest is brh_nearest_dir on either side and without a cap (ivx_probe_nearest_dir is ivx_probe_nearest then)
 extern "C" int brh_nearest(brh_session *s, brh_batch left, brh_columns lcols, brh_batch right, brh_columns rcols,
                            int filter_op, uint32_t k, int include_overlaps, int compute_distance,
                            ArrowArray *left_idx, ArrowSchema *left_idx_schema, ArrowArray *right_idx, ArrowSchema *right_idx_schema,
                            ArrowArray *distance, ArrowSchema *distance_schema)
+{
+    return brh_nearest_dir(s, left, lcols, right, rcols, filter_op, k, include_overlaps, compute_distance, BRH_NEAR_ANY, -1,
+                           left_idx, left_idx_schema, right_idx, right_idx_schema, distance, distance_schema);
+}
+
+extern "C" int brh_nearest_dir(brh_session *s, brh_batch left, brh_columns lcols, brh_batch right, brh_columns rcols,
+                               int filter_op, uint32_t k, int include_overlaps, int compute_distance, int direction, int64_t max_distance,
+                               ArrowArray *left_idx, ArrowSchema *left_idx_schema, ArrowArray *right_idx, ArrowSchema *right_idx_schema,
+                               ArrowArray *distance, ArrowSchema *distance_schema)
 {
     if (!s) return 1;
     KeyDict kd; Side32 L, R;
@@ -509,8 +520,8 @@ extern "C" int brh_nearest(brh_session *s, brh_batch left, brh_columns lcols, br
     std::vector<uint32_t> bi(cap ? cap : 1), pi(cap ? cap : 1);
     std::vector<int64_t> di(compute_distance ? (cap ? cap : 1) : 0);
     uint64_t rows = 0;
-    st = ivx_probe_nearest(s->ctx, g.ix, IVX_MEM_HOST, kd.ids[1].data(), R.s.data(), R.e.data(), R.s.size(), filter_op == BRH_STRICT, k,
-                           include_overlaps, bi.data(), pi.data(), compute_distance ? di.data() : nullptr, cap, &rows);
+    st = ivx_probe_nearest_dir(s->ctx, g.ix, IVX_MEM_HOST, kd.ids[1].data(), R.s.data(), R.e.data(), R.s.size(), filter_op == BRH_STRICT, k,
+                               include_overlaps, direction, max_distance, bi.data(), pi.data(), compute_distance ? di.data() : nullptr, cap, &rows);
     if (st != IVX_OK) return fail_ivx(s, st);
     std::vector<uint8_t> valid(rows ? rows : 1);
     for (uint64_t i = 0; i < rows; i++) { valid[i] = bi[i] != IVX_NULL_IDX; if (!valid[i]) bi[i] = 0; }   // nearest.rs:378-379

@@ -45,6 +45,12 @@ EXT_SYMBOLS = ["ivx_probe_overlap_select"]
 # their own
 WHERE_SYMBOLS = ["ivx_probe_overlap_count_where", "ivx_probe_mark_build_where", "ivx_probe_overlap_agg_where",
                  "ivx_probe_overlap_select_where", "ivx_pairs_where"]
+# every symbol include/ivx_nearest.h declares (checked by tests/test_nearest_dir_abi.py): nearest on one side only and / or
+# within a distance cap, a list of its own
+NEAREST_SYMBOLS = ["ivx_probe_nearest_dir"]
+# directions of ivx_probe_nearest_dir, in the order of the IVX_NEAR_* enum (include/ivx_nearest.h), and their aliases
+NEAR_DIRECTIONS = ("any", "before", "after")
+NEAR_ALIASES = {"upstream": "before", "downstream": "after"}
 # pairs per tile of ivx_pairs_where's two passes (csrc/ivx_where.hpp PW_TILE = PW_T * PW_PI; tests/test_gpu_overlap_where.py)
 PAIRS_WHERE_TILE = 1024
 
@@ -240,6 +246,8 @@ def lib():
         L.ivx_probe_overlap_select_where.argtypes = head + [C.c_void_p, C.c_uint32, C.c_int, W] + [C.c_void_p] * 2
         L.ivx_pairs_where.argtypes = ([C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64,
                                        C.c_void_p, C.c_void_p, C.c_uint64, W, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)])
+        L.ivx_probe_nearest_dir.restype = C.c_int
+        L.ivx_probe_nearest_dir.argtypes = head + [C.c_int, C.c_uint32, C.c_int, C.c_int, C.c_int64] + [C.c_void_p] * 3 + [C.c_uint64, C.POINTER(C.c_uint64)]
         L.ivx_depth.argtypes = ([C.c_void_p, C.c_int] + [C.c_void_p] * 6 + [C.c_uint64] + [C.c_void_p] * 4 + [C.c_uint64] +
                                 [C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32] + [C.c_void_p] * 4 +
                                 [C.c_uint64, C.POINTER(C.c_uint64)])
@@ -1015,6 +1023,33 @@ class Ctx:
         self._chk(lib().ivx_probe_nearest(self.h, ix.h, C.c_int(mem), _ptr(key), _ptr(s), _ptr(e), C.c_uint64(n),
                                            C.c_int(int(strict)), C.c_uint32(int(k)), C.c_int(int(overlap)),
                                            _ptr(ob), _ptr(op), _ptr(od), C.c_uint64(cap), C.byref(rows)))
+        r = rows.value
+        return ob[:r], op[:r], (od[:r] if distance else None)
+
+    # ---- a6': one side only and / or within a distance cap (include/ivx_nearest.h) ----
+    def nearest_dir(self, ix, key, start, end, k=1, overlap=True, strict=False, distance=True, direction="any", max_distance=None):
+        """nearest() restricted to build rows that end before the probe row ("before" / "upstream") or start after it ("after" /
+        "downstream"), and / or to build rows no farther than max_distance (None: no cap).  Direction does not touch
+        overlapping rows: `overlap` alone decides them.  direction="any" without a cap is nearest()."""
+        d = NEAR_ALIASES.get(direction, direction)
+        if d not in NEAR_DIRECTIONS:
+            raise ValueError(f"direction must be one of {NEAR_DIRECTIONS + tuple(NEAR_ALIASES)}, got {direction!r}")
+        if max_distance is not None and int(max_distance) < 0:
+            raise ValueError(f"max_distance must be >= 0 or None, got {max_distance!r}")
+        key, s, e, n, mem = _cols(key, start, end, np.int32)
+        cap = n * max(int(k), 1)
+        if mem == MEM_DEVICE:
+            import torch
+            ob = torch.empty(max(cap, 1), dtype=torch.int32, device=s.device)
+            op = torch.empty(max(cap, 1), dtype=torch.int32, device=s.device)
+            od = torch.empty(max(cap, 1), dtype=torch.int64, device=s.device) if distance else None
+        else:
+            ob = np.empty(max(cap, 1), np.uint32); op = np.empty(max(cap, 1), np.uint32)
+            od = np.empty(max(cap, 1), np.int64) if distance else None
+        rows = C.c_uint64(0)
+        self._chk(lib().ivx_probe_nearest_dir(self.h, ix.h, mem, _ptr(key), _ptr(s), _ptr(e), n, int(strict), int(k), int(overlap),
+                                               NEAR_DIRECTIONS.index(d), -1 if max_distance is None else int(max_distance),
+                                               _ptr(ob), _ptr(op), _ptr(od), cap, C.byref(rows)))
         r = rows.value
         return ob[:r], op[:r], (od[:r] if distance else None)
 

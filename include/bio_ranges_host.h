@@ -85,6 +85,18 @@ int brh_nearest(brh_session *s, brh_batch left, brh_columns lcols, brh_batch rig
                 struct ArrowArray *right_idx, struct ArrowSchema *right_idx_schema,
                 struct ArrowArray *distance, struct ArrowSchema *distance_schema);
 
+/* nearest on one side only and / or within a distance cap (ivx_nearest.h ivx_probe_nearest_dir): brh_nearest plus
+ * direction = BRH_NEAR_ANY | BRH_NEAR_BEFORE (only left rows that end before the right row: "upstream") | BRH_NEAR_AFTER
+ * (only left rows that start after it: "downstream") and max_distance (< 0: no cap; else no left row farther than that is
+ * an answer, and a right row without one gets the NULL row).  Direction does not touch overlapping rows: include_overlaps
+ * alone decides them.  BRH_NEAR_ANY with max_distance < 0 is brh_nearest.  Another direction is refused. */
+enum { BRH_NEAR_ANY = 0, BRH_NEAR_BEFORE = 1, BRH_NEAR_AFTER = 2 };
+int brh_nearest_dir(brh_session *s, brh_batch left, brh_columns lcols, brh_batch right, brh_columns rcols,
+                    int filter_op, uint32_t k, int include_overlaps, int compute_distance, int direction, int64_t max_distance,
+                    struct ArrowArray *left_idx, struct ArrowSchema *left_idx_schema,
+                    struct ArrowArray *right_idx, struct ArrowSchema *right_idx_schema,
+                    struct ArrowArray *distance, struct ArrowSchema *distance_schema);
+
 /* IntervalJoinExec (interval_join.rs:442-550, :1418-1677): `build` is the SQL join's left side.
  * strict_predicate = the planner's `<`/`>` rewrite: both sides' END minus one (intervals.rs:85-115).
  * nearest_algorithm != 0 = Algorithm::CoitreesNearest (one row per probe row, NULL build index when
