@@ -498,6 +498,101 @@ def probe_overlap_agg(E, M, n):
     return res
 
 
+SEL_CASE_BY = ("max_val", "min_overlap", "last_row")
+
+
+def _family_in(E, M, n):
+    """what the select and threshold cases share: probe_overlap_agg's rows, a small int64 value per build row (many ties),
+    and the head of the call"""
+    k, s, e = (M.put(a) for a in ivals(n, 29, span=4000))
+    val = M.put(np.random.default_rng(30).integers(-5, 6, E.n_build).astype(np.int64))
+    return (k, s, e, val), (E.ix[0].h, M.mem, k.p, s.p, e.p, u64(n))
+
+
+def _where():
+    """min_bases 10 and half of the probe row"""
+    return pyivx.OverlapWhereC(10, 1, 2, 0, 0, 0)
+
+
+@case
+def probe_overlap_select(E, M, n):
+    """both outputs, three criteria: the value, the overlap length, the last row"""
+    (k, s, e, val), head = _family_in(E, M, n)
+    res = {}
+    for by in SEL_CASE_BY:
+        bi, sc = M.out(n, np.uint32), M.out(n, np.int64)
+        res["st." + by] = E.call("ivx_probe_overlap_select", *head, val.p, u32(8), cint(pyivx.SEL_BY.index(by)), bi.p, sc.p, outs=[bi, sc])
+        res["idx." + by], res["score." + by] = bi.np()[:n], sc.np()[:n]
+    return res
+
+
+@case
+def probe_overlap_count_where(E, M, n):
+    """all three outputs; then the total alone, whose per-row counts live in scratch and go through the device reduction"""
+    (k, s, e, val), head = _family_in(E, M, n)
+    w = _where()
+    res = {}
+    pr, ex, tot = M.out(n, np.uint32), M.out(n, np.uint8), u64(0xDEAD)
+    res["st.count"] = E.call("ivx_probe_overlap_count_where", *head, C.byref(w), pr.p, ex.p, C.byref(tot), outs=[pr, ex], count=tot)
+    res["per_row"], res["exists"], res["total"] = pr.np()[:n], ex.np()[:n], tot.value
+    tot2 = u64(0xDEAD)
+    res["st.total"] = E.call("ivx_probe_overlap_count_where", *head, C.byref(w), None, None, C.byref(tot2), count=tot2)
+    res["total2"] = tot2.value
+    return res
+
+
+@case
+def probe_mark_build_where(E, M, n):
+    (k, s, e, val), head = _family_in(E, M, n)
+    w = _where()
+    mine = np.zeros((E.n_build + 31) // 32, np.uint32)
+    mine[::3] = 0x00010001                                  # bits the caller had set: they survive
+    marks = M.put(mine)
+    st = E.call("ivx_probe_mark_build_where", *head, C.byref(w), marks.p, outs=[(marks, mine)])
+    got = marks.np()
+    assert ((got & mine) == mine).all()
+    return {"st.marks": st, "marks": got}
+
+
+@case
+def probe_overlap_agg_where(E, M, n):
+    (k, s, e, val), head = _family_in(E, M, n)
+    w = _where()
+    outs = [M.out(n, dt) for dt in AGG_DTS]
+    res = {"st.agg": E.call("ivx_probe_overlap_agg_where", *head, val.p, u32(8), C.byref(w), *[o.p for o in outs], outs=outs)}
+    res.update({"agg." + name: o.np()[:n] for name, o in zip(pyivx.AGG_OUTPUTS, outs)})
+    return res
+
+
+@case
+def probe_overlap_select_where(E, M, n):
+    (k, s, e, val), head = _family_in(E, M, n)
+    w = _where()
+    bi, sc = M.out(n, np.uint32), M.out(n, np.int64)
+    st = E.call("ivx_probe_overlap_select_where", *head, val.p, u32(8), cint(pyivx.SEL_BY.index("max_overlap")), C.byref(w), bi.p, sc.p,
+                outs=[bi, sc])
+    return {"st.select": st, "idx": bi.np()[:n], "score": sc.np()[:n]}
+
+
+@case
+def pairs_where(E, M, n):
+    """the pair filter over n pairs of (row i of the build's first n rows, probe row i): sizing, fill, one short"""
+    (k, s, e, val), head = _family_in(E, M, n)
+    w = _where()
+    bsd, bed = M.put(E.build_cols[1][:max(n, 1)]), M.put(E.build_cols[2][:max(n, 1)])
+    ids = M.put(np.arange(n, dtype=np.uint32))
+    res = {}
+
+    def call(cap, bufs):
+        ob, op, m = M.out(cap, np.uint32), M.out(cap, np.uint32), u64(0xDEAD)
+        give = bufs and cap > 0                               # (output columns without capacity are refused)
+        st = E.call("ivx_pairs_where", M.mem, ids.p, ids.p, u64(n), bsd.p, bed.p, u64(n), s.p, e.p, u64(n), C.byref(w),
+                    ob.p if give else None, op.p if give else None, u64(cap), C.byref(m), outs=[ob, op], count=m)
+        return st, m.value, [ob, op]
+    sized(res, "pairs", call)
+    return res
+
+
 @case
 def bits_mark(E, M, n):
     rng = np.random.default_rng(8)
@@ -555,6 +650,49 @@ def probe_nearest(E, M, n):
                 outs=[b, p, d], count=rows)
     r = rows.value
     return {"st": st, "rows": r, "b": b.np()[:r], "p": p.np()[:r], "d": d.np()[:r]}
+
+
+# (direction, include_overlaps, max_distance) of the nearest_dir cases: each side with and without overlaps, without a cap and
+# within 32; both sides within 32.  ("any" without a cap is ivx_probe_nearest: the case above.)
+NEAR_DIR_CALLS = [(d, ovl, D) for d in ("before", "after") for ovl in (1, 0) for D in (-1, 32)] + [("any", 1, 32)]
+
+
+def near_dir_tag(d, ovl, D):
+    return f"{d}.ovl{ovl}.d{D}"
+
+
+def nearest_dir_calls(E, M, n, k):
+    """ivx_probe_nearest_dir for every NEAR_DIR_CALLS on probe_nearest's rows, k answers a row at the most"""
+    ks, s, e = (M.put(a) for a in ivals(n, 11))
+    cap = k * n
+    res = {}
+    for d, ovl, D in NEAR_DIR_CALLS:
+        b, p, dist = M.out(cap, np.uint32), M.out(cap, np.uint32), M.out(cap, np.int64)
+        rows = u64(0xDEAD)
+        st = E.call("ivx_probe_nearest_dir", E.ix[3].h, M.mem, ks.p, s.p, e.p, u64(n), cint(0), u32(k), cint(ovl),
+                    cint(pyivx.NEAR_DIRECTIONS.index(d)), i64(D), b.p, p.p, dist.p, u64(cap), C.byref(rows), outs=[b, p, dist], count=rows)
+        r, tag = rows.value, near_dir_tag(d, ovl, D)
+        res.update({tag + ".st": st, tag + ".rows": r, tag + ".b": b.np()[:r], tag + ".p": p.np()[:r], tag + ".d": dist.np()[:r]})
+    return res
+
+
+def nearest_dir_want(oix, n, k):
+    """tag -> (build rows, probe rows, distances) that nearest_dir_calls must give, from the restatement `oix`
+    (tests/nearest_dir_oracle.NearIndex over the Env's build columns)"""
+    p = ivals(n, 11)
+    return {near_dir_tag(d, ovl, D): oix.query(*p, k=k, overlap=bool(ovl), direction=d, max_distance=None if D < 0 else D)
+            for d, ovl, D in NEAR_DIR_CALLS}
+
+
+def assert_nearest_dir(got, want, what):
+    for tag, (wb, wp, wd) in want.items():
+        assert got[tag + ".st"] == OK and got[tag + ".rows"] == len(wb), (what, tag, got[tag + ".st"], got[tag + ".rows"], len(wb))
+        assert (got[tag + ".b"] == wb).all() and (got[tag + ".p"] == wp).all() and (got[tag + ".d"] == wd).all(), (what, tag)
+
+
+@case
+def probe_nearest_dir(E, M, n):
+    return nearest_dir_calls(E, M, n, 2)
 
 
 @case

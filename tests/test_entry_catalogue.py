@@ -1,7 +1,8 @@
-"""No GPU: the catalogue every entry walk iterates over (entry_cases.CASES) cannot fall behind the header.  Every ivx_*
-function include/ivx.h declares is either the target of a catalogue case -- the case `name` calls `ivx_` + name -- or stands
+"""No GPU: the catalogue every entry walk iterates over (entry_cases.CASES) cannot fall behind the headers.  Every ivx_*
+function include/ivx.h or a companion header include/ivx_*.h declares is either the target of a catalogue case -- the case `name` calls `ivx_` + name -- or stands
 in NO_COLUMNS below, the entries that take no column of the caller's and so have nothing to stage, refuse or copy back.
-Adding an entry to the header without a case (or without a reason here) fails this test."""
+Adding an entry to a header, or a companion header with entries, without a case (or without a reason here) fails this test."""
+import glob
 import os
 import re
 
@@ -36,20 +37,40 @@ NO_COLUMNS = {
 DECL = re.compile(r"^(?:ivx_status|void|uint64_t|double|const char \*)\s*\*?(ivx_\w+)\(", re.M)
 
 
+def headers():
+    """include/ivx.h and every companion header beside it"""
+    inc = os.path.join(ROOT, "include")
+    return [os.path.join(inc, "ivx.h")] + sorted(glob.glob(os.path.join(inc, "ivx_*.h")))
+
+
+def code_of(path):
+    with open(path) as f:
+        return re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)        # (comments name entries, too)
+
+
 def declared():
-    with open(os.path.join(ROOT, "include", "ivx.h")) as f:
-        text = f.read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)              # (comments name entries, too)
-    return sorted(set(DECL.findall(text)))
+    return sorted({name for h in headers() for name in DECL.findall(code_of(h))})
+
+
+COMPANIONS = {
+    "ivx_select.h": ["ivx_probe_overlap_select"],
+    "ivx_where.h": ["ivx_pairs_where", "ivx_probe_mark_build_where", "ivx_probe_overlap_agg_where", "ivx_probe_overlap_count_where",
+                    "ivx_probe_overlap_select_where"],
+    "ivx_nearest.h": ["ivx_probe_nearest_dir"],
+}
 
 
 def test_the_header_parses():
     names = declared()
-    assert len(names) >= 57 and "ivx_ctx_create" in names and "ivx_take_view" in names, names
-    # every `ivx_x(` of the header outside comments and macros is one of them: the pattern misses no return type
-    with open(os.path.join(ROOT, "include", "ivx.h")) as f:
-        text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
-    assert sorted(set(re.findall(r"\b(ivx_\w+)\(", text))) == names
+    assert len(names) >= 57 + 7 and "ivx_ctx_create" in names and "ivx_take_view" in names, names
+    assert len(headers()) >= 4, headers()
+    # every `ivx_x(` of a header outside comments and macros is a declaration: the pattern misses no return type
+    for h in headers():
+        text = code_of(h)
+        mine = sorted(set(DECL.findall(text)))
+        assert sorted(set(re.findall(r"\b(ivx_\w+)\(", text))) == mine, h
+        if os.path.basename(h) in COMPANIONS:
+            assert mine == COMPANIONS[os.path.basename(h)], h
 
 
 def test_every_declared_entry_has_a_case_or_a_reason():
@@ -58,6 +79,6 @@ def test_every_declared_entry_has_a_case_or_a_reason():
     assert not cases & set(NO_COLUMNS)
     assert all(NO_COLUMNS.values())
     stale = sorted((cases | set(NO_COLUMNS)) - set(names))
-    assert not stale, f"not declared in include/ivx.h: {stale}"
+    assert not stale, f"declared in no header under include/: {stale}"
     missing = sorted(set(names) - cases - set(NO_COLUMNS))
-    assert not missing, f"declared in include/ivx.h, no case in tests/entry_cases.py and no reason in NO_COLUMNS: {missing}"
+    assert not missing, f"declared under include/, no case in tests/entry_cases.py and no reason in NO_COLUMNS: {missing}"

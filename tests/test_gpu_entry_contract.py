@@ -63,7 +63,8 @@ class Args:
         self.src = H.put(np.arange(64, dtype=np.int64))
         self.bits = H.put(np.zeros(8, np.uint8))
         self.views = H.put(np.zeros(32 * 16, np.uint8))            # 32 empty strings
-        self.val = H.put(np.arange(E.n_build, dtype=np.int64))     # overlap_agg: one value per build row
+        self.val = H.put(np.arange(E.n_build, dtype=np.int64))     # overlap_agg, overlap_select: one value per build row
+        self.w = pyivx.OverlapWhereC(10, 1, 2, 0, 0, 0)             # the *_where entries: min_bases 10, half of the probe row
         self.o = [H.out(64, np.int64) for _ in range(8)]       # outputs: enough bytes for any column of 8 rows
         self.count = u64(0)
         self.handle = C.c_void_p()
@@ -86,6 +87,14 @@ class Args:
             "ivx_probe_exists": [E.ix[0].h, H, *cols, o[0]],
             "ivx_probe_mark_build": [E.ix[0].h, H, *cols, o[0]],
             "ivx_probe_overlap_agg": [E.ix[0].h, H, *cols, self.val.p, u32(8), *o[:6]],
+            "ivx_probe_overlap_select": [E.ix[0].h, H, *cols, self.val.p, u32(8), cint(1), o[0], o[1]],
+            "ivx_probe_overlap_count_where": [E.ix[0].h, H, *cols, C.byref(self.w), o[0], o[1], cnt],
+            "ivx_probe_mark_build_where": [E.ix[0].h, H, *cols, C.byref(self.w), o[0]],
+            "ivx_probe_overlap_agg_where": [E.ix[0].h, H, *cols, self.val.p, u32(8), C.byref(self.w), *o[:6]],
+            "ivx_probe_overlap_select_where": [E.ix[0].h, H, *cols, self.val.p, u32(8), cint(1), C.byref(self.w), o[0], o[1]],
+            "ivx_pairs_where": [H, self.idx.p, self.idx.p, u64(n), self.s.p, self.e.p, u64(n), self.s.p, self.e.p, u64(n), C.byref(self.w),
+                                o[0], o[1], u64(64), cnt],
+            "ivx_probe_nearest_dir": [E.ix[3].h, H, *cols, cint(0), u32(1), cint(1), cint(1), i64(10), o[0], o[1], o[2], u64(n), cnt],
             "ivx_bits_mark": [H, self.idx.p, u64(n), o[0], u64(64)],
             "ivx_bits_select": [H, self.bits.p, u64(64), cint(1), o[0], u64(64), cnt],
             "ivx_probe_count": [E.ix[1].h, H, *cols, cint(0), o[0]],
@@ -127,6 +136,8 @@ BAD_MEM = (INVALID, "bad mem")
 ALIGN = (INVALID, "depth profile: output pointer not aligned to its element size")
 ALIGN_ANY = (INVALID, "depth profile: pointer not aligned to its element size")      # quantize and hist check key_hi as well
 DESCENDING = np.array([3, 1], np.int32)                                                # cuts are host memory in both modes
+NEGATIVE_W = pyivx.OverlapWhereC(-1, 0, 0, 0, 0, 0)                                    # thresholds (host structs in both modes) that break a rule
+ABOVE_ONE_W = pyivx.OverlapWhereC(0, 3, 2, 0, 0, 0)
 
 # (entry, {argument position after ctx: bad value}) -> (status, ivx_last_error), the texts as csrc/ivx_capi.hip has them
 ERRORS = [
@@ -225,6 +236,42 @@ ERRORS = [
     ("ivx_probe_overlap_agg", {1: MEM2, 7: u32(3)}, BAD_MEM),
     ("ivx_depth_profile_quantize", {1: 2, 7: 32}, BAD_MEM),
     ("ivx_depth_profile_hist", {1: DEVICE, 7: 0, 8: ODD}, (INVALID, "depth profile: n_bins outside 1 .. 65536")),
+    # ---- the entries of the companion headers (include/ivx_select.h, ivx_where.h, ivx_nearest.h)
+    # mem = 2
+    ("ivx_probe_overlap_select", {1: MEM2}, BAD_MEM), ("ivx_probe_overlap_count_where", {1: MEM2}, BAD_MEM),
+    ("ivx_probe_mark_build_where", {1: MEM2}, BAD_MEM), ("ivx_probe_overlap_agg_where", {1: MEM2}, BAD_MEM),
+    ("ivx_probe_overlap_select_where", {1: MEM2}, BAD_MEM), ("ivx_pairs_where", {0: MEM2}, BAD_MEM), ("ivx_probe_nearest_dir", {1: MEM2}, BAD_MEM),
+    # a null required column
+    ("ivx_probe_overlap_select", {3: None}, (INVALID, "null coordinate column")),
+    ("ivx_probe_overlap_select", {9: None}, (INVALID, "overlap_select: null build_idx")),
+    ("ivx_probe_overlap_select", {6: None}, (INVALID, "overlap_select: null value column")),
+    ("ivx_probe_overlap_count_where", {4: None}, (INVALID, "null coordinate column")),
+    ("ivx_probe_mark_build_where", {7: None}, (INVALID, "null mark bitmap")),
+    ("ivx_probe_overlap_agg_where", {6: None}, (INVALID, "overlap_agg: null value column")),
+    ("ivx_probe_overlap_select_where", {10: None}, (INVALID, "overlap_select: null build_idx")),
+    ("ivx_pairs_where", {1: None}, (INVALID, "pairs_where: null pair columns")),
+    ("ivx_pairs_where", {8: None}, (INVALID, "pairs_where: null coordinate column")),
+    ("ivx_pairs_where", {11: None}, (INVALID, "pairs_where: null output columns")),
+    ("ivx_probe_nearest_dir", {3: None}, (INVALID, "null coordinate column")),
+    ("ivx_probe_nearest_dir", {11: None}, (INVALID, "null output column")),
+    # the null count word
+    ("ivx_pairs_where", {14: None}, (INVALID, "pairs_where: null n_out")), ("ivx_probe_nearest_dir", {15: None}, (INVALID, "null rows")),
+    # no output wanted; val_bytes = 3, an unknown criterion; a direction of 3; a threshold that breaks a rule
+    ("ivx_probe_overlap_count_where", {7: None, 8: None, 9: None}, (INVALID, "overlap_count_where: no output wanted")),
+    ("ivx_probe_overlap_agg_where", {9: None, 10: None, 11: None, 12: None, 13: None, 14: None}, (INVALID, "overlap_agg: no output wanted")),
+    ("ivx_probe_overlap_select", {7: u32(3)}, (INVALID, "overlap_select: val_bytes is 4 or 8")),
+    ("ivx_probe_overlap_select", {8: cint(6)}, (INVALID, "overlap_select: unknown criterion")),
+    ("ivx_probe_overlap_select_where", {8: cint(-1)}, (INVALID, "overlap_select: unknown criterion")),
+    ("ivx_probe_nearest_dir", {9: cint(3)}, (INVALID, "nearest: direction must be IVX_NEAR_ANY, IVX_NEAR_BEFORE or IVX_NEAR_AFTER")),
+    ("ivx_probe_nearest_dir", {9: cint(3), 10: i64(-1)}, (INVALID, "nearest: direction must be IVX_NEAR_ANY, IVX_NEAR_BEFORE or IVX_NEAR_AFTER")),
+    ("ivx_probe_mark_build_where", {6: C.byref(NEGATIVE_W)}, (INVALID, "overlap_where: min_bases is negative")),
+    ("ivx_pairs_where", {10: C.byref(ABOVE_ONE_W)}, (INVALID, "overlap_where: a fraction is above 1 (num > den)")),
+    # two bad arguments at once: which message wins
+    ("ivx_probe_overlap_agg_where", {1: MEM2, 7: u32(3)}, BAD_MEM),
+    ("ivx_probe_overlap_count_where", {6: C.byref(NEGATIVE_W), 7: None, 8: None, 9: None}, (INVALID, "overlap_where: min_bases is negative")),
+    ("ivx_probe_overlap_select_where", {7: u32(3), 9: C.byref(NEGATIVE_W)}, (INVALID, "overlap_where: min_bases is negative")),
+    ("ivx_pairs_where", {0: MEM2, 14: None}, (INVALID, "pairs_where: null n_out")),
+    ("ivx_probe_nearest_dir", {1: MEM2, 9: cint(3)}, BAD_MEM),
 ]
 
 

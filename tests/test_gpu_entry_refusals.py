@@ -9,7 +9,7 @@ so no hook is needed: trim, set the limit to L0 = what the live indexes take, ru
 (below), raise the limit to R + B and go again, until the case runs through -- with the tightest limit that suffices, where
 no reservation got its 1/8 slack -- and equals the never-limited baseline bit for bit.
 
-R1  every catalogue case (entry_cases.py) and probe_nearest_k1, host and device mode, the default paths and every forced
+R1  every catalogue case (entry_cases.py), probe_nearest_k1 and probe_nearest_dir_k1, host and device mode, the default paths and every forced
     path of test_gpu_entry_state.KNOBS, on the designed 200 000-row build (region and lean forms).  After each refused
     attempt, the limit still set: only OK / OOM / CAPACITY / INVALID statuses and a clean ivx_ctx_synchronize; the refused
     call's out-handle is NULL and its count 0 or the baseline's; in host mode its output buffers are untouched; the output
@@ -54,6 +54,10 @@ Refusal points met per (case, knobs, mode), copied from one run; a row changes w
     index_build                       join_path=regions+rowval_path=regions            66      65
     intersect                         default                                          70      50
     merge                             default                                          30      16
+    pairs_where                       default                                          20       3
+    pairs_where                       join_path=direct                                 20       3
+    pairs_where                       join_path=regions                                20       3
+    pairs_where                       join_path=regions+part=two                       20       3
     probe_count                       default                                           7       0
     probe_count                       part=two+rowval_path=regions                     15       7
     probe_count                       rowval_path=direct                                7       0
@@ -72,7 +76,15 @@ Refusal points met per (case, knobs, mode), copied from one run; a row changes w
     probe_mark_build                  join_path=direct                                  7       0
     probe_mark_build                  join_path=regions                                14       6
     probe_mark_build                  join_path=regions+part=two                        7       0
+    probe_mark_build_where            default                                           7       0
+    probe_mark_build_where            join_path=direct                                  7       0
+    probe_mark_build_where            join_path=regions                                14       6
+    probe_mark_build_where            join_path=regions+part=two                        7       0
     probe_nearest                     default                                          19       7
+    probe_nearest_dir                 default                                          19       7
+    probe_nearest_dir_k1              default                                          11       0
+    probe_nearest_dir_k1              nearest_path=direct                              11       0
+    probe_nearest_dir_k1              nearest_path=routed                              21       9
     probe_nearest_k1                  default                                          11       0
     probe_nearest_k1                  nearest_path=direct                              11       0
     probe_nearest_k1                  nearest_path=routed                              21       9
@@ -80,14 +92,30 @@ Refusal points met per (case, knobs, mode), copied from one run; a row changes w
     probe_overlap_agg                 join_path=direct                                 18       0
     probe_overlap_agg                 join_path=regions                                29      10
     probe_overlap_agg                 join_path=regions+part=two                       18       0
+    probe_overlap_agg_where           default                                          18       0
+    probe_overlap_agg_where           join_path=direct                                 18       0
+    probe_overlap_agg_where           join_path=regions                                29      10
+    probe_overlap_agg_where           join_path=regions+part=two                       18       0
     probe_overlap_count               default                                           7       0
     probe_overlap_count               join_path=direct                                  7       0
     probe_overlap_count               join_path=regions                                15       7
     probe_overlap_count               join_path=regions+part=two                       15       7
+    probe_overlap_count_where         default                                          11       1
+    probe_overlap_count_where         join_path=direct                                 11       1
+    probe_overlap_count_where         join_path=regions                                20      10
+    probe_overlap_count_where         join_path=regions+part=two                       11       1
     probe_overlap_fill                default                                           9       0
     probe_overlap_fill                join_path=direct                                  9       0
     probe_overlap_fill                join_path=regions                                15       6
     probe_overlap_fill                join_path=regions+part=two                       15       5
+    probe_overlap_select              default                                          10       0
+    probe_overlap_select              join_path=direct                                 10       0
+    probe_overlap_select              join_path=regions                                21      10
+    probe_overlap_select              join_path=regions+part=two                       10       0
+    probe_overlap_select_where        default                                           9       0
+    probe_overlap_select_where        join_path=direct                                  9       0
+    probe_overlap_select_where        join_path=regions                                20      10
+    probe_overlap_select_where        join_path=regions+part=two                        9       0
     scatter_fixed                     default                                           5       0
     subtract                          default                                          72      52
     take_bits                         default                                           8       0
@@ -137,11 +165,23 @@ NO_RESERVATION = {
     ("depth_profile_summarize", "device"): "ivx_depth_regions.hip region_aggregates: a profile of at most two tiles makes no aggregates",
     ("depth_profile_windows", "device"): "the same: Env.profile has at most 2 * 1024 steps",
     ("probe_nearest_k1", "device"): "ivx_ops32.hip ivx_nearest_probe: k = 1 takes the direct kernel",
+    ("probe_nearest_dir_k1", "device"): "ivx_ops32.hip nearest_probe_dir_t: k = 1 below 2^21 rows launches k_probe_nearest1_dir on the caller's pointers",
+    ("probe_overlap_select", "device"): "ivx_select.hip ivx_sel_probe: ivx_direct_probe on the caller's pointers, no scratch",
+    ("probe_overlap_select_where", "device"): "the same kernel behind WhereOp (ivx_capi.hip overlap_select_impl)",
+    ("probe_mark_build_where", "device"): "ivx_marks.hip ivx_mark_probe: ivx_direct_probe behind WhereOp, ORs into the caller's bitmap",
+    ("probe_overlap_agg_where", "device"): "ivx_agg.hip ivx_agg_probe: ivx_direct_probe behind WhereOp, no scratch",
+    # (NOT probe_overlap_count_where: its total-only call takes WS_T6 in either mode; NOT pairs_where: WS_T5, WS_T6 and the scan's;
+    #  NOT probe_nearest_dir: k = 2 takes WS_T2..WS_T5)
 }
 # forced paths that end in the direct kernel all the same: the table above applies to them
 DIRECT_ALL_THE_SAME = {
     ("probe_mark_build", "join_path=regions+part=two"): "ivx_regions_probe.hip ivx_mark_probe_regions: *took = false with IVX_PART=two",
     ("probe_overlap_agg", "join_path=regions+part=two"): "ivx_regions_probe.hip ivx_agg_probe_regions: the same",
+    # lean_route is the one gate of every lean launcher: the four below take it with the same arguments
+    ("probe_overlap_select", "join_path=regions+part=two"): "ivx_regions_probe.hip ivx_sel_probe_regions: lean_route gives *took = false",
+    ("probe_overlap_select_where", "join_path=regions+part=two"): "ivx_sel_probe_regions: the same",
+    ("probe_mark_build_where", "join_path=regions+part=two"): "ivx_mark_probe_regions: the same",
+    ("probe_overlap_agg_where", "join_path=regions+part=two"): "ivx_agg_probe_regions: the same",
 }
 # Outputs a refused call legitimately wrote BEFORE the reservation that was refused: (entry, index among the call's outputs)
 # -> where the source does it.  Everything else must still hold the pattern.

@@ -27,7 +27,8 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import depth_oracle as dorc  # noqa: E402
 import depth_per_base_oracle as pbo  # noqa: E402
 import ctypes as C  # noqa: E402
-from entry_cases import CASES, Env, Mode, _same, ivals, pyivx  # noqa: E402
+import nearest_dir_oracle as ndo  # noqa: E402
+from entry_cases import CASES, Env, Mode, _same, assert_nearest_dir, ivals, nearest_dir_calls, nearest_dir_want, pyivx  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -83,7 +84,13 @@ def probe_nearest_k1(E, M, n):
     return {"st": st, "rows": r, "b": b.np()[:r], "p": p.np()[:r], "d": d.np()[:r]}
 
 
-LOCAL_CASES = {"probe_nearest_k1": probe_nearest_k1}
+def probe_nearest_dir_k1(E, M, n):
+    """ivx_probe_nearest_dir with k = 1, the one k that reads IVX_NEAREST_PATH (ivx_ops32.hip: nearest_probe_dir_t; the
+    catalogue's probe_nearest_dir asks for k = 2) -- the catalogue's calls on the catalogue's columns"""
+    return nearest_dir_calls(E, M, n, 1)
+
+
+LOCAL_CASES = {"probe_nearest_k1": probe_nearest_k1, "probe_nearest_dir_k1": probe_nearest_dir_k1}
 
 
 def run_case(E, name, dev, knobs):
@@ -138,6 +145,14 @@ def E():
     e.close()
 
 
+@pytest.fixture(scope="module")
+def near_want(E):
+    """what probe_nearest_dir_k1 and the catalogue's probe_nearest_dir (k = 2) must give on E's build: the restatement of
+    tests/nearest_dir_oracle.py, computed once"""
+    oix = ndo.NearIndex(*E.build_cols)
+    return {"probe_nearest_dir_k1": nearest_dir_want(oix, N, 1), "probe_nearest_dir": nearest_dir_want(oix, N, 2)}
+
+
 class Probe:
     """probe rows as host columns and as device tensors, and the oracle's pairs with `build`"""
 
@@ -189,11 +204,16 @@ ROWVAL_KNOBS = [{"IVX_ROWVAL_PATH": "direct"}, {"IVX_ROWVAL_PATH": "regions"}, {
 NEAREST_KNOBS = [{"IVX_NEAREST_PATH": "direct"}, {"IVX_NEAREST_PATH": "routed"}]
 # the path knobs an entry's layer honours (ivx_capi.hip overlap_common / ivx_probe_mark_build; ivx_ops32.hip); index_build
 # probes the overlap, count and coverage indexes it built, so it takes those two at once.  IVX_NEAREST_PATH is read for
-# k = 1 alone: the catalogue's probe_nearest and index_build ask for k = 2 and run once, probe_nearest_k1 (above) under both
+# k = 1 alone: the catalogue's probe_nearest, probe_nearest_dir and index_build ask for k = 2 and run once, probe_nearest_k1 and
+# probe_nearest_dir_k1 (above) under both.  The select and threshold entries choose their path with region_path_wanted
+# (ivx_capi.hip), which reads IVX_JOIN_PATH; ivx_pairs_where has one path and reads no knob: it runs under the three all the same
 KNOBS = {
     "probe_overlap_count": JOIN_KNOBS, "probe_overlap_fill": JOIN_KNOBS, "probe_exists": JOIN_KNOBS, "probe_mark_build": JOIN_KNOBS,
     "probe_overlap_agg": JOIN_KNOBS, "probe_count": ROWVAL_KNOBS, "probe_coverage": ROWVAL_KNOBS, "probe_nearest_k1": NEAREST_KNOBS,
     "index_build": [{**JOIN_KNOBS[0], **ROWVAL_KNOBS[0]}, {**JOIN_KNOBS[1], **ROWVAL_KNOBS[1]}, {**JOIN_KNOBS[2], **ROWVAL_KNOBS[3]}],
+    "probe_overlap_select": JOIN_KNOBS, "probe_overlap_count_where": JOIN_KNOBS, "probe_mark_build_where": JOIN_KNOBS,
+    "probe_overlap_agg_where": JOIN_KNOBS, "probe_overlap_select_where": JOIN_KNOBS, "pairs_where": JOIN_KNOBS,
+    "probe_nearest_dir_k1": NEAREST_KNOBS,
 }
 S0_RUNS = [(name, knobs) for name in NAMES + sorted(LOCAL_CASES) for knobs in KNOBS.get(name, [{}])]
 
@@ -208,7 +228,7 @@ MODES = [pytest.param(False, id="host"), pytest.param(True, id="device")]
 @pytest.mark.parametrize("value", [0, 1])
 @pytest.mark.parametrize("dev", MODES)
 @pytest.mark.parametrize("name,knobs", S0_RUNS, ids=[f"{n}-{knob_id(k)}" for n, k in S0_RUNS])
-def test_s0_entry_on_poisoned_state(E, base, name, knobs, dev, value):
+def test_s0_entry_on_poisoned_state(E, base, near_want, name, knobs, dev, value):
     want = base(name, dev, knobs)
     E.ctx.synchronize()
     E.ctx.debug_poison(value, ALL_BUT_POOL)
@@ -220,6 +240,8 @@ def test_s0_entry_on_poisoned_state(E, base, name, knobs, dev, value):
         wb, wp, wd = orc.nearest(*E.build_cols, *ivals(N, 11), k=1)
         assert got["st"] == pyivx.OK and got["rows"] == len(wb) == N
         assert (got["b"] == wb).all() and (got["p"] == wp).all() and (got["d"] == wd).all(), knobs
+    if name in near_want:                                       # probe_nearest_dir_k1 on either path, the catalogue's k = 2: the restatement's
+        assert_nearest_dir(got, near_want[name], (name, knobs, dev, value))
 
 
 def test_poison_refuses_a_word_above_one(E):
@@ -259,6 +281,13 @@ JOIN_AFTER = {
     "depth_profile_merge": (D, D), "depth_profile_quantize": (D, D), "depth_profile_hist": (D, D),      # drop_plans()
     "take_fixed": (D, K), "scatter_fixed": (D, K), "take_bits": (D, K),                    # no scratch on the device; host mode stages WS_IN_START / WS_IN_END
     "take_utf8": (D, D), "take_view": (D, D),   # WS_T0 (ivx_take.hip)
+    "probe_overlap_select": (D, D),             # drop_join_plan() (ivx_capi.hip overlap_select_impl)
+    "probe_overlap_count_where": (D, D),        # drop_join_plan() (ivx_probe_overlap_count_where)
+    "probe_mark_build_where": (D, D),           # drop_join_plan() (mark_build_impl)
+    "probe_overlap_agg_where": (D, D),          # drop_join_plan() (overlap_agg_impl)
+    "probe_overlap_select_where": (D, D),       # drop_join_plan() (overlap_select_impl)
+    "pairs_where": (D, D),                      # drop_join_plan() (ivx_pairs_where); WS_T5 / WS_T6 on top (ivx_where.hip)
+    "probe_nearest_dir": (D, K2),               # no drop in the entry; k = 2: WS_T2..WS_T5 (ivx_ops32.hip nearest_probe_dir_t), as probe_nearest
 }
 # ... and of the SUBTRACT plan of a sizing call, at the default paths (1 000 rows take every direct kernel).  The plan's slots
 # (ivx_sweep.hip): WS_T0..WS_T5, WS_T7, WS_T9, WS_RA0..2, WS_RB0..2 -- no staging slot, so host mode drops no more than device mode.
@@ -278,6 +307,11 @@ SUB_AFTER = {
     "depth_profile_merge": (D, D), "depth_profile_quantize": (D, D), "depth_profile_hist": (D, D),
     "take_fixed": (K, K), "scatter_fixed": (K, K), "take_bits": (K, K),
     "take_utf8": (D, D), "take_view": (D, D),
+    # drop_join_plan() only, then the direct kernel on staged or caller's columns (ivx_select.hip, ivx_marks.hip, ivx_agg.hip: no scratch)
+    "probe_overlap_select": (K, K), "probe_mark_build_where": (K, K), "probe_overlap_agg_where": (K, K), "probe_overlap_select_where": (K, K),
+    "probe_overlap_count_where": (K, K),        # the same; its total-only form takes WS_T6, which is no slot of the plan
+    "pairs_where": (D, D),                      # WS_T5 (ivx_where.hip ivx_pairs_where_device: the tile counts)
+    "probe_nearest_dir": (D, D),                # WS_T2..WS_T5
 }
 
 
@@ -354,7 +388,7 @@ def wide(E):
 
 
 @pytest.mark.parametrize("dev", MODES)
-@pytest.mark.parametrize("name", ["bits_mark", "take_fixed", "probe_nearest", "merge", "depth_profile_read"])
+@pytest.mark.parametrize("name", ["bits_mark", "take_fixed", "probe_nearest", "probe_nearest_dir", "merge", "depth_profile_read"])
 def test_s1_join_plan_two_level(E, base, wide, name, dev):
     ix, pr = wide
     join_sequence(E, base, ix, pr, "paged", True, name, dev, int(dev))

@@ -42,7 +42,7 @@ from conftest import ROOT
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import entry_cases as ec  # noqa: E402
 from entry_cases import CASES, NK, OK, SIZES, Delay, Env, LateMode, Mode, _same, cint, pyivx, shaped, u32, u64  # noqa: E402
-from test_gpu_entry_state import designed, inside, probe_nearest_k1  # noqa: E402
+from test_gpu_entry_state import LOCAL_CASES, designed, inside  # noqa: E402
 from test_gpu_region_forms import env  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -244,7 +244,26 @@ N_ROWS = 100_000
 PER_ROW = [("probe_overlap_count", {"IVX_JOIN_PATH": "regions"}), ("probe_exists", {"IVX_JOIN_PATH": "regions"}),
            ("probe_mark_build", {"IVX_JOIN_PATH": "regions"}), ("probe_overlap_agg", {"IVX_JOIN_PATH": "regions"}),
            ("probe_count", {"IVX_ROWVAL_PATH": "regions"}), ("probe_coverage", {"IVX_ROWVAL_PATH": "regions"}),
-           ("probe_nearest_k1", {"IVX_NEAREST_PATH": "routed"})]
+           ("probe_nearest_k1", {"IVX_NEAREST_PATH": "routed"}),
+           ("probe_overlap_select", {"IVX_JOIN_PATH": "regions"}), ("probe_overlap_count_where", {"IVX_JOIN_PATH": "regions"}),
+           ("probe_mark_build_where", {"IVX_JOIN_PATH": "regions"}), ("probe_overlap_agg_where", {"IVX_JOIN_PATH": "regions"}),
+           ("probe_overlap_select_where", {"IVX_JOIN_PATH": "regions"}), ("pairs_where", {"IVX_JOIN_PATH": "regions"}),
+           ("probe_nearest_dir_k1", {"IVX_NEAREST_PATH": "routed"})]
+NULL = pyivx.NULL_IDX
+# name -> the rows (or words) of the host-mode result that say "this row met the build", of which more than half must: a
+# probe that matched nothing would compare zeros with zeros.  spread_probes' rows are 1 .. 100 long and start inside a build row
+# of 256 that reaches at least 192 further: every row lies inside a build row, and passes the cases' threshold (min_bases 10,
+# half of the probe row) unless it is shorter than 10 -- nine rows in ten.  One-sided nearest rows without overlaps find the
+# build row that ends (starts) within 64 coordinates of them when no cap is set.
+MET = {
+    "probe_overlap_count": lambda w: w["per_row"] != 0, "probe_exists": lambda w: w["exists"] != 0, "probe_mark_build": lambda w: w["marks"] != 0,
+    "probe_overlap_agg": lambda w: w["count"] != 0, "probe_count": lambda w: w["out0"] != 0, "probe_coverage": lambda w: w["out0"] != 0,
+    "probe_nearest_k1": lambda w: w["b"] != 0,
+    "probe_overlap_select": lambda w: w["idx.max_val"] != NULL, "probe_overlap_count_where": lambda w: w["per_row"] != 0,
+    "probe_mark_build_where": lambda w: w["marks"] != 0, "probe_overlap_agg_where": lambda w: w["agg.count"] != 0,
+    "probe_overlap_select_where": lambda w: w["idx"] != NULL,
+    "probe_nearest_dir_k1": lambda w: (w["before.ovl0.d-1.b"] != NULL) & (w["after.ovl0.d-1.d"] > 0),
+}
 
 
 def spread_probes(n, seed):
@@ -254,15 +273,26 @@ def spread_probes(n, seed):
 
 @pytest.mark.parametrize("name,knobs", PER_ROW, ids=[n for n, _ in PER_ROW])
 def test_late_per_row_family_routed(W, name, knobs):
-    case = CASES.get(name) or probe_nearest_k1
+    case = CASES.get(name) or LOCAL_CASES[name]
     with env(**knobs), shaped(cols=spread_probes):
         want = W.host(("rows", name), lambda E, M: case(E, M, N_ROWS))
         got, _ = W.late(lambda E, M: case(E, M, N_ROWS))
     assert_equal(got, want, name)
+    assert all(v == OK for k, v in want.items() if k.startswith("st.") or k.endswith(".st")), name
     # the rows met the build: a probe that matched nothing would compare zeros with zeros
-    key = {"probe_overlap_count": "per_row", "probe_exists": "exists", "probe_mark_build": "marks", "probe_overlap_agg": "count",
-           "probe_count": "out0", "probe_coverage": "out0", "probe_nearest_k1": "b"}[name]
-    assert np.count_nonzero(want[key]) > len(want[key]) // 2, name
+    if name == "pairs_where":
+        # pair i is (build row i, probe row i), the probe rows anywhere: next to none of the pairs is a match at all.  What the
+        # filter must return is worked out from the columns (the threshold of entry_cases._where, restated): the passing pairs,
+        # in order -- and there are some, where the decoy's zero columns (pair (0, 0), one base long) give none
+        bs, be = (c[:N_ROWS].astype(np.int64) for c in W.H.build_cols[1:])
+        ps, pe = (c.astype(np.int64) for c in spread_probes(N_ROWS, 29)[1:])
+        length = np.minimum(pe, be) - np.maximum(ps, bs) + 1
+        keep = np.flatnonzero((length >= 10) & (2 * length >= pe - ps + 1)).astype(np.uint32)
+        assert len(keep) > 0 and want["pairs.fill"] == (OK, len(keep)), (len(keep), want["pairs.fill"])
+        assert (want["pairs.fill.0"] == keep).all() and (want["pairs.fill.1"] == keep).all()
+        return
+    met = MET[name](want)
+    assert np.count_nonzero(met) > len(met) // 2, name
 
 
 # ------------------------------------------------------------------ 3c. the sweeps

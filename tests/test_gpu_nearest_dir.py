@@ -24,6 +24,7 @@ NULL = pyivx.NULL_IDX
 I32_MIN, I32_MAX = -2**31, 2**31 - 1
 CAPS = (None, 0, 1, 50, 10**9)
 PATHS = ("direct", "routed")
+DEVICE_SEED = 3         # the table the seed-parametrised tests also run in IVX_MEM_DEVICE: the one with rows of end < start on both sides
 
 
 @pytest.fixture(scope="module")
@@ -76,12 +77,37 @@ def indexes(ctx):
         ix.free()
 
 
-def run(ctx, ix, p, path=None, **kw):
+def dev(a):
+    import torch
+    a = np.ascontiguousarray(a)
+    return torch.from_numpy((a.view(np.int32) if a.dtype == np.uint32 else a).copy()).cuda()
+
+
+_DEV_COLS = {}      # id of a probe table's key column -> (the table, its device tensors): a table goes to the device once
+
+
+def dev_cols(p):
+    if id(p[0]) not in _DEV_COLS:
+        import torch
+        _DEV_COLS[id(p[0])] = (p, tuple(dev(c) for c in p))
+        torch.cuda.synchronize()                # (the context runs on a stream of its own)
+    return _DEV_COLS[id(p[0])][1]
+
+
+def run(ctx, ix, p, path=None, device=False, **kw):
+    """one ivx_probe_nearest_dir call on host columns, or -- device -- on the same columns as device tensors (IVX_MEM_DEVICE),
+    the outputs read back; under IVX_NEAREST_PATH=path if given"""
+    def call():
+        if not device:
+            return ctx.nearest_dir(ix, *p, **kw)
+        b, q, d = ctx.nearest_dir(ix, *dev_cols(p), **kw)
+        ctx.synchronize()
+        return b.cpu().numpy().view(np.uint32), q.cpu().numpy().view(np.uint32), None if d is None else d.cpu().numpy()
     if path is None:
-        return ctx.nearest_dir(ix, *p, **kw)
+        return call()
     os.environ["IVX_NEAREST_PATH"] = path
     try:
-        return ctx.nearest_dir(ix, *p, **kw)
+        return call()
     finally:
         del os.environ["IVX_NEAREST_PATH"]
 
@@ -127,6 +153,10 @@ def test_k1_direct_and_routed(ctx, indexes, seed, direction):
             what = (direction, ovl, strict, D, path)
             same(run(ctx, ix, p, path, overlap=ovl, strict=strict, direction=direction, max_distance=D), exp, what)
             same(run(ctx, ix, p, path, overlap=ovl, strict=strict, direction=direction, max_distance=D, distance=False), exp, what, distance=False)
+            if seed == DEVICE_SEED:             # the same columns as device tensors, against the same `exp`
+                same(run(ctx, ix, p, path, device=True, overlap=ovl, strict=strict, direction=direction, max_distance=D), exp, what + ("device",))
+                same(run(ctx, ix, p, path, device=True, overlap=ovl, strict=strict, direction=direction, max_distance=D, distance=False), exp,
+                     what + ("device",), distance=False)
 
 
 @pytest.mark.parametrize("direction", ndo.DIRECTIONS)
@@ -137,7 +167,13 @@ def test_k_above_one(ctx, indexes, seed, direction):
     for k, ovl, strict, D in itertools.product((2, 5), (True, False), (False, True), CAPS):
         what = (direction, k, ovl, strict, D)
         same(run(ctx, ix, p, k=k, overlap=ovl, strict=strict, direction=direction, max_distance=D), want(seed, k, ovl, strict, direction, D), what)
+        if seed == DEVICE_SEED:
+            same(run(ctx, ix, p, device=True, k=k, overlap=ovl, strict=strict, direction=direction, max_distance=D), want(seed, k, ovl, strict, direction, D),
+                 what + ("device",))
     same(run(ctx, ix, p, k=5, direction=direction, max_distance=50, distance=False), want(seed, 5, True, False, direction, 50), direction, distance=False)
+    if seed == DEVICE_SEED:
+        same(run(ctx, ix, p, device=True, k=5, direction=direction, max_distance=50, distance=False), want(seed, 5, True, False, direction, 50),
+             (direction, "device"), distance=False)
 
 
 @pytest.mark.parametrize("seed", [1, 3])
@@ -167,17 +203,20 @@ def test_aliases(ctx, indexes):
 
 # ---------------------------------------------------------------- edge shapes
 
-def all_forms(ctx, ix, oix, p, what, ks=(1, 3), caps=(None, 50), paths=PATHS):
+def all_forms(ctx, ix, oix, p, what, ks=(1, 3), caps=(None, 50), paths=PATHS, device=False):
+    """device: each call on device tensors as well, beside the host call, against the same restatement"""
     for direction, ovl, strict, D, k in itertools.product(ndo.DIRECTIONS, (True, False), (False, True), caps, ks):
         exp = oix.query(*p, k=k, overlap=ovl, strict=strict, direction=direction, max_distance=D)
         for path in (paths if k == 1 else (None,)):
-            same(run(ctx, ix, p, path, k=k, overlap=ovl, strict=strict, direction=direction, max_distance=D), exp, (what, direction, ovl, strict, D, k, path))
+            for on_device in ((False, True) if device else (False,)):
+                same(run(ctx, ix, p, path, device=on_device, k=k, overlap=ovl, strict=strict, direction=direction, max_distance=D), exp,
+                     (what, direction, ovl, strict, D, k, path, on_device))
 
 
 @pytest.mark.parametrize("n", [1, 63, 64, 65, 257])
 def test_small_batches(ctx, indexes, n):
     _, (pk, ps, pe), _, oix = tables(1)
-    all_forms(ctx, indexes(1), oix, (pk[100:100 + n].copy(), ps[100:100 + n].copy(), pe[100:100 + n].copy()), n)
+    all_forms(ctx, indexes(1), oix, (pk[100:100 + n].copy(), ps[100:100 + n].copy(), pe[100:100 + n].copy()), n, device=True)
 
 
 @pytest.mark.parametrize("per_wave", [64, 32])
@@ -254,35 +293,62 @@ def test_k_beyond_the_rows_on_a_side(ctx):
 
 # ---------------------------------------------------------------- arguments
 
-def raw(ctx, ix, p, n, k, direction, D, ob, op, od, cap, rows, strict=0, ovl=1):
-    ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
-    return pyivx.lib().ivx_probe_nearest_dir(ctx.h, ix.h, pyivx.MEM_HOST, ptr(p[0]), ptr(p[1]), ptr(p[2]), n, strict, k, ovl, direction, D,
-                                             ptr(ob), ptr(op), ptr(od), cap, rows)
+def raw(ctx, ix, p, n, k, direction, D, ob, op, od, cap, rows, strict=0, ovl=1, mem=pyivx.MEM_HOST):
+    return pyivx.lib().ivx_probe_nearest_dir(ctx.h, ix.h, mem, pyivx._ptr(p[0]), pyivx._ptr(p[1]), pyivx._ptr(p[2]), n, strict, k, ovl, direction, D,
+                                             pyivx._ptr(ob), pyivx._ptr(op), pyivx._ptr(od), cap, rows)
 
 
 def test_capacity_and_refusals(ctx, indexes):
+    """the capacity protocol and the refusals at the ABI, on host arrays and -- IVX_MEM_DEVICE -- on device tensors that hold the
+    same pattern before the call and are read back after it"""
+    for mem in ("host", "device"):
+        capacity_and_refusals(ctx, indexes, mem)
+
+
+def capacity_and_refusals(ctx, indexes, mem):
     b, (pk, ps, pe), nk, oix = tables(1)
     ix = indexes(1)
     n = 2000
-    p = (pk[:n].copy(), ps[:n].copy(), pe[:n].copy())
+    hp = (pk[:n].copy(), ps[:n].copy(), pe[:n].copy())
 
-    def fresh(m):
+    def pattern(m):
         return np.full(m, 0xA5A5A5A5, np.uint32), np.full(m, 0xA5A5A5A5, np.uint32), np.full(m, 0x5A5A5A5A5A5A5A5A, np.int64)
 
+    if mem == "host":
+        p, fresh, back, mode = hp, pattern, (lambda *bufs: bufs), pyivx.MEM_HOST
+    else:
+        import torch
+        p, mode = tuple(dev(c) for c in hp), pyivx.MEM_DEVICE
+        torch.cuda.synchronize()                # (the context runs on a stream of its own)
+
+        def fresh(m):
+            bufs = tuple(dev(a) for a in pattern(m))
+            torch.cuda.synchronize()
+            return bufs
+
+        def back(*bufs):
+            ctx.synchronize()
+            return tuple(t.cpu().numpy().view(np.uint32 if t.dtype == torch.int32 else np.int64) for t in bufs)
+
     def untouched(ob, op, od):
+        ob, op, od = back(ob, op, od)
         return (ob == 0xA5A5A5A5).all() and (op == 0xA5A5A5A5).all() and (od == 0x5A5A5A5A5A5A5A5A).all()
 
-    # cap too small: IVX_ERR_CAPACITY with the rows it would take
+    # cap too small: IVX_ERR_CAPACITY with the rows it would take, nothing written; the exact capacity: the answer, and the
+    # pattern behind `rows`
     for k in (1, 3):
-        exp = oix.query(*p, k=k, direction="before", max_distance=1000)
+        exp = oix.query(*hp, k=k, direction="before", max_distance=1000)
         ob, op, od = fresh(n * 3)
         rows = C.c_uint64(7)
-        assert raw(ctx, ix, p, n, k, 1, 1000, ob, op, od, len(exp[0]) - 1, C.byref(rows)) == pyivx.ERR_CAPACITY, k
+        assert raw(ctx, ix, p, n, k, 1, 1000, ob, op, od, len(exp[0]) - 1, C.byref(rows), mem=mode) == pyivx.ERR_CAPACITY, k
         assert rows.value == len(exp[0]), k
+        assert untouched(ob, op, od), k         # (host mode copies nothing back; in device mode no kernel got the caller's buffers)
         rows = C.c_uint64(7)
-        assert raw(ctx, ix, p, n, k, 1, 1000, ob, op, od, len(exp[0]), C.byref(rows)) == pyivx.OK, k
-        assert rows.value == len(exp[0]) and (ob[:rows.value] == exp[0]).all() and (od[:rows.value] == exp[2]).all(), k
-        assert (ob[rows.value:] == 0xA5A5A5A5).all()
+        assert raw(ctx, ix, p, n, k, 1, 1000, ob, op, od, len(exp[0]), C.byref(rows), mem=mode) == pyivx.OK, k
+        gb, gp, gd = back(ob, op, od)
+        assert rows.value == len(exp[0]) and (gb[:rows.value] == exp[0]).all() and (gd[:rows.value] == exp[2]).all(), k
+        assert (gp[:rows.value] == exp[1]).all(), k
+        assert (gb[rows.value:] == 0xA5A5A5A5).all() and (gp[rows.value:] == 0xA5A5A5A5).all() and (gd[rows.value:] == 0x5A5A5A5A5A5A5A5A).all(), k
     # a bad direction, a null column, another index kind: refused, nothing written
     cnt = ctx.build(pyivx.KIND_COUNT, *b, n_keys=nk)
     for status, index, direction, D, null in ((pyivx.ERR_INVALID, ix, 3, -1, None), (pyivx.ERR_INVALID, ix, -1, 10, None),
@@ -292,11 +358,11 @@ def test_capacity_and_refusals(ctx, indexes):
         for k in (1, 3):
             ob, op, od = fresh(n * 3)
             rows = C.c_uint64(7)
-            got = raw(ctx, index, p, n, k, direction, D, None if null == "ob" else ob, None if null == "op" else op, od, n * 3, C.byref(rows))
+            got = raw(ctx, index, p, n, k, direction, D, None if null == "ob" else ob, None if null == "op" else op, od, n * 3, C.byref(rows), mem=mode)
             assert got == status, (status, direction, D, null, k)
             assert untouched(ob, op, od) and rows.value == (0 if status == pyivx.ERR_INVALID else 7), (status, direction, D, null, k)
     ob, op, od = fresh(n * 3)
-    assert raw(ctx, ix, p, n, 1, 1, 10, ob, op, od, n * 3, None) == pyivx.ERR_INVALID and untouched(ob, op, od)
+    assert raw(ctx, ix, p, n, 1, 1, 10, ob, op, od, n * 3, None, mem=mode) == pyivx.ERR_INVALID and untouched(ob, op, od)
     with pytest.raises(pyivx.IvxError) as ei:
         ctx.nearest_dir(cnt, *p, direction="before")
     assert ei.value.status == pyivx.ERR_UNSUPPORTED
@@ -304,4 +370,70 @@ def test_capacity_and_refusals(ctx, indexes):
     # n = 0 is a no-op
     ob, op, od = fresh(8)
     rows = C.c_uint64(7)
-    assert raw(ctx, ix, p, 0, 1, 2, 5, ob, op, od, 8, C.byref(rows)) == pyivx.OK and rows.value == 0 and untouched(ob, op, od)
+    assert raw(ctx, ix, p, 0, 1, 2, 5, ob, op, od, 8, C.byref(rows), mem=mode) == pyivx.OK and rows.value == 0 and untouched(ob, op, od)
+
+
+# ---------------------------------------------------------------- the unforced switch
+
+SWITCH_ROWS = 1 << 21       # ivx_ops32.hip nearest_probe_dir_t: k = 1 takes the routed kernel from this many rows (ivx_nearest_probe's switch)
+SWITCH_CAP = 300            # the cap of the switch test; the table's build rows lie some 300 apart per key
+SWITCH_SAMPLE = 20_000
+
+
+@functools.lru_cache(maxsize=None)
+def switch_table():
+    """2^21 probe rows on the table of DEVICE_SEED (some of them with end < start), a fixed sample of them and what the
+    restatement answers for the sample: direction "before" within SWITCH_CAP, without overlaps -- most of the table's probe rows
+    overlap a build row, and with overlaps k = 1 would never reach the cursor the direction is about"""
+    _, _, nk, oix = tables(DEVICE_SEED)
+    pk, ps, pe = synth(SWITCH_ROWS, 170, nkeys=nk, mean_len=100, span=3_000_000)
+    pe[::13] = ps[::13] - 1 - (np.arange(len(pe[::13])) % 50).astype(np.int32)
+    sample = np.sort(np.random.default_rng(171).choice(SWITCH_ROWS - 1, SWITCH_SAMPLE, replace=False))
+    exp = oix.query(pk[sample], ps[sample], pe[sample], k=1, overlap=False, direction="before", max_distance=SWITCH_CAP)
+    return (pk, ps, pe), sample, exp
+
+
+def test_switch_sample_bites():
+    """on the restatement alone: the sample has rows with a neighbour at distance > 0 within the cap and rows without"""
+    _, sample, (wb, wp, wd) = switch_table()
+    assert len(wb) == SWITCH_SAMPLE and (wp == np.arange(SWITCH_SAMPLE)).all()
+    assert ((wb != NULL) & (wd > 0)).sum() >= SWITCH_SAMPLE // 10 and (wb == NULL).sum() >= SWITCH_SAMPLE // 10
+
+
+def test_unforced_switch_to_the_routed_kernel(ctx, indexes):
+    """IVX_NEAREST_PATH unset, device mode, k = 1, "before" within a cap: one row below 2^21 the call reserves no scratch (the
+    direct kernel on the caller's columns), at 2^21 it does (the route pass); either result equals the forced-direct run bit for
+    bit, and the restatement on a fixed sample of the rows (rows are answered independently)"""
+    import torch
+    assert "IVX_NEAREST_PATH" not in os.environ
+    ix = indexes(DEVICE_SEED)
+    assert ix.forms()["nroute_nreg"] > 0, ix.forms()                         # a routing view: the routed kernel can run
+    p, sample, exp = switch_table()
+    dp = dev_cols(p)
+    kw = dict(k=1, overlap=False, direction="before", max_distance=SWITCH_CAP)
+    for m, routed in ((SWITCH_ROWS - 1, False), (SWITCH_ROWS, True)):
+        q = [c[:m] for c in dp]
+        c = pyivx.Ctx(0)
+        try:
+            c.trim(0)
+            rest = c.reserved_bytes()
+            got = c.nearest_dir(ix, *q, **kw)
+            c.synchronize()
+            assert (c.reserved_bytes() > rest) == routed, (m, rest, c.reserved_bytes())
+            forced = run_forced_direct(ctx, ix, q, kw)
+            assert all(bool(torch.equal(g, f)) for g, f in zip(got, forced)), m
+            gb, gp, gd = (t.cpu().numpy() for t in got)
+            assert len(gb) == m and (gp.view(np.uint32) == np.arange(m)).all()
+            assert (gb.view(np.uint32)[sample] == exp[0]).all() and (gd[sample] == exp[2]).all(), m
+        finally:
+            c.close()
+
+
+def run_forced_direct(ctx, ix, q, kw):
+    os.environ["IVX_NEAREST_PATH"] = "direct"
+    try:
+        out = ctx.nearest_dir(ix, *q, **kw)
+        ctx.synchronize()
+        return out
+    finally:
+        del os.environ["IVX_NEAREST_PATH"]

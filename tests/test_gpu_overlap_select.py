@@ -511,16 +511,11 @@ def test_select_between_count_and_fill(ctx):
 # ---------------------------------------------------------------- G9: the catalogue's walks, as a local case
 
 def probe_overlap_select(E, M, n):
-    """both outputs, three criteria: an int64 value per build row, the overlap length, the last row -- the catalogue's
-    columns (entry_cases.ivals), through the entry itself"""
-    k, s, e = (M.put(a) for a in ivals(n, 29, span=4000))
-    val = M.put(np.random.default_rng(30).integers(-5, 6, E.n_build).astype(np.int64))
-    res = {}
-    for by in ("max_val", "min_overlap", "last_row"):
-        bi, sc = M.out(n, np.uint32), M.out(n, np.int64)
-        res["st." + by] = E.call("ivx_probe_overlap_select", E.ix[0].h, M.mem, k.p, s.p, e.p, u64(n), val.p, u32(8), cint(BY.index(by)),
-                                 bi.p, sc.p, outs=[bi, sc])
-        res["idx." + by], res["score." + by] = bi.np()[:n], sc.np()[:n]
+    """the catalogue's case (entry_cases.py): both outputs, three criteria -- an int64 value per build row, the overlap length,
+    the last row -- on the catalogue's columns, through the entry itself"""
+    from entry_cases import CASES, SEL_CASE_BY
+    res = CASES["probe_overlap_select"](E, M, n)
+    assert sorted(res) == sorted(f"{what}.{by}" for what in ("st", "idx", "score") for by in SEL_CASE_BY) and SEL_CASE_BY == ("max_val", "min_overlap", "last_row")
     return res
 
 

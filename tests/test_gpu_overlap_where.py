@@ -663,39 +663,24 @@ def test_where_count_drops_the_join_plan(ctx, lean):
 
 # ---------------------------------------------------------------- the catalogue's walks, as a local case
 
+WHERE_CASES = ("probe_overlap_count_where", "probe_mark_build_where", "probe_overlap_agg_where", "probe_overlap_select_where",
+               "pairs_where")
+
+
 def probe_where(E, M, n):
-    """all five entries under probe 1/2 and min_bases 10 -- the catalogue's columns (entry_cases.ivals), through the entries
-    themselves"""
-    k, s, e = (M.put(a) for a in ivals(n, 29, span=4000))
-    val = M.put(np.random.default_rng(30).integers(-5, 6, E.n_build).astype(np.int64))
-    w = pyivx.OverlapWhereC(10, 1, 2, 0, 0, 0)
-    head = (E.ix[0].h, M.mem, k.p, s.p, e.p, u64(n))
+    """all five entries under probe 1/2 and min_bases 10: the catalogue's five cases (entry_cases.py) one after the other on
+    one context, their results in one dict (the cases name their results apart)"""
+    from entry_cases import CASES
     res = {}
-    pr, ex, tot = M.out(n, np.uint32), M.out(n, np.uint8), u64(0xDEAD)
-    res["st.count"] = E.call("ivx_probe_overlap_count_where", *head, C.byref(w), pr.p, ex.p, C.byref(tot), outs=[pr, ex], count=tot)
-    res["per_row"], res["exists"], res["total"] = pr.np()[:n], ex.np()[:n], tot.value
-    tot2 = u64(0xDEAD)
-    res["st.total"] = E.call("ivx_probe_overlap_count_where", *head, C.byref(w), None, None, C.byref(tot2), count=tot2)
-    res["total2"] = tot2.value
-    nw = (E.n_build + 31) // 32
-    mine = np.zeros(nw, np.uint32)
-    mine[::3] = 0x00010001
-    marks = M.put(mine)
-    res["st.marks"] = E.call("ivx_probe_mark_build_where", *head, C.byref(w), marks.p, outs=[(marks, mine)])
-    res["marks"] = marks.np()
-    outs = [M.out(n, dt) for dt in (np.uint32,) + (np.int64,) * 5]
-    res["st.agg"] = E.call("ivx_probe_overlap_agg_where", *head, val.p, u32(8), C.byref(w), *[o.p for o in outs], outs=outs)
-    res.update({"agg." + name: o.np()[:n] for name, o in zip(pyivx.AGG_OUTPUTS, outs)})
-    bi, sc = M.out(n, np.uint32), M.out(n, np.int64)
-    res["st.select"] = E.call("ivx_probe_overlap_select_where", *head, val.p, u32(8), cint(2), C.byref(w), bi.p, sc.p, outs=[bi, sc])
-    res["idx"], res["score"] = bi.np()[:n], sc.np()[:n]
-    # the pair filter over n pairs of (row i of the build's first n rows, probe row i)
-    bsd, bed = M.put(E.build_cols[1][:max(n, 1)]), M.put(E.build_cols[2][:max(n, 1)])
-    ids = M.put(np.arange(n, dtype=np.uint32))
-    ob, op, m = M.out(n, np.uint32), M.out(n, np.uint32), u64(0xDEAD)
-    res["st.pairs"] = E.call("ivx_pairs_where", M.mem, ids.p, ids.p, u64(n), bsd.p, bed.p, u64(n), s.p, e.p, u64(n), C.byref(w),
-                             ob.p if n else None, op.p if n else None, u64(n), C.byref(m), outs=[ob, op], count=m)
-    res["n_out"], res["ob"], res["op"] = m.value, ob.np()[:m.value], op.np()[:m.value]
+    for name in WHERE_CASES:
+        one = CASES[name](E, M, n)
+        assert not set(one) & set(res), name
+        res.update(one)
+    # the pair filter is the catalogue's sizing / fill / one-short triple (entry_cases.sized: the fill is IVX_OK with the sizing
+    # call's count, one short is IVX_ERR_CAPACITY): the sizing call's status, and what the fill wrote, under the names used below
+    res["st.pairs"], res["n_out"] = res["pairs.sizing"]
+    assert res["pairs.fill"] == (OK, res["n_out"]) and res.get("pairs.short", (CAPACITY, res["n_out"])) == (CAPACITY, res["n_out"]), n
+    res["ob"], res["op"] = res["pairs.fill.0"], res["pairs.fill.1"]
     return res
 
 

@@ -44,6 +44,35 @@ def test_any_without_a_cap_is_the_reference(degenerate):
     assert (gb == NULL).all() and (gp == np.arange(len(p[0]))).all() and (gd == -1).all()
 
 
+@pytest.mark.parametrize("build", ["default", "designed"])
+def test_the_catalogue_case_bites(build):
+    """the precondition of the catalogue's probe_nearest_dir cases (tests/entry_cases.py), on the restatement alone: on both
+    builds the walks use, every one-sided call without overlaps and within the cap answers at least 100 of the 1 000 rows with
+    a neighbour at distance > 0 and leaves at least 100 NULL -- a kernel that ignored the direction, the cap or
+    include_overlaps would change rows of either kind.  (On the designed build every row overlaps a build row: with
+    include_overlaps the cursors are never reached there.)"""
+    import entry_cases as ec
+    from test_gpu_entry_state import designed         # (importing the walk's module needs no GPU)
+    assert ec.ivals(1000, 3)[0].dtype == np.uint32 and ec.SHAPE["cols"] is None
+    b = ec.ivals(1000, 1) if build == "default" else designed()
+    oix = ndo.NearIndex(*b)
+    one_sided = [(d, ovl, D) for d, ovl, D in ec.NEAR_DIR_CALLS if d != "any" and not ovl and D >= 0]
+    assert sorted(d for d, _, _ in one_sided) == ["after", "before"] and all(D == 32 for _, _, D in one_sided)
+    for k in (1, 2):
+        want = ec.nearest_dir_want(oix, 1000, k)
+        assert sorted(want) == sorted(ec.near_dir_tag(*c) for c in ec.NEAR_DIR_CALLS)
+        for call in one_sided:
+            wb, wp, wd = want[ec.near_dir_tag(*call)]
+            found = np.unique(wp[(wb != NULL) & (wd > 0)])
+            nulls = wp[wb == NULL]
+            assert len(found) >= 100 and len(nulls) >= 100, (build, k, call, len(found), len(nulls))
+            assert (wd[wb != NULL] <= 32).all() and (wd[wb != NULL] > 0).all(), (build, k, call)
+        # ... and the two sides, the cap and include_overlaps each change the answer
+        t = ec.near_dir_tag
+        for a, c in ((t("before", 0, 32), t("after", 0, 32)), (t("before", 0, 32), t("before", 0, -1)), (t("after", 0, -1), t("after", 1, -1))):
+            assert len(want[a][0]) != len(want[c][0]) or (want[a][0] != want[c][0]).any(), (build, k, a, c)
+
+
 def _as_lists(n, res):
     out = {i: [] for i in range(n)}
     for b, p, d in zip(*res):
